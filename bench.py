@@ -14,14 +14,23 @@ Inputs are resident in HBM before the timed region.  Residuals per step = E_phot
 
 Multi-GPU: factor-graph links are sharded over ranks (rank r owns the contiguous range [r*2n/world, (r+1)*2n/world) of the directed edges),
 keyframes replicated; a reduced window runs the one-collective LM sequence (linearize at the candidate: ONE all-reduce of
-the packed normal equations per step, the error totals in its tail; strong scaling).  Single-GPU runs also measure one rank
-of an 8-rank job on this device (`shard_emulation`: one-rank RCCL communicator, the peers' share from a table).
+the packed normal equations per step, the error totals in its tail; strong scaling).  Single-GPU runs with `--full` also
+measure one rank of an 8-rank job on this device (`shard_emulation`: one-rank RCCL communicator, the peers' share from a table).
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets the window up, warms up, times the N steps and prints the
+headline figures (`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything else the benchmark measures takes runs of its
+own and is reported with `--full` only: the per-kernel launch times and both roofs, the phase split of a step, the emulated
+rank of an 8-rank job, the other LM sequence, the host placement and the CPU-port baseline (`--mode edge`: the other
+operator calls, CS 16, shuffled samples, the tracker frames and the CPU port).  `--dump-outputs DIR` writes what the timed
+path computed in its last step as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds of the engine
+can be compared output for output.
 """
 from __future__ import annotations
 
 import argparse
+import gc
 import json
 import os
 import sys
@@ -109,6 +118,28 @@ def issue_roofline(pmc, ms):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write `arrays` (name -> array) as out_dir/<name>.npy in float32 or float64, at most DUMP_LIMIT_BYTES in all: an
+    array that does not fit what is left is replaced by a fixed, seeded sample of its elements, written next to the
+    indices it took (<name>_sample_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > left:
+            n_keep = max(0, (left // 2) // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=n_keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+            left -= 8 * idx.size
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def cpu_baseline(win, budget_s: float = 20.0):
     """Reference-style CPU path (oracle/, kind = "port": materialise J per residual, then reduce) timed on a bounded
     sample of the same workload: both directed edges of a few links, linearize + error evaluation.  The OpenMP thread
@@ -164,27 +195,32 @@ def cpu_baseline(win, budget_s: float = 20.0):
                 lm_iters_per_sec=(1.0 / (t_used / n_edges * 2 * len(w.links))))
 
 
-def edge_mode(capi, synth, torch):
+def edge_mode(capi, synth, torch, steps, warmup, full=False, dump_dir=None):
     """Latency of the drop-in path: what ISAM2 / the tracker call one factor at a time -- reference
     defaults N = 3072 samples of a 64x80x16 keyframe, CS 16 and 32, samples in the reference's shuffled order
     (mapper.cpp:1326-1340) and raster-sorted (sage_sort_locations) -- and one full BASELINE config-1 tracker frame
     (<= 40 LM iterations, TrackNewFrame = photometric + reprojection, TrackFrame = photometric + match geometry with
     scale).  Every call ends with the host reading `error` (stream synchronise), like the reference's .item<float>().
-    The CPU port (oracle) runs the same calls on the host cores beside it."""
+    The CPU port (oracle) runs the same calls on the host cores beside it.  The headline call (photometric linearize, CS 32,
+    raster-sorted) is timed over `steps` calls after `warmup`; everything else runs with `full` only."""
     import ctypes as C
-    from oracle import oracle as orc
-    from tests.helpers import presample_source
-    orc.build()
-    cpu_threads = min(16, os.cpu_count() or 1)   # the port's reduction stage stops scaling there (see cpu_baseline)
-    orc.set_threads(cpu_threads)
     L = capi.lib()
     H, W, FS, NS, REP = 64, 80, 16, 3072, 200
     ws = capi.Workspace()
-    res = {"cpu_port_threads": cpu_threads}
+    res = {}
+    if full:
+        from oracle import oracle as orc
+        orc.build()
+        cpu_threads = min(16, os.cpu_count() or 1)   # the port's reduction stage stops scaling there (see cpu_baseline)
+        orc.set_threads(cpu_threads)
+        res["cpu_port_threads"] = cpu_threads
     f = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    headline = (32, "sorted", "photometric_jac_error")
+    key = "photometric_jac_error_CS32_sorted_us"
+    dumped = {}
 
-    def timeit(fn, rep=REP):
-        for _ in range(10):
+    def timeit(fn, rep=REP, n_warm=10):
+        for _ in range(n_warm):
             fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -193,10 +229,11 @@ def edge_mode(capi, synth, torch):
         torch.cuda.synchronize()
         return 1e6 * (time.perf_counter() - t0) / rep
 
-    # ctypes overhead of a call of this arity (NULL workspace -> SAGE_E_INVALID before anything runs)
-    noop = lambda: L.sage_photometric_jac_error_calculate(None, *([None] * 19), C.c_float(1), None, C.c_float(0), None, 0, 16, 32)
-    res["ctypes_noop_us"] = timeit(noop, 2000)
-    for CS in (16, 32):
+    if full:
+        # ctypes overhead of a call of this arity (NULL workspace -> SAGE_E_INVALID before anything runs)
+        noop = lambda: L.sage_photometric_jac_error_calculate(None, *([None] * 19), C.c_float(1), None, C.c_float(0), None, 0, 16, 32)
+        res["ctypes_noop_us"] = timeit(noop, 2000)
+    for CS in ((16, 32) if full else (32,)):
         w = synth.make_window(K=2, H=H, W=W, FS=FS, CS=CS, L=4, n_samples=NS, seed=0)
         a, b = w.keyframes
         pyr = capi.make_pyramid(w.cams[0], w.L)
@@ -209,7 +246,7 @@ def edge_mode(capi, synth, torch):
         dpt1, dgrad1 = capi.depth_and_grad(ws, kb.bias, kb.basis, b.code, b.scale, H, W, CS)
         wts = np.ascontiguousarray(w.photo_weights, np.float32)
         wp = wts.ctypes.data_as(C.POINTER(C.c_float))
-        for order in ("shuffled", "sorted"):
+        for order in (("shuffled", "sorted") if full else ("sorted",)):
             ka = capi.DeviceKeyframe(a, H, W)
             if order == "sorted":
                 lo, ho, ok = capi.sort_locations(ws, ka.loc1d, ka.homo, H, W)
@@ -239,8 +276,18 @@ def edge_mode(capi, synth, torch):
                     C.c_float(w.geo_loss_param), C.c_float(w.geo_weight), ka.N, CS),
             }
             for name, fn in calls.items():
-                assert fn() == 0, name
-                res[f"{name}_CS{CS}_{order}_us"] = timeit(fn)
+                if (CS, order, name) == headline:
+                    assert fn() == 0, name
+                    res[key] = timeit(fn, steps, warmup)
+                    torch.cuda.synchronize()
+                    Dp = 13 + CS
+                    dumped = {"AtA": AtA[:Dp * Dp].reshape(Dp, Dp).cpu().numpy(), "Atb": Atb[:Dp].cpu().numpy(),
+                              "error": np.array([err.value], np.float32), "num_inliers": np.array([nin.value], np.float32)}
+                elif full:
+                    assert fn() == 0, name
+                    res[f"{name}_CS{CS}_{order}_us"] = timeit(fn)
+        if not full:
+            continue
         # the same four calls through the CPU port (default OpenMP threads), CS as above, once per CS
         t = {}
         for name, fn in {
@@ -252,32 +299,34 @@ def edge_mode(capi, synth, torch):
             for _ in range(5):
                 fn()
             res[f"cpu_port_{name}_CS{CS}_us"] = 1e6 * (time.perf_counter() - t0) / 5
-    # ---- one tracker frame (config 1: CS 32) ----
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from tests.test_gpu_tracker import Scene
-    sc = Scene(capi, orc)
-    cfg = capi.lm_config_default()
-    for name, dof, up, uk in (("TrackNewFrame_photo+reproj", 6, True, True), ("TrackNewFrame_photo", 6, True, False),
-                              ("TrackFrame_photo+matchgeom", 7, True, True)):
-        prob = sc.problem(dof, up, uk)
-        s0 = float(sc.s_true) * (0.96 if dof == 7 else 1.0)
-        rc, _, _, _, iters, tr = capi.track_frame(cfg, dof, prob, sc.start_pose(), s0)
-        assert rc == 0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(20):
-            capi.track_frame(cfg, dof, prob, sc.start_pose(), s0)
-        ms = 1e3 * (time.perf_counter() - t0) / 20
-        lin, errf = sc.oracle_callbacks(dof, up, uk)
-        t0 = time.perf_counter()
-        capi.track_lm(cfg, dof, lin, errf, sc.start_pose(), s0)
-        cpu_ms = 1e3 * (time.perf_counter() - t0)
-        res[name] = dict(ms_per_frame=ms, lm_iterations=iters, candidate_evaluations=len(tr), cpu_port_ms_per_frame=cpu_ms)
-    sc.close()
+    if full:
+        # ---- one tracker frame (config 1: CS 32) ----
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from tests.test_gpu_tracker import Scene
+        sc = Scene(capi, orc)
+        cfg = capi.lm_config_default()
+        for name, dof, up, uk in (("TrackNewFrame_photo+reproj", 6, True, True), ("TrackNewFrame_photo", 6, True, False),
+                                  ("TrackFrame_photo+matchgeom", 7, True, True)):
+            prob = sc.problem(dof, up, uk)
+            s0 = float(sc.s_true) * (0.96 if dof == 7 else 1.0)
+            rc, _, _, _, iters, tr = capi.track_frame(cfg, dof, prob, sc.start_pose(), s0)
+            assert rc == 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                capi.track_frame(cfg, dof, prob, sc.start_pose(), s0)
+            ms = 1e3 * (time.perf_counter() - t0) / 20
+            lin, errf = sc.oracle_callbacks(dof, up, uk)
+            t0 = time.perf_counter()
+            capi.track_lm(cfg, dof, lin, errf, sc.start_pose(), s0)
+            cpu_ms = 1e3 * (time.perf_counter() - t0)
+            res[name] = dict(ms_per_frame=ms, lm_iterations=iters, candidate_evaluations=len(tr), cpu_port_ms_per_frame=cpu_ms)
+        sc.close()
     ws.close()
-    key = "photometric_jac_error_CS32_sorted_us"
+    if dump_dir:
+        dump_outputs(dump_dir, dumped)
     return {"metric": "us per drop-in operator call (photometric linearize, N=3072, 64x80x16, CS 32, raster-sorted samples)",
-            "value": res[key], "unit": "us/call", "n_gpus": 1, "steps": REP, "warmup": 10, "ms_per_step": res[key] / 1e3,
+            "value": res[key], "unit": "us/call", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": res[key] / 1e3,
             "higher_is_better": False, "scaling": "n/a", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "BASELINE config 1: 2-keyframe tracker BA / per-edge operator API at the reference defaults "
                                    "(64x80x16 feature maps, N = 3072 samples, CS 16 and 32)"},
@@ -423,7 +472,16 @@ def main():
                          "line: one-rank RCCL communicator, the peers' share from a table); 'off' skips it")
     ap.add_argument("--mode", choices=["window", "edge"], default="window",
                     help="edge: latency of the drop-in per-edge operator API and of a full tracker frame (config 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (per-kernel times and roofs, phase split, "
+                         "emulated shard, the other LM sequence, host placement, CPU-port baseline; edge mode: the other "
+                         "calls, the tracker frames and the CPU port)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    full = args.full
     loops = []
     synth_kw = {}
     if args.config == 1:
@@ -518,7 +576,7 @@ def main():
         capi.bind_thread_to_device(dev_index)
     if args.mode == "edge":
         os.sched_setaffinity(0, full_affinity)     # (no host solve in this mode; its CPU leg wants its 16 threads on 16 cores)
-        out = edge_mode(capi, synth, torch)
+        out = edge_mode(capi, synth, torch, args.steps, args.warmup, full=full, dump_dir=args.dump_outputs)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
         return
     win_h = synth.make_window(K=args.keyframes, H=args.height, W=args.width, FS=args.fs, CS=args.cs, L=4, seed=0,
@@ -645,48 +703,66 @@ def main():
                     state.iters = 0
                 hist.append(lm_step())
 
-    # instrumented pass FIRST (every hot kernel + the phase marks: eleven event records per step, 30-50 us of the
-    # stream's time): the other kernels' durations and phase_ms come from it.  It also brings the GPU / host clocks up:
-    # the step time of this loop settles only after ~25 steps (profiles/r04_step_series.txt: 2.2, 1.9, 1.88, 1.84 ...
-    # 1.78 ms), more than --warmup 5 covers.
-    win.set_profiling(1)
-    n_instr = int(os.environ.get("SAGE_BENCH_INSTR_STEPS", min(max(args.steps, 1), 9 * RESTART)))   # (dev knob)
+    # pre-timed pass FIRST: it brings the GPU / host clocks up -- the step time of this loop settles only after ~25 steps
+    # (profiles/r04_step_series.txt: 2.2, 1.9, 1.88, 1.84 ... 1.78 ms), more than --warmup 5 covers.  With --full it is
+    # the instrumented pass (every hot kernel + the phase marks: eleven event records per step, 30-50 us of the stream's
+    # time): the other kernels' durations and phase_ms come from it.
+    win.set_profiling(1 if full else 0)
+    n_instr = int(os.environ.get("SAGE_BENCH_INSTR_STEPS", 9 * RESTART))   # (dev knob; the clocks settle whatever --steps is)
     run_steps(RESTART)
-    for which in range(4):
-        win.kernel_time(which)
-    win.phase_time()
+    if full:
+        for which in range(4):
+            win.kernel_time(which)
+        win.phase_time()
     barrier()
     t1 = time.perf_counter()
     run_steps(n_instr)
     barrier()
     ms_instr = 1e3 * (time.perf_counter() - t1) / max(1, n_instr)
-    ktime_full = [win.kernel_time(which) for which in range(4)]
-    phase, phase_n = win.phase_time()
+    if full:
+        ktime_full = [win.kernel_time(which) for which in range(4)]
+        phase, phase_n = win.phase_time()
     del hist[:]
-    # W warm-up steps, then the timed region: HIP events around the dominant kernel only (the roofline's live launch
-    # duration: two event records per step)
-    win.set_profiling(2)
+    # W warm-up steps, then the timed region.  --full: HIP events around the dominant kernel only (the roofline's live
+    # launch duration: two event records per step)
+    win.set_profiling(2 if full else 0)
     win.reset()
     damp = float(cfg.init_damp)
     state.iters = 0
     state.damp = damp
+    gc.disable()                     # (no collector pause inside the warm-up and the timed steps)
     for i in range(args.warmup):
         hist.append(lm_step())
-    for which in range(4):
-        win.kernel_time(which)
+    if full:
+        for which in range(4):
+            win.kernel_time(which)
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    gc.enable()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    ktime = [win.kernel_time(0)] + ktime_full[1:]
-    win.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the LM loop holds after the last timed step: its trace row, the window's variables, the step the
+        # solver took and the (reduced) normal equations it solved
+        last = hist[-1]
+        K = len(win_h.keyframes)
+        kf = [win.get_keyframe(k) for k in range(K)]
+        dump_outputs(args.dump_outputs, {
+            "lm_last_step": np.array([last[0], last[1], float(last[2]), damp], np.float64),
+            "poses": np.stack([p for p, _, _ in kf]), "codes": np.stack([c for _, c, _ in kf]),
+            "scales": np.array([sc for _, _, sc in kf], np.float32),
+            "delta": win.delta(),
+            "normal_equations": packed.cpu().numpy()})
     per_rank_ms = None
-    if dist is not None:
+    if full:
+        ktime = [win.kernel_time(0)] + ktime_full[1:]
+    win.set_profiling(False)
+    if dist is not None and full:
         # average launch duration of the three hot kernels on every rank (HIP events on the window's stream)
         mine = torch.tensor([ktime[i][0] / max(1, ktime[i][1]) for i in range(3)] + [1e3 * (time.perf_counter() - t0)],
                             dtype=torch.float64, device="cpu" if one_dev else "cuda")
@@ -713,26 +789,7 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        # dominant kernel: the fused photometric linearize; algorithmic bytes of ONE launch on this rank
-        # (windows that take the domain-decomposed solve shard by whole links, the others by directed edge)
-        schur = world > 1 and (os.environ.get("SAGE_SHARD_SCHUR", "1" if args.keyframes >= 256 else "0") not in ("0", ""))
-        px_launch = (2 * len(capi.shard_links(len(win_h.links), rank, world)) if schur else
-                     len(capi.shard_edges(len(win_h.links), rank, world))) * N
-        ms_photo = ktime[0][0] / max(1, ktime[0][1])
-        ms_geo = ktime[1][0] / max(1, ktime[1][1])
-        ach = px_launch * bytes_photo_px / (ms_photo * 1e-3) / 1e9 if ms_photo > 0 else 0.0
-        ach_geo = px_launch * bytes_geo_px / (ms_geo * 1e-3) / 1e9 if ms_geo > 0 else 0.0
-        headline = world == 1 and args.keyframes == 64 and args.height == 128 and args.fs == 16 and args.cs == 32
-        pmc_ok = headline and pmc_constants_current()
         n_acc = int(sum(1 for h in hist[args.warmup:] if h[2]))
-        # phases of an iteration on rank 0's stream timeline (HIP events); "host_idle" = the rest of the step: accept /
-        # reject decision, the error totals' all-reduce, launch gaps
-        phase_ms = None
-        if phase_n > 0:
-            phase_ms = {k: v / phase_n for k, v in phase.items()}
-            phase_ms["host_idle"] = max(0.0, ms_instr - sum(phase_ms.values()))
-            phase_ms["iterations_sampled"] = phase_n
-            phase_ms["ms_per_step_instrumented"] = ms_instr  # the pass the marks were taken in (BEFORE the warm-up and the timed region)
         out = {
             "metric": f"M residuals/sec (+ LM iters/sec), {args.keyframes}-keyframe feature-metric BA @{args.height}x{args.width}",
             "value": residuals_per_step * args.steps / elapsed / 1e6,
@@ -740,7 +797,7 @@ def main():
             "lm_iters_per_sec": args.steps / elapsed,
             "accepted_iters_per_sec": n_acc / elapsed,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # untimed steps this process ran before the W warm-up steps (instrumented pass: kernel events + phase marks)
+            # untimed steps this process ran before the W warm-up steps (the pre-timed pass; --full: kernel events + phase marks)
             "pre_timed_steps": RESTART + n_instr,
             "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -759,90 +816,110 @@ def main():
                               "system from one pass); no separate error pass; +1 linearize after every restart"),
                        "accepted_steps": n_acc,
                        "error_first_last": [hist[0][0], hist[-1][1]]},
-            "roofline": {"bound": "hbm",
-                         # r06: BOTH roofs in the parsed line.  hbm_algorithmic = SURVEY s8(d)'s bytes over the
-                         # launch time (the contract's `frac`); issue_serialised = (VALU + MFMA issue time per SIMD + LDS-array
-                         # time per CU) / launch time at the MEASURED engine clock -- ~1 means the three pipes run one after the
-                         # other, which is what binds this kernel (profiles/r06_photo_wave_timeline.txt), not HBM
-                         "roofs": roofs(PMC_K64["photo"], ms_photo, ach) if pmc_ok else
-                                  {"hbm_algorithmic": {"achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS}},
-                         "kernel": "photo_kernel<CS,FS,true,2> (fused photometric linearize of the LM iteration; since r05 it also "
-                                   "contracts the geometric edge's code0 blocks of the same pair -- the merged linearize)",
-                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "bound_note": "the HBM figure is SURVEY s8(d)'s algorithmic-byte roofline of the PHOTOMETRIC factor alone "
-                                       "(492 B per source pixel at FS 16 / CS 32) over this kernel's launch time, although the kernel "
-                                       "now does a third of the geometric factor's contractions as well; `linearize_pair` prices "
-                                       "both factor types' algorithmic bytes against both kernels' time.  What binds the kernel is "
-                                       "VALU + MFMA issue and the LDS pipe (see issue), not HBM",
-                         # both linearize kernels of a step as one unit: (B_photo + B_geo) per source pixel over t_photo + t_geo
-                         # (r04, separate kernels: 4.70 GB / (0.639 + 0.494 ms) = 4.15 TB/s = 0.519)
-                         "linearize_pair": {"achieved": px_launch * (bytes_photo_px + bytes_geo_px) / ((ms_photo + ms_geo) * 1e-3) / 1e9
-                                            if ms_photo + ms_geo > 0 else 0.0,
-                                            "frac": px_launch * (bytes_photo_px + bytes_geo_px) / ((ms_photo + ms_geo) * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                            if ms_photo + ms_geo > 0 else 0.0,
-                                            "bytes_per_launch_pair": px_launch * (bytes_photo_px + bytes_geo_px),
-                                            "ms": ms_photo + ms_geo},
-                         "traffic": PMC_TRAFFIC_BYTES_K64["hbm_bytes_per_launch"] if pmc_ok else None,
-                         "traffic_source": ("rocprofv3 --pmc FETCH_SIZE(x2 gfx950 correction)+WRITE_SIZE, " + PMC_K64["source"]
-                                            if pmc_ok else "none: " + ("the kernel sources no longer hash to the committed counter "
-                                            "summary's build (" + PMC_K64["source"] + ")" if headline else "counters are committed "
-                                            "for the headline workload only")),
-                         "issue": issue_roofline(PMC_K64["photo"], ms_photo) if pmc_ok else None,
-                         "bytes_per_launch": px_launch * bytes_photo_px, "avg_launch_ms": ms_photo,
-                         "geo_kernel": {"achieved": ach_geo, "frac": ach_geo / HBM_PEAK_GBS, "avg_launch_ms": ms_geo,
-                                        "bytes_per_launch": px_launch * bytes_geo_px,
-                                        "issue": issue_roofline(PMC_K64["geo"], ms_geo) if pmc_ok else None},
-                         # (the window's error pass evaluates both factor types in the photometric error kernel: no
-                         #  separate geometric launch)
-                         "error_pass_ms": {"photo+geo" if ktime[3][1] == 0 else "photo": ktime[2][0] / max(1, ktime[2][1]),
-                                           **({"geo": ktime[3][0] / ktime[3][1]} if ktime[3][1] else {})}},
         }
-        if phase_ms:
-            out["phase_ms"] = phase_ms
-        if world == 1 and args.emulate_shard != "off" and len(win_h.links) >= 8:
-            er, ew = (int(v) for v in args.emulate_shard.split("/"))
+        if full:
+            # dominant kernel: the fused photometric linearize; algorithmic bytes of ONE launch on this rank
+            # (windows that take the domain-decomposed solve shard by whole links, the others by directed edge)
+            schur = world > 1 and (os.environ.get("SAGE_SHARD_SCHUR", "1" if args.keyframes >= 256 else "0") not in ("0", ""))
+            px_launch = (2 * len(capi.shard_links(len(win_h.links), rank, world)) if schur else
+                         len(capi.shard_edges(len(win_h.links), rank, world))) * N
+            ms_photo = ktime[0][0] / max(1, ktime[0][1])
+            ms_geo = ktime[1][0] / max(1, ktime[1][1])
+            ach = px_launch * bytes_photo_px / (ms_photo * 1e-3) / 1e9 if ms_photo > 0 else 0.0
+            ach_geo = px_launch * bytes_geo_px / (ms_geo * 1e-3) / 1e9 if ms_geo > 0 else 0.0
+            headline = world == 1 and args.keyframes == 64 and args.height == 128 and args.fs == 16 and args.cs == 32
+            pmc_ok = headline and pmc_constants_current()
+            # phases of an iteration on rank 0's stream timeline (HIP events); "host_idle" = the rest of the step: accept /
+            # reject decision, the error totals' all-reduce, launch gaps
+            phase_ms = None
+            if phase_n > 0:
+                phase_ms = {k: v / phase_n for k, v in phase.items()}
+                phase_ms["host_idle"] = max(0.0, ms_instr - sum(phase_ms.values()))
+                phase_ms["iterations_sampled"] = phase_n
+                phase_ms["ms_per_step_instrumented"] = ms_instr  # the pass the marks were taken in (BEFORE the warm-up and the timed region)
+            out["roofline"] = {"bound": "hbm",
+                               # r06: BOTH roofs in the parsed line.  hbm_algorithmic = SURVEY s8(d)'s bytes over the
+                               # launch time (the contract's `frac`); issue_serialised = (VALU + MFMA issue time per SIMD + LDS-array
+                               # time per CU) / launch time at the MEASURED engine clock -- ~1 means the three pipes run one after the
+                               # other, which is what binds this kernel (profiles/r06_photo_wave_timeline.txt), not HBM
+                               "roofs": roofs(PMC_K64["photo"], ms_photo, ach) if pmc_ok else
+                                        {"hbm_algorithmic": {"achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS}},
+                               "kernel": "photo_kernel<CS,FS,true,2> (fused photometric linearize of the LM iteration; since r05 it also "
+                                         "contracts the geometric edge's code0 blocks of the same pair -- the merged linearize)",
+                               "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "bound_note": "the HBM figure is SURVEY s8(d)'s algorithmic-byte roofline of the PHOTOMETRIC factor alone "
+                                             "(492 B per source pixel at FS 16 / CS 32) over this kernel's launch time, although the kernel "
+                                             "now does a third of the geometric factor's contractions as well; `linearize_pair` prices "
+                                             "both factor types' algorithmic bytes against both kernels' time.  What binds the kernel is "
+                                             "VALU + MFMA issue and the LDS pipe (see issue), not HBM",
+                               # both linearize kernels of a step as one unit: (B_photo + B_geo) per source pixel over t_photo + t_geo
+                               # (r04, separate kernels: 4.70 GB / (0.639 + 0.494 ms) = 4.15 TB/s = 0.519)
+                               "linearize_pair": {"achieved": px_launch * (bytes_photo_px + bytes_geo_px) / ((ms_photo + ms_geo) * 1e-3) / 1e9
+                                                  if ms_photo + ms_geo > 0 else 0.0,
+                                                  "frac": px_launch * (bytes_photo_px + bytes_geo_px) / ((ms_photo + ms_geo) * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                                  if ms_photo + ms_geo > 0 else 0.0,
+                                                  "bytes_per_launch_pair": px_launch * (bytes_photo_px + bytes_geo_px),
+                                                  "ms": ms_photo + ms_geo},
+                               "traffic": PMC_TRAFFIC_BYTES_K64["hbm_bytes_per_launch"] if pmc_ok else None,
+                               "traffic_source": ("rocprofv3 --pmc FETCH_SIZE(x2 gfx950 correction)+WRITE_SIZE, " + PMC_K64["source"]
+                                                  if pmc_ok else "none: " + ("the kernel sources no longer hash to the committed counter "
+                                                  "summary's build (" + PMC_K64["source"] + ")" if headline else "counters are committed "
+                                                  "for the headline workload only")),
+                               "issue": issue_roofline(PMC_K64["photo"], ms_photo) if pmc_ok else None,
+                               "bytes_per_launch": px_launch * bytes_photo_px, "avg_launch_ms": ms_photo,
+                               "geo_kernel": {"achieved": ach_geo, "frac": ach_geo / HBM_PEAK_GBS, "avg_launch_ms": ms_geo,
+                                              "bytes_per_launch": px_launch * bytes_geo_px,
+                                              "issue": issue_roofline(PMC_K64["geo"], ms_geo) if pmc_ok else None},
+                               # (the window's error pass evaluates both factor types in the photometric error kernel: no
+                               #  separate geometric launch)
+                               "error_pass_ms": {"photo+geo" if ktime[3][1] == 0 else "photo": ktime[2][0] / max(1, ktime[2][1]),
+                                                 **({"geo": ktime[3][0] / ktime[3][1]} if ktime[3][1] else {})}}
+            if phase_ms:
+                out["phase_ms"] = phase_ms
+            if world == 1 and args.emulate_shard != "off" and len(win_h.links) >= 8:
+                er, ew = (int(v) for v in args.emulate_shard.split("/"))
+                try:
+                    out["shard_emulation"] = shard_emulation(capi, torch, win, win_h, er, ew, args.steps, RESTART, ms_per_step)
+                except Exception as exc:            # the headline line must not depend on the emulation
+                    out["shard_emulation"] = {"error": repr(exc)}
+                se = out["shard_emulation"]
+                if isinstance(se, dict) and "speedup_vs_one_gpu_classic" in se:
+                    # r06: the ceiling belongs in the line, not only in DESIGN.md
+                    sp = se["speedup_vs_one_gpu_classic"]
+                    se["ceiling_note"] = (
+                        f"one rank of {ew} measured on this device runs an LM iteration {sp:.1f}x faster than the one-GPU step BEFORE any "
+                        "xGMI transfer: the >= 6x strong-scaling target is out of reach at this window size by design -- the "
+                        "replicated host factorisation (a chain of K/2 block rows per half, ~0.2 ms) does not shard.  The four-chain "
+                        "elimination was costed again in r06 (DESIGN s7): two of its four chains sit between two separators and drag "
+                        "3-row arrow chains of the same length behind them -- ~2x the multiply-adds, ~14 host threads per rank for "
+                        "~30 us of critical path; not built")
+                if classic_seq and se.get("one_gpu_ms_per_step_same_sequence", 0) == se.get("one_gpu_ms_per_step_same_sequence", float("nan")):
+                    # the same window with the engine's other LM sequence (SageLmConfig.linearize_at_candidate = 1: the candidate is
+                    # evaluated by the linearize kernels, an accepted iteration has no separate error pass; identical iterates and
+                    # decisions) -- reported next to `value`, which stays on the classic sequence of SURVEY s8d
+                    ms_c = se["one_gpu_ms_per_step_same_sequence"]
+                    out["linearize_at_candidate"] = {"ms_per_step": ms_c, "lm_iters_per_sec": 1e3 / ms_c,
+                                                     "value": residuals_per_step / (ms_c * 1e-3) / 1e6, "unit": "Mresiduals/s",
+                                                     "note": "median of the iterations 2..3 after each restart (every timed iteration "
+                                                             "accepted); a rejected iteration costs a linearize here instead of an error pass"}
+            # where the host side ran (the replicated solve is a fifth of the step and lives on host cores that a one-GPU host
+            # shares with its other tenants: DESIGN s7 "what the slow processes are")
             try:
-                out["shard_emulation"] = shard_emulation(capi, torch, win, win_h, er, ew, args.steps, RESTART, ms_per_step)
-            except Exception as exc:            # the headline line must not depend on the emulation
-                out["shard_emulation"] = {"error": repr(exc)}
-            se = out["shard_emulation"]
-            if isinstance(se, dict) and "speedup_vs_one_gpu_classic" in se:
-                # r06: the ceiling belongs in the line, not only in DESIGN.md
-                sp = se["speedup_vs_one_gpu_classic"]
-                se["ceiling_note"] = (
-                    f"one rank of {ew} measured on this device runs an LM iteration {sp:.1f}x faster than the one-GPU step BEFORE any "
-                    "xGMI transfer: the >= 6x strong-scaling target is out of reach at this window size by design -- the "
-                    "replicated host factorisation (a chain of K/2 block rows per half, ~0.2 ms) does not shard.  The four-chain "
-                    "elimination was costed again in r06 (DESIGN s7): two of its four chains sit between two separators and drag "
-                    "3-row arrow chains of the same length behind them -- ~2x the multiply-adds, ~14 host threads per rank for "
-                    "~30 us of critical path; not built")
-            if classic_seq and se.get("one_gpu_ms_per_step_same_sequence", 0) == se.get("one_gpu_ms_per_step_same_sequence", float("nan")):
-                # the same window with the engine's other LM sequence (SageLmConfig.linearize_at_candidate = 1: the candidate is
-                # evaluated by the linearize kernels, an accepted iteration has no separate error pass; identical iterates and
-                # decisions) -- reported next to `value`, which stays on the classic sequence of SURVEY s8d
-                ms_c = se["one_gpu_ms_per_step_same_sequence"]
-                out["linearize_at_candidate"] = {"ms_per_step": ms_c, "lm_iters_per_sec": 1e3 / ms_c,
-                                                 "value": residuals_per_step / (ms_c * 1e-3) / 1e6, "unit": "Mresiduals/s",
-                                                 "note": "median of the iterations 2..3 after each restart (every timed iteration "
-                                                         "accepted); a rejected iteration costs a linearize here instead of an error pass"}
-        # where the host side ran (the replicated solve is a fifth of the step and lives on host cores that a 1-GPU box
-        # shares with the node's other tenants: DESIGN s7 "what the slow processes are")
-        try:
-            import ctypes
-            out["host_placement"] = {"lm_thread_cpu": int(ctypes.CDLL(None).sched_getcpu()),
-                                     "lm_thread_mask_cpus": len(os.sched_getaffinity(0)),
-                                     "solver_helper_cpus": capi.solver_helper_cpus(),
-                                     "placement_monitor_moves": capi.solver_placement_moves(),
-                                     "placement_monitor": "opt-in (SAGE_PLACEMENT_MONITOR=1); off" if os.environ.get("SAGE_PLACEMENT_MONITOR", "0") in ("", "0") else "on",
-                                     "host_threads_running": capi.host_threads_running(),
-                                     "loadavg_1min": float(open("/proc/loadavg").read().split()[0])}
-        except Exception as e:                                  # diagnostics only
-            out["host_placement"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            # the baseline's OpenMP team inherits the caller's mask: give it back every CPU the process started with (the
-            # binding above narrows the LM thread to one L3 domain)
-            os.sched_setaffinity(0, full_affinity)
-            out["cpu_baseline"] = cpu_baseline(win_h)
+                import ctypes
+                out["host_placement"] = {"lm_thread_cpu": int(ctypes.CDLL(None).sched_getcpu()),
+                                         "lm_thread_mask_cpus": len(os.sched_getaffinity(0)),
+                                         "solver_helper_cpus": capi.solver_helper_cpus(),
+                                         "placement_monitor_moves": capi.solver_placement_moves(),
+                                         "placement_monitor": "opt-in (SAGE_PLACEMENT_MONITOR=1); off" if os.environ.get("SAGE_PLACEMENT_MONITOR", "0") in ("", "0") else "on",
+                                         "host_threads_running": capi.host_threads_running(),
+                                         "loadavg_1min": float(open("/proc/loadavg").read().split()[0])}
+            except Exception as e:                                  # diagnostics only
+                out["host_placement"] = {"error": str(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                # the baseline's OpenMP team inherits the caller's mask: give it back every CPU the process started with (the
+                # binding above narrows the LM thread to one L3 domain)
+                os.sched_setaffinity(0, full_affinity)
+                out["cpu_baseline"] = cpu_baseline(win_h)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     win.close()
     if rccl_comm is not None:

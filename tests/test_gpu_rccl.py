@@ -197,7 +197,7 @@ def test_bench_launches_its_own_ranks_one_device_gloo():
     """`python bench.py --gpus 2` without a launcher re-executes itself under torch.distributed.run: two ranks, ONE JSON
     line with n_gpus 2, per-rank kernel times, the sharded collective named (gloo hook with the one-device knob)."""
     r = _bench({"SAGE_BENCH_ONE_DEVICE": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--keyframes", "8",
-               "--height", "64", "--width", "80", "--no-cpu-baseline")
+               "--height", "64", "--width", "80", "--no-cpu-baseline", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
