@@ -7,8 +7,6 @@
 //   sage_damped_solve_qr_f32 core/system/camera_tracker.cpp:1182-1183 (colPivHouseholderQr in fp32)
 //   sage_track_lm            core/system/camera_tracker.cpp:1156-1279 (+ LMConvergence :527-573)
 #include <algorithm>
-#include <map>
-#include <memory>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -16,14 +14,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
-#include <condition_variable>
 #include <cstring>
 #include <ctime>
-#include <pthread.h>
 #include <sched.h>
-#include <sys/syscall.h>
-#include <unistd.h>
-#include <mutex>
 #include <numeric>
 #include <random>
 #include <vector>
@@ -1432,7 +1425,6 @@ void EnvelopeMatrix::solve_inplace(std::vector<double> &b) const
 // ------------------------------------------------------------------------------------------------
 namespace sage
 {
-static void host_threads_atexit_once(); // (defined with host_threads_shutdown below)
 namespace
 {
 #define SAGE_STOREU(p, v) __builtin_memcpy((p), &(v), sizeof(v8d))
@@ -1731,13 +1723,7 @@ static inline __attribute__((always_inline)) bool factor_diag(double *S, double 
 }
 
 // The device streams the blocks in row order (solve_kernels.hip): wait until every block of row i carries this solve's
-// ticket.  (Not inlined: keeps <chrono> out of the target_clones bodies.)
-static double mono_seconds()
-{
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
+// ticket.
 // from_col: only the blocks (i, j >= from_col) -- the others have been consumed already (the arrow-row tasks take their
 // blocks one by one).  Structural fill blocks (E.fill) are zeroed here instead of waited for: this is their first touch.
 static __attribute__((noinline)) bool wait_row_tickets(const BlockEnvelope &E, int i, double *T, int from_col = 0,
@@ -2195,8 +2181,6 @@ struct SepTaskA
 // Which long arrow-row chains a thread takes: domain 0 = the caller's L3 domain (first half), 1 = the second half's own L3
 // domain of a two-domain placement, -1 = a pool worker elsewhere on the node (short tasks and pair products only)
 static thread_local int tl_domain = 0;
-static std::atomic<int> g_domain_threads[2] = {{-1}, {0}}; // pool workers per domain (-1: unknown / no pool)
-static std::atomic<bool> g_two_domains{false};             // the second half, its look-ahead and its chains sit on domain 1
 struct SepTaskB
 {
   int i, i2, half, k0, k1; // common columns [k0, k1), i2 < i
@@ -2632,75 +2616,35 @@ static void sep_work_c(SepJob &J, bool wait_for_go)
   }
 }
 
-// Worker pool for the arrow rows: persistent threads that sleep on a condition variable, are woken by
-// block_chol_arm(true) and spin for a job for a few milliseconds (like the helper of the second half).
-struct SepPool
+static inline void cpu_relax() { __builtin_ia32_pause(); }
+
+// Worker pool for the arrow rows (host_threads.h Worker, n threads): woken by block_chol_arm(true), spins for a job for
+// 20 ms at most.  A caller that owns the pool (`busy`) hands its SepJob over through posted / open / active.
+struct SepPool final : Worker
 {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<bool> armed{false};
-  std::atomic<unsigned> posted{0};
+  explicit SepPool(int n) : Worker(n, 20e-3) {}
   std::atomic<bool> open{false};
   std::atomic<int> active{0};
   std::atomic<bool> busy{false};
   std::atomic<SepJob *> job{nullptr};
-  std::vector<pthread_t> tids;
-  std::vector<std::thread> ths; // joinable: host_threads_shutdown() stops and joins them, block_chol_arm() starts them again
-  int n_workers = 0;
-  std::atomic<bool> quit{false}, running{false};
-  unsigned seen0 = 0;
-  std::unique_ptr<std::atomic<int>[]> ktid, cpu; // per worker: kernel thread id, CPU it is pinned to (-1: none) -- placement monitor
-  std::vector<int> dom; // per worker: 0 / 1 = pinned to a core of the first / second half's L3 domain, -1 elsewhere (place_pool)
-  std::atomic<int> near_cpu{-1};
-  std::atomic<int> near_mode{-1};
-  void loop(int idx)
+  void run(int t) override
   {
-    unsigned seen = seen0;
-    for (;;)
+    // hand-off: the owner does `open = false` THEN reads `active`; a worker does `active += 1` THEN reads `open`.
+    // A store followed by a load of another variable needs sequential consistency on both sides (with release /
+    // acquire the two may be reordered -- the owner reads active == 0 while a late worker still reads open == true
+    // and runs a job that lives on the owner's stack after the owner has returned)
+    active.fetch_add(1, std::memory_order_seq_cst);
+    if (open.load(std::memory_order_seq_cst))
     {
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return armed.load(std::memory_order_acquire) || quit.load(std::memory_order_acquire); });
-      }
-      if (quit.load(std::memory_order_acquire))
-        return;
-      double t0 = mono_seconds();
-      unsigned spins = 0;
-      while (armed.load(std::memory_order_acquire) && !quit.load(std::memory_order_relaxed))
-      {
-        const unsigned p = posted.load(std::memory_order_acquire);
-        if (p != seen)
-        {
-          seen = p;
-          // hand-off: the owner does `open = false` THEN reads `active`; a worker does `active += 1` THEN reads `open`.
-          // A store followed by a load of another variable needs sequential consistency on both sides (with release /
-          // acquire the two may be reordered -- the owner reads active == 0 while a late worker still reads open == true
-          // and runs a job that lives on the owner's stack after the owner has returned)
-          active.fetch_add(1, std::memory_order_seq_cst);
-          if (open.load(std::memory_order_seq_cst))
-          {
-            SepJob *j = job.load(std::memory_order_acquire);
-            tl_domain = (size_t)idx < dom.size() ? dom[idx] : 0;
-            sep_work(*j);
-            sep_work_c(*j, true);
-          }
-          active.fetch_sub(1, std::memory_order_seq_cst);
-          t0 = mono_seconds(); // the idle time-out counts from the last job, not from the wake-up
-        }
-        __builtin_ia32_pause();
-        // nobody came for 20 ms: back to sleep.  Only while no job is open (the owner clears `armed` itself when its solve
-        // is done): a worker that timed out in the middle of another caller's arm / post must not disarm the pool
-        if ((++spins & 1023) == 0 && mono_seconds() - t0 > 20e-3 && !open.load(std::memory_order_acquire))
-          armed.store(false, std::memory_order_release);
-      }
+      SepJob *j = job.load(std::memory_order_acquire);
+      tl_domain = th[t].dom.load(std::memory_order_acquire);
+      sep_work(*j);
+      sep_work_c(*j, true);
     }
+    active.fetch_sub(1, std::memory_order_seq_cst);
   }
+  bool hold() const override { return open.load(std::memory_order_acquire); } // (an open job keeps the pool armed)
 };
-// ---- life cycle of the solver's host threads (r06).  The OBJECTS (CholHelper x 3, SepPool) are made once and never freed
-// -- a caller that lost a race with a shutdown still holds valid memory and, by the hand-over protocols' design, depends on
-// no thread that has not claimed its job -- but the THREADS are joinable: block_chol_arm() starts them on demand,
-// host_threads_shutdown() (sage_shutdown(), the last sage_window_destroy, atexit) stops and joins them.  Nothing is detached.
-static std::mutex g_threads_mu;
 static std::atomic<SepPool *> g_sep_pool_made{nullptr}; // (the placement monitor must not CREATE the pool by asking for it)
 static SepPool *sep_pool()
 {
@@ -2712,43 +2656,11 @@ static SepPool *sep_pool()
     n = std::min(n, (int)hw - 4);
     if (n < 1)
       return (SepPool *)nullptr;
-    SepPool *q = new SepPool;
-    q->n_workers = n;
-    q->ktid.reset(new std::atomic<int>[n]);
-    q->cpu.reset(new std::atomic<int>[n]);
-    for (int i = 0; i < n; ++i)
-    {
-      q->ktid[i].store(0);
-      q->cpu[i].store(-1);
-    }
+    SepPool *q = new SepPool(n);
     g_sep_pool_made.store(q, std::memory_order_release);
     return q;
   }();
   return p;
-}
-// (g_threads_mu held)
-static void sep_pool_start(SepPool *q)
-{
-  if (q->running.load(std::memory_order_acquire))
-    return;
-  host_threads_atexit_once();
-  q->quit.store(false, std::memory_order_release);
-  q->tids.clear();
-  q->ths.clear();
-  q->near_cpu.store(-1, std::memory_order_release); // new threads: not pinned yet, place_pool places them again
-  q->near_mode.store(-1, std::memory_order_release);
-  q->seen0 = q->posted.load(std::memory_order_acquire);
-  for (int i = 0; i < q->n_workers; ++i)
-  {
-    q->ktid[i].store(0);
-    q->cpu[i].store(-1);
-    q->ths.emplace_back([q, i] {
-      q->ktid[i].store((int)syscall(SYS_gettid), std::memory_order_release);
-      q->loop(i);
-    });
-    q->tids.push_back(q->ths.back().native_handle());
-  }
-  q->running.store(true, std::memory_order_release);
 }
 
 static int block_chol_range(const BlockEnvelope &E, double *T, double *X, double *y, int phase, int lo, int hi,
@@ -2758,16 +2670,13 @@ static int block_chol_range(const BlockEnvelope &E, double *T, double *X, double
 }
 
 // Helper threads of a split window: [0] takes the second half, [1] / [2] are the look-ahead stages of the first / second
-// half (BlockEnvelope::RowPipe).  A helper sleeps on a condition variable, is woken by block_chol_arm() (called while the
-// caller still waits for the device), then spins for a job so that picking one up costs no wake-up latency.  Nobody
-// depends on a helper that has not claimed its job: the second half is claimed back and run by the caller, a half without
-// a look-ahead stage runs as one thread.
-struct CholHelper
+// half (BlockEnvelope::RowPipe).  A helper (host_threads.h Worker, one thread) is woken by block_chol_arm() (called while
+// the caller still waits for the device), then spins for a job for 8 ms at most so that picking one up costs no wake-up
+// latency.  Nobody depends on a helper that has not claimed its job: the second half is claimed back and run by the
+// caller, a half without a look-ahead stage runs as one thread.
+struct CholHelper final : Worker
 {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<bool> armed{false};
-  std::atomic<unsigned> posted{0};
+  explicit CholHelper(int kind_) : Worker(1, 8e-3), kind(kind_) {}
   std::atomic<int> claim{0};   // 0 free, 1 helper, 2 caller
   std::atomic<int> p1_rc{-2};  // result of the helper's factorisation pass (-2: not finished)
   std::atomic<int> go_p2{0};   // 1: run the back substitution, 2: skip it
@@ -2775,54 +2684,22 @@ struct CholHelper
   std::atomic<bool> busy{false}; // one client at a time
   const BlockEnvelope *E = nullptr;
   double *T = nullptr, *X = nullptr, *y = nullptr;
-  int kind = 0; // 0: second half (factorisation, later the back substitution), 1: look-ahead stage of rows [lo, hi)
+  const int kind; // 0: second half (factorisation, later the back substitution), 1: look-ahead stage of rows [lo, hi)
   int lo = 0, hi = 0;
-  std::thread th;
-  pthread_t tid{};
-  std::atomic<int> ktid{0};    // kernel thread id (its /proc/self/task entry: the placement monitor reads its run-queue delay)
-  std::atomic<int> cpu{-1};    // the CPU it is pinned to (-1: not pinned)
-  std::atomic<int> near_cpu{-1}, near_mode{-1};
-  std::atomic<bool> quit{false}, running{false}; // joinable thread: started by block_chol_arm, stopped by host_threads_shutdown
-  unsigned seen0 = 0;
-  static void cpu_relax() { __builtin_ia32_pause(); }
-  void loop();
+  void run(int) override;
 };
 static CholHelper *chol_helper(int idx = 0)
 {
-  // the objects live for the life of the process (see "life cycle" above); their threads come and go
+  // the objects live for the life of the process (host_threads.h); their threads come and go
   static CholHelper **hs = [] {
     CholHelper **v = new CholHelper *[3]{nullptr, nullptr, nullptr};
     const unsigned hc = std::thread::hardware_concurrency();
     for (int i = 0; i < 3; ++i)
-    {
-      if (hc < (i == 0 ? 2u : 4u))
-        continue;
-      CholHelper *p = new CholHelper;
-      p->kind = i == 0 ? 0 : 1;
-      v[i] = p;
-    }
+      if (hc >= (i == 0 ? 2u : 4u))
+        v[i] = new CholHelper(i == 0 ? 0 : 1);
     return v;
   }();
   return hs[idx];
-}
-// (g_threads_mu held)
-static void chol_helper_start(CholHelper *p)
-{
-  if (p->running.load(std::memory_order_acquire))
-    return;
-  host_threads_atexit_once();
-  p->quit.store(false, std::memory_order_release);
-  p->ktid.store(0, std::memory_order_release);
-  p->cpu.store(-1, std::memory_order_release);
-  p->near_cpu.store(-1, std::memory_order_release);
-  p->near_mode.store(-1, std::memory_order_release);
-  p->seen0 = p->posted.load(std::memory_order_acquire);
-  p->th = std::thread([p] {
-    p->ktid.store((int)syscall(SYS_gettid), std::memory_order_release);
-    p->loop();
-  });
-  p->tid = p->th.native_handle();
-  p->running.store(true, std::memory_order_release);
 }
 
 static std::atomic<long long> g_lookahead_count{0};
@@ -2857,7 +2734,7 @@ static bool lookahead_engage(int idx, const BlockEnvelope &E, double *T, double 
   unsigned spins = 0;
   while (h->claim.load(std::memory_order_acquire) == 0)
   {
-    CholHelper::cpu_relax();
+    cpu_relax();
     if ((++spins & 63) == 0 && mono_seconds() - t0 > 20e-6)
     {
       int e0 = 0;
@@ -2875,727 +2752,42 @@ static void lookahead_release(int idx)
 {
   CholHelper *h = chol_helper(idx);
   while (h->p1_rc.load(std::memory_order_acquire) == -2)
-    CholHelper::cpu_relax();
+    cpu_relax();
   h->armed.store(false, std::memory_order_release);
   h->busy.store(false, std::memory_order_release);
 }
 
-void CholHelper::loop()
+void CholHelper::run(int)
 {
-  unsigned seen = seen0; // (sampled by the thread that started this one, before it can post: a restarted thread does not
-                         //  answer posts from before its time and cannot miss the starter's first one)
-  for (;;)
+  int expect = 0;
+  if (!claim.compare_exchange_strong(expect, 1, std::memory_order_acq_rel))
+    return;
+  const BlockEnvelope &e = *E;
+  if (kind == 1)
   {
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return armed.load(std::memory_order_acquire) || quit.load(std::memory_order_acquire); });
-    }
-    if (quit.load(std::memory_order_acquire))
-      return;
-    const double t0 = mono_seconds();
-    unsigned spins = 0;
-    while (armed.load(std::memory_order_acquire) && !quit.load(std::memory_order_relaxed))
-    {
-      const unsigned p = posted.load(std::memory_order_acquire);
-      if (p != seen)
-      {
-        seen = p;
-        int expect = 0;
-        if (claim.compare_exchange_strong(expect, 1, std::memory_order_acq_rel))
-        {
-          const BlockEnvelope &e = *E;
-          if (kind == 1)
-          {
-            const int rc = block_chol_range(e, T, X, y, 0, lo, hi, 2);
-            p1_rc.store(rc == -2 ? -3 : rc, std::memory_order_release); // (-2 is the "not finished" value)
-          }
-          else
-          {
-            const bool piped = lookahead_engage(2, e, T, X, y, e.n1, e.n1 + e.n2);
-            const int rc = block_chol_range(e, T, X, y, 0, e.n1, e.n1 + e.n2, piped ? 1 : 0);
-            if (piped)
-              lookahead_release(2);
-            p1_rc.store(rc, std::memory_order_release);
-            int g;
-            while ((g = go_p2.load(std::memory_order_acquire)) == 0)
-              cpu_relax();
-            if (g == 1)
-              block_chol_range(e, T, X, y, 1, e.n1, e.n1 + e.n2);
-            p2_done.store(1, std::memory_order_release);
-          }
-        }
-      }
-      cpu_relax();
-      if ((++spins & 1023) == 0 && mono_seconds() - t0 > 8e-3) // nobody came: back to sleep
-        armed.store(false, std::memory_order_release);
-    }
+    const int rc = block_chol_range(e, T, X, y, 0, lo, hi, 2);
+    p1_rc.store(rc == -2 ? -3 : rc, std::memory_order_release); // (-2 is the "not finished" value)
+    return;
   }
+  const bool piped = lookahead_engage(2, e, T, X, y, e.n1, e.n1 + e.n2);
+  const int rc = block_chol_range(e, T, X, y, 0, e.n1, e.n1 + e.n2, piped ? 1 : 0);
+  if (piped)
+    lookahead_release(2);
+  p1_rc.store(rc, std::memory_order_release);
+  int g;
+  while ((g = go_p2.load(std::memory_order_acquire)) == 0)
+    cpu_relax();
+  if (g == 1)
+    block_chol_range(e, T, X, y, 1, e.n1, e.n1 + e.n2);
+  p2_done.store(1, std::memory_order_release);
 }
 } // namespace
 
-// CPU list file of sysfs ("0-7,128-135") -> cpu numbers
-static std::vector<int> read_cpu_list(const char *path)
+Worker *solve_worker(int idx, bool make)
 {
-  std::vector<int> out;
-  FILE *f = fopen(path, "r");
-  if (!f)
-    return out;
-  char buf[4096];
-  if (fgets(buf, sizeof(buf), f))
-  {
-    const char *p = buf;
-    while (*p)
-    {
-      char *end;
-      const long a = strtol(p, &end, 10);
-      if (end == p)
-        break;
-      long b = a;
-      p = end;
-      if (*p == '-')
-      {
-        b = strtol(p + 1, &end, 10);
-        p = end;
-      }
-      for (long c = a; c <= b && out.size() < 4096; ++c)
-        out.push_back((int)c);
-      if (*p == ',')
-        ++p;
-    }
-  }
-  fclose(f);
-  return out;
-}
-
-// ---- which CPUs the solve's threads may be placed on.  Default: the calling thread's affinity mask.  r05: a GPU box is a
-// slice of a node whose other GPUs run other jobs -- their host threads sit on CPUs of the same NUMA node, and a helper
-// pinned onto a core another tenant saturates runs its half of the factorisation at half speed for the life of the
-// process (~1 process in 8 measured +60..200 us per solve).  sage_bind_thread_to_device therefore samples /proc/stat and
-// hands over the CPUs of QUIET physical cores (placement_set_allowed); the caller's own mask may be narrower than that
-// (its L3 domain), the loop-closure plans' second domain is looked for in the handed-over set.
-static std::mutex g_place_mu;
-static bool g_place_override = false;
-static cpu_set_t g_place_allowed;
-// (heap-allocated and never destroyed: a thread of this library may still look at them while the process runs its static
-//  destructors)
-static std::map<std::pair<int, bool>, std::vector<int>> &g_ccx_cache = *new std::map<std::pair<int, bool>, std::vector<int>>;
-static std::map<std::pair<int, size_t>, std::vector<int>> &g_dom2_cache = *new std::map<std::pair<int, size_t>, std::vector<int>>;
-
-void placement_set_allowed(const cpu_set_t *allowed)
-{
-  std::lock_guard<std::mutex> lk(g_place_mu);
-  g_place_override = allowed != nullptr;
-  if (allowed)
-    g_place_allowed = *allowed;
-  g_ccx_cache.clear();
-  g_dom2_cache.clear();
-}
-
-static bool placement_allowed(cpu_set_t *out) // (g_place_mu held)
-{
-  if (g_place_override)
-  {
-    *out = g_place_allowed;
-    return true;
-  }
-  return sched_getaffinity(0, sizeof(*out), out) == 0;
-}
-
-// CPUs that were busy (> 25 % non-idle) during a window of `ms` milliseconds; empty when /proc/stat cannot be read
-std::vector<int> placement_busy_cpus(int ms)
-{
-  auto snap = [](std::map<int, std::pair<unsigned long long, unsigned long long>> &m) {
-    FILE *f = fopen("/proc/stat", "r");
-    if (!f)
-      return false;
-    char line[512];
-    while (fgets(line, sizeof(line), f))
-    {
-      int cpu;
-      unsigned long long v[8] = {0};
-      if (sscanf(line, "cpu%d %llu %llu %llu %llu %llu %llu %llu %llu", &cpu, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6],
-                 &v[7]) >= 5)
-      {
-        unsigned long long tot = 0;
-        for (int i = 0; i < 8; ++i)
-          tot += v[i];
-        m[cpu] = {tot, v[3] + v[4]};
-      }
-    }
-    fclose(f);
-    return !m.empty();
-  };
-  std::map<int, std::pair<unsigned long long, unsigned long long>> a, b;
-  std::vector<int> out;
-  if (!snap(a))
-    return out;
-  std::this_thread::sleep_for(std::chrono::milliseconds(ms));
-  if (!snap(b))
-    return out;
-  for (const auto &kv : a)
-  {
-    auto it = b.find(kv.first);
-    if (it == b.end())
-      continue;
-    const double tot = (double)(it->second.first - kv.second.first), idle = (double)(it->second.second - kv.second.second);
-    if (tot >= 4.0 && 1.0 - idle / tot > 0.25) // (USER_HZ ticks: at least 4 in the window)
-      out.push_back(kv.first);
-  }
-  return out;
-}
-
-// hardware threads of the physical core of `cpu`
-std::vector<int> placement_core_siblings(int cpu)
-{
-  char path[128];
-  snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", cpu);
-  std::vector<int> sib = read_cpu_list(path);
-  if (sib.empty())
-    sib.push_back(cpu);
-  return sib;
-}
-
-std::vector<int> placement_l3_domain(int cpu)
-{
-  char path[128];
-  snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu);
-  return read_cpu_list(path);
-}
-
-// Thread placement of the solve: the caller, the helper of the second half and the worker pool each get their own
-// PHYSICAL core of the caller's CCX (cores that share its L3): the halves and the arrow-row tasks then work out of one
-// cache and one NUMA node (a helper on the far socket takes ~35 % longer for its half), and no two of them share a core
-// through SMT (r03: a pool thread on the helper's sibling made the helper's half 35-45 % slower on config 5).
-// cores[0] -> helper, cores[1 + t] -> pool thread t; threads the CCX has no core left for fall back to the rest of the
-// caller's NUMA node as a set.
-static std::vector<int> sibling_free_cores(const std::vector<int> &cpus, int caller_cpu, const cpu_set_t &allowed)
-{
-  std::vector<int> cores, seen_core;
-  char path[128];
-  snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", caller_cpu);
-  const std::vector<int> caller_sib = read_cpu_list(path);
-  const int caller_core = caller_sib.empty() ? caller_cpu : *std::min_element(caller_sib.begin(), caller_sib.end());
-  for (int c : cpus)
-  {
-    if (c >= CPU_SETSIZE || !CPU_ISSET(c, &allowed))
-      continue;
-    snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
-    const std::vector<int> sib = read_cpu_list(path);
-    const int core = sib.empty() ? c : *std::min_element(sib.begin(), sib.end());
-    if (core == caller_core || std::find(seen_core.begin(), seen_core.end(), core) != seen_core.end())
-      continue;
-    seen_core.push_back(core);
-    cores.push_back(c); // the first allowed hardware thread of that core
-  }
-  return cores;
-}
-
-static std::vector<int> node_cpus_of(int cpu)
-{
-  char path[128];
-  for (int node = 0; node < 64; ++node)
-  {
-    snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
-    const std::vector<int> nl = read_cpu_list(path);
-    if (std::find(nl.begin(), nl.end(), cpu) != nl.end())
-      return nl;
-  }
-  return {};
-}
-
-// (sysfs is read once per caller CPU: the arm call sits at the start of every solve; returned by value -- the cache is
-//  cleared when the allowed set changes)
-static std::vector<int> ccx_cores_of(int cpu, bool with_node)
-{
-  std::lock_guard<std::mutex> lk(g_place_mu);
-  auto it = g_ccx_cache.find({cpu, with_node});
-  if (it != g_ccx_cache.end())
-    return it->second;
-  std::vector<int> cores;
-  char path[128];
-  snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu);
-  const std::vector<int> l3 = read_cpu_list(path);
-  cpu_set_t allowed;
-  if (!l3.empty() && placement_allowed(&allowed))
-  {
-    cores = sibling_free_cores(l3, cpu, allowed);
-    if (with_node)
-      for (int c : sibling_free_cores(node_cpus_of(cpu), cpu, allowed))
-        if (std::find(cores.begin(), cores.end(), c) == cores.end())
-          cores.push_back(c);
-  }
-  return g_ccx_cache.emplace(std::make_pair(cpu, with_node), std::move(cores)).first->second;
-}
-
-static void pin_one(pthread_t t, int cpu)
-{
-  cpu_set_t want;
-  CPU_ZERO(&want);
-  CPU_SET(cpu, &want);
-  (void)pthread_setaffinity_np(t, sizeof(want), &want);
-}
-
-// cores of ANOTHER L3 domain of the caller's NUMA node (the next one with at least `want` free physical cores), or empty
-static std::vector<int> second_domain_cores_uncached(int cpu, size_t want);
-static std::vector<int> second_domain_cores(int cpu, size_t want)
-{
-  // (sysfs is read once per caller CPU and size: the arm call sits at the start of every solve)
-  std::lock_guard<std::mutex> lk(g_place_mu);
-  auto it = g_dom2_cache.find({cpu, want});
-  if (it != g_dom2_cache.end())
-    return it->second;
-  return g_dom2_cache.emplace(std::make_pair(cpu, want), second_domain_cores_uncached(cpu, want)).first->second;
-}
-static std::vector<int> second_domain_cores_uncached(int cpu, size_t want)
-{
-  char path[128];
-  snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu);
-  const std::vector<int> l3a = read_cpu_list(path);
-  cpu_set_t allowed;
-  if (l3a.empty() || !placement_allowed(&allowed))
-    return {};
-  std::vector<int> seen = l3a;
-  for (int c : node_cpus_of(cpu))
-  {
-    if (std::find(seen.begin(), seen.end(), c) != seen.end() || c >= CPU_SETSIZE || !CPU_ISSET(c, &allowed))
-      continue;
-    snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", c);
-    const std::vector<int> l3b = read_cpu_list(path);
-    if (l3b.empty())
-      continue;
-    seen.insert(seen.end(), l3b.begin(), l3b.end());
-    std::vector<int> cores = sibling_free_cores(l3b, cpu, allowed);
-    if (cores.size() >= want)
-      return cores;
-  }
-  return {};
-}
-
-// ---- placement monitor (r05).  The box's other tenants move: a core that was quiet when the helpers were placed may carry
-// somebody else's thread a minute later, and a helper that shares its hardware thread (it then waits on the run queue when the
-// solve wakes it) or its physical core (SMT: ~2/3 speed) slows every solve of the process from then on.  A background thread
-// looks every 250 ms at (a) the run-queue delay of the three helper threads (/proc/self/task/<tid>/schedstat) and (b) the load
-// on the OTHER hardware threads of their cores (/proc/stat); a helper that is crowded in two consecutive looks is moved to
-// a core of its own L3 domain (else the caller's, else the NUMA node) that is idle on all its hardware threads; the workers of
-// the loop-closure plans' arrow-row pool are watched the same way once the pool exists.  SAGE_PLACEMENT_MONITOR=0 turns it off; SAGE_DEBUG_TIMING prints the moves.
-static std::atomic<bool> g_monitor_started{false};
-static std::atomic<int> g_monitor_moves{0};
-static std::mutex g_pin_mu;
-static std::mutex g_monitor_mu;
-static std::condition_variable g_monitor_cv;
-static bool g_monitor_stop = false;           // (g_monitor_mu)
-static std::thread *g_monitor_thread = nullptr; // (g_threads_mu)
-
-static long long read_run_delay_ns(int ktid)
-{
-  char path[96];
-  snprintf(path, sizeof(path), "/proc/self/task/%d/schedstat", ktid);
-  FILE *f = fopen(path, "r");
-  if (!f)
-    return -1;
-  unsigned long long run = 0, delay = 0;
-  const int n = fscanf(f, "%llu %llu", &run, &delay);
-  fclose(f);
-  return n == 2 ? (long long)delay : -1;
-}
-
-static bool stat_snapshot(std::map<int, std::pair<unsigned long long, unsigned long long>> &m)
-{
-  FILE *f = fopen("/proc/stat", "r");
-  if (!f)
-    return false;
-  char line[512];
-  while (fgets(line, sizeof(line), f))
-  {
-    int cpu;
-    unsigned long long v[8] = {0};
-    if (sscanf(line, "cpu%d %llu %llu %llu %llu %llu %llu %llu %llu", &cpu, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6],
-               &v[7]) >= 5)
-    {
-      unsigned long long tot = 0;
-      for (int i = 0; i < 8; ++i)
-        tot += v[i];
-      m[cpu] = {tot, v[3] + v[4]};
-    }
-  }
-  fclose(f);
-  return !m.empty();
-}
-
-static void placement_monitor_loop()
-{
-  const bool verbose = sage::env_flag("SAGE_DEBUG_TIMING");
-  std::map<int, std::pair<unsigned long long, unsigned long long>> prev, cur;
-  // watched threads: slots 0..2 the helpers, 3.. the arrow-row pool's workers (once a loop-closure plan has made the pool)
-  std::vector<long long> prev_delay(3, -1);
-  std::vector<int> strikes(3, 0);
-  stat_snapshot(prev);
-  {
-    // its own affinity: the CPUs the placement may use (not the one-L3 mask inherited from the LM thread that started it,
-    // where it would compete with the thread that spins)
-    cpu_set_t allowed;
-    bool ok;
-    {
-      std::lock_guard<std::mutex> lk(g_place_mu);
-      ok = placement_allowed(&allowed);
-    }
-    if (ok)
-      (void)pthread_setaffinity_np(pthread_self(), sizeof(allowed), &allowed);
-  }
-  for (;;)
-  {
-    {
-      std::unique_lock<std::mutex> lm(g_monitor_mu);
-      if (g_monitor_cv.wait_for(lm, std::chrono::milliseconds(250), [] { return g_monitor_stop; }))
-        return;
-    }
-    cur.clear();
-    if (!stat_snapshot(cur))
-      continue;
-    auto busy = [&](int c) {
-      auto a = prev.find(c), b = cur.find(c);
-      if (a == prev.end() || b == cur.end())
-        return 0.0;
-      const double tot = (double)(b->second.first - a->second.first), idle = (double)(b->second.second - a->second.second);
-      return tot >= 4.0 ? 1.0 - idle / tot : 0.0;
-    };
-    CholHelper *hs[3] = {chol_helper(0), chol_helper(1), chol_helper(2)};
-    SepPool *q = g_sep_pool_made.load(std::memory_order_acquire);
-    const int nq = q ? q->n_workers : 0;
-    prev_delay.resize(3 + nq, -1);
-    strikes.resize(3 + nq, 0);
-    auto slot_cpu = [&](int i) -> std::atomic<int> * {
-      return i < 3 ? ((hs[i] && hs[i]->running.load(std::memory_order_acquire)) ? &hs[i]->cpu : nullptr)
-                   : (q->running.load(std::memory_order_acquire) ? &q->cpu[i - 3] : nullptr);
-    };
-    auto slot_ktid = [&](int i) { return i < 3 ? (hs[i] ? hs[i]->ktid.load(std::memory_order_acquire) : 0) : q->ktid[i - 3].load(std::memory_order_acquire); };
-    auto slot_thread = [&](int i) { return i < 3 ? hs[i]->tid : q->tids[i - 3]; };
-    const int near = hs[0] ? hs[0]->near_cpu.load(std::memory_order_acquire) : (q ? q->near_cpu.load(std::memory_order_acquire) : -1);
-    for (int i = 0; i < 3 + nq; ++i)
-    {
-      std::atomic<int> *pc = slot_cpu(i);
-      if (!pc)
-        continue;
-      const int c = pc->load(std::memory_order_acquire), kt = slot_ktid(i);
-      if (c < 0 || kt <= 0)
-        continue;
-      const long long d = read_run_delay_ns(kt);
-      const long long dd = (d >= 0 && prev_delay[i] >= 0) ? d - prev_delay[i] : 0;
-      prev_delay[i] = d;
-      bool crowded = dd > 2000000; // > 2 ms on the run queue in a quarter second: somebody shares the hardware thread
-      double sib_busy = 0.0;
-      for (int sib : placement_core_siblings(c))
-        if (sib != c)
-          sib_busy = std::max(sib_busy, busy(sib));
-      crowded = crowded || sib_busy > 0.3;
-      strikes[i] = crowded ? strikes[i] + 1 : 0;
-      if (strikes[i] < 2 || near < 0)
-        continue;
-      // a quiet core: the thread's own L3 domain first (a pool worker of the second half's domain stays there), then the
-      // caller's domain and node; idle on all hardware threads, not used by another watched thread
-      std::vector<int> cands = placement_l3_domain(c);
-      for (int x : ccx_cores_of(near, true))
-        cands.push_back(x);
-      cpu_set_t allowed;
-      {
-        std::lock_guard<std::mutex> lk(g_place_mu);
-        if (!placement_allowed(&allowed))
-          continue;
-      }
-      const std::vector<int> near_sib = placement_core_siblings(near);
-      int target = -1;
-      for (int cand : cands)
-      {
-        if (cand >= CPU_SETSIZE || !CPU_ISSET(cand, &allowed) || std::find(near_sib.begin(), near_sib.end(), cand) != near_sib.end())
-          continue;
-        bool ok = true;
-        for (int sib : placement_core_siblings(cand))
-        {
-          ok = ok && busy(sib) < 0.1;
-          for (int j = 0; j < 3 + nq && ok; ++j)
-          {
-            std::atomic<int> *pj = slot_cpu(j);
-            ok = !(pj && pj->load(std::memory_order_acquire) == sib);
-          }
-        }
-        if (ok)
-        {
-          target = cand;
-          break;
-        }
-      }
-      if (target < 0)
-        continue;
-      {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        pin_one(slot_thread(i), target);
-        pc->store(target, std::memory_order_release);
-      }
-      g_monitor_moves.fetch_add(1, std::memory_order_relaxed);
-      strikes[i] = 0;
-      if (verbose)
-        fprintf(stderr, "[sage placement] %s %d: cpu %d crowded (run-queue delay %.1f ms, sibling load %.0f %%) -> cpu %d\n",
-                i < 3 ? "helper" : "pool worker", i < 3 ? i : i - 3, c, dd * 1e-6, 100.0 * sib_busy, target);
-    }
-    prev.swap(cur);
-  }
-}
-
-
-// r06: OPT-IN (SAGE_PLACEMENT_MONITOR=1 or sage_placement_monitor(1)) -- a drop-in library does not edit thread affinities
-// from a background thread unless asked to.  Joinable: host_threads_shutdown() stops it.
-static std::atomic<int> g_monitor_wanted{-1}; // -1: ask the environment, 0 / 1: set through the API
-static void placement_monitor_start()
-{
-  int want = g_monitor_wanted.load(std::memory_order_acquire);
-  if (want < 0)
-  {
-    const char *e = getenv("SAGE_PLACEMENT_MONITOR");
-    want = (e && atoi(e) != 0) ? 1 : 0;
-    g_monitor_wanted.store(want, std::memory_order_release);
-  }
-  if (!want || g_monitor_started.load(std::memory_order_acquire))
-    return;
-  bool expect = false;
-  if (!g_monitor_started.compare_exchange_strong(expect, true))
-    return;
-  std::lock_guard<std::mutex> lk(g_threads_mu);
-  host_threads_atexit_once();
-  {
-    std::lock_guard<std::mutex> lm(g_monitor_mu);
-    g_monitor_stop = false;
-  }
-  g_monitor_thread = new std::thread(placement_monitor_loop);
-}
-// (g_threads_mu held)
-static void placement_monitor_stop()
-{
-  if (!g_monitor_thread)
-    return;
-  {
-    std::lock_guard<std::mutex> lm(g_monitor_mu);
-    g_monitor_stop = true;
-  }
-  g_monitor_cv.notify_all();
-  g_monitor_thread->join();
-  delete g_monitor_thread;
-  g_monitor_thread = nullptr;
-  g_monitor_started.store(false, std::memory_order_release);
-}
-void placement_monitor_enable(int on)
-{
-  g_monitor_wanted.store(on ? 1 : 0, std::memory_order_release);
-  if (!on)
-  {
-    std::lock_guard<std::mutex> lk(g_threads_mu);
-    placement_monitor_stop();
-  }
-}
-int placement_monitor_running() { return g_monitor_started.load(std::memory_order_acquire) ? 1 : 0; }
-
-int placement_helper_cpus(int *cpus, int n)
-{
-  int k = 0;
-  for (int idx = 0; idx < 3 && k < n; ++idx)
-    if (CholHelper *h = chol_helper(idx))
-      cpus[k++] = h->cpu.load(std::memory_order_acquire);
-  return k;
-}
-int placement_monitor_moves() { return g_monitor_moves.load(std::memory_order_relaxed); }
-
-// mode 0: everything on the caller's L3 domain A -- A[0] second half, A[1] / A[2] look-ahead stages, pool from A[3] on;
-// mode 1: no look-ahead stages -- A[0] second half, pool from A[1] on;
-// mode 2 (two domains): A[0] look-ahead of the first half, pool workers for the first half's chains from A[1] on;
-//         B[0] second half, B[1] its look-ahead stage, pool workers for the second half's chains from B[2] on
-static void place_helper(CholHelper *h, int cpu, int idx, int mode, const std::vector<int> &B)
-{
-  if (cpu < 0 || (cpu == h->near_cpu.load(std::memory_order_acquire) && mode == h->near_mode.load(std::memory_order_acquire)))
-    return;
-  h->near_cpu.store(cpu, std::memory_order_release);
-  h->near_mode.store(mode, std::memory_order_release);
-  const std::vector<int> &A = ccx_cores_of(cpu, false);
-  int core = -1;
-  if (mode == 2)
-    core = idx == 0 ? (B.size() > 0 ? B[0] : -1) : idx == 1 ? (A.size() > 0 ? A[0] : -1) : (B.size() > 1 ? B[1] : -1);
-  else if ((int)A.size() > idx)
-    core = A[idx];
-  if (core >= 0)
-  {
-    std::lock_guard<std::mutex> pin_lk(g_pin_mu); // (the placement monitor re-pins under the same lock: cpu and affinity stay in step)
-    pin_one(h->tid, core);
-    h->cpu.store(core, std::memory_order_release);
-  }
-  placement_monitor_start(); // (opt-in; takes g_threads_mu -- not under g_pin_mu, which the monitor itself takes)
-}
-
-static void place_pool(SepPool *q, int cpu, int mode, const std::vector<int> &B, int chains_per_half)
-{
-  if (cpu < 0 || (cpu == q->near_cpu.load(std::memory_order_acquire) && mode == q->near_mode.load(std::memory_order_acquire)))
-    return;
-  q->near_cpu.store(cpu, std::memory_order_release);
-  q->near_mode.store(mode, std::memory_order_release);
-  const std::vector<int> &cores = ccx_cores_of(cpu, true); // domain A first, then the rest of the NUMA node
-  const size_t n_ccx = ccx_cores_of(cpu, false).size();
-  std::lock_guard<std::mutex> pin_lk(g_pin_mu);
-  q->dom.assign(q->tids.size(), -1);
-  int n0 = 0, n1 = 0;
-  if (mode == 2)
-  {
-    size_t t = 0;
-    for (size_t c = 1; c < n_ccx && (int)c <= chains_per_half && t < q->tids.size(); ++c, ++t, ++n0)
-    {
-      pin_one(q->tids[t], cores[c]);
-      q->cpu[t].store(cores[c], std::memory_order_release);
-      q->dom[t] = 0;
-    }
-    for (size_t c = 2; c < B.size() && (int)c - 1 <= chains_per_half && t < q->tids.size(); ++c, ++t, ++n1)
-    {
-      pin_one(q->tids[t], B[c]);
-      q->cpu[t].store(B[c], std::memory_order_release);
-      q->dom[t] = 1;
-    }
-    // the rest: the remaining cores of domain A, then of the node (short tasks, pair products, back substitution)
-    for (size_t c = 1 + (size_t)n0; t < q->tids.size() && c < cores.size(); ++c)
-    {
-      if (std::find(B.begin(), B.end(), cores[c]) != B.end())
-        continue;
-      q->cpu[t].store(cores[c], std::memory_order_release);
-      pin_one(q->tids[t++], cores[c]);
-    }
-  }
-  else
-  {
-    const size_t off = mode == 1 ? 1 : 3;
-    for (size_t t = 0; t < q->tids.size() && t + off < cores.size(); ++t)
-    {
-      pin_one(q->tids[t], cores[t + off]);
-      q->cpu[t].store(cores[t + off], std::memory_order_release);
-      q->dom[t] = t + off < n_ccx ? 0 : -1;
-      n0 += q->dom[t] == 0 ? 1 : 0;
-    }
-  }
-  g_domain_threads[0].store(n0, std::memory_order_release);
-  g_domain_threads[1].store(n1, std::memory_order_release);
-  g_two_domains.store(mode == 2, std::memory_order_release);
-}
-
-bool block_chol_arm(bool with_pool, int long_arrow_chains)
-{
-  static const bool no_la_env = sage::env_flag("SAGE_SOLVE_NO_LOOKAHEAD");
-  const int cpu = sched_getcpu();
-  // r05: a loop-closure plan's long arrow-row chains run ~30 % slower on another L3 domain than their half and the separator
-  // then waits for them (config 5: six chains, four cores left next to the two halves and their look-ahead stages: 1.1-1.4 ms).
-  // The two halves do not reference each other: when the chains do not fit domain A, the SECOND half moves to a domain B of
-  // its own with its look-ahead stage and its chains (mode 2) -- every chain then sits next to the half it follows.  Without
-  // a second domain the look-ahead stages' cores go to the chains when that makes them fit (mode 1).
-  int mode = no_la_env ? 1 : 0;
-  std::vector<int> B;
-  const int per_half = (long_arrow_chains + 1) / 2;
-  if (mode == 0 && with_pool && long_arrow_chains > 0 && !sage::env_flag("SAGE_SOLVE_KEEP_LOOKAHEAD"))
-  {
-    const int n_ccx = (int)ccx_cores_of(cpu, false).size(); // cores of domain A without the caller's
-    if (long_arrow_chains > n_ccx - 3)
-    {
-      if (!sage::env_flag("SAGE_SOLVE_ONE_DOMAIN"))
-        B = second_domain_cores(cpu, (size_t)(2 + per_half));
-      if (!B.empty() && n_ccx >= 1 + per_half)
-        mode = 2;
-      else if (long_arrow_chains <= n_ccx - 1)
-        mode = 1;
-    }
-  }
-  const bool no_la = mode == 1;
-  for (int idx = 0; idx < (no_la ? 1 : 3); ++idx)
-  {
-    CholHelper *h = chol_helper(idx);
-    if (h && !h->running.load(std::memory_order_acquire))
-    {
-      std::lock_guard<std::mutex> lk(g_threads_mu);
-      chol_helper_start(h);
-    }
-    if (h && !h->armed.load(std::memory_order_acquire))
-    {
-      place_helper(h, cpu, idx, mode, B);
-      {
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->armed.store(true, std::memory_order_release);
-      }
-      h->cv.notify_one();
-    }
-  }
-  placement_monitor_start(); // (opt-in: two relaxed loads when it is off or already running)
-  if (!with_pool)
-    return no_la;
-  SepPool *q = sep_pool();
-  if (q && !q->running.load(std::memory_order_acquire))
-  {
-    std::lock_guard<std::mutex> lk(g_threads_mu);
-    sep_pool_start(q);
-  }
-  if (q && !q->armed.load(std::memory_order_acquire))
-  {
-    place_pool(q, cpu, mode, B, per_half);
-    {
-      std::lock_guard<std::mutex> lk(q->mu);
-      q->armed.store(true, std::memory_order_release);
-    }
-    q->cv.notify_all();
-  }
-  return no_la;
-}
-
-// Stop and join every host thread this library started (helpers, arrow-row pool, placement monitor).  Safe to call at any
-// time no solve is in flight; the next block_chol_arm() starts them again.  Called by sage_shutdown(), by the last
-// sage_window_destroy and at process exit.
-void host_threads_shutdown()
-{
-  std::lock_guard<std::mutex> lk(g_threads_mu);
-  placement_monitor_stop();
-  for (int idx = 0; idx < 3; ++idx)
-  {
-    CholHelper *h = chol_helper(idx);
-    if (!h || !h->running.load(std::memory_order_acquire))
-      continue;
-    {
-      std::lock_guard<std::mutex> lh(h->mu);
-      h->quit.store(true, std::memory_order_release);
-    }
-    h->cv.notify_all();
-    h->th.join();
-    h->armed.store(false, std::memory_order_release);
-    h->cpu.store(-1, std::memory_order_release);
-    h->running.store(false, std::memory_order_release);
-  }
-  if (SepPool *q = g_sep_pool_made.load(std::memory_order_acquire))
-    if (q->running.load(std::memory_order_acquire))
-    {
-      {
-        std::lock_guard<std::mutex> lq(q->mu);
-        q->quit.store(true, std::memory_order_release);
-      }
-      q->cv.notify_all();
-      for (std::thread &t : q->ths)
-        t.join();
-      q->ths.clear();
-      q->tids.clear();
-      q->armed.store(false, std::memory_order_release);
-      q->running.store(false, std::memory_order_release);
-    }
-}
-int host_threads_running()
-{
-  int n = placement_monitor_running();
-  for (int idx = 0; idx < 3; ++idx)
-    if (CholHelper *h = chol_helper(idx))
-      n += h->running.load(std::memory_order_acquire) ? 1 : 0;
-  if (SepPool *q = g_sep_pool_made.load(std::memory_order_acquire))
-    n += q->running.load(std::memory_order_acquire) ? q->n_workers : 0;
-  return n;
-}
-static void host_threads_atexit_once()
-{
-  static std::once_flag once;
-  std::call_once(once, [] { atexit(host_threads_shutdown); });
+  if (idx < 3)
+    return chol_helper(idx);
+  return make ? sep_pool() : g_sep_pool_made.load(std::memory_order_acquire);
 }
 
 // rows of the separator part whose ranges run far along a half (> 16 columns): the chains the pool's fast threads carry
@@ -3911,7 +3103,7 @@ int block_chol_solve_tr(const BlockEnvelope &E0, double *T, double *X, double *y
   if (helper_has_it)
   {
     while ((rc2 = h->p1_rc.load(std::memory_order_acquire)) == -2)
-      CholHelper::cpu_relax();
+      cpu_relax();
   }
   else
     rc2 = rc == 0 ? block_chol_range(E, T, X, y, 0, E.n1, sep0) : 0;
@@ -3925,7 +3117,7 @@ int block_chol_solve_tr(const BlockEnvelope &E0, double *T, double *X, double *y
       job.abort.store(1, std::memory_order_release);
     sep_work(job); // the caller takes tasks too (all of them when no pool thread is around)
     while (job.doneB.load(std::memory_order_acquire) < (int)job.tb.size())
-      CholHelper::cpu_relax();
+      cpu_relax();
     if (dbg)
       fprintf(stderr, "[sage block chol] arrow tasks (%zu row chains, %zu pair products) done %.0f us after the halves\n",
               job.ta.size(), job.tb.size(), 1e6 * (mono_seconds() - tp[2]));
@@ -3948,14 +3140,14 @@ int block_chol_solve_tr(const BlockEnvelope &E0, double *T, double *X, double *y
     {
       sep_work_c(job, false);
       while (job.doneC.load(std::memory_order_acquire) < (int)job.tc.size())
-        CholHelper::cpu_relax();
+        cpu_relax();
       E.bs_skip_from = sep0;
     }
     if (pool_mine)
     {
       pool->open.store(false, std::memory_order_seq_cst);
       while (pool->active.load(std::memory_order_seq_cst) != 0)
-        CholHelper::cpu_relax();
+        cpu_relax();
       pool->armed.store(false, std::memory_order_release);
       pool->busy.store(false, std::memory_order_release);
     }
@@ -3974,7 +3166,7 @@ int block_chol_solve_tr(const BlockEnvelope &E0, double *T, double *X, double *y
     tp[4] = mono_seconds();
   if (helper_has_it)
     while (!h->p2_done.load(std::memory_order_acquire))
-      CholHelper::cpu_relax();
+      cpu_relax();
   if (dbg)
   {
     tp[5] = mono_seconds();
@@ -4083,9 +3275,13 @@ extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const i
     env.a_first = bp.a_first.data(); env.a_cnt = bp.a_cnt.data(); env.a_off = bp.a_off.data();
     env.n1 = bp.n1; env.n2 = bp.n2;
     env.col_ptr = bp.col_ptr.data(); env.col_rows = bp.col_rows.data();
-    if (bp.n1 > 0)
-      env.no_lookahead = sage::block_chol_arm(sage::block_plan_has_arrow_rows(env), sage::block_plan_long_arrow_chains(env));
-    const int rcf = sage::block_chol_solve_tr(env, T.data(), X.data(), y.data());
+    int rcf;
+    {
+      sage::SolveLease lease; // (arm and solve: no shutdown joins a helper in between)
+      if (bp.n1 > 0)
+        env.no_lookahead = sage::block_chol_arm(sage::block_plan_has_arrow_rows(env), sage::block_plan_long_arrow_chains(env));
+      rcf = sage::block_chol_solve_tr(env, T.data(), X.data(), y.data());
+    }
     if (dbg2)
       fprintf(stderr, "[sage block_solve] fixed-block Cholesky + substitution %.3f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());

@@ -5,8 +5,9 @@
 
 #include <utility>
 #include <atomic>
-#include <sched.h>
 #include <vector>
+
+#include "host_threads.h" // the threads the block solve runs on, block_chol_arm, SolveLease
 
 namespace sage
 {
@@ -43,7 +44,7 @@ struct EnvelopeMatrix
 // ([c][r] = A[i*Bp + r][j*Bp + c]); Bp is 40 or 24.
 // n1/n2 > 0 declare that rows [0,n1) and [n1,n1+n2) do not reference each other (two halves of a window split at a
 // separator, solve_kernels.hip solver_create): they are factorised concurrently on two cores when a helper thread is
-// available (block_chol_arm), otherwise one after the other.
+// armed (block_chol_arm, host_threads.h), otherwise one after the other.
 struct BlockEnvelope
 {
   int K = 0, Bp = 0;
@@ -94,7 +95,8 @@ struct BlockEnvelope
 };
 // In place: T becomes L^T blockwise, X (K*Bp*Bp) receives the inverses of the diagonal factors, y (K*Bp) the
 // right-hand side on entry and the solution on return.  Returns 0, or 1 + the block column of the first non-positive
-// pivot, -1 for an unsupported Bp, -2 when a block's ticket did not arrive within two seconds.
+// pivot, -1 for an unsupported Bp, -2 when a block's ticket did not arrive within two seconds.  A split plan (n1 > 0)
+// hands work to whichever helper / pool is armed, also by another caller: call it under a SolveLease (host_threads.h).
 int block_chol_solve_tr(const BlockEnvelope &env, double *T, double *X, double *y);
 // Partial factorisation for domain decomposition (shard_solve.cpp; storage as above, no A ranges): rows [0, nI) are
 // factorised and forward-substituted; the separator rows [nI, K) receive L_ij for j < nI, their blocks (i, j >= nI) end
@@ -102,27 +104,6 @@ int block_chol_solve_tr(const BlockEnvelope &env, double *T, double *X, double *
 // block_chol_partial_back: x of the rows [0, nI) given x of the separators in y[nI..K).  Returns as block_chol_solve_tr.
 int block_chol_partial(const BlockEnvelope &env, double *T, double *X, double *y, int nI);
 int block_chol_partial_back(const BlockEnvelope &env, double *T, double *X, double *y, int nI);
-// Wake the helper thread ahead of a block_chol_solve_tr call with n1 > 0 (it then spins for the job for a few
-// milliseconds at most); call it when the system is about to be produced, e.g. before waiting on the D2H copy.
-// with_pool: also wake the worker pool that shares the long separator ("arrow") rows of a loop-closure plan.
-// Returns true when the solve should run its halves without look-ahead stages (BlockEnvelope::no_lookahead): a plan whose
-// long arrow-row chains (block_plan_long_arrow_chains) do not fit the cores the look-ahead stages leave free in the caller's
-// L3 domain but do fit with those two cores.
-bool block_chol_arm(bool with_pool = false, int long_arrow_chains = 0);
-// placement of the solve's threads (host_math.cpp "which CPUs the solve's threads may be placed on")
-void placement_set_allowed(const cpu_set_t *allowed); // nullptr: back to the calling thread's affinity mask
-std::vector<int> placement_busy_cpus(int ms);
-std::vector<int> placement_core_siblings(int cpu);
-std::vector<int> placement_l3_domain(int cpu);
-int placement_helper_cpus(int *cpus, int n); // CPUs the solve's (up to three) helper threads are pinned to
-int placement_monitor_moves();              // helpers moved off crowded cores so far (placement monitor)
-// r06: the placement monitor is OPT-IN (SAGE_PLACEMENT_MONITOR=1 or placement_monitor_enable(1)); every thread the solve
-// starts (helpers, arrow-row pool, monitor) is joinable: host_threads_shutdown() stops and joins them, the next
-// block_chol_arm() starts them again.  host_threads_running() = how many are alive.
-void placement_monitor_enable(int on);
-int placement_monitor_running();
-void host_threads_shutdown();
-int host_threads_running();
 int block_plan_long_arrow_chains(const BlockEnvelope &env);
 // true when the separator rows of the plan reach far into the halves (cover keyframes of loop closures): the
 // factorisation then wants the worker pool

@@ -483,6 +483,9 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
     // tickets each one, so the host works on row 0 while the rest is still crossing PCIe (no D2H copy, no stream sync).
     static const bool dbgt = sage::env_flag("SAGE_DEBUG_TIMING");
     hipError_t eh;
+    // held from the arm until block_chol_solve_tr returns, also without a split (the solve may still hand work to helpers
+    // another caller armed): no shutdown joins a helper in between
+    SolveLease lease;
     bool no_lookahead = false;
     if (S->n1 > 0)
     {

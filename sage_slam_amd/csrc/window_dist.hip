@@ -3,65 +3,36 @@
 #include "runtime_internal.h"
 #include <unistd.h>
 
-static bool device_local_cpulist(int device, char *buf, size_t n)
+// CPUs the GPU hangs off (sysfs local_cpulist of its PCI device); empty when unknown
+static std::vector<int> device_local_cpus(int device)
 {
   char bdf[64] = {0};
   if (hipDeviceGetPCIBusId(bdf, (int)sizeof(bdf), device) != hipSuccess)
-    return false;
+    return {};
   for (char *p = bdf; *p; ++p)
     *p = (char)tolower((unsigned char)*p);
   char path[160];
   snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/local_cpulist", bdf);
-  FILE *f = fopen(path, "r");
-  if (!f)
-    return false;
-  buf[0] = 0;
-  const bool got = fgets(buf, (int)n, f) != nullptr;
-  fclose(f);
-  return got;
-}
-
-static std::vector<int> parse_cpulist(const char *buf)
-{
-  std::vector<int> out;
-  for (const char *p = buf; *p;)
-  {
-    char *end;
-    const long a = strtol(p, &end, 10);
-    if (end == p)
-      break;
-    long b = a;
-    p = end;
-    if (*p == '-')
-    {
-      b = strtol(p + 1, &end, 10);
-      p = end;
-    }
-    for (long c = a; c <= b && c < CPU_SETSIZE; ++c)
-      out.push_back((int)c);
-    if (*p == ',')
-      ++p;
-  }
-  return out;
+  return sage::read_cpu_list(path);
 }
 
 // One process per GPU: keep the driving thread on the CPUs the GPU hangs off (its NUMA node: the window solve reads
 // freshly DMA'd pinned memory), and -- when several GPUs share that node -- on its own L3 domain (CCX) of the node: the
-// solve pins its helper / worker threads to the other cores of the caller's CCX (host_math.cpp), so two ranks whose
+// solve pins its helper / worker threads to the other cores of the caller's CCX (host_threads.cpp), so two ranks whose
 // driving threads shared a CCX would share those cores.  Returns the number of CPUs the thread is bound to (0: unchanged).
 extern "C" int sage_bind_thread_to_device(int device)
 {
-  char buf[4096] = {0};
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return SAGE_E_INVALID;
-  if (!device_local_cpulist(device, buf, sizeof(buf)))
+  const std::vector<int> local = device_local_cpus(device);
+  if (local.empty())
     return 0;
   cpu_set_t allowed, want;
   if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0)
     return 0;
   std::vector<int> cpus;
-  for (int c : parse_cpulist(buf))
+  for (int c : local)
     if (CPU_ISSET(c, &allowed))
       cpus.push_back(c);
   if (cpus.empty())
@@ -70,8 +41,7 @@ extern "C" int sage_bind_thread_to_device(int device)
   int on_node = 0, my_pos = 0;
   for (int d = 0; d < ndev; ++d)
   {
-    char other[4096] = {0};
-    if (d == device || (device_local_cpulist(d, other, sizeof(other)) && strcmp(other, buf) == 0))
+    if (d == device || device_local_cpus(d) == local)
     {
       if (d < device)
         ++my_pos;
@@ -87,18 +57,10 @@ extern "C" int sage_bind_thread_to_device(int device)
     {
       if (seen[c])
         continue;
-      char path[160], lb[4096] = {0};
-      snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", c);
-      FILE *f = fopen(path, "r");
       std::vector<int> g;
-      if (f)
-      {
-        if (fgets(lb, sizeof(lb), f))
-          for (int x : parse_cpulist(lb))
-            if (x < CPU_SETSIZE && CPU_ISSET(x, &allowed) && std::find(cpus.begin(), cpus.end(), x) != cpus.end())
-              g.push_back(x);
-        fclose(f);
-      }
+      for (int x : sage::placement_l3_domain(c))
+        if (CPU_ISSET(x, &allowed) && std::find(cpus.begin(), cpus.end(), x) != cpus.end())
+          g.push_back(x);
       if (g.empty())
         g.push_back(c);
       for (int x : g)
@@ -112,7 +74,7 @@ extern "C" int sage_bind_thread_to_device(int device)
     }
   }
   // r05: the box is a slice of a node whose other GPUs run other tenants' jobs on CPUs of the same NUMA node.  Look at the
-  // load (250 ms of /proc/stat), keep to physical cores that are quiet on all their hardware threads, and -- alone on the node
+  // load (250 ms: placement_busy_cpus), keep to physical cores that are quiet on all their hardware threads, and -- alone on the node
   // -- move to the L3 domain with the most of them; the solve's helper threads are placed on quiet cores only
   // (placement_set_allowed: the whole node's quiet CPUs, so that a loop-closure plan still finds its second domain).
   if (!sage::env_flag("SAGE_BIND_NO_PROBE"))
@@ -127,8 +89,8 @@ extern "C" int sage_bind_thread_to_device(int device)
     cpu_set_t quiet_node;
     CPU_ZERO(&quiet_node);
     int n_quiet_node = 0;
-    for (int c : parse_cpulist(buf))
-      if (c < CPU_SETSIZE && CPU_ISSET(c, &allowed) && !noisy[c])
+    for (int c : local)
+      if (CPU_ISSET(c, &allowed) && !noisy[c])
       {
         CPU_SET(c, &quiet_node);
         ++n_quiet_node;

@@ -378,6 +378,77 @@ def test_loop_closure_solve_is_bit_identical_in_every_placement():
     assert len(set(outs.values())) == 1, {k: v[:16] for k, v in outs.items()}
 
 
+_SHUTDOWN_RACE_SNIPPET = _ARROW_SNIPPET.split("ref = np.linalg.solve")[0] + r"""
+import os, threading, time
+def n_tasks():
+    return len(os.listdir("/proc/self/task"))
+def band_plan(K, window, seed):
+    rng = np.random.default_rng(seed)
+    lk = [(j, i) for i in range(K) for j in range(max(0, i - window), i)]
+    m = np.eye(K, dtype=bool)
+    for a, b in lk:
+        m[a, b] = m[b, a] = True
+    Jb = rng.normal(size=(2 * K * B, K * B))
+    H = (Jb.T @ Jb) * np.kron(m, np.ones((B, B))) + 6 * K * B * np.eye(K * B)
+    pk = np.concatenate([np.stack([H[k * B:(k + 1) * B, k * B:(k + 1) * B] for k in range(K)]).reshape(-1),
+                         np.stack([H[a * B:(a + 1) * B, b * B:(b + 1) * B] for a, b in lk]).reshape(-1),
+                         rng.normal(size=K * B), np.zeros(4)])
+    return pk, K, lk
+base = n_tasks()
+plans = [band_plan(36, 3, 5), (packed, K, links)]            # a split window, a loop-closure plan (worker pool)
+refs = [capi.block_solve(p, k, l, B, 1e-4) for p, k, l in plans]
+capi.shutdown()
+stop = threading.Event()
+errs = []
+def solver(i):
+    try:
+        p, k, l = plans[i % 2]
+        while not stop.is_set():
+            if not np.array_equal(capi.block_solve(p, k, l, B, 1e-4), refs[i % 2]):
+                errs.append("result differs")
+    except Exception as e:
+        errs.append(repr(e))
+def churn():
+    try:
+        on = False
+        while not stop.is_set():
+            on = not on
+            capi.placement_monitor(on)
+            time.sleep(0.002)
+            capi.shutdown()
+    except Exception as e:
+        errs.append(repr(e))
+ts = [threading.Thread(target=solver, args=(i,)) for i in range(4)] + [threading.Thread(target=churn)]
+for t in ts:
+    t.start()
+time.sleep(3.0)
+stop.set()
+for t in ts:
+    t.join(timeout=120)
+hung = sum(t.is_alive() for t in ts)
+capi.placement_monitor(False)
+capi.shutdown()
+sys.stdout.write("%d %d %d %d %s" % (hung, capi.host_threads_running(), base, n_tasks(), ";".join(errs[:3]) or "ok"))
+"""
+
+
+def test_shutdown_races_window_less_solves_and_the_monitor():
+    """the solve lease: window-less solves on several threads (a split window, a loop-closure plan with the worker pool)
+    while another thread keeps calling sage_shutdown() and toggling the placement monitor.  A shutdown waits for the solves
+    in flight, so no thread is joined while a solve can pin, arm, post to or wait on it: every result is the single-thread
+    result bit for bit, nothing hangs, and after a final shutdown every thread of the library is joined."""
+    if (os.cpu_count() or 1) < 4:
+        pytest.skip("no helper threads on < 4 CPUs")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SAGE_SOLVE_") and k != "SAGE_PLACEMENT_MONITOR"}
+    r = subprocess.run([sys.executable, "-c", _SHUTDOWN_RACE_SNIPPET], capture_output=True, text=True, env=env,
+                       cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    hung, running, base, tasks, errs = r.stdout.split(maxsplit=4)
+    assert hung == "0", "a solve or the shutdown thread hung"
+    assert errs == "ok", errs
+    assert running == "0" and tasks == base, (running, base, tasks)
+
+
 def test_block_solve_concurrent_callers_share_the_helpers():
     """several host threads factorise split windows at the same time: the helper threads (second half, look-ahead
     stages, worker pool) serve one caller at a time, the others run their halves themselves -- every result is the
