@@ -229,11 +229,12 @@ int sage_factor_hessian_blocks(int type, int CS, const float *AtA_host, const fl
 /* solve (A + damp*diag(A)) x = b, column-pivoted Householder QR in fp32 (camera_tracker.cpp:1182-1183). */
 int sage_damped_solve_qr_f32(const float *A, const float *b, int n, float damp, float *x);
 
-/* damped solve of the block-sparse normal equations in double (envelope Cholesky):
+/* damped solve of the block-sparse normal equations in double (block Cholesky, B <= 40):
  *   (H + diag_add + damp*diag(H + diag_add)) delta = g + g_add
  * packed = [diag K*B*B | link nlinks*B*B (rows = links[2l], cols = links[2l+1], links[2l] < links[2l+1]) | g K*B | 4]
  * (host memory, the layout of sage_window_packed_dev); diag_add / g_add (K*B doubles, may be NULL) carry the
- * diagonal priors.  Returns SAGE_E_NOT_PSD if the damped matrix is not positive definite. */
+ * diagonal priors.  Returns SAGE_E_NOT_PSD if the damped matrix is not positive definite,
+ * SAGE_E_UNSUPPORTED for B > 40. */
 int sage_block_solve(const double *packed_host, int K, int nlinks, const int32_t *links, int B, double damp,
                      const double *diag_add, const double *g_add, double *delta);
 /* diagnostics: how many half-factorisations of split windows ran as two stages (a look-ahead thread + the chain
@@ -589,7 +590,8 @@ int sage_window_set_allreduce(SageWindow *w, SageAllReduceFn fn, void *user);
  * sage_window_packed_dev; diag_add / g_add: the K*B diagonal priors of sage_block_solve, applied by the keyframe's
  * designated owner (the lowest rank touching it).  The separator buffer ends with 8 doubles: [0..3] the rank's error
  * / inlier totals at the linearisation point (tail of the packed buffer), [4..7] free for the caller (prior errors).
- * delta (K*B doubles): entries of the keyframes this rank touches are written, the others left alone. */
+ * delta (K*B doubles): entries of the keyframes this rank touches are written, the others left alone.  B <= 40, as
+ * for sage_block_solve: the plan constructors return SAGE_E_UNSUPPORTED above that. */
 typedef struct SageShardPlan SageShardPlan;
 int sage_shard_plan_create(int K, int nlinks, const int32_t *links, int B, int rank, int world, SageShardPlan **out);
 void sage_shard_plan_destroy(SageShardPlan *p);

@@ -1055,364 +1055,6 @@ extern "C" int sage_track_lm(const SageLmConfig *cfgp, int dof, SageTrackLineari
   return rc;
 }
 
-// ---------------------------------------------------------------- envelope Cholesky (window solve)
-namespace sage
-{
-
-void EnvelopeMatrix::init(int n_, const std::vector<int> &first_)
-{
-  n = n_;
-  first = first_;
-  rowptr.resize(n + 1);
-  size_t off = 0;
-  for (int r = 0; r < n; ++r)
-  {
-    rowptr[r] = off;
-    off += (size_t)(r - first[r] + 1);
-  }
-  rowptr[n] = off;
-  data.assign(off, 0.0);
-}
-
-// dot product with reassociation allowed (SIMD + several accumulators); runtime-dispatched to the widest ISA
-// of the host (the LM step is host-bound on this solve once the kernels are fast).
-__attribute__((target_clones("avx512f", "avx2", "default"))) static double env_dot(const double *a, const double *b,
-                                                                                   int len)
-{
-#pragma clang fp reassociate(on)
-  double acc = 0.0;
-#pragma clang loop vectorize(enable) interleave_count(4)
-  for (int k = 0; k < len; ++k)
-    acc += a[k] * b[k];
-  return acc;
-}
-
-__attribute__((target_clones("avx512f", "avx2", "default"))) static void env_axpy(double *y, const double *x, double a,
-                                                                                  int len)
-{
-#pragma clang loop vectorize(enable) interleave_count(4)
-  for (int k = 0; k < len; ++k)
-    y[k] -= a * x[k];
-}
-
-namespace
-{
-struct SpinBarrier
-{
-  std::atomic<int> count{0};
-  std::atomic<int> gen{0};
-  int n;
-  explicit SpinBarrier(int n_) : n(n_) {}
-  void wait()
-  {
-    if (n <= 1)
-      return;
-    const int g = gen.load(std::memory_order_acquire);
-    if (count.fetch_add(1, std::memory_order_acq_rel) == n - 1)
-    {
-      count.store(0, std::memory_order_relaxed);
-      gen.fetch_add(1, std::memory_order_release);
-    }
-    else
-      while (gen.load(std::memory_order_acquire) == g)
-        __builtin_ia32_pause();
-  }
-};
-
-typedef double v8d __attribute__((vector_size(64), aligned(8)));
-
-// (macros, not functions: a v8d crossing a function boundary would need the AVX-512 ABI in every clone)
-#define SAGE_LOADU(dst, p) __builtin_memcpy(&(dst), (p), sizeof(v8d))
-#define SAGE_HSUM(v) ((((v)[0] + (v)[4]) + ((v)[2] + (v)[6])) + (((v)[1] + (v)[5]) + ((v)[3] + (v)[7])))
-
-// C_i[j] -= dot(A_i[0:len], B_j[0:len]) for i < ni, j < nj with a 4x4 register-blocked micro-kernel, k vectorised
-// (8 doubles: one zmm, two ymm or four xmm depending on the clone the resolver picks).
-__attribute__((target_clones("avx512f", "avx2", "default"))) static void gemm_nt_sub(double *const *C, int coff,
-                                                                                     const double *const *A,
-                                                                                     const double *const *B, int ni,
-                                                                                     int nj, int len_full,
-                                                                                     bool b_lower_tri, int lower_only_row0)
-{
-  // b_lower_tri: row j of B is zero beyond column j (inverse of a Cholesky factor) -> the k range of tile column j0
-  //              stops at j0+4 (rounded up to whole vectors);
-  // lower_only_row0 >= 0: only outputs with j <= lower_only_row0 + i are needed (lower triangle of a diagonal block)
-  for (int i0 = 0; i0 < ni; i0 += 4)
-  {
-    const int mi = ni - i0 < 4 ? ni - i0 : 4;
-    for (int j0 = 0; j0 < nj; j0 += 4)
-    {
-      if (lower_only_row0 >= 0 && j0 > lower_only_row0 + i0 + 3)
-        break;
-      const int mj = nj - j0 < 4 ? nj - j0 : 4;
-      int len = len_full;
-      if (b_lower_tri)
-      {
-        const int need = ((j0 + 4 + 7) / 8) * 8;
-        len = need < len_full ? need : len_full;
-      }
-      const double *a[4], *b[4];
-      for (int t = 0; t < 4; ++t)
-      {
-        a[t] = A[i0 + (t < mi ? t : 0)];
-        b[t] = B[j0 + (t < mj ? t : 0)];
-      }
-      v8d acc[4][4];
-      for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = v8d{0, 0, 0, 0, 0, 0, 0, 0};
-      int k = 0;
-      for (; k + 8 <= len; k += 8)
-      {
-        v8d a0, a1, a2, a3, b0, b1, b2, b3;
-        SAGE_LOADU(a0, a[0] + k); SAGE_LOADU(a1, a[1] + k); SAGE_LOADU(a2, a[2] + k); SAGE_LOADU(a3, a[3] + k);
-        SAGE_LOADU(b0, b[0] + k); SAGE_LOADU(b1, b[1] + k); SAGE_LOADU(b2, b[2] + k); SAGE_LOADU(b3, b[3] + k);
-        acc[0][0] += a0 * b0; acc[0][1] += a0 * b1; acc[0][2] += a0 * b2; acc[0][3] += a0 * b3;
-        acc[1][0] += a1 * b0; acc[1][1] += a1 * b1; acc[1][2] += a1 * b2; acc[1][3] += a1 * b3;
-        acc[2][0] += a2 * b0; acc[2][1] += a2 * b1; acc[2][2] += a2 * b2; acc[2][3] += a2 * b3;
-        acc[3][0] += a3 * b0; acc[3][1] += a3 * b1; acc[3][2] += a3 * b2; acc[3][3] += a3 * b3;
-      }
-      double tail[4][4] = {{0}};
-      for (; k < len; ++k)
-        for (int i = 0; i < 4; ++i)
-          for (int j = 0; j < 4; ++j)
-            tail[i][j] += a[i][k] * b[j][k];
-      for (int i = 0; i < mi; ++i)
-        for (int j = 0; j < mj; ++j)
-          C[i0 + i][coff + j0 + j] -= SAGE_HSUM(acc[i][j]) + tail[i][j];
-    }
-  }
-}
-} // namespace
-
-// In-place Cholesky of an nb x nb diagonal block given by row pointers (row i holds columns 0..i) and the inverse
-// W of its factor (dense nb x nb row-major, lower triangular).  One multiversioned function so the short inner loops
-// are compiled for the widest host ISA without a per-call dispatch.  Returns false if not positive definite.
-__attribute__((target_clones("avx512f", "avx2", "default"))) static bool diag_factor(double *const *L, int nb, double *W,
-                                                                                 double *col)
-{
-  for (int j = 0; j < nb; ++j)
-  {
-    const double d = L[j][j];
-    if (!(d > 0.0))
-      return false;
-    const double sj = std::sqrt(d), inv = 1.0 / sj;
-    L[j][j] = sj;
-    for (int i = j + 1; i < nb; ++i)
-    {
-      L[i][j] *= inv;
-      col[i] = L[i][j];
-    }
-    for (int i = j + 1; i < nb; ++i) // right-looking update of the trailing rows, contiguous in k
-    {
-      const double lij = col[i];
-      double *Li = L[i];
-#pragma clang loop vectorize(enable)
-      for (int k = j + 1; k <= i; ++k)
-        Li[k] -= lij * col[k];
-    }
-  }
-  for (int i = 0; i < nb; ++i) // W = inv(L): row i = (e_i - sum_{k<i} L[i][k] W[k][:]) / L[i][i]
-  {
-    double *Wi = W + (size_t)i * nb;
-    for (int j = 0; j < nb; ++j)
-      Wi[j] = 0.0;
-    Wi[i] = 1.0;
-    for (int k = 0; k < i; ++k)
-    {
-      const double lik = L[i][k];
-      const double *Wk = W + (size_t)k * nb;
-#pragma clang loop vectorize(enable)
-      for (int j = 0; j <= k; ++j)
-        Wi[j] -= lik * Wk[j];
-    }
-    const double inv = 1.0 / L[i][i];
-#pragma clang loop vectorize(enable)
-    for (int j = 0; j <= i; ++j)
-      Wi[j] *= inv;
-  }
-  return true;
-}
-
-// Blocked left-looking Cholesky on the row-contiguous envelope.  With block > 1 the rows come in aligned groups
-// of `block` rows sharing `first` (the window's keyframe blocks); then for block row I and block column J < I
-//     S    = A_IJ - L_I[:, k0:cJ] * L_J[:, k0:cJ]^T          (GEMM, k contiguous in both operands)
-//     L_IJ = S * inv(L_JJ)^T                                   (GEMM against the cached inverse of the diagonal factor)
-// and the diagonal block is a dense block x block Cholesky of A_II - L_I[:, f:r0] L_I[:, f:r0]^T.
-// The GEMMs are split over `threads` by rows of the block row.
-bool EnvelopeMatrix::cholesky_inplace(int block, int threads)
-{
-  bool uniform = block > 1 && n % block == 0;
-  if (uniform)
-    for (int r = 0; r < n && uniform; ++r)
-      uniform = first[r] == first[(r / block) * block] && first[r] % block == 0;
-  if (!uniform)
-  {
-    // generic envelope: plain row-wise left-looking factorisation
-    for (int r = 0; r < n; ++r)
-    {
-      double *Lr = &data[rowptr[r]];
-      const int fr = first[r];
-      for (int c = fr; c <= r; ++c)
-      {
-        const double *Lc = &data[rowptr[c]];
-        const int fc = first[c];
-        const int k0 = fr > fc ? fr : fc;
-        const double s = Lr[c - fr] - env_dot(Lr + (k0 - fr), Lc + (k0 - fc), c - k0);
-        if (c < r)
-          Lr[c - fr] = s / Lc[c - fc];
-        else
-        {
-          if (!(s > 0.0))
-            return false;
-          Lr[c - fr] = std::sqrt(s);
-        }
-      }
-    }
-    return true;
-  }
-  const int nb = block, NB = n / nb;
-  threads = std::max(1, std::min(threads, nb / 4));
-  if (nb < 16)
-    threads = 1;
-  std::vector<double> winv((size_t)NB * nb * nb, 0.0); // inverse of every diagonal factor block (lower triangular)
-  std::atomic<bool> ok{true};
-  SpinBarrier bar(threads);
-  double t_gemm1 = 0, t_gemm2 = 0, t_diag = 0, t_scalar = 0;
-  auto tk = [] { return std::chrono::steady_clock::now(); };
-  auto dtm = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  auto worker = [&](int tid) {
-    std::vector<double> tmp((size_t)nb * nb);
-    std::vector<double *> crow(nb);
-    std::vector<const double *> arow(nb), brow(nb), trow(nb);
-    // this thread's slice of the block row
-    const int per = (nb + threads - 1) / threads;
-    const int i_lo = std::min(nb, tid * per), i_hi = std::min(nb, i_lo + per), ni = i_hi - i_lo;
-    for (int I = 0; I < NB; ++I)
-    {
-      const int r0 = I * nb, f = first[r0];
-      for (int J = f / nb; J < I; ++J)
-      {
-        const int c0 = J * nb, fJ = first[c0], k0 = f > fJ ? f : fJ, len = c0 - k0;
-        if (ni > 0)
-        {
-          for (int i = 0; i < ni; ++i)
-          {
-            double *row = &data[rowptr[r0 + i_lo + i]];
-            crow[i] = row;          // column c is at row[c - f]
-            arow[i] = row + (k0 - f);
-          }
-          for (int j = 0; j < nb; ++j)
-            brow[j] = &data[rowptr[c0 + j]] + (k0 - fJ);
-          auto q0 = tk();
-          gemm_nt_sub(crow.data(), c0 - f, arow.data(), brow.data(), ni, nb, len, false, -1);
-          if (tid == 0) t_gemm1 += dtm(q0, tk());
-          auto q1 = tk();
-          // L_IJ = S * Winv_J^T : copy S, clear the destination, accumulate with the (negated) GEMM
-          const double *W = &winv[(size_t)J * nb * nb];
-          for (int i = 0; i < ni; ++i)
-          {
-            double *dst = crow[i] + (c0 - f);
-            for (int j = 0; j < nb; ++j)
-            {
-              tmp[(size_t)i * nb + j] = -dst[j];
-              dst[j] = 0.0;
-            }
-            trow[i] = &tmp[(size_t)i * nb];
-          }
-          for (int j = 0; j < nb; ++j)
-            brow[j] = W + (size_t)j * nb;
-          gemm_nt_sub(crow.data(), c0 - f, trow.data(), brow.data(), ni, nb, nb, true, -1);
-          if (tid == 0) t_gemm2 += dtm(q1, tk());
-        }
-        // no barrier needed between block columns: thread t only touches its own rows of block row I,
-        // and block rows < I are final
-      }
-      // diagonal block: subtract the left part (own rows x all rows of the block -> needs everyone's left parts)
-      bar.wait();
-      auto q2 = tk();
-      if (ni > 0)
-      {
-        for (int i = 0; i < ni; ++i)
-        {
-          double *row = &data[rowptr[r0 + i_lo + i]];
-          crow[i] = row;
-          arow[i] = row;
-        }
-        for (int j = 0; j < nb; ++j)
-          brow[j] = &data[rowptr[r0 + j]];
-        // only columns j <= i are stored: accumulate the full ni x nb slice into tmp, then fold the lower part back
-        for (int i = 0; i < ni; ++i)
-        {
-          for (int j = 0; j < nb; ++j)
-            tmp[(size_t)i * nb + j] = 0.0;
-          crow[i] = &tmp[(size_t)i * nb];
-        }
-        gemm_nt_sub(crow.data(), 0, arow.data(), brow.data(), ni, std::min(nb, i_hi), r0 - f, false, i_lo);
-        for (int i = 0; i < ni; ++i)
-        {
-          double *dst = &data[rowptr[r0 + i_lo + i]] + (r0 - f);
-          for (int j = 0; j <= i_lo + i; ++j)
-            dst[j] += tmp[(size_t)i * nb + j];
-        }
-      }
-      bar.wait();
-      if (tid == 0) t_diag += dtm(q2, tk());
-      auto q3 = tk();
-      if (tid == 0)
-      {
-        // dense Cholesky of the nb x nb diagonal block (lower part, in place) + the inverse of its factor
-        std::vector<double *> drow(nb);
-        std::vector<double> colbuf(nb);
-        for (int i = 0; i < nb; ++i)
-          drow[i] = &data[rowptr[r0 + i]] + (r0 - f);
-        if (!diag_factor(drow.data(), nb, &winv[(size_t)I * nb * nb], colbuf.data()))
-          ok.store(false);
-      }
-      bar.wait();
-      if (tid == 0) t_scalar += dtm(q3, tk());
-      if (!ok.load())
-        return;
-    }
-  };
-  if (threads == 1)
-    worker(0);
-  else
-  {
-    std::vector<std::thread> pool;
-    for (int t = 1; t < threads; ++t)
-      pool.emplace_back(worker, t);
-    worker(0);
-    for (auto &th : pool)
-      th.join();
-  }
-  if (sage::env_flag("SAGE_DEBUG_TIMING"))
-    fprintf(stderr, "[sage cholesky] gemm(S) %.3f gemm(trsm) %.3f diag-gemm %.3f diag-chol+inv %.3f ms\n", t_gemm1,
-            t_gemm2, t_diag, t_scalar);
-  return ok.load();
-}
-
-void EnvelopeMatrix::solve_inplace(std::vector<double> &b) const
-{
-  // L y = b
-  for (int r = 0; r < n; ++r)
-  {
-    const double *Lr = &data[rowptr[r]];
-    const int fr = first[r];
-    b[r] = (b[r] - env_dot(Lr, &b[fr], r - fr)) / Lr[r - fr];
-  }
-  // L^T x = y
-  for (int r = n - 1; r >= 0; --r)
-  {
-    const double *Lr = &data[rowptr[r]];
-    const int fr = first[r];
-    const double x = b[r] / Lr[r - fr];
-    b[r] = x;
-    env_axpy(&b[fr], Lr, x, r - fr);
-  }
-}
-
-} // namespace sage
-
 // ------------------------------------------------------------------------------------------------
 // Fixed-block-size Cholesky on transposed block storage (the window solve's host leg).
 //
@@ -1421,12 +1063,16 @@ void EnvelopeMatrix::solve_inplace(std::vector<double> &b) const
 //   C_ij^T[c][:]  -= sum_k sum_t T_jk[t][c] * T_ik[t][:]         (trailing update)
 //   T_ij[c][:]     = sum_{t<=c} X_j[t][c] * C_ij^T[t][:]          (L_ij = C_ij L_jj^-T)
 // so the micro-kernel is 4 output rows x NV vectors of accumulators, NV loads + 4 broadcasts + 4*NV FMAs per step,
-// no horizontal sums (the envelope code above pays one per output).
+// no horizontal sums.
 // ------------------------------------------------------------------------------------------------
 namespace sage
 {
 namespace
 {
+typedef double v8d __attribute__((vector_size(64), aligned(8)));
+
+// (macros, not functions: a v8d crossing a function boundary would need the AVX-512 ABI in every clone)
+#define SAGE_LOADU(dst, p) __builtin_memcpy(&(dst), (p), sizeof(v8d))
 #define SAGE_STOREU(p, v) __builtin_memcpy((p), &(v), sizeof(v8d))
 
 // The blocks of a row arrive by DMA straight into DRAM (no cache allocation on this platform): a row's first touch of
@@ -3191,154 +2837,95 @@ extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const i
 {
   if (!packed || K < 1 || B < 1 || nlinks < 0 || (nlinks > 0 && !links) || !delta)
     return SAGE_E_INVALID;
-  // the factorisation works on blocks padded to a multiple of 8 rows (identity on the padding) so that every
-  // GEMM inner length is a whole number of 8-double vectors
-  const int Bp = (B + 7) / 8 * 8;
-  const int BB = B * B, n = K * Bp, n_out = K * B;
+  // the factorisation works on blocks padded to Bp rows (identity on the padding): the fixed-block kernels' sizes
+  const int Bp = sage::padded_block(B);
+  if (Bp == 0)
+    return SAGE_E_UNSUPPORTED;
+  const int BB = B * B, BBp = Bp * Bp;
   const double *diag = packed;
   const double *lnk = diag + (size_t)K * BB;
   const double *g = lnk + (size_t)nlinks * BB;
-  // envelope: first non-zero block column of each block row
-  std::vector<int> first_blk(K);
-  for (int k = 0; k < K; ++k)
-    first_blk[k] = k;
+  std::vector<std::pair<int, int>> lk(nlinks);
   for (int l = 0; l < nlinks; ++l)
   {
     const int a = links[2 * l], b = links[2 * l + 1];
     if (a < 0 || b <= a || b >= K)
       return SAGE_E_INVALID;
-    first_blk[b] = std::min(first_blk[b], a);
+    lk[l] = {a, b};
   }
-  if (Bp == 40 || Bp == 24)
+  // transposed-block storage (the one the window engine runs on the device-scattered storage), with the same
+  // elimination order and two-core split
+  sage::BlockPlan bp;
   {
-    // fixed-size transposed-block path (the one the window engine runs on the device-scattered storage), with the
-    // same elimination order and two-core split
-    const int BBp = Bp * Bp;
-    std::vector<std::pair<int, int>> lk(nlinks);
-    for (int l = 0; l < nlinks; ++l)
-      lk[l] = {links[2 * l], links[2 * l + 1]};
-    sage::BlockPlan bp;
+    const int rcp = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
+    if (rcp == SAGE_E_UNSUPPORTED) // duplicate links accumulate on this path: plan without them
     {
-      const int rcp = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
-      if (rcp == SAGE_E_UNSUPPORTED) // duplicate links accumulate on this path: plan without them
-      {
-        std::sort(lk.begin(), lk.end());
-        lk.erase(std::unique(lk.begin(), lk.end()), lk.end());
-        const int rcq = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
-        if (rcq != SAGE_OK)
-          return rcq;
-      }
-      else if (rcp != SAGE_OK)
-        return rcp;
+      std::sort(lk.begin(), lk.end());
+      lk.erase(std::unique(lk.begin(), lk.end()), lk.end());
+      const int rcq = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
+      if (rcq != SAGE_OK)
+        return rcq;
     }
-    const int nblk = bp.nblk;
-    auto bidx = [&](int i, int j) {
-      return j < bp.row_first[i] ? bp.a_off[i] + j - bp.a_first[i] : bp.row_off[i] + j - bp.row_first[i];
-    };
-    std::vector<double> T((size_t)nblk * BBp, 0.0), X((size_t)K * BBp), y((size_t)K * Bp, 0.0);
-    for (int q = 0; q < K; ++q)
-    {
-      const int k = bp.perm[q];
-      double *D = T.data() + (size_t)bidx(q, q) * BBp;
-      for (int i = 0; i < Bp; ++i)
-        for (int j = 0; j < Bp; ++j)
-        {
-          double v = 0.0;
-          if (i < B && j < B)
-          {
-            v = 0.5 * (diag[(size_t)k * BB + i * B + j] + diag[(size_t)k * BB + j * B + i]);
-            if (i == j)
-              v = (v + (diag_add ? diag_add[k * B + i] : 0.0)) * (1.0 + damp);
-          }
-          else if (i == j)
-            v = 1.0 + damp;
-          D[i * Bp + j] = v;
-        }
-      for (int i = 0; i < B; ++i)
-        y[(size_t)q * Bp + i] = g[(size_t)k * B + i] + (g_add ? g_add[k * B + i] : 0.0);
-    }
-    for (int l = 0; l < nlinks; ++l)
-    {
-      const int a = links[2 * l], b = links[2 * l + 1];
-      const int qi = std::max(bp.pos[a], bp.pos[b]), qj = std::min(bp.pos[a], bp.pos[b]);
-      // stored block is [c in column keyframe][r in row keyframe]; the packed link block is [r in a][c in b]
-      double *D = T.data() + (size_t)bidx(qi, qj) * BBp;
-      const bool row_is_a = bp.perm[qi] == a;
-      for (int i = 0; i < B; ++i)
-        for (int j = 0; j < B; ++j)
-          D[row_is_a ? j * Bp + i : i * Bp + j] += lnk[(size_t)l * BB + i * B + j];
-    }
-    static const bool dbg2 = sage::env_flag("SAGE_DEBUG_TIMING");
-    const auto t0 = std::chrono::steady_clock::now();
-    sage::BlockEnvelope env;
-    env.K = K; env.Bp = Bp; env.row_first = bp.row_first.data(); env.row_off = bp.row_off.data();
-    env.a_first = bp.a_first.data(); env.a_cnt = bp.a_cnt.data(); env.a_off = bp.a_off.data();
-    env.n1 = bp.n1; env.n2 = bp.n2;
-    env.col_ptr = bp.col_ptr.data(); env.col_rows = bp.col_rows.data();
-    int rcf;
-    {
-      sage::SolveLease lease; // (arm and solve: no shutdown joins a helper in between)
-      if (bp.n1 > 0)
-        env.no_lookahead = sage::block_chol_arm(sage::block_plan_has_arrow_rows(env), sage::block_plan_long_arrow_chains(env));
-      rcf = sage::block_chol_solve_tr(env, T.data(), X.data(), y.data());
-    }
-    if (dbg2)
-      fprintf(stderr, "[sage block_solve] fixed-block Cholesky + substitution %.3f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    if (rcf != 0)
-      return SAGE_E_NOT_PSD;
-    for (int k = 0; k < K; ++k)
-      std::memcpy(delta + (size_t)k * B, y.data() + (size_t)bp.pos[k] * Bp, sizeof(double) * B);
-    return SAGE_OK;
+    else if (rcp != SAGE_OK)
+      return rcp;
   }
-  std::vector<int> first(n);
-  for (int k = 0; k < K; ++k)
+  const int nblk = bp.nblk;
+  auto bidx = [&](int i, int j) {
+    return j < bp.row_first[i] ? bp.a_off[i] + j - bp.a_first[i] : bp.row_off[i] + j - bp.row_first[i];
+  };
+  std::vector<double> T((size_t)nblk * BBp, 0.0), X((size_t)K * BBp), y((size_t)K * Bp, 0.0);
+  for (int q = 0; q < K; ++q)
+  {
+    const int k = bp.perm[q];
+    double *D = T.data() + (size_t)bidx(q, q) * BBp;
     for (int i = 0; i < Bp; ++i)
-      first[k * Bp + i] = first_blk[k] * Bp;
-  static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
-  auto tnow = [] { return std::chrono::steady_clock::now(); };
-  auto t_a = tnow();
-  sage::EnvelopeMatrix M;
-  M.init(n, first);
-  std::vector<double> rhs(n, 0.0);
-  for (int k = 0; k < K; ++k)
-  {
+      for (int j = 0; j < Bp; ++j)
+      {
+        double v = 0.0;
+        if (i < B && j < B)
+        {
+          v = 0.5 * (diag[(size_t)k * BB + i * B + j] + diag[(size_t)k * BB + j * B + i]);
+          if (i == j)
+            v = (v + (diag_add ? diag_add[k * B + i] : 0.0)) * (1.0 + damp);
+        }
+        else if (i == j)
+          v = 1.0 + damp;
+        D[i * Bp + j] = v;
+      }
     for (int i = 0; i < B; ++i)
-    {
-      for (int j = 0; j <= i; ++j)
-        M.at(k * Bp + i, k * Bp + j) = 0.5 * (diag[(size_t)k * BB + i * B + j] + diag[(size_t)k * BB + j * B + i]);
-      rhs[k * Bp + i] = g[(size_t)k * B + i] + (g_add ? g_add[k * B + i] : 0.0);
-      if (diag_add)
-        M.at(k * Bp + i, k * Bp + i) += diag_add[k * B + i];
-    }
-    for (int i = B; i < Bp; ++i)
-      M.at(k * Bp + i, k * Bp + i) = 1.0; // padding rows: identity, rhs 0 -> delta 0
+      y[(size_t)q * Bp + i] = g[(size_t)k * B + i] + (g_add ? g_add[k * B + i] : 0.0);
   }
   for (int l = 0; l < nlinks; ++l)
   {
-    const int a = links[2 * l], b = links[2 * l + 1]; // block (a,b) -> lower-triangle rows of b
+    const int a = links[2 * l], b = links[2 * l + 1];
+    const int qi = std::max(bp.pos[a], bp.pos[b]), qj = std::min(bp.pos[a], bp.pos[b]);
+    // stored block is [c in column keyframe][r in row keyframe]; the packed link block is [r in a][c in b]
+    double *D = T.data() + (size_t)bidx(qi, qj) * BBp;
+    const bool row_is_a = bp.perm[qi] == a;
     for (int i = 0; i < B; ++i)
       for (int j = 0; j < B; ++j)
-        M.at(b * Bp + j, a * Bp + i) += lnk[(size_t)l * BB + i * B + j];
+        D[row_is_a ? j * Bp + i : i * Bp + j] += lnk[(size_t)l * BB + i * B + j];
   }
-  for (int r = 0; r < n; ++r) // LM damping H + damp*diag(H) (camera_tracker.cpp:1182)
-    M.at(r, r) *= (1.0 + damp);
-  static const int n_threads = getenv("SAGE_SOLVE_THREADS") ? std::max(1, atoi(getenv("SAGE_SOLVE_THREADS")))
-                                                            : 1; // EPYC 9575F: the thread split loses at n ~ 2.5k
-  auto t_b = tnow();
-  if (!M.cholesky_inplace(Bp, n_threads))
-    return SAGE_E_NOT_PSD;
-  auto t_c = tnow();
-  M.solve_inplace(rhs);
-  if (dbg)
+  static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
+  const auto t0 = std::chrono::steady_clock::now();
+  sage::BlockEnvelope env;
+  env.K = K; env.Bp = Bp; env.row_first = bp.row_first.data(); env.row_off = bp.row_off.data();
+  env.a_first = bp.a_first.data(); env.a_cnt = bp.a_cnt.data(); env.a_off = bp.a_off.data();
+  env.n1 = bp.n1; env.n2 = bp.n2;
+  env.col_ptr = bp.col_ptr.data(); env.col_rows = bp.col_rows.data();
+  int rcf;
   {
-    auto t_d = tnow();
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    fprintf(stderr, "[sage block_solve] n %d threads %d: assemble %.3f cholesky %.3f substitution %.3f ms\n", n,
-            n_threads, ms(t_a, t_b), ms(t_b, t_c), ms(t_c, t_d));
+    sage::SolveLease lease; // (arm and solve: no shutdown joins a helper in between)
+    if (bp.n1 > 0)
+      env.no_lookahead = sage::block_chol_arm(sage::block_plan_has_arrow_rows(env), sage::block_plan_long_arrow_chains(env));
+    rcf = sage::block_chol_solve_tr(env, T.data(), X.data(), y.data());
   }
+  if (dbg)
+    fprintf(stderr, "[sage block_solve] fixed-block Cholesky + substitution %.3f ms\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  if (rcf != 0)
+    return SAGE_E_NOT_PSD;
   for (int k = 0; k < K; ++k)
-    std::memcpy(delta + (size_t)k * B, rhs.data() + (size_t)k * Bp, sizeof(double) * B);
-  (void)n_out;
+    std::memcpy(delta + (size_t)k * B, y.data() + (size_t)bp.pos[k] * Bp, sizeof(double) * B);
   return SAGE_OK;
 }

@@ -21,21 +21,9 @@ inline bool env_flag(const char *name)
 void sym_eig(std::vector<double> &A, int n, std::vector<double> &w, std::vector<double> &V);
 void rotation_to_angle_axis_as_reference(const float *R, float eps, float *out);
 
-// Envelope (skyline) Cholesky of a symmetric positive definite matrix given by its lower triangle:
-// row r stores columns first[r]..r contiguously at data[rowptr[r]...].
-struct EnvelopeMatrix
-{
-  int n = 0;
-  std::vector<int> first;      // first stored column of each row
-  std::vector<size_t> rowptr;  // offset of column first[r] in data
-  std::vector<double> data;
-  void init(int n_, const std::vector<int> &first_);
-  inline double &at(int r, int c) { return data[rowptr[r] + (size_t)(c - first[r])]; } // first[r] <= c <= r
-  // returns false if not positive definite.  block > 1: rows come in aligned groups of `block` rows that share
-  // `first` (the window's keyframe blocks) -> the rows of a group are factorised in parallel on `threads` threads.
-  bool cholesky_inplace(int block = 1, int threads = 1);
-  void solve_inplace(std::vector<double> &b) const; // after cholesky_inplace: b <- A^-1 b
-};
+// Padded block size of the fixed-block Cholesky for B unknowns per keyframe: the B x B blocks are padded with identity
+// rows to 24 or 40.  0: B outside 1..40, no block kernel for it.
+inline int padded_block(int B) { return B < 1 ? 0 : B <= 24 ? 24 : B <= 40 ? 40 : 0; }
 
 // Block-envelope Cholesky solve on the storage the device scatter kernel produces (solve_kernels.hip).  Row i keeps
 // the blocks of columns B = [row_first[i], i] at T + (row_off[i] + j - row_first[i]) * Bp*Bp and, optionally, a

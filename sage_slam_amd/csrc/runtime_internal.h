@@ -242,7 +242,6 @@ struct SageWindow
   int n_depth = 0;                      // keyframes this rank's edges touch (= entries of depth_items)
   int dpt_set = -1;                     // variable set the depth maps currently hold (-1: none) ...
   bool dgrad_valid = false;             // ... and whether their gradients are up to date as well
-  DeviceSolver *last_solver = nullptr;   // the solver whose pinned mirror holds the pending candidate
   SageAllReduceFn allreduce = nullptr;  // sharded windows: caller-provided sum all-reduce (see sage_ba.h)
   void *allreduce_user = nullptr;
   void *rccl_hook = nullptr;            // sage_window_use_rccl: owned {comm, stream} record behind `allreduce`
@@ -275,7 +274,7 @@ struct SageWindow
   int n_work_p = 0, n_work_g = 0, tpb_p = 1, tpb_g = 1;
   std::vector<double> host_packed;
   std::vector<double> delta;
-  // device solver (solve_kernels.hip); nullptr -> host envelope Cholesky (envelope wider than the LDS panel).  After a device solve the candidate's host mirrors are refreshed lazily (sync_candidate).
+  // device solver (solve_kernels.hip); nullptr -> duplicate links: host block solve (sage_block_solve).  After a device solve the candidate's host mirrors are refreshed lazily (sync_candidate).
   sage::DeviceSolver *solver = nullptr;
   bool cand_pending = false;
   double residuals_per_lin = 0, bytes_per_lin = 0;

@@ -11,6 +11,11 @@
 //   every rank: (sum_r C^(r)) d_S = sum_r c^(r)   (block-envelope Cholesky over the separators, identical on all ranks)
 //   rank r:   d_I = A_II^-1 (b_I - A_IS d_S)
 //
+// Both steps run on the fixed-block Cholesky of the window solve (host_math.cpp, blocks padded to 24 / 40, so B <= 40):
+// the local system keeps the interior keyframes first and the rank's separators last, block_chol_partial factorises
+// the interior rows and leaves C^(r) / c^(r) in the separator rows, block_chol_partial_back substitutes d_I; the
+// separator system is a packed system for sage_block_solve.
+//
 // Payload at K = 64, 8 ranks, B = 39: 96 blocks + rhs = 1.2 MB instead of the 3.0 MB packed system; per-rank
 // factorisation: 8 interior keyframes + the 21-keyframe separator system instead of all 64 keyframes.
 // The result equals the single-rank solve of the summed system to rounding (tests/test_shard_schur.py, world 2/4/8;
@@ -45,17 +50,11 @@ struct SageShardPlan
   std::vector<int32_t> sep_pairs;  // flat (i, j), i < j, in block order: the "links" of the separator system
   int n_pair_blocks = 0;
   size_t sep_doubles = 0;
-  // state between eliminate() and solve()
-  sage::EnvelopeMatrix LI;         // Cholesky factor of the damped interior matrix
-  std::vector<double> LS;          // [nS_local*B][nI*B]  rows of L^-1 A_IS^T  (i.e. A_SI L^-T)
-  std::vector<double> y;           // L^-1 b_I
-  std::vector<int> ls_first;       // first non-zero column of every row of LS
   std::vector<int> int_pos;        // keyframe -> position among interior, or -1
-  bool have_factor = false;
+  bool have_factor = false;        // eliminate() has left a factor for solve()
   bool assembled = false;          // domains of one assembled system (sage_shard_plan_create_domains)
-  // fixed-block path (padded block size 40 / 24, the AVX-512 kernels of the window solve): local block system with the
-  // interior keyframes at positions [0, nI) (elimination order) and this rank's separators at [nI, nI + nS)
-  bool fast = false;
+  // local block system on the fixed-block kernels of the window solve (block size padded to Bp = 24 / 40): the interior
+  // keyframes at positions [0, nI) (elimination order) and this rank's separators at [nI, nI + nS)
   int Bp = 0, nloc = 0, nblk = 0;
   std::vector<int32_t> row_first, row_off;
   std::vector<double> T, X, yv;
@@ -63,23 +62,6 @@ struct SageShardPlan
 
 namespace
 {
-__attribute__((target_clones("avx512f", "avx2", "default"))) double sdot(const double *a, const double *b, int len)
-{
-#pragma clang fp reassociate(on)
-  double acc = 0.0;
-#pragma clang loop vectorize(enable) interleave_count(4)
-  for (int k = 0; k < len; ++k)
-    acc += a[k] * b[k];
-  return acc;
-}
-
-__attribute__((target_clones("avx512f", "avx2", "default"))) void saxpy(double *y, const double *x, double a, int len)
-{
-#pragma clang loop vectorize(enable) interleave_count(4)
-  for (int k = 0; k < len; ++k)
-    y[k] -= a * x[k];
-}
-
 inline int touch_rank_range(const SageShardPlan &p, int link)
 {
   // rank owning `link` (ranges are contiguous and ordered)
@@ -93,6 +75,9 @@ inline int touch_rank_range(const SageShardPlan &p, int link)
 static int finish_plan(SageShardPlan *p, const std::vector<int> &link_dom, const std::vector<char> &is_sep)
 {
   const int K = p->K, world = p->world, rank = p->rank;
+  p->Bp = sage::padded_block(p->B); // the fixed-block kernels' padded block size
+  if (p->Bp == 0)
+    return SAGE_E_UNSUPPORTED;
   // touch[r][k]: domain r couples keyframe k through its interior (Schur fill: all separators a domain touches become
   // mutually coupled).  Assembled mode: a link between two separators is just that one block, not a reason for fill.
   std::vector<std::vector<char>> touch(world, std::vector<char>(K, 0));
@@ -165,42 +150,37 @@ static int finish_plan(SageShardPlan *p, const std::vector<int> &link_dom, const
     p->pair_block.emplace(std::make_pair(s, s), s);
   p->n_pair_blocks = nb;
   p->sep_doubles = (size_t)nb * p->B * p->B + p->sep_all.size() * (size_t)p->B + 8;
-  // ---- block envelope of the local system for the fixed-block path
-  p->Bp = (p->B + 7) / 8 * 8;
-  p->fast = (p->Bp == 40 || p->Bp == 24);
-  if (p->fast)
+  // ---- block envelope of the local system
+  const int nI = (int)p->interior.size(), nS = (int)p->sep_local.size();
+  p->nloc = nI + nS;
+  std::vector<int> lpos(K, -1);
+  for (int i = 0; i < nI; ++i)
+    lpos[p->interior[i]] = i;
+  for (int i = 0; i < nS; ++i)
+    lpos[p->sep_all[p->sep_local[i]]] = nI + i;
+  p->row_first.resize(p->nloc);
+  for (int q = 0; q < p->nloc; ++q)
+    p->row_first[q] = q;
+  for (int l : p->local_links)
   {
-    const int nI = (int)p->interior.size(), nS = (int)p->sep_local.size();
-    p->nloc = nI + nS;
-    std::vector<int> lpos(K, -1);
-    for (int i = 0; i < nI; ++i)
-      lpos[p->interior[i]] = i;
-    for (int i = 0; i < nS; ++i)
-      lpos[p->sep_all[p->sep_local[i]]] = nI + i;
-    p->row_first.resize(p->nloc);
-    for (int q = 0; q < p->nloc; ++q)
-      p->row_first[q] = q;
-    for (int l : p->local_links)
-    {
-      const int a = lpos[p->links[l].first], b = lpos[p->links[l].second];
-      if (a < 0 || b < 0)
-        return SAGE_E_STATE;
-      p->row_first[std::max(a, b)] = std::min(p->row_first[std::max(a, b)], (int32_t)std::min(a, b));
-    }
-    // a separator row receives fill from every earlier separator that shares interior columns with it: keep the
-    // separator rows' envelopes contiguous down to the first interior column any of them reaches
-    p->row_off.resize(p->nloc);
-    int nb2 = 0;
-    for (int q = 0; q < p->nloc; ++q)
-    {
-      p->row_off[q] = nb2;
-      nb2 += q - p->row_first[q] + 1;
-    }
-    p->nblk = nb2;
-    p->T.assign((size_t)nb2 * p->Bp * p->Bp, 0.0);
-    p->X.assign((size_t)p->nloc * p->Bp * p->Bp, 0.0);
-    p->yv.assign((size_t)p->nloc * p->Bp, 0.0);
+    const int a = lpos[p->links[l].first], b = lpos[p->links[l].second];
+    if (a < 0 || b < 0)
+      return SAGE_E_STATE;
+    p->row_first[std::max(a, b)] = std::min(p->row_first[std::max(a, b)], (int32_t)std::min(a, b));
   }
+  // a separator row receives fill from every earlier separator that shares interior columns with it: keep the
+  // separator rows' envelopes contiguous down to the first interior column any of them reaches
+  p->row_off.resize(p->nloc);
+  int nb2 = 0;
+  for (int q = 0; q < p->nloc; ++q)
+  {
+    p->row_off[q] = nb2;
+    nb2 += q - p->row_first[q] + 1;
+  }
+  p->nblk = nb2;
+  p->T.assign((size_t)nb2 * p->Bp * p->Bp, 0.0);
+  p->X.assign((size_t)p->nloc * p->Bp * p->Bp, 0.0);
+  p->yv.assign((size_t)p->nloc * p->Bp, 0.0);
   return SAGE_OK;
 }
 
@@ -385,7 +365,6 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
   auto tnow = [] { return std::chrono::steady_clock::now(); };
   const auto t0 = tnow();
   const int nI = (int)p->interior.size(), nS = (int)p->sep_local.size();
-  const int NI = nI * B, NS = nS * B;
   std::fill(sep_out, sep_out + p->sep_doubles, 0.0);
   double *sep_rhs = sep_out + (size_t)p->n_pair_blocks * BB;
   // tail: this rank's error / inlier totals at the linearisation point ride along
@@ -397,228 +376,77 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
   std::vector<int> spos(K, -1);
   for (int i = 0; i < nS; ++i)
     spos[p->sep_all[p->sep_local[i]]] = i;
-  if (p->fast)
+  const int Bp = p->Bp, BBp = Bp * Bp;
+  std::fill(p->T.begin(), p->T.end(), 0.0);
+  std::fill(p->yv.begin(), p->yv.end(), 0.0);
+  auto blk = [&](int i, int j) { return p->T.data() + (size_t)(p->row_off[i] + j - p->row_first[i]) * BBp; };
+  auto lpos = [&](int k) { return p->int_pos[k] >= 0 ? p->int_pos[k] : (spos[k] >= 0 ? nI + spos[k] : -1); };
+  for (int q = 0; q < p->nloc; ++q)
   {
-    const int Bp = p->Bp, BBp = Bp * Bp;
-    std::fill(p->T.begin(), p->T.end(), 0.0);
-    std::fill(p->yv.begin(), p->yv.end(), 0.0);
-    auto blk = [&](int i, int j) { return p->T.data() + (size_t)(p->row_off[i] + j - p->row_first[i]) * BBp; };
-    auto lpos = [&](int k) { return p->int_pos[k] >= 0 ? p->int_pos[k] : (spos[k] >= 0 ? nI + spos[k] : -1); };
-    for (int q = 0; q < p->nloc; ++q)
-    {
-      const int k = q < nI ? p->interior[q] : p->sep_all[p->sep_local[q - nI]];
-      const bool contributes = q < nI || !p->assembled || p->rank == 0; // separator diagonals: see the scalar path
-      double *D = blk(q, q);
-      for (int r = 0; r < Bp; ++r)
-        for (int c = 0; c < Bp; ++c)
-        {
-          double v = 0.0;
-          if (r < B && c < B)
-            v = contributes ? S.diag_elem(k, r, c) : 0.0;
-          else if (r == c)
-            v = 1.0; // padding: identity
-          D[r * Bp + c] = v;
-        }
-      if (contributes)
-        for (int r = 0; r < B; ++r)
-          p->yv[(size_t)q * Bp + r] = S.rhs(k, r);
-    }
-    for (int l : p->local_links)
-    {
-      const int a = p->links[l].first, b = p->links[l].second;
-      const int qa = lpos(a), qb = lpos(b);
-      if (qa < 0 || qb < 0)
-        return SAGE_E_STATE;
-      const int qi = std::max(qa, qb), qj = std::min(qa, qb);
-      double *D = blk(qi, qj); // stored [c in column position][r in row position]; the packed block is [r in a][c in b]
-      const bool row_is_a = qi == qa;
-      const double *src = S.lnk + (size_t)l * BB;
-      for (int r = 0; r < B; ++r)
-        for (int c = 0; c < B; ++c)
-          D[row_is_a ? c * Bp + r : r * Bp + c] += src[r * B + c];
-    }
-    sage::BlockEnvelope env;
-    env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
-    const auto t1 = tnow();
-    const int rcf = sage::block_chol_partial(env, p->T.data(), p->X.data(), p->yv.data(), nI);
-    if (rcf != 0)
-      return SAGE_E_NOT_PSD;
-    p->have_factor = true;
-    // Schur complement blocks and right-hand side of this rank's separators -> separator buffer
-    for (int i = 0; i < nS; ++i)
-    {
-      for (int j = 0; j <= i; ++j)
+    const int k = q < nI ? p->interior[q] : p->sep_all[p->sep_local[q - nI]];
+    // separator diagonal blocks / right-hand sides: every rank's own contribution (rank mode: its packed buffer only holds
+    // its own edge sums); in assembled mode the buffer is complete and domain 0 alone contributes them
+    const bool contributes = q < nI || !p->assembled || p->rank == 0;
+    double *D = blk(q, q);
+    for (int r = 0; r < Bp; ++r)
+      for (int c = 0; c < Bp; ++c)
       {
-        if (nI + j < p->row_first[nI + i])
-          continue; // outside the envelope: structurally zero
-        const auto it = p->pair_block.find({p->sep_local[j], p->sep_local[i]});
-        if (it == p->pair_block.end())
-          continue; // (inside the envelope but coupled by nothing: zero)
-        const double *src = blk(nI + i, nI + j); // [cc][rr] = C[(s_i, rr), (s_j, cc)], valid for rr >= cc when i == j
-        double *dst = sep_out + (size_t)it->second * BB; // rows s_j, cols s_i
-        for (int r = 0; r < B; ++r)
-          for (int c = 0; c < B; ++c)
-            dst[r * B + c] = (i != j || c >= r) ? src[r * Bp + c] : src[c * Bp + r];
+        double v = 0.0;
+        if (r < B && c < B)
+          v = contributes ? S.diag_elem(k, r, c) : 0.0;
+        else if (r == c)
+          v = 1.0; // padding: identity
+        D[r * Bp + c] = v;
       }
+    if (contributes)
       for (int r = 0; r < B; ++r)
-        sep_rhs[(size_t)p->sep_local[i] * B + r] = p->yv[(size_t)(nI + i) * Bp + r];
-    }
-    if (dbg)
-    {
-      auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-      fprintf(stderr, "[sage shard eliminate] fixed-block: build %.3f partial factorisation %.3f scatter %.3f ms (%d interior, %d separators)\n",
-              ms(t0, t1), ms(t1, tnow()), 0.0, nI, nS);
-    }
-    return SAGE_OK;
+        p->yv[(size_t)q * Bp + r] = S.rhs(k, r);
   }
-  // ---- interior matrix in envelope form: first[] from the links among interior keyframes
-  std::vector<int> first_blk(nI);
-  for (int i = 0; i < nI; ++i)
-    first_blk[i] = i;
   for (int l : p->local_links)
   {
-    const int a = p->int_pos[p->links[l].first], b = p->int_pos[p->links[l].second];
-    if (a >= 0 && b >= 0)
-      first_blk[std::max(a, b)] = std::min(first_blk[std::max(a, b)], std::min(a, b));
-  }
-  std::vector<int> first(NI);
-  for (int i = 0; i < nI; ++i)
-    for (int r = 0; r < B; ++r)
-      first[i * B + r] = first_blk[i] * B;
-  p->LI.init(NI, first);
-  for (int i = 0; i < nI; ++i)
-  {
-    const int k = p->interior[i];
-    for (int r = 0; r < B; ++r)
-      for (int c = 0; c <= r; ++c)
-        p->LI.at(i * B + r, i * B + c) = S.diag_elem(k, r, c);
-  }
-  // A_SS (local contribution), A_SI
-  std::vector<double> ASS((size_t)NS * NS, 0.0), ASI((size_t)NS * std::max(NI, 1), 0.0), bS(NS, 0.0), bI(NI, 0.0);
-  // separator diagonal blocks / right-hand sides: every rank's own contribution (rank mode: its packed buffer only holds
-  // its own edge sums); in assembled mode the buffer is complete and domain 0 alone contributes them
-  if (!p->assembled || p->rank == 0)
-    for (int i = 0; i < nS; ++i)
-    {
-      const int k = p->sep_all[p->sep_local[i]];
-      for (int r = 0; r < B; ++r)
-      {
-        for (int c = 0; c < B; ++c)
-          ASS[(size_t)(i * B + r) * NS + i * B + c] = S.diag_elem(k, r, c);
-        bS[i * B + r] = S.rhs(k, r);
-      }
-    }
-  for (int i = 0; i < nI; ++i)
-    for (int r = 0; r < B; ++r)
-      bI[i * B + r] = S.rhs(p->interior[i], r);
-  for (int l : p->local_links)
-  {
-    const int a = p->links[l].first, b = p->links[l].second; // block rows = a, cols = b
-    const double *blk = S.lnk + (size_t)l * BB;
-    const int ia = p->int_pos[a], ib = p->int_pos[b], sa = spos[a], sb = spos[b];
+    const int a = p->links[l].first, b = p->links[l].second;
+    const int qa = lpos(a), qb = lpos(b);
+    if (qa < 0 || qb < 0)
+      return SAGE_E_STATE;
+    const int qi = std::max(qa, qb), qj = std::min(qa, qb);
+    double *D = blk(qi, qj); // stored [c in column position][r in row position]; the packed block is [r in a][c in b]
+    const bool row_is_a = qi == qa;
+    const double *src = S.lnk + (size_t)l * BB;
     for (int r = 0; r < B; ++r)
       for (int c = 0; c < B; ++c)
-      {
-        const double v = blk[r * B + c]; // A[a*B + r][b*B + c]
-        if (ia >= 0 && ib >= 0)
-        {
-          if (ib > ia)
-            p->LI.at(ib * B + c, ia * B + r) += v;
-          else
-            p->LI.at(ia * B + r, ib * B + c) += v;
-        }
-        else if (sa >= 0 && sb >= 0)
-        {
-          ASS[(size_t)(sa * B + r) * NS + sb * B + c] += v;
-          ASS[(size_t)(sb * B + c) * NS + sa * B + r] += v;
-        }
-        else if (sa >= 0 && ib >= 0)
-          ASI[(size_t)(sa * B + r) * NI + ib * B + c] += v;
-        else if (ia >= 0 && sb >= 0)
-          ASI[(size_t)(sb * B + c) * NI + ia * B + r] += v;
-        else
-          return SAGE_E_STATE; // a link of this rank touching a keyframe that is neither interior nor its separator
-      }
+        D[row_is_a ? c * Bp + r : r * Bp + c] += src[r * B + c];
   }
-  // ---- eliminate the interior
-  p->have_factor = false;
+  sage::BlockEnvelope env;
+  env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
   const auto t1 = tnow();
-  auto t2 = t1, t3 = t1;
-  if (NI > 0)
-  {
-    if (!p->LI.cholesky_inplace(B, 1))
-      return SAGE_E_NOT_PSD;
-    t2 = tnow();
-    // forward substitutions: y = L^-1 b_I ; rows of LS = L^-1 (A_SI row)^T
-    // v <- L^-1 v, skipping the leading zeros of v (a separator row of A_SI only touches the interior keyframes next
-    // to it, which the elimination order puts last); returns the index of the first non-zero
-    auto forward = [&](double *v) {
-      int z = 0;
-      while (z < NI && v[z] == 0.0)
-        ++z;
-      for (int r = z; r < NI; ++r)
-      {
-        const int fr = std::max(p->LI.first[r], z);
-        const double *Lr = &p->LI.data[p->LI.rowptr[r]] - p->LI.first[r];
-        v[r] = (v[r] - sdot(Lr + fr, v + fr, r - fr)) / Lr[r];
-      }
-      return z;
-    };
-    p->y = bI;
-    forward(p->y.data());
-    p->LS = ASI;
-    p->ls_first.assign(NS, 0);
-    for (int s2 = 0; s2 < NS; ++s2)
-      p->ls_first[s2] = forward(&p->LS[(size_t)s2 * NI]);
-    t3 = tnow();
-    // C = A_SS - LS LS^T ; c = b_S - LS y
-    for (int i = 0; i < NS; ++i)
-    {
-      const double *li = &p->LS[(size_t)i * NI];
-      for (int j = i; j < NS; ++j)
-      {
-        const double *lj = &p->LS[(size_t)j * NI];
-        const int z = std::max(p->ls_first[i], p->ls_first[j]);
-        const double acc = z < NI ? sdot(li + z, lj + z, NI - z) : 0.0;
-        ASS[(size_t)i * NS + j] -= acc;
-        if (j != i)
-          ASS[(size_t)j * NS + i] -= acc;
-      }
-      const int z = p->ls_first[i];
-      bS[i] -= z < NI ? sdot(li + z, p->y.data() + z, NI - z) : 0.0;
-    }
-  }
-  else
-  {
-    p->LS.clear();
-    p->y.clear();
-  }
+  const int rcf = sage::block_chol_partial(env, p->T.data(), p->X.data(), p->yv.data(), nI);
+  if (rcf != 0)
+    return SAGE_E_NOT_PSD;
   p->have_factor = true;
+  // Schur complement blocks and right-hand side of this rank's separators -> separator buffer
+  for (int i = 0; i < nS; ++i)
+  {
+    for (int j = 0; j <= i; ++j)
+    {
+      if (nI + j < p->row_first[nI + i])
+        continue; // outside the envelope: structurally zero
+      const auto it = p->pair_block.find({p->sep_local[j], p->sep_local[i]});
+      if (it == p->pair_block.end())
+        continue; // (inside the envelope but coupled by nothing: zero)
+      const double *src = blk(nI + i, nI + j); // [cc][rr] = C[(s_i, rr), (s_j, cc)], valid for rr >= cc when i == j
+      double *dst = sep_out + (size_t)it->second * BB; // rows s_j, cols s_i
+      for (int r = 0; r < B; ++r)
+        for (int c = 0; c < B; ++c)
+          dst[r * B + c] = (i != j || c >= r) ? src[r * Bp + c] : src[c * Bp + r];
+    }
+    for (int r = 0; r < B; ++r)
+      sep_rhs[(size_t)p->sep_local[i] * B + r] = p->yv[(size_t)(nI + i) * Bp + r];
+  }
   if (dbg)
   {
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    fprintf(stderr, "[sage shard eliminate] build %.3f chol(I) %.3f forward(S rows) %.3f schur %.3f ms (NI %d NS %d)\n",
-            ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, tnow()), NI, NS);
-  }
-  // ---- scatter into the separator buffer (upper-triangular block pairs)
-  for (int i = 0; i < nS; ++i)
-  {
-    for (int j = i; j < nS; ++j)
-    {
-      const auto it = p->pair_block.find({p->sep_local[i], p->sep_local[j]});
-      if (it == p->pair_block.end())
-      {
-        if (p->assembled)
-          continue; // domain 0 lists every separator: pairs nothing couples are structurally zero
-        return SAGE_E_STATE;
-      }
-      double *dst = sep_out + (size_t)it->second * BB;
-      for (int r = 0; r < B; ++r)
-        for (int c = 0; c < B; ++c)
-          dst[r * B + c] = ASS[(size_t)(i * B + r) * NS + j * B + c];
-    }
-    for (int r = 0; r < B; ++r)
-      sep_rhs[(size_t)p->sep_local[i] * B + r] = bS[i * B + r];
+    fprintf(stderr, "[sage shard eliminate] fixed-block: build %.3f partial factorisation %.3f scatter %.3f ms (%d interior, %d separators)\n",
+            ms(t0, t1), ms(t1, tnow()), 0.0, nI, nS);
   }
   return SAGE_OK;
 }
@@ -639,50 +467,21 @@ extern "C" int sage_shard_solve(SageShardPlan *p, const double *sep_reduced, dou
     if (rc)
       return rc;
   }
-  if (p->fast)
-  {
-    const int Bp = p->Bp, nI2 = (int)p->interior.size(), nS2 = (int)p->sep_local.size();
-    for (int s2 = 0; s2 < nS2; ++s2)
-    {
-      for (int r = 0; r < B; ++r)
-        p->yv[(size_t)(nI2 + s2) * Bp + r] = dS[(size_t)p->sep_local[s2] * B + r];
-      for (int r = B; r < Bp; ++r)
-        p->yv[(size_t)(nI2 + s2) * Bp + r] = 0.0;
-    }
-    sage::BlockEnvelope env;
-    env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
-    if (sage::block_chol_partial_back(env, p->T.data(), p->X.data(), p->yv.data(), nI2) != 0)
-      return SAGE_E_STATE;
-    for (int i = 0; i < nI2; ++i)
-      for (int r = 0; r < B; ++r)
-        delta[(size_t)p->interior[i] * B + r] = p->yv[(size_t)i * Bp + r];
-    for (int s2 = 0; s2 < nS2; ++s2)
-      for (int r = 0; r < B; ++r)
-        delta[(size_t)p->sep_all[p->sep_local[s2]] * B + r] = dS[(size_t)p->sep_local[s2] * B + r];
-    return SAGE_OK;
-  }
-  // ---- back-substitute the interior: d_I = L^-T (y - LS^T d_S(local))
-  const int nI = (int)p->interior.size(), nS = (int)p->sep_local.size(), NI = nI * B;
-  std::vector<double> v(p->y);
+  const int Bp = p->Bp, nI = (int)p->interior.size(), nS = (int)p->sep_local.size();
   for (int s = 0; s < nS; ++s)
-    for (int r = 0; r < B; ++r)
-    {
-      const double d = dS[(size_t)p->sep_local[s] * B + r];
-      const int row = s * B + r, z = NI > 0 ? p->ls_first[row] : 0;
-      if (z < NI)
-        saxpy(v.data() + z, &p->LS[(size_t)row * NI] + z, d, NI - z);
-    }
-  for (int r = NI - 1; r >= 0; --r)
   {
-    const int fr = p->LI.first[r];
-    const double *Lr = &p->LI.data[p->LI.rowptr[r]];
-    const double x = v[r] / Lr[r - fr];
-    v[r] = x;
-    saxpy(v.data() + fr, Lr, x, r - fr);
+    for (int r = 0; r < B; ++r)
+      p->yv[(size_t)(nI + s) * Bp + r] = dS[(size_t)p->sep_local[s] * B + r];
+    for (int r = B; r < Bp; ++r)
+      p->yv[(size_t)(nI + s) * Bp + r] = 0.0;
   }
+  sage::BlockEnvelope env;
+  env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
+  if (sage::block_chol_partial_back(env, p->T.data(), p->X.data(), p->yv.data(), nI) != 0)
+    return SAGE_E_STATE;
   for (int i = 0; i < nI; ++i)
     for (int r = 0; r < B; ++r)
-      delta[(size_t)p->interior[i] * B + r] = v[i * B + r];
+      delta[(size_t)p->interior[i] * B + r] = p->yv[(size_t)i * Bp + r];
   for (int s = 0; s < nS; ++s)
     for (int r = 0; r < B; ++r)
       delta[(size_t)p->sep_all[p->sep_local[s]] * B + r] = dS[(size_t)p->sep_local[s] * B + r];

@@ -336,14 +336,12 @@ struct DeviceSolver
                                       // entry T = start of the separator rows, entry T+1 = nblk
 };
 
-static int solver_bp(int B) { return (B + 7) / 8 * 8; }
-
 int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
                   hipStream_t stream, bool allow_split)
 {
   *out = nullptr;
-  const int Bp = solver_bp(B);
-  if ((Bp != 40 && Bp != 24) || K < 1)
+  const int Bp = sage::padded_block(B);
+  if (Bp == 0 || K < 1)
     return SAGE_E_UNSUPPORTED;
   BlockPlan bp;
   {

@@ -1538,7 +1538,7 @@ int window_sync_candidate(SageWindow *w, bool stream_idle)
   if (!stream_idle)
     SAGE_HIP(hipStreamSynchronize(w->stream));
   w->cand_pending = false;
-  const DeviceSolver *S = w->last_solver ? w->last_solver : w->solver;
+  const DeviceSolver *S = w->solver;
   if (solver_host_status(S) != 0)
     return SAGE_E_NOT_PSD;
   const int K = w->K, CS = w->cfg.CS, VS = w->VS;
@@ -1639,48 +1639,13 @@ static int window_total_error(SageWindow *w, int from_linearize, double *err, bo
   return rc_out;
 }
 
-extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
+// diagonal priors (a9): code prior on every keyframe, scale / pose priors on keyframe 0
+static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::vector<double> &gadd)
 {
-  if (!w || !w->finalized || !w->have_lin)
-    return SAGE_E_STATE;
   const SageWindowConfig &c = w->cfg;
-  const int K = w->K, B = w->B, CS = c.CS, BB = B * B, n = K * B;
-  if (w->solver)
-  {
-    // device path: nothing leaves HBM but the candidate's host mirror (pinned, async); no synchronisation here
-    // unless the caller asks for the step norm
-    int rc = window_sync_candidate(w); // an unconsumed earlier candidate (a re-solve with another damping)
-    if (rc && rc != SAGE_E_NOT_PSD)
-      return rc;
-    if (w->dpt_set == 1)
-      w->dpt_set = -1; // the solve rewrites the candidate set
-    rc = solver_run(w->solver, w->stream, w->packed.as<double>(), w->vars[0].as<float>(), w->vars[1].as<float>(), CS,
-                    damp, c.code_prior_weight, c.scale_prior_weight, c.pose_prior_weight, w->scale_init[0],
-                    &w->pose_init[0]);
-    if (rc)
-      return rc;
-    window_phase_mark(w, 3);
-    w->cand_pending = true;
-    w->last_solver = w->solver;
-    if (step_norm)
-    {
-      if ((rc = window_sync_candidate(w)))
-        return rc;
-      *step_norm = std::sqrt(solver_host_step_norm2(w->last_solver ? w->last_solver : w->solver));
-    }
-    return SAGE_OK;
-  }
-  const size_t np = sage_window_packed_count(w);
-  static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
-  auto tnow = [] { return std::chrono::steady_clock::now(); };
-  auto t_a = tnow();
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  auto t_b = tnow();
-  SAGE_HIP(hipMemcpyAsync(w->host_packed.data(), w->packed.p, np * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  auto t_c = tnow();
-  // diagonal priors (a9): code prior on every keyframe, scale / pose priors on keyframe 0
-  std::vector<double> dadd((size_t)n, 0.0), gadd((size_t)n, 0.0);
+  const int K = w->K, B = w->B, CS = c.CS;
+  dadd.assign((size_t)K * B, 0.0);
+  gadd.assign((size_t)K * B, 0.0);
   for (int k = 0; k < K; ++k)
     for (int i = 0; i < CS; ++i)
     {
@@ -1703,36 +1668,92 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
       gadd[i] += c.pose_prior_weight * loc[i];
     }
   }
+}
+
+// candidate = retract(current, delta).  local_only (sharded windows): only the keyframes this rank touches, the others
+// keep their (stale) current values
+static void window_retract_candidate(SageWindow *w, bool local_only)
+{
+  const int K = w->K, B = w->B, CS = w->cfg.CS;
+  if (local_only)
+  {
+    w->pose[1] = w->pose[0];
+    w->code[1] = w->code[0];
+    w->scale[1] = w->scale[0];
+  }
+  for (int k = 0; k < K; ++k)
+  {
+    if (local_only && !sage_shard_keyframe_is_local(w->shard, k))
+      continue;
+    float d6[6];
+    for (int i = 0; i < 6; ++i)
+      d6[i] = (float)w->delta[(size_t)k * B + i];
+    sage_pose_retract(&w->pose[0][(size_t)k * 12], d6, &w->pose[1][(size_t)k * 12]);
+    for (int i = 0; i < CS; ++i)
+      w->code[1][(size_t)k * CS + i] = w->code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
+    w->scale[1][k] = w->scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
+  }
+}
+
+extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
+{
+  if (!w || !w->finalized || !w->have_lin)
+    return SAGE_E_STATE;
+  const SageWindowConfig &c = w->cfg;
+  const int K = w->K, B = w->B, CS = c.CS;
+  if (w->solver)
+  {
+    // device path: nothing leaves HBM but the candidate's host mirror (pinned, async); no synchronisation here
+    // unless the caller asks for the step norm
+    int rc = window_sync_candidate(w); // an unconsumed earlier candidate (a re-solve with another damping)
+    if (rc && rc != SAGE_E_NOT_PSD)
+      return rc;
+    if (w->dpt_set == 1)
+      w->dpt_set = -1; // the solve rewrites the candidate set
+    rc = solver_run(w->solver, w->stream, w->packed.as<double>(), w->vars[0].as<float>(), w->vars[1].as<float>(), CS,
+                    damp, c.code_prior_weight, c.scale_prior_weight, c.pose_prior_weight, w->scale_init[0],
+                    &w->pose_init[0]);
+    if (rc)
+      return rc;
+    window_phase_mark(w, 3);
+    w->cand_pending = true;
+    if (step_norm)
+    {
+      if ((rc = window_sync_candidate(w)))
+        return rc;
+      *step_norm = std::sqrt(solver_host_step_norm2(w->solver));
+    }
+    return SAGE_OK;
+  }
+  const size_t np = sage_window_packed_count(w);
+  static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
+  auto tnow = [] { return std::chrono::steady_clock::now(); };
+  auto t_a = tnow();
+  SAGE_HIP(hipStreamSynchronize(w->stream));
+  auto t_b = tnow();
+  SAGE_HIP(hipMemcpyAsync(w->host_packed.data(), w->packed.p, np * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+  SAGE_HIP(hipStreamSynchronize(w->stream));
+  auto t_c = tnow();
+  // no device solver: the window has duplicate links (solver_create refused them), the host block solve sums them
+  std::vector<double> dadd, gadd;
+  window_priors(w, dadd, gadd);
   std::vector<int32_t> lk(2 * w->links.size());
   for (size_t l = 0; l < w->links.size(); ++l)
   {
     lk[2 * l] = w->links[l].first;
     lk[2 * l + 1] = w->links[l].second;
   }
-  std::vector<double> rhs((size_t)n);
-  (void)BB;
   int rcs = sage_block_solve(w->host_packed.data(), K, (int)w->links.size(), lk.data(), B, damp, dadd.data(),
-                             gadd.data(), rhs.data());
+                             gadd.data(), w->delta.data()); // (writes delta only on success)
   if (rcs)
     return rcs;
   auto t_d = tnow();
-  w->delta = rhs;
   double nrm = 0;
-  for (double v : rhs)
+  for (double v : w->delta)
     nrm += v * v;
   if (step_norm)
     *step_norm = std::sqrt(nrm);
-  // candidate = retract(current, delta)
-  for (int k = 0; k < K; ++k)
-  {
-    float d6[6];
-    for (int i = 0; i < 6; ++i)
-      d6[i] = (float)rhs[k * B + i];
-    sage_pose_retract(&w->pose[0][(size_t)k * 12], d6, &w->pose[1][(size_t)k * 12]);
-    for (int i = 0; i < CS; ++i)
-      w->code[1][(size_t)k * CS + i] = w->code[0][(size_t)k * CS + i] + (float)rhs[k * B + 6 + i];
-    w->scale[1][k] = w->scale[0][k] + (float)rhs[k * B + 6 + CS];
-  }
+  window_retract_candidate(w, false);
   const int rcu = window_upload_vars(w, 1);
   if (dbg)
   {
@@ -1828,36 +1849,6 @@ extern "C" int sage_window_get_delta(const SageWindow *w, double *delta)
   return SAGE_OK;
 }
 
-static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::vector<double> &gadd)
-{
-  const SageWindowConfig &c = w->cfg;
-  const int K = w->K, B = w->B, CS = c.CS;
-  dadd.assign((size_t)K * B, 0.0);
-  gadd.assign((size_t)K * B, 0.0);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < CS; ++i)
-    {
-      dadd[k * B + 6 + i] += c.code_prior_weight;
-      gadd[k * B + 6 + i] += c.code_prior_weight * (0.0 - (double)w->code[0][(size_t)k * CS + i]);
-    }
-  if (c.scale_prior_weight > 0)
-  {
-    const double s = w->scale[0][0];
-    dadd[6 + CS] += c.scale_prior_weight / (s * s);
-    gadd[6 + CS] += c.scale_prior_weight / s * (std::log((double)w->scale_init[0]) - std::log(s));
-  }
-  if (c.pose_prior_weight > 0)
-  {
-    double loc[6];
-    pose_local(&w->pose[0][0], &w->pose_init[0], loc);
-    for (int i = 0; i < 6; ++i)
-    {
-      dadd[i] += c.pose_prior_weight;
-      gadd[i] += c.pose_prior_weight * loc[i];
-    }
-  }
-}
-
 // prior error terms of the keyframes THIS rank owns (the other ranks' copies of their variables are stale here)
 static double prior_error_owned(const SageWindow *w, int set)
 {
@@ -1895,8 +1886,7 @@ __global__ void add_to_double_kernel(double *p, double v) { p[0] += v; }
 // Returns SAGE_E_NOT_PSD consistently on every rank (a rank whose local elimination fails poisons the payload).
 static int schur_solve(SageWindow *w, double damp, double *lin_error)
 {
-  const SageWindowConfig &c = w->cfg;
-  const int K = w->K, B = w->B, CS = c.CS;
+  const int K = w->K, B = w->B;
   const size_t np = sage_window_packed_count(w), ns = w->h_sep.size();
   SAGE_HIP(hipMemcpyAsync(w->host_packed.data(), w->packed.p, np * sizeof(double), hipMemcpyDeviceToHost, w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream));
@@ -1927,22 +1917,7 @@ static int schur_solve(SageWindow *w, double damp, double *lin_error)
   rc = sage_shard_solve(w->shard, w->h_sep.data(), w->delta.data());
   if (rc)
     return rc; // SAGE_E_NOT_PSD of the separator system: identical on every rank
-  // candidate = retract(current, delta) for the keyframes this rank touches; the others keep their (stale) values
-  w->pose[1] = w->pose[0];
-  w->code[1] = w->code[0];
-  w->scale[1] = w->scale[0];
-  for (int k = 0; k < K; ++k)
-  {
-    if (!sage_shard_keyframe_is_local(w->shard, k))
-      continue;
-    float d6[6];
-    for (int i = 0; i < 6; ++i)
-      d6[i] = (float)w->delta[(size_t)k * B + i];
-    sage_pose_retract(&w->pose[0][(size_t)k * 12], d6, &w->pose[1][(size_t)k * 12]);
-    for (int i = 0; i < CS; ++i)
-      w->code[1][(size_t)k * CS + i] = w->code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
-    w->scale[1][k] = w->scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
-  }
+  window_retract_candidate(w, true);
   w->cand_pending = false;
   return window_upload_vars(w, 1);
 }

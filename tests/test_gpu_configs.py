@@ -58,13 +58,13 @@ def add_priors(H, g, w, CS):
     return H, g
 
 
-def prior_vectors(w, CS):
+def prior_vectors(w, CS, code_w=1e-3):
     K, B = len(w.keyframes), 7 + CS
     dadd = np.zeros(K * B); gadd = np.zeros(K * B)
     for k, kf in enumerate(w.keyframes):
         idx = np.arange(k * B + 6, k * B + 6 + CS)
-        dadd[idx] += 1e-3
-        gadd[idx] += 1e-3 * (0 - kf.code.astype(np.float64))
+        dadd[idx] += code_w
+        gadd[idx] += code_w * (0 - kf.code.astype(np.float64))
     s = float(w.keyframes[0].scale)
     dadd[6 + CS] += 1e4 / (s * s)
     dadd[:6] += 1e4
@@ -302,6 +302,26 @@ def test_config4_highres_k16(capi, orc):
         win.lm_step(st, cfg)
         errs.append((st.error, st.candidate_error, st.accepted))
     assert errs[0][2] == 1 and errs[-1][1] < errs[0][0], errs
+    win.close()
+
+
+def test_window_solve_duplicate_link(capi):
+    """A link added twice: the device solver refuses the window's plan, so the window solves on the host
+    (sage_block_solve sums the two link blocks).  Same delta as the host block solve of the same packed system and
+    priors, and an LM step runs end to end."""
+    K, CS = 5, 16
+    w = synth.make_window(K=K, H=32, W=40, FS=16, CS=CS, L=3, seed=5, back_links=2)
+    w.links.append(w.links[1])
+    win = capi.Window(w)
+    win.linearize()
+    packed = win.packed_host().astype(np.float64)
+    dadd, gadd = prior_vectors(w, CS, code_w=float(np.float32(1e-3)))   # the engine's fp32 code prior weight
+    win.solve(DAMP)
+    dref = capi.block_solve(packed[:-4], K, w.links, 7 + CS, DAMP, dadd, gadd)
+    assert rel(win.delta(), dref) < 1e-12
+    st = capi.SageLmState()
+    win.lm_step(st, capi.lm_config_default())                         # raises unless SAGE_OK
+    assert np.isfinite(st.error) and np.isfinite(st.candidate_error)
     win.close()
 
 

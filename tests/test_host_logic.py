@@ -137,9 +137,10 @@ def test_damped_qr_solve():
         assert rel(x, ref) < 1e-4
 
 
-def test_block_solve_matches_dense():
+@pytest.mark.parametrize("CS", [16, 3, 18, 33])   # B = 23 (product), 10, 25, 40: padded to 24 / 40 like the product's
+def test_block_solve_matches_dense(CS):
     rng = np.random.default_rng(3)
-    K, CS = 7, 16
+    K = 7
     B = 7 + CS
     links = [(j, i) for i in range(K) for j in range(max(0, i - 3), i)] + [(0, 6)]   # band + a loop closure
     n = K * B
@@ -164,6 +165,9 @@ def test_block_solve_matches_dense():
     assert rel(d, ref) < 1e-9
     with pytest.raises(capi.SageError):                                 # not positive definite
         capi.block_solve(-packed, K, links, B, 0.0)
+    with pytest.raises(capi.SageError) as ei:                           # B > 40: no block kernel for it
+        capi.block_solve(np.zeros((K + len(links)) * 41 * 41 + K * 41), K, links, 41, 1e-3)
+    assert ei.value.code == -2                                           # SAGE_E_UNSUPPORTED
 
 
 @pytest.mark.parametrize("K,CS,window", [(24, 32, 3), (20, 16, 5), (33, 32, 1)])

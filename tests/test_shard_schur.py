@@ -3,7 +3,8 @@ process.  Each rank sees only the packed normal equations of ITS link range, eli
 contributes a Schur complement to the separator buffer; the buffers are summed (what the all-reduce does); every rank
 solves the separator system and back-substitutes its keyframes.  The merged delta must equal the single-rank damped
 solve of the summed system (sage_block_solve) -- world 2, 4 and 8, temporal windows with and without loop closures,
-CS 16 (B = 23) and 32 (B = 39), priors owned by exactly one rank."""
+CS 16 (B = 23) and 32 (B = 39) as the product runs them, CS 3, 18 and 33 (B = 10, 25, 40: the other padded block
+sizes), priors owned by exactly one rank."""
 import numpy as np
 import pytest
 
@@ -37,7 +38,8 @@ def packed_of(K, links, B, per_link, owned):
 
 
 @pytest.mark.parametrize("world", [2, 4, 8])
-@pytest.mark.parametrize("K,CS,loops", [(64, 32, []), (40, 16, [(0, 39), (3, 30)]), (17, 32, [])])
+@pytest.mark.parametrize("K,CS,loops", [(64, 32, []), (40, 16, [(0, 39), (3, 30)]), (17, 32, []),
+                                       (30, 3, [(2, 27)]), (24, 18, []), (20, 33, [(0, 19)])])
 def test_schur_sharded_solve_equals_single_rank(world, K, CS, loops):
     B = 7 + CS
     links = [(j, i) for i in range(K) for j in range(max(0, i - 3), i)] + loops
@@ -81,9 +83,13 @@ def test_schur_sharded_solve_equals_single_rank(world, K, CS, loops):
     assert np.allclose(sep_sum[-8:-4], full[-4:])
     for p in plans:
         p.close()
+    with pytest.raises(capi.SageError) as ei:                         # B > 40: no block kernel for it
+        capi.ShardPlan(K, links, 41, 0, world)
+    assert ei.value.code == -2                                         # SAGE_E_UNSUPPORTED
 
 
-@pytest.mark.parametrize("K,CS,loops", [(64, 32, []), (40, 16, [(0, 39), (3, 30)]), (30, 32, [(2, 27)])])
+@pytest.mark.parametrize("K,CS,loops", [(64, 32, []), (40, 16, [(0, 39), (3, 30)]), (30, 32, [(2, 27)]),
+                                       (30, 3, [(2, 27)]), (24, 18, []), (20, 33, [(0, 19)])])
 @pytest.mark.parametrize("ndomains", [1, 2, 4])
 def test_block_solve_domains_equals_block_solve(K, CS, loops, ndomains):
     """sage_block_solve_domains: the same decomposition inside one process (keyframe-range domains on host threads,
@@ -98,3 +104,6 @@ def test_block_solve_domains_equals_block_solve(K, CS, loops, ndomains):
     ref = capi.block_solve(full[:-4], K, links, B, 1e-3, dadd, gadd)
     d = capi.block_solve_domains(full, K, links, B, 1e-3, ndomains, dadd, gadd)
     assert rel(d, ref) < 1e-9
+    with pytest.raises(capi.SageError) as ei:                         # B > 40: no block kernel for it
+        capi.block_solve_domains(np.zeros((K + len(links)) * 41 * 41 + K * 41 + 4), K, links, 41, 1e-3, ndomains)
+    assert ei.value.code == -2                                         # SAGE_E_UNSUPPORTED
