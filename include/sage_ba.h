@@ -576,7 +576,13 @@ int sage_sample_locations(SageWorkspace *ws, const int64_t *valid_loc1d_dev, con
  * over all ranks, enqueued so that it is ordered with the window's stream (an RCCL ncclAllReduce on that stream, or
  * torch.distributed.all_reduce when the window runs on torch's current stream).  Returns 0 on success.  With the
  * hook installed sage_window_lm_step drives a sharded window as well: the host code between the launches stays
- * native, the hook is entered twice per iteration (packed buffer, 4-double error buffer). */
+ * native.  Per iteration the hook is entered, in the classic sequence, once for the packed buffer and then once per
+ * candidate evaluation for the 4-double error buffer; in the linearize-at-candidate sequence (the default of a reduced
+ * window) once per evaluation for the candidate's packed buffer, after one more for the packed buffer at the current
+ * estimate whenever that system has to be formed (the first iteration, after sage_window_reset); in the
+ * domain-decomposed sequence once per evaluation for the separator buffer, followed by the 4-double error buffer when
+ * the evaluation reaches the error pass.  (An evaluation whose host solve reports a non-positive pivot at once enters
+ * it not at all.) */
 typedef int (*SageAllReduceFn)(double *dev_buf, size_t n, void *user);
 int sage_window_set_allreduce(SageWindow *w, SageAllReduceFn fn, void *user);
 

@@ -1258,10 +1258,13 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
   hipLaunchKernelGGL(assemble_kernel, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
   SAGE_HIP(hipGetLastError());
   window_phase_mark(w, 1);
-  w->have_lin = true;
-  w->lin_epoch = set == 0 ? w->vars_epoch : 0; // (a candidate's system becomes current only through lm_step's accept)
-  w->spec_err_valid = false;
-  w->packed_reduced = false;
+  if (ap.packed == w->packed.as<double>()) // (a system assembled elsewhere is booked by the caller)
+  {
+    w->have_lin = true;
+    w->lin_epoch = set == 0 ? w->vars_epoch : 0; // (a candidate's system becomes current only through lm_step's accept)
+    w->spec_err_valid = false;
+    w->packed_reduced = false;
+  }
   return SAGE_OK;
 }
 
@@ -1553,6 +1556,21 @@ int window_sync_candidate(SageWindow *w, bool stream_idle)
   return SAGE_OK;
 }
 
+// wait for the totals of the last window_mirror_totals: spin on their tickets (with the kernels of a shard 8x shorter,
+// the 20-30 us wake-up of a thread blocked in a stream synchronise would be 4 % of an iteration), take up the candidate
+// -- a non-positive pivot of its factorisation shows up there (*not_psd) -- and synchronise only if the spin timed out
+static int window_wait_mirror(SageWindow *w, bool *not_psd)
+{
+  const bool idle = window_spin_totals(w, true);
+  const int rc = window_sync_candidate(w, idle);
+  if (rc && rc != SAGE_E_NOT_PSD)
+    return rc;
+  *not_psd = rc == SAGE_E_NOT_PSD;
+  if (!idle)
+    SAGE_HIP(hipStreamSynchronize(w->stream));
+  return SAGE_OK;
+}
+
 // prior error terms at a variable set (a9): code prior w*||c||^2/CS per keyframe (code_factor.cpp:99-104, zero
 // prior code), scale prior on keyframe 0 w*(ln s0 - ln s)^2 (scale_factor.cpp:102-129), pose prior on kf 0.
 static void pose_local(const float *origin, const float *other, double out[6])
@@ -1600,6 +1618,13 @@ static double prior_error(const SageWindow *w, int set)
   return e;
 }
 
+// total error from the pinned mirror: the edge totals at h_err[at], h_err[at + 1] (0: a system's tail, 4: an error
+// pass's totals) plus the prior terms at variable set `set`
+static double mirrored_error(const SageWindow *w, int at, int set)
+{
+  return w->h_err[at] + w->h_err[at + 1] + prior_error(w, set);
+}
+
 extern "C" int sage_window_total_error(SageWindow *w, int from_linearize, double *err)
 {
   return window_total_error(w, from_linearize, err, false);
@@ -1623,8 +1648,7 @@ static int window_total_error(SageWindow *w, int from_linearize, double *err, bo
     // sage_window_set_allreduce leaves the mirror unwritten and takes the copies below: ADVICE r5)
     if (!stream_idle)
       SAGE_HIP(hipStreamSynchronize(w->stream));
-    const double *m = w->h_err + (from_linearize ? 0 : 4);
-    *err = m[0] + m[1] + prior_error(w, from_linearize ? 0 : 1);
+    *err = mirrored_error(w, from_linearize ? 0 : 4, from_linearize ? 0 : 1);
     return rc_out;
   }
   if (from_linearize)
@@ -1978,17 +2002,65 @@ __global__ void copy_doubles_kernel(const double *__restrict__ src, double *__re
     dst[i] = src[i];
 }
 
-// SageLmConfig::linearize_at_candidate: one LM iteration in which the candidate is evaluated by the linearize kernels.
-// `packed` holds the system at the current estimate (kept from the previous accepted iteration); per evaluation: damped
-// solve -> candidate; linearize at the candidate into a second buffer (its finalize kernels deliver the error); accepted:
-// the two buffers swap -- the candidate's system IS the next iteration's, nothing is re-evaluated or copied; rejected:
-// `packed` never left and the damping goes up.  Decisions, damping schedule and iterates are those of
-// the default sequence; sage_window_get_edge afterwards returns the per-edge results of the LAST evaluation.
-static int lm_step_at_candidate(SageWindow *w, SageLmState *st, const SageLmConfig *cfg, bool sharded)
+// The LM iteration (sage_window_lm_step): one policy -- accept test, give-up test, damping schedule -- around the steps
+// of one of three sequences, which take the same decisions and walk the same iterates.  classic: linearize (+ all-reduce
+// of `packed`); per evaluation a damped solve and an error pass (+ all-reduce of its 4 totals).  schur (sharded windows
+// with a shard plan): linearize; per evaluation a local elimination, an all-reduce of the separator system, the separator
+// solve, an error pass and an all-reduce of its 4 totals.  at_candidate: per evaluation a damped solve and a linearize at the
+// candidate into packed_save (its finalize kernels deliver the error); accepted: the two buffers swap -- the candidate's
+// system IS the next iteration's, nothing is re-evaluated or copied; rejected: `packed` never left.
+enum class LmSeq { classic, schur, at_candidate };
+
+// (rank-independent decision: the window's link count, not this rank's share of it -- a rank without links must issue
+//  the same collectives as the others).  linearize_at_candidate 0 = automatic: the sequence with one collective and no
+//  separate error pass per iteration whenever the window is reduced over ranks (the shard's kernels are short there, the
+//  second collective and its host round trip are not), the classic sequence on a single rank
+static LmSeq lm_sequence_for(const SageWindow *w, const SageLmConfig *cfg)
+{
+  const bool sharded = w->allreduce != nullptr; // (a hook on a single-rank window is honoured too)
+  if (sharded && w->shard)
+    return LmSeq::schur;
+  const bool at_candidate = cfg->linearize_at_candidate > 0 || (cfg->linearize_at_candidate == 0 && sharded);
+  return at_candidate && !w->links.empty() ? LmSeq::at_candidate : LmSeq::classic;
+}
+
+// what one evaluation leaves for a later step of the same iteration
+struct LmEval
+{
+  double cur_tot[4];  // at_candidate: the mirrored totals of the current estimate, put back by a rejection
+  bool have_cur_tot;  // (a synchronous non-positive pivot of the solve leaves the mirror alone: nothing to put back)
+};
+
+// at_candidate: the (reduced) system at variable set `set` into dst, its totals into the pinned mirror with their tickets
+// -- the host never blocks in a stream synchronise on the iteration's critical path.  A reduced window assembles only the
+// blocks its own edges touch (into packed_loc) and sums out of place into dst; the emulated peers' share of iterate `it`
+// is added behind the sum.  The caller books what dst holds now.
+static int window_form_system(SageWindow *w, int set, double *dst, int it)
 {
   int rc;
-  auto clampd = [&](double d) { return std::min(std::max((double)cfg->min_damp, d), (double)cfg->max_damp); };
+  if (!w->allreduce)
+    return (rc = window_linearize_set(w, set, dst, false, true)) ? rc : window_mirror_totals(w, false, dst);
+  if ((rc = window_linearize_set(w, set, w->packed_loc.as<double>(), true, true)) ||
+      (rc = window_allreduce_into(w, w->packed_loc.as<double>(), dst, sage_window_packed_count(w), it)))
+    return rc;
+  window_phase_mark(w, 2);
+  return window_mirror_totals(w, false, dst);
+}
+
+// the system at the current estimate, before the first evaluation (at_candidate: and its error, st->error)
+static int lm_prepare(LmSeq seq, SageWindow *w, SageLmState *st)
+{
+  int rc;
+  const bool sharded = w->allreduce != nullptr;
   const size_t np = sage_window_packed_count(w);
+  if (seq != LmSeq::at_candidate)
+  {
+    if ((rc = window_linearize_set(w, 0, nullptr, false, true)) ||
+        (seq == LmSeq::classic && sharded && (rc = window_allreduce(w, w->packed.as<double>(), np, w->emu_cur))))
+      return rc;
+    window_phase_mark(w, 2);
+    return SAGE_OK;
+  }
   if ((rc = w->packed_save.reserve(np * sizeof(double))))
     return rc;
   if (sharded && !w->packed_loc.p)
@@ -1997,28 +2069,17 @@ static int lm_step_at_candidate(SageWindow *w, SageLmState *st, const SageLmConf
       return rc;
     SAGE_HIP(hipMemsetAsync(w->packed_loc.p, 0, np * sizeof(double), w->stream)); // blocks of other ranks: zero for good
   }
-  // one evaluation: linearize at variable set `set`, the (reduced) system into `dst`, its totals into the pinned mirror with
-  // their tickets -- the host never blocks in a stream synchronise on the iteration's critical path.  A reduced window
-  // assembles only the blocks its own edges touch (into packed_loc) and sums out of place into dst; the emulated peers'
-  // share of iterate `it` is added behind the sum.
-  auto evaluate = [&](int set, double *dst, int it) -> int {
-    int r;
-    if (!sharded)
-      return (r = window_linearize_set(w, set, dst, false, true)) ? r : window_mirror_totals(w, false, dst);
-    if ((r = window_linearize_set(w, set, w->packed_loc.as<double>(), true, true)) ||
-        (r = window_allreduce_into(w, w->packed_loc.as<double>(), dst, np, it)))
-      return r;
-    window_phase_mark(w, 2);
-    return window_mirror_totals(w, false, dst);
-  };
-  // the system at the current estimate is reused only if it is the GLOBAL one: sage_window_linearize / _prepass leave a
-  // rank-local `packed` behind on a sharded window (every rank sees the same flags: same call sequence on all ranks)
+  // the system at the current estimate is reused only if it is the GLOBAL one: sage_window_linearize / _prepass and the
+  // classic sequence leave a system behind that is not booked as reduced (every rank sees the same flags: same call
+  // sequence on all ranks)
   bool mirrored_now = false;
   if (!(w->have_lin && w->lin_epoch == w->vars_epoch && (!sharded || w->packed_reduced)))
   {
-    if ((rc = evaluate(0, w->packed.as<double>(), w->emu_cur)))
+    if ((rc = window_form_system(w, 0, w->packed.as<double>(), w->emu_cur)))
       return rc;
-    w->packed_reduced = true;
+    w->have_lin = true;
+    w->lin_epoch = w->vars_epoch;
+    w->packed_reduced = true; // (summed over the ranks, or nothing to sum)
     w->spec_err_valid = false;
     mirrored_now = true;
   }
@@ -2030,205 +2091,140 @@ static int lm_step_at_candidate(SageWindow *w, SageLmState *st, const SageLmConf
       return rc;
     if (!window_spin_totals(w, true))
       SAGE_HIP(hipStreamSynchronize(w->stream));
-    w->spec_error = w->h_err[0] + w->h_err[1] + prior_error(w, 0);
+    w->spec_error = mirrored_error(w, 0, 0);
     w->spec_err_valid = true;
   }
   st->error = w->spec_error;
-  int evals = 0;
-  st->accepted = 0;
-  for (;;)
-  {
-    rc = sage_window_solve(w, st->damp, nullptr);
-    bool not_psd = rc == SAGE_E_NOT_PSD;
-    if (rc && !not_psd)
-      return rc;
-    double cur_tot[4] = {0, 0, 0, 0};
-    bool have_cur_tot = false; // (a synchronous NOT_PSD of the solve leaves the mirror alone: nothing to put back)
-    st->candidate_error = INFINITY;
-    if (!not_psd)
-    {
-      const uint64_t lin_epoch = w->lin_epoch;
-      const bool was_reduced = w->packed_reduced;
-      std::memcpy(cur_tot, w->h_err, sizeof(cur_tot)); // (mirrored and seen at the end of the previous evaluation)
-      have_cur_tot = true;
-      if ((rc = evaluate(1, w->packed_save.as<double>(), w->emu_cur + 1)))
-        return rc;
-      w->lin_epoch = lin_epoch; // (`packed` still is the current estimate's system; the candidate's sits in packed_save)
-      w->packed_reduced = was_reduced;
-      w->spec_err_valid = true; // spec_error still is the error at the current estimate
-      const bool idle = window_spin_totals(w, true);
-      rc = window_sync_candidate(w, idle); // a non-positive pivot of the factorisation shows up here
-      if (rc && rc != SAGE_E_NOT_PSD)
-        return rc;
-      not_psd = rc == SAGE_E_NOT_PSD;
-      if (!idle)
-        SAGE_HIP(hipStreamSynchronize(w->stream));
-      if (!not_psd)
-        st->candidate_error = w->h_err[0] + w->h_err[1] + prior_error(w, 1);
-    }
-    ++evals;
-    if (st->candidate_error < st->error)
-    {
-      st->accepted = 1;
-      if ((rc = sage_window_accept(w)))
-        return rc;
-      std::swap(w->packed.p, w->packed_save.p); // the candidate's system IS the next iteration's
-      std::swap(w->packed.cap, w->packed_save.cap);
-      w->lin_epoch = w->vars_epoch;
-      w->packed_reduced = true; // (summed over the ranks by evaluate(), or nothing to sum)
-      w->spec_error = st->candidate_error;
-      st->damp = clampd(st->damp / cfg->damp_dec_factor);
-      break;
-    }
-    // rejected: `packed` never left; the mirror goes back to the current estimate's totals
-    if (have_cur_tot)
-      std::memcpy(w->h_err, cur_tot, sizeof(cur_tot));
-    const bool give_up = st->damp >= cfg->max_damp || (cfg->max_inner_evals > 0 && evals >= cfg->max_inner_evals);
-    st->damp = clampd(st->damp * cfg->damp_inc_factor);
-    if (give_up)
-      break;
-  }
-  st->iters += 1;
   return SAGE_OK;
+}
+
+// one damped solve at st->damp and the candidate's error -> st->candidate_error (INFINITY for a non-positive pivot,
+// reported by the solve at once or by window_sync_candidate: a rejected evaluation, not a hard error -- every rank factors
+// the same reduced system, so all of them take that branch together and issue the same collectives).  first: classic and
+// schur learn st->error here
+static int lm_evaluate(LmSeq seq, SageWindow *w, SageLmState *st, bool first, LmEval &ev)
+{
+  int rc;
+  const bool sharded = w->allreduce != nullptr;
+  if (seq == LmSeq::schur)
+  {
+    double lin_error = 0;
+    if ((rc = schur_solve(w, st->damp, &lin_error)) && rc != SAGE_E_NOT_PSD)
+      return rc;
+    window_phase_mark(w, 3);
+    if (first)
+      st->error = lin_error;
+    st->candidate_error = INFINITY;
+    if (rc == SAGE_E_NOT_PSD)
+      return SAGE_OK;
+    if ((rc = sage_window_error(w, 1)))
+      return rc;
+    hipLaunchKernelGGL(add_to_double_kernel, dim3(1), dim3(1), 0, w->stream, w->errbuf.as<double>(),
+                       prior_error_owned(w, 1));
+    if (w->allreduce(w->errbuf.as<double>(), 4, w->allreduce_user))
+      return SAGE_E_STATE;
+    double t4[4];
+    SAGE_HIP(hipMemcpyAsync(t4, w->errbuf.p, sizeof(t4), hipMemcpyDeviceToHost, w->stream));
+    SAGE_HIP(hipStreamSynchronize(w->stream));
+    st->candidate_error = t4[0] + t4[1];
+    return SAGE_OK;
+  }
+  // everything of one evaluation is enqueued before the host looks at a number
+  rc = sage_window_solve(w, st->damp, nullptr);
+  if (rc == SAGE_E_NOT_PSD) // (no error pass, no collective)
+  {
+    st->candidate_error = INFINITY;
+    return first && seq == LmSeq::classic ? sage_window_total_error(w, 1, &st->error) : SAGE_OK;
+  }
+  if (rc)
+    return rc;
+  if (seq == LmSeq::at_candidate)
+  {
+    std::memcpy(ev.cur_tot, w->h_err, sizeof(ev.cur_tot)); // (mirrored and seen at the end of the previous evaluation)
+    ev.have_cur_tot = true;
+    bool not_psd;
+    if ((rc = window_form_system(w, 1, w->packed_save.as<double>(), w->emu_cur + 1)) ||
+        (rc = window_wait_mirror(w, &not_psd)))
+      return rc;
+    st->candidate_error = not_psd ? INFINITY : mirrored_error(w, 0, 1);
+    return SAGE_OK;
+  }
+  if ((rc = window_error_pass(w, 1, !sharded)))
+    return rc;
+  if (!sharded)
+  {
+    // the error at the linearisation point (tail of the packed buffer) is read together with the candidate's
+    const bool idle = window_spin_totals(w);
+    if (first && (rc = window_total_error(w, 1, &st->error, idle)))
+      return rc;
+    if ((rc = window_total_error(w, 0, &st->candidate_error, idle)) == SAGE_E_NOT_PSD)
+      st->candidate_error = INFINITY;
+    return rc == SAGE_E_NOT_PSD ? SAGE_OK : rc;
+  }
+  bool not_psd;
+  if ((rc = window_allreduce(w, w->errbuf.as<double>(), 4, w->emu_cur + 1)) || (rc = window_mirror_totals(w, true)) ||
+      (rc = window_wait_mirror(w, &not_psd)))
+    return rc;
+  if (first)
+    st->error = mirrored_error(w, 0, 0);
+  st->candidate_error = not_psd ? INFINITY : mirrored_error(w, 4, 1);
+  return SAGE_OK;
+}
+
+// the candidate becomes the current estimate (at_candidate: and its system, formed in packed_save, the current system)
+static int lm_accept(LmSeq seq, SageWindow *w, const SageLmState *st)
+{
+  const int rc = sage_window_accept(w);
+  if (rc || seq != LmSeq::at_candidate)
+    return rc;
+  std::swap(w->packed.p, w->packed_save.p);
+  std::swap(w->packed.cap, w->packed_save.cap);
+  w->lin_epoch = w->vars_epoch;
+  w->packed_reduced = true; // (summed over the ranks by window_form_system, or nothing to sum)
+  w->spec_error = st->candidate_error;
+  return SAGE_OK;
+}
+
+// the candidate is dropped (at_candidate: the mirror goes back to the current estimate's totals)
+static void lm_reject(SageWindow *w, const LmEval &ev)
+{
+  if (ev.have_cur_tot)
+    std::memcpy(w->h_err, ev.cur_tot, sizeof(ev.cur_tot));
 }
 
 extern "C" int sage_window_lm_step(SageWindow *w, SageLmState *st, const SageLmConfig *cfg)
 {
   if (!w || !st || !cfg)
     return SAGE_E_INVALID;
-  int rc;
   if (w->world > 1 && !w->allreduce)
     return SAGE_E_STATE;
-  const bool sharded = w->allreduce != nullptr; // (a hook on a single-rank window is honoured too)
+  const LmSeq seq = lm_sequence_for(w, cfg);
+  auto clampd = [&](double d) { return std::min(std::max((double)cfg->min_damp, d), (double)cfg->max_damp); };
   if (st->iters == 0 && st->damp <= 0)
     st->damp = cfg->init_damp;
-  auto clampd = [&](double d) { return std::min(std::max((double)cfg->min_damp, d), (double)cfg->max_damp); };
-  const bool schur = sharded && w->shard != nullptr;
   window_phase_mark(w, 0);
-  // (rank-independent decision: the window's link count, not this rank's share of it -- a rank without links must
-  //  issue the same collectives as the others).  linearize_at_candidate 0 = automatic: the sequence with one collective
-  //  and no separate error pass per iteration whenever the window is reduced over ranks (the shard's kernels are short
-  //  there, the second collective and its host round trip are not), the classic sequence on a single rank
-  const bool at_candidate = cfg->linearize_at_candidate > 0 || (cfg->linearize_at_candidate == 0 && sharded);
-  if (at_candidate && !schur && !w->links.empty())
-    return lm_step_at_candidate(w, st, cfg, sharded);
-  if ((rc = window_linearize_set(w, 0, nullptr, false, true)))
+  int rc = lm_prepare(seq, w, st);
+  if (rc)
     return rc;
-  if (sharded && !schur && (rc = window_allreduce(w, w->packed.as<double>(), sage_window_packed_count(w), w->emu_cur)))
-    return rc;
-  window_phase_mark(w, 2);
-  int evals = 0;
   st->accepted = 0;
-  while (schur)
+  for (int evals = 1;; ++evals)
   {
-    // domain-decomposed iteration: the collectives are the separator system and the 4-double error totals
-    double lin_error = 0;
-    rc = schur_solve(w, st->damp, &lin_error);
-    if (rc && rc != SAGE_E_NOT_PSD)
+    LmEval ev{};
+    if ((rc = lm_evaluate(seq, w, st, evals == 1, ev)))
       return rc;
-    window_phase_mark(w, 3);
-    if (evals == 0)
-      st->error = lin_error;
-    if (rc == SAGE_E_NOT_PSD)
-      st->candidate_error = INFINITY;
-    else
-    {
-      if ((rc = sage_window_error(w, 1)))
-        return rc;
-      hipLaunchKernelGGL(add_to_double_kernel, dim3(1), dim3(1), 0, w->stream, w->errbuf.as<double>(),
-                         prior_error_owned(w, 1));
-      if (w->allreduce(w->errbuf.as<double>(), 4, w->allreduce_user))
-        return SAGE_E_STATE;
-      double t4[4];
-      SAGE_HIP(hipMemcpyAsync(t4, w->errbuf.p, sizeof(t4), hipMemcpyDeviceToHost, w->stream));
-      SAGE_HIP(hipStreamSynchronize(w->stream));
-      st->candidate_error = t4[0] + t4[1];
-    }
-    ++evals;
     if (st->candidate_error < st->error)
     {
       st->accepted = 1;
+      if ((rc = lm_accept(seq, w, st)))
+        return rc;
+      st->damp = clampd(st->damp / cfg->damp_dec_factor);
       break;
     }
+    lm_reject(w, ev);
     const bool give_up = st->damp >= cfg->max_damp || (cfg->max_inner_evals > 0 && evals >= cfg->max_inner_evals);
     st->damp = clampd(st->damp * cfg->damp_inc_factor);
     if (give_up)
       break;
-  }
-  while (!schur)
-  {
-    // everything of one evaluation is enqueued before the host looks at a number: the error at the linearisation
-    // point (tail of the packed buffer) is read together with the candidate's
-    rc = sage_window_solve(w, st->damp, nullptr);
-    if (rc == SAGE_E_NOT_PSD)
-    {
-      // the damped system has a non-positive pivot: a rejected evaluation (every rank factors the same system and
-      // takes this branch together; no error pass, no collective)
-      if (evals == 0 && (rc = sage_window_total_error(w, 1, &st->error)))
-        return rc;
-      st->candidate_error = INFINITY;
-      ++evals;
-      if (st->damp >= cfg->max_damp || (cfg->max_inner_evals > 0 && evals >= cfg->max_inner_evals))
-      {
-        st->damp = clampd(st->damp * cfg->damp_inc_factor);
-        break;
-      }
-      st->damp = clampd(st->damp * cfg->damp_inc_factor);
-      continue;
-    }
-    if (rc)
-      return rc;
-    if ((rc = window_error_pass(w, 1, !sharded)))
-      return rc;
-    if (sharded)
-    {
-      if ((rc = window_allreduce(w, w->errbuf.as<double>(), 4, w->emu_cur + 1)) || (rc = window_mirror_totals(w, true)))
-        return rc;
-      // (the host spins on the mirror's tickets instead of blocking in a stream synchronise: with the kernels of a shard
-      //  8x shorter, the 20-30 us wake-up of a blocked thread would be 4 % of an iteration)
-      const bool idle = window_spin_totals(w, true);
-      // a non-positive pivot of the damped system is a REJECTED evaluation (raise the damping), not a hard error; every
-      // rank factors the same reduced system, so all of them take this branch together and the number of collectives
-      // per iteration stays the same on every rank
-      rc = window_sync_candidate(w, idle);
-      if (rc && rc != SAGE_E_NOT_PSD)
-        return rc;
-      const bool not_psd = rc == SAGE_E_NOT_PSD;
-      if (!idle)
-        SAGE_HIP(hipStreamSynchronize(w->stream));
-      if (evals == 0)
-        st->error = w->h_err[0] + w->h_err[1] + prior_error(w, 0);
-      st->candidate_error = not_psd ? INFINITY : w->h_err[4] + w->h_err[5] + prior_error(w, 1);
-    }
-    else
-    {
-      const bool idle = window_spin_totals(w);
-      if (evals == 0 && (rc = window_total_error(w, 1, &st->error, idle)))
-        return rc;
-      rc = window_total_error(w, 0, &st->candidate_error, idle);
-      if (rc == SAGE_E_NOT_PSD)
-        st->candidate_error = INFINITY;
-      else if (rc)
-        return rc;
-    }
-    ++evals;
-    if (st->candidate_error < st->error)
-    {
-      st->accepted = 1;
-      break;
-    }
-    if (st->damp >= cfg->max_damp || (cfg->max_inner_evals > 0 && evals >= cfg->max_inner_evals))
-    {
-      st->damp = clampd(st->damp * cfg->damp_inc_factor);
-      break;
-    }
-    st->damp = clampd(st->damp * cfg->damp_inc_factor);
-  }
-  if (st->accepted)
-  {
-    if ((rc = sage_window_accept(w)))
-      return rc;
-    st->damp = clampd(st->damp / cfg->damp_dec_factor);
   }
   st->iters += 1;
   return SAGE_OK;

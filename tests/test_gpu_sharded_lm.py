@@ -1,5 +1,6 @@
 """Sharded LM iteration on the GPU: two ranks (gloo, both on cuda:0) drive sage_window_lm_step through the all-reduce
 hook (sage_window_set_allreduce) and must walk the same LM trajectory as the single-rank window."""
+import json
 import os
 import socket
 
@@ -18,16 +19,34 @@ def _make():
     return synth.make_window(K=6, H=48, W=64, FS=16, CS=32, L=3, n_samples=900, seed=5)
 
 
-def _run(win, capi, steps, at_candidate=False):
+def _run(win, capi, steps, at_candidate=False, rec=None):
     cfg = capi.lm_config_default()
     cfg.max_inner_evals = 1
     cfg.linearize_at_candidate = {True: 1, False: -1, None: 0}[at_candidate]   # None: the engine's automatic choice
     st = capi.SageLmState()
     trace = []
     for _ in range(steps):
+        if rec is not None:
+            rec.step()
         win.lm_step(st, cfg)
         trace.append((st.error, st.candidate_error, int(st.accepted), st.damp))
     return np.array(trace)
+
+
+class _Recorder:
+    """torch.distributed stand-in for Window.set_allreduce: records the size of every all-reduce the hook is entered for,
+    per LM step; `dist` (optional) then does the sum."""
+
+    def __init__(self, dist=None):
+        self.dist, self.steps = dist, []
+
+    def step(self):
+        self.steps.append([])
+
+    def all_reduce(self, t, group=None):
+        self.steps[-1].append(t.numel())
+        if self.dist is not None:
+            self.dist.all_reduce(t, group=group)
 
 
 def _worker(rank, world, port, out_dir):
@@ -112,8 +131,11 @@ def _schur_worker(rank, world, port, out_dir):
     from sage_slam_amd import capi
     w = _make_long()
     win = capi.Window(w, rank=rank, world=world)
-    win.set_allreduce(dist)
-    np.save(os.path.join(out_dir, f"strace_{rank}.npy"), _run(win, capi, 4))
+    rec = _Recorder(dist)
+    win.set_allreduce(rec)
+    np.save(os.path.join(out_dir, f"strace_{rank}.npy"), _run(win, capi, 4, rec=rec))
+    with open(os.path.join(out_dir, f"scalls_{rank}.json"), "w") as f:
+        json.dump(rec.steps, f)
     win.sync_variables()
     np.save(os.path.join(out_dir, f"svars_{rank}.npy"), _all_vars(win, len(w.keyframes)))
     dist.destroy_process_group()
@@ -137,6 +159,57 @@ def test_schur_sharded_lm_step_matches_single_rank(tmp_path, world):
     for r in range(world):
         v = np.load(tmp_path / f"svars_{r}.npy")
         assert np.abs(v - v_ref).max() < 2e-5 * max(1.0, np.abs(v_ref).max())
+    # the collectives: per evaluation (max_inner_evals = 1: one per step) the separator system, then the 4 error totals
+    # when the evaluation reached the error pass -- the same list on every rank
+    calls = [json.loads((tmp_path / f"scalls_{r}.json").read_text()) for r in range(world)]
+    plan = capi.ShardPlan(len(w.keyframes), w.links, ref.B, 0, world)
+    ns = plan.sep_count
+    plan.close()
+    assert ns != 4 and all(c == calls[0] for c in calls[1:])
+    assert calls[0] == [[ns, 4] if np.isfinite(cand) else [ns] for cand in traces[0][:, 1]]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# which collectives each sequence issues: a one-rank window with a recording all-reduce hook (the engine honours a hook
+# on a single rank; the sum over one rank leaves the buffer as it is).  classic: the packed system, then the 4 error
+# totals per evaluation; linearize-at-candidate (forced or automatic): the candidate's packed system per evaluation, and
+# one more first whenever the system at the current estimate has to be formed (first step, after a reset)
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dec,inner", [(10.0, 1), (1.0e5, 0)])       # (1e5, 0): rejections, as in test_gpu_parity
+def test_collectives_of_each_lm_sequence(dec, inner):
+    from sage_slam_amd import capi, synth
+    w = synth.make_window(K=8, H=48, W=64, FS=16, CS=32, L=3, n_samples=1500, seed=14)
+
+    def run(variant):
+        win, rec = capi.Window(w), _Recorder()
+        win.set_allreduce(rec)
+        cfg = capi.lm_config_default()
+        cfg.damp_dec_factor = dec; cfg.max_inner_evals = inner; cfg.linearize_at_candidate = variant
+        st, accepted = capi.SageLmState(), []
+        for i in range(steps):
+            if i == 9:                                          # back to the initial variables: the system is formed anew
+                win.reset(); st = capi.SageLmState()
+            rec.step()
+            win.lm_step(st, cfg)
+            accepted.append(st.accepted)
+        npk = win.packed_count
+        win.close()
+        return rec.steps, accepted, npk
+
+    steps = 11
+    classic, acc, npk = run(-1)
+    assert npk != 4
+    evals = [len(c) - 1 for c in classic]
+    assert classic == [[npk] + [4] * e for e in evals] and min(evals) >= 1
+    if inner == 1:
+        assert evals == [1] * steps
+    else:
+        assert sum(evals) > steps                               # the config rejects
+    formed = [1 if i in (0, 9) else 0 for i in range(steps)]
+    for variant in (1, 0):
+        calls, acc_v, _ = run(variant)
+        assert acc_v == acc                                     # same decisions
+        assert calls == [[npk] * (f + e) for f, e in zip(formed, evals)]
 
 
 # ---------------------------------------------------------------------------------------------------------------
