@@ -374,12 +374,15 @@ int sage_window_num_links(const SageWindow *w);
 int sage_window_block_size(const SageWindow *w);       /* B = 7 + CS: [pose6, code CS, scale] */
 /* packed normal-equation buffer (device, DOUBLE), the all-reduce payload:
  *   [ diag blocks K*B*B | link blocks nlinks*B*B (row = older kf, col = newer kf) | g K*B | err_photo err_geo n_photo n_geo ]
+ * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry terms';
+ * the two inlier counts stay dense-only -- see sage_window_add_keypoint_term)
  * fp32 per-edge results are summed in double, like the reference widens AtA/Atb to double before gtsam adds
  * the factors (core/gtsam/photometric_factor.cpp:305-306); keeping the payload in double keeps the sum exact
  * across ranks too. */
 size_t sage_window_packed_count(const SageWindow *w);
 double *sage_window_packed_dev(SageWindow *w);
-/* number of residuals one linearize evaluates on this shard (E_photo*L*N*FS + E_geo*N) and its algorithmic bytes */
+/* number of residuals one linearize evaluates on this shard (E_photo*L*N*FS + E_geo*N, + 2N / 3N per reprojection /
+ * match-geometry term) and its algorithmic bytes (dense factors) */
 double sage_window_residuals_per_linearize(const SageWindow *w);
 double sage_window_bytes_per_linearize(const SageWindow *w);
 
@@ -421,6 +424,47 @@ int sage_window_get_delta(const SageWindow *w, double *delta);
  * the two -- what the assembly forms -- is the same normal equations. */
 int sage_window_get_edge(const SageWindow *w, int type, int e, float *AtA, float *Atb, float *err, float *n_in);
 
+/* Matched-keypoint terms on the directed edges of a window: the mapper's third factor type (core/mapping/mapper.cpp:346-374
+ * adds photometric, reprojection and geometric factors per link and direction; demo/main.cpp:254-278: weight 5, loss
+ * 0.1 W^2, up to 512 keypoints).  Same arithmetic as the per-edge operators below (sage_reprojection_jac_error_calculate,
+ * sage_match_geometry_jac_error_calculate), but every term of the window is evaluated in ONE launch per linearize / error
+ * pass and summed into the same packed system and error totals as the dense factors, so sage_window_solve, sage_window_lm_step
+ * and the sharded sequences see them without knowing.
+ *   kind SAGE_KP_REPROJECTION    fair loss, D = 13+CS [pose0 pose1 code0 scale0] (the photometric edge layout), 2N residuals
+ *   kind SAGE_KP_MATCH_GEOMETRY  loss SAGE_LOSS_*, D = 14+2CS [pose0 pose1 code0 code1 scale0 scale1] (the geometric edge
+ *                                layout), 3N residuals
+ * `edge` = 2 * link + direction as sage_window_get_edge numbers them; keyframe "0" is the direction's source.  Camera =
+ * cfg.pyr.cam[0], eps = cfg.eps; bias / basis / code / scale / pose are the window's keyframes' at the variable set being
+ * evaluated.  Add after the edge's link and before sage_window_finalize (SAGE_E_STATE afterwards); any number of terms per
+ * edge; SAGE_E_INVALID for a bad edge / kind / loss, N < 1 (the reference adds no factor without matches,
+ * core/mapping/df_work.cpp:416), a missing array or a location outside the image.  The arrays are DEVICE memory and are
+ * copied by the call (unlike the keyframe views): the caller may free them afterwards.  Returns the term id >= 0: ids count
+ * the add calls of the whole window.  On a sharded window a term belongs to the rank that owns its directed edge (settled at
+ * finalize: add and sage_window_set_shard may come in either order); reading a term of another rank answers SAGE_E_INVALID.
+ * get_keypoint_term: host copy of the term's last linearize in the reference's per-edge layout (AtA [D,D], Atb [D], error;
+ * n_in = inliers for reprojection, N for match geometry); SAGE_E_STATE before the first linearize.
+ * Totals: the terms' errors ride in the two error slots of the 4-double tails (packed buffer, error buffer) -- reprojection in
+ * the photometric slot, match geometry in the geometric one: slot 0 + slot 1 = sum of dense + sum of keypoint errors.  The
+ * inlier slots stay dense-only.  Not covered: the gtsam factor cache (sage_window_prepass / sage_window_factor serve the dense
+ * factors only), the loop-closure variant with fixed depths, links that carry keypoint terms but no dense factor. */
+enum { SAGE_KP_REPROJECTION = 0, SAGE_KP_MATCH_GEOMETRY = 1 };
+typedef struct SageKeypointTerm
+{
+  int32_t kind;                   /* SAGE_KP_*                                                          */
+  int32_t edge;                   /* directed edge 2*link + direction, numbered as sage_window_get_edge */
+  int32_t N;                      /* matched keypoints, >= 1                                            */
+  const int32_t *loc1d_0;         /* [N]   device: flat pixel of the keypoint in the edge's keyframe "0" */
+  const float *homo0;             /* [N,3] device                                                       */
+  const float *matched_2d;        /* reprojection:   [N,2] device, pixels in keyframe "1"               */
+  const int32_t *matched_loc1d_1; /* match geometry: [N]   device                                       */
+  const float *matched_homo1;     /* match geometry: [N,3] device                                       */
+  float loss_param, weight;
+  int32_t loss;                   /* match geometry: SAGE_LOSS_*; ignored for reprojection              */
+} SageKeypointTerm;
+int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTerm *t);
+int sage_window_num_keypoint_terms(const SageWindow *w);
+int sage_window_get_keypoint_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err, float *n_in);
+
 /* f2 (core/gtsam/photometric_factor.cpp:72-219, geometric_factor.cpp:41-233, mapper.cpp:544-551): the
  * batched per-Values prepass behind the gtsam factors.  ISAM2 calls linearize(values) / error(values) factor by factor
  * with the same Values; the adapter's factor hands the window's values over and the engine evaluates the WHOLE window
@@ -454,8 +498,8 @@ int sage_factor_cut_blocks(int type, int CS, const double *C, const float *Atb, 
                            int32_t *dims_out, int32_t *nkeys_out);
 
 /* kernel timing with HIP events on the engine's own stream (bench.py's roofline): when enabled every launch of
- * the four hot kernels is bracketed by an event pair.  which: 0 photometric linearize, 1 geometric linearize,
- * 2 photometric error, 3 geometric error.  get_kernel_time synchronises, returns the accumulated milliseconds and
+ * the hot kernels is bracketed by an event pair.  which: 0 photometric linearize, 1 geometric linearize,
+ * 2 photometric error, 3 geometric error, 4 keypoint-term linearize, 5 keypoint-term error.  get_kernel_time synchronises, returns the accumulated milliseconds and
  * launch count since the last reset, and resets them. */
 /* on: 0 off, 1 every hot kernel + the phase marks, 2 the photometric linearize only (two event records per iteration
  * instead of eleven: each record is a few microseconds of the stream's time). */

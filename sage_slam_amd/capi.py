@@ -70,6 +70,15 @@ class SageWindowConfig(C.Structure):
                 ("use_photo", C.c_int32), ("use_geo", C.c_int32)]
 
 
+SAGE_KP_REPROJECTION, SAGE_KP_MATCH_GEOMETRY = 0, 1
+
+
+class SageKeypointTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("edge", C.c_int32), ("N", C.c_int32), ("loc1d_0", C.c_void_p), ("homo0", C.c_void_p),
+                ("matched_2d", C.c_void_p), ("matched_loc1d_1", C.c_void_p), ("matched_homo1", C.c_void_p),
+                ("loss_param", C.c_float), ("weight", C.c_float), ("loss", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -98,7 +107,7 @@ SYMBOLS = [
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
     "sage_window_error", "sage_window_tune_runs", "sage_window_set_runs", "sage_window_error_dev", "sage_window_solve", "sage_window_total_error",
     "sage_window_accept", "sage_window_reset", "sage_window_get_keyframe", "sage_window_set_keyframe", "sage_window_get_delta",
-    "sage_window_get_edge", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_factor_psd", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
+    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_factor_psd", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
     "sage_valid_locations", "sage_shuffle_indices", "sage_sample_locations",
     "sage_reprojection_jac_error_calculate", "sage_reprojection_error_calculate",
     "sage_tracker_reproj_jac_error_calculate", "sage_tracker_reproj_error_calculate",
@@ -489,7 +498,11 @@ class Window:
     """``SageWindow``: batched K-keyframe BA window on one GPU (one shard of the edge set)."""
 
     def __init__(self, win, rank: int = 0, world: int = 1, stream=None, use_photo=True, use_geo=True,
-                 code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4):
+                 code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None):
+        """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches``,
+        or by hand): kind ("reprojection" | "match_geometry"), edge (2 * link + direction), loc0 [N] int32, homo0 [N,3],
+        matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry, loss (a MG_LOSS name).
+        They are added before the finalize this constructor performs."""
         import torch
         self.win = win
         self.pyr = make_pyramid(win.cams[0], win.L)
@@ -525,6 +538,11 @@ class Window:
             gl = getattr(win, "link_geo_loss", None)     # optional per-link Cauchy parameters (mapper.cpp:367-373)
             if gl is not None and gl[r] > 0:
                 _chk(L.sage_window_set_link_geo_loss(self.h, r, C.c_float(gl[r])), "sage_window_set_link_geo_loss")
+        self.keypoint_terms = list(keypoint_terms or [])
+        for t in self.keypoint_terms:
+            r = self.add_keypoint_term(t)
+            if r < 0:
+                raise SageError(r, "sage_window_add_keypoint_term")
         _chk(L.sage_window_set_shard(self.h, rank, world), "sage_window_set_shard")
         _chk(L.sage_window_finalize(self.h), "sage_window_finalize")
         self.K = L.sage_window_num_keyframes(self.h)
@@ -533,6 +551,48 @@ class Window:
         self.packed_count = L.sage_window_packed_count(self.h)
         self.residuals_per_linearize = L.sage_window_residuals_per_linearize(self.h)
         self.bytes_per_linearize = L.sage_window_bytes_per_linearize(self.h)
+
+    def add_keypoint_term(self, t) -> int:
+        """``sage_window_add_keypoint_term`` with the arrays of dict ``t`` uploaded for the call (the engine copies them);
+        returns the term id, or the negative status code."""
+        import torch
+        kind = {"reprojection": SAGE_KP_REPROJECTION, "match_geometry": SAGE_KP_MATCH_GEOMETRY}.get(t["kind"], t["kind"])
+        mg = "loc1" in t
+        N = int(np.asarray(t["loc0"]).shape[0])
+        dev = dict(loc0=_dev(t["loc0"], np.int32), homo0=_dev(t["homo0"], np.float32))
+        kt = SageKeypointTerm()
+        kt.kind = int(kind)
+        kt.edge, kt.N = int(t["edge"]), N
+        kt.loc1d_0, kt.homo0 = dev["loc0"].data_ptr(), dev["homo0"].data_ptr()
+        if mg:
+            dev["loc1"] = _dev(t["loc1"], np.int32); dev["homo1"] = _dev(t["homo1"], np.float32)
+            kt.matched_loc1d_1, kt.matched_homo1 = dev["loc1"].data_ptr(), dev["homo1"].data_ptr()
+            loss = t.get("loss", "fair")
+            kt.loss = MG_LOSS[loss] if isinstance(loss, str) else int(loss)
+        else:
+            dev["m2d"] = _dev(t["matched_2d"], np.float32)
+            kt.matched_2d = dev["m2d"].data_ptr()
+        kt.loss_param, kt.weight = float(t["loss_param"]), float(t["weight"])
+        torch.cuda.synchronize()
+        return int(lib().sage_window_add_keypoint_term(self.h, C.byref(kt)))
+
+    def num_keypoint_terms(self) -> int:
+        return int(lib().sage_window_num_keypoint_terms(self.h))
+
+    def get_keypoint_term(self, i, check=True):
+        """host copy of term i's last linearize -> dict(AtA [D,D], Atb [D], error, num_inliers); with ``check=False`` the
+        status code is returned next to the dict instead of raising."""
+        kind = self.keypoint_terms[i]["kind"] if 0 <= i < len(self.keypoint_terms) else "reprojection"
+        mg = kind in ("match_geometry", SAGE_KP_MATCH_GEOMETRY)
+        D = 14 + 2 * self.win.CS if mg else 13 + self.win.CS
+        A = np.zeros((D, D), np.float32); b = np.zeros(D, np.float32)
+        err = C.c_float(); nin = C.c_float()
+        rc = lib().sage_window_get_keypoint_term(self.h, int(i), _fp(A), _fp(b), C.byref(err), C.byref(nin))
+        out = dict(AtA=A, Atb=b, error=err.value, num_inliers=nin.value)
+        if not check:
+            return rc, out
+        _chk(rc, "sage_window_get_keypoint_term")
+        return out
 
     # raw-pointer views for torch.distributed (plumbing only)
     def packed_tensor(self):
@@ -704,7 +764,8 @@ class Window:
         _chk(lib().sage_window_set_profiling(self.h, int(on)), "sage_window_set_profiling")
 
     def kernel_time(self, which: int):
-        """(total_ms, launches) of hot kernel `which` since the last call (0 photo lin, 1 geo lin, 2 photo err, 3 geo err)."""
+        """(total_ms, launches) of hot kernel `which` since the last call (0 photo lin, 1 geo lin, 2 photo err, 3 geo err,
+        4 keypoint-term linearize, 5 keypoint-term error)."""
         ms = C.c_double(); n = C.c_int()
         _chk(lib().sage_window_get_kernel_time(self.h, which, C.byref(ms), C.byref(n)), "sage_window_get_kernel_time")
         return ms.value, n.value

@@ -12,6 +12,7 @@
 // Second half of the file: cuda/match_geometry_factor_kernels.cpp (13 kernels there, one templated kernel here).
 #include "sage_device.h"
 #include "sage_internal.h"
+#include "keypoint_batch.h"
 
 namespace sage
 {
@@ -32,11 +33,12 @@ struct ReprojParams
   float *sval; // [N]
 };
 
-// MODE 0: mapper factor (D = 13+CS), MODE 1: tracker (D = 6)
-template <int CS, int MODE, bool JAC>
+// MODE 0: mapper factor (D = 13+CS), MODE 1: tracker (D = 6); LD: row stride in floats (0: D + 1, the residual column last)
+template <int CS, int MODE, bool JAC, int LD = 0>
 __device__ __forceinline__ void reproj_rows_body(const ReprojParams &p, int idx)
 {
   constexpr int D = MODE == 0 ? 13 + CS : 6;
+  constexpr int RS = LD ? LD : D + 1;
   const float fx = p.cam.fx, fy = p.cam.fy, cx = p.cam.cx, cy = p.cam.cy;
   const float hm[3] = {p.homo[3 * idx + 0], p.homo[3 * idx + 1], p.homo[3 * idx + 2]};
   float d0;
@@ -71,7 +73,7 @@ __device__ __forceinline__ void reproj_rows_body(const ReprojParams &p, int idx)
     return;
   const float inv_z = 1.0f / X[2];
   const float x_z = inv_z * X[0], y_z = inv_z * X[1];
-  float *row0 = p.rows + ((size_t)idx * 2 + 0) * (D + 1), *row1 = p.rows + ((size_t)idx * 2 + 1) * (D + 1);
+  float *row0 = p.rows + ((size_t)idx * 2 + 0) * RS, *row1 = p.rows + ((size_t)idx * 2 + 1) * RS;
   if (MODE == 1)
   {
     const float J0[6] = {fx * inv_z, 0.f, -fx * x_z * inv_z, -fx * x_z * y_z, fx * (1.0f + x_z * x_z), -fx * y_z}; // :348
@@ -400,10 +402,11 @@ struct MgParams
   float *rows, *serr, *sval;
 };
 
-template <int CS, int MODE, bool JAC>
+template <int CS, int MODE, bool JAC, int LD = 0>
 __device__ __forceinline__ void mg_rows_body(const MgParams &p, int idx)
 {
   constexpr int D = MODE == 0 ? 14 + 2 * CS : (MODE == 1 ? 14 : (MODE == 2 ? 6 : 7));
+  constexpr int RS = LD ? LD : D + 1;
   const float h0[3] = {p.homo0[3 * idx + 0], p.homo0[3 * idx + 1], p.homo0[3 * idx + 2]};
   const float h1[3] = {p.homo1[3 * idx + 0], p.homo1[3 * idx + 1], p.homo1[3 * idx + 2]};
   const float ss = p.scale0 + p.scale1;
@@ -504,7 +507,7 @@ __device__ __forceinline__ void mg_rows_body(const MgParams &p, int idx)
 #pragma unroll
   for (int i = 0; i < 3; ++i)
   {
-    float *row = p.rows + ((size_t)idx * 3 + i) * (D + 1);
+    float *row = p.rows + ((size_t)idx * 3 + i) * RS;
 #pragma unroll
     for (int j = 0; j < 6; ++j)
     {
@@ -786,6 +789,228 @@ hipError_t launch_cycle_match(hipStream_t s, const float *desc0, const float *de
   hipLaunchKernelGGL(best_match_kernel, dim3(grid), dim3(256), shm, s, desc1, raw_matched1, desc0, K, C, HW, cyc_matched0);
   hipLaunchKernelGGL(cycle_flags_kernel, dim3((K + 255) / 256), dim3(256), 0, s, kp_loc0, cyc_matched0, K, W, cyc_thresh,
                      inlier, n_inliers_dev);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// window terms (sage_window_add_keypoint_term): every local term of a window in ONE launch, a workgroup per term.
+// The per-edge operators above write the weighted rows to memory and contract them in a second launch (D workgroups);
+// here the rows of kKpChunk keypoints at a time stay in LDS (stride padded to four floats: 64 x 2 x 48 floats = 24 KB for
+// reprojection at CS = 32, 64 x 3 x 80 = 60 KB for match geometry) and are contracted into per-thread 4 x 4 register tiles of
+// [AtA | Atb] that live across the chunks: two 16-byte LDS reads per 16 multiply-adds.  Only the tiles on and above the
+// diagonal are formed (CS = 32: 78 / 210 of them, so 256 / tiles row groups share a chunk's rows) and mirrored on the way
+// out.  Sums in double, every order fixed (rows ascending per group, groups ascending, lanes by shuffle): no atomics,
+// bit-reproducible.  weight / n_inliers, the 10 * weight fallback and the statistics are folded in by the same workgroup.
+// The relative pose is formed here from the window's variable array, as the dense kernels do.
+// ------------------------------------------------------------------------------------------------
+template <int CS, int KIND, bool JAC>
+__device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams &prm, const float *s_pose, float *s_rows,
+                                            float *s_err, float *s_val, double *s_red)
+{
+  constexpr int D = KIND == 0 ? 13 + CS : 14 + 2 * CS;
+  constexpr int RPP = KIND == 0 ? 2 : 3;
+  constexpr int LD = (D + 1 + 3) / 4 * 4;
+  constexpr int NT = LD / 4;               // tiles per side (rows past D are dropped on the way out)
+  constexpr int NTILES = NT * (NT + 1) / 2;
+  constexpr int NGRP = 256 / NTILES;
+  static_assert(NGRP >= 1, "more tiles than threads");
+  static_assert((size_t)NTILES * 16 * sizeof(double) <= (size_t)kKpChunk * RPP * LD * sizeof(float), "group fold scratch");
+  const int tid = threadIdx.x;
+  const float *x0 = prm.vars + (size_t)T.k0 * prm.VS, *x1 = prm.vars + (size_t)T.k1 * prm.VS;
+  ReprojParams rp{};
+  MgParams mp{};
+  if (KIND == 0)
+  {
+    rp.R10 = s_pose; rp.t10 = s_pose + 9; rp.R0 = x0; rp.t0 = x0 + 9; rp.R1 = x1; rp.t1 = x1 + 9;
+    rp.bias0 = T.bias0; rp.basis0 = T.basis0; rp.code0 = x0 + 13; rp.scale0 = x0[12];
+    rp.cam = prm.cam; rp.eps = prm.eps; rp.loss_param = T.loss_param; rp.weight = T.weight;
+    rp.rows = s_rows; rp.serr = s_err; rp.sval = s_val;
+  }
+  else
+  {
+    mp.R10 = s_pose; mp.t10 = s_pose + 9; mp.R0 = x0; mp.t0 = x0 + 9; mp.R1 = x1; mp.t1 = x1 + 9;
+    mp.bias0 = T.bias0; mp.bias1 = T.bias1; mp.basis0 = T.basis0; mp.basis1 = T.basis1;
+    mp.code0 = x0 + 13; mp.code1 = x1 + 13; mp.scale0 = x0[12]; mp.scale1 = x1[12];
+    mp.loss_param = T.loss_param; mp.weight = T.weight; mp.loss = T.loss;
+    mp.rows = s_rows; mp.serr = s_err; mp.sval = s_val;
+  }
+  // this thread's tile (ti <= tj) and row group
+  const int grp = tid / NTILES;
+  const bool active = JAC && grp < NGRP;
+  int ti = 0, tj = 0;
+  {
+    int rem = tid % NTILES;
+    while (rem >= NT - ti)
+    {
+      rem -= NT - ti;
+      ++ti;
+    }
+    tj = ti + rem;
+  }
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[i][j] = 0.0;
+  double se = 0.0, sn = 0.0; // lanes of wave 0: keypoint `lane` of every chunk
+  for (int c0 = 0; c0 < T.N; c0 += kKpChunk)
+  {
+    const int cnt = min(kKpChunk, T.N - c0);
+    if (tid < cnt)
+    {
+      if (KIND == 0)
+      {
+        rp.loc = T.loc0 + c0; rp.homo = T.homo0 + (size_t)3 * c0; rp.matched = T.matched + (size_t)2 * c0; rp.N = cnt;
+        reproj_rows_body<CS, 0, JAC, LD>(rp, tid);
+      }
+      else
+      {
+        mp.loc0 = T.loc0 + c0; mp.loc1 = T.loc1 + c0; mp.homo0 = T.homo0 + (size_t)3 * c0; mp.homo1 = T.homo1 + (size_t)3 * c0;
+        mp.N = cnt;
+        mg_rows_body<CS, 0, JAC, LD>(mp, tid);
+      }
+      if (JAC)
+        for (int r = 0; r < RPP; ++r) // the padding columns take part in the tiles: keep them finite
+          for (int c = D + 1; c < LD; ++c)
+            s_rows[((size_t)tid * RPP + r) * LD + c] = 0.f;
+    }
+    __syncthreads();
+    if (tid < cnt)
+    {
+      se += (double)s_err[tid];
+      sn += (double)s_val[tid];
+    }
+    if (active)
+    {
+      const float *ra = s_rows + 4 * ti, *rb = s_rows + 4 * tj;
+      for (int k = grp; k < RPP * cnt; k += NGRP)
+      {
+        const float4 a = *reinterpret_cast<const float4 *>(ra + (size_t)k * LD);
+        const float4 b = *reinterpret_cast<const float4 *>(rb + (size_t)k * LD);
+        const double av[4] = {(double)a.x, (double)a.y, (double)a.z, (double)a.w};
+        const double bv[4] = {(double)b.x, (double)b.y, (double)b.z, (double)b.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] += av[i] * bv[j];
+      }
+    }
+    __syncthreads();
+  }
+  // statistics: wave 0, fixed lane order
+  if (tid < 64)
+  {
+    for (int off = 32; off > 0; off >>= 1)
+    {
+      se += __shfl_down(se, off);
+      sn += __shfl_down(sn, off);
+    }
+    if (tid == 0)
+    {
+      s_red[0] = sn;
+      s_red[1] = se;
+    }
+  }
+  __syncthreads();
+  const double ninl = s_red[0];
+  const double sc = ninl > 0.0 ? (double)T.weight / ninl : 0.0;
+  if (tid == 0)
+  {
+    prm.stats[2 * (size_t)T.stat + 0] = ninl > 0.0 ? (float)(sc * s_red[1]) : T.weight * 10.0f;
+    prm.stats[2 * (size_t)T.stat + 1] = (float)ninl;
+  }
+  if (!JAC)
+    return;
+  // row groups folded into group 0, one after the other (the rows' LDS is free now)
+  double *s_fold = reinterpret_cast<double *>(s_rows);
+  for (int g = 1; g < NGRP; ++g)
+  {
+    if (grp == g)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          s_fold[((size_t)(i * 4 + j)) * NTILES + tid % NTILES] = acc[i][j];
+    __syncthreads();
+    if (grp == 0)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] += s_fold[((size_t)(i * 4 + j)) * NTILES + tid];
+    __syncthreads();
+  }
+  if (grp != 0)
+    return;
+  float *AtA = (KIND == 0 ? prm.AtA_r : prm.AtA_m) + (size_t)T.out * D * D;
+  float *Atb = (KIND == 0 ? prm.Atb_r : prm.Atb_m) + (size_t)T.out * D;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+      const int r = 4 * ti + i, c = 4 * tj + j;
+      if (r >= D || c > D)
+        continue;
+      const float v = (float)(sc * acc[i][j]);
+      if (c == D)
+        Atb[r] = v;
+      else
+      {
+        AtA[(size_t)r * D + c] = v;
+        if (ti != tj)
+          AtA[(size_t)c * D + r] = v;
+      }
+    }
+}
+
+template <int CS, bool JAC>
+__global__ __launch_bounds__(256) void keypoint_batch_kernel(const KpBatchParams prm)
+{
+  extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+  __shared__ float s_pose[12], s_err[kKpChunk], s_val[kKpChunk];
+  __shared__ double s_red[2];
+  const KpTerm T = prm.terms[blockIdx.x];
+  if (threadIdx.x == 0)
+  {
+    const Pose p10 = relative_pose(load_pose(prm.vars + (size_t)T.k0 * prm.VS), load_pose(prm.vars + (size_t)T.k1 * prm.VS));
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+      s_pose[i] = p10.R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      s_pose[9 + i] = p10.t[i];
+  }
+  __syncthreads();
+  if (T.kind == SAGE_KP_REPROJECTION)
+    kp_term_run<CS, 0, JAC>(T, prm, s_pose, s_dyn, s_err, s_val, s_red);
+  else
+    kp_term_run<CS, 1, JAC>(T, prm, s_pose, s_dyn, s_err, s_val, s_red);
+}
+
+hipError_t launch_keypoint_batch(hipStream_t s, int CS, bool jac, int n_terms, bool any_match_geometry, const KpBatchParams &p)
+{
+  if (n_terms <= 0)
+    return hipSuccess;
+  const size_t lds = jac ? kp_batch_lds_bytes(CS, any_match_geometry) : 0; // (the error variant forms no rows)
+  if (CS == 32)
+  {
+    if (jac)
+      hipLaunchKernelGGL((keypoint_batch_kernel<32, true>), dim3(n_terms), dim3(256), lds, s, p);
+    else
+      hipLaunchKernelGGL((keypoint_batch_kernel<32, false>), dim3(n_terms), dim3(256), lds, s, p);
+  }
+  else if (CS == 16)
+  {
+    if (jac)
+      hipLaunchKernelGGL((keypoint_batch_kernel<16, true>), dim3(n_terms), dim3(256), lds, s, p);
+    else
+      hipLaunchKernelGGL((keypoint_batch_kernel<16, false>), dim3(n_terms), dim3(256), lds, s, p);
+  }
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -42,6 +42,7 @@ extern "C"
 #include "host_math.h"
 #include "sage_ba.h"
 #include "sage_internal.h"
+#include "keypoint_batch.h"
 
 using namespace sage;
 
@@ -177,8 +178,8 @@ namespace sage
 {
 struct AdjEntry // one (edge, role) incidence of a keyframe
 {
-  int32_t type; // 0 photo, 1 geo
-  int32_t edge; // local edge index
+  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1)
+  int32_t edge; // local edge index; types 2 / 3: index among the local terms of the kind
   int32_t role; // 0: keyframe is the edge's source ("0"), 1: destination ("1")
 };
 
@@ -200,6 +201,18 @@ struct AssembleParams
   int K, nlinks, CS, n_edges_p, n_edges_g;
   int split;               // > 1: every output block is shared by `split` consecutive workgroups (small workgroups)
   const int32_t *blocks;   // optional: the output blocks to assemble (ids 0..K-1 keyframes, K..K+nlinks-1 links, K+nlinks tail)
+  // keypoint terms (null / 0 without them): per-kind results, {error, inliers} of all local terms (reprojection first), and
+  // per link the terms on its two directions (AdjEntry::role = direction)
+  const float *AtA_kr, *Atb_kr, *AtA_km, *Atb_km, *stats_k;
+  const int32_t *link_kp_start; // [nlinks+1]
+  const AdjEntry *link_kp;
+  int n_kr, n_km;
+};
+
+struct KpTotals // error pass: the local terms' {error, inliers}, reprojection first
+{
+  const float *stats;
+  int n_kr, n_km;
 };
 
 struct ErrorTotalsSide
@@ -290,6 +303,21 @@ struct SageWindow
                                           // ever written, the rest stays zero), the send buffer of the out-of-place all-reduce
   DevBuf asm_blocks;                      // ids of those blocks (keyframes, links, tail) for the assembly of packed_loc
   int n_asm_blocks = 0;
+  // matched-keypoint terms (sage_window_add_keypoint_term): host copies as added, then (finalize) this rank's terms in one
+  // device pool + table, reprojection terms first
+  struct KeypointTermHost
+  {
+    int32_t kind, edge, N, loss;
+    float loss_param, weight;
+    std::vector<int32_t> loc0, loc1;
+    std::vector<float> homo0, second; // second: matched_2d [N,2] (reprojection) or matched_homo1 [N,3] (match geometry)
+  };
+  std::vector<KeypointTermHost> kp_added;
+  std::vector<int> kp_local;            // per term id: index among this rank's terms, -1 = another rank's
+  int n_kr = 0, n_km = 0;               // local reprojection / match-geometry terms
+  bool kp_lin = false;                  // the terms have been linearized at least once
+  DevBuf kp_pool, kp_table, kp_link_start, kp_link;
+  DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, stats_k; // stats_k: [2][n_kr + n_km][2] -- last linearize, last error pass
   // optional out-of-place form of the all-reduce hook (native RCCL: send != recv); without it: copy + in-place hook
   int (*allreduce2)(const double *send, double *recv, size_t n, void *user) = nullptr;
   // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
@@ -320,10 +348,10 @@ struct SageWindow
   int phase_n = 0;
   bool profiling = false;
   int prof_level = 0; // 1: all hot kernels + phase marks, 2: the photometric linearize only
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[4];
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6]; // (4 / 5: keypoint-term linearize / error launch)
   std::vector<hipEvent_t> ev_free; // recycled events (creating / destroying one per mark costs API time inside the region being profiled)
-  double prof_ms[4] = {0, 0, 0, 0};
-  int prof_n[4] = {0, 0, 0, 0};
+  double prof_ms[6] = {0, 0, 0, 0, 0, 0};
+  int prof_n[6] = {0, 0, 0, 0, 0, 0};
 };
 
 

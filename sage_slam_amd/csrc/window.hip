@@ -27,6 +27,9 @@ __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 }
 
 // one workgroup per output block; thread per element; contributions summed in a fixed order (deterministic)
+// KP: the window carries keypoint terms (AdjEntry::type 2 / 3, the link lists, their share of the tail); windows without them
+// run the instantiation that knows nothing of them
+template <bool KP>
 __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
 {
   const int B = 7 + p.CS, BB = B * B;
@@ -65,19 +68,21 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     for (int a = a0; a < a1; ++a)
     {
       const AdjEntry ae = p.adj[a];
-      const int D = ae.type == 0 ? Dp : Dg;
-      const float *A = ae.type == 0 ? p.AtA_p : p.AtA_g;
-      const float *b = ae.type == 0 ? p.Atb_p : p.Atb_g;
+      const int lt = KP ? (ae.type & 1) : ae.type; // column map: keypoint terms (types 2 / 3) share the dense layouts
+      const bool kp = KP && ae.type >= 2;
+      const int D = lt == 0 ? Dp : Dg;
+      const float *A = kp ? (lt == 0 ? p.AtA_kr : p.AtA_km) : (lt == 0 ? p.AtA_p : p.AtA_g);
+      const float *b = kp ? (lt == 0 ? p.Atb_kr : p.Atb_km) : (lt == 0 ? p.Atb_p : p.Atb_g);
 #pragma unroll
       for (int s = 0; s < S; ++s)
       {
         if (!valid[s])
           continue;
-        const int ci = edge_col(ae.type, ae.role, bi[s], p.CS);
-        const int cj = isg[s] ? 0 : edge_col(ae.type, ae.role, bj[s], p.CS);
+        const int ci = edge_col(lt, ae.role, bi[s], p.CS);
+        const int cj = isg[s] ? 0 : edge_col(lt, ae.role, bj[s], p.CS);
         if (ci < 0 || cj < 0)
           continue;
-        const double *Wd = ae.type == 0 ? p.wide_p : p.wide_g;
+        const double *Wd = kp ? nullptr : (lt == 0 ? p.wide_p : p.wide_g);
         if (Wd)
           acc[s] += Wd[(size_t)ae.edge * (D * D + D) + (isg[s] ? (size_t)D * D + ci : (size_t)ci * D + cj)];
         else
@@ -125,6 +130,16 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
             acc += Wd ? Wd[(size_t)le.e_ba * ws + (size_t)ci * D + cj] : (double)A[(size_t)le.e_ba * D * D + (size_t)ci * D + cj];
         }
       }
+      if (KP && p.link_kp_start) // keypoint terms of the link's two directions, in the order they were added (per kind)
+        for (int a = p.link_kp_start[l]; a < p.link_kp_start[l + 1]; ++a)
+        {
+          const AdjEntry ae = p.link_kp[a];
+          const int lt = ae.type & 1, D = lt == 0 ? Dp : Dg;
+          const float *A = lt == 0 ? p.AtA_kr : p.AtA_km;
+          const int ci = edge_col(lt, ae.role, bi, p.CS), cj = edge_col(lt, 1 - ae.role, bj, p.CS); // (role = direction)
+          if (ci >= 0 && cj >= 0)
+            acc += (double)A[(size_t)ae.edge * D * D + (size_t)ci * D + cj];
+        }
       lnk[(size_t)l * BB + idx] = acc;
     }
   }
@@ -142,6 +157,13 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     if (st && wave < 4)
       for (int e = lane; e < n; e += 64)
         acc += (double)st[2 * e + which];
+    if (KP && p.stats_k && wave < 2) // the terms' errors: reprojection in the photometric slot, match geometry in the geometric one
+    {
+      const float *sk = p.stats_k + (photo ? 0 : 2 * (size_t)p.n_kr);
+      const int nk = photo ? p.n_kr : p.n_km;
+      for (int t = lane; t < nk; t += 64)
+        acc += (double)sk[2 * t];
+    }
     for (int off = 32; off > 0; off >>= 1)
       acc += __shfl_down(acc, off);
     if (lane == 0 && wave < 4)
@@ -181,8 +203,9 @@ __global__ __launch_bounds__(kFinalizeBlock) void window_finalize_kernel(const W
 // (what stats_finalize_kernel does: photometric_factor_kernels.cpp:1049-1058, geometric :868-878) and their totals
 // (a wave-parallel sum in a fixed lane order) -- same summation orders, three launches and their gaps less on the step's critical path.
 
+template <bool KP>
 __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSide ph, const ErrorTotalsSide ge, double *out,
-                                                            double *mirror, double epoch)
+                                                            double *mirror, double epoch, const KpTotals kp)
 {
   for (int idx = threadIdx.x; idx < ph.n_edges + ge.n_edges; idx += blockDim.x)
   {
@@ -236,6 +259,13 @@ __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSid
     for (int u = 0; u < 8; ++u)
       if (e0 + 64 * u < sd.n_edges)
         acc += (double)v[u];
+  }
+  if (KP && kp.stats && which == 0) // keypoint terms (written by the batched kernel before this one): same slots as the linearize tail
+  {
+    const float *sk = kp.stats + (photo ? 0 : 2 * (size_t)kp.n_kr);
+    const int nk = photo ? kp.n_kr : kp.n_km;
+    for (int t = lane; t < nk; t += 64)
+      acc += (double)sk[2 * t];
   }
   for (int off = 32; off > 0; off >>= 1)
     acc += __shfl_down(acc, off);
@@ -414,7 +444,7 @@ extern "C" int sage_window_set_profiling(SageWindow *w, int on)
 
 extern "C" int sage_window_get_kernel_time(SageWindow *w, int which, double *total_ms, int *launches)
 {
-  if (!w || which < 0 || which > 3)
+  if (!w || which < 0 || which > 5)
     return SAGE_E_INVALID;
   SAGE_HIP(hipStreamSynchronize(w->stream));
   for (auto &pr : w->pending[which])
@@ -505,7 +535,8 @@ extern "C" void sage_window_destroy(SageWindow *w)
                     &w->pk, &w->f0s, &w->ptab[0], &w->ptab[1], &w->gtab[0], &w->gtab[1], &w->work_p, &w->first_p, &w->tiles_p,
                     &w->work_g, &w->first_g, &w->tiles_g, &w->part_p, &w->part_g, &w->AtA_p, &w->Atb_p,
                     &w->stats_p, &w->AtA_g, &w->Atb_g, &w->stats_g, &w->adj_start, &w->adj, &w->link_edges,
-                    &w->packed, &w->errbuf};
+                    &w->packed, &w->errbuf, &w->kp_pool, &w->kp_table, &w->kp_link_start, &w->kp_link, &w->AtA_kr, &w->Atb_kr,
+                    &w->AtA_km, &w->Atb_km, &w->stats_k};
   for (DevBuf *b : bufs)
     b->release();
   std::free(w->rccl_hook); // (the communicator itself belongs to the caller)
@@ -564,6 +595,207 @@ extern "C" int sage_window_set_link_geo_loss(SageWindow *w, int link, float loss
   if (!w || w->finalized || link < 0 || link >= (int)w->links.size() || !(loss_param >= 0.f))
     return w && w->finalized ? SAGE_E_STATE : SAGE_E_INVALID;
   w->link_geo_loss[link] = loss_param;
+  return SAGE_OK;
+}
+
+// ---- matched-keypoint terms ------------------------------------------------------------------------------------------
+// add: arguments first (no device is touched for a bad call), then the caller's device arrays are copied to the host -- the
+// locations are validated there (the kernel indexes bias / basis rows with them unchecked) -- and finalize lays this rank's
+// terms out in one device pool behind one table: what lets a single launch serve them all
+extern "C" int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTerm *t)
+{
+  if (!w || !t)
+    return SAGE_E_INVALID;
+  if (w->finalized)
+    return SAGE_E_STATE;
+  const bool rep = t->kind == SAGE_KP_REPROJECTION, mg = t->kind == SAGE_KP_MATCH_GEOMETRY;
+  if ((!rep && !mg) || t->edge < 0 || t->edge >= 2 * (int)w->links.size() || t->N < 1 || t->N > (1 << 20) || !t->loc1d_0 ||
+      !t->homo0 || !(t->weight >= 0.f))
+    return SAGE_E_INVALID;
+  if (rep && (!t->matched_2d || !(t->loss_param > 0.f)))
+    return SAGE_E_INVALID;
+  if (mg && (!t->matched_loc1d_1 || !t->matched_homo1 || t->loss < SAGE_LOSS_FAIR || t->loss > SAGE_LOSS_UNBIASED ||
+             (t->loss != SAGE_LOSS_L2 && !(t->loss_param > 0.f))))
+    return SAGE_E_INVALID;
+  SageWindow::KeypointTermHost h;
+  h.kind = t->kind; h.edge = t->edge; h.N = t->N; h.loss = mg ? t->loss : 0;
+  h.loss_param = t->loss_param; h.weight = t->weight;
+  const size_t N = (size_t)t->N;
+  h.loc0.resize(N);
+  h.homo0.resize(3 * N);
+  h.second.resize((rep ? 2 : 3) * N);
+  SAGE_HIP(hipStreamSynchronize(w->stream)); // (the caller may have filled the arrays on the window's stream)
+  SAGE_HIP(hipMemcpy(h.loc0.data(), t->loc1d_0, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  SAGE_HIP(hipMemcpy(h.homo0.data(), t->homo0, 3 * N * sizeof(float), hipMemcpyDeviceToHost));
+  SAGE_HIP(hipMemcpy(h.second.data(), rep ? t->matched_2d : t->matched_homo1, h.second.size() * sizeof(float),
+                     hipMemcpyDeviceToHost));
+  if (mg)
+  {
+    h.loc1.resize(N);
+    SAGE_HIP(hipMemcpy(h.loc1.data(), t->matched_loc1d_1, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  const int32_t HW = (int32_t)w->cfg.pyr.cam[0].h * (int32_t)w->cfg.pyr.cam[0].w;
+  for (int32_t v : h.loc0)
+    if (v < 0 || v >= HW)
+      return SAGE_E_INVALID;
+  for (int32_t v : h.loc1)
+    if (v < 0 || v >= HW)
+      return SAGE_E_INVALID;
+  w->kp_added.push_back(std::move(h));
+  return (int)w->kp_added.size() - 1;
+}
+
+extern "C" int sage_window_num_keypoint_terms(const SageWindow *w) { return w ? (int)w->kp_added.size() : 0; }
+
+extern "C" int sage_window_get_keypoint_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err, float *n_in)
+{
+  if (!w || term < 0 || term >= (int)w->kp_added.size())
+    return SAGE_E_INVALID;
+  if (!w->finalized)
+    return SAGE_E_STATE;
+  const int lt = w->kp_local[term];
+  if (lt < 0)
+    return SAGE_E_INVALID; // another rank's
+  if (!w->kp_lin)
+    return SAGE_E_STATE;
+  const bool rep = w->kp_added[term].kind == SAGE_KP_REPROJECTION;
+  const size_t D = rep ? 13 + w->cfg.CS : 14 + 2 * w->cfg.CS;
+  const size_t out = rep ? (size_t)lt : (size_t)(lt - w->n_kr);
+  SAGE_HIP(hipStreamSynchronize(w->stream));
+  if (AtA)
+    SAGE_HIP(hipMemcpy(AtA, (rep ? w->AtA_kr : w->AtA_km).as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
+  if (Atb)
+    SAGE_HIP(hipMemcpy(Atb, (rep ? w->Atb_kr : w->Atb_km).as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
+  float s2[2];
+  SAGE_HIP(hipMemcpy(s2, w->stats_k.as<float>() + (size_t)lt * 2, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (err)
+    *err = s2[0];
+  if (n_in)
+    *n_in = s2[1];
+  return SAGE_OK;
+}
+
+// finalize: this rank's terms (those of its directed edges), reprojection first, each kind in the order of the add calls
+static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjEntry>> &adjv, double *residuals)
+{
+  const int CS = w->cfg.CS, nterms = (int)w->kp_added.size();
+  w->kp_local.assign(nterms, -1);
+  w->n_kr = w->n_km = 0;
+  if (nterms == 0)
+    return SAGE_OK;
+  std::vector<int> order;
+  for (int kind = 0; kind < 2; ++kind)
+    for (int i = 0; i < nterms; ++i)
+      if (w->kp_added[i].kind == kind && window_local_edge(w, w->kp_added[i].edge) >= 0)
+      {
+        w->kp_local[i] = (int)order.size();
+        order.push_back(i);
+        (kind == 0 ? w->n_kr : w->n_km) += 1;
+      }
+  const int nloc = (int)order.size();
+  if (nloc == 0)
+    return SAGE_OK;
+  // pool: 4-byte words, every array 16-byte aligned
+  std::vector<uint32_t> pool;
+  auto put = [&pool](const void *src, size_t words) {
+    const size_t off = pool.size();
+    pool.resize(off + (words + 3) / 4 * 4, 0u);
+    std::memcpy(pool.data() + off, src, words * sizeof(uint32_t));
+    return off;
+  };
+  struct Offs
+  {
+    size_t loc0, loc1, homo0, second;
+  };
+  std::vector<Offs> offs(nloc);
+  for (int t = 0; t < nloc; ++t)
+  {
+    const SageWindow::KeypointTermHost &h = w->kp_added[order[t]];
+    offs[t].loc0 = put(h.loc0.data(), h.loc0.size());
+    offs[t].loc1 = h.loc1.empty() ? 0 : put(h.loc1.data(), h.loc1.size());
+    offs[t].homo0 = put(h.homo0.data(), h.homo0.size());
+    offs[t].second = put(h.second.data(), h.second.size());
+  }
+  int rc;
+  if ((rc = upload(w->kp_pool, pool, w->stream)))
+    return rc;
+  const uint32_t *base = w->kp_pool.as<uint32_t>();
+  std::vector<KpTerm> table(nloc);
+  std::vector<std::vector<AdjEntry>> per_link(w->links.size());
+  for (int t = 0; t < nloc; ++t)
+  {
+    const SageWindow::KeypointTermHost &h = w->kp_added[order[t]];
+    const int l = h.edge / 2, dir = h.edge % 2;
+    const int k0 = dir == 0 ? w->links[l].first : w->links[l].second, k1 = dir == 0 ? w->links[l].second : w->links[l].first;
+    KpTerm kt{};
+    kt.kind = h.kind; kt.loss = h.loss; kt.N = h.N;
+    kt.out = h.kind == 0 ? t : t - w->n_kr;
+    kt.stat = t;
+    kt.k0 = k0; kt.k1 = k1;
+    kt.loss_param = h.loss_param; kt.weight = h.weight;
+    kt.loc0 = reinterpret_cast<const int32_t *>(base + offs[t].loc0);
+    kt.homo0 = reinterpret_cast<const float *>(base + offs[t].homo0);
+    if (h.kind == 0)
+      kt.matched = reinterpret_cast<const float *>(base + offs[t].second);
+    else
+    {
+      kt.loc1 = reinterpret_cast<const int32_t *>(base + offs[t].loc1);
+      kt.homo1 = reinterpret_cast<const float *>(base + offs[t].second);
+    }
+    kt.bias0 = w->views[k0].bias; kt.basis0 = w->views[k0].basis;
+    kt.bias1 = w->views[k1].bias; kt.basis1 = w->views[k1].basis;
+    table[t] = kt;
+    adjv[k0].push_back(AdjEntry{2 + h.kind, kt.out, 0});
+    adjv[k1].push_back(AdjEntry{2 + h.kind, kt.out, 1});
+    per_link[l].push_back(AdjEntry{2 + h.kind, kt.out, dir});
+    *residuals += (h.kind == 0 ? 2.0 : 3.0) * h.N;
+  }
+  std::vector<int32_t> lstart(w->links.size() + 1, 0);
+  std::vector<AdjEntry> lkp;
+  for (size_t l = 0; l < w->links.size(); ++l)
+  {
+    lstart[l] = (int32_t)lkp.size();
+    lkp.insert(lkp.end(), per_link[l].begin(), per_link[l].end());
+  }
+  lstart[w->links.size()] = (int32_t)lkp.size();
+  const size_t Dp = 13 + CS, Dg = 14 + 2 * CS;
+  if ((rc = upload(w->kp_table, table, w->stream)) || (rc = upload(w->kp_link_start, lstart, w->stream)) ||
+      (rc = upload(w->kp_link, lkp, w->stream)) ||
+      (rc = w->AtA_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * Dp * sizeof(float))) ||
+      (rc = w->Atb_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * sizeof(float))) ||
+      (rc = w->AtA_km.reserve(std::max<size_t>(1, w->n_km) * Dg * Dg * sizeof(float))) ||
+      (rc = w->Atb_km.reserve(std::max<size_t>(1, w->n_km) * Dg * sizeof(float))) ||
+      (rc = w->stats_k.reserve((size_t)2 * nloc * 2 * sizeof(float))))
+    return rc;
+  SAGE_HIP(hipMemsetAsync(w->stats_k.p, 0, (size_t)2 * nloc * 2 * sizeof(float), w->stream));
+  SAGE_HIP(hipStreamSynchronize(w->stream)); // (the host vectors go out of scope)
+  return SAGE_OK;
+}
+
+// the batched kernel over this rank's terms at variable set `set`; linearize -> stats_k[0], error pass -> stats_k[1]
+static int window_launch_keypoints(SageWindow *w, int set, bool jac)
+{
+  const int nloc = w->n_kr + w->n_km;
+  if (nloc == 0)
+    return SAGE_OK;
+  KpBatchParams kp{};
+  kp.terms = w->kp_table.as<KpTerm>();
+  kp.vars = w->vars[set].as<float>();
+  kp.VS = w->VS;
+  kp.cam = w->cfg.pyr.cam[0];
+  kp.eps = w->cfg.eps;
+  kp.AtA_r = w->AtA_kr.as<float>(); kp.Atb_r = w->Atb_kr.as<float>();
+  kp.AtA_m = w->AtA_km.as<float>(); kp.Atb_m = w->Atb_km.as<float>();
+  kp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * nloc);
+  LaunchCommon lc{};
+  prof_attach(w, jac ? 4 : 5, lc);
+  if (lc.ev_start)
+    (void)hipEventRecord(lc.ev_start, w->stream);
+  SAGE_HIP(launch_keypoint_batch(w->stream, w->cfg.CS, jac, nloc, w->n_km > 0, kp));
+  if (lc.ev_stop)
+    (void)hipEventRecord(lc.ev_stop, w->stream);
+  if (jac)
+    w->kp_lin = true;
   return SAGE_OK;
 }
 
@@ -923,6 +1155,8 @@ extern "C" int sage_window_finalize(SageWindow *w)
       return rc;
     SAGE_HIP(hipStreamSynchronize(w->stream));
   }
+  if ((rc = window_finalize_keypoints(w, adjv, &residuals)))
+    return rc;
   w->residuals_per_lin = residuals;
   w->bytes_per_lin = bytes;
   // ---- work lists
@@ -1174,6 +1408,16 @@ static AssembleParams window_assemble_params(SageWindow *w)
   ap.n_edges_g = w->n_edges;
   ap.split = 1;
   ap.blocks = nullptr;
+  if (w->n_kr + w->n_km > 0)
+  {
+    ap.AtA_kr = w->AtA_kr.as<float>(); ap.Atb_kr = w->Atb_kr.as<float>();
+    ap.AtA_km = w->AtA_km.as<float>(); ap.Atb_km = w->Atb_km.as<float>();
+    ap.stats_k = w->stats_k.as<float>();
+    ap.link_kp_start = w->kp_link_start.as<int32_t>();
+    ap.link_kp = w->kp_link.as<AdjEntry>();
+    ap.n_kr = w->n_kr;
+    ap.n_km = w->n_km;
+  }
   return ap;
 }
 
@@ -1217,6 +1461,11 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
       SAGE_HIP(launch_photo_linearize(w->stream, c.CS, c.FS, nullptr, w->ptab[set].as<PhotoEdge>(), lcp, c.pyr,
                                       c.photo_weights, c.eps, out));
     }
+    {
+      const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
+      if (rck)
+        return rck;
+    }
     WindowFinalizeParams fp{};
     fp.n_p = c.use_photo ? w->n_edges : 0;
     fp.n_g = c.use_geo ? w->n_edges : 0;
@@ -1255,7 +1504,10 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     ap.blocks = w->asm_blocks.as<int32_t>();
     nblocks = w->n_asm_blocks;
   }
-  hipLaunchKernelGGL(assemble_kernel, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
+  if (w->n_kr + w->n_km > 0)
+    hipLaunchKernelGGL(assemble_kernel<true>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
+  else
+    hipLaunchKernelGGL(assemble_kernel<false>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
   SAGE_HIP(hipGetLastError());
   window_phase_mark(w, 1);
   if (ap.packed == w->packed.as<double>()) // (a system assembled elsewhere is booked by the caller)
@@ -1437,9 +1689,23 @@ static int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     ge = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->stats_g.as<float>(), 10.0f * c.geo_weight,
                          c.geo_weight, w->n_edges, 2, 0, 1};
   }
+  KpTotals kpt{};
+  if (w->n_kr + w->n_km > 0)
+  {
+    // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
+    const int rck = window_launch_keypoints(w, which, false);
+    if (rck)
+      return rck;
+    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * (w->n_kr + w->n_km), w->n_kr, w->n_km};
+  }
   w->err_epoch += 1;
-  hipLaunchKernelGGL(error_totals_kernel, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(),
-                     w->world == 1 && !w->allreduce && w->h_err ? w->h_err + 4 : nullptr, (double)w->err_epoch);
+  double *const mirror = w->world == 1 && !w->allreduce && w->h_err ? w->h_err + 4 : nullptr;
+  if (kpt.stats)
+    hipLaunchKernelGGL(error_totals_kernel<true>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
+                       (double)w->err_epoch, kpt);
+  else
+    hipLaunchKernelGGL(error_totals_kernel<false>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
+                       (double)w->err_epoch, kpt);
   SAGE_HIP(hipGetLastError());
   window_phase_mark(w, 4);
   if (speculate_gradients && has && c.use_geo && w->dpt_set == which && !w->dgrad_valid)

@@ -313,3 +313,46 @@ def depth_and_grad(kf: Keyframe, H: int, W: int):
     unscaled = (kf.bias + kf.basis @ kf.code).astype(F32).reshape(1, H, W)
     g = spatial_grad(unscaled)[:, 0]
     return (F32(kf.scale) * unscaled[0]).astype(F32), (F32(kf.scale) * g).astype(F32)
+
+
+# --------------------------------------------------------------------------- matched keypoints (window keypoint terms)
+def _project_true(w: Window, k0: int, k1: int, n: int, seed: int, noise_px: float, outlier_share: float):
+    """n keypoints drawn from keyframe k0's samples, projected into k1 with the window's TRUE variables, plus pixel noise;
+    a share of the matches is replaced by uniform gross outliers -> (loc0 int32 [n], homo0 [n,3], pixels in k1 [n,2])."""
+    a, b = w.keyframes[k0], w.keyframes[k1]
+    rng = np.random.default_rng([seed, k0, k1, n])
+    pick = rng.choice(a.loc1d.size, size=n, replace=n > a.loc1d.size)
+    loc0 = a.loc1d[pick].astype(np.int64)
+    homo0 = a.homo[pick].astype(np.float64)
+    d = float(a.scale_true) * (a.bias[loc0].astype(np.float64) + a.basis[loc0].astype(np.float64) @ a.code_true.astype(np.float64))
+    Xw = (a.R_true.astype(np.float64) @ (d[:, None] * homo0).T).T + a.t_true.astype(np.float64)
+    X1 = (b.R_true.astype(np.float64).T @ (Xw - b.t_true.astype(np.float64)).T).T
+    cam = w.cams[0]
+    px = np.stack([X1[:, 0] / X1[:, 2] * float(cam.fx) + float(cam.cx), X1[:, 1] / X1[:, 2] * float(cam.fy) + float(cam.cy)], 1)
+    px = px + rng.normal(0.0, noise_px, px.shape)
+    n_out = int(round(outlier_share * n))
+    if n_out > 0:
+        bad = rng.choice(n, size=n_out, replace=False)
+        px[bad] = np.stack([rng.uniform(0, w.W - 1, n_out), rng.uniform(0, w.H - 1, n_out)], 1)
+    return loc0.astype(np.int32), homo0.astype(F32), px
+
+
+def make_reprojection_matches(w: Window, k0: int, k1: int, n: int, seed: int, noise_px: float = 1.0,
+                              outlier_share: float = 0.1) -> dict:
+    """Matches of a reprojection term on the directed edge k0 -> k1 (what the reference's factor is constructed with,
+    ``core/gtsam/reprojection_factor.cpp:41-188``): dict(kind, loc0 [n] int32, homo0 [n,3], matched_2d [n,2] pixels in k1).
+    Deterministic per (seed, k0, k1, n)."""
+    loc0, homo0, px = _project_true(w, k0, k1, n, seed, noise_px, outlier_share)
+    return dict(kind="reprojection", loc0=loc0, homo0=homo0, matched_2d=px.astype(F32))
+
+
+def make_match_geometry_matches(w: Window, k0: int, k1: int, n: int, seed: int, noise_px: float = 1.0,
+                                outlier_share: float = 0.1) -> dict:
+    """Matches of a match-geometry term: the match is the rounded in-image pixel of k1 with its ray ->
+    dict(kind, loc0 [n] int32, homo0 [n,3], loc1 [n] int32, homo1 [n,3])."""
+    loc0, homo0, px = _project_true(w, k0, k1, n, seed, noise_px, outlier_share)
+    cam = w.cams[0]
+    x = np.clip(np.rint(px[:, 0]), 0, w.W - 1).astype(np.int64)
+    y = np.clip(np.rint(px[:, 1]), 0, w.H - 1).astype(np.int64)
+    homo1 = np.stack([(x - float(cam.cx)) / float(cam.fx), (y - float(cam.cy)) / float(cam.fy), np.ones(n)], 1)
+    return dict(kind="match_geometry", loc0=loc0, homo0=homo0, loc1=(y * w.W + x).astype(np.int32), homo1=homo1.astype(F32))
