@@ -1,7 +1,8 @@
 // runtime_internal.h -- shared by the host-runtime translation units behind the C ABI (include/sage_ba.h):
 //   operators.hip       workspaces, the per-edge operator API (df::*_calculate mirrors), the producer entry points
 //   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame)
-//   window.hip          the batched window engine: tables, work lists, linearize / error / solve / LM iteration
+//   window.hip          the batched window engine on a finalized window: linearize / error / solve / LM iteration
+//   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
 #pragma once
