@@ -9,7 +9,8 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
-#include "host_math.h"
+#include "host_math.h" // env_flag
+#include "host_threads.h"
 
 namespace sage
 {

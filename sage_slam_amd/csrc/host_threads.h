@@ -1,6 +1,6 @@
 // host_threads.h -- the library's own host threads (host_threads.cpp): CPU topology, where the solve's threads are placed,
 // the placement monitor, and the one Worker type every thread of the solve runs on.  The jobs and their hand-over protocols
-// stay with the Cholesky (host_math.cpp).
+// stay with the Cholesky (block_solver.cpp).
 #pragma once
 #include <pthread.h>
 #include <sched.h>
@@ -66,7 +66,7 @@ private:
   unsigned seen0 = 0;
 };
 
-// the solve's workers (host_math.cpp): 0 = the second half's helper, 1 / 2 = the look-ahead stages of the halves (null on
+// the solve's workers (block_solver.cpp): 0 = the second half's helper, 1 / 2 = the look-ahead stages of the halves (null on
 // hosts with too few CPUs), 3 = the arrow-row pool (null: none; only made when `make`)
 constexpr int kSolveWorkers = 4;
 Worker *solve_worker(int idx, bool make = true);
@@ -89,7 +89,7 @@ struct SolveLease
 // whose long arrow-row chains (block_plan_long_arrow_chains) do not fit the cores the look-ahead stages leave free in the
 // caller's L3 domain but do fit with those two cores.
 bool block_chol_arm(bool with_pool = false, int long_arrow_chains = 0);
-// the arrow-row pool's placement, read by host_math.cpp's task split: pool workers per L3 domain (-1: unknown / no pool),
+// the arrow-row pool's placement, read by block_solver.cpp's task split: pool workers per L3 domain (-1: unknown / no pool),
 // and whether the second half, its look-ahead stage and its chains sit on a domain of their own
 extern std::atomic<int> g_domain_threads[2];
 extern std::atomic<bool> g_two_domains;

@@ -41,6 +41,7 @@ extern "C"
 #endif
 
 #include "host_math.h"
+#include "host_threads.h" // placement, shutdown (the window units do not touch the block solver itself)
 #include "sage_ba.h"
 #include "sage_internal.h"
 #include "keypoint_batch.h"

@@ -11,7 +11,7 @@
 //   every rank: (sum_r C^(r)) d_S = sum_r c^(r)   (block-envelope Cholesky over the separators, identical on all ranks)
 //   rank r:   d_I = A_II^-1 (b_I - A_IS d_S)
 //
-// Both steps run on the fixed-block Cholesky of the window solve (host_math.cpp, blocks padded to 24 / 40, so B <= 40):
+// Both steps run on the fixed-block Cholesky of the window solve (block_solver.cpp, blocks padded to 24 / 40, so B <= 40):
 // the local system keeps the interior keyframes first and the rank's separators last, block_chol_partial factorises
 // the interior rows and leaves C^(r) / c^(r) in the separator rows, block_chol_partial_back substitutes d_I; the
 // separator system is a packed system for sage_block_solve.
@@ -29,6 +29,7 @@
 #include <map>
 #include <vector>
 
+#include "block_solver.h"
 #include "host_math.h"
 #include "sage_ba.h"
 
@@ -354,6 +355,17 @@ struct LocalSystem
 };
 } // namespace
 
+// the local system's storage (interior rows first, the rank's separators last; no A ranges) as the block solver sees it
+static sage::BlockEnvelope local_envelope(const SageShardPlan &p)
+{
+  sage::BlockEnvelope env;
+  env.K = p.nloc;
+  env.Bp = p.Bp;
+  env.row_first = p.row_first.data();
+  env.row_off = p.row_off.data();
+  return env;
+}
+
 extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local, double damp, const double *diag_add,
                                     const double *g_add, double *sep_out)
 {
@@ -376,10 +388,11 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
   std::vector<int> spos(K, -1);
   for (int i = 0; i < nS; ++i)
     spos[p->sep_all[p->sep_local[i]]] = i;
-  const int Bp = p->Bp, BBp = Bp * Bp;
+  const int Bp = p->Bp;
   std::fill(p->T.begin(), p->T.end(), 0.0);
   std::fill(p->yv.begin(), p->yv.end(), 0.0);
-  auto blk = [&](int i, int j) { return p->T.data() + (size_t)(p->row_off[i] + j - p->row_first[i]) * BBp; };
+  const sage::BlockEnvelope env = local_envelope(*p);
+  auto blk = [&](int i, int j) { return env.block(p->T.data(), i, j); };
   auto lpos = [&](int k) { return p->int_pos[k] >= 0 ? p->int_pos[k] : (spos[k] >= 0 ? nI + spos[k] : -1); };
   for (int q = 0; q < p->nloc; ++q)
   {
@@ -416,8 +429,6 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
       for (int c = 0; c < B; ++c)
         D[row_is_a ? c * Bp + r : r * Bp + c] += src[r * B + c];
   }
-  sage::BlockEnvelope env;
-  env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
   const auto t1 = tnow();
   const int rcf = sage::block_chol_partial(env, p->T.data(), p->X.data(), p->yv.data(), nI);
   if (rcf != 0)
@@ -475,8 +486,7 @@ extern "C" int sage_shard_solve(SageShardPlan *p, const double *sep_reduced, dou
     for (int r = B; r < Bp; ++r)
       p->yv[(size_t)(nI + s) * Bp + r] = 0.0;
   }
-  sage::BlockEnvelope env;
-  env.K = p->nloc; env.Bp = Bp; env.row_first = p->row_first.data(); env.row_off = p->row_off.data();
+  const sage::BlockEnvelope env = local_envelope(*p);
   if (sage::block_chol_partial_back(env, p->T.data(), p->X.data(), p->yv.data(), nI) != 0)
     return SAGE_E_STATE;
   for (int i = 0; i < nI; ++i)

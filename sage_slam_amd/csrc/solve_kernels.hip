@@ -9,7 +9,7 @@
 //   scatter   packed [K diag blocks | link blocks | gradient] (double)  ->  block-envelope storage of the lower
 //             triangle (+ priors, LM damping, identity padding to BP rows), streamed into pinned host memory in the
 //             order the factorisation consumes it, a ticket per block
-//   factor    fixed-block Cholesky + substitutions on host cores (host_math.cpp: block_chol_solve_tr -- two halves and
+//   factor    fixed-block Cholesky + substitutions on host cores (block_solver.cpp: block_chol_solve_tr -- two halves and
 //             a separator, each half as two pipelined stages)
 //   retract   candidate variables = retract(current, delta), read zero-copy from the host's solution
 //
@@ -28,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_solver.h"
 #include "host_math.h"
 #include "sage_device.h"
 #include "sage_internal.h"
@@ -317,23 +318,19 @@ struct DeviceSolver
   void *h_pinned = nullptr; // [K*VS floats | K*B doubles | tail double | status int | go word of the pre-launched retract]
   size_t h_go_off = 0;
   unsigned go_epoch = 0;
-  size_t h_vars_off = 0, h_delta_off = 0, h_tail_off = 0, h_status_off = 0, h_bytes = 0;
+  size_t h_vars_off = 0, h_delta_off = 0, h_tail_off = 0, h_bytes = 0;
   SolvePlan plan{};
   int VS = 0;
   void *h_T = nullptr, *h_y = nullptr;       // pinned, one allocation: block storage, then the right-hand side
   std::vector<double> h_X;                   // inverses of the diagonal factors
-  std::vector<int32_t> h_row_first, h_row_off, h_a_first, h_a_cnt, h_a_off, h_col_ptr, h_col_rows;
-  int n1 = 0, n2 = 0; // two independent leading row ranges [0,n1) and [n1,n1+n2) of the elimination order (0: none)
+  BlockPlan host_plan;                       // elimination order and block storage (what the host factorisation reads)
   // hybrid path: the scatter kernel writes blocks + rhs straight into h_T / h_y in consumption order and posts a
   // ticket (the epoch of this solve) per block in h_flags
   const int32_t *d_order = nullptr;
   unsigned *h_flags = nullptr;
   unsigned epoch = 0;
   int scatter_wgs = 32;
-  std::vector<int32_t> h_pos, h_perm; // elimination order (host copies)
   std::vector<uint8_t> h_fill;        // per block: structural fill-in (not delivered by the scatter kernel: BlockEnvelope::fill)
-  std::vector<int32_t> h_pair_off;    // order-list offset of "pair row" t (row t of the first half + row t of the second);
-                                      // entry T = start of the separator rows, entry T+1 = nblk
 };
 
 int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
@@ -351,8 +348,8 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   }
   const int n1 = bp.n1, n2 = bp.n2, nblk = bp.nblk;
   const std::vector<int32_t> &perm = bp.perm, &pos = bp.pos, &row_first = bp.row_first, &row_off = bp.row_off,
-                             &a_first = bp.a_first, &a_cnt = bp.a_cnt, &a_off = bp.a_off, &blk_row = bp.blk_row,
-                             &blk_col = bp.blk_col, &blk_src = bp.blk_src;
+                             &a_cnt = bp.a_cnt, &a_off = bp.a_off, &blk_row = bp.blk_row, &blk_col = bp.blk_col,
+                             &blk_src = bp.blk_src;
   DeviceSolver *S = new DeviceSolver;
   S->K = K; S->B = B; S->Bp = Bp; S->nblk = nblk; S->nlinks = (int)links.size(); S->VS = VS;
   // one allocation for the int tables
@@ -367,7 +364,7 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   const size_t o_rf = put(row_first), o_ro = put(row_off), o_br = put(blk_row), o_bc = put(blk_col),
                o_bs = put(blk_src), o_pm = put(perm), o_ps = put(pos);
   // consumption order of the host factorisation: the two halves row by row side by side, the separator last
-  std::vector<int32_t> order, pair_off;
+  std::vector<int32_t> order;
   {
     auto push_row = [&](int i) {
       for (int q = 0; q < a_cnt[i]; ++q)
@@ -379,16 +376,13 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
     {
       for (int t = 0; t < std::max(n1, n2); ++t)
       {
-        pair_off.push_back((int32_t)order.size());
         if (t < n1)
           push_row(t);
         if (t < n2)
           push_row(n1 + t);
       }
-      pair_off.push_back((int32_t)order.size());
       for (int i = n1 + n2; i < K; ++i)
         push_row(i);
-      pair_off.push_back((int32_t)order.size());
     }
     else
       for (int i = 0; i < K; ++i)
@@ -406,13 +400,6 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   if (hipStreamSynchronize(stream) != hipSuccess)
     return fail((int)hipErrorUnknown);
   const size_t ty_doubles = (size_t)nblk * Bp * Bp + (size_t)K * Bp;
-  S->h_row_first = row_first;
-  S->h_row_off = row_off;
-  S->h_a_first = a_first;
-  S->h_a_cnt = a_cnt;
-  S->h_a_off = a_off;
-  S->h_col_ptr = bp.col_ptr;
-  S->h_col_rows = bp.col_rows;
   {
     if (hipHostMalloc(&S->h_T, ty_doubles * sizeof(double) + (size_t)nblk * sizeof(unsigned), hipHostMallocDefault) !=
         hipSuccess)
@@ -434,18 +421,14 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   P.K = K; P.B = B; P.Bp = Bp; P.nblk = nblk; P.nlinks = (int)links.size();
   P.row_first = base + o_rf; P.row_off = base + o_ro;
   P.blk_row = base + o_br; P.blk_col = base + o_bc; P.blk_src = base + o_bs; P.perm = base + o_pm; P.pos = base + o_ps;
-  S->n1 = n1;
-  S->n2 = n2;
   S->d_order = base + o_ord;
-  S->h_pos = pos;
-  S->h_perm = perm;
   S->h_fill.assign((size_t)nblk, 0);
   for (int b = 0; b < nblk; ++b)
     S->h_fill[b] = (blk_src[b] < 0 && blk_row[b] != blk_col[b]) ? 1 : 0;
-  S->h_pair_off = pair_off;
   if (const char *e = getenv("SAGE_SCATTER_WGS")) // (diagnostic: workgroups of the scatter kernel)
     S->scatter_wgs = std::max(1, atoi(e));
   std::memset(S->h_pinned, 0, S->h_bytes);
+  S->host_plan = std::move(bp); // (last: the tables above are references into it)
   *out = S;
   return SAGE_OK;
 }
@@ -484,18 +467,11 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
     // held from the arm until block_chol_solve_tr returns, also without a split (the solve may still hand work to helpers
     // another caller armed): no shutdown joins a helper in between
     SolveLease lease;
-    bool no_lookahead = false;
-    if (S->n1 > 0)
-    {
-      // the helper core (and, for loop-closure plans with long separator rows, the worker pool) wakes up while this
-      // thread waits for the device
-      BlockEnvelope pe;
-      pe.K = S->K; pe.Bp = S->Bp;
-      pe.row_first = S->h_row_first.data(); pe.row_off = S->h_row_off.data();
-      pe.a_first = S->h_a_first.data(); pe.a_cnt = S->h_a_cnt.data(); pe.a_off = S->h_a_off.data();
-      pe.n1 = S->n1; pe.n2 = S->n2;
-      no_lookahead = block_chol_arm(block_plan_has_arrow_rows(pe), block_plan_long_arrow_chains(pe));
-    }
+    BlockEnvelope env = envelope_of(S->host_plan, S->Bp);
+    // the helper core (and, for loop-closure plans with long separator rows, the worker pool) wakes up while this
+    // thread waits for the device
+    if (env.n1 > 0)
+      env.no_lookahead = block_chol_arm(block_plan_has_arrow_rows(env), block_plan_long_arrow_chains(env));
     S->epoch += 1;
     if (S->epoch == 0) // wrapped: 0 is the "never written" value
       S->epoch = 1;
@@ -528,15 +504,8 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
       }
     } guard{go, S->go_epoch | 0x80000000u};
     const auto t1 = std::chrono::steady_clock::now();
-    BlockEnvelope env;
-    env.K = S->K; env.Bp = S->Bp;
-    env.row_first = S->h_row_first.data(); env.row_off = S->h_row_off.data();
-    env.a_first = S->h_a_first.data(); env.a_cnt = S->h_a_cnt.data(); env.a_off = S->h_a_off.data();
-    env.col_ptr = S->h_col_ptr.data(); env.col_rows = S->h_col_rows.data();
-    env.n1 = S->n1; env.n2 = S->n2;
     env.ready = S->h_flags; env.epoch = S->epoch;
     env.fill = S->h_fill.data();
-    env.no_lookahead = no_lookahead;
     const int bad = block_chol_solve_tr(env, reinterpret_cast<double *>(S->h_T), S->h_X.data(),
                                         reinterpret_cast<double *>(S->h_y));
     const auto t2 = std::chrono::steady_clock::now();

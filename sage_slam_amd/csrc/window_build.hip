@@ -4,7 +4,7 @@
 #include "runtime_internal.h"
 #include "window_plan.h"
 
-// live windows of the process: the last sage_window_destroy stops the solver's host threads (host_math.cpp "life cycle")
+// live windows of the process: the last sage_window_destroy stops the solver's host threads (host_threads.cpp "life cycle")
 static std::atomic<int> g_live_windows{0};
 
 extern "C" int sage_window_create(const SageWindowConfig *cfg, void *hip_stream, SageWindow **out)
