@@ -1,5 +1,6 @@
-// keypoint_batch.h -- the matched-keypoint terms of a window (sage_window_add_keypoint_term): device table row and the
-// launch of the batched kernel (keypoint_kernels.hip), shared with the window engine (window.hip).
+// keypoint_batch.h -- what the host units see of the matched-keypoint factors (keypoint_kernels.hip): system sizes and
+// scratch layout, the parameter / output structs and launches of the per-edge operators (operators.hip), and the device
+// table row and launch of a window's terms (sage_window_add_keypoint_term; window.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,62 @@
 
 namespace sage
 {
+
+// system size D by factor, mode and code size; rows per keypoint
+//   reprojection    mode 0 mapper [pose0 pose1 code0 scale0], 1 tracker (relative pose)
+//   match geometry  mode 0 mapper [pose0 pose1 code0 code1 scale0 scale1], 1 loop [pose0 pose1 scale0 scale1],
+//                   2 tracker (relative pose), 3 tracker (relative pose + scale0)
+constexpr int reproj_dim(int mode, int CS) { return mode == 0 ? 13 + CS : 6; }
+constexpr int mg_dim(int mode, int CS) { return mode == 0 ? 14 + 2 * CS : (mode == 1 ? 14 : (mode == 2 ? 6 : 7)); }
+constexpr int kReprojRows = 2, kMgRows = 3;
+
+// one factor evaluation's working set: weighted rows [rpp * N][D + 1] (the residual is the last column) | serr [N] | sval [N]
+constexpr size_t kp_rows_floats(int rpp, int N, int D) { return (size_t)rpp * N * (D + 1) + (size_t)2 * N; }
+constexpr size_t kp_scratch_floats(int rpp, int N, int D) { return kp_rows_floats(rpp, N, D) + 4; }
+template <class P>
+__host__ __device__ inline void kp_place(P &p, float *base, int rpp, int D)
+{
+  p.rows = base;
+  p.serr = base + (size_t)rpp * p.N * (D + 1);
+  p.sval = p.serr + p.N;
+}
+
+struct ReprojParams
+{
+  const float *R10, *t10, *R0, *t0, *R1, *t1; // mapper: all six; tracker: R10/t10 = the relative pose
+  const float *bias0, *basis0, *code0;        // mapper
+  const int32_t *loc;                         // mapper
+  const float *dpts0;                         // tracker: sampled depths [N]
+  const float *homo, *matched;                // [N,3], [N,2]
+  float scale0;
+  SageCamera cam;
+  float eps, loss_param, weight;
+  int N;
+  float *rows, *serr, *sval; // placed by the launch (kp_place)
+};
+
+// loss 0 fair, 1 L2, 2 huber, 3 unbiased (mapper only)
+struct MgParams
+{
+  const float *R10, *t10, *R0, *t0, *R1, *t1;
+  const float *bias0, *bias1, *basis0, *basis1, *code0, *code1; // mode 0
+  const float *dpts0, *dpts1;                                   // mode 1: unscaled; mode 2/3: scaled
+  const float *homo0, *homo1;
+  const int32_t *loc0, *loc1;
+  float scale0, scale1, loss_param, weight;
+  int loss, N;
+  float *rows, *serr, *sval;
+};
+
+struct KpOut
+{
+  float *AtA, *Atb; // [D][D], [D]: jac only
+  float *stats;     // {error, num_inliers}
+};
+
+// scratch: kp_scratch_floats(rows per keypoint, N, D) floats
+hipError_t launch_reproj(hipStream_t s, int CS, bool tracker, bool jac, const ReprojParams &p, float *scratch, const KpOut &out);
+hipError_t launch_match_geom(hipStream_t s, int mode, int CS, bool jac, const MgParams &p, float *scratch, const KpOut &out);
 
 constexpr int kKpChunk = 64; // keypoints whose weighted rows sit in LDS at a time
 
@@ -40,7 +97,7 @@ struct KpBatchParams
 // dynamic LDS of the batched kernel: the chunk's rows, stride padded to four floats
 inline size_t kp_batch_lds_bytes(int CS, bool any_match_geometry)
 {
-  const int D = any_match_geometry ? 14 + 2 * CS : 13 + CS, rpp = any_match_geometry ? 3 : 2;
+  const int D = any_match_geometry ? mg_dim(0, CS) : reproj_dim(0, CS), rpp = any_match_geometry ? kMgRows : kReprojRows;
   return (size_t)kKpChunk * rpp * (size_t)((D + 1 + 3) / 4 * 4) * sizeof(float);
 }
 

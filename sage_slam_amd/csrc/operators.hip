@@ -343,28 +343,24 @@ extern "C" int sage_depth_and_grad(SageWorkspace *ws, float *dpt, float *grad, c
   return SAGE_OK;
 }
 
-// ---- sparse reprojection factor (reproj_kernels.hip) ----
+// ---- sparse reprojection factor (keypoint_kernels.hip) ----
 static int reproj_common(SageWorkspace *ws, bool tracker, bool jac, float *AtA, float *Atb, float *error_host,
-                         float *num_inliers_host, const float *R10, const float *t10, const float *R0, const float *t0,
-                         const float *R1, const float *t1, const float *bias0, const float *basis0, const float *code0,
-                         const int32_t *loc, const float *dpts0, const float *homo, const float *matched, float scale0,
-                         const SageCamera *cam, float eps, float loss_param, float weight, int N, int CS)
+                         float *num_inliers_host, ReprojParams p, const SageCamera *cam, int CS)
 {
-  if (!ws || !cam || N < 0 || !R10 || !t10 || (N > 0 && (!homo || !matched)) || (jac && (!AtA || !Atb)))
+  const int N = p.N;
+  if (!ws || !cam || N < 0 || !p.R10 || !p.t10 || (N > 0 && (!p.homo || !p.matched)) || (jac && (!AtA || !Atb)))
     return SAGE_E_INVALID;
-  if (!tracker && (!bias0 || !basis0 || !code0 || (N > 0 && !loc) || (jac && (!R0 || !t0 || !R1 || !t1))))
+  if (!tracker && (!p.bias0 || !p.basis0 || !p.code0 || (N > 0 && !p.loc) || (jac && (!p.R0 || !p.t0 || !p.R1 || !p.t1))))
     return SAGE_E_INVALID;
-  if (tracker && N > 0 && !dpts0)
+  if (tracker && N > 0 && !p.dpts0)
     return SAGE_E_INVALID;
   if (!tracker && CS != 16 && CS != 32)
     return SAGE_E_UNSUPPORTED;
-  const int D = tracker ? 6 : 13 + CS;
+  p.cam = *cam;
   int rc;
-  if ((rc = ws->misc.reserve(reproj_scratch_floats(N, D) * sizeof(float))))
+  if ((rc = ws->misc.reserve(kp_scratch_floats(kReprojRows, N, reproj_dim(tracker ? 1 : 0, CS)) * sizeof(float))))
     return rc;
-  SAGE_HIP(launch_reproj(ws->stream, CS, tracker, jac, R10, t10, R0, t0, R1, t1, bias0, basis0, code0, loc, dpts0, homo,
-                         matched, scale0, *cam, eps, loss_param, weight, N, ws->misc.as<float>(), AtA, Atb,
-                         ws_stats(ws)));
+  SAGE_HIP(launch_reproj(ws->stream, CS, tracker, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, ws_stats(ws)}));
   if (ws->defer_fetch)
     return SAGE_OK;
   return ws_fetch_stats(ws, error_host, num_inliers_host);
@@ -378,8 +374,11 @@ extern "C" int sage_reprojection_jac_error_calculate(SageWorkspace *ws, float *A
                                                      float scale0, const SageCamera *cam, float eps, float loss_param,
                                                      float weight, int N, int CS)
 {
-  return reproj_common(ws, false, true, AtA_dev, Atb_dev, error_host, num_inliers_host, R10, t10, R0, t0, R1, t1, bias0,
-                       basis0, code0, loc1d, nullptr, homo, matched_2d, scale0, cam, eps, loss_param, weight, N, CS);
+  ReprojParams p{};
+  p.R10 = R10; p.t10 = t10; p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1;
+  p.bias0 = bias0; p.basis0 = basis0; p.code0 = code0; p.loc = loc1d; p.homo = homo; p.matched = matched_2d;
+  p.scale0 = scale0; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
+  return reproj_common(ws, false, true, AtA_dev, Atb_dev, error_host, num_inliers_host, p, cam, CS);
 }
 
 extern "C" int sage_reprojection_error_calculate(SageWorkspace *ws, float *error_host, float *num_inliers_host,
@@ -389,9 +388,11 @@ extern "C" int sage_reprojection_error_calculate(SageWorkspace *ws, float *error
                                                  const SageCamera *cam, float eps, float loss_param, float weight, int N,
                                                  int CS)
 {
-  return reproj_common(ws, false, false, nullptr, nullptr, error_host, num_inliers_host, R10, t10, nullptr, nullptr,
-                       nullptr, nullptr, bias0, basis0, code0, loc1d, nullptr, homo, matched_2d, scale0, cam, eps,
-                       loss_param, weight, N, CS);
+  ReprojParams p{};
+  p.R10 = R10; p.t10 = t10;
+  p.bias0 = bias0; p.basis0 = basis0; p.code0 = code0; p.loc = loc1d; p.homo = homo; p.matched = matched_2d;
+  p.scale0 = scale0; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
+  return reproj_common(ws, false, false, nullptr, nullptr, error_host, num_inliers_host, p, cam, CS);
 }
 
 extern "C" int sage_tracker_reproj_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev,
@@ -400,9 +401,10 @@ extern "C" int sage_tracker_reproj_jac_error_calculate(SageWorkspace *ws, float 
                                                        const float *matched_2d, const SageCamera *cam, float eps,
                                                        float loss_param, float weight, int N)
 {
-  return reproj_common(ws, true, true, AtA_dev, Atb_dev, error_host, num_inliers_host, R, t, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, sampled_dpts0, homo, matched_2d, 1.f, cam, eps,
-                       loss_param, weight, N, 16);
+  ReprojParams p{}; // tracker: R10 / t10 = the relative pose, depths handed over
+  p.R10 = R; p.t10 = t; p.dpts0 = sampled_dpts0; p.homo = homo; p.matched = matched_2d;
+  p.scale0 = 1.f; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
+  return reproj_common(ws, true, true, AtA_dev, Atb_dev, error_host, num_inliers_host, p, cam, 16);
 }
 
 extern "C" int sage_tracker_reproj_error_calculate(SageWorkspace *ws, float *error_host, float *num_inliers_host,
@@ -410,38 +412,32 @@ extern "C" int sage_tracker_reproj_error_calculate(SageWorkspace *ws, float *err
                                                    const float *homo, const float *matched_2d, const SageCamera *cam,
                                                    float eps, float loss_param, float weight, int N)
 {
-  return reproj_common(ws, true, false, nullptr, nullptr, error_host, num_inliers_host, R, t, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, sampled_dpts0, homo, matched_2d, 1.f, cam, eps,
-                       loss_param, weight, N, 16);
+  ReprojParams p{}; // tracker: R10 / t10 = the relative pose, depths handed over
+  p.R10 = R; p.t10 = t; p.dpts0 = sampled_dpts0; p.homo = homo; p.matched = matched_2d;
+  p.scale0 = 1.f; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
+  return reproj_common(ws, true, false, nullptr, nullptr, error_host, num_inliers_host, p, cam, 16);
 }
 
 // ---- match-geometry factors (keypoint_kernels.hip) ----
-static int mg_common(SageWorkspace *ws, int mode, int loss, bool jac, float *AtA, float *Atb, float *error_host,
-                     const float *R10, const float *t10, const float *R0, const float *t0, const float *R1,
-                     const float *t1, const float *bias0, const float *bias1, const float *basis0, const float *basis1,
-                     const float *code0, const float *code1, const float *dpts0, const float *dpts1, const float *homo0,
-                     const float *homo1, const int32_t *loc0, const int32_t *loc1, float scale0, float scale1,
-                     float loss_param, float weight, int N, int CS)
+static int mg_common(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *error_host, const MgParams &p,
+                     int CS)
 {
-  if (!ws || N < 1 || !R10 || !t10 || !homo0 || !homo1 || (jac && (!AtA || !Atb)))
+  if (!ws || p.N < 1 || !p.R10 || !p.t10 || !p.homo0 || !p.homo1 || (jac && (!AtA || !Atb)))
     return SAGE_E_INVALID;
-  if (mode == 0 && (!bias0 || !bias1 || !basis0 || !basis1 || !code0 || !code1 || !loc0 || !loc1))
+  if (mode == 0 && (!p.bias0 || !p.bias1 || !p.basis0 || !p.basis1 || !p.code0 || !p.code1 || !p.loc0 || !p.loc1))
     return SAGE_E_INVALID;
-  if (mode != 0 && (!dpts0 || !dpts1))
+  if (mode != 0 && (!p.dpts0 || !p.dpts1))
     return SAGE_E_INVALID;
-  if (mode <= 1 && jac && (!R0 || !t0 || !R1 || !t1))
+  if (mode <= 1 && jac && (!p.R0 || !p.t0 || !p.R1 || !p.t1))
     return SAGE_E_INVALID;
-  if (loss < 0 || loss > 3 || (loss == SAGE_LOSS_UNBIASED && mode != 0) || (mode != 0 && loss != SAGE_LOSS_FAIR))
+  if (p.loss < 0 || p.loss > 3 || (p.loss == SAGE_LOSS_UNBIASED && mode != 0) || (mode != 0 && p.loss != SAGE_LOSS_FAIR))
     return SAGE_E_INVALID;
   if (mode == 0 && CS != 16 && CS != 32)
     return SAGE_E_UNSUPPORTED;
-  const int D = mode == 0 ? 14 + 2 * CS : (mode == 1 ? 14 : (mode == 2 ? 6 : 7));
   int rc;
-  if ((rc = ws->misc.reserve(mg_scratch_floats(N, D) * sizeof(float))))
+  if ((rc = ws->misc.reserve(kp_scratch_floats(kMgRows, p.N, mg_dim(mode, CS)) * sizeof(float))))
     return rc;
-  SAGE_HIP(launch_match_geom(ws->stream, mode, loss, CS, jac, R10, t10, R0, t0, R1, t1, bias0, bias1, basis0, basis1,
-                             code0, code1, dpts0, dpts1, homo0, homo1, loc0, loc1, scale0, scale1, loss_param, weight, N,
-                             ws->misc.as<float>(), AtA, Atb, ws_stats(ws)));
+  SAGE_HIP(launch_match_geom(ws->stream, mode, CS, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, ws_stats(ws)}));
   if (ws->defer_fetch)
     return SAGE_OK;
   return ws_fetch_stats(ws, error_host, nullptr);
@@ -457,9 +453,13 @@ extern "C" int sage_match_geometry_jac_error_calculate(SageWorkspace *ws, float 
                                                        const int32_t *matched_loc1d_1, float scale0, float scale1,
                                                        float loss_param, float weight, int loss, int N, int CS)
 {
-  return mg_common(ws, 0, loss, true, AtA_dev, Atb_dev, error_host, R10, t10, R0, t0, R1, t1, bias0, bias1, basis0,
-                   basis1, code0, code1, nullptr, nullptr, homo0, matched_homo1, loc1d_0, matched_loc1d_1, scale0, scale1,
-                   loss_param, weight, N, CS);
+  MgParams p{};
+  p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = loss; p.N = N;
+  p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1;
+  p.bias0 = bias0; p.bias1 = bias1; p.basis0 = basis0; p.basis1 = basis1; p.code0 = code0; p.code1 = code1;
+  p.loc0 = loc1d_0; p.loc1 = matched_loc1d_1;
+  return mg_common(ws, 0, true, AtA_dev, Atb_dev, error_host, p, CS);
 }
 
 extern "C" int sage_match_geometry_error_calculate(SageWorkspace *ws, float *error_host, const float *R10,
@@ -469,9 +469,12 @@ extern "C" int sage_match_geometry_error_calculate(SageWorkspace *ws, float *err
                                                    const int32_t *loc1d_0, const int32_t *matched_loc1d_1, float scale0,
                                                    float scale1, float loss_param, float weight, int loss, int N, int CS)
 {
-  return mg_common(ws, 0, loss, false, nullptr, nullptr, error_host, R10, t10, nullptr, nullptr, nullptr, nullptr, bias0,
-                   bias1, basis0, basis1, code0, code1, nullptr, nullptr, homo0, matched_homo1, loc1d_0, matched_loc1d_1,
-                   scale0, scale1, loss_param, weight, N, CS);
+  MgParams p{};
+  p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = loss; p.N = N;
+  p.bias0 = bias0; p.bias1 = bias1; p.basis0 = basis0; p.basis1 = basis1; p.code0 = code0; p.code1 = code1;
+  p.loc0 = loc1d_0; p.loc1 = matched_loc1d_1;
+  return mg_common(ws, 0, false, nullptr, nullptr, error_host, p, CS);
 }
 
 extern "C" int sage_loop_mg_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host,
@@ -481,9 +484,11 @@ extern "C" int sage_loop_mg_jac_error_calculate(SageWorkspace *ws, float *AtA_de
                                                 const float *matched_homo1, float scale0, float scale1, float loss_param,
                                                 float weight, int N)
 {
-  return mg_common(ws, 1, SAGE_LOSS_FAIR, true, AtA_dev, Atb_dev, error_host, R10, t10, R0, t0, R1, t1, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, unscaled_dpts0, matched_unscaled_dpts1, homo0, matched_homo1,
-                   nullptr, nullptr, scale0, scale1, loss_param, weight, N, 16);
+  MgParams p{};
+  p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
+  p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1; p.dpts0 = unscaled_dpts0; p.dpts1 = matched_unscaled_dpts1;
+  return mg_common(ws, 1, true, AtA_dev, Atb_dev, error_host, p, 16);
 }
 
 extern "C" int sage_loop_mg_error_calculate(SageWorkspace *ws, float *error_host, const float *R10, const float *t10,
@@ -491,9 +496,11 @@ extern "C" int sage_loop_mg_error_calculate(SageWorkspace *ws, float *error_host
                                             const float *homo0, const float *matched_homo1, float scale0, float scale1,
                                             float loss_param, float weight, int N)
 {
-  return mg_common(ws, 1, SAGE_LOSS_FAIR, false, nullptr, nullptr, error_host, R10, t10, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, unscaled_dpts0, matched_unscaled_dpts1,
-                   homo0, matched_homo1, nullptr, nullptr, scale0, scale1, loss_param, weight, N, 16);
+  MgParams p{};
+  p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
+  p.dpts0 = unscaled_dpts0; p.dpts1 = matched_unscaled_dpts1;
+  return mg_common(ws, 1, false, nullptr, nullptr, error_host, p, 16);
 }
 
 extern "C" int sage_tracker_match_geom_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev,
@@ -502,9 +509,11 @@ extern "C" int sage_tracker_match_geom_jac_error_calculate(SageWorkspace *ws, fl
                                                            const float *homo0, const float *matched_homo1, float scale0,
                                                            float loss_param, float weight, int with_scale, int N)
 {
-  return mg_common(ws, with_scale ? 3 : 2, SAGE_LOSS_FAIR, true, AtA_dev, Atb_dev, error_host, R, t, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sampled_dpts0, matched_dpts1,
-                   homo0, matched_homo1, nullptr, nullptr, scale0, 1.f, loss_param, weight, N, 16);
+  MgParams p{};
+  p.R10 = R; p.t10 = t; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = 1.f; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
+  p.dpts0 = sampled_dpts0; p.dpts1 = matched_dpts1;
+  return mg_common(ws, with_scale ? 3 : 2, true, AtA_dev, Atb_dev, error_host, p, 16);
 }
 
 extern "C" int sage_tracker_match_geom_error_calculate(SageWorkspace *ws, float *error_host, const float *R,
@@ -512,9 +521,11 @@ extern "C" int sage_tracker_match_geom_error_calculate(SageWorkspace *ws, float 
                                                        const float *matched_dpts1, const float *homo0,
                                                        const float *matched_homo1, float loss_param, float weight, int N)
 {
-  return mg_common(ws, 2, SAGE_LOSS_FAIR, false, nullptr, nullptr, error_host, R, t, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sampled_dpts0, matched_dpts1, homo0,
-                   matched_homo1, nullptr, nullptr, 1.f, 1.f, loss_param, weight, N, 16);
+  MgParams p{};
+  p.R10 = R; p.t10 = t; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = 1.f; p.scale1 = 1.f; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
+  p.dpts0 = sampled_dpts0; p.dpts1 = matched_dpts1;
+  return mg_common(ws, 2, false, nullptr, nullptr, error_host, p, 16);
 }
 
 extern "C" int sage_cycle_match(SageWorkspace *ws, const float *desc0, const float *desc1, const int64_t *kp_loc1d_0,

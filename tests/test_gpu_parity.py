@@ -784,7 +784,7 @@ def test_valid_locations_and_seeded_sampling(capi, orc):
     ws.close()
 
 
-@pytest.mark.parametrize("CS,N", [(32, 300), (16, 129), (32, 1)])
+@pytest.mark.parametrize("CS,N", [(32, 300), (16, 129), (32, 1), (16, 1000)])
 def test_reprojection_factor_parity(capi, orc, CS, N):
     """f3 sparse reprojection factor (fair loss), mapper (D = 13+CS) and tracker (D = 6) variants, linearize and
     error-only, against the fp32 oracle: AtA/Atb rel-L2 <= 2e-5, error rel <= 1e-5, inlier counts exact; keypoints
@@ -851,7 +851,7 @@ def test_reprojection_factor_parity(capi, orc, CS, N):
     ws.close()
 
 
-@pytest.mark.parametrize("CS,N", [(32, 257), (16, 40)])
+@pytest.mark.parametrize("CS,N", [(32, 257), (16, 40), (16, 700)])
 def test_match_geometry_factor_family_parity(capi, orc, CS, N):
     """f3 match-geometry factors against the fp32 oracle: mapper factor with the four losses (linearize + error), loop
     factor, tracker (6-dof and 7-dof with scale, + error): AtA/Atb rel-L2 <= 2e-5, error rel <= 1e-5.  Includes an
