@@ -28,19 +28,11 @@ extern "C" void sage_workspace_destroy(SageWorkspace *ws)
 {
   if (!ws)
     return;
-  ws->work.release();
-  ws->edge_first.release();
-  ws->edge_tiles.release();
-  ws->partials.release();
-  ws->misc.release();
-  ws->dpt0.release();
-  ws->trk_dpts.release();
-  ws->trk_kp_dpts.release();
   if (ws->host_stats)
     (void)hipHostFree(ws->host_stats);
   if (ws->trk_host)
     (void)hipHostFree(ws->trk_host);
-  delete ws;
+  delete ws; // (its device buffers go with it: DevBuf)
 }
 
 static int ws_prepare(SageWorkspace *ws, int N, size_t partial_floats, LaunchCommon *lc)

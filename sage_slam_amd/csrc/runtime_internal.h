@@ -2,9 +2,12 @@
 //   operators.hip       workspaces, the per-edge operator API (df::*_calculate mirrors), the producer entry points
 //   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame)
 //   window.hip          the batched window engine on a finalized window: linearize / error / solve / LM iteration
+//   window_profile.hip  optional kernel timing of a window: event pool, per-kernel event pairs, phase marks
 //   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
+// window_state.h holds the parts SageWindow is made of (host variables, dense factor side, totals mirror, distributed
+// state, profiler); DevBuf owns its allocation
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -59,21 +62,37 @@ using namespace sage;
 namespace sage_rt
 {
 
+// a device allocation and its owner: released when it goes out of scope; moves, never copies
 struct DevBuf
 {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept { swap(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept
+  {
+    DevBuf(std::move(o)).swap(*this); // (what this one held goes with the temporary)
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void swap(DevBuf &o) noexcept
+  {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
   int reserve(size_t bytes)
   {
     if (bytes <= cap)
       return 0;
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess)
+    {
+      p = nullptr;
       return (int)e;
+    }
     cap = bytes;
     return 0;
   }
@@ -229,6 +248,8 @@ struct ErrorTotalsSide
 
 } // namespace sage
 
+#include "window_state.h"
+
 struct SageWindow
 {
   SageWindowConfig cfg;
@@ -237,11 +258,8 @@ struct SageWindow
   int rank = 0, world = 1;
   int K = 0, B = 0, VS = 0; // VS: floats per keyframe in the device variable array
   std::vector<SageKeyframeView> views;
-  // host variables: [set][kf] ; set 0 = current, 1 = candidate
-  std::vector<float> pose[2], code[2], scale[2];
+  HostVars hv;                      // host variables of both sets, their initial values
   std::vector<float> link_geo_loss; // per link: the geometric factors' Cauchy parameter, 0 = cfg.geo_loss_param
-  std::vector<float> code_init, scale_init, pose_init;
-  std::vector<float> code_added; // codes as added (code_init is the zero prior mean)
   std::vector<std::pair<int, int>> links; // (a, b) with a < b
   std::vector<int> local_links;           // indices into links (links with at least one local directed edge)
   std::vector<int> local_edges;           // this rank's directed edges, global ids 2 * link + direction, ascending (local edge
@@ -249,7 +267,6 @@ struct SageWindow
   int n_edges = 0;                        // local directed edges per factor type (= 2 * local links)
   // device
   DevBuf vars[2];                       // [K][VS]: pose 12, scale 1, code CS
-  DevBuf wide_p, wide_g;                // per-edge results before their fp32 rounding (EdgeOut::wide)
   DevBuf sorted_loc, sorted_homo;       // raster-ordered copies of the keyframes' sampled locations
   std::vector<std::pair<const int64_t *, const float *>> user_samples; // the caller's arrays
   std::vector<int> user_n; // ... and their lengths (views[k].N becomes the tile-padded slot count for keyframes relaid with holes)
@@ -257,36 +274,17 @@ struct SageWindow
   int n_depth = 0;                      // keyframes this rank's edges touch (= entries of depth_items)
   int dpt_set = -1;                     // variable set the depth maps currently hold (-1: none) ...
   bool dgrad_valid = false;             // ... and whether their gradients are up to date as well
-  SageAllReduceFn allreduce = nullptr;  // sharded windows: caller-provided sum all-reduce (see sage_ba.h)
-  void *allreduce_user = nullptr;
-  void *rccl_hook = nullptr;            // sage_window_use_rccl: owned {comm, stream} record behind `allreduce`
-  // sharded windows, domain-decomposed solve (shard_solve.cpp): the all-reduced payload is the separator system
-  SageShardPlan *shard = nullptr;
-  DevBuf sepbuf;                        // device copy of the separator buffer (what the collective sums)
-  std::vector<double> h_sep;
-  double *h_err = nullptr;              // pinned [16]: {linearize tail[4], error pass totals[4], tickets of error_totals_kernel[4],
-                                        // tickets of mirror_totals_kernel[4]} written by the kernels
-  uint64_t mirror_epoch = 0;            // ticket value of the last mirror_totals_kernel (its own slots: h_err[12..15])
-  // development aid (sage_window_emulate_peers): after every all-reduce the contribution of the ranks that are not there
-  // is added from a caller-provided table of packed systems (one per LM iterate since the last reset)
-  const double *emu_rest = nullptr;
-  int emu_n = 0, emu_cur = 0;           // emu_cur: index of the current iterate (reset -> 0, accept -> +1)
-  uint64_t err_epoch = 0;               // ticket value of the last error pass (a host thread can spin on the mirror
-                                        // instead of synchronising the stream: window_spin_totals)
   DevBuf geo_px;                        // merged linearize: per local edge and source pixel {omega, D, dD/dx, dD/dy} (geo -> photo)
   bool merge_ok = false;                // both factor types on, geometric weight > 0, not switched off (SAGE_NO_MERGE)
   DevBuf pk;                            // engine-internal channel-group pyramids [K][3 (f,gx,gy)][FS/4][P][4]
   DevBuf f0s;                           // per keyframe: pre-sampled source features, negated [L][FS/4][N][4]
-  DevBuf ptab[2], gtab[2];              // edge tables per variable set
-  DevBuf work_p, first_p, tiles_p, work_g, first_g, tiles_g;
-  DevBuf rec_first_p, rec_count_p;      // photometric linearize: partial RECORDS per edge (flush_p sub-tiles each)
-  int flush_p = 0, n_rec_p = 0;
+  DenseSide dense[2];                   // [kPhoto], [kGeo]: edge tables, work list, partials, per-edge results
+  PhotoRecordPlan photo_rec;            // the photometric linearize's partial records
   std::vector<int> Nedge;               // samples (slots) per local directed edge: what the photometric run plan is built from
   int tpb_heur = 1;                     // run length the static rule chose (sage_window_tune_runs measures alternatives)
-  DevBuf part_p, part_g;
-  DevBuf AtA_p, Atb_p, stats_p, AtA_g, Atb_g, stats_g;
   DevBuf adj_start, adj, link_edges, packed, errbuf;
-  int n_work_p = 0, n_work_g = 0, tpb_p = 1, tpb_g = 1;
+  TotalsMirror mirror;                  // pinned totals + tickets; written by the kernels only if kernels_mirror_totals()
+  WindowDist dist;                      // all-reduce hook, shard plan, peer emulation, this rank's share of `packed`
   std::vector<double> host_packed;
   std::vector<double> delta;
   // device solver (solve_kernels.hip); nullptr -> duplicate links: host block solve (sage_block_solve).  After a device solve the candidate's host mirrors are refreshed lazily (sync_candidate).
@@ -297,14 +295,9 @@ struct SageWindow
   // linearize-at-candidate LM (SageLmConfig::linearize_at_candidate): which variables the packed system belongs to
   uint64_t vars_epoch = 1, lin_epoch = 0; // lin_epoch == vars_epoch: `packed` is the linearisation at the current variables
   bool spec_err_valid = false;
-  bool packed_reduced = false; // sharded windows: `packed` has been summed over the ranks since it was last assembled
   double spec_error = 0.0;                // total error at that linearisation point (priors included)
   DevBuf packed_save;                     // linearize-at-candidate: the candidate's (reduced) system is formed here; an accepted
                                           // candidate swaps it with `packed` (which always is the current estimate's system)
-  DevBuf packed_loc;                      // reduced windows: this rank's un-reduced share (only the blocks its edges touch are
-                                          // ever written, the rest stays zero), the send buffer of the out-of-place all-reduce
-  DevBuf asm_blocks;                      // ids of those blocks (keyframes, links, tail) for the assembly of packed_loc
-  int n_asm_blocks = 0;
   // matched-keypoint terms (sage_window_add_keypoint_term): host copies as added, then (finalize) this rank's terms in one
   // device pool + table, reprojection terms first
   struct KeypointTermHost
@@ -320,40 +313,27 @@ struct SageWindow
   bool kp_lin = false;                  // the terms have been linearized at least once
   DevBuf kp_pool, kp_table, kp_link_start, kp_link;
   DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, stats_k; // stats_k: [2][n_kr + n_km][2] -- last linearize, last error pass
-  // optional out-of-place form of the all-reduce hook (native RCCL: send != recv); without it: copy + in-place hook
-  int (*allreduce2)(const double *send, double *recv, size_t n, void *user) = nullptr;
   // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
   // (all K keyframes) they were evaluated at
   struct FactorCache
   {
     bool lin = false, err = false;
     std::vector<float> pose, code, scale;         // the key: [K][12], [K][CS], [K]
-    std::vector<float> Ap, bp, sp, Ag, bg, sg;    // per local directed edge: AtA, Atb, (error, n_inliers)
-    // sage_window_prepare_factors: the projected (NearestPsd) double matrices of every local edge, computed on several
-    // host threads right after a prepass; psd_mode < 0: not prepared for the cached linearisation
-    std::vector<double> Cp, Cg;
-    int psd_mode = -1;
+    struct Side
+    {
+      std::vector<float> A, b, s; // per local directed edge: AtA, Atb, (error, n_inliers)
+      // sage_window_prepare_factors: the projected (NearestPsd) double matrices of every local edge, computed on several
+      // host threads right after a prepass
+      std::vector<double> C;
+    } side[2];                    // [kPhoto], [kGeo]
+    int psd_mode = -1;            // < 0: the projected matrices are not prepared for the cached linearisation
   } fc;
-  // optional kernel timing (HIP events on `stream`)
-  // phase marks of an LM iteration on the stream's timeline (profiling only): 0 start of the iteration, 1 system
-  // assembled, 2 all-reduce of the system enqueued / done, 3 candidate written (scatter + host factorisation + retract),
-  // 4 error pass done.  An iteration is the list of marks in the order they were recorded (the classic sequence and the
-  // linearize-at-candidate one order them differently, a rejected evaluation repeats some): the time between two
-  // consecutive marks is booked to the phase the LATER mark closes
-  struct PhaseMarks
-  {
-    std::vector<std::pair<int, hipEvent_t>> ev; // (mark, event) in the order they were recorded
-  };
-  std::vector<PhaseMarks> phase_pending;
-  PhaseMarks phase_cur;
-  double phase_ms[4] = {0, 0, 0, 0}; // linearize, all-reduce, solve, error pass
-  int phase_n = 0;
-  bool profiling = false;
-  int prof_level = 0; // 1: all hot kernels + phase marks, 2: the photometric linearize only
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6]; // (4 / 5: keypoint-term linearize / error launch)
-  std::vector<hipEvent_t> ev_free; // recycled events (creating / destroying one per mark costs API time inside the region being profiled)
-  double prof_ms[6] = {0, 0, 0, 0, 0, 0};
-  int prof_n[6] = {0, 0, 0, 0, 0, 0};
+  WindowProfiler prof;            // optional kernel timing (window_profile.hip)
+
+  // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an
+  // all-reduce hook only (a reduced total is mirrored after the sum: mirror_totals_kernel; a one-rank RCCL communicator or
+  // sage_window_set_allreduce leaves the mirror to that kernel too).  The ONE condition writers and readers share
+  bool kernels_mirror_totals() const { return world == 1 && !dist.allreduce && mirror.h; }
 };
 
 
@@ -370,6 +350,9 @@ static int upload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
 }
 int window_upload_vars(SageWindow *w, int set);
 int window_local_edge(const SageWindow *w, int global_edge); // local index of directed edge 2 * link + dir, or -1
+std::vector<int32_t> window_link_pairs(const SageWindow *w);  // [nlinks][2]: the links as the host solvers take them
 int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false);
 int window_sync_candidate(SageWindow *w, bool stream_idle = false);
+// window_profile.hip
+void prof_attach(SageWindow *w, int which, LaunchCommon &lc); // profiling: an event pair for kernel `which` (LaunchCommon::ev_*)
 void window_phase_mark(SageWindow *w, int which); // profiling: record phase mark `which` on the window's stream

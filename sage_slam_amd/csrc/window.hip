@@ -6,9 +6,6 @@
 namespace sage
 {
 
-
-
-
 // B-index (0..6+CS: pose 6, code CS, scale) -> column of the per-edge system, or -1 if absent
 __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 {
@@ -317,167 +314,12 @@ __global__ void add_doubles_kernel(const double *__restrict__ src, double *__res
 }
 
 } // namespace sage
-static bool ev_get(SageWindow *w, hipEvent_t *e)
+std::vector<int32_t> window_link_pairs(const SageWindow *w)
 {
-  if (!w->ev_free.empty())
-  {
-    *e = w->ev_free.back();
-    w->ev_free.pop_back();
-    return true;
-  }
-  return hipEventCreate(e) == hipSuccess;
-}
-static void ev_put(SageWindow *w, hipEvent_t e)
-{
-  if (e)
-    w->ev_free.push_back(e);
-}
-
-static void prof_attach(SageWindow *w, int which, LaunchCommon &lc)
-{
-  if (!w->profiling || (w->prof_level == 2 && which != 0))
-    return;
-  hipEvent_t a, b;
-  if (!ev_get(w, &a))
-    return;
-  if (!ev_get(w, &b))
-  {
-    ev_put(w, a);
-    return;
-  }
-  lc.ev_start = a;
-  lc.ev_stop = b;
-  w->pending[which].emplace_back(a, b);
-}
-
-void window_phase_mark(SageWindow *w, int which)
-{
-  if (!w->profiling || w->prof_level == 2)
-    return;
-  if (which == 0) // a new iteration: the previous one's marks are complete
-  {
-    if (w->phase_cur.ev.size() >= 2)
-    {
-      if (w->phase_pending.size() >= 1024) // nobody collects them: keep the newest
-      {
-        for (auto &m : w->phase_pending.front().ev)
-          ev_put(w, m.second);
-        w->phase_pending.erase(w->phase_pending.begin());
-      }
-      w->phase_pending.push_back(std::move(w->phase_cur));
-    }
-    else
-      for (auto &m : w->phase_cur.ev)
-        ev_put(w, m.second);
-    w->phase_cur = SageWindow::PhaseMarks{};
-  }
-  else if (w->phase_cur.ev.empty())
-    return; // (a mark outside an iteration: sage_window_solve / _error called on their own)
-  hipEvent_t e;
-  if (w->phase_cur.ev.size() >= 64 || !ev_get(w, &e))
-    return;
-  (void)hipEventRecord(e, w->stream);
-  w->phase_cur.ev.emplace_back(which, e);
-}
-
-extern "C" int sage_window_get_phase_time(SageWindow *w, double *ms4, int *iterations)
-{
-  if (!w || !ms4)
-    return SAGE_E_INVALID;
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  window_phase_mark(w, 0); // flush the iteration in progress
-  for (auto &m : w->phase_cur.ev) // (the mark the flush just recorded opens nothing)
-    ev_put(w, m.second);
-  w->phase_cur = SageWindow::PhaseMarks{};
-  for (auto &pm : w->phase_pending)
-  {
-    // the time between two consecutive marks belongs to the phase the later one closes (1 linearize, 2 all-reduce,
-    // 3 solve, 4 error pass); every evaluation of an iteration counts
-    double d4[4] = {0, 0, 0, 0};
-    bool ok = true;
-    for (size_t i = 1; i < pm.ev.size() && ok; ++i)
-    {
-      float d = 0.f;
-      ok = hipEventElapsedTime(&d, pm.ev[i - 1].second, pm.ev[i].second) == hipSuccess;
-      const int ph = pm.ev[i].first;
-      if (ok && ph >= 1 && ph <= 4)
-        d4[ph - 1] += d;
-    }
-    if (ok)
-    {
-      for (int i = 0; i < 4; ++i)
-        w->phase_ms[i] += d4[i];
-      w->phase_n += 1;
-    }
-    for (auto &m : pm.ev)
-      ev_put(w, m.second);
-  }
-  w->phase_pending.clear();
-  for (int i = 0; i < 4; ++i)
-  {
-    ms4[i] = w->phase_ms[i];
-    w->phase_ms[i] = 0;
-  }
-  if (iterations)
-    *iterations = w->phase_n;
-  w->phase_n = 0;
-  return SAGE_OK;
-}
-
-extern "C" int sage_window_set_profiling(SageWindow *w, int on)
-{
-  if (!w)
-    return SAGE_E_INVALID;
-  w->profiling = on != 0;
-  w->prof_level = on;
-  // a stock of events up front: creating them inside the region being profiled costs API time there
-  while (w->profiling && w->ev_free.size() < 512)
-  {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess)
-      break;
-    w->ev_free.push_back(e);
-  }
-  return SAGE_OK;
-}
-
-extern "C" int sage_window_get_kernel_time(SageWindow *w, int which, double *total_ms, int *launches)
-{
-  if (!w || which < 0 || which > 5)
-    return SAGE_E_INVALID;
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  for (auto &pr : w->pending[which])
-  {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess)
-    {
-      w->prof_ms[which] += ms;
-      w->prof_n[which] += 1;
-    }
-    ev_put(w, pr.first);
-    ev_put(w, pr.second);
-  }
-  w->pending[which].clear();
-  if (total_ms)
-    *total_ms = w->prof_ms[which];
-  if (launches)
-    *launches = w->prof_n[which];
-  w->prof_ms[which] = 0;
-  w->prof_n[which] = 0;
-  return SAGE_OK;
-}
-
-static void upload_vars_host(SageWindow *w, int set, std::vector<float> &buf)
-{
-  buf.assign((size_t)w->K * w->VS, 0.f);
-  const int CS = w->cfg.CS;
-  for (int k = 0; k < w->K; ++k)
-  {
-    float *d = &buf[(size_t)k * w->VS];
-    std::memcpy(d, &w->pose[set][(size_t)k * 12], 12 * sizeof(float));
-    d[12] = w->scale[set][k];
-    std::memcpy(d + 13, &w->code[set][(size_t)k * CS], CS * sizeof(float));
-  }
+  std::vector<int32_t> lk;
+  for (const auto &l : w->links)
+    lk.insert(lk.end(), {l.first, l.second});
+  return lk;
 }
 
 int window_upload_vars(SageWindow *w, int set)
@@ -486,8 +328,9 @@ int window_upload_vars(SageWindow *w, int set)
     w->dpt_set = -1;
   if (set == 0)
     ++w->vars_epoch; // whatever was linearised is no longer the system at the current variables
-  std::vector<float> buf;
-  upload_vars_host(w, set, buf);
+  std::vector<float> buf((size_t)w->K * w->VS, 0.f);
+  for (int k = 0; k < w->K; ++k)
+    w->hv.pack(set, k, w->cfg.CS, &buf[(size_t)k * w->VS]);
   SAGE_HIP(hipMemcpyAsync(w->vars[set].p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice, w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream)); // buf is a temporary
   return SAGE_OK;
@@ -542,25 +385,36 @@ int window_local_edge(const SageWindow *w, int global_edge)
   return it != w->local_edges.end() && *it == global_edge ? (int)(it - w->local_edges.begin()) : -1;
 }
 
-static LaunchCommon window_lc(SageWindow *w, bool photo, bool photo_linearize = false)
+static LaunchCommon window_lc(SageWindow *w, int type, bool photo_linearize = false)
 {
+  const DenseSide &sd = w->dense[type];
   LaunchCommon lc{};
-  lc.work = (photo ? w->work_p : w->work_g).as<WorkItem>();
-  lc.edge_first = (photo ? w->first_p : w->first_g).as<int32_t>();
-  lc.edge_tiles = (photo ? w->tiles_p : w->tiles_g).as<int32_t>();
-  lc.n_work = photo ? w->n_work_p : w->n_work_g;
+  lc.work = sd.work.as<WorkItem>();
+  lc.edge_first = sd.first.as<int32_t>();
+  lc.edge_tiles = sd.tiles.as<int32_t>();
+  lc.n_work = sd.n_work;
   lc.n_edges = w->n_edges;
-  lc.partials = photo ? w->part_p.as<float>() : w->part_g.as<float>();
-  lc.tiles_per_block = photo ? w->tpb_p : w->tpb_g;
-  lc.packed = photo;
-  if (photo_linearize && w->flush_p > 0)
+  lc.partials = sd.part.as<float>();
+  lc.tiles_per_block = sd.tpb;
+  lc.packed = type == kPhoto;
+  if (photo_linearize && w->photo_rec.flush > 0)
   {
     // the linearize (and its per-edge finalize) count partial RECORDS, the error pass work items
-    lc.edge_first = w->rec_first_p.as<int32_t>();
-    lc.edge_tiles = w->rec_count_p.as<int32_t>();
-    lc.flush = w->flush_p;
+    lc.edge_first = w->photo_rec.first.as<int32_t>();
+    lc.edge_tiles = w->photo_rec.count.as<int32_t>();
+    lc.flush = w->photo_rec.flush;
   }
   return lc;
+}
+
+// what the per-edge finalize of either factor type takes from its side (E / P: PhotoEdge / PhotoFinalizeParams, Geo...)
+template <class E, class P>
+static void finalize_side(P &fp, const DenseSide &sd, int set, const LaunchCommon &lc)
+{
+  const EdgeOut out = sd.out();
+  fp.table = sd.tab[set].as<E>();
+  fp.edge_first = lc.edge_first; fp.edge_tiles = lc.edge_tiles; fp.partials = lc.partials;
+  fp.AtA = out.AtA; fp.Atb = out.Atb; fp.stats = out.stats; fp.wide = out.wide;
 }
 
 static AssembleParams window_assemble_params(SageWindow *w)
@@ -568,19 +422,20 @@ static AssembleParams window_assemble_params(SageWindow *w)
   const SageWindowConfig &c = w->cfg;
   AssembleParams ap{};
   const bool has = w->n_edges > 0;
-  ap.AtA_p = (has && c.use_photo) ? w->AtA_p.as<float>() : nullptr;
-  ap.Atb_p = w->Atb_p.as<float>();
-  ap.stats_p = (has && c.use_photo) ? w->stats_p.as<float>() : nullptr;
-  ap.AtA_g = (has && c.use_geo) ? w->AtA_g.as<float>() : nullptr;
-  ap.wide_p = (has && c.use_photo) ? w->wide_p.as<double>() : nullptr;
-  ap.wide_g = (has && c.use_geo) ? w->wide_g.as<double>() : nullptr;
-  ap.Atb_g = w->Atb_g.as<float>();
-  ap.stats_g = (has && c.use_geo) ? w->stats_g.as<float>() : nullptr;
+  const EdgeOut op = w->dense[kPhoto].out(), og = w->dense[kGeo].out();
+  ap.AtA_p = (has && c.use_photo) ? op.AtA : nullptr;
+  ap.Atb_p = op.Atb;
+  ap.stats_p = (has && c.use_photo) ? op.stats : nullptr;
+  ap.wide_p = (has && c.use_photo) ? op.wide : nullptr;
+  ap.AtA_g = (has && c.use_geo) ? og.AtA : nullptr;
+  ap.Atb_g = og.Atb;
+  ap.stats_g = (has && c.use_geo) ? og.stats : nullptr;
+  ap.wide_g = (has && c.use_geo) ? og.wide : nullptr;
   ap.adj_start = w->adj_start.as<int32_t>();
   ap.adj = w->adj.as<AdjEntry>();
   ap.links = w->link_edges.as<LinkEdges>();
   ap.packed = w->packed.as<double>();
-  ap.tail_mirror = w->world == 1 && !w->allreduce ? w->h_err : nullptr; // (a reduced tail is mirrored after the sum)
+  ap.tail_mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kTail : nullptr;
   ap.K = w->K;
   ap.nlinks = (int)w->links.size();
   ap.CS = c.CS;
@@ -622,24 +477,22 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->dpt_set = set;
     w->dgrad_valid = true;
     // main kernels only (stage 1), then ONE finalize launch for both factor types (window_finalize_kernel)
-    LaunchCommon lcg = window_lc(w, false), lcp = window_lc(w, true, true);
+    LaunchCommon lcg = window_lc(w, kGeo), lcp = window_lc(w, kPhoto, true);
     lcg.stage = 1;
     lcp.stage = 1;
     merge = merge && w->merge_ok;
     lcg.merge_geo_weight = lcp.merge_geo_weight = merge ? c.geo_weight : 0.f;
     if (c.use_geo)
     {
-      EdgeOut out{w->AtA_g.as<float>(), w->Atb_g.as<float>(), w->stats_g.as<float>(), w->wide_g.as<double>()};
       prof_attach(w, 1, lcg);
-      SAGE_HIP(launch_geo_linearize(w->stream, c.CS, nullptr, w->gtab[set].as<GeoEdge>(), lcg, c.pyr.cam[0], c.eps,
-                                    c.geo_loss_param, c.geo_weight, out));
+      SAGE_HIP(launch_geo_linearize(w->stream, c.CS, nullptr, w->dense[kGeo].tab[set].as<GeoEdge>(), lcg, c.pyr.cam[0], c.eps,
+                                    c.geo_loss_param, c.geo_weight, w->dense[kGeo].out()));
     }
     if (c.use_photo)
     {
-      EdgeOut out{w->AtA_p.as<float>(), w->Atb_p.as<float>(), w->stats_p.as<float>(), w->wide_p.as<double>()};
       prof_attach(w, 0, lcp);
-      SAGE_HIP(launch_photo_linearize(w->stream, c.CS, c.FS, nullptr, w->ptab[set].as<PhotoEdge>(), lcp, c.pyr,
-                                      c.photo_weights, c.eps, out));
+      SAGE_HIP(launch_photo_linearize(w->stream, c.CS, c.FS, nullptr, w->dense[kPhoto].tab[set].as<PhotoEdge>(), lcp, c.pyr,
+                                      c.photo_weights, c.eps, w->dense[kPhoto].out()));
     }
     {
       const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
@@ -649,16 +502,10 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     WindowFinalizeParams fp{};
     fp.n_p = c.use_photo ? w->n_edges : 0;
     fp.n_g = c.use_geo ? w->n_edges : 0;
-    fp.ph.table = w->ptab[set].as<PhotoEdge>();
-    fp.ph.edge_first = lcp.edge_first; fp.ph.edge_tiles = lcp.edge_tiles; fp.ph.partials = lcp.partials;
-    fp.ph.AtA = w->AtA_p.as<float>(); fp.ph.Atb = w->Atb_p.as<float>(); fp.ph.stats = w->stats_p.as<float>();
-    fp.ph.wide = w->wide_p.as<double>();
+    finalize_side<PhotoEdge>(fp.ph, w->dense[kPhoto], set, lcp);
     for (int l = 0; l < c.pyr.levels; ++l)
       fp.ph.wsum += c.photo_weights[l];
-    fp.ge.table = w->gtab[set].as<GeoEdge>();
-    fp.ge.edge_first = lcg.edge_first; fp.ge.edge_tiles = lcg.edge_tiles; fp.ge.partials = lcg.partials;
-    fp.ge.AtA = w->AtA_g.as<float>(); fp.ge.Atb = w->Atb_g.as<float>(); fp.ge.stats = w->stats_g.as<float>();
-    fp.ge.wide = w->wide_g.as<double>();
+    finalize_side<GeoEdge>(fp.ge, w->dense[kGeo], set, lcg);
     fp.ge.weight = c.geo_weight;
     if (merge)
     {
@@ -679,10 +526,10 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
   // gathers per element -- 17 us; one 1024-thread workgroup per block with two elements per thread took 27 us)
   ap.split = 4;
   int nblocks = w->K + ap.nlinks + 1;
-  if (local_blocks && w->n_asm_blocks > 0)
+  if (local_blocks && w->dist.n_asm_blocks > 0)
   {
-    ap.blocks = w->asm_blocks.as<int32_t>();
-    nblocks = w->n_asm_blocks;
+    ap.blocks = w->dist.asm_blocks.as<int32_t>();
+    nblocks = w->dist.n_asm_blocks;
   }
   if (w->n_kr + w->n_km > 0)
     hipLaunchKernelGGL(assemble_kernel<true>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
@@ -695,7 +542,7 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->have_lin = true;
     w->lin_epoch = set == 0 ? w->vars_epoch : 0; // (a candidate's system becomes current only through lm_step's accept)
     w->spec_err_valid = false;
-    w->packed_reduced = false;
+    w->dist.packed_reduced = false;
   }
   return SAGE_OK;
 }
@@ -734,29 +581,29 @@ static int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
   const bool fused = has && c.use_photo && c.use_geo;
   if (has && c.use_photo)
   {
-    LaunchCommon lc = window_lc(w, true);
+    LaunchCommon lc = window_lc(w, kPhoto);
     prof_attach(w, 2, lc);
     lc.stage = 1; // main kernel only: the per-edge statistics are formed by error_totals_kernel below
     lc.fused_geo_loss_param = fused ? c.geo_loss_param : 0.f;
-    SAGE_HIP(launch_photo_error(w->stream, c.CS, c.FS, nullptr, w->ptab[which].as<PhotoEdge>(), lc, c.pyr,
-                                c.photo_weights, c.eps, w->stats_p.as<float>()));
+    SAGE_HIP(launch_photo_error(w->stream, c.CS, c.FS, nullptr, w->dense[kPhoto].tab[which].as<PhotoEdge>(), lc, c.pyr,
+                                c.photo_weights, c.eps, w->dense[kPhoto].stats.as<float>()));
     float wsum = 0.f;
     for (int l = 0; l < c.pyr.levels; ++l)
       wsum += c.photo_weights[l];
-    ph = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->stats_p.as<float>(), 10.0f * wsum, 1.0f, w->n_edges,
+    ph = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->dense[kPhoto].stats.as<float>(), 10.0f * wsum, 1.0f, w->n_edges,
                          fused ? 4 : 2, 0, 1};
     if (fused)
-      ge = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->stats_g.as<float>(), 10.0f * c.geo_weight,
+      ge = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight,
                            c.geo_weight, w->n_edges, 4, 2, 3};
   }
   if (has && c.use_geo && !fused)
   {
-    LaunchCommon lc = window_lc(w, false);
+    LaunchCommon lc = window_lc(w, kGeo);
     prof_attach(w, 3, lc);
     lc.stage = 1;
-    SAGE_HIP(launch_geo_error(w->stream, c.CS, nullptr, w->gtab[which].as<GeoEdge>(), lc, c.pyr.cam[0], c.eps,
-                              c.geo_loss_param, c.geo_weight, w->stats_g.as<float>()));
-    ge = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->stats_g.as<float>(), 10.0f * c.geo_weight,
+    SAGE_HIP(launch_geo_error(w->stream, c.CS, nullptr, w->dense[kGeo].tab[which].as<GeoEdge>(), lc, c.pyr.cam[0], c.eps,
+                              c.geo_loss_param, c.geo_weight, w->dense[kGeo].stats.as<float>()));
+    ge = ErrorTotalsSide{lc.edge_first, lc.edge_tiles, lc.partials, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight,
                          c.geo_weight, w->n_edges, 2, 0, 1};
   }
   KpTotals kpt{};
@@ -768,14 +615,14 @@ static int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
       return rck;
     kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * (w->n_kr + w->n_km), w->n_kr, w->n_km};
   }
-  w->err_epoch += 1;
-  double *const mirror = w->world == 1 && !w->allreduce && w->h_err ? w->h_err + 4 : nullptr;
+  w->mirror.err_epoch += 1;
+  double *const mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kError : nullptr;
   if (kpt.stats)
     hipLaunchKernelGGL(error_totals_kernel<true>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
-                       (double)w->err_epoch, kpt);
+                       (double)w->mirror.err_epoch, kpt);
   else
     hipLaunchKernelGGL(error_totals_kernel<false>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
-                       (double)w->err_epoch, kpt);
+                       (double)w->mirror.err_epoch, kpt);
   SAGE_HIP(hipGetLastError());
   window_phase_mark(w, 4);
   if (speculate_gradients && has && c.use_geo && w->dpt_set == which && !w->dgrad_valid)
@@ -799,12 +646,12 @@ static int window_total_error(SageWindow *w, int from_linearize, double *err, bo
 static bool window_spin_totals(SageWindow *w, bool reduced_mirror = false)
 {
   // (reduced_mirror: the totals have just been mirrored by mirror_totals_kernel -- its own tickets and epoch)
-  if (!w->h_err)
+  if (!w->mirror.h)
     return false;
-  if (!reduced_mirror && (w->world != 1 || w->allreduce || w->err_epoch == 0))
+  if (!reduced_mirror && (!w->kernels_mirror_totals() || w->mirror.err_epoch == 0))
     return false;
-  const volatile double *t = w->h_err + (reduced_mirror ? 12 : 8);
-  const double want = (double)(reduced_mirror ? w->mirror_epoch : w->err_epoch);
+  const volatile double *t = w->mirror.h + (reduced_mirror ? TotalsMirror::kMirrorTickets : TotalsMirror::kErrorTickets);
+  const double want = (double)(reduced_mirror ? w->mirror.mirror_epoch : w->mirror.err_epoch);
   const auto t0 = std::chrono::steady_clock::now();
   unsigned spins = 0;
   while (!(t[0] == want && t[1] == want && t[2] == want && t[3] == want))
@@ -821,12 +668,12 @@ static bool window_spin_totals(SageWindow *w, bool reduced_mirror = false)
 // the window's all-reduce of n doubles + (peer emulation) the absent ranks' share from table entry `iterate`
 static int window_allreduce(SageWindow *w, double *buf, size_t n, int iterate)
 {
-  if (w->allreduce && w->allreduce(buf, n, w->allreduce_user))
+  if (w->dist.allreduce && w->dist.allreduce(buf, n, w->dist.allreduce_user))
     return SAGE_E_STATE;
-  if (w->emu_rest && w->emu_n > 0)
+  if (w->dist.emu_rest && w->dist.emu_n > 0)
   {
     const size_t np = sage_window_packed_count(w);
-    const double *rest = w->emu_rest + (size_t)(((iterate % w->emu_n) + w->emu_n) % w->emu_n) * np;
+    const double *rest = w->dist.emu_rest + (size_t)(((iterate % w->dist.emu_n) + w->dist.emu_n) % w->dist.emu_n) * np;
     if (n == np)
       hipLaunchKernelGGL(add_doubles_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, w->stream, rest, buf, np);
     else if (n == 4) // error totals of a candidate: the tail of the absent ranks' system at that iterate
@@ -843,14 +690,14 @@ static int window_allreduce(SageWindow *w, double *buf, size_t n, int iterate)
 __global__ void copy_doubles_kernel(const double *__restrict__ src, double *__restrict__ dst, size_t n);
 static int window_allreduce_into(SageWindow *w, const double *send, double *recv, size_t n, int iterate)
 {
-  if (w->allreduce2)
+  if (w->dist.allreduce2)
   {
-    if (w->allreduce2(send, recv, n, w->allreduce_user))
+    if (w->dist.allreduce2(send, recv, n, w->dist.allreduce_user))
       return SAGE_E_STATE;
-    SageAllReduceFn keep = w->allreduce;
-    w->allreduce = nullptr; // (the sum is done: window_allreduce below only adds the emulated peers' share)
+    SageAllReduceFn keep = w->dist.allreduce;
+    w->dist.allreduce = nullptr; // (the sum is done: window_allreduce below only adds the emulated peers' share)
     const int rc = window_allreduce(w, recv, n, iterate);
-    w->allreduce = keep;
+    w->dist.allreduce = keep;
     return rc;
   }
   hipLaunchKernelGGL(copy_doubles_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w->stream, send, recv, n);
@@ -861,11 +708,11 @@ static int window_allreduce_into(SageWindow *w, const double *send, double *recv
 // enqueue the mirror of the (reduced) totals and their tickets
 static int window_mirror_totals(SageWindow *w, bool with_err, const double *system = nullptr)
 {
-  w->mirror_epoch += 1;
+  w->mirror.mirror_epoch += 1;
   hipLaunchKernelGGL(mirror_totals_kernel, dim3(1), dim3(64), 0, w->stream,
                      (system ? system : w->packed.as<double>()) + sage_window_packed_count(w) - 4,
                      with_err ? w->errbuf.as<double>() : nullptr,
-                     w->h_err, (double)w->mirror_epoch);
+                     w->mirror.h, (double)w->mirror.mirror_epoch);
   SAGE_HIP(hipGetLastError());
   return SAGE_OK;
 }
@@ -880,14 +727,9 @@ int window_sync_candidate(SageWindow *w, bool stream_idle)
   const DeviceSolver *S = w->solver;
   if (solver_host_status(S) != 0)
     return SAGE_E_NOT_PSD;
-  const int K = w->K, CS = w->cfg.CS, VS = w->VS;
   const float *v = solver_host_vars(S);
-  for (int k = 0; k < K; ++k)
-  {
-    std::memcpy(&w->pose[1][(size_t)k * 12], v + (size_t)k * VS, 12 * sizeof(float));
-    w->scale[1][k] = v[(size_t)k * VS + 12];
-    std::memcpy(&w->code[1][(size_t)k * CS], v + (size_t)k * VS + 13, CS * sizeof(float));
-  }
+  for (int k = 0; k < w->K; ++k)
+    w->hv.unpack(1, k, w->cfg.CS, v + (size_t)k * w->VS);
   std::memcpy(w->delta.data(), solver_host_delta(S), w->delta.size() * sizeof(double));
   return SAGE_OK;
 }
@@ -928,37 +770,48 @@ static void pose_local(const float *origin, const float *other, double out[6])
   out[5] = k * (Rr[3] - Rr[1]);
 }
 
-static double prior_error(const SageWindow *w, int set)
+// owned_only (sharded windows): the terms of the keyframes THIS rank owns (the other ranks' copies of their variables are
+// stale here).  The owned sum takes keyframe 0's scale / pose terms right behind its code term, the full sum behind every
+// keyframe's code term: each keeps its order, so neither total moves in the last bit
+static double prior_error(const SageWindow *w, int set, bool owned_only = false)
 {
   const SageWindowConfig &c = w->cfg;
   double e = 0;
+  auto keyframe0_terms = [&] {
+    if (c.scale_prior_weight > 0)
+    {
+      const double d = std::log((double)w->hv.scale_init[0]) - std::log((double)w->hv.scale[set][0]);
+      e += c.scale_prior_weight * d * d;
+    }
+    if (c.pose_prior_weight > 0)
+    {
+      double loc[6];
+      pose_local(&w->hv.pose[set][0], &w->hv.pose_init[0], loc);
+      for (int i = 0; i < 6; ++i)
+        e += c.pose_prior_weight * loc[i] * loc[i];
+    }
+  };
   for (int k = 0; k < w->K; ++k)
   {
+    if (owned_only && sage_shard_keyframe_owner(w->dist.shard, k) != w->rank)
+      continue;
     double s = 0;
     for (int i = 0; i < c.CS; ++i)
-      s += (double)w->code[set][(size_t)k * c.CS + i] * w->code[set][(size_t)k * c.CS + i];
+      s += (double)w->hv.code[set][(size_t)k * c.CS + i] * w->hv.code[set][(size_t)k * c.CS + i];
     e += c.code_prior_weight * s / c.CS;
+    if (owned_only && k == 0)
+      keyframe0_terms();
   }
-  if (c.scale_prior_weight > 0)
-  {
-    const double d = std::log((double)w->scale_init[0]) - std::log((double)w->scale[set][0]);
-    e += c.scale_prior_weight * d * d;
-  }
-  if (c.pose_prior_weight > 0)
-  {
-    double loc[6];
-    pose_local(&w->pose[set][0], &w->pose_init[0], loc);
-    for (int i = 0; i < 6; ++i)
-      e += c.pose_prior_weight * loc[i] * loc[i];
-  }
+  if (!owned_only)
+    keyframe0_terms();
   return e;
 }
 
-// total error from the pinned mirror: the edge totals at h_err[at], h_err[at + 1] (0: a system's tail, 4: an error
+// total error from the pinned mirror: the edge totals at mirror.h[at], mirror.h[at + 1] (kTail: a system's tail, kError: an error
 // pass's totals) plus the prior terms at variable set `set`
 static double mirrored_error(const SageWindow *w, int at, int set)
 {
-  return w->h_err[at] + w->h_err[at + 1] + prior_error(w, set);
+  return w->mirror.h[at] + w->mirror.h[at + 1] + prior_error(w, set);
 }
 
 extern "C" int sage_window_total_error(SageWindow *w, int from_linearize, double *err)
@@ -977,14 +830,14 @@ static int window_total_error(SageWindow *w, int from_linearize, double *err, bo
     return rcs;
   // a failed factorisation only invalidates the CANDIDATE: the error at the linearisation point is still served
   const int rc_out = from_linearize ? SAGE_OK : rcs;
-  if (w->world == 1 && !w->allreduce && w->h_err)
+  if (w->kernels_mirror_totals())
   {
-    // single-rank window WITHOUT an all-reduce hook: the kernels mirrored the totals into pinned host memory (the same
-    // condition the writers use -- ap.tail_mirror, the error_totals mirror; a one-rank RCCL communicator or
-    // sage_window_set_allreduce leaves the mirror unwritten and takes the copies below: ADVICE r5)
+    // the kernels mirrored the totals into pinned host memory (the writers -- ap.tail_mirror, the error_totals mirror -- ask
+    // the same predicate; a one-rank RCCL communicator or sage_window_set_allreduce leaves the mirror unwritten and takes
+    // the copies below: ADVICE r5)
     if (!stream_idle)
       SAGE_HIP(hipStreamSynchronize(w->stream));
-    *err = mirrored_error(w, from_linearize ? 0 : 4, from_linearize ? 0 : 1);
+    *err = mirrored_error(w, from_linearize ? TotalsMirror::kTail : TotalsMirror::kError, from_linearize ? 0 : 1);
     return rc_out;
   }
   if (from_linearize)
@@ -1010,18 +863,18 @@ static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::v
     for (int i = 0; i < CS; ++i)
     {
       dadd[k * B + 6 + i] += c.code_prior_weight;
-      gadd[k * B + 6 + i] += c.code_prior_weight * (0.0 - (double)w->code[0][(size_t)k * CS + i]);
+      gadd[k * B + 6 + i] += c.code_prior_weight * (0.0 - (double)w->hv.code[0][(size_t)k * CS + i]);
     }
   if (c.scale_prior_weight > 0)
   {
-    const double s = w->scale[0][0];
+    const double s = w->hv.scale[0][0];
     dadd[6 + CS] += c.scale_prior_weight / (s * s);
-    gadd[6 + CS] += c.scale_prior_weight / s * (std::log((double)w->scale_init[0]) - std::log(s));
+    gadd[6 + CS] += c.scale_prior_weight / s * (std::log((double)w->hv.scale_init[0]) - std::log(s));
   }
   if (c.pose_prior_weight > 0)
   {
     double loc[6];
-    pose_local(&w->pose[0][0], &w->pose_init[0], loc);
+    pose_local(&w->hv.pose[0][0], &w->hv.pose_init[0], loc);
     for (int i = 0; i < 6; ++i)
     {
       dadd[i] += c.pose_prior_weight;
@@ -1036,22 +889,18 @@ static void window_retract_candidate(SageWindow *w, bool local_only)
 {
   const int K = w->K, B = w->B, CS = w->cfg.CS;
   if (local_only)
-  {
-    w->pose[1] = w->pose[0];
-    w->code[1] = w->code[0];
-    w->scale[1] = w->scale[0];
-  }
+    w->hv.copy_set(1, 0);
   for (int k = 0; k < K; ++k)
   {
-    if (local_only && !sage_shard_keyframe_is_local(w->shard, k))
+    if (local_only && !sage_shard_keyframe_is_local(w->dist.shard, k))
       continue;
     float d6[6];
     for (int i = 0; i < 6; ++i)
       d6[i] = (float)w->delta[(size_t)k * B + i];
-    sage_pose_retract(&w->pose[0][(size_t)k * 12], d6, &w->pose[1][(size_t)k * 12]);
+    sage_pose_retract(&w->hv.pose[0][(size_t)k * 12], d6, &w->hv.pose[1][(size_t)k * 12]);
     for (int i = 0; i < CS; ++i)
-      w->code[1][(size_t)k * CS + i] = w->code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
-    w->scale[1][k] = w->scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
+      w->hv.code[1][(size_t)k * CS + i] = w->hv.code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
+    w->hv.scale[1][k] = w->hv.scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
   }
 }
 
@@ -1071,8 +920,8 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
     if (w->dpt_set == 1)
       w->dpt_set = -1; // the solve rewrites the candidate set
     rc = solver_run(w->solver, w->stream, w->packed.as<double>(), w->vars[0].as<float>(), w->vars[1].as<float>(), CS,
-                    damp, c.code_prior_weight, c.scale_prior_weight, c.pose_prior_weight, w->scale_init[0],
-                    &w->pose_init[0]);
+                    damp, c.code_prior_weight, c.scale_prior_weight, c.pose_prior_weight, w->hv.scale_init[0],
+                    &w->hv.pose_init[0]);
     if (rc)
       return rc;
     window_phase_mark(w, 3);
@@ -1097,12 +946,7 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
   // no device solver: the window has duplicate links (solver_create refused them), the host block solve sums them
   std::vector<double> dadd, gadd;
   window_priors(w, dadd, gadd);
-  std::vector<int32_t> lk(2 * w->links.size());
-  for (size_t l = 0; l < w->links.size(); ++l)
-  {
-    lk[2 * l] = w->links[l].first;
-    lk[2 * l + 1] = w->links[l].second;
-  }
+  const std::vector<int32_t> lk = window_link_pairs(w);
   int rcs = sage_block_solve(w->host_packed.data(), K, (int)w->links.size(), lk.data(), B, damp, dadd.data(),
                              gadd.data(), w->delta.data()); // (writes delta only on success)
   if (rcs)
@@ -1132,11 +976,9 @@ extern "C" int sage_window_accept(SageWindow *w)
   int rcs = window_sync_candidate(w);
   if (rcs)
     return rcs;
-  w->pose[0] = w->pose[1];
-  w->code[0] = w->code[1];
-  w->scale[0] = w->scale[1];
+  w->hv.copy_set(0, 1);
   ++w->vars_epoch;
-  ++w->emu_cur;
+  ++w->dist.emu_cur;
   w->dpt_set = w->dpt_set == 1 ? 0 : -1; // depth maps evaluated at the candidate now belong to the current set
   // (a kernel, not hipMemcpyAsync: a device-to-device copy of 11 KB costs ~10 us of API time on the step's critical path)
   const int nv = w->K * w->VS;
@@ -1153,15 +995,15 @@ extern "C" int sage_window_reset(SageWindow *w)
   (void)window_sync_candidate(w);
   for (int s = 0; s < 2; ++s)
   {
-    w->pose[s] = w->pose_init;
-    w->code[s] = w->code_added;
-    w->scale[s] = w->scale_init;
+    w->hv.pose[s] = w->hv.pose_init;
+    w->hv.code[s] = w->hv.code_added;
+    w->hv.scale[s] = w->hv.scale_init;
   }
   int rc;
   if ((rc = window_upload_vars(w, 0)) || (rc = window_upload_vars(w, 1)))
     return rc;
   w->have_lin = false;
-  w->emu_cur = 0;
+  w->dist.emu_cur = 0;
   return SAGE_OK;
 }
 
@@ -1170,11 +1012,11 @@ extern "C" int sage_window_get_keyframe(const SageWindow *w, int kf, float *pose
   if (!w || kf < 0 || kf >= w->K)
     return SAGE_E_INVALID;
   if (pose12)
-    std::memcpy(pose12, &w->pose[0][(size_t)kf * 12], 12 * sizeof(float));
+    std::memcpy(pose12, &w->hv.pose[0][(size_t)kf * 12], 12 * sizeof(float));
   if (code)
-    std::memcpy(code, &w->code[0][(size_t)kf * w->cfg.CS], w->cfg.CS * sizeof(float));
+    std::memcpy(code, &w->hv.code[0][(size_t)kf * w->cfg.CS], w->cfg.CS * sizeof(float));
   if (scale)
-    *scale = w->scale[0][kf];
+    *scale = w->hv.scale[0][kf];
   return SAGE_OK;
 }
 
@@ -1185,9 +1027,9 @@ extern "C" int sage_window_set_keyframe(SageWindow *w, int kf, const float *pose
   (void)window_sync_candidate(w);
   for (int s = 0; s < 2; ++s)
   {
-    std::memcpy(&w->pose[s][(size_t)kf * 12], pose12, 12 * sizeof(float));
-    std::memcpy(&w->code[s][(size_t)kf * w->cfg.CS], code, w->cfg.CS * sizeof(float));
-    w->scale[s][kf] = scale;
+    std::memcpy(&w->hv.pose[s][(size_t)kf * 12], pose12, 12 * sizeof(float));
+    std::memcpy(&w->hv.code[s][(size_t)kf * w->cfg.CS], code, w->cfg.CS * sizeof(float));
+    w->hv.scale[s][kf] = scale;
   }
   if (w->finalized)
   {
@@ -1209,35 +1051,6 @@ extern "C" int sage_window_get_delta(const SageWindow *w, double *delta)
   return SAGE_OK;
 }
 
-// prior error terms of the keyframes THIS rank owns (the other ranks' copies of their variables are stale here)
-static double prior_error_owned(const SageWindow *w, int set)
-{
-  const SageWindowConfig &c = w->cfg;
-  double e = 0;
-  for (int k = 0; k < w->K; ++k)
-  {
-    if (sage_shard_keyframe_owner(w->shard, k) != w->rank)
-      continue;
-    double s2 = 0;
-    for (int i = 0; i < c.CS; ++i)
-      s2 += (double)w->code[set][(size_t)k * c.CS + i] * w->code[set][(size_t)k * c.CS + i];
-    e += c.code_prior_weight * s2 / c.CS;
-    if (k == 0 && c.scale_prior_weight > 0)
-    {
-      const double d = std::log((double)w->scale_init[0]) - std::log((double)w->scale[set][0]);
-      e += c.scale_prior_weight * d * d;
-    }
-    if (k == 0 && c.pose_prior_weight > 0)
-    {
-      double loc[6];
-      pose_local(&w->pose[set][0], &w->pose_init[0], loc);
-      for (int i = 0; i < 6; ++i)
-        e += c.pose_prior_weight * loc[i] * loc[i];
-    }
-  }
-  return e;
-}
-
 __global__ void add_to_double_kernel(double *p, double v) { p[0] += v; }
 
 // local elimination -> all-reduce of the separator system -> separator solve + back substitution of this rank's
@@ -1247,12 +1060,12 @@ __global__ void add_to_double_kernel(double *p, double v) { p[0] += v; }
 static int schur_solve(SageWindow *w, double damp, double *lin_error)
 {
   const int K = w->K, B = w->B;
-  const size_t np = sage_window_packed_count(w), ns = w->h_sep.size();
+  const size_t np = sage_window_packed_count(w), ns = w->dist.h_sep.size();
   SAGE_HIP(hipMemcpyAsync(w->host_packed.data(), w->packed.p, np * sizeof(double), hipMemcpyDeviceToHost, w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream));
   std::vector<double> dadd, gadd;
   window_priors(w, dadd, gadd);
-  int rc = sage_shard_eliminate(w->shard, w->host_packed.data(), damp, dadd.data(), gadd.data(), w->h_sep.data());
+  int rc = sage_shard_eliminate(w->dist.shard, w->host_packed.data(), damp, dadd.data(), gadd.data(), w->dist.h_sep.data());
   if (rc && rc != SAGE_E_NOT_PSD)
     return rc;
   if (rc == SAGE_E_NOT_PSD)
@@ -1260,21 +1073,21 @@ static int schur_solve(SageWindow *w, double damp, double *lin_error)
     // a failed local elimination is flagged in the spare tail slot [ns-3] (a positive count after the sum: every rank
     // sees it); the separator blocks of this rank are void, the error totals at the linearisation point (tail[0..4],
     // written by sage_shard_eliminate before it factorises) stay finite so that st->error is valid on every rank
-    std::fill(w->h_sep.begin(), w->h_sep.end() - 8, 0.0);
-    w->h_sep[ns - 3] = 1.0;
+    std::fill(w->dist.h_sep.begin(), w->dist.h_sep.end() - 8, 0.0);
+    w->dist.h_sep[ns - 3] = 1.0;
   }
-  w->h_sep[ns - 4] = prior_error_owned(w, 0);
-  SAGE_HIP(hipMemcpyAsync(w->sepbuf.p, w->h_sep.data(), ns * sizeof(double), hipMemcpyHostToDevice, w->stream));
-  if (w->allreduce(w->sepbuf.as<double>(), ns, w->allreduce_user))
+  w->dist.h_sep[ns - 4] = prior_error(w, 0, true);
+  SAGE_HIP(hipMemcpyAsync(w->dist.sepbuf.p, w->dist.h_sep.data(), ns * sizeof(double), hipMemcpyHostToDevice, w->stream));
+  if (w->dist.allreduce(w->dist.sepbuf.as<double>(), ns, w->dist.allreduce_user))
     return SAGE_E_STATE;
-  SAGE_HIP(hipMemcpyAsync(w->h_sep.data(), w->sepbuf.p, ns * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+  SAGE_HIP(hipMemcpyAsync(w->dist.h_sep.data(), w->dist.sepbuf.p, ns * sizeof(double), hipMemcpyDeviceToHost, w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream));
   if (lin_error)
-    *lin_error = w->h_sep[ns - 8] + w->h_sep[ns - 7] + w->h_sep[ns - 4];
-  if (w->h_sep[ns - 3] > 0.0 || std::isnan(w->h_sep[0]))
+    *lin_error = w->dist.h_sep[ns - 8] + w->dist.h_sep[ns - 7] + w->dist.h_sep[ns - 4];
+  if (w->dist.h_sep[ns - 3] > 0.0 || std::isnan(w->dist.h_sep[0]))
     return SAGE_E_NOT_PSD;
   w->delta.assign((size_t)K * B, 0.0);
-  rc = sage_shard_solve(w->shard, w->h_sep.data(), w->delta.data());
+  rc = sage_shard_solve(w->dist.shard, w->dist.h_sep.data(), w->delta.data());
   if (rc)
     return rc; // SAGE_E_NOT_PSD of the separator system: identical on every rank
   window_retract_candidate(w, true);
@@ -1287,45 +1100,29 @@ extern "C" int sage_window_sync_variables(SageWindow *w)
 {
   if (!w || !w->finalized)
     return SAGE_E_STATE;
-  if (!w->shard)
+  if (!w->dist.shard)
     return SAGE_OK; // every rank solves the whole system: nothing to exchange
-  if (!w->allreduce)
+  if (!w->dist.allreduce)
     return SAGE_E_STATE;
   const int K = w->K, CS = w->cfg.CS, VS = 13 + CS;
   std::vector<double> buf((size_t)K * VS, 0.0);
   for (int k = 0; k < K; ++k)
-    if (sage_shard_keyframe_owner(w->shard, k) == w->rank)
-    {
-      double *b = &buf[(size_t)k * VS];
-      for (int i = 0; i < 12; ++i)
-        b[i] = w->pose[0][(size_t)k * 12 + i];
-      b[12] = w->scale[0][k];
-      for (int i = 0; i < CS; ++i)
-        b[13 + i] = w->code[0][(size_t)k * CS + i];
-    }
-  DevBuf d;
-  int rc = d.reserve(buf.size() * sizeof(double));
-  if (rc)
-    return rc;
-  SAGE_HIP(hipMemcpyAsync(d.p, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice, w->stream));
-  if (w->allreduce(d.as<double>(), buf.size(), w->allreduce_user))
+    if (sage_shard_keyframe_owner(w->dist.shard, k) == w->rank)
+      w->hv.pack(0, k, CS, &buf[(size_t)k * VS]);
+  int rc;
   {
-    d.release();
-    return SAGE_E_STATE;
+    DevBuf d; // the collective's device buffer: gone with this block, on every way out of it
+    if ((rc = d.reserve(buf.size() * sizeof(double))))
+      return rc;
+    SAGE_HIP(hipMemcpyAsync(d.p, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice, w->stream));
+    if (w->dist.allreduce(d.as<double>(), buf.size(), w->dist.allreduce_user))
+      return SAGE_E_STATE;
+    SAGE_HIP(hipMemcpyAsync(buf.data(), d.p, buf.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+    SAGE_HIP(hipStreamSynchronize(w->stream));
   }
-  SAGE_HIP(hipMemcpyAsync(buf.data(), d.p, buf.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  d.release();
   for (int s = 0; s < 2; ++s)
     for (int k = 0; k < K; ++k)
-    {
-      const double *b = &buf[(size_t)k * VS];
-      for (int i = 0; i < 12; ++i)
-        w->pose[s][(size_t)k * 12 + i] = (float)b[i];
-      w->scale[s][k] = (float)b[12];
-      for (int i = 0; i < CS; ++i)
-        w->code[s][(size_t)k * CS + i] = (float)b[13 + i];
-    }
+      w->hv.unpack(s, k, CS, &buf[(size_t)k * VS]);
   if ((rc = window_upload_vars(w, 0)) || (rc = window_upload_vars(w, 1)))
     return rc;
   return SAGE_OK;
@@ -1353,8 +1150,8 @@ enum class LmSeq { classic, schur, at_candidate };
 //  second collective and its host round trip are not), the classic sequence on a single rank
 static LmSeq lm_sequence_for(const SageWindow *w, const SageLmConfig *cfg)
 {
-  const bool sharded = w->allreduce != nullptr; // (a hook on a single-rank window is honoured too)
-  if (sharded && w->shard)
+  const bool sharded = w->dist.allreduce != nullptr; // (a hook on a single-rank window is honoured too)
+  if (sharded && w->dist.shard)
     return LmSeq::schur;
   const bool at_candidate = cfg->linearize_at_candidate > 0 || (cfg->linearize_at_candidate == 0 && sharded);
   return at_candidate && !w->links.empty() ? LmSeq::at_candidate : LmSeq::classic;
@@ -1374,10 +1171,10 @@ struct LmEval
 static int window_form_system(SageWindow *w, int set, double *dst, int it)
 {
   int rc;
-  if (!w->allreduce)
+  if (!w->dist.allreduce)
     return (rc = window_linearize_set(w, set, dst, false, true)) ? rc : window_mirror_totals(w, false, dst);
-  if ((rc = window_linearize_set(w, set, w->packed_loc.as<double>(), true, true)) ||
-      (rc = window_allreduce_into(w, w->packed_loc.as<double>(), dst, sage_window_packed_count(w), it)))
+  if ((rc = window_linearize_set(w, set, w->dist.packed_loc.as<double>(), true, true)) ||
+      (rc = window_allreduce_into(w, w->dist.packed_loc.as<double>(), dst, sage_window_packed_count(w), it)))
     return rc;
   window_phase_mark(w, 2);
   return window_mirror_totals(w, false, dst);
@@ -1387,35 +1184,35 @@ static int window_form_system(SageWindow *w, int set, double *dst, int it)
 static int lm_prepare(LmSeq seq, SageWindow *w, SageLmState *st)
 {
   int rc;
-  const bool sharded = w->allreduce != nullptr;
+  const bool sharded = w->dist.allreduce != nullptr;
   const size_t np = sage_window_packed_count(w);
   if (seq != LmSeq::at_candidate)
   {
     if ((rc = window_linearize_set(w, 0, nullptr, false, true)) ||
-        (seq == LmSeq::classic && sharded && (rc = window_allreduce(w, w->packed.as<double>(), np, w->emu_cur))))
+        (seq == LmSeq::classic && sharded && (rc = window_allreduce(w, w->packed.as<double>(), np, w->dist.emu_cur))))
       return rc;
     window_phase_mark(w, 2);
     return SAGE_OK;
   }
   if ((rc = w->packed_save.reserve(np * sizeof(double))))
     return rc;
-  if (sharded && !w->packed_loc.p)
+  if (sharded && !w->dist.packed_loc.p)
   {
-    if ((rc = w->packed_loc.reserve(np * sizeof(double))))
+    if ((rc = w->dist.packed_loc.reserve(np * sizeof(double))))
       return rc;
-    SAGE_HIP(hipMemsetAsync(w->packed_loc.p, 0, np * sizeof(double), w->stream)); // blocks of other ranks: zero for good
+    SAGE_HIP(hipMemsetAsync(w->dist.packed_loc.p, 0, np * sizeof(double), w->stream)); // blocks of other ranks: zero for good
   }
   // the system at the current estimate is reused only if it is the GLOBAL one: sage_window_linearize / _prepass and the
   // classic sequence leave a system behind that is not booked as reduced (every rank sees the same flags: same call
   // sequence on all ranks)
   bool mirrored_now = false;
-  if (!(w->have_lin && w->lin_epoch == w->vars_epoch && (!sharded || w->packed_reduced)))
+  if (!(w->have_lin && w->lin_epoch == w->vars_epoch && (!sharded || w->dist.packed_reduced)))
   {
-    if ((rc = window_form_system(w, 0, w->packed.as<double>(), w->emu_cur)))
+    if ((rc = window_form_system(w, 0, w->packed.as<double>(), w->dist.emu_cur)))
       return rc;
     w->have_lin = true;
     w->lin_epoch = w->vars_epoch;
-    w->packed_reduced = true; // (summed over the ranks, or nothing to sum)
+    w->dist.packed_reduced = true; // (summed over the ranks, or nothing to sum)
     w->spec_err_valid = false;
     mirrored_now = true;
   }
@@ -1427,7 +1224,7 @@ static int lm_prepare(LmSeq seq, SageWindow *w, SageLmState *st)
       return rc;
     if (!window_spin_totals(w, true))
       SAGE_HIP(hipStreamSynchronize(w->stream));
-    w->spec_error = mirrored_error(w, 0, 0);
+    w->spec_error = mirrored_error(w, TotalsMirror::kTail, 0);
     w->spec_err_valid = true;
   }
   st->error = w->spec_error;
@@ -1441,7 +1238,7 @@ static int lm_prepare(LmSeq seq, SageWindow *w, SageLmState *st)
 static int lm_evaluate(LmSeq seq, SageWindow *w, SageLmState *st, bool first, LmEval &ev)
 {
   int rc;
-  const bool sharded = w->allreduce != nullptr;
+  const bool sharded = w->dist.allreduce != nullptr;
   if (seq == LmSeq::schur)
   {
     double lin_error = 0;
@@ -1456,8 +1253,8 @@ static int lm_evaluate(LmSeq seq, SageWindow *w, SageLmState *st, bool first, Lm
     if ((rc = sage_window_error(w, 1)))
       return rc;
     hipLaunchKernelGGL(add_to_double_kernel, dim3(1), dim3(1), 0, w->stream, w->errbuf.as<double>(),
-                       prior_error_owned(w, 1));
-    if (w->allreduce(w->errbuf.as<double>(), 4, w->allreduce_user))
+                       prior_error(w, 1, true));
+    if (w->dist.allreduce(w->errbuf.as<double>(), 4, w->dist.allreduce_user))
       return SAGE_E_STATE;
     double t4[4];
     SAGE_HIP(hipMemcpyAsync(t4, w->errbuf.p, sizeof(t4), hipMemcpyDeviceToHost, w->stream));
@@ -1476,13 +1273,13 @@ static int lm_evaluate(LmSeq seq, SageWindow *w, SageLmState *st, bool first, Lm
     return rc;
   if (seq == LmSeq::at_candidate)
   {
-    std::memcpy(ev.cur_tot, w->h_err, sizeof(ev.cur_tot)); // (mirrored and seen at the end of the previous evaluation)
+    std::memcpy(ev.cur_tot, w->mirror.h, sizeof(ev.cur_tot)); // (mirrored and seen at the end of the previous evaluation)
     ev.have_cur_tot = true;
     bool not_psd;
-    if ((rc = window_form_system(w, 1, w->packed_save.as<double>(), w->emu_cur + 1)) ||
+    if ((rc = window_form_system(w, 1, w->packed_save.as<double>(), w->dist.emu_cur + 1)) ||
         (rc = window_wait_mirror(w, &not_psd)))
       return rc;
-    st->candidate_error = not_psd ? INFINITY : mirrored_error(w, 0, 1);
+    st->candidate_error = not_psd ? INFINITY : mirrored_error(w, TotalsMirror::kTail, 1);
     return SAGE_OK;
   }
   if ((rc = window_error_pass(w, 1, !sharded)))
@@ -1498,12 +1295,12 @@ static int lm_evaluate(LmSeq seq, SageWindow *w, SageLmState *st, bool first, Lm
     return rc == SAGE_E_NOT_PSD ? SAGE_OK : rc;
   }
   bool not_psd;
-  if ((rc = window_allreduce(w, w->errbuf.as<double>(), 4, w->emu_cur + 1)) || (rc = window_mirror_totals(w, true)) ||
+  if ((rc = window_allreduce(w, w->errbuf.as<double>(), 4, w->dist.emu_cur + 1)) || (rc = window_mirror_totals(w, true)) ||
       (rc = window_wait_mirror(w, &not_psd)))
     return rc;
   if (first)
-    st->error = mirrored_error(w, 0, 0);
-  st->candidate_error = not_psd ? INFINITY : mirrored_error(w, 4, 1);
+    st->error = mirrored_error(w, TotalsMirror::kTail, 0);
+  st->candidate_error = not_psd ? INFINITY : mirrored_error(w, TotalsMirror::kError, 1);
   return SAGE_OK;
 }
 
@@ -1513,10 +1310,9 @@ static int lm_accept(LmSeq seq, SageWindow *w, const SageLmState *st)
   const int rc = sage_window_accept(w);
   if (rc || seq != LmSeq::at_candidate)
     return rc;
-  std::swap(w->packed.p, w->packed_save.p);
-  std::swap(w->packed.cap, w->packed_save.cap);
+  w->packed.swap(w->packed_save);
   w->lin_epoch = w->vars_epoch;
-  w->packed_reduced = true; // (summed over the ranks by window_form_system, or nothing to sum)
+  w->dist.packed_reduced = true; // (summed over the ranks by window_form_system, or nothing to sum)
   w->spec_error = st->candidate_error;
   return SAGE_OK;
 }
@@ -1525,14 +1321,14 @@ static int lm_accept(LmSeq seq, SageWindow *w, const SageLmState *st)
 static void lm_reject(SageWindow *w, const LmEval &ev)
 {
   if (ev.have_cur_tot)
-    std::memcpy(w->h_err, ev.cur_tot, sizeof(ev.cur_tot));
+    std::memcpy(w->mirror.h, ev.cur_tot, sizeof(ev.cur_tot));
 }
 
 extern "C" int sage_window_lm_step(SageWindow *w, SageLmState *st, const SageLmConfig *cfg)
 {
   if (!w || !st || !cfg)
     return SAGE_E_INVALID;
-  if (w->world > 1 && !w->allreduce)
+  if (w->world > 1 && !w->dist.allreduce)
     return SAGE_E_STATE;
   const LmSeq seq = lm_sequence_for(w, cfg);
   auto clampd = [&](double d) { return std::min(std::max((double)cfg->min_damp, d), (double)cfg->max_damp); };

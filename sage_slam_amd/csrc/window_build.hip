@@ -41,33 +41,10 @@ extern "C" void sage_window_destroy(SageWindow *w)
         sage::host_threads_shutdown();
     }
   } last_out;
-  DevBuf *bufs[] = {&w->packed_save, &w->packed_loc, &w->asm_blocks, &w->geo_px, &w->rec_first_p, &w->rec_count_p, &w->wide_p, &w->wide_g, &w->sorted_loc, &w->sorted_homo, &w->vars[0], &w->vars[1], &w->dpt, &w->dgrad, &w->depth_items[0], &w->depth_items[1],
-                    &w->pk, &w->f0s, &w->ptab[0], &w->ptab[1], &w->gtab[0], &w->gtab[1], &w->work_p, &w->first_p, &w->tiles_p,
-                    &w->work_g, &w->first_g, &w->tiles_g, &w->part_p, &w->part_g, &w->AtA_p, &w->Atb_p,
-                    &w->stats_p, &w->AtA_g, &w->Atb_g, &w->stats_g, &w->adj_start, &w->adj, &w->link_edges,
-                    &w->packed, &w->errbuf, &w->kp_pool, &w->kp_table, &w->kp_link_start, &w->kp_link, &w->AtA_kr, &w->Atb_kr,
-                    &w->AtA_km, &w->Atb_km, &w->stats_k};
-  for (DevBuf *b : bufs)
-    b->release();
-  std::free(w->rccl_hook); // (the communicator itself belongs to the caller)
-  sage_shard_plan_destroy(w->shard);
-  w->sepbuf.release();
+  // device buffers, the pinned mirror and the profiler's events go with their owners (DevBuf, TotalsMirror, WindowProfiler)
+  std::free(w->dist.rccl_hook); // (the communicator itself belongs to the caller)
+  sage_shard_plan_destroy(w->dist.shard);
   solver_destroy(w->solver);
-  if (w->h_err)
-    (void)hipHostFree(w->h_err);
-  for (auto &pm : w->phase_pending)
-    for (auto &m : pm.ev)
-      (void)hipEventDestroy(m.second);
-  for (auto &m : w->phase_cur.ev)
-    (void)hipEventDestroy(m.second);
-  for (auto &pend : w->pending)
-    for (auto &pr : pend)
-    {
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
-  for (hipEvent_t e : w->ev_free)
-    (void)hipEventDestroy(e);
   delete w;
 }
 
@@ -81,13 +58,13 @@ extern "C" int sage_window_add_keyframe(SageWindow *w, const SageKeyframeView *v
   w->views.push_back(*v);
   for (int s = 0; s < 2; ++s)
   {
-    w->pose[s].insert(w->pose[s].end(), pose12, pose12 + 12);
-    w->code[s].insert(w->code[s].end(), code, code + w->cfg.CS);
-    w->scale[s].push_back(scale);
+    w->hv.pose[s].insert(w->hv.pose[s].end(), pose12, pose12 + 12);
+    w->hv.code[s].insert(w->hv.code[s].end(), code, code + w->cfg.CS);
+    w->hv.scale[s].push_back(scale);
   }
-  w->pose_init.insert(w->pose_init.end(), pose12, pose12 + 12);
-  w->code_added.insert(w->code_added.end(), code, code + w->cfg.CS);
-  w->scale_init.push_back(scale);
+  w->hv.pose_init.insert(w->hv.pose_init.end(), pose12, pose12 + 12);
+  w->hv.code_added.insert(w->hv.code_added.end(), code, code + w->cfg.CS);
+  w->hv.scale_init.push_back(scale);
   return w->K++;
 }
 
@@ -291,22 +268,31 @@ static int photo_flush_for_runs(int tpb)
   return plan::record_cadence(tpb);
 }
 
+// a side's work list: items, per edge its first item and its number of items (the caller synchronises before `wl` dies)
+static int upload_work_list(DenseSide &sd, const WorkList &wl, hipStream_t s)
+{
+  int rc;
+  sd.n_work = (int)wl.work.size();
+  sd.tpb = wl.tiles_per_block;
+  if ((rc = upload(sd.work, wl.work, s)) || (rc = upload(sd.first, wl.edge_first, s)) || (rc = upload(sd.tiles, wl.edge_tiles, s)))
+    return rc;
+  return SAGE_OK;
+}
+
 // (re)build the photometric work list for runs of `tpb` sub-tiles and upload it; the partial-record buffer grows to fit
 static int window_plan_photo_runs(SageWindow *w, int tpb, int flush)
 {
   WorkList wp;
   wp.build(w->Nedge, tpb, nullptr, flush);
   int rc;
-  w->n_work_p = (int)wp.work.size();
-  w->tpb_p = wp.tiles_per_block;
-  w->flush_p = wp.flush;
-  w->n_rec_p = wp.n_records;
-  if ((rc = upload(w->work_p, wp.work, w->stream)) || (rc = upload(w->first_p, wp.edge_first, w->stream)) ||
-      (rc = upload(w->tiles_p, wp.edge_tiles, w->stream)) || (rc = upload(w->rec_first_p, wp.rec_first, w->stream)) ||
-      (rc = upload(w->rec_count_p, wp.rec_count, w->stream)))
+  w->photo_rec.flush = wp.flush;
+  w->photo_rec.n = wp.n_records;
+  DenseSide &ph = w->dense[kPhoto];
+  if ((rc = upload_work_list(ph, wp, w->stream)) || (rc = upload(w->photo_rec.first, wp.rec_first, w->stream)) ||
+      (rc = upload(w->photo_rec.count, wp.rec_count, w->stream)))
     return rc;
   SAGE_HIP(hipStreamSynchronize(w->stream)); // (the host vectors go out of scope)
-  return w->part_p.reserve(std::max<size_t>(1, std::max(w->n_work_p, w->n_rec_p)) * photo_partial_floats(w->cfg.CS) * sizeof(float));
+  return ph.part.reserve(std::max<size_t>(1, std::max(ph.n_work, w->photo_rec.n)) * photo_partial_floats(w->cfg.CS) * sizeof(float));
 }
 
 // edge lengths in the plan's unit: sub-tiles per edge
@@ -416,18 +402,6 @@ static int finalize_pyramids(SageWindow *w)
   return SAGE_OK;
 }
 
-// the sample relay's device temporaries, released on every way out of it (DevBuf itself has no destructor: the window's
-// buffers are released by sage_window_destroy)
-struct RelayTemps
-{
-  DevBuf items, mark, status, tiles, pad;
-  ~RelayTemps()
-  {
-    for (DevBuf *b : {&items, &mark, &status, &tiles, &pad})
-      b->release();
-  }
-};
-
 // 4. leaves sorted_loc / sorted_homo and the views pointing at them: the sampled locations validated (the kernels index depth
 //    maps / basis rows with them unchecked) and relaid in tile order (engine-owned copies; see producers.hip: the sums are order
 //    independent, the L1 is not); views[k].N becomes the slot count of a keyframe relaid with holes
@@ -465,7 +439,10 @@ static int finalize_samples(SageWindow *w)
                         w->sorted_loc.as<long long>() + soff[k], w->sorted_homo.as<float>() + 3 * soff[k],
                         w->views[k].N};
   std::vector<int> status((size_t)2 * K, 0), tiles_nonempty(K, 0), pad_flags(K, 0);
-  RelayTemps d; // (declared after the host vectors: released before they die)
+  struct
+  {
+    DevBuf items, mark, status, tiles, pad;
+  } d; // the relay's device temporaries (declared after the host vectors: released before they die)
   if ((rc = upload(d.items, items, w->stream)) || (rc = d.mark.reserve((size_t)K * HW * sizeof(int))) ||
       (rc = d.status.reserve((size_t)2 * K * sizeof(int))) || (rc = d.tiles.reserve((size_t)K * sizeof(int))))
     return rc;
@@ -636,7 +613,7 @@ static int finalize_edge_tables(SageWindow *w, FinalizeState &fs)
       if (s == 0)
         (w->local_edges[e] % 2 == 0 ? fs.le[l].e_ab : fs.le[l].e_ba) = e;
     }
-    if ((rc = upload(w->ptab[s], pt, w->stream)) || (rc = upload(w->gtab[s], gt, w->stream)))
+    if ((rc = upload(w->dense[kPhoto].tab[s], pt, w->stream)) || (rc = upload(w->dense[kGeo].tab[s], gt, w->stream)))
       return rc;
     SAGE_HIP(hipStreamSynchronize(w->stream));
   }
@@ -663,10 +640,7 @@ static int finalize_work_lists(SageWindow *w, const FinalizeState &fs)
     tpb_g = std::max(1, atoi(e));
   WorkList wl;
   wl.build(fs.Nedge, tpb_g);
-  w->n_work_g = (int)wl.work.size();
-  w->tpb_g = wl.tiles_per_block;
-  if ((rc = upload(w->work_g, wl.work, w->stream)) || (rc = upload(w->first_g, wl.edge_first, w->stream)) ||
-      (rc = upload(w->tiles_g, wl.edge_tiles, w->stream)))
+  if ((rc = upload_work_list(w->dense[kGeo], wl, w->stream)))
     return rc;
   SAGE_HIP(hipStreamSynchronize(w->stream));
   int tpb = plan::photo_run(tiles, w->cfg.FS);
@@ -686,16 +660,10 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
 {
   const int CS = w->cfg.CS, K = w->K;
   int rc;
-  const size_t Dp = 13 + CS, Dg = 14 + 2 * CS;
   const size_t ne = std::max(1, w->n_edges);
-  if ((rc = w->part_p.reserve(std::max<size_t>(1, std::max(w->n_work_p, w->n_rec_p)) * photo_partial_floats(CS) * sizeof(float))) ||
-      (rc = w->part_g.reserve(std::max<size_t>(1, w->n_work_g) * geo_partial_floats(CS) * sizeof(float))) ||
-      (rc = w->AtA_p.reserve(ne * Dp * Dp * sizeof(float))) || (rc = w->Atb_p.reserve(ne * Dp * sizeof(float))) ||
-      (rc = w->stats_p.reserve(ne * 2 * sizeof(float))) || (rc = w->AtA_g.reserve(ne * Dg * Dg * sizeof(float))) ||
-      (rc = w->Atb_g.reserve(ne * Dg * sizeof(float))) || (rc = w->stats_g.reserve(ne * 2 * sizeof(float))))
-    return rc;
-  if ((rc = w->wide_p.reserve(ne * (Dp * Dp + Dp) * sizeof(double))) ||
-      (rc = w->wide_g.reserve(ne * (Dg * Dg + Dg) * sizeof(double))))
+  DenseSide &ph = w->dense[kPhoto], &ge = w->dense[kGeo];
+  if ((rc = ph.reserve_results(ne, dense_dim(kPhoto, CS), std::max(ph.n_work, w->photo_rec.n), photo_partial_floats(CS))) ||
+      (rc = ge.reserve_results(ne, dense_dim(kGeo, CS), ge.n_work, geo_partial_floats(CS))))
     return rc;
   // adjacency for the assembly
   std::vector<int32_t> adj_start(K + 1, 0);
@@ -722,17 +690,17 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
       if (fs.le[l].e_ab >= 0 || fs.le[l].e_ba >= 0)
         ids.push_back(K + (int32_t)l);
     ids.push_back(K + (int32_t)w->links.size()); // the tail
-    w->n_asm_blocks = (int)ids.size();
-    if ((rc = upload(w->asm_blocks, ids, w->stream)))
+    w->dist.n_asm_blocks = (int)ids.size();
+    if ((rc = upload(w->dist.asm_blocks, ids, w->stream)))
       return rc;
     SAGE_HIP(hipStreamSynchronize(w->stream));
   }
   SAGE_HIP(hipMemsetAsync(w->packed.p, 0, sage_window_packed_count(w) * sizeof(double), w->stream));
   SAGE_HIP(hipMemsetAsync(w->errbuf.p, 0, 4 * sizeof(double), w->stream));
-  if (!w->h_err)
+  if (!w->mirror.h)
   {
-    SAGE_HIP(hipHostMalloc(reinterpret_cast<void **>(&w->h_err), 16 * sizeof(double), hipHostMallocDefault));
-    std::memset(w->h_err, 0, 16 * sizeof(double));
+    SAGE_HIP(hipHostMalloc(reinterpret_cast<void **>(&w->mirror.h), TotalsMirror::kDoubles * sizeof(double), hipHostMallocDefault));
+    std::memset(w->mirror.h, 0, TotalsMirror::kDoubles * sizeof(double));
   }
   w->host_packed.assign(sage_window_packed_count(w), 0.0);
   w->delta.assign((size_t)K * w->B, 0.0);
@@ -748,17 +716,12 @@ static int finalize_solver(SageWindow *w, const FinalizeState &fs)
     return rc;
   if (!fs.domain_solve)
     return SAGE_OK;
-  std::vector<int32_t> lk(2 * w->links.size());
-  for (size_t l = 0; l < w->links.size(); ++l)
-  {
-    lk[2 * l] = w->links[l].first;
-    lk[2 * l + 1] = w->links[l].second;
-  }
-  if ((rc = sage_shard_plan_create(w->K, (int)w->links.size(), lk.data(), w->B, w->rank, w->world, &w->shard)))
+  const std::vector<int32_t> lk = window_link_pairs(w);
+  if ((rc = sage_shard_plan_create(w->K, (int)w->links.size(), lk.data(), w->B, w->rank, w->world, &w->dist.shard)))
     return rc;
-  const size_t ns = sage_shard_sep_count(w->shard);
-  w->h_sep.assign(ns, 0.0);
-  if ((rc = w->sepbuf.reserve(ns * sizeof(double))))
+  const size_t ns = sage_shard_sep_count(w->dist.shard);
+  w->dist.h_sep.assign(ns, 0.0);
+  if ((rc = w->dist.sepbuf.reserve(ns * sizeof(double))))
     return rc;
   w->host_packed.resize(sage_window_packed_count(w));
   return SAGE_OK;
@@ -813,18 +776,18 @@ extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_
     return SAGE_E_STATE;
   const int rule = w->tpb_heur;
   if (tpb_out)
-    *tpb_out = w->tpb_p;
+    *tpb_out = w->dense[kPhoto].tpb;
   if (tpb_rule_out)
     *tpb_rule_out = rule;
   if (ms_rule_out)
     *ms_rule_out = 0.f;
   if (ms_best_out)
     *ms_best_out = 0.f;
-  if (getenv("SAGE_PHOTO_TPB") || w->world > 1 || w->allreduce || w->n_edges == 0 || !(w->cfg.use_photo))
+  if (getenv("SAGE_PHOTO_TPB") || w->world > 1 || w->dist.allreduce || w->n_edges == 0 || !(w->cfg.use_photo))
     return SAGE_OK;
   const std::vector<int> cand = plan::tune_candidates(rule, plan::typical_edge(edge_tiles(w->Nedge)));
-  const bool prof_was = w->profiling;
-  const int level_was = w->prof_level;
+  const bool prof_was = w->prof.profiling;
+  const int level_was = w->prof.prof_level;
   int rc = sage_window_set_profiling(w, 1);
   double best_ms = 0.0, rule_ms = 0.0;
   int best = rule;
@@ -879,7 +842,7 @@ extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_
     best = rule;
   const int rc2 = window_plan_photo_runs(w, rc ? rule : best, photo_flush_for_runs(rc ? rule : best));
   if (tpb_out)
-    *tpb_out = w->tpb_p;
+    *tpb_out = w->dense[kPhoto].tpb;
   if (ms_rule_out)
     *ms_rule_out = (float)rule_ms;
   if (ms_best_out)

@@ -177,9 +177,9 @@ extern "C" int sage_window_set_allreduce(SageWindow *w, SageAllReduceFn fn, void
 {
   if (!w)
     return SAGE_E_INVALID;
-  w->allreduce = fn;
-  w->allreduce2 = nullptr;
-  w->allreduce_user = user;
+  w->dist.allreduce = fn;
+  w->dist.allreduce2 = nullptr;
+  w->dist.allreduce_user = user;
   return SAGE_OK;
 }
 
@@ -236,17 +236,6 @@ struct RcclHook
   hipStream_t stream;
 };
 
-int rccl_allreduce_cb(double *buf, size_t n, void *user)
-{
-  RcclHook *h = static_cast<RcclHook *>(user);
-  const ncclResult_t r = rccl().AllReduce(buf, buf, n, ncclDouble, ncclSum, h->comm, h->stream);
-  if (r != ncclSuccess)
-  {
-    fprintf(stderr, "[sage] ncclAllReduce: %s\n", rccl().GetErrorString ? rccl().GetErrorString(r) : "error");
-    return 1;
-  }
-  return 0;
-}
 int rccl_allreduce2_cb(const double *send, double *recv, size_t n, void *user)
 {
   RcclHook *h = static_cast<RcclHook *>(user);
@@ -258,6 +247,7 @@ int rccl_allreduce2_cb(const double *send, double *recv, size_t n, void *user)
   }
   return 0;
 }
+int rccl_allreduce_cb(double *buf, size_t n, void *user) { return rccl_allreduce2_cb(buf, buf, n, user); } // in place
 } // namespace
 
 extern "C" int sage_rccl_unique_id(unsigned char *id128)
@@ -322,16 +312,16 @@ extern "C" int sage_window_use_rccl(SageWindow *w, void *nccl_comm)
     return SAGE_E_INVALID;
   if (!rccl().ok)
     return SAGE_E_UNSUPPORTED;
-  std::free(w->rccl_hook);
+  std::free(w->dist.rccl_hook);
   RcclHook *h = static_cast<RcclHook *>(std::malloc(sizeof(RcclHook)));
   if (!h)
     return SAGE_E_STATE;
   h->comm = static_cast<ncclComm_t>(nccl_comm);
   h->stream = w->stream;
-  w->rccl_hook = h;
-  w->allreduce = rccl_allreduce_cb;
-  w->allreduce2 = rccl_allreduce2_cb;
-  w->allreduce_user = h;
+  w->dist.rccl_hook = h;
+  w->dist.allreduce = rccl_allreduce_cb;
+  w->dist.allreduce2 = rccl_allreduce2_cb;
+  w->dist.allreduce_user = h;
   return SAGE_OK;
 }
 
@@ -344,9 +334,9 @@ extern "C" int sage_window_emulate_peers(SageWindow *w, const double *rest_dev, 
 {
   if (!w || (rest_dev && n_iterates < 1))
     return SAGE_E_INVALID;
-  w->emu_rest = rest_dev;
-  w->emu_n = rest_dev ? n_iterates : 0;
-  w->emu_cur = 0;
+  w->dist.emu_rest = rest_dev;
+  w->dist.emu_n = rest_dev ? n_iterates : 0;
+  w->dist.emu_cur = 0;
   return SAGE_OK;
 }
 

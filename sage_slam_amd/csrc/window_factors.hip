@@ -11,16 +11,15 @@ extern "C" int sage_window_get_edge(const SageWindow *w, int type, int e, float 
   const int le = window_local_edge(w, e);
   if (le < 0)
     return SAGE_E_INVALID;
-  const size_t D = type == 0 ? 13 + w->cfg.CS : 14 + 2 * w->cfg.CS;
-  const DevBuf &A = type == 0 ? w->AtA_p : w->AtA_g, &b = type == 0 ? w->Atb_p : w->Atb_g,
-               &st = type == 0 ? w->stats_p : w->stats_g;
+  const size_t D = dense_dim(type, w->cfg.CS);
+  const EdgeOut out = w->dense[type].out();
   SAGE_HIP(hipStreamSynchronize(w->stream));
   if (AtA)
-    SAGE_HIP(hipMemcpy(AtA, A.as<float>() + (size_t)le * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
+    SAGE_HIP(hipMemcpy(AtA, out.AtA + (size_t)le * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
   if (Atb)
-    SAGE_HIP(hipMemcpy(Atb, b.as<float>() + (size_t)le * D, D * sizeof(float), hipMemcpyDeviceToHost));
+    SAGE_HIP(hipMemcpy(Atb, out.Atb + (size_t)le * D, D * sizeof(float), hipMemcpyDeviceToHost));
   float s2[2];
-  SAGE_HIP(hipMemcpy(s2, st.as<float>() + (size_t)le * 2, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  SAGE_HIP(hipMemcpy(s2, out.stats + (size_t)le * 2, 2 * sizeof(float), hipMemcpyDeviceToHost));
   if (err)
     *err = s2[0];
   if (n_in)
@@ -62,22 +61,22 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
     fc.scale.assign(scales, scales + K);
   }
   // the window's CURRENT variables become the requested values (both sets: a later solve starts from them)
-  if (std::memcmp(w->pose[0].data(), pose12, np * sizeof(float)) != 0 ||
-      std::memcmp(w->code[0].data(), codes, nc * sizeof(float)) != 0 ||
-      std::memcmp(w->scale[0].data(), scales, (size_t)K * sizeof(float)) != 0)
+  if (std::memcmp(w->hv.pose[0].data(), pose12, np * sizeof(float)) != 0 ||
+      std::memcmp(w->hv.code[0].data(), codes, nc * sizeof(float)) != 0 ||
+      std::memcmp(w->hv.scale[0].data(), scales, (size_t)K * sizeof(float)) != 0)
   {
     (void)window_sync_candidate(w);
     for (int s = 0; s < 2; ++s)
     {
-      w->pose[s].assign(pose12, pose12 + np);
-      w->code[s].assign(codes, codes + nc);
-      w->scale[s].assign(scales, scales + K);
+      w->hv.pose[s].assign(pose12, pose12 + np);
+      w->hv.code[s].assign(codes, codes + nc);
+      w->hv.scale[s].assign(scales, scales + K);
     }
     if ((rc = window_upload_vars(w, 0)) || (rc = window_upload_vars(w, 1)))
       return rc;
     w->have_lin = false;
   }
-  const size_t ne = (size_t)w->n_edges, Dp = 13 + CS, Dg = 14 + 2 * CS;
+  const size_t ne = (size_t)w->n_edges;
   if (jacobians)
   {
     if ((rc = sage_window_linearize(w)))
@@ -90,23 +89,17 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
     dst.resize(n);
     return n ? hipMemcpy(dst.data(), src.p, n * sizeof(float), hipMemcpyDeviceToHost) : hipSuccess;
   };
-  if (w->cfg.use_photo)
+  for (int type = kPhoto; type <= kGeo; ++type)
   {
+    if (!(type == kPhoto ? w->cfg.use_photo : w->cfg.use_geo))
+      continue;
+    const size_t D = dense_dim(type, CS);
     if (jacobians)
     {
-      SAGE_HIP(pull(fc.Ap, w->AtA_p, ne * Dp * Dp));
-      SAGE_HIP(pull(fc.bp, w->Atb_p, ne * Dp));
+      SAGE_HIP(pull(fc.side[type].A, w->dense[type].AtA, ne * D * D));
+      SAGE_HIP(pull(fc.side[type].b, w->dense[type].Atb, ne * D));
     }
-    SAGE_HIP(pull(fc.sp, w->stats_p, ne * 2));
-  }
-  if (w->cfg.use_geo)
-  {
-    if (jacobians)
-    {
-      SAGE_HIP(pull(fc.Ag, w->AtA_g, ne * Dg * Dg));
-      SAGE_HIP(pull(fc.bg, w->Atb_g, ne * Dg));
-    }
-    SAGE_HIP(pull(fc.sg, w->stats_g, ne * 2));
+    SAGE_HIP(pull(fc.side[type].s, w->dense[type].stats, ne * 2));
   }
   fc.lin = jacobians != 0;
   fc.err = true;
@@ -123,7 +116,7 @@ extern "C" int sage_window_factor_error(const SageWindow *w, int type, int e, do
   if (!fc.err)
     return SAGE_E_STATE;
   const int le = local_edge_index(w, e);
-  const std::vector<float> &st = type == 0 ? fc.sp : fc.sg;
+  const std::vector<float> &st = fc.side[type].s;
   if (le < 0 || (size_t)le * 2 + 1 >= st.size())
     return SAGE_E_INVALID;
   *err_out = (double)st[(size_t)le * 2];
@@ -140,13 +133,13 @@ extern "C" int sage_window_factor(const SageWindow *w, int type, int e, int psd_
     return SAGE_E_STATE;
   const int le = local_edge_index(w, e);
   const int CS = w->cfg.CS;
-  const size_t D = type == 0 ? 13 + CS : 14 + 2 * CS;
-  const std::vector<float> &A = type == 0 ? fc.Ap : fc.Ag, &b = type == 0 ? fc.bp : fc.bg, &st = type == 0 ? fc.sp : fc.sg;
+  const size_t D = dense_dim(type, CS);
+  const std::vector<float> &A = fc.side[type].A, &b = fc.side[type].b, &st = fc.side[type].s;
   if (le < 0 || ((size_t)le + 1) * D * D > A.size())
     return SAGE_E_INVALID;
   if (f_out)
     *f_out = (double)st[(size_t)le * 2];
-  const std::vector<double> &Cc = type == 0 ? fc.Cp : fc.Cg;
+  const std::vector<double> &Cc = fc.side[type].C;
   if (fc.psd_mode == psd_mode && ((size_t)le + 1) * D * D <= Cc.size()) // prepared on the host threads already
     return sage_factor_cut_blocks(type, CS, Cc.data() + (size_t)le * D * D, b.data() + (size_t)le * D, G_out, g_out,
                                   dims_out, nkeys_out);
@@ -168,11 +161,11 @@ extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_th
   if (fc.psd_mode == psd_mode)
     return SAGE_OK;
   const int CS = w->cfg.CS;
-  const size_t Dp = 13 + CS, Dg = 14 + 2 * CS;
-  const size_t nep = fc.Ap.size() / (Dp * Dp), neg = fc.Ag.size() / (Dg * Dg);
+  const size_t Dp = dense_dim(kPhoto, CS), Dg = dense_dim(kGeo, CS);
+  const size_t nep = fc.side[kPhoto].A.size() / (Dp * Dp), neg = fc.side[kGeo].A.size() / (Dg * Dg);
   fc.psd_mode = -1; // the projected matrices are being rewritten: whatever they held is gone until this call succeeds
-  fc.Cp.assign(nep * Dp * Dp, 0.0);
-  fc.Cg.assign(neg * Dg * Dg, 0.0);
+  fc.side[kPhoto].C.assign(nep * Dp * Dp, 0.0);
+  fc.side[kGeo].C.assign(neg * Dg * Dg, 0.0);
   const size_t total = nep + neg;
   if (n_threads <= 0)
     n_threads = (int)std::min<unsigned>(64u, std::max(1u, std::thread::hardware_concurrency() / 4)); // a quarter of the host, <= 64
@@ -188,9 +181,9 @@ extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_th
         return;
       int rc;
       if (i < neg)
-        rc = sage_factor_psd(1, CS, fc.Ag.data() + i * Dg * Dg, psd_mode, fc.Cg.data() + i * Dg * Dg);
+        rc = sage_factor_psd(1, CS, fc.side[kGeo].A.data() + i * Dg * Dg, psd_mode, fc.side[kGeo].C.data() + i * Dg * Dg);
       else
-        rc = sage_factor_psd(0, CS, fc.Ap.data() + (i - neg) * Dp * Dp, psd_mode, fc.Cp.data() + (i - neg) * Dp * Dp);
+        rc = sage_factor_psd(0, CS, fc.side[kPhoto].A.data() + (i - neg) * Dp * Dp, psd_mode, fc.side[kPhoto].C.data() + (i - neg) * Dp * Dp);
       if (rc)
         bad.store(rc, std::memory_order_relaxed);
     }

@@ -1,0 +1,143 @@
+// window_state.h -- the parts SageWindow (runtime_internal.h) is made of, one struct per owner: the host variables, a dense
+// factor type's device state, the totals mirror, the distributed state, the profiler.  Included from runtime_internal.h
+// (after DevBuf); host code only.
+#pragma once
+
+namespace sage_rt
+{
+
+enum : int { kPhoto = 0, kGeo = 1 }; // dense factor types: AdjEntry::type, the `type` of the C ABI
+
+// columns of a dense factor type's per-edge system
+static inline size_t dense_dim(int type, int CS) { return type == kPhoto ? 13 + (size_t)CS : 14 + 2 * (size_t)CS; }
+
+// ---- host variables: [set][kf]; set 0 = current, 1 = candidate ----
+struct HostVars
+{
+  std::vector<float> pose[2], code[2], scale[2];
+  std::vector<float> code_init, scale_init, pose_init;
+  std::vector<float> code_added; // codes as added (code_init is the zero prior mean)
+  void copy_set(int dst, int src) { pose[dst] = pose[src], code[dst] = code[src], scale[dst] = scale[src]; }
+
+  // a keyframe's record of the [K][VS] device layout: pose 12, scale 1, code CS (T: float on the device, double as the
+  // payload of sage_window_sync_variables)
+  template <class T>
+  void pack(int set, int k, int CS, T *rec) const
+  {
+    for (int i = 0; i < 12; ++i)
+      rec[i] = pose[set][(size_t)k * 12 + i];
+    rec[12] = scale[set][k];
+    for (int i = 0; i < CS; ++i)
+      rec[13 + i] = code[set][(size_t)k * CS + i];
+  }
+  template <class T>
+  void unpack(int set, int k, int CS, const T *rec)
+  {
+    for (int i = 0; i < 12; ++i)
+      pose[set][(size_t)k * 12 + i] = (float)rec[i];
+    scale[set][k] = (float)rec[12];
+    for (int i = 0; i < CS; ++i)
+      code[set][(size_t)k * CS + i] = (float)rec[13 + i];
+  }
+};
+
+// ---- one dense factor type (photometric / geometric) on the device ----
+struct DenseSide
+{
+  DevBuf tab[2];              // edge table per variable set (PhotoEdge / GeoEdge)
+  DevBuf work, first, tiles;  // work list: items, per edge its first item and its number of items
+  DevBuf part;                // workgroup partials
+  DevBuf AtA, Atb, stats;     // per-edge results
+  DevBuf wide;                // ... before their fp32 rounding (EdgeOut::wide)
+  int n_work = 0, tpb = 1;
+  EdgeOut out() const { return EdgeOut{AtA.as<float>(), Atb.as<float>(), stats.as<float>(), wide.as<double>()}; }
+  // room for the results of `ne` edges with D columns and for `records` partials of `partial_floats` floats
+  int reserve_results(size_t ne, size_t D, size_t records, size_t partial_floats)
+  {
+    int rc;
+    if ((rc = part.reserve(std::max<size_t>(1, records) * partial_floats * sizeof(float))) ||
+        (rc = AtA.reserve(ne * D * D * sizeof(float))) || (rc = Atb.reserve(ne * D * sizeof(float))) ||
+        (rc = stats.reserve(ne * 2 * sizeof(float))) || (rc = wide.reserve(ne * (D * D + D) * sizeof(double))))
+      return rc;
+    return 0;
+  }
+};
+
+// photometric linearize only: partial RECORDS per edge (`flush` sub-tiles each; the error pass counts work items)
+struct PhotoRecordPlan
+{
+  DevBuf first, count;
+  int flush = 0, n = 0;
+};
+
+// ---- pinned mirror of the totals, written by the kernels; the host spins on the tickets instead of synchronising ----
+struct TotalsMirror
+{
+  // slot groups of h[kDoubles]: the linearize tail {err_photo, err_geo, n_photo, n_geo}, the error pass's totals (same
+  // order), the tickets of error_totals_kernel, the tickets of mirror_totals_kernel
+  enum : int { kTail = 0, kError = 4, kErrorTickets = 8, kMirrorTickets = 12, kDoubles = 16 };
+  double *h = nullptr;       // hipHostMalloc'd by finalize, freed here
+  uint64_t err_epoch = 0;    // ticket value of the last error pass
+  uint64_t mirror_epoch = 0; // ticket value of the last mirror_totals_kernel
+  TotalsMirror() = default;
+  TotalsMirror(const TotalsMirror &) = delete;
+  TotalsMirror &operator=(const TotalsMirror &) = delete;
+  ~TotalsMirror()
+  {
+    if (h)
+      (void)hipHostFree(h);
+  }
+};
+
+// ---- sharded windows ----
+struct WindowDist
+{
+  SageAllReduceFn allreduce = nullptr; // caller-provided sum all-reduce (see sage_ba.h)
+  // optional out-of-place form of the hook (native RCCL: send != recv); without it: copy + in-place hook
+  int (*allreduce2)(const double *send, double *recv, size_t n, void *user) = nullptr;
+  void *allreduce_user = nullptr;
+  void *rccl_hook = nullptr;           // sage_window_use_rccl: owned {comm, stream} record behind `allreduce`
+  // domain-decomposed solve (shard_solve.cpp): the all-reduced payload is the separator system
+  SageShardPlan *shard = nullptr;
+  DevBuf sepbuf;                       // device copy of the separator buffer (what the collective sums)
+  std::vector<double> h_sep;
+  // development aid (sage_window_emulate_peers): after every all-reduce the contribution of the ranks that are not there
+  // is added from a caller-provided table of packed systems (one per LM iterate since the last reset)
+  const double *emu_rest = nullptr;
+  int emu_n = 0, emu_cur = 0;          // emu_cur: index of the current iterate (reset -> 0, accept -> +1)
+  DevBuf packed_loc;                   // reduced windows: this rank's un-reduced share (only the blocks its edges touch are
+                                       // ever written, the rest stays zero), the send buffer of the out-of-place all-reduce
+  DevBuf asm_blocks;                   // ids of those blocks (keyframes, links, tail) for the assembly of packed_loc
+  int n_asm_blocks = 0;
+  bool packed_reduced = false;         // `packed` has been summed over the ranks since it was last assembled
+};
+
+// ---- optional kernel timing (HIP events on the window's stream): window_profile.hip ----
+struct WindowProfiler
+{
+  // phase marks of an LM iteration on the stream's timeline: 0 start of the iteration, 1 system assembled, 2 all-reduce of
+  // the system enqueued / done, 3 candidate written (scatter + host factorisation + retract), 4 error pass done.  An
+  // iteration is the list of marks in the order they were recorded (the classic sequence and the linearize-at-candidate
+  // one order them differently, a rejected evaluation repeats some): the time between two consecutive marks is booked to
+  // the phase the LATER mark closes
+  struct PhaseMarks
+  {
+    std::vector<std::pair<int, hipEvent_t>> ev; // (mark, event) in the order they were recorded
+  };
+  std::vector<PhaseMarks> phase_pending;
+  PhaseMarks phase_cur;
+  double phase_ms[4] = {0, 0, 0, 0}; // linearize, all-reduce, solve, error pass
+  int phase_n = 0;
+  bool profiling = false;
+  int prof_level = 0; // 1: all hot kernels + phase marks, 2: the photometric linearize only
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6]; // (4 / 5: keypoint-term linearize / error launch)
+  std::vector<hipEvent_t> ev_free; // recycled events (creating / destroying one per mark costs API time inside the region being profiled)
+  double prof_ms[6] = {0, 0, 0, 0, 0, 0};
+  int prof_n[6] = {0, 0, 0, 0, 0, 0};
+  WindowProfiler() = default;
+  WindowProfiler(const WindowProfiler &) = delete;
+  WindowProfiler &operator=(const WindowProfiler &) = delete;
+  ~WindowProfiler(); // destroys every event it holds
+};
+
+} // namespace sage_rt
