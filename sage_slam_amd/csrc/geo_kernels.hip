@@ -15,15 +15,11 @@
 #include "sage_internal.h"
 #include "finalize_bodies.h"
 
-#ifndef SAGE_GEO_WAVES
-#define SAGE_GEO_WAVES 2 // workgroups per CU the linearize kernel is register-budgeted for (x4 waves)
-#endif
-#ifndef SAGE_GEO_AHEAD
-#define SAGE_GEO_AHEAD 2 // pixel groups whose operand loads are in flight ahead of the MFMAs
-#endif
-
 namespace sage
 {
+
+constexpr int kGeoWaves = 2; // workgroups per CU the linearize kernel is register-budgeted for (x4 waves)
+constexpr int kGeoAhead = 2; // pixel groups whose operand loads are in flight ahead of the MFMAs
 
 struct GeoParams
 {
@@ -40,11 +36,6 @@ struct GeoParams
 // MERGE (linearize only; LaunchCommon::merge_geo_weight): the blocks that involve code0 only through t0 = kappa*b0 -- the
 // 3 t0 t0^T tiles and the 2 y t0^T tiles of 15 at CS = 32 -- are contracted by the photometric kernel of the same pair,
 // which gets {omega, D, grad D} of every pixel through GeoEdge::px_out; their accumulators stay zero here
-
-__device__ __forceinline__ int gload_loc(const void *loc, int is64, int n)
-{
-  return is64 ? (int)reinterpret_cast<const long long *>(loc)[n] : reinterpret_cast<const int *>(loc)[n];
-}
 
 // per-pixel hand-over from the geometry phase (lane = pixel) to the contraction phase (lane = (channel i, pixel k)):
 //   [0..3] tap byte offsets (int bits)  [4..7] sqrt(omega)*tap weights  [8] sqrt(omega)*kappa  [9] loc*CS*4 (int bits)
@@ -95,7 +86,7 @@ __device__ __forceinline__ void geo_scalar_rc(int k, int &r, int &c)
 constexpr int kGeoLinBlock = kBlock;
 
 template <int CS, bool JAC, bool MERGE = false>
-__global__ __launch_bounds__(kBlock, JAC ? SAGE_GEO_WAVES : 4) void geo_kernel(const GeoParams prm)
+__global__ __launch_bounds__(kBlock, JAC ? kGeoWaves : 4) void geo_kernel(const GeoParams prm)
 {
   constexpr int NW = kWaves;
   constexpr int N16 = geo_n16(CS);
@@ -157,7 +148,7 @@ __global__ __launch_bounds__(kBlock, JAC ? SAGE_GEO_WAVES : 4) void geo_kernel(c
     const int tile = wi.tile + h;
     const int n = tile * kTile + wq * 64 + lane;
     bool in_range = n < N;
-    int my_loc = in_range ? gload_loc(E.loc, E.loc_is_i64, n) : 0;
+    int my_loc = in_range ? load_loc(E.loc, E.loc_is_i64, n) : 0;
     in_range = in_range && (unsigned)my_loc < (unsigned)(W * H); // a location outside the image is dropped, not read
     my_loc = in_range ? my_loc : 0;
     // depth of the source pixel: s0*(bias + basis.code), read from the keyframe's depth map (:514-521)
@@ -272,14 +263,15 @@ __global__ __launch_bounds__(kBlock, JAC ? SAGE_GEO_WAVES : 4) void geo_kernel(c
     {
       const int i = lane & 15, k = lane >> 4;
       const uint32_t lane_off = (uint32_t)i * (NB == 2 ? 8u : 4u);
-      constexpr int G = 16, AHEAD = SAGE_GEO_AHEAD;
+      constexpr int G = 16, AHEAD = kGeoAhead;
       f32x4 o4[G + 1], w4[G + 1];
       float yi[G + 1], kap[G + 1];
       int locp[G + 1];
       float tb[G + 1][NB], tq[G + 1][4][NB]; // CS = 16: one channel per lane
       f32x2 tbp[G + 1], tqp[G + 1][4];         // CS = 32: a channel pair per lane, kept as register pairs
 // (macros, not lambdas: a buffer descriptor captured by a closure loses its provable uniformity and every load
-//  becomes a waterfall loop)
+//  becomes a waterfall loop; with the descriptors as arguments instead, the lambdas compile to another instruction stream
+//  and register allocation of all four linearize kernels -- profiles/photo_kernel_refactor_ab.txt)
 #define SAGE_GEO_READ_STASH(g)                                                         \
   {                                                                                    \
     const float *p_ = st_w + ((g) * 4 + k) * kGeoStashLD;                              \
@@ -451,9 +443,8 @@ __global__ __launch_bounds__(kFinalizeBlock) void geo_finalize_kernel(const GeoF
 
 hipError_t launch_stats_finalize(hipStream_t s, const LaunchCommon &lc, float *stats, float fallback, float scale);
 
-template <int CS>
-static hipError_t geo_lin_impl(hipStream_t s, const GeoEdge *single, const GeoEdge *table, const LaunchCommon &lc,
-                               const SageCamera &cam, float eps, float loss_param, float weight, const EdgeOut &out)
+static GeoParams make_geo_params(const GeoEdge *single, const GeoEdge *table, const LaunchCommon &lc, const SageCamera &cam,
+                                 float eps, float loss_param)
 {
   GeoParams p{};
   if (single)
@@ -468,6 +459,14 @@ static hipError_t geo_lin_impl(hipStream_t s, const GeoEdge *single, const GeoEd
   p.width = (int)cam.w;
   p.height = (int)cam.h;
   p.n_work = lc.n_work;
+  return p;
+}
+
+template <int CS>
+static hipError_t geo_lin_impl(hipStream_t s, const GeoEdge *single, const GeoEdge *table, const LaunchCommon &lc,
+                               const SageCamera &cam, float eps, float loss_param, float weight, const EdgeOut &out)
+{
+  const GeoParams p = make_geo_params(single, table, lc, cam, eps, loss_param);
   if (lc.stage != 2)
   {
     if (lc.ev_start)
@@ -507,19 +506,7 @@ template <int CS>
 static hipError_t geo_err_impl(hipStream_t s, const GeoEdge *single, const GeoEdge *table, const LaunchCommon &lc,
                                const SageCamera &cam, float eps, float loss_param, float weight, float *stats)
 {
-  GeoParams p{};
-  if (single)
-    p.single = *single;
-  p.table = table;
-  p.work = lc.work;
-  p.partials = lc.partials;
-  p.cam = cam;
-  p.eps = eps;
-  p.loss_param = loss_param;
-  p.tiles_per_block = lc.tiles_per_block;
-  p.width = (int)cam.w;
-  p.height = (int)cam.h;
-  p.n_work = lc.n_work;
+  const GeoParams p = make_geo_params(single, table, lc, cam, eps, loss_param);
   if (lc.ev_start)
     (void)hipEventRecord(lc.ev_start, s);
   hipLaunchKernelGGL((geo_kernel<CS, false>), dim3(lc.n_work), dim3(kBlock), 0, s, p);

@@ -9,9 +9,18 @@
 //        with h = (fx_l gx, fy_l gy) the level-scaled sampled gradient, r = m (f0 - f1)
 //   J_c = h^T P_unit,  P_unit = Q M_n,  Q = [A | q] (2x7): A = Jpi_unit R1^T [I | -[Xw]x],  q = dpi/dd
 //        M_n = [[I6, -I6, 0, 0], [0, 0, s0 b_n^T, d_n/s0]]            (P_pose1 = -P_pose0)
-//   => per pixel S = Q^T G Q (7x7), u = Q^T v (7); 37 scalars are summed with wave64 DPP reductions,
-//      the code blocks  sum_n S66 b_n b_n^T  and  sum_n [S(0:6,6); S66 d; u6] b_n^T  are f32 MFMA
-//      (v_mfma_f32_16x16x4_f32, K = 4 pixels) contractions fed from the LDS basis tile.
+//   => per pixel S = Q^T G Q (7x7), u = Q^T v (7).  Everything that is summed over the pixels is an f32 MFMA
+//      (v_mfma_f32_16x16x4_f32, K = 4 pixels) contraction over a wave's 64 pixels:
+//        code-code tiles   sum_n S66 b_n b_n^T                      cross tiles   sum_n [S(0:6,6); S66 d; u6] b_n^T
+//        pose tile         sum_n [GQ0 GQ1 v]^T [Q0 Q1 q6 d]: the 34 pose / scale sums as one more tile instead of 34 wave
+//                          reductions (folded into the record's scalar slots when the record is written)
+//      The basis rows b_n come from global memory directly in MFMA operand layout (16 lanes x dwordx2 = one 128-byte row),
+//      hand-tracked loads kPhotoAhead pixel groups ahead; the per-pixel rows travel from the sampling phase (lane = pixel) to
+//      the contraction (lane = (channel, pixel)) through a wave-private LDS stash.  Only error, inliers and sigma d^2 are
+//      summed per lane and wave-reduced once per record.
+//   Sampling (engine layout): the wave copies the bounding box of its 64 destination footprints into LDS with LDS-direct
+//      buffer loads and reads every bilinear tap as a ds_read_b128 ("LDS-staged sampler" below); footprints that do not
+//      fit, and the per-edge operator API's reference layout (MODE 0), gather through the texture path.
 //
 // Algorithmic bytes per source pixel: 4*[4*FS*rho + CS + 6].
 #include <type_traits>
@@ -49,55 +58,20 @@ struct PhotoParams
   int exact_coord;
 };
 
-__device__ __forceinline__ int load_loc(const void *loc, int is64, int n)
-{
-  return is64 ? (int)reinterpret_cast<const long long *>(loc)[n] : reinterpret_cast<const int *>(loc)[n];
-}
+// ---- tuning constants (each with the measurement that set it; the alternatives that were code are in DESIGN s7) ----
+constexpr int kPhotoWaves = 3;     // workgroups per CU the linearize kernel is register-budgeted for (x4 waves)
+// error pass at FS = 16: 5 workgroups per CU (94 VGPRs, no spills; 4: 0.255 ms, 5: 0.246, 6 spills: 0.45); FS = 32 lands at
+// 102 VGPRs = 5 per SIMD on its own (asking for it costs 2 spills)
+constexpr int kPhotoErrWaves = 5;
+// channel groups of a level unrolled together on the texture path (their tap loads are then in flight together).  Error pass:
+// fully unrolled, the FS = 32 kernel (8 groups) needs 168 VGPR + 61 spilled registers; 4 -> 150 / 0.  Linearize: all of them
+constexpr int kPhotoErrGunroll = 4;
+constexpr int kPhotoLinGunroll = 8;
+constexpr int kPhotoPrioSampling = 3; // s_setprio of the linearize kernel's sampling phase (its contraction phases run at 0)
+// pixel groups of basis rows in flight ahead of the contraction (FS = 16 and FS = 32 alike since the lockstep fills; r05 ran
+// FS = 32 with 1)
+constexpr int kPhotoAhead = 6;
 
-#ifndef SAGE_PHOTO_ERR_WAVES
-#define SAGE_PHOTO_ERR_WAVES 5 // error pass at FS = 16: 5 workgroups per CU (94 VGPRs, no spills; 4: 0.255 ms, 5: 0.246, 6 spills: 0.45);
-                               // FS = 32 lands at 102 VGPRs = 5 per SIMD on its own (asking for it costs 2 spills)
-#endif
-#ifndef SAGE_PHOTO_WAVES
-#define SAGE_PHOTO_WAVES 3 // workgroups per CU the linearize kernel is register-budgeted for (x4 waves)
-#endif
-// error pass: channel groups of a level unrolled together (their tap loads are then in flight together).  Fully unrolled,
-// the FS = 32 kernel (8 groups) needs 168 VGPR + 61 spilled registers; 4 -> 150 / 0
-#ifndef SAGE_PHOTO_ERR_GUNROLL
-#define SAGE_PHOTO_ERR_GUNROLL 4
-#endif
-#ifndef SAGE_PHOTO_PRIO_SAMPLING
-#define SAGE_PHOTO_PRIO_SAMPLING 3 // s_setprio of the linearize kernel's sampling phase (its contraction phases run at 0)
-#endif
-// r06: the next sub-tile's per-pixel inputs of phase A (location, homogeneous coordinates, depth: a chain of dependent global
-// loads, 3.3 k cycles of a wave's 36 k per sub-tile in the wave timeline) are asked for during the current sub-tile's phases
-// C / D: photometric linearize 0.622 -> 0.611 ms in the cold micro-bench (profiles/r06_kernel_ab_experiments.txt); +4 VGPRs.
-// 0 = off (A/B)
-#ifndef SAGE_PHOTO_PREFETCH_A
-#define SAGE_PHOTO_PREFETCH_A 1
-#endif
-#ifndef SAGE_PHOTO_LOCKSTEP
-// r06: the four waves of a workgroup issue every staging fill TOGETHER (one s_barrier ahead of each fill; a wave on the
-// texture path or with a dead slice executes the same number of barriers).  The waves' tiles are x-neighbours: a box row
-// of 11 texels spans 2.4 cache lines of which 1.3 also belong to the neighbour's box -- issued within a few hundred
-// cycles of each other the second request hits the CU's L1 instead of going to the L2 (which holds ~5 us of this
-// kernel's stream and never caught it).  Config 4 (FS = 32): L1 -> L2 requests 9.5e7 -> 7.7e7, memory-side fetch
-// -8 %, linearize 1.20 -> 1.105 ms, error pass 0.625 -> 0.528 ms; K = 64 (FS = 16): -1 % on all three kernels
-// (profiles/r06_kernel_ab_experiments.txt s12).  Bit mask: 1 linearize FS >= 32, 2 linearize FS = 16, 4 / 8 error pass.
-#define SAGE_PHOTO_LOCKSTEP 15
-#endif
-#ifndef SAGE_PHOTO_FS32_SLOAD
-// FS >= 32 (BASELINE config 4): r05 kept the per-lane pose loads of phase C and one group of basis prefetch there -- bound by its memory
-// side (fetch 1.58 x algorithmic), that kernel lost 4 % with the scalar loads + six groups in flight that FS = 16 runs with.  With the
-// lockstep fills (fetch 1.38 x) the order is reversed: scalar loads + six groups -1.7 % (profiles/r06_kernel_ab_experiments.txt s16).
-#define SAGE_PHOTO_FS32_SLOAD 1 // FS >= 32: poses of phase C by per-lane loads (0, r05) or scalar loads (1)
-#endif
-#ifndef SAGE_PHOTO_FS32_AHEAD
-#define SAGE_PHOTO_FS32_AHEAD 6 // FS >= 32: pixel groups of basis rows in flight ahead of the contraction (r05: 1)
-#endif
-#ifndef SAGE_PHOTO_LIN_GUNROLL
-#define SAGE_PHOTO_LIN_GUNROLL 8
-#endif
 // scripts/isa_census.py compiles this file with -DSAGE_PHASE_MARKERS: comment lines in the generated code that name the
 // phase which follows (a scheduling barrier on both sides keeps the instructions of a phase between its markers)
 #ifdef SAGE_PHASE_MARKERS
@@ -133,6 +107,18 @@ __device__ unsigned long long g_photo_trace[(size_t)kTraceMaxWg * 4 * kTraceSubs
       __builtin_amdgcn_sched_barrier(0);                                                                       \
     }                                                                                                          \
   } while (0)
+// header of a wave's trace (slot kTraceSubs - 1): where and when it ran, which work item it had
+__device__ __forceinline__ void photo_trace_header(int bid, int wave, int edge, int tile, unsigned long long t_entry)
+{
+  unsigned long long *h = g_photo_trace + (((size_t)bid * 4 + wave) * kTraceSubs + (kTraceSubs - 1)) * kTraceMarks;
+  h[0] = (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_REG_HW_ID
+  h[1] = (unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11)); // HW_REG_XCC_ID
+  h[2] = __builtin_amdgcn_s_memrealtime();
+  h[3] = __builtin_readcyclecounter();
+  h[4] = (unsigned)edge;
+  h[5] = (unsigned)tile;
+  h[6] = t_entry;
+}
 #else
 #define SAGE_TMARK(m) \
   do                  \
@@ -163,10 +149,7 @@ constexpr int kStageCapC = 64;   // texels per array, levels >= 1 together: one 
 static_assert(3 * (kStageCap0 + kStageCapC) * 16 <= 64 * kPhotoStashLD * 4, "the staging regions alias the wave's stash");
 // error pass: only feat1 is sampled -- one array, kErrStageGroups channel groups staged together (their regions side by
 // side: [group][level 0: kStageCap0 | coarse: kStageCapC] float4 = 3 KiB per group and wave)
-#ifndef SAGE_PHOTO_ERR_STAGE_GROUPS
-#define SAGE_PHOTO_ERR_STAGE_GROUPS 2
-#endif
-constexpr int kErrStageGroups = SAGE_PHOTO_ERR_STAGE_GROUPS;
+constexpr int kErrStageGroups = 2;
 constexpr int kErrStageGroupBytes = (kStageCap0 + kStageCapC) * 16;
 
 // 16-byte LDS read at a byte address of the workgroup's LDS allocation (ds_read_b128 v, vaddr offset:imm)
@@ -204,7 +187,7 @@ __device__ __forceinline__ f32x4 gload16(const float *sbase, uint32_t voff)
   return v;
 }
 // basis rows of the contraction phase: same discipline (the compiler batches tracked loads four at a time and waits for the
-// first right behind the fourth -- two pixel groups of cover; as hand-tracked loads they stay SAGE_PHOTO_AHEAD groups ahead)
+// first right behind the fourth -- two pixel groups of cover; as hand-tracked loads they stay kPhotoAhead groups ahead)
 __device__ __forceinline__ f32x2 bload8(__amdgpu_buffer_rsrc_t r, uint32_t voff)
 {
   f32x2 v;
@@ -322,17 +305,7 @@ __device__ __forceinline__ float wave_fminmax(float v)
 
 // second-level accumulators of the noise-critical tiles (the two cross tiles and the pose tile: 3 x 4 floats per lane),
 // one region per wave (see "second level" in the kernel)
-#ifndef SAGE_PHOTO_L2_TILES
-#define SAGE_PHOTO_L2_TILES 3
-#endif
-constexpr int kPhotoL2Tiles = SAGE_PHOTO_L2_TILES;
-// CS = 32: the noise-critical tiles (two cross tiles, pose tile) accumulate the even and the odd pixel groups of a sub-tile
-// in two accumulator sets -- fp32 chains of 32 instead of 64 fmaf, a quarter of the chain's rounding variance -- merged
-// before the second-level update (r03: K = 64 LM step vs the fp32 oracle 9.1 -> 7.6e-5 together with a record every 4
-// sub-tiles; same register allocation, kernel time unchanged)
-#ifndef SAGE_PHOTO_ALT_ACC
-#define SAGE_PHOTO_ALT_ACC 1
-#endif
+constexpr int kPhotoL2Tiles = 3;
 
 // One (level, channel-group) step of the sampler in the engine's channel-group layout: 4 taps x (f1, gx, gy) dwordx4
 // loads + the pre-sampled source features.
@@ -341,6 +314,150 @@ struct TapBatch
 {
   f32x4 t1[4], tx[JAC ? 4 : 1], ty[JAC ? 4 : 1], f0;
 };
+
+// Error pass with LaunchCommon::fused_geo_loss_param: the geometric error of the same edge at the warp of phase A
+// (geometric_factor_kernels.cpp:127-218) -- D1 bilinear at the level-0 coordinates (no half-pixel shift), rho = D1 - z,
+// Cauchy error log(1 + (m rho)^2 / c) for the pixels in front of the camera (`ok`)
+__device__ __forceinline__ float fused_geo_error(const float *dpt1, float p, float q, int W, int H, float m, float z, float loss,
+                                                 bool ok)
+{
+  Taps tg;
+  make_taps(tg, p, q, W, H);
+  float Ds = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    Ds += tg.w[k] * dpt1[tg.off[k]];
+  const float mr = m * (Ds - z);
+  return ok ? logf(1.0f + mr * mr / loss) : 0.f;
+}
+
+// Second level of the accumulation: the LM step's distance from the exact step is set by the fp32 accumulation chains of the
+// two cross tiles (rows c, sigma d, u6: the code gradient and the pose-code blocks) and of the pose tile; the code-code tiles
+// do not matter (measured tile by tile, DESIGN s4).  After every sub-tile each lane moves its 12 values of those tiles into a
+// wave-private LDS slot `l2` (fp32 add of 64-fmaf partial sums; no barrier, no record) and restarts their chains at zero; the
+// last sub-tile of a run adds the slot back before the record is written.
+// (r06: three wave-uniform cases with the 12 LDS reads / writes of a case issued TOGETHER -- the per-element form compiled to
+//  12 x [branch, ds_read, wait, add, branch, ds_write] in series, 1.7-2.4 k cycles per sub-tile in the wave timeline,
+//  profiles/r06_photo_wave_timeline.txt)
+template <int NT>
+__device__ __forceinline__ void second_level_update(f32x4 (&acc)[NT + 1], float *l2, bool first_of_run, bool last_of_run)
+{
+  constexpr int T0 = NT + 1 - kPhotoL2Tiles; // CS = 32: tiles 3, 4 (cross) and 5 (pose); CS = 16: every tile
+  float prev[kPhotoL2Tiles][4];
+  if (!first_of_run)
+  {
+#pragma unroll
+    for (int t = 0; t < kPhotoL2Tiles; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        prev[t][r] = l2[(t * 4 + r) * 64];
+  }
+  else
+  {
+#pragma unroll
+    for (int t = 0; t < kPhotoL2Tiles; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        prev[t][r] = 0.f;
+  }
+  if (last_of_run)
+  {
+#pragma unroll
+    for (int t = 0; t < kPhotoL2Tiles; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        acc[T0 + t][r] += prev[t][r];
+  }
+  else
+  {
+#pragma unroll
+    for (int t = 0; t < kPhotoL2Tiles; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+      {
+        l2[(t * 4 + r) * 64] = prev[t][r] + acc[T0 + t][r];
+        acc[T0 + t][r] = 0.f;
+      }
+  }
+}
+
+// MODE 0 sampler: reference layout, dword gathers through the texture path; the source features are sampled in the kernel at
+// the level-0 source coordinates (su, sv) (+0.5).  Adds the pixel's G, v, e with the level weights and focal lengths.
+template <int FS, bool JAC>
+__device__ __forceinline__ void sample_reference_layout(const PhotoParams &prm, __amdgpu_buffer_rsrc_t r_f0,
+                                                        __amdgpu_buffer_rsrc_t r_f1, __amdgpu_buffer_rsrc_t r_g1, float fx0,
+                                                        float fy0, uint32_t plane, int nlev, float su, float sv, float p, float q,
+                                                        float &G00, float &G01, float &G11, float &v0, float &v1, float &err)
+{
+  const SagePyramid &pyr = prm.pyr;
+  for (int l = 0; l < nlev; ++l)
+  {
+    const float fxl = pyr.cam[l].fx, fyl = pyr.cam[l].fy;
+    const int Wl = prm.lw[l], Hl = prm.lh[l];
+    const float rx = prm.rx[l], ry = prm.ry[l];
+    Taps ts, td;
+    if (prm.exact_coord) // (wave-uniform)
+    {
+      make_taps(ts, level_coord_exact(su, fxl, fx0), level_coord_exact(sv, fyl, fy0), Wl, Hl);
+      make_taps(td, level_coord_exact(p + 0.5f, fxl, fx0), level_coord_exact(q + 0.5f, fyl, fy0), Wl, Hl);
+    }
+    else
+    {
+      make_taps(ts, su * rx - 0.5f, sv * ry - 0.5f, Wl, Hl);
+      make_taps(td, (p + 0.5f) * rx - 0.5f, (q + 0.5f) * ry - 0.5f, Wl, Hl);
+    }
+    const uint32_t lo = (uint32_t)pyr.level_offsets[l];
+    uint32_t so[4], dof[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      so[k] = (lo + (uint32_t)ts.off[k]) * 4u;
+      dof[k] = (lo + (uint32_t)td.off[k]) * 4u;
+    }
+    float g00 = 0.f, g01 = 0.f, g11 = 0.f, a0 = 0.f, a1 = 0.f, ee = 0.f;
+#pragma unroll 4
+    for (int c = 0; c < FS; ++c)
+    {
+      const uint32_t soff = (uint32_t)c * plane;
+      float f0 = 0.f, f1 = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+      {
+        f0 += ts.w[k] * buf_load(r_f0, so[k], soff);
+        f1 += td.w[k] * buf_load(r_f1, dof[k], soff);
+      }
+      const float diff = f0 - f1;
+      ee += diff * diff;
+      if (JAC)
+      {
+        const uint32_t soff_y = (uint32_t)(FS + c) * plane;
+        float gx = 0.f, gy = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+        {
+          gx += td.w[k] * buf_load(r_g1, dof[k], soff);
+          gy += td.w[k] * buf_load(r_g1, dof[k], soff_y);
+        }
+        const float hx = fxl * gx, hy = fyl * gy;
+        g00 += hx * hx;
+        g01 += hx * hy;
+        g11 += hy * hy;
+        a0 += hx * diff;
+        a1 += hy * diff;
+      }
+    }
+    const float wl = prm.w[l];
+    err += wl * ee;
+    if (JAC)
+    {
+      G00 += wl * g00;
+      G01 += wl * g01;
+      G11 += wl * g11;
+      v0 += wl * a0;
+      v1 += wl * a1;
+    }
+  }
+}
 
 // MODE 0: reference layout [FS][P] / [2][FS][P], dword gathers, source features sampled in-kernel (per-edge operator API)
 // MODE 2: MODE 1 + the merged linearize (the geometric edge's code0 blocks ride in this kernel's contractions; linearize only)
@@ -359,15 +476,21 @@ struct TapBatch
 //   D  code blocks: f32 MFMA 16x16x4 with the basis rows loaded from global memory directly in operand layout
 //      (lane = (channel pair i, pixel k): 16 lanes x dwordx2 = one 128-byte basis row; CS = 32: operand block 0 = even
 //      channels, block 1 = odd channels)
+//   E  second level of the noise-critical tiles (second_level_update), then one partial record per `flush` sub-tiles
+//
+// Where the sub-tile loop's phases are in the text: "phase A" .. "phase E" banners below.  fused_geo_error,
+// sample_reference_layout and second_level_update are functions; the staged and the texture-path sampler of the engine
+// layout, phases C and D and the record writer are inline ON PURPOSE: the register allocation of the engine kernels is
+// tuned by hand, and each of them, moved into a function or lambda (phase D: its three macros as lambdas), compiled to
+// another instruction stream (profiles/photo_kernel_refactor_ab.txt).  Moving one is a kernel change, to be measured as one.
 template <int CS, int FS, bool JAC, int MODE>
-__global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3) : SAGE_PHOTO_WAVES) void photo_kernel(const PhotoParams prm)
+__global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? kPhotoErrWaves : 3) : kPhotoWaves) void photo_kernel(const PhotoParams prm)
 {
   constexpr bool PACKED = MODE >= 1;
   constexpr bool MERGE = JAC && MODE == 2; // engine layout + the geometric edge's code0 blocks (LaunchCommon::merge_geo_weight)
   constexpr int NB = CS / 16;
   constexpr int NG = FS / 4;
-  // channel groups of a level unrolled together (linearize: all; error pass: at most SAGE_PHOTO_ERR_GUNROLL)
-  constexpr int GUNROLL_MAX = JAC ? SAGE_PHOTO_LIN_GUNROLL : SAGE_PHOTO_ERR_GUNROLL;
+  constexpr int GUNROLL_MAX = JAC ? kPhotoLinGunroll : kPhotoErrGunroll; // texture path: channel groups unrolled together
   constexpr int GUNROLL = NG > GUNROLL_MAX ? GUNROLL_MAX : NG;
   constexpr int NT = photo_tiles(CS);
   constexpr int YY = NT; // the pose tile: accumulated like the code tiles, folded into the scalar slots at the end
@@ -468,34 +591,22 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
                        //  array nothing in the program writes or reads is not allocated)
   __syncthreads(); // s_red zeroed
 
-
 #ifdef SAGE_PHOTO_TRACE
   if constexpr (JAC && MODE == 2)
-  {
     if (bid < kTraceMaxWg && lane == 0)
-    {
-      unsigned long long *h = g_photo_trace + (((size_t)bid * 4 + wave) * kTraceSubs + (kTraceSubs - 1)) * kTraceMarks;
-      h[0] = (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_REG_HW_ID
-      h[1] = (unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11)); // HW_REG_XCC_ID
-      h[2] = __builtin_amdgcn_s_memrealtime();
-      h[3] = __builtin_readcyclecounter();
-      h[4] = (unsigned)wi.edge;
-      h[5] = (unsigned)wi.tile;
-      h[6] = t_entry_;
-    }
-  }
+      photo_trace_header(bid, wave, wi.edge, wi.tile, t_entry_);
 #endif
 
   const int nsub = min(prm.tiles_per_block, (N + kTile - 1) / kTile - wi.tile);
   const int flush = JAC ? max(1, prm.flush) : 1;
   const int rec_base = (JAC && prm.rec_first) ? uni(prm.rec_first[wi.edge]) + wi.tile / flush : bid;
   int run_pos = 0, rec_idx = 0; // sub-tiles since the last partial record, records written so far
-#if SAGE_PHOTO_PREFETCH_A
-  // next sub-tile's per-pixel inputs of phase A, asked for during the contraction phase of the current one (linearize, engine layout)
+  // r06: the next sub-tile's per-pixel inputs of phase A (location, homogeneous coordinates, depth: a chain of dependent global
+  // loads, 3.3 k cycles of a wave's 36 k per sub-tile in the wave timeline) are asked for during the current sub-tile's phases
+  // C / D (linearize, engine layout): 0.622 -> 0.611 ms in the cold micro-bench (profiles/r06_kernel_ab_experiments.txt); +4 VGPRs
   int pf_loc = 0;
   float pf_d = 1.0f, pf_hm0 = 0.f, pf_hm1 = 0.f, pf_hm2 = 1.f;
   bool pf_in = false;
-#endif
   for (int sub = 0; sub < nsub; ++sub)
   {
   // (the thread index is re-derived per sub-tile behind an opaque barrier: everything computed from it -- operand lane
@@ -514,6 +625,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
     for (int t = NT + 1 - kPhotoL2Tiles; t < NT + 1; ++t)
       acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  // ==== phase A: warp ====
   SAGE_PHASE("A_warp");
   SAGE_TMARK(0);
   const int tile = wi.tile + sub;
@@ -522,7 +634,6 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
   int my_loc;
   float d;
   float hm[3] = {0.f, 0.f, 1.f};
-#if SAGE_PHOTO_PREFETCH_A
   if (JAC && PACKED && sub > 0)
   {
     in_range = pf_in;
@@ -531,7 +642,6 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
     hm[0] = pf_hm0; hm[1] = pf_hm1; hm[2] = pf_hm2;
   }
   else
-#endif
   {
   my_loc = in_range ? load_loc(E.loc, E.loc_is_i64, n) : 0;
   // a location outside the image is dropped here (the window engine and sage_sort_locations reject it up front; the
@@ -562,18 +672,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
   const float m = mask_lookup(E.mask1, p, q, W0, H0);
   float vm = (pos && in_range) ? m : 0.0f; // sampled_valid_mask_1 (:237)
   if (fuse_geo)
-  {
-    // geometric_factor_kernels.cpp:127-218 at the same warp: D1 bilinear at the level-0 coordinates (no half-pixel
-    // shift), rho = D1 - z, Cauchy error log(1 + (m rho)^2 / c) for the pixels in front of the camera
-    Taps tg;
-    make_taps(tg, p, q, W0, H0);
-    float Ds = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      Ds += tg.w[k] * E.dpt1_geo[tg.off[k]];
-    const float mr = m * (Ds - X[2]);
-    gerr_acc += (pos && in_range) ? logf(1.0f + mr * mr / geo_loss) : 0.f;
-  }
+    gerr_acc += fused_geo_error(E.dpt1_geo, p, q, W0, H0, m, X[2], geo_loss, pos && in_range);
 
   float G00 = 0.f, G01 = 0.f, G11 = 0.f, v0 = 0.f, v1 = 0.f, err = 0.f;
   // one (level, channel group) step: bilinear interpolation of the 4 taps of feat1 (and d/dx, d/dy), difference to the
@@ -640,6 +739,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       }
     }
   };
+  // ==== phase B: sampling -> G, v, err of the pixel (engine layout: staged or texture path; MODE 0: reference layout) ====
   bool slice_live = true; // linearize, engine layout: false when no pixel of this wave's slice is an inlier
   SAGE_PHASE("B_setup");
   SAGE_TMARK(1);
@@ -648,7 +748,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
     // wave priority: a wave in its sampling phase goes ahead of the waves of its SIMD that are in their VALU / MFMA
     // phases (r03: 0.906 -> 0.879 ms)
     if (JAC)
-      __builtin_amdgcn_s_setprio(SAGE_PHOTO_PRIO_SAMPLING);
+      __builtin_amdgcn_s_setprio(kPhotoPrioSampling);
     bool staged = false;
     float pmn = 0.f, pmx = 0.f, qmn = 0.f, qmx = 0.f;
     {
@@ -702,14 +802,18 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       }
       staged = cnt0 <= kStageCap0 && cntC <= kStageCapC; // (6 x 6 + 4 x 4 + 3 x 3 = 61 coarse texels, one more row / column at an image border)
     }
-    constexpr bool LOCKSTEP = ((SAGE_PHOTO_LOCKSTEP) >> ((JAC ? 0 : 2) + (FS >= 32 ? 0 : 1))) & 1;
+    // r06, lockstep fills: the four waves of a workgroup issue every staging fill TOGETHER (one s_barrier ahead of each fill;
+    // a wave on the texture path or with a dead slice executes the same number of barriers).  The waves' tiles are
+    // x-neighbours: a box row of 11 texels spans 2.4 cache lines of which 1.3 also belong to the neighbour's box -- issued
+    // within a few hundred cycles of each other the second request hits the CU's L1 instead of going to the L2.  Config 4
+    // (FS = 32): L1 -> L2 requests 9.5e7 -> 7.7e7, linearize 1.20 -> 1.105 ms, error pass 0.625 -> 0.528 ms; K = 64
+    // (FS = 16): -1 % on all three kernels (profiles/r06_kernel_ab_experiments.txt s12)
     constexpr int NBAR = JAC ? NG : (NG + kErrStageGroups - 1) / kErrStageGroups; // staging fills per slice
     if (!slice_live)
     {
       // nothing to sample
-      if constexpr (LOCKSTEP)
-        for (int g = 0; g < NBAR; ++g)
-          __builtin_amdgcn_s_barrier();
+      for (int g = 0; g < NBAR; ++g)
+        __builtin_amdgcn_s_barrier();
     }
     else if (staged)
     {
@@ -807,8 +911,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
 #pragma unroll
       for (int l = 0; l < kStageLevels; ++l)
         f0q[l] = gload16(f0_base(l, 0), f0_vo);
-      if constexpr (LOCKSTEP)
-        __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       stage0(0u);
       stageC(0u);
       // running sums of the slice as channel PAIRS (one v_pk_fma_f32 per sum and step; the halves meet once, below)
@@ -880,8 +983,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
         {
           f0q[0] = gload16(f0_base(0, g + 1), f0_vo);
           lgkm_wait0(); // level-0 taps have been read: the region takes the next group
-          if constexpr (LOCKSTEP)
-            __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_s_barrier();
           stage0(soffn);
           vm_wait_keep<7>(f0q[1]);
         }
@@ -933,8 +1035,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       for (int g0 = 0; g0 < NG; g0 += kErrStageGroups)
       {
         lgkm_wait0(); // (the previous batch's taps / the previous sub-tile's have been read)
-        if constexpr (LOCKSTEP)
-          __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int j = 0; j < kErrStageGroups; ++j)
         {
@@ -986,9 +1087,8 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       // ================= texture-path sampler: (level, channel group) steps, the 13 dwordx4 loads of a step issued
       // together, then reduced =================
       SAGE_PHASE("B_texture_path");
-      if constexpr (LOCKSTEP)
-        for (int g = 0; g < NBAR; ++g)
-          __builtin_amdgcn_s_barrier();
+      for (int g = 0; g < NBAR; ++g)
+        __builtin_amdgcn_s_barrier();
       const f32x4 *f0s = reinterpret_cast<const f32x4 *>(E.f0s) + (in_range ? n : 0);
       for (int l = 0; l < nlev; ++l)
       {
@@ -1042,73 +1142,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       su = (float)(my_loc % W0) + 0.5f;
       sv = (float)(my_loc / W0) + 0.5f;
     }
-    for (int l = 0; l < nlev; ++l)
-    {
-      const float fxl = pyr.cam[l].fx, fyl = pyr.cam[l].fy;
-      const int Wl = prm.lw[l], Hl = prm.lh[l];
-      const float rx = prm.rx[l], ry = prm.ry[l];
-      Taps ts, td;
-      if (prm.exact_coord) // (wave-uniform)
-      {
-        make_taps(ts, level_coord_exact(su, fxl, fx0), level_coord_exact(sv, fyl, fy0), Wl, Hl);
-        make_taps(td, level_coord_exact(p + 0.5f, fxl, fx0), level_coord_exact(q + 0.5f, fyl, fy0), Wl, Hl);
-      }
-      else
-      {
-        make_taps(ts, su * rx - 0.5f, sv * ry - 0.5f, Wl, Hl);
-        make_taps(td, (p + 0.5f) * rx - 0.5f, (q + 0.5f) * ry - 0.5f, Wl, Hl);
-      }
-      const uint32_t lo = (uint32_t)pyr.level_offsets[l];
-      uint32_t so[4], dof[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-      {
-        so[k] = (lo + (uint32_t)ts.off[k]) * 4u;
-        dof[k] = (lo + (uint32_t)td.off[k]) * 4u;
-      }
-      float g00 = 0.f, g01 = 0.f, g11 = 0.f, a0 = 0.f, a1 = 0.f, ee = 0.f;
-#pragma unroll 4
-      for (int c = 0; c < FS; ++c)
-      {
-        const uint32_t soff = (uint32_t)c * plane;
-        float f0 = 0.f, f1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-          f0 += ts.w[k] * buf_load(r_f0, so[k], soff);
-          f1 += td.w[k] * buf_load(r_f1, dof[k], soff);
-        }
-        const float diff = f0 - f1;
-        ee += diff * diff;
-        if (JAC)
-        {
-          const uint32_t soff_y = (uint32_t)(FS + c) * plane;
-          float gx = 0.f, gy = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-          {
-            gx += td.w[k] * buf_load(r_g1, dof[k], soff);
-            gy += td.w[k] * buf_load(r_g1, dof[k], soff_y);
-          }
-          const float hx = fxl * gx, hy = fyl * gy;
-          g00 += hx * hx;
-          g01 += hx * hy;
-          g11 += hy * hy;
-          a0 += hx * diff;
-          a1 += hy * diff;
-        }
-      }
-      const float wl = prm.w[l];
-      err += wl * ee;
-      if (JAC)
-      {
-        G00 += wl * g00;
-        G01 += wl * g01;
-        G11 += wl * g11;
-        v0 += wl * a0;
-        v1 += wl * a1;
-      }
-    }
+    sample_reference_layout<FS, JAC>(prm, r_f0, r_f1, r_g1, fx0, fy0, plane, nlev, su, sv, p, q, G00, G01, G11, v0, v1, err);
   }
   err *= vm; // within_mask * pow(diff,2)  (:228)
   err_acc += err;
@@ -1116,11 +1150,10 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
   if (!JAC)
     continue;
 
-  // ---- per-pixel 7x7 reduced system ----
+  // ==== phase C: per-pixel 7x7 reduced system, rows -> stash ====
   SAGE_PHASE("C_rows");
   __builtin_amdgcn_s_setprio(0);
-#if SAGE_PHOTO_PREFETCH_A
-  if (PACKED && sub + 1 < nsub)
+  if (PACKED && sub + 1 < nsub) // phase A of the next sub-tile: location and homogeneous coordinates asked for
   {
     const int n2 = n + kTile;
     pf_in = n2 < N;
@@ -1128,7 +1161,6 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
     const float *hp2 = E.homo + 3 * (pf_in ? n2 : 0);
     pf_hm0 = hp2[0]; pf_hm1 = hp2[1]; pf_hm2 = hp2[2];
   }
-#endif
   if (slice_live)
   {
   const bool live = vm != 0.0f;
@@ -1148,17 +1180,7 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
     // world-from-keyframe poses, re-read per sub-tile through the scalar cache: held across the sampling phase their 24 SGPRs
     // were spilled to VGPR lanes and every use paid a v_readlane
     Pose p0, p1;
-    if constexpr (FS >= 32 && !SAGE_PHOTO_FS32_SLOAD)
-    {
-      // (r05, FS = 32 while its fetch was 1.58 x the algorithmic bytes: 4 % faster with the per-lane loads the compiler makes of this --
-      //  seven round trips in series that hold the wave back from its next burst of requests; off since the lockstep fills)
-      const float *R0p = E.R0, *R1p = E.R1;
-      asm volatile("" : "+s"(R0p), "+s"(R1p));
-      p0 = load_pose2(R0p, E.t0);
-      p1 = load_pose2(R1p, E.t1);
-    }
-    else
-      sload_pose_pair(E.R0, E.t0, E.R1, E.t1, p0, p1);
+    sload_pose_pair(E.R0, E.t0, E.R1, E.t1, p0, p1);
     // (engine layout: the homogeneous coordinates are read again and the warp of phase A recomputed -- same operations,
     //  same values -- instead of ten registers staying live across the sampling phase)
     if (PACKED)
@@ -1249,28 +1271,23 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
   __builtin_amdgcn_wave_barrier(); // same-wave LDS hand-over (in-order LDS pipe): no workgroup barrier needed
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 
-  // ---- MFMA contractions over this wave's 64 pixels, 4 pixels (K) per instruction; basis rows streamed from
-  //      global memory in operand layout, AHEAD groups in flight ----
+  // ==== phase D: MFMA contractions over this wave's 64 pixels, 4 pixels (K) per instruction; basis rows streamed from
+  //      global memory in operand layout, AHEAD groups in flight ====
   SAGE_PHASE("D_contract");
   SAGE_TMARK(4);
   {
-#if SAGE_PHOTO_ALT_ACC
-    // extra accumulator sets of the three noise-critical tiles (live in this phase only): pixel group g goes to set g mod
-    // (SAGE_PHOTO_ALT_ACC + 1), set 0 = acc
-    f32x4 accb[SAGE_PHOTO_ALT_ACC][3];
-#pragma unroll
-    for (int u = 0; u < SAGE_PHOTO_ALT_ACC; ++u)
-      accb[u][0] = accb[u][1] = accb[u][2] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
+    // CS = 32: the noise-critical tiles (two cross tiles, pose tile) accumulate the even and the odd pixel groups of a sub-tile
+    // in two accumulator sets (acc and, live in this phase only, acc_odd) -- fp32 chains of 32 instead of 64 fmaf, a quarter of
+    // the chain's rounding variance -- merged before the second-level update (r03: K = 64 LM step vs the fp32 oracle
+    // 9.1 -> 7.6e-5 together with a record every 4 sub-tiles; same register allocation, kernel time unchanged)
+    f32x4 acc_odd[3]; // cross tile 0, cross tile 1, pose tile
+    acc_odd[0] = acc_odd[1] = acc_odd[2] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int i = lane & 15, k = lane >> 4;
     // rows 9..15 of the cross operand are zero: those lanes read slot 39 of the pixel's stash row (written as 0.f); row 8
     // (slot 38) is the merged linearize's scale1-code0 row, zero otherwise
     const int ai_slot = i < 8 ? i : (i == 8 ? 38 : 39);
     const uint32_t lane_off = (uint32_t)i * (NB == 2 ? 8u : 4u);
-#ifndef SAGE_PHOTO_AHEAD
-#define SAGE_PHOTO_AHEAD 6
-#endif
-    constexpr int G = 16, AHEAD = FS >= 32 ? SAGE_PHOTO_FS32_AHEAD : SAGE_PHOTO_AHEAD;
+    constexpr int G = 16, AHEAD = kPhotoAhead;
     float bl[G], bh[G], ai[G], sg[G], ya[G], yb[G];
     f32x2 vb[G]; // the loaded pairs stay whole until their wait (a half copied out earlier would be read before it landed)
     int locp[G];
@@ -1315,20 +1332,16 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
       bl[g] = vb[g][0];
       bh[g] = NB == 2 ? vb[g][1] : 0.f;
       const float a = ai[g];
-#if SAGE_PHOTO_ALT_ACC
-      if constexpr (CS == 32 && (g % (SAGE_PHOTO_ALT_ACC + 1)) != 0)
+      if constexpr (CS == 32 && g % 2 != 0)
       {
-        constexpr int NS = SAGE_PHOTO_ALT_ACC + 1;
-        const int u = g % NS - 1;
-        accb[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[g], yb[g], accb[u][2], 0, 0, 0);
+        acc_odd[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[g], yb[g], acc_odd[2], 0, 0, 0);
         acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(sg[g] * bl[g], bl[g], acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(sg[g] * bl[g], bh[g], acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(sg[g] * bh[g], bh[g], acc[2], 0, 0, 0);
-        accb[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bl[g], accb[u][0], 0, 0, 0);
-        accb[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bh[g], accb[u][1], 0, 0, 0);
+        acc_odd[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bl[g], acc_odd[0], 0, 0, 0);
+        acc_odd[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bh[g], acc_odd[1], 0, 0, 0);
         return;
       }
-#endif
       acc[YY] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[g], yb[g], acc[YY], 0, 0, 0);
       if constexpr (CS == 32)
       {
@@ -1344,88 +1357,27 @@ __global__ __launch_bounds__(kBlock, !JAC ? (FS == 16 ? SAGE_PHOTO_ERR_WAVES : 3
         acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bl[g], acc[1], 0, 0, 0);
       }
     });
-#if SAGE_PHOTO_ALT_ACC
     if (CS == 32)
     {
-      // pairwise merge of the sets
-#if SAGE_PHOTO_ALT_ACC == 3
-      acc[3] = (acc[3] + accb[0][0]) + (accb[1][0] + accb[2][0]);
-      acc[4] = (acc[4] + accb[0][1]) + (accb[1][1] + accb[2][1]);
-      acc[YY] = (acc[YY] + accb[0][2]) + (accb[1][2] + accb[2][2]);
-#else
-#pragma unroll
-      for (int u = 0; u < SAGE_PHOTO_ALT_ACC; ++u)
-      {
-        acc[3] += accb[u][0]; acc[4] += accb[u][1]; acc[YY] += accb[u][2];
-      }
-#endif
+      acc[3] += acc_odd[0]; acc[4] += acc_odd[1]; acc[YY] += acc_odd[2];
     }
-#endif
   }
   __builtin_amdgcn_wave_barrier(); // the stash is rewritten by the next sub-tile
   SAGE_PHASE("E_second_level_flush");
   SAGE_TMARK(5);
   } // slice_live
-#if SAGE_PHOTO_PREFETCH_A
-  if (PACKED && sub + 1 < nsub)
+  if (PACKED && sub + 1 < nsub) // ... and, the location having landed, its depth
   {
     pf_in = pf_in && (unsigned)pf_loc < (unsigned)(W0 * H0);
     pf_loc = pf_in ? pf_loc : 0;
     pf_d = pf_in ? E.dpt0[pf_loc] : 1.0f;
     pf_hm0 = pf_in ? pf_hm0 : 0.f; pf_hm1 = pf_in ? pf_hm1 : 0.f; pf_hm2 = pf_in ? pf_hm2 : 1.f;
   }
-#endif
-  // ---- second level: the LM step's distance from the exact step is set by the fp32 accumulation chains of the two
-  //      cross tiles (rows c, sigma d, u6: the code gradient and the pose-code blocks) and of the pose tile; the code-code
-  //      tiles do not matter (measured tile by tile, DESIGN s4).  After every sub-tile each lane moves its 12 values of
-  //      those tiles into a wave-private LDS slot (fp32 add of 64-fmaf partial sums; no barrier, no record) and restarts
-  //      their chains at zero; the last sub-tile of the run adds the slot back before the record is written. ----
-  // (r06: written as three wave-uniform cases with the 12 LDS reads / writes of a case issued TOGETHER -- the per-element
-  //  form compiled to 12 x [branch, ds_read, wait, add, branch, ds_write] in series, 1.7-2.4 k cycles per sub-tile in the wave
-  //  timeline (profiles/r06_photo_wave_timeline.txt); `run_pos` counts the sub-tiles since the last record: no `sub % flush`)
+  // ==== phase E: second level of the noise-critical tiles (`run_pos` counts the sub-tiles since the last record: no `sub % flush`) ====
   const bool last_of_run = sub + 1 == nsub || run_pos + 1 == flush;
   const bool first_of_run = run_pos == 0;
   if (nsub > 1 && !(first_of_run && last_of_run))
-  {
-    float *l2 = s_l2 + wave * (kPhotoL2Tiles * 256) + lane;
-    constexpr int T0 = NT + 1 - kPhotoL2Tiles; // CS = 32: tiles 3, 4 (cross) and 5 (pose); CS = 16: every tile
-    float prev[kPhotoL2Tiles][4];
-    if (!first_of_run)
-    {
-#pragma unroll
-      for (int t = 0; t < kPhotoL2Tiles; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          prev[t][r] = l2[(t * 4 + r) * 64];
-    }
-    else
-    {
-#pragma unroll
-      for (int t = 0; t < kPhotoL2Tiles; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          prev[t][r] = 0.f;
-    }
-    if (last_of_run)
-    {
-#pragma unroll
-      for (int t = 0; t < kPhotoL2Tiles; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          acc[T0 + t][r] += prev[t][r];
-    }
-    else
-    {
-#pragma unroll
-      for (int t = 0; t < kPhotoL2Tiles; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-        {
-          l2[(t * 4 + r) * 64] = prev[t][r] + acc[T0 + t][r];
-          acc[T0 + t][r] = 0.f;
-        }
-    }
-  }
+    second_level_update<NT>(acc, s_l2 + wave * (kPhotoL2Tiles * 256) + lane, first_of_run, last_of_run);
   // ---- flush: one partial record per `flush` sub-tiles.  The fp32 accumulation chains (64 fmaf per sub-tile and
   //      accumulator) are what the LM step's distance from the exact step grows with (DESIGN s4); the workgroup keeps
   //      walking its run of sub-tiles (pose / descriptor prologue amortised, vertically adjacent bands stay in its L1/L2)
@@ -1685,34 +1637,38 @@ static hipError_t photo_err_impl(hipStream_t s, const PhotoEdge *single, const P
   return launch_stats_finalize(s, lc, stats, 10.0f * wsum, 1.0f);
 }
 
+// the compiled (CS, FS) pairs: f(integral_constant CS, integral_constant FS) of the one asked for
+template <class F>
+static hipError_t dispatch_cs_fs(int CS, int FS, F &&f)
+{
+  using std::integral_constant;
+  if (CS == 32 && FS == 16)
+    return f(integral_constant<int, 32>{}, integral_constant<int, 16>{});
+  if (CS == 16 && FS == 16)
+    return f(integral_constant<int, 16>{}, integral_constant<int, 16>{});
+  if (CS == 32 && FS == 32)
+    return f(integral_constant<int, 32>{}, integral_constant<int, 32>{});
+  if (CS == 16 && FS == 32)
+    return f(integral_constant<int, 16>{}, integral_constant<int, 32>{});
+  return hipErrorInvalidValue;
+}
+
 hipError_t launch_photo_linearize(hipStream_t s, int CS, int FS, const PhotoEdge *single, const PhotoEdge *table,
                                   const LaunchCommon &lc, const SagePyramid &pyr, const float *weights_host,
                                   float eps, const EdgeOut &out)
 {
-  if (CS == 32 && FS == 16)
-    return photo_lin_impl<32, 16>(s, single, table, lc, pyr, weights_host, eps, out);
-  if (CS == 16 && FS == 16)
-    return photo_lin_impl<16, 16>(s, single, table, lc, pyr, weights_host, eps, out);
-  if (CS == 32 && FS == 32)
-    return photo_lin_impl<32, 32>(s, single, table, lc, pyr, weights_host, eps, out);
-  if (CS == 16 && FS == 32)
-    return photo_lin_impl<16, 32>(s, single, table, lc, pyr, weights_host, eps, out);
-  return hipErrorInvalidValue;
+  return dispatch_cs_fs(CS, FS, [&](auto cs, auto fs) {
+    return photo_lin_impl<decltype(cs)::value, decltype(fs)::value>(s, single, table, lc, pyr, weights_host, eps, out);
+  });
 }
 
 hipError_t launch_photo_error(hipStream_t s, int CS, int FS, const PhotoEdge *single, const PhotoEdge *table,
                               const LaunchCommon &lc, const SagePyramid &pyr, const float *weights_host,
                               float eps, float *stats)
 {
-  if (CS == 32 && FS == 16)
-    return photo_err_impl<32, 16>(s, single, table, lc, pyr, weights_host, eps, stats);
-  if (CS == 16 && FS == 16)
-    return photo_err_impl<16, 16>(s, single, table, lc, pyr, weights_host, eps, stats);
-  if (CS == 32 && FS == 32)
-    return photo_err_impl<32, 32>(s, single, table, lc, pyr, weights_host, eps, stats);
-  if (CS == 16 && FS == 32)
-    return photo_err_impl<16, 32>(s, single, table, lc, pyr, weights_host, eps, stats);
-  return hipErrorInvalidValue;
+  return dispatch_cs_fs(CS, FS, [&](auto cs, auto fs) {
+    return photo_err_impl<decltype(cs)::value, decltype(fs)::value>(s, single, table, lc, pyr, weights_host, eps, stats);
+  });
 }
 
 } // namespace sage

@@ -61,6 +61,12 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, uint32_t vo
   return __builtin_bit_cast(f32x4, v);
 }
 
+// sample n's pixel location (index into the level-0 image) from an int32 or int64 location array
+__device__ __forceinline__ int load_loc(const void *loc, int is64, int n)
+{
+  return is64 ? (int)reinterpret_cast<const long long *>(loc)[n] : reinterpret_cast<const int *>(loc)[n];
+}
+
 // ---------------------------------------------------------------- wave64 sum (DPP)
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ float dpp_add(float v)

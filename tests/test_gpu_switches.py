@@ -142,7 +142,7 @@ def test_border_taps_with_full_mask_match_oracle(tmp_path, orc, H, W, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# r06: the four waves of a photometric workgroup meet at one s_barrier per staging fill (photo_kernels.hip, SAGE_PHOTO_LOCKSTEP).
+# r06: the four waves of a photometric workgroup meet at one s_barrier per staging fill (photo_kernels.hip, "lockstep fills").
 # A wave whose footprint does not fit the staging regions samples through the texture path, a wave without inliers skips
 # the sampling altogether -- both must still execute the SAME NUMBER of barriers as their staged neighbours, or the
 # workgroup hangs (or, worse, pairs up barriers of different fills).  Here keyframes 1 and 3 are pushed towards the scene:
