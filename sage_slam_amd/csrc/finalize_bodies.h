@@ -1,6 +1,6 @@
 // finalize_bodies.h -- per-edge finalize of the two dense factor types as device functions: the stand-alone finalize
 // kernels (photo_kernels.hip / geo_kernels.hip: drop-in operators, factor cache) and the window's one-launch
-// finalize + assembly (window.hip) share them.  One workgroup per edge; `s` is the workgroup's LDS scratch.
+// finalize + assembly (window_eval.hip) share them.  One workgroup per edge; `s` is the workgroup's LDS scratch.
 #pragma once
 #include "sage_internal.h"
 

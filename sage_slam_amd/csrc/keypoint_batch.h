@@ -1,6 +1,6 @@
 // keypoint_batch.h -- what the host units see of the matched-keypoint factors (keypoint_kernels.hip): system sizes and
 // scratch layout, the parameter / output structs and launches of the per-edge operators (operators.hip), and the device
-// table row and launch of a window's terms (sage_window_add_keypoint_term; window.hip).
+// table row and launch of a window's terms (sage_window_add_keypoint_term; window_eval.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,11 @@
 // runtime_internal.h -- shared by the host-runtime translation units behind the C ABI (include/sage_ba.h):
 //   operators.hip       workspaces, the per-edge operator API (df::*_calculate mirrors), the producer entry points
 //   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame)
-//   window.hip          the batched window engine on a finalized window: linearize / error / solve / LM iteration
+//   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
+//   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
+//   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
+//   window_solve.hip    from a system to a candidate: priors, damped solve, separator solve, accept / reset / variable exchange
+//   window_lm.hip       the LM iteration: one policy around three sequences (classic, schur, at_candidate)
 //   window_profile.hip  optional kernel timing of a window: event pool, per-kernel event pairs, phase marks
 //   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
@@ -348,11 +352,29 @@ static int upload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
     SAGE_HIP(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
   return 0;
 }
+// window.hip
 int window_upload_vars(SageWindow *w, int set);
 int window_local_edge(const SageWindow *w, int global_edge); // local index of directed edge 2 * link + dir, or -1
 std::vector<int32_t> window_link_pairs(const SageWindow *w);  // [nlinks][2]: the links as the host solvers take them
+// window_eval.hip
 int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false);
+int window_error_pass(SageWindow *w, int which, bool speculate_gradients);
+// window_reduce.hip
+int window_collective(SageWindow *w, double *buf, size_t n);                 // the hook's sum in place, nothing else
+int window_allreduce(SageWindow *w, double *buf, size_t n, int iterate);     // ... + the emulated peers' share at `iterate`
+int window_allreduce_into(SageWindow *w, const double *send, double *recv, size_t n, int iterate); // the same out of place
+int window_mirror_totals(SageWindow *w, bool with_err, const double *system = nullptr); // enqueue totals + tickets -> mirror
+bool window_wait_error_totals(SageWindow *w);   // spin on the last error pass's tickets; false: none to come / timed out
+bool window_wait_reduced_totals(SageWindow *w); // ... on the last window_mirror_totals'
+int window_wait_mirror(SageWindow *w, bool *not_psd); // the reduced totals and the candidate, a synchronise only on a time-out
+double mirrored_error(const SageWindow *w, int at, int set); // mirror.h[at] + mirror.h[at + 1] + the priors at `set`
+int window_total_error(SageWindow *w, int from_linearize, double *err, bool stream_idle);
+int window_copy_floats(SageWindow *w, const float *src, float *dst, int n); // one-launch device copy on the window's stream
+void window_add_to_double(SageWindow *w, double *p, double v);              // p[0] += v on the window's stream
+// window_solve.hip
+double window_prior_error(const SageWindow *w, int set, bool owned_only = false);
 int window_sync_candidate(SageWindow *w, bool stream_idle = false);
+int window_schur_solve(SageWindow *w, double damp, double *lin_error);
 // window_profile.hip
 void prof_attach(SageWindow *w, int which, LaunchCommon &lc); // profiling: an event pair for kernel `which` (LaunchCommon::ev_*)
 void window_phase_mark(SageWindow *w, int which); // profiling: record phase mark `which` on the window's stream

@@ -1,6 +1,6 @@
 // window_build.hip -- the build-time half of the window engine: create / destroy, keyframes, links and keypoint terms as they are
 // added, sage_window_finalize as a list of stages (its policy: window_plan.h), the photometric run plan and its tuning.  Host
-// code only: kernels are reached through the launch_* wrappers; what iterates on a finalized window is window.hip.
+// code only: kernels are reached through the launch_* wrappers; what runs on a finalized window is window_eval / _reduce / _solve / _lm.hip.
 #include "runtime_internal.h"
 #include "window_plan.h"
 

@@ -87,6 +87,31 @@ struct TotalsMirror
     if (h)
       (void)hipHostFree(h);
   }
+  // spin until the four tickets of `ticket_group` (kErrorTickets / kMirrorTickets) show `epoch`: what their kernel wrote before
+  // them is in h then, and everything enqueued ahead of that kernel has landed.  Instead of a stream synchronise: a host
+  // thread blocked there for more than a few dozen microseconds wakes up through an interrupt, 20-30 us after the kernel
+  // has finished -- on the LM iteration's critical path.  false: timed out (the caller synchronises the stream)
+  bool wait(int ticket_group, uint64_t epoch) const
+  {
+    const double *t = h + ticket_group;
+    const double want = (double)epoch;
+    auto ticket = [t](int i) {
+      double v;
+      __atomic_load(t + i, &v, __ATOMIC_ACQUIRE); // (a plain load on x86; the device is the writer)
+      return v;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (!(ticket(0) == want && ticket(1) == want && ticket(2) == want && ticket(3) == want))
+    {
+      __builtin_ia32_pause();
+      if ((++spins & 0x3ff) == 0 &&
+          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
+        return false;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return true;
+  }
 };
 
 // ---- sharded windows ----

@@ -216,10 +216,13 @@ def test_collectives_of_each_lm_sequence(dec, inner):
 # r05: peer emulation (sage_window_emulate_peers; bench.py's shard_emulation): ONE rank of a 3-rank job on one device, a
 # one-rank RCCL communicator on its stream, the other ranks' share of every reduced system from a table that was computed
 # beforehand at the iterates of the job's own trajectory -- the rank must walk the single-rank window's trajectory
-# (same accept / reject decisions, errors and iterates to the reduction's rounding)
+# (same accept / reject decisions, errors and iterates to the reduction's rounding).  hook "callback": the same behind an
+# in-place hook (sage_window_set_allreduce; the sum over one rank leaves the buffer as it is) -- the engine then copies its
+# share next to the system before the sum, and adds the peers' share behind it
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rank", [0, 2])
-def test_emulated_peers_walk_the_real_trajectory(rank):
+@pytest.mark.parametrize("rank,hook", [pytest.param(0, "rccl", id="0"), pytest.param(2, "rccl", id="2"),
+                                       pytest.param(0, "callback", id="0-callback")])
+def test_emulated_peers_walk_the_real_trajectory(rank, hook):
     import torch
     from sage_slam_amd import capi
     w = _make()
@@ -239,7 +242,7 @@ def test_emulated_peers_walk_the_real_trajectory(rank):
             ref.append((st.error, st.candidate_error, int(st.accepted), st.damp))
     v_ref = _all_vars(full, K)
     full.close()
-    comm = capi.rccl_comm_create(capi.rccl_unique_id(), 0, 1)
+    comm = capi.rccl_comm_create(capi.rccl_unique_id(), 0, 1) if hook == "rccl" else None
     sh = capi.Window(w, rank=rank, world=world)
     rest = torch.empty(steps + 1, sh.packed_count, dtype=torch.float64, device="cuda")
     for i in range(steps + 1):
@@ -249,13 +252,18 @@ def test_emulated_peers_walk_the_real_trajectory(rank):
         torch.cuda.synchronize()
         rest[i] = table[i] - sh.packed_tensor()
     sh.reset()
-    sh.use_rccl(comm)
+    rec = None if hook == "rccl" else _Recorder()
+    if rec is None:
+        sh.use_rccl(comm)
+    else:
+        sh.set_allreduce(rec)
     sh.emulate_peers(rest)
-    got = _run(sh, capi, steps, at_candidate=None)            # automatic: the one-collective sequence of a reduced window
+    got = _run(sh, capi, steps, at_candidate=None, rec=rec)   # automatic: the one-collective sequence of a reduced window
     ref = np.array(ref)
     assert np.array_equal(got[:, 2], ref[:, 2]) and np.array_equal(got[:, 3], ref[:, 3])
     np.testing.assert_allclose(got[:, :2], ref[:, :2], rtol=2e-6)
     v = _all_vars(sh, K)
     assert np.abs(v - v_ref).max() < 2e-5 * max(1.0, np.abs(v_ref).max())
     sh.close()
-    capi.rccl_comm_destroy(comm)
+    if comm is not None:
+        capi.rccl_comm_destroy(comm)
