@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "block_solver.h"
+#include "damped_system.h"
 #include "host_math.h" // env_flag
 #include "sage_ba.h"
 
@@ -1487,7 +1488,7 @@ bool block_plan_has_arrow_rows(const BlockEnvelope &E)
   return reach > 64; // (a plain split window: <= 2 x 3 blocks per separator row)
 }
 
-int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool allow_split, BlockPlan &out)
+int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool may_split, BlockPlan &out)
 {
   std::vector<int32_t> &perm = out.perm, &pos = out.pos, &row_first = out.row_first, &row_off = out.row_off,
                        &a_first = out.a_first, &a_cnt = out.a_cnt, &a_off = out.a_off, &blk_row = out.blk_row,
@@ -1505,7 +1506,7 @@ int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool allow
   for (auto &l : links)
     if (l.first < 0 || l.second <= l.first || l.second >= K)
       return SAGE_E_INVALID;
-  if (allow_split && K >= 16)
+  if (may_split && K >= 16)
   {
     // the helper's half runs a little slower than the caller's (it wakes from sleep for every solve): give it
     // `bias` rows less
@@ -1816,38 +1817,29 @@ extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const i
   if (rcp != SAGE_OK)
     return rcp;
   const int nblk = bp.nblk;
+  // per keyframe, then per link: a link listed twice accumulates (damped_system.h has the element rules)
   std::vector<double> T((size_t)nblk * BBp, 0.0), X((size_t)K * BBp), y((size_t)K * Bp, 0.0);
   for (int q = 0; q < K; ++q)
   {
     const int k = bp.perm[q];
     double *D = T.data() + (size_t)bp.index(q, q) * BBp;
-    for (int i = 0; i < Bp; ++i)
-      for (int j = 0; j < Bp; ++j)
-      {
-        double v = 0.0;
-        if (i < B && j < B)
-        {
-          v = 0.5 * (diag[(size_t)k * BB + i * B + j] + diag[(size_t)k * BB + j * B + i]);
-          if (i == j)
-            v = (v + (diag_add ? diag_add[k * B + i] : 0.0)) * (1.0 + damp);
-        }
-        else if (i == j)
-          v = 1.0 + damp;
-        D[i * Bp + j] = v;
-      }
-    for (int i = 0; i < B; ++i)
-      y[(size_t)q * Bp + i] = g[(size_t)k * B + i] + (g_add ? g_add[k * B + i] : 0.0);
+    for (int r = 0; r < Bp; ++r)
+      for (int c = 0; c < Bp; ++c)
+        D[sage::stored_slot(r, c, Bp)] =
+            (r < B && c < B) ? sage::damped_diag_elem(diag + (size_t)k * BB, B, r, c, diag_add ? diag_add[k * B + r] : 0.0, damp)
+                             : sage::damped_pad_elem(r, c, damp);
+    for (int r = 0; r < B; ++r)
+      y[(size_t)q * Bp + r] = sage::damped_rhs_elem(g[(size_t)k * B + r], g_add ? g_add[k * B + r] : 0.0);
   }
   for (int l = 0; l < nlinks; ++l)
   {
     const int a = links[2 * l], b = links[2 * l + 1];
     const int qi = std::max(bp.pos[a], bp.pos[b]), qj = std::min(bp.pos[a], bp.pos[b]);
-    // stored block is [c in column keyframe][r in row keyframe]; the packed link block is [r in a][c in b]
     double *D = T.data() + (size_t)bp.index(qi, qj) * BBp;
     const bool row_is_a = bp.perm[qi] == a;
-    for (int i = 0; i < B; ++i)
-      for (int j = 0; j < B; ++j)
-        D[row_is_a ? j * Bp + i : i * Bp + j] += lnk[(size_t)l * BB + i * B + j];
+    for (int r = 0; r < B; ++r)
+      for (int c = 0; c < B; ++c)
+        D[sage::stored_slot(r, c, Bp)] += lnk[(size_t)l * BB + sage::link_elem(row_is_a, r, c, B)];
   }
   static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
   const auto t0 = std::chrono::steady_clock::now();

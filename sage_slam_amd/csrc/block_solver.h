@@ -127,7 +127,7 @@ struct BlockPlan
     return j < row_first[i] ? a_off[i] + j - a_first[i] : row_off[i] + j - row_first[i];
   }
 };
-int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool allow_split, BlockPlan &out);
+int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool may_split, BlockPlan &out);
 // the envelope of a plan's storage with Bp-padded blocks: K, Bp, the five range tables, n1 / n2 and the column lists.
 // The caller adds what is its own (ready / epoch / fill / no_lookahead); the plan must outlive the envelope.
 BlockEnvelope envelope_of(const BlockPlan &plan, int Bp);

@@ -1,0 +1,147 @@
+// damped_system.h -- the window's damped normal equations, its priors and its retraction, each written once for the
+// device kernels (solve_kernels.hip) and the host code that mirrors them (window_solve.hip, block_solver.cpp,
+// shard_solve.cpp, host_math.cpp).  Plain C++17, no HIP include: hipcc reads SAGE_HD as __host__ __device__, the host
+// compiler as nothing.
+//
+//   A = H + P + damp * diag(H + P)     H: packed [K diag blocks | link blocks | gradient] (double), P: diagonal priors
+//
+// The three builders of A's block storage keep their own iteration (per block on the device, per keyframe and per link
+// with accumulation of duplicate links in sage_block_solve, local positions and ownership of priors in the shard); what
+// an element is and where it goes is decided here.
+#pragma once
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define SAGE_HD __host__ __device__
+#else
+#define SAGE_HD
+#endif
+
+namespace sage
+{
+
+// ---- pose algebra (poses are 12 floats: R row-major, then t) ----
+
+// gtsam_traits.h:78-89 : [t1 - R1 R0^T t0, log(R1 R0^T)]
+SAGE_HD inline void pose_local(const float *origin, const float *other, double out[6])
+{
+  double Rr[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      Rr[i * 3 + j] = (double)other[i * 3 + 0] * origin[j * 3 + 0] + (double)other[i * 3 + 1] * origin[j * 3 + 1] +
+                      (double)other[i * 3 + 2] * origin[j * 3 + 2];
+  for (int i = 0; i < 3; ++i)
+    out[i] = other[9 + i] - (Rr[i * 3 + 0] * origin[9] + Rr[i * 3 + 1] * origin[10] + Rr[i * 3 + 2] * origin[11]);
+  const double tr = Rr[0] + Rr[4] + Rr[8];
+  const double cs = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0)));
+  const double th = acos(cs);
+  const double k = th < 1e-8 ? 0.5 : th / (2.0 * sin(th));
+  out[3] = k * (Rr[7] - Rr[5]);
+  out[4] = k * (Rr[2] - Rr[6]);
+  out[5] = k * (Rr[3] - Rr[1]);
+}
+
+// mapping_utils.h:316-346 (fp32)
+SAGE_HD inline void se3_exp(const float *omega, const float *v, float *R, float *t)
+{
+  float theta = sqrtf(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
+  float n[3] = {1.f, 0.f, 0.f}; // "a casual rotation direction vector" when theta == 0
+  if (theta > 0)
+  {
+    n[0] = omega[0] / theta;
+    n[1] = omega[1] / theta;
+    n[2] = omega[2] / theta;
+  }
+  theta = fmaxf(theta, 1.0e-14f);
+  const float s = sinf(theta), c = cosf(theta);
+  const float K[3][3] = {{0, -n[2], n[1]}, {n[2], 0, -n[0]}, {-n[1], n[0], 0}};
+  float K2[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      K2[i][j] = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
+  const float a = (1.0f - c) / theta, b = (theta - s) / theta;
+  for (int i = 0; i < 3; ++i)
+  {
+    float acc = 0.f;
+    for (int j = 0; j < 3; ++j)
+    {
+      const float id = (i == j) ? 1.f : 0.f;
+      R[i * 3 + j] = id + s * K[i][j] + (1.0f - c) * K2[i][j];
+      acc += (id + a * K[i][j] + b * K2[i][j]) * v[j];
+    }
+    t[i] = acc;
+  }
+}
+
+// gtsam_traits.h:45-70, camera_tracker.cpp:491-512 : out = exp(d) * pose, d = [v, omega] (left update); out != pose
+SAGE_HD inline void pose_retract(const float *pose, const float *d, float *out)
+{
+  float dR[9], dt[3];
+  se3_exp(d + 3, d, dR, dt);
+  for (int i = 0; i < 3; ++i)
+  {
+    for (int j = 0; j < 3; ++j)
+      out[i * 3 + j] = dR[i * 3 + 0] * pose[0 * 3 + j] + dR[i * 3 + 1] * pose[1 * 3 + j] + dR[i * 3 + 2] * pose[2 * 3 + j];
+    out[9 + i] = dR[i * 3 + 0] * pose[9] + dR[i * 3 + 1] * pose[10] + dR[i * 3 + 2] * pose[11] + dt[i];
+  }
+}
+
+// ---- priors (a9): code prior on every keyframe (zero prior mean), scale / pose priors on keyframe 0 ----
+struct SolvePriors
+{
+  double code_w, scale_w, pose_w;
+  float scale_init0;
+  float pose_init0[12];
+};
+
+// what the priors add to row r of keyframe kf (rows: pose 6, code CS, scale), given that keyframe's current variables:
+// da on the diagonal of H, ga on the gradient
+SAGE_HD inline void prior_row(const SolvePriors &pri, int kf, int r, int CS, const float *pose, float scale,
+                              const float *code, double &da, double &ga)
+{
+  da = 0.0;
+  ga = 0.0;
+  if (r >= 6 && r < 6 + CS)
+  {
+    da = pri.code_w;
+    ga = pri.code_w * (0.0 - (double)code[r - 6]);
+  }
+  if (kf == 0 && r == 6 + CS && pri.scale_w > 0)
+  {
+    const double s = (double)scale;
+    da = pri.scale_w / (s * s);
+    ga = pri.scale_w / s * (log((double)pri.scale_init0) - log(s));
+  }
+  if (kf == 0 && r < 6 && pri.pose_w > 0)
+  {
+    double loc[6];
+    pose_local(pose, pri.pose_init0, loc);
+    da = pri.pose_w;
+    ga = pri.pose_w * loc[r];
+  }
+}
+
+// ---- element rules of the damped system ----
+
+// element (r, c) of a keyframe's diagonal block: symmetrised, the prior and the LM damping H + damp*diag(H)
+// (camera_tracker.cpp:1182) on the diagonal
+SAGE_HD inline double damped_diag_elem(const double *D, int B, int r, int c, double prior, double damp)
+{
+  double v = 0.5 * (D[r * B + c] + D[c * B + r]);
+  if (r == c)
+    v = (v + prior) * (1.0 + damp);
+  return v;
+}
+
+// the blocks are padded from B to Bp rows with a (damped) identity: delta 0 on the padding rows
+SAGE_HD inline double damped_pad_elem(int r, int c, double damp) { return r == c ? 1.0 + damp : 0.0; }
+
+SAGE_HD inline double damped_rhs_elem(double g, double g_prior) { return g + g_prior; }
+
+// Blocks are stored transposed: element (r in the row keyframe, c in the column keyframe) at [c][r].
+SAGE_HD inline int stored_slot(int r, int c, int Bp) { return c * Bp + r; }
+
+// ... and comes from this element of the packed link block (a, b), a < b, which is [row in a][column in b]
+SAGE_HD inline int link_elem(bool row_is_a, int r, int c, int B) { return row_is_a ? r * B + c : c * B + r; }
+
+} // namespace sage

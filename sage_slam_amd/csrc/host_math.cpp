@@ -17,6 +17,7 @@
 #include <random>
 #include <vector>
 
+#include "damped_system.h"
 #include "host_math.h"
 #include "sage_ba.h"
 
@@ -92,50 +93,16 @@ extern "C" void sage_se3_exp(const float *omega, const float *v, float *R, float
 {
   if (!omega || !v || !R || !t) // (void helpers: a null argument is a no-op, never a fault)
     return;
-  float theta = std::sqrt(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
-  float n[3] = {1.f, 0.f, 0.f}; // "a casual rotation direction vector" when theta == 0
-  if (theta > 0)
-  {
-    n[0] = omega[0] / theta;
-    n[1] = omega[1] / theta;
-    n[2] = omega[2] / theta;
-  }
-  theta = std::max(theta, 1.0e-14f);
-  const float s = std::sin(theta), c = std::cos(theta);
-  const float K[3][3] = {{0, -n[2], n[1]}, {n[2], 0, -n[0]}, {-n[1], n[0], 0}};
-  float K2[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)
-      K2[i][j] = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
-  const float a = (1.0f - c) / theta, b = (theta - s) / theta;
-  for (int i = 0; i < 3; ++i)
-  {
-    float acc = 0.f;
-    for (int j = 0; j < 3; ++j)
-    {
-      const float id = (i == j) ? 1.f : 0.f;
-      R[i * 3 + j] = id + s * K[i][j] + (1.0f - c) * K2[i][j];
-      acc += (id + a * K[i][j] + b * K2[i][j]) * v[j];
-    }
-    t[i] = acc;
-  }
+  sage::se3_exp(omega, v, R, t);
 }
 
 extern "C" void sage_pose_retract(const float *pose, const float *d, float *out)
 {
   if (!pose || !d || !out)
     return;
-  float dR[9], dt[3];
-  sage_se3_exp(d + 3, d, dR, dt); // delta = [v, omega]
-  float R[9], t[3];
-  for (int i = 0; i < 3; ++i)
-  {
-    for (int j = 0; j < 3; ++j)
-      R[i * 3 + j] = dR[i * 3 + 0] * pose[0 * 3 + j] + dR[i * 3 + 1] * pose[1 * 3 + j] + dR[i * 3 + 2] * pose[2 * 3 + j];
-    t[i] = dR[i * 3 + 0] * pose[9] + dR[i * 3 + 1] * pose[10] + dR[i * 3 + 2] * pose[11] + dt[i];
-  }
-  std::memcpy(out, R, sizeof(R));
-  std::memcpy(out + 9, t, sizeof(t));
+  float o[12]; // (out may be pose)
+  sage::pose_retract(pose, d, o); // delta = [v, omega]
+  std::memcpy(out, o, sizeof(o));
 }
 
 // ---------------------------------------------------------------- dense helpers (double)

@@ -268,14 +268,17 @@ hipError_t launch_gaussian_pyramid_with_grad(hipStream_t s, float *pyr, float *g
                                              const float *mask, const SagePyramid &p, int FS, float *scratch_mask);
 
 
-// ---- device solver of the window's damped normal equations (solve_kernels.hip) ----
+// ---- hybrid solve of the window's damped normal equations (solve_kernels.hip): device scatter, host factorisation,
+// device retract ----
 struct DeviceSolver;
-// SAGE_E_UNSUPPORTED when the block envelope is wider than the LDS panel (the caller keeps the host solver)
+struct SolvePriors; // damped_system.h
+// SAGE_E_UNSUPPORTED when the block solver has no kernels for B (padded_block) or the links hold a duplicate (the caller
+// keeps the host solver, which accumulates duplicate links)
 int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
-                  hipStream_t stream, bool allow_split = true);
+                  hipStream_t stream);
 void solver_destroy(DeviceSolver *S);
 int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, const float *vars0, float *vars1, int CS,
-               double damp, double code_w, double scale_w, double pose_w, float scale_init0, const float *pose_init0);
+               double damp, const SolvePriors &pri);
 // valid after the stream has been synchronised
 const float *solver_host_vars(const DeviceSolver *S);
 const double *solver_host_delta(const DeviceSolver *S);

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "block_solver.h"
+#include "damped_system.h"
 #include "host_math.h"
 #include "sage_ba.h"
 
@@ -320,38 +321,17 @@ extern "C" int sage_shard_keyframe_is_local(const SageShardPlan *p, int kf)
   return s >= 0 && std::find(p->sep_local.begin(), p->sep_local.end(), s) != p->sep_local.end();
 }
 
-// this rank's damped contribution: element (r, c) of block (kr, kc) of  A^(r) = H^(r) + P^(r) + damp * diag(...)
+// what is specific to a rank's contribution  A^(r) = H^(r) + P^(r) + damp * diag(...)  (elements: damped_system.h): a
+// keyframe's prior is added by its owner only; a separator's diagonal block and right-hand side come from every rank that
+// touches it (rank mode: its packed buffer only holds its own edge sums) or, when the buffer is the complete assembled
+// system, from domain 0 alone
 namespace
 {
 struct LocalSystem
 {
   const SageShardPlan &p;
-  const double *diag, *lnk, *g;
-  const double *dadd, *gadd;
-  double damp;
-  int B, BB;
-  LocalSystem(const SageShardPlan &pl, const double *packed, double dmp, const double *da, const double *ga)
-      : p(pl), dadd(da), gadd(ga), damp(dmp), B(pl.B), BB(pl.B * pl.B)
-  {
-    diag = packed;
-    lnk = diag + (size_t)p.K * BB;
-    g = lnk + (size_t)p.nlinks * BB;
-  }
   bool owns_prior(int k) const { return p.kf_owner[k] == p.rank; }
-  double diag_elem(int k, int r, int c) const // symmetrised like the full solve (0.5 (D + D^T)) + prior + damping
-  {
-    double v = 0.5 * (diag[(size_t)k * BB + r * B + c] + diag[(size_t)k * BB + c * B + r]);
-    if (r == c)
-    {
-      const double pr = (dadd && owns_prior(k)) ? dadd[(size_t)k * B + r] : 0.0;
-      v = (v + pr) * (1.0 + damp);
-    }
-    return v;
-  }
-  double rhs(int k, int r) const
-  {
-    return g[(size_t)k * B + r] + ((gadd && owns_prior(k)) ? gadd[(size_t)k * B + r] : 0.0);
-  }
+  bool contributes(bool interior) const { return interior || !p.assembled || p.rank == 0; }
 };
 } // namespace
 
@@ -372,7 +352,8 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
   if (!p || !packed_local || !sep_out)
     return SAGE_E_INVALID;
   const int B = p->B, BB = B * B, K = p->K;
-  const LocalSystem S(*p, packed_local, damp, diag_add, g_add);
+  const LocalSystem S{*p};
+  const double *diag = packed_local, *lnk = diag + (size_t)K * BB, *g = lnk + (size_t)p->nlinks * BB;
   static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
   auto tnow = [] { return std::chrono::steady_clock::now(); };
   const auto t0 = tnow();
@@ -397,23 +378,22 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
   for (int q = 0; q < p->nloc; ++q)
   {
     const int k = q < nI ? p->interior[q] : p->sep_all[p->sep_local[q - nI]];
-    // separator diagonal blocks / right-hand sides: every rank's own contribution (rank mode: its packed buffer only holds
-    // its own edge sums); in assembled mode the buffer is complete and domain 0 alone contributes them
-    const bool contributes = q < nI || !p->assembled || p->rank == 0;
+    const bool contributes = S.contributes(q < nI), prior = S.owns_prior(k);
     double *D = blk(q, q);
     for (int r = 0; r < Bp; ++r)
       for (int c = 0; c < Bp; ++c)
       {
-        double v = 0.0;
+        double v = sage::damped_pad_elem(r, c, damp);
         if (r < B && c < B)
-          v = contributes ? S.diag_elem(k, r, c) : 0.0;
-        else if (r == c)
-          v = 1.0; // padding: identity
-        D[r * Bp + c] = v;
+          v = contributes ? sage::damped_diag_elem(diag + (size_t)k * BB, B, r, c,
+                                                   (diag_add && prior) ? diag_add[(size_t)k * B + r] : 0.0, damp)
+                          : 0.0;
+        D[sage::stored_slot(r, c, Bp)] = v;
       }
     if (contributes)
       for (int r = 0; r < B; ++r)
-        p->yv[(size_t)q * Bp + r] = S.rhs(k, r);
+        p->yv[(size_t)q * Bp + r] =
+            sage::damped_rhs_elem(g[(size_t)k * B + r], (g_add && prior) ? g_add[(size_t)k * B + r] : 0.0);
   }
   for (int l : p->local_links)
   {
@@ -422,12 +402,11 @@ extern "C" int sage_shard_eliminate(SageShardPlan *p, const double *packed_local
     if (qa < 0 || qb < 0)
       return SAGE_E_STATE;
     const int qi = std::max(qa, qb), qj = std::min(qa, qb);
-    double *D = blk(qi, qj); // stored [c in column position][r in row position]; the packed block is [r in a][c in b]
+    double *D = blk(qi, qj);
     const bool row_is_a = qi == qa;
-    const double *src = S.lnk + (size_t)l * BB;
     for (int r = 0; r < B; ++r)
       for (int c = 0; c < B; ++c)
-        D[row_is_a ? c * Bp + r : r * Bp + c] += src[r * B + c];
+        D[sage::stored_slot(r, c, Bp)] += lnk[(size_t)l * BB + sage::link_elem(row_is_a, r, c, B)];
   }
   const auto t1 = tnow();
   const int rcf = sage::block_chol_partial(env, p->T.data(), p->X.data(), p->yv.data(), nI);

@@ -1,14 +1,14 @@
-// solve_kernels.hip -- damped Gauss-Newton/LM step of the keyframe window on the device (gfx950).
+// solve_kernels.hip -- damped Gauss-Newton/LM step of the keyframe window: the hybrid solve (gfx950 + host cores).
 //
 // Replaces, for the batched window engine, the host side of the reference's optimisation step: the normal
 // equations the factors hand to the solver (core/gtsam/photometric_factor.cpp:106-219 -> gtsam HessianFactor,
 // ISAM2 update, core/mapping/mapper.cpp:118-156) and the LM damping policy of camera_tracker.cpp:1182
 // (H + damp*diag(H)), followed by the manifold retraction of gtsam_traits.h:45-70.  The window's block normal
-// equations (keyframe blocks of B = 7+CS rows, coupled along factor-graph links) stay in HBM end to end:
+// equations are keyframe blocks of B = 7+CS rows, coupled along factor-graph links:
 //
-//   scatter   packed [K diag blocks | link blocks | gradient] (double)  ->  block-envelope storage of the lower
-//             triangle (+ priors, LM damping, identity padding to BP rows), streamed into pinned host memory in the
-//             order the factorisation consumes it, a ticket per block
+//   scatter   packed [K diag blocks | link blocks | gradient] (double, HBM)  ->  block-envelope storage of the lower
+//             triangle (+ priors, LM damping, identity padding to Bp rows: damped_system.h), streamed into pinned host
+//             memory in the order the factorisation consumes it, a ticket per block
 //   factor    fixed-block Cholesky + substitutions on host cores (block_solver.cpp: block_chol_solve_tr -- two halves and
 //             a separator, each half as two pipelined stages)
 //   retract   candidate variables = retract(current, delta), read zero-copy from the host's solution
@@ -16,19 +16,18 @@
 // Everything is double: cond(H_damped) ~ 1e9 on the headline window.
 //
 // Why the factorisation is on the host: it is a dependency chain of K*B = 2.5 k pivots with ~27 M fused multiply-adds
-// in total.  A one-workgroup device factorisation took 4.2 ms on MI355X (K = 64, B = 39: 1.1 us per pivot, 16 waves
-// re-issue the panel update between two barriers; removed in r04), AVX-512 host cores do the same work in 0.13 ms.  So:
-// scatter on the device -> block storage over PCIe (pinned, 3.2 MB, overlapped with the factorisation) -> host
-// Cholesky -> retract on the device.
+// in total.  A device factorisation in one workgroup took 4.2 ms on MI355X (K = 64, B = 39; removed in r04), AVX-512 host
+// cores do the same work in 0.13 ms.  The block storage (3.2 MB) crosses PCIe overlapped with the factorisation.
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
+#include <atomic>
 #include <chrono>
-#include <cstdlib>
+#include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "block_solver.h"
+#include "damped_system.h"
 #include "host_math.h"
 #include "sage_device.h"
 #include "sage_internal.h"
@@ -41,59 +40,49 @@ struct SolvePlan
   int K, B, Bp, nblk, nlinks;
   const int32_t *row_first; // [K] first block column of block row i
   const int32_t *row_off;   // [K] index of block (i, row_first[i]) in the block storage
-  const int32_t *blk_row, *blk_col, *blk_src; // [nblk]; src = link index (bit 30: stored block is the link block
-                                               // itself rather than its transpose) or -1
+  const int32_t *blk_row, *blk_col, *blk_src; // [nblk]; src = link index (bit 30: the row keyframe is the link's first
+                                               // end) or -1
   const int32_t *perm, *pos; // elimination order: perm[position] = keyframe, pos[keyframe] = position
 };
 
-struct SolvePriors
+// Head of the pinned result block; the candidate variables [K*VS floats] and the delta [K*B doubles] follow it.
+struct SolveResult
 {
-  double code_w, scale_w, pose_w;
-  float scale_init0;
-  float pose_init0[12];
+  double step_norm2; // |delta|^2
+  int status;        // 0 candidate written, 1 no candidate (the host aborted the solve: non-positive pivot / error), 2 the
+                     // host's word never came -- the caller then treats the evaluation as failed instead of reading a
+                     // stale candidate
+  unsigned go;       // the host's word to the pre-launched retract (solve_retract_kernel)
 };
+static size_t result_vars_offset() { return sizeof(SolveResult); }
+static size_t result_delta_offset(int K, int VS) { return (sizeof(SolveResult) + (size_t)K * VS * sizeof(float) + 15) / 16 * 16; }
 
-// gtsam_traits.h:78-89 : [t1 - R1 R0^T t0, log(R1 R0^T)]
-__device__ inline void pose_local_dev(const float *origin, const float *other, double out[6])
-{
-  double Rr[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)
-      Rr[i * 3 + j] = (double)other[i * 3 + 0] * origin[j * 3 + 0] + (double)other[i * 3 + 1] * origin[j * 3 + 1] +
-                      (double)other[i * 3 + 2] * origin[j * 3 + 2];
-  for (int i = 0; i < 3; ++i)
-    out[i] = other[9 + i] - (Rr[i * 3 + 0] * origin[9] + Rr[i * 3 + 1] * origin[10] + Rr[i * 3 + 2] * origin[11]);
-  const double tr = Rr[0] + Rr[4] + Rr[8];
-  const double cs = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0)));
-  const double th = acos(cs);
-  const double k = th < 1e-8 ? 0.5 : th / (2.0 * sin(th));
-  out[3] = k * (Rr[7] - Rr[5]);
-  out[4] = k * (Rr[2] - Rr[6]);
-  out[5] = k * (Rr[3] - Rr[1]);
-}
+// Workgroups of the scatter kernel.  Not measured against other counts on record; r04 measured the kernel itself at this
+// count (88 -> 73 us with one system-scope release per block).
+constexpr int kScatterWorkgroups = 32;
 
 // ------------------------------------------------------------------------------------------------
-// scatter: a workgroup per envelope block (device factorisation), or a few workgroups walking the blocks in the order
-// the host factorisation consumes them and writing straight into pinned host memory (hybrid path): every block is
-// followed by a ticket in `flags`, so the host starts on row 0 while the later rows are still crossing PCIe.
+// scatter: a few workgroups walk the blocks in the order the host factorisation consumes them and write straight into
+// pinned host memory: every block is followed by a ticket in `flags`, so the host starts on row 0 while the later rows
+// are still crossing PCIe.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, const double *__restrict__ packed,
                                                             const float *__restrict__ vars0, int VS, int CS,
-                                                            const SolvePriors pri, double damp, int transposed,
+                                                            const SolvePriors pri, double damp,
                                                             double *__restrict__ L, double *__restrict__ y,
                                                             const int32_t *__restrict__ order, unsigned *flags,
-                                                            unsigned epoch, int first, int count, int deliver_fill)
+                                                            unsigned epoch)
 {
   const int tid = threadIdx.x;
   const int B = P.B, Bp = P.Bp, BB = B * B;
   __shared__ double s_dadd[64], s_gadd[64];
-  for (int it = first + blockIdx.x; it < first + count; it += gridDim.x) // [first, first+count) of the order list
+  for (int it = blockIdx.x; it < P.nblk; it += gridDim.x)
   {
-    const int b = order ? order[it] : it;
+    const int b = order[it];
     const int i = P.blk_row[b], j = P.blk_col[b], srcf = P.blk_src[b];
     const int src = srcf < 0 ? -1 : (srcf & 0x3fffffff);
-    const bool flip = srcf >= 0 && (srcf & 0x40000000);
-    if (flags && src < 0 && i != j && !deliver_fill)
+    const bool row_is_a = srcf >= 0 && (srcf & 0x40000000);
+    if (src < 0 && i != j)
       continue; // structural fill-in: the host zeroes it at its first touch (BlockEnvelope::fill) -- nothing to deliver
     const int kf = P.perm[i]; // keyframe of this block row
     const double *diag = packed + (size_t)kf * BB;
@@ -102,120 +91,57 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
     double *out = L + (size_t)b * Bp * Bp;
     if (i == j)
     {
-      // diagonal priors (a9): code prior on every keyframe (zero prior mean), scale / pose priors on keyframe 0
       const float *var = vars0 + (size_t)kf * VS; // pose 12, scale, code CS
       if (tid < B)
       {
-        double da = 0.0, ga = 0.0;
-        if (tid >= 6 && tid < 6 + CS)
-        {
-          da = pri.code_w;
-          ga = pri.code_w * (0.0 - (double)var[13 + tid - 6]);
-        }
-        if (kf == 0 && tid == 6 + CS && pri.scale_w > 0)
-        {
-          const double s = (double)var[12];
-          da = pri.scale_w / (s * s);
-          ga = pri.scale_w / s * (log((double)pri.scale_init0) - log(s));
-        }
-        if (kf == 0 && tid < 6 && pri.pose_w > 0)
-        {
-          double loc[6];
-          pose_local_dev(var, pri.pose_init0, loc);
-          da = pri.pose_w;
-          ga = pri.pose_w * loc[tid];
-        }
+        double da, ga;
+        prior_row(pri, kf, tid, CS, var, var[12], var + 13, da, ga);
         s_dadd[tid] = da;
         s_gadd[tid] = ga;
       }
       __syncthreads();
     }
-    // consecutive threads write consecutive doubles (the stores may be crossing PCIe); (r, c) = element of the block
+    // consecutive threads write consecutive doubles (the stores are crossing PCIe)
     for (int o = tid; o < Bp * Bp; o += blockDim.x)
     {
-      const int hi = o / Bp, lo = o - hi * Bp;
-      const int r = transposed ? lo : hi, c = transposed ? hi : lo; // transposed: block stored [c][r]
+      const int c = o / Bp, r = o - c * Bp; // o == stored_slot(r, c, Bp)
       double v = 0.0;
       if (i == j)
-      {
-        if (r < B && c < B)
-        {
-          v = 0.5 * (diag[r * B + c] + diag[c * B + r]);
-          if (r == c)
-            v = (v + s_dadd[r]) * (1.0 + damp); // LM damping H + damp*diag(H) (camera_tracker.cpp:1182)
-        }
-        else if (r == c)
-          v = 1.0 + damp; // identity padding: delta 0 on the padding rows
-      }
-      else if (src >= 0 && r < B && c < B)
-        v = flip ? lnk[r * B + c] : lnk[c * B + r]; // packed link block is (a,b), a < b; this block is (row kf, col kf)
+        v = (r < B && c < B) ? damped_diag_elem(diag, B, r, c, s_dadd[r], damp) : damped_pad_elem(r, c, damp);
+      else if (r < B && c < B)
+        v = lnk[link_elem(row_is_a, r, c, B)];
       out[o] = v;
     }
     if (i == j)
       for (int r = tid; r < Bp; r += blockDim.x)
-        y[(size_t)i * Bp + r] = r < B ? g[r] + s_gadd[r] : 0.0;
-    if (flags)
+        y[(size_t)i * Bp + r] = r < B ? damped_rhs_elem(g[r], s_gadd[r]) : 0.0;
+    // the block (and its rhs rows) are visible to the host before the ticket is: the workgroup barrier orders every
+    // lane's stores before lane 0's system-scope release (one cache write-back per block instead of one per wave)
+    __syncthreads();
+    if (tid == 0)
     {
-      // the block (and its rhs rows) are visible to the host before the ticket is: the workgroup barrier orders every
-      // lane's stores before lane 0's system-scope release (one cache write-back per block instead of one per wave)
-      __syncthreads();
-      if (tid == 0)
-      {
-        __threadfence_system();
-        *reinterpret_cast<volatile unsigned *>(flags + b) = epoch;
-      }
+      __threadfence_system();
+      *reinterpret_cast<volatile unsigned *>(flags + b) = epoch;
     }
-    else
-      __syncthreads(); // s_dadd / s_gadd are reused by the next block
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// retract: candidate = current (+) delta   (gtsam_traits.h:45-70; tangent order [trans, rot], left update)
+// retract: candidate = current (+) delta   (damped_system.h pose_retract; tangent order [trans, rot], left update)
 // ------------------------------------------------------------------------------------------------
-__device__ inline void se3_exp_dev(const float *omega, const float *v, float *R, float *t) // mapping_utils.h:316-346
-{
-  float theta = sqrtf(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
-  float n[3] = {1.f, 0.f, 0.f};
-  if (theta > 0)
-  {
-    n[0] = omega[0] / theta;
-    n[1] = omega[1] / theta;
-    n[2] = omega[2] / theta;
-  }
-  theta = fmaxf(theta, 1.0e-14f);
-  const float s = sinf(theta), c = cosf(theta);
-  const float Km[3][3] = {{0, -n[2], n[1]}, {n[2], 0, -n[0]}, {-n[1], n[0], 0}};
-  float K2[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)
-      K2[i][j] = Km[i][0] * Km[0][j] + Km[i][1] * Km[1][j] + Km[i][2] * Km[2][j];
-  const float a = (1.0f - c) / theta, b = (theta - s) / theta;
-  for (int i = 0; i < 3; ++i)
-  {
-    float acc = 0.f;
-    for (int j = 0; j < 3; ++j)
-    {
-      const float id = (i == j) ? 1.f : 0.f;
-      R[i * 3 + j] = id + s * Km[i][j] + (1.0f - c) * K2[i][j];
-      acc += (id + a * Km[i][j] + b * K2[i][j]) * v[j];
-    }
-    t[i] = acc;
-  }
-}
-
 // One workgroup.  Besides the candidate variables (device) it writes the host mirror -- candidate variables, delta and
 // |delta|^2 -- straight into pinned host memory (h_*: device-visible), so no copy follows the solve.
-// (1024 threads: in the hybrid path x lives in pinned host memory -- every read is a PCIe round trip, so the kernel's
-// time is the number of sequential reads per thread)
+// (1024 threads: x lives in pinned host memory -- every read is a PCIe round trip, so the kernel's time is the number of
+// sequential reads per thread)
 __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__restrict__ x, int K, int B, int Bp, int CS,
                                                             int VS, const int32_t *__restrict__ pos,
                                                             const float *__restrict__ vars0,
                                                             float *__restrict__ vars1, float *__restrict__ h_vars,
-                                                            double *__restrict__ h_delta, double *__restrict__ h_tail,
-                                                            const volatile unsigned *go, unsigned epoch)
+                                                            double *__restrict__ h_delta, SolveResult *h_res,
+                                                            unsigned epoch)
 {
   const int tid = threadIdx.x;
+  const volatile unsigned *go = &h_res->go;
   // The kernel is enqueued BEFORE the host factorises (right behind the scatter) and waits here for the host's word in
   // pinned memory: the solution is there (go == epoch), or there is none (bit 31 set: non-positive pivot / abort).  The
   // launch latency of a kernel issued into an idle queue (tens of microseconds on the step's critical path) is hidden
@@ -249,10 +175,8 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
     }
     __threadfence_system();
     s_go = (v & 0x80000000u) ? 0 : 1;
-    // status word of the host mirror (solver_host_status): 0 candidate written, 1 no candidate (the host aborted the solve:
-    // non-positive pivot / error), 2 the host's word never came -- the caller then treats the evaluation as failed instead
-    // of reading a stale candidate
-    *reinterpret_cast<volatile int *>(h_tail + 1) = timed_out ? 2 : (s_go ? 0 : 1);
+    volatile int *status = &h_res->status;
+    *status = timed_out ? 2 : (s_go ? 0 : 1);
   }
   __syncthreads();
   if (!s_go)
@@ -277,21 +201,13 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
   {
     const double *xk = x + (size_t)pos[k] * Bp;
     const float *v0 = vars0 + (size_t)k * VS;
-    float d6[6], dR[9], dt[3], o[12];
+    float d6[6];
     for (int i = 0; i < 6; ++i)
       d6[i] = (float)xk[i];
-    se3_exp_dev(d6 + 3, d6, dR, dt);
-    for (int i = 0; i < 3; ++i)
-    {
-      for (int j = 0; j < 3; ++j)
-        o[i * 3 + j] = dR[i * 3 + 0] * v0[0 * 3 + j] + dR[i * 3 + 1] * v0[1 * 3 + j] + dR[i * 3 + 2] * v0[2 * 3 + j];
-      o[9 + i] = dR[i * 3 + 0] * v0[9] + dR[i * 3 + 1] * v0[10] + dR[i * 3 + 2] * v0[11] + dt[i];
-    }
+    float *o = vars1 + (size_t)k * VS; // the device candidate; the host mirror gets its copy
+    pose_retract(v0, d6, o);
     for (int i = 0; i < 12; ++i)
-    {
-      vars1[(size_t)k * VS + i] = o[i];
       h_vars[(size_t)k * VS + i] = o[i];
-    }
   }
   __shared__ double s_n[16];
   for (int off = 32; off > 0; off >>= 1)
@@ -304,7 +220,7 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
     double tot = 0.0;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) // fixed order
       tot += s_n[w];
-    h_tail[0] = tot;
+    h_res->step_norm2 = tot;
   }
 }
 
@@ -313,44 +229,52 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
 // ------------------------------------------------------------------------------------------------
 struct DeviceSolver
 {
-  int K = 0, B = 0, Bp = 0, nblk = 0, nlinks = 0;
-  void *d_int = nullptr;   // all int tables in one allocation
-  void *h_pinned = nullptr; // [K*VS floats | K*B doubles | tail double | status int | go word of the pre-launched retract]
-  size_t h_go_off = 0;
-  unsigned go_epoch = 0;
-  size_t h_vars_off = 0, h_delta_off = 0, h_tail_off = 0, h_bytes = 0;
+  int K = 0, B = 0, Bp = 0, nblk = 0, nlinks = 0, VS = 0;
+  void *d_int = nullptr;    // all int tables in one allocation
+  void *h_pinned = nullptr; // [SolveResult | K*VS floats | K*B doubles]
+  void *h_T = nullptr;      // pinned, one allocation: block storage, then the right-hand side, then the tickets
+  double *h_y = nullptr;
+  unsigned *h_flags = nullptr; // a ticket (the epoch of the solve that wrote it) per block
+  unsigned epoch = 0, go_epoch = 0;
   SolvePlan plan{};
-  int VS = 0;
-  void *h_T = nullptr, *h_y = nullptr;       // pinned, one allocation: block storage, then the right-hand side
-  std::vector<double> h_X;                   // inverses of the diagonal factors
-  BlockPlan host_plan;                       // elimination order and block storage (what the host factorisation reads)
-  // hybrid path: the scatter kernel writes blocks + rhs straight into h_T / h_y in consumption order and posts a
-  // ticket (the epoch of this solve) per block in h_flags
-  const int32_t *d_order = nullptr;
-  unsigned *h_flags = nullptr;
-  unsigned epoch = 0;
-  int scatter_wgs = 32;
-  std::vector<uint8_t> h_fill;        // per block: structural fill-in (not delivered by the scatter kernel: BlockEnvelope::fill)
+  const int32_t *d_order = nullptr; // the blocks in the order the host factorisation consumes them
+  std::vector<double> h_X;          // inverses of the diagonal factors
+  BlockPlan host_plan;              // elimination order and block storage (what the host factorisation reads)
+  std::vector<uint8_t> h_fill;      // per block: structural fill-in (not delivered by the scatter kernel: BlockEnvelope::fill)
+
+  DeviceSolver() = default;
+  DeviceSolver(const DeviceSolver &) = delete;
+  DeviceSolver &operator=(const DeviceSolver &) = delete;
+  ~DeviceSolver()
+  {
+    if (d_int)
+      (void)hipFree(d_int);
+    if (h_pinned)
+      (void)hipHostFree(h_pinned);
+    if (h_T)
+      (void)hipHostFree(h_T);
+  }
+  SolveResult *result() const { return reinterpret_cast<SolveResult *>(h_pinned); }
+  float *host_vars() const { return reinterpret_cast<float *>(reinterpret_cast<char *>(h_pinned) + result_vars_offset()); }
+  double *host_delta() const { return reinterpret_cast<double *>(reinterpret_cast<char *>(h_pinned) + result_delta_offset(K, VS)); }
 };
 
 int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
-                  hipStream_t stream, bool allow_split)
+                  hipStream_t stream)
 {
   *out = nullptr;
   const int Bp = sage::padded_block(B);
   if (Bp == 0 || K < 1)
     return SAGE_E_UNSUPPORTED;
   BlockPlan bp;
-  {
-    const int rcp = plan_blocks(K, links, allow_split && !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
-    if (rcp != SAGE_OK)
-      return rcp;
-  }
+  const int rcp = plan_blocks(K, links, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
+  if (rcp != SAGE_OK)
+    return rcp;
   const int n1 = bp.n1, n2 = bp.n2, nblk = bp.nblk;
   const std::vector<int32_t> &perm = bp.perm, &pos = bp.pos, &row_first = bp.row_first, &row_off = bp.row_off,
                              &a_cnt = bp.a_cnt, &a_off = bp.a_off, &blk_row = bp.blk_row, &blk_col = bp.blk_col,
                              &blk_src = bp.blk_src;
-  DeviceSolver *S = new DeviceSolver;
+  std::unique_ptr<DeviceSolver> S(new DeviceSolver); // (an early return releases what has been allocated so far)
   S->K = K; S->B = B; S->Bp = Bp; S->nblk = nblk; S->nlinks = (int)links.size(); S->VS = VS;
   // one allocation for the int tables
   std::vector<int32_t> all;
@@ -365,57 +289,46 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
                o_bs = put(blk_src), o_pm = put(perm), o_ps = put(pos);
   // consumption order of the host factorisation: the two halves row by row side by side, the separator last
   std::vector<int32_t> order;
-  {
-    auto push_row = [&](int i) {
-      for (int q = 0; q < a_cnt[i]; ++q)
-        order.push_back(a_off[i] + q);
-      for (int q = 0; q <= i - row_first[i]; ++q)
-        order.push_back(row_off[i] + q);
-    };
-    if (n1 > 0)
-    {
-      for (int t = 0; t < std::max(n1, n2); ++t)
-      {
-        if (t < n1)
-          push_row(t);
-        if (t < n2)
-          push_row(n1 + t);
-      }
-      for (int i = n1 + n2; i < K; ++i)
-        push_row(i);
-    }
-    else
-      for (int i = 0; i < K; ++i)
-        push_row(i);
-  }
-  const size_t o_ord = put(order);
-  auto fail = [&](int rc) {
-    solver_destroy(S);
-    return rc;
+  auto push_row = [&](int i) {
+    for (int q = 0; q < a_cnt[i]; ++q)
+      order.push_back(a_off[i] + q);
+    for (int q = 0; q <= i - row_first[i]; ++q)
+      order.push_back(row_off[i] + q);
   };
-  if (hipMalloc(&S->d_int, all.size() * sizeof(int32_t)) != hipSuccess)
-    return fail((int)hipErrorOutOfMemory);
-  if (hipMemcpyAsync(S->d_int, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess)
-    return fail((int)hipErrorUnknown);
-  if (hipStreamSynchronize(stream) != hipSuccess)
-    return fail((int)hipErrorUnknown);
-  const size_t ty_doubles = (size_t)nblk * Bp * Bp + (size_t)K * Bp;
+  if (n1 > 0)
   {
-    if (hipHostMalloc(&S->h_T, ty_doubles * sizeof(double) + (size_t)nblk * sizeof(unsigned), hipHostMallocDefault) !=
-        hipSuccess)
-      return fail((int)hipErrorOutOfMemory);
-    S->h_y = reinterpret_cast<double *>(S->h_T) + (size_t)nblk * Bp * Bp;
-    S->h_flags = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(S->h_T) + ty_doubles);
-    std::memset(S->h_flags, 0, (size_t)nblk * sizeof(unsigned));
-    S->h_X.assign((size_t)K * Bp * Bp, 0.0);
+    for (int t = 0; t < std::max(n1, n2); ++t)
+    {
+      if (t < n1)
+        push_row(t);
+      if (t < n2)
+        push_row(n1 + t);
+    }
+    for (int i = n1 + n2; i < K; ++i)
+      push_row(i);
   }
-  S->h_vars_off = 0;
-  S->h_delta_off = ((size_t)K * VS * sizeof(float) + 15) / 16 * 16;
-  S->h_tail_off = S->h_delta_off + (size_t)K * B * sizeof(double);
-  S->h_go_off = S->h_tail_off + 2 * sizeof(double);
-  S->h_bytes = S->h_go_off + 2 * sizeof(double);
-  if (hipHostMalloc(&S->h_pinned, S->h_bytes, hipHostMallocDefault) != hipSuccess)
-    return fail((int)hipErrorOutOfMemory);
+  else
+    for (int i = 0; i < K; ++i)
+      push_row(i);
+  const size_t o_ord = put(order);
+  if (hipMalloc(&S->d_int, all.size() * sizeof(int32_t)) != hipSuccess)
+    return (int)hipErrorOutOfMemory;
+  if (hipMemcpyAsync(S->d_int, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess)
+    return (int)hipErrorUnknown;
+  if (hipStreamSynchronize(stream) != hipSuccess)
+    return (int)hipErrorUnknown;
+  const size_t ty_doubles = (size_t)nblk * Bp * Bp + (size_t)K * Bp;
+  if (hipHostMalloc(&S->h_T, ty_doubles * sizeof(double) + (size_t)nblk * sizeof(unsigned), hipHostMallocDefault) !=
+      hipSuccess)
+    return (int)hipErrorOutOfMemory;
+  S->h_y = reinterpret_cast<double *>(S->h_T) + (size_t)nblk * Bp * Bp;
+  S->h_flags = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(S->h_T) + ty_doubles);
+  std::memset(S->h_flags, 0, (size_t)nblk * sizeof(unsigned));
+  S->h_X.assign((size_t)K * Bp * Bp, 0.0);
+  const size_t h_bytes = result_delta_offset(K, VS) + (size_t)K * B * sizeof(double);
+  if (hipHostMalloc(&S->h_pinned, h_bytes, hipHostMallocDefault) != hipSuccess)
+    return (int)hipErrorOutOfMemory;
+  std::memset(S->h_pinned, 0, h_bytes);
   const int32_t *base = reinterpret_cast<const int32_t *>(S->d_int);
   SolvePlan &P = S->plan;
   P.K = K; P.B = B; P.Bp = Bp; P.nblk = nblk; P.nlinks = (int)links.size();
@@ -425,106 +338,77 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   S->h_fill.assign((size_t)nblk, 0);
   for (int b = 0; b < nblk; ++b)
     S->h_fill[b] = (blk_src[b] < 0 && blk_row[b] != blk_col[b]) ? 1 : 0;
-  if (const char *e = getenv("SAGE_SCATTER_WGS")) // (diagnostic: workgroups of the scatter kernel)
-    S->scatter_wgs = std::max(1, atoi(e));
-  std::memset(S->h_pinned, 0, S->h_bytes);
   S->host_plan = std::move(bp); // (last: the tables above are references into it)
-  *out = S;
+  *out = S.release();
   return SAGE_OK;
 }
 
-void solver_destroy(DeviceSolver *S)
-{
-  if (!S)
-    return;
-  void *bufs[] = {S->d_int};
-  for (void *p : bufs)
-    if (p)
-      (void)hipFree(p);
-  void *hbufs[] = {S->h_pinned, S->h_T};
-  for (void *p : hbufs)
-    if (p)
-      (void)hipHostFree(p);
-  delete S;
-}
+void solver_destroy(DeviceSolver *S) { delete S; }
 
 // enqueue scatter and retract, factorise on the host in between (the retract waits on the device for the host's word);
 // the candidate's host mirror is valid once the stream has drained (or a later kernel's ticket has been seen).
+// The dependency chain of the factorisation runs on host cores, everything around it stays on the device: the scatter
+// kernel streams the blocks into pinned host memory in the order the factorisation consumes them and tickets each one,
+// so the host works on row 0 while the rest is still crossing PCIe (no D2H copy, no stream sync).
 int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, const float *vars0, float *vars1,
-               int CS, double damp, double code_w, double scale_w, double pose_w, float scale_init0,
-               const float *pose_init0)
+               int CS, double damp, const SolvePriors &pri)
 {
-  SolvePriors pri{};
-  pri.code_w = code_w; pri.scale_w = scale_w; pri.pose_w = pose_w; pri.scale_init0 = scale_init0;
-  for (int i = 0; i < 12; ++i)
-    pri.pose_init0[i] = pose_init0[i];
+  static const bool dbgt = sage::env_flag("SAGE_DEBUG_TIMING");
+  hipError_t eh;
+  // held from the arm until block_chol_solve_tr returns, also without a split (the solve may still hand work to helpers
+  // another caller armed): no shutdown joins a helper in between
+  SolveLease lease;
+  BlockEnvelope env = envelope_of(S->host_plan, S->Bp);
+  // the helper core (and, for loop-closure plans with long separator rows, the worker pool) wakes up while this
+  // thread waits for the device
+  if (env.n1 > 0)
+    env.no_lookahead = block_chol_arm(block_plan_has_arrow_rows(env), block_plan_long_arrow_chains(env));
+  S->epoch += 1;
+  if (S->epoch == 0) // wrapped: 0 is the "never written" value
+    S->epoch = 1;
+  hipLaunchKernelGGL(solve_scatter_kernel, dim3(std::min(kScatterWorkgroups, S->nblk)), dim3(256), 0, stream, S->plan,
+                     packed_dev, vars0, S->VS, CS, pri, damp, reinterpret_cast<double *>(S->h_T), S->h_y, S->d_order,
+                     S->h_flags, S->epoch);
+  if ((eh = hipGetLastError()) != hipSuccess)
+    return (int)eh;
+  // the retract right behind the scatter: it waits on the device for this thread's word (solve_retract_kernel)
+  volatile unsigned *go = &S->result()->go;
+  S->go_epoch = (S->go_epoch + 1) & 0x7fffffffu;
+  if (S->go_epoch == 0)
+    S->go_epoch = 1;
+  hipLaunchKernelGGL(solve_retract_kernel, dim3(1), dim3(1024), 0, stream, S->h_y, S->K, S->B, S->Bp, CS, S->VS,
+                     S->plan.pos, vars0, vars1, S->host_vars(), S->host_delta(), S->result(), S->go_epoch);
+  if ((eh = hipGetLastError()) != hipSuccess)
+    return (int)eh;
+  struct GoGuard // whatever happens below, the waiting kernel gets its word
   {
-    // hybrid: the dependency chain of the factorisation runs on host cores, everything around it stays on the device.
-    // The scatter kernel streams the blocks into pinned host memory in the order the factorisation consumes them and
-    // tickets each one, so the host works on row 0 while the rest is still crossing PCIe (no D2H copy, no stream sync).
-    static const bool dbgt = sage::env_flag("SAGE_DEBUG_TIMING");
-    hipError_t eh;
-    // held from the arm until block_chol_solve_tr returns, also without a split (the solve may still hand work to helpers
-    // another caller armed): no shutdown joins a helper in between
-    SolveLease lease;
-    BlockEnvelope env = envelope_of(S->host_plan, S->Bp);
-    // the helper core (and, for loop-closure plans with long separator rows, the worker pool) wakes up while this
-    // thread waits for the device
-    if (env.n1 > 0)
-      env.no_lookahead = block_chol_arm(block_plan_has_arrow_rows(env), block_plan_long_arrow_chains(env));
-    S->epoch += 1;
-    if (S->epoch == 0) // wrapped: 0 is the "never written" value
-      S->epoch = 1;
-    hipLaunchKernelGGL(solve_scatter_kernel, dim3(std::min(S->scatter_wgs, S->nblk)), dim3(256), 0, stream, S->plan,
-                       packed_dev, vars0, S->VS, CS, pri, damp, 1, reinterpret_cast<double *>(S->h_T),
-                       reinterpret_cast<double *>(S->h_y), S->d_order, S->h_flags, S->epoch, 0, S->nblk,
-                       sage::env_flag("SAGE_SCATTER_FILL") ? 1 : 0); // (diagnostic: ship the zero fill blocks as r04 did)
-    if ((eh = hipGetLastError()) != hipSuccess)
-      return (int)eh;
-    // the retract right behind the scatter: it waits on the device for this thread's word (solve_retract_kernel)
-    char *hp = reinterpret_cast<char *>(S->h_pinned);
-    volatile unsigned *go = reinterpret_cast<volatile unsigned *>(hp + S->h_go_off);
-    S->go_epoch = (S->go_epoch + 1) & 0x7fffffffu;
-    if (S->go_epoch == 0)
-      S->go_epoch = 1;
-    hipLaunchKernelGGL(solve_retract_kernel, dim3(1), dim3(1024), 0, stream,
-                       reinterpret_cast<const double *>(S->h_y), S->K, S->B, S->Bp, CS, S->VS, S->plan.pos, vars0, vars1,
-                       reinterpret_cast<float *>(hp + S->h_vars_off), reinterpret_cast<double *>(hp + S->h_delta_off),
-                       reinterpret_cast<double *>(hp + S->h_tail_off), go, S->go_epoch);
-    if ((eh = hipGetLastError()) != hipSuccess)
-      return (int)eh;
-    struct GoGuard // whatever happens below, the waiting kernel gets its word
+    volatile unsigned *go;
+    unsigned word;
+    ~GoGuard()
     {
-      volatile unsigned *go;
-      unsigned word;
-      ~GoGuard()
-      {
-        std::atomic_thread_fence(std::memory_order_release);
-        *go = word;
-      }
-    } guard{go, S->go_epoch | 0x80000000u};
-    const auto t1 = std::chrono::steady_clock::now();
-    env.ready = S->h_flags; env.epoch = S->epoch;
-    env.fill = S->h_fill.data();
-    const int bad = block_chol_solve_tr(env, reinterpret_cast<double *>(S->h_T), S->h_X.data(),
-                                        reinterpret_cast<double *>(S->h_y));
-    const auto t2 = std::chrono::steady_clock::now();
-    if (dbgt)
-      fprintf(stderr, "[sage hybrid solve] wait for the system + host cholesky %.3f ms\n",
-              std::chrono::duration<double, std::milli>(t2 - t1).count());
-    if (bad == -2)
-      return SAGE_E_STATE; // the device never delivered a block (see block_chol_solve_tr)
-    if (bad)
-      return SAGE_E_NOT_PSD;
-    guard.word = S->go_epoch; // the solution is in h_y: go
-    (void)eh;
-  }
+      std::atomic_thread_fence(std::memory_order_release);
+      *go = word;
+    }
+  } guard{go, S->go_epoch | 0x80000000u};
+  const auto t1 = std::chrono::steady_clock::now();
+  env.ready = S->h_flags; env.epoch = S->epoch;
+  env.fill = S->h_fill.data();
+  const int bad = block_chol_solve_tr(env, reinterpret_cast<double *>(S->h_T), S->h_X.data(), S->h_y);
+  const auto t2 = std::chrono::steady_clock::now();
+  if (dbgt)
+    fprintf(stderr, "[sage hybrid solve] wait for the system + host cholesky %.3f ms\n",
+            std::chrono::duration<double, std::milli>(t2 - t1).count());
+  if (bad == -2)
+    return SAGE_E_STATE; // the device never delivered a block (see block_chol_solve_tr)
+  if (bad)
+    return SAGE_E_NOT_PSD;
+  guard.word = S->go_epoch; // the solution is in h_y: go
   return SAGE_OK;
 }
 
-const float *solver_host_vars(const DeviceSolver *S) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(S->h_pinned) + S->h_vars_off); }
-const double *solver_host_delta(const DeviceSolver *S) { return reinterpret_cast<const double *>(reinterpret_cast<const char *>(S->h_pinned) + S->h_delta_off); }
-double solver_host_step_norm2(const DeviceSolver *S) { return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(S->h_pinned) + S->h_tail_off); }
-int solver_host_status(const DeviceSolver *S) { return *reinterpret_cast<const int *>(reinterpret_cast<const char *>(S->h_pinned) + S->h_tail_off + sizeof(double)); }
+const float *solver_host_vars(const DeviceSolver *S) { return S->host_vars(); }
+const double *solver_host_delta(const DeviceSolver *S) { return S->host_delta(); }
+double solver_host_step_norm2(const DeviceSolver *S) { return S->result()->step_norm2; }
+int solver_host_status(const DeviceSolver *S) { return S->result()->status; }
 
 } // namespace sage

@@ -1,29 +1,11 @@
 // window_solve.hip -- from a system to a candidate: the prior terms, the damped solve (device solver, or the host block solve
 // of windows with duplicate links), the sharded windows' separator solve, taking up the candidate the device solver left in
 // pinned memory, and what becomes of a candidate afterwards: accept, reset, the exchange of the owners' variables.
+#include "damped_system.h"
 #include "runtime_internal.h"
 
 // prior error terms at a variable set (a9): code prior w*||c||^2/CS per keyframe (code_factor.cpp:99-104, zero
 // prior code), scale prior on keyframe 0 w*(ln s0 - ln s)^2 (scale_factor.cpp:102-129), pose prior on kf 0.
-static void pose_local(const float *origin, const float *other, double out[6])
-{
-  // gtsam_traits.h:78-89 : [t1 - R1 R0^T t0, log(R1 R0^T)]
-  double Rr[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)
-      Rr[i * 3 + j] = (double)other[i * 3 + 0] * origin[j * 3 + 0] + (double)other[i * 3 + 1] * origin[j * 3 + 1] +
-                      (double)other[i * 3 + 2] * origin[j * 3 + 2];
-  for (int i = 0; i < 3; ++i)
-    out[i] = other[9 + i] - (Rr[i * 3 + 0] * origin[9] + Rr[i * 3 + 1] * origin[10] + Rr[i * 3 + 2] * origin[11]);
-  const double tr = Rr[0] + Rr[4] + Rr[8];
-  const double cs = std::min(1.0, std::max(-1.0, 0.5 * (tr - 1.0)));
-  const double th = std::acos(cs);
-  const double k = th < 1e-8 ? 0.5 : th / (2.0 * std::sin(th));
-  out[3] = k * (Rr[7] - Rr[5]);
-  out[4] = k * (Rr[2] - Rr[6]);
-  out[5] = k * (Rr[3] - Rr[1]);
-}
-
 // owned_only (sharded windows): the terms of the keyframes THIS rank owns (the other ranks' copies of their variables are
 // stale here).  The owned sum takes keyframe 0's scale / pose terms right behind its code term, the full sum behind every
 // keyframe's code term: each keeps its order, so neither total moves in the last bit
@@ -40,7 +22,7 @@ double window_prior_error(const SageWindow *w, int set, bool owned_only)
     if (c.pose_prior_weight > 0)
     {
       double loc[6];
-      pose_local(&w->hv.pose[set][0], &w->hv.pose_init[0], loc);
+      sage::pose_local(&w->hv.pose[set][0], &w->hv.pose_init[0], loc);
       for (int i = 0; i < 6; ++i)
         e += c.pose_prior_weight * loc[i] * loc[i];
     }
@@ -61,35 +43,27 @@ double window_prior_error(const SageWindow *w, int set, bool owned_only)
   return e;
 }
 
-// diagonal priors (a9): code prior on every keyframe, scale / pose priors on keyframe 0
-static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::vector<double> &gadd)
+static sage::SolvePriors window_solve_priors(const SageWindow *w)
 {
   const SageWindowConfig &c = w->cfg;
-  const int K = w->K, B = w->B, CS = c.CS;
+  sage::SolvePriors pri{};
+  pri.code_w = c.code_prior_weight; pri.scale_w = c.scale_prior_weight; pri.pose_w = c.pose_prior_weight;
+  pri.scale_init0 = w->hv.scale_init[0];
+  std::copy_n(&w->hv.pose_init[0], 12, pri.pose_init0);
+  return pri;
+}
+
+// diagonal priors (a9) at the current variables, for the host solves: what the scatter kernel adds on the device
+static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::vector<double> &gadd)
+{
+  const int K = w->K, B = w->B, CS = w->cfg.CS;
+  const sage::SolvePriors pri = window_solve_priors(w);
   dadd.assign((size_t)K * B, 0.0);
   gadd.assign((size_t)K * B, 0.0);
   for (int k = 0; k < K; ++k)
-    for (int i = 0; i < CS; ++i)
-    {
-      dadd[k * B + 6 + i] += c.code_prior_weight;
-      gadd[k * B + 6 + i] += c.code_prior_weight * (0.0 - (double)w->hv.code[0][(size_t)k * CS + i]);
-    }
-  if (c.scale_prior_weight > 0)
-  {
-    const double s = w->hv.scale[0][0];
-    dadd[6 + CS] += c.scale_prior_weight / (s * s);
-    gadd[6 + CS] += c.scale_prior_weight / s * (std::log((double)w->hv.scale_init[0]) - std::log(s));
-  }
-  if (c.pose_prior_weight > 0)
-  {
-    double loc[6];
-    pose_local(&w->hv.pose[0][0], &w->hv.pose_init[0], loc);
-    for (int i = 0; i < 6; ++i)
-    {
-      dadd[i] += c.pose_prior_weight;
-      gadd[i] += c.pose_prior_weight * loc[i];
-    }
-  }
+    for (int r = 0; r < B; ++r)
+      sage::prior_row(pri, k, r, CS, &w->hv.pose[0][(size_t)k * 12], w->hv.scale[0][k], &w->hv.code[0][(size_t)k * CS],
+                      dadd[(size_t)k * B + r], gadd[(size_t)k * B + r]);
 }
 
 // candidate = retract(current, delta).  local_only (sharded windows): only the keyframes this rank touches, the others
@@ -149,8 +123,7 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
     if (w->dpt_set == 1)
       w->dpt_set = -1; // the solve rewrites the candidate set
     rc = solver_run(w->solver, w->stream, w->packed.as<double>(), w->vars[0].as<float>(), w->vars[1].as<float>(), CS,
-                    damp, c.code_prior_weight, c.scale_prior_weight, c.pose_prior_weight, w->hv.scale_init[0],
-                    &w->hv.pose_init[0]);
+                    damp, window_solve_priors(w));
     if (rc)
       return rc;
     window_phase_mark(w, 3);

@@ -62,3 +62,36 @@ def damped_delta(H, g, damp):
     """(H + damp*diag(H)) d = g in fp64 (reference LM damping, camera_tracker.cpp:1182)."""
     Hd = H + damp * np.diag(np.diag(H))
     return np.linalg.solve(Hd, g)
+
+
+def pose_local(origin, other):
+    """[t1 - R1 R0^T t0, log(R1 R0^T)] of two poses [R row-major | t] (gtsam_traits.h:78-89), in fp64."""
+    origin = np.asarray(origin, np.float64); other = np.asarray(other, np.float64)
+    Rr = other[:9].reshape(3, 3) @ origin[:9].reshape(3, 3).T
+    th = np.arccos(np.clip(0.5 * (np.trace(Rr) - 1.0), -1.0, 1.0))
+    k = 0.5 if th < 1e-8 else th / (2.0 * np.sin(th))
+    return np.concatenate([other[9:] - Rr @ origin[9:], k * np.array([Rr[2, 1] - Rr[1, 2], Rr[0, 2] - Rr[2, 0], Rr[1, 0] - Rr[0, 1]])])
+
+
+def prior_vectors(w, CS, code_w=1e-3, codes=None, pose0=None, scale0=None):
+    """Diagonal and gradient additions of the engine's default priors (SageWindowConfig): code prior `code_w` towards zero on
+    every keyframe, scale and pose prior 1e4 on keyframe 0 (code_factor.cpp:55-56,99-104; scale_factor.cpp:122-124;
+    df_work.cpp:24-34).  The initial values are the window's; `codes` [K, CS], `pose0` [R row-major | t] and `scale0` are the
+    current ones where they have moved (after an accepted step): the scale and pose priors then have a gradient."""
+    K, B = len(w.keyframes), 7 + CS
+    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
+    for k, kf in enumerate(w.keyframes):
+        idx = np.arange(k * B + 6, k * B + 6 + CS)
+        dadd[idx] += code_w
+        gadd[idx] += code_w * (0 - (kf.code if codes is None else codes[k]).astype(np.float64))
+    kf0 = w.keyframes[0]
+    s_init = float(kf0.scale)
+    s = s_init if scale0 is None else float(scale0)
+    dadd[6 + CS] += 1e4 / (s * s)
+    dadd[:6] += 1e4
+    if scale0 is not None:
+        gadd[6 + CS] += 1e4 / s * (np.log(s_init) - np.log(s))
+    if pose0 is not None:
+        init = np.concatenate([np.asarray(kf0.R, np.float32).ravel(), np.asarray(kf0.t, np.float32).ravel()])
+        gadd[:6] += 1e4 * pose_local(pose0, init)
+    return dadd, gadd

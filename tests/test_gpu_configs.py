@@ -26,7 +26,7 @@ import pytest
 from tests.conftest import summary_line
 
 from sage_slam_amd import synth
-from tests.helpers import damped_delta, oracle_geo, oracle_photo, rel
+from tests.helpers import damped_delta, oracle_geo, oracle_photo, prior_vectors, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -56,19 +56,6 @@ def add_priors(H, g, w, CS):
     H[6 + CS, 6 + CS] += 1e4 / (s * s)
     H[np.arange(6), np.arange(6)] += 1e4
     return H, g
-
-
-def prior_vectors(w, CS, code_w=1e-3):
-    K, B = len(w.keyframes), 7 + CS
-    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
-    for k, kf in enumerate(w.keyframes):
-        idx = np.arange(k * B + 6, k * B + 6 + CS)
-        dadd[idx] += code_w
-        gadd[idx] += code_w * (0 - kf.code.astype(np.float64))
-    s = float(w.keyframes[0].scale)
-    dadd[6 + CS] += 1e4 / (s * s)
-    dadd[:6] += 1e4
-    return dadd, gadd
 
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -12,7 +12,7 @@ import pytest
 
 from sage_slam_amd import synth
 from tests.conftest import summary_line
-from tests.helpers import damped_delta, oracle_geo, oracle_photo, presample_source, rel
+from tests.helpers import damped_delta, oracle_geo, oracle_photo, presample_source, prior_vectors, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -606,14 +606,7 @@ def test_long_window_lm(capi):
     win.linearize()
     packed = win.packed_host().astype(np.float64)
     B = 7 + CS
-    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
-    for k, kf in enumerate(w.keyframes):
-        idx = np.arange(k * B + 6, k * B + 6 + CS)
-        dadd[idx] += 1e-3
-        gadd[idx] += 1e-3 * (0 - kf.code.astype(np.float64))
-    s = float(w.keyframes[0].scale)
-    dadd[6 + CS] += 1e4 / (s * s)
-    dadd[:6] += 1e4
+    dadd, gadd = prior_vectors(w, CS)
     win.solve(1e-3)
     dref = capi.block_solve(packed[:-4], K, w.links, B, 1e-3, dadd, gadd)
     assert rel(win.delta(), dref) < 1e-7
@@ -716,12 +709,21 @@ def test_full_size_properties(capi, orc, cfg):
 
 
 @pytest.mark.parametrize("CS,K,back,extra", [(32, 6, 2, [(0, 5)]), (16, 7, 3, []), (32, 12, 3, [(0, 11), (2, 9)]),
-                                              (16, 14, 13, [])])   # all-to-all: envelope wider than the device panel
+                                              (16, 14, 13, []),         # all-to-all: every block of the envelope is a link
+                                              (32, 16, 3, []),          # the smallest window the planner splits (K >= 16)
+                                              (16, 18, 3, [(0, 17)])])  # split plan with structural fill blocks
 def test_device_solver_matches_host_cholesky(capi, CS, K, back, extra):
-    """The one-workgroup block-envelope Cholesky (solve_kernels.hip) against the host block Cholesky
-    (sage_block_solve, double) on the SAME packed normal equations, priors and damping: both are fp64 direct
-    solves of a cond ~1e9 system, so they agree to ~cond*eps; also a loop-closure envelope and the padded
-    B = 23 -> 24 case, candidate variables = retract(current, delta), and a second solve with another damping."""
+    """The hybrid solve (solve_kernels.hip: device scatter into pinned block storage, host block Cholesky behind the
+    blocks' tickets, device retract) against the host block Cholesky of the assembled system (sage_block_solve, double)
+    on the SAME packed normal equations, priors and damping: both are fp64 direct solves of a cond ~1e9 system, so they
+    agree to ~cond*eps; also a loop-closure envelope, the padded B = 23 -> 24 case, split plans (two halves and a
+    separator, a ticket per block) without and with fill blocks the device does not deliver, candidate variables =
+    retract(current, delta), a second solve with another damping, and (K = 6) a solve after an accepted step, where
+    the scale and pose priors of keyframe 0 have a gradient.
+    The bound of the K = 16, K = 18 and after-the-step cases is the 1e-7 of the earlier ones: both sides are fp64 direct
+    solves of one system that differ only in rounding order, and the code before the three builders shared one definition
+    met it on each: K = 16 1.7e-8 / 2.7e-9, K = 18 1.0e-8 / 1.6e-9 (damp 1e-3 / 1e-1), after the step 2.9e-8
+    (profiles/solve_system_refactor_ab.txt)."""
     w = synth.make_window(K=K, H=32, W=40, FS=16, CS=CS, L=3, seed=5, back_links=back)
     for lk in extra:
         if lk not in w.links:
@@ -730,14 +732,7 @@ def test_device_solver_matches_host_cholesky(capi, CS, K, back, extra):
     win.linearize()
     packed = win.packed_host().astype(np.float64)
     B = 7 + CS
-    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
-    for k, kf in enumerate(w.keyframes):
-        idx = np.arange(k * B + 6, k * B + 6 + CS)
-        dadd[idx] += 1e-3
-        gadd[idx] += 1e-3 * (0 - kf.code.astype(np.float64))
-    s = float(w.keyframes[0].scale)
-    dadd[6 + CS] += 1e4 / (s * s)
-    dadd[:6] += 1e4                      # pose prior: current == initial pose -> zero gradient
+    dadd, gadd = prior_vectors(w, CS)    # current == initial pose and scale: those priors have no gradient yet
     for damp in (1e-3, 1e-1):
         nrm = win.solve(damp)
         dh = win.delta()
@@ -754,6 +749,17 @@ def test_device_solver_matches_host_cholesky(capi, CS, K, back, extra):
     win.accept()
     pose, code, scale = win.get_keyframe(1)
     assert np.allclose(code, w.keyframes[1].code + win.delta()[B + 6:B + 6 + CS].astype(np.float32), atol=1e-6)
+    if K == 6:
+        # keyframe 0 has moved: its scale and pose priors pull back, with the gradient the device forms from the variables
+        cur = [win.get_keyframe(k) for k in range(K)]
+        dadd, gadd = prior_vectors(w, CS, codes=[c[1] for c in cur], pose0=cur[0][0], scale0=cur[0][2])
+        assert np.abs(gadd[:6]).min() > 0 and gadd[6 + CS] != 0
+        win.linearize()
+        packed = win.packed_host().astype(np.float64)
+        win.solve(1e-3)
+        dref = capi.block_solve(packed[:-4], K, w.links, B, 1e-3, dadd, gadd)
+        print(f"CS {CS} K {K} after an accepted step: device vs host solve rel-L2 {rel(win.delta(), dref):.3e}")
+        assert rel(win.delta(), dref) < 1e-7     # (the bound of the cases above: see the docstring)
     win.close()
 
 

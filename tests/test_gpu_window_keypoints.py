@@ -10,7 +10,7 @@ import pytest
 
 from sage_slam_amd import synth
 from tests.conftest import summary_line
-from tests.helpers import rel
+from tests.helpers import prior_vectors, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -258,14 +258,7 @@ def test_solve_matches_host_block_solve(capi, CS):
     win = capi.Window(w, keypoint_terms=all_terms(w, rep=True, mg_loss="fair"))
     win.linearize()
     packed = win.packed_host().astype(np.float64)
-    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
-    for k, kf in enumerate(w.keyframes):                      # the priors of test_device_solver_matches_host_cholesky
-        idx = np.arange(k * B + 6, k * B + 6 + CS)
-        dadd[idx] += 1e-3
-        gadd[idx] += 1e-3 * (0 - kf.code.astype(np.float64))
-    s = float(w.keyframes[0].scale)
-    dadd[6 + CS] += 1e4 / (s * s)
-    dadd[:6] += 1e4
+    dadd, gadd = prior_vectors(w, CS)
     for damp in (1e-3, 1e-1):
         win.solve(damp)
         d = rel(win.delta(), capi.block_solve(packed[:-4], K, w.links, B, damp, dadd, gadd))

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from sage_slam_amd import capi, synth
-from tests.helpers import oracle_geo, oracle_photo, rel
+from tests.helpers import oracle_geo, oracle_photo, prior_vectors, rel
 
 
 def _free_port():
@@ -89,17 +89,6 @@ def test_two_rank_shard_equals_single_rank(orc, tmp_path):
 SCHUR_WINDOW = dict(K=12, H=16, W=20, FS=16, CS=16, L=2, seed=5, back_links=3, border=1, erode=2)
 
 
-def _schur_priors(w):
-    K, CS, B = len(w.keyframes), w.CS, 7 + w.CS
-    dadd = np.zeros(K * B); gadd = np.zeros(K * B)
-    for k, kf in enumerate(w.keyframes):
-        dadd[k * B + 6:k * B + 6 + CS] = 1e-3
-        gadd[k * B + 6:k * B + 6 + CS] = 1e-3 * (0 - kf.code.astype(np.float64))
-    dadd[:6] += 1e4
-    dadd[6 + CS] += 1e4 / float(w.keyframes[0].scale) ** 2
-    return dadd, gadd
-
-
 def _schur_worker(rank, world, port, out_dir):
     import torch
     import torch.distributed as dist
@@ -110,7 +99,7 @@ def _schur_worker(rank, world, port, out_dir):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     w = synth.make_window(**SCHUR_WINDOW)
     K, CS, B = len(w.keyframes), w.CS, 7 + w.CS
-    dadd, gadd = _schur_priors(w)
+    dadd, gadd = prior_vectors(w, CS)
     owned = capi.shard_links(len(w.links), rank, world)
     packed_local = capi.assemble_packed(K, w.links, CS, _edge_results(orc, w, owned))   # NOT reduced
     plan = capi.ShardPlan(K, w.links, B, rank, world)
@@ -135,7 +124,7 @@ def test_schur_sharded_solve_over_gloo(orc, tmp_path, world):
     mp.spawn(_schur_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     w = synth.make_window(**SCHUR_WINDOW)
     K, CS, B = len(w.keyframes), w.CS, 7 + w.CS
-    dadd, gadd = _schur_priors(w)
+    dadd, gadd = prior_vectors(w, CS)
     full = capi.assemble_packed(K, w.links, CS, _edge_results(orc, w, range(len(w.links))))
     ref = capi.block_solve(full[:-4], K, w.links, B, 1e-3, dadd, gadd)
     merged = np.full(K * B, np.nan)
