@@ -360,6 +360,25 @@ int sage_window_add_link(SageWindow *w, int kf_a, int kf_b);
 /* the Cauchy parameter of ONE link's two geometric edges (before finalize; 0 = the window's geo_loss_param): the mapper
  * derives it per link from the newer keyframe, geo_loss_param_factor * kf->avg_squared_dpt_bias (mapper.cpp:367-373) */
 int sage_window_set_link_geo_loss(SageWindow *w, int link, float loss_param);
+/* a link that carries keypoint terms only (mapper.cpp:393-446 EnqueueLink with a subset of the factor types; the links of
+ * DeepFactors::LoopClosurePoseScaleMGEstimate, core/deepfactors.cpp:388-575): it contributes no photometric or geometric
+ * edge, whatever use_photo / use_geo say, but it is part of the solver's structure and owns a link block of the packed
+ * buffer.  Returns a link id in the numbering of sage_window_add_link, so `edge = 2 * link + direction` addresses its two
+ * directions in sage_window_add_keypoint_term; ownership of those directions on a sharded window follows the same rule as
+ * every other link's.  sage_window_get_edge / sage_window_factor on such a link answer SAGE_E_INVALID.  A window whose links
+ * are all of this kind launches no dense kernel and still assembles, reduces, solves and iterates.  Before finalize
+ * (SAGE_E_STATE afterwards). */
+int sage_window_add_keypoint_link(SageWindow *w, int kf_a, int kf_b);
+/* held variables: the parts of keyframe `kf` named by the mask `what` keep their values through every solve -- their rows
+ * and columns of the damped system are replaced by the identity (no off-diagonal element, right-hand side 0, no prior), so
+ * their delta is exactly zero, the free variables see the system with the held ones eliminated at their current values,
+ * and the candidate copies them bit for bit.  0 clears.  The packed buffer, the all-reduce payload and the per-edge results
+ * are untouched: every factor is still evaluated, and the prior ERROR terms of held variables stay in the total (constants).
+ * sage_window_set_keyframe on a held keyframe still sets it.  Before finalize (SAGE_E_STATE afterwards); SAGE_E_INVALID for
+ * a bad keyframe or mask.  A window that uses the domain-decomposed solve and holds anything answers SAGE_E_UNSUPPORTED at
+ * finalize. */
+enum { SAGE_HOLD_POSE = 1, SAGE_HOLD_CODE = 2, SAGE_HOLD_SCALE = 4 };
+int sage_window_hold(SageWindow *w, int kf, int what);
 /* edge sharding for multi-GPU: this process evaluates the contiguous range [rank*2n/world, (rank+1)*2n/world) of the 2n
  * DIRECTED edges (edge 2l = link l a -> b, 2l + 1 = b -> a, links in the order they were added; both factor types of a
  * direction together) -- r05: the two directions of a link may sit on two ranks (42 links on 8 ranks are 5 or 6 each, 84
@@ -374,7 +393,7 @@ int sage_window_num_links(const SageWindow *w);
 int sage_window_block_size(const SageWindow *w);       /* B = 7 + CS: [pose6, code CS, scale] */
 /* packed normal-equation buffer (device, DOUBLE), the all-reduce payload:
  *   [ diag blocks K*B*B | link blocks nlinks*B*B (row = older kf, col = newer kf) | g K*B | err_photo err_geo n_photo n_geo ]
- * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry terms';
+ * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry and loop-MG terms';
  * the two inlier counts stay dense-only -- see sage_window_add_keypoint_term)
  * fp32 per-edge results are summed in double, like the reference widens AtA/Atb to double before gtsam adds
  * the factors (core/gtsam/photometric_factor.cpp:305-306); keeping the payload in double keeps the sum exact
@@ -382,7 +401,7 @@ int sage_window_block_size(const SageWindow *w);       /* B = 7 + CS: [pose6, co
 size_t sage_window_packed_count(const SageWindow *w);
 double *sage_window_packed_dev(SageWindow *w);
 /* number of residuals one linearize evaluates on this shard (E_photo*L*N*FS + E_geo*N, + 2N / 3N per reprojection /
- * match-geometry term) and its algorithmic bytes (dense factors) */
+ * match-geometry / loop-MG term) and its algorithmic bytes (dense factors) */
 double sage_window_residuals_per_linearize(const SageWindow *w);
 double sage_window_bytes_per_linearize(const SageWindow *w);
 
@@ -433,6 +452,11 @@ int sage_window_get_edge(const SageWindow *w, int type, int e, float *AtA, float
  *   kind SAGE_KP_REPROJECTION    fair loss, D = 13+CS [pose0 pose1 code0 scale0] (the photometric edge layout), 2N residuals
  *   kind SAGE_KP_MATCH_GEOMETRY  loss SAGE_LOSS_*, D = 14+2CS [pose0 pose1 code0 code1 scale0 scale1] (the geometric edge
  *                                layout), 3N residuals
+ *   kind SAGE_KP_LOOP_MG         fair loss, D = 14 [pose0 pose1 scale0 scale1], 3N residuals: match geometry with the depths
+ *                                fixed at graph-build time (LoopMGFactor, core/deepfactors.cpp:388-575; the arithmetic of
+ *                                sage_loop_mg_jac_error_calculate).  The two unscaled depth arrays are the caller's; poses
+ *                                and scales are the window's.  loc1d_0, matched_loc1d_1 and loss are ignored (may be NULL /
+ *                                0); loss_param > 0.  No code row or column of the system receives anything from it.
  * `edge` = 2 * link + direction as sage_window_get_edge numbers them; keyframe "0" is the direction's source.  Camera =
  * cfg.pyr.cam[0], eps = cfg.eps; bias / basis / code / scale / pose are the window's keyframes' at the variable set being
  * evaluated.  Add after the edge's link and before sage_window_finalize (SAGE_E_STATE afterwards); any number of terms per
@@ -442,12 +466,12 @@ int sage_window_get_edge(const SageWindow *w, int type, int e, float *AtA, float
  * the add calls of the whole window.  On a sharded window a term belongs to the rank that owns its directed edge (settled at
  * finalize: add and sage_window_set_shard may come in either order); reading a term of another rank answers SAGE_E_INVALID.
  * get_keypoint_term: host copy of the term's last linearize in the reference's per-edge layout (AtA [D,D], Atb [D], error;
- * n_in = inliers for reprojection, N for match geometry); SAGE_E_STATE before the first linearize.
+ * n_in = inliers for reprojection, N for match geometry and loop-MG); SAGE_E_STATE before the first linearize.
  * Totals: the terms' errors ride in the two error slots of the 4-double tails (packed buffer, error buffer) -- reprojection in
- * the photometric slot, match geometry in the geometric one: slot 0 + slot 1 = sum of dense + sum of keypoint errors.  The
- * inlier slots stay dense-only.  Not covered: the gtsam factor cache (sage_window_prepass / sage_window_factor serve the dense
- * factors only), the loop-closure variant with fixed depths, links that carry keypoint terms but no dense factor. */
-enum { SAGE_KP_REPROJECTION = 0, SAGE_KP_MATCH_GEOMETRY = 1 };
+ * the photometric slot, match geometry and loop-MG in the geometric one: slot 0 + slot 1 = sum of dense + sum of keypoint
+ * errors.  The inlier slots stay dense-only.  Not covered: the gtsam factor cache (sage_window_prepass / sage_window_factor
+ * serve the dense factors only). */
+enum { SAGE_KP_REPROJECTION = 0, SAGE_KP_MATCH_GEOMETRY = 1, SAGE_KP_LOOP_MG = 2 };
 typedef struct SageKeypointTerm
 {
   int32_t kind;                   /* SAGE_KP_*                                                          */
@@ -460,6 +484,7 @@ typedef struct SageKeypointTerm
   const float *matched_homo1;     /* match geometry: [N,3] device                                       */
   float loss_param, weight;
   int32_t loss;                   /* match geometry: SAGE_LOSS_*; ignored for reprojection              */
+  const float *unscaled_dpts0, *matched_unscaled_dpts1; /* loop-MG: [N] device each, depths before their keyframe's scale */
 } SageKeypointTerm;
 int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTerm *t);
 int sage_window_num_keypoint_terms(const SageWindow *w);

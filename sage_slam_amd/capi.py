@@ -70,13 +70,22 @@ class SageWindowConfig(C.Structure):
                 ("use_photo", C.c_int32), ("use_geo", C.c_int32)]
 
 
-SAGE_KP_REPROJECTION, SAGE_KP_MATCH_GEOMETRY = 0, 1
+SAGE_KP_REPROJECTION, SAGE_KP_MATCH_GEOMETRY, SAGE_KP_LOOP_MG = 0, 1, 2
+SAGE_HOLD_POSE, SAGE_HOLD_CODE, SAGE_HOLD_SCALE = 1, 2, 4
+KP_KINDS = {"reprojection": SAGE_KP_REPROJECTION, "match_geometry": SAGE_KP_MATCH_GEOMETRY, "loop_mg": SAGE_KP_LOOP_MG}
 
 
 class SageKeypointTerm(C.Structure):
     _fields_ = [("kind", C.c_int32), ("edge", C.c_int32), ("N", C.c_int32), ("loc1d_0", C.c_void_p), ("homo0", C.c_void_p),
                 ("matched_2d", C.c_void_p), ("matched_loc1d_1", C.c_void_p), ("matched_homo1", C.c_void_p),
-                ("loss_param", C.c_float), ("weight", C.c_float), ("loss", C.c_int32)]
+                ("loss_param", C.c_float), ("weight", C.c_float), ("loss", C.c_int32), ("unscaled_dpts0", C.c_void_p),
+                ("matched_unscaled_dpts1", C.c_void_p)]
+
+
+def kp_term_dim(kind, CS: int) -> int:
+    """system size D of a window keypoint term by kind (name or SAGE_KP_*)"""
+    kind = KP_KINDS.get(kind, kind)
+    return {SAGE_KP_REPROJECTION: 13 + CS, SAGE_KP_MATCH_GEOMETRY: 14 + 2 * CS, SAGE_KP_LOOP_MG: 14}[kind]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -101,7 +110,7 @@ SYMBOLS = [
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
     "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame",
-    "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_set_link_geo_loss",
+    "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
     "sage_window_block_size", "sage_window_packed_count", "sage_window_packed_dev",
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
@@ -498,11 +507,17 @@ class Window:
     """``SageWindow``: batched K-keyframe BA window on one GPU (one shard of the edge set)."""
 
     def __init__(self, win, rank: int = 0, world: int = 1, stream=None, use_photo=True, use_geo=True,
-                 code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None):
-        """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches``,
-        or by hand): kind ("reprojection" | "match_geometry"), edge (2 * link + direction), loc0 [N] int32, homo0 [N,3],
-        matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry, loss (a MG_LOSS name).
-        They are added before the finalize this constructor performs."""
+                 code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None,
+                 keypoint_links=None, holds=None):
+        """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches`` /
+        ``make_loop_mg_*``, or by hand): kind ("reprojection" | "match_geometry" | "loop_mg"), edge (2 * link + direction),
+        loc0 [N] int32, homo0 [N,3], matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry,
+        loss (a MG_LOSS name); loop_mg: homo0, homo1 and the unscaled depths u0 [N], u1 [N].
+        ``keypoint_links``: optional list of (a, b), links that carry keypoint terms only (``sage_window_add_keypoint_link``);
+        they are added after the window's dense links, so their ids start at ``len(win.links)`` (``self.links`` lists both;
+        a ``win`` with ``links=[]`` gives a window without a dense edge).
+        ``holds``: optional dict keyframe -> mask of SAGE_HOLD_* (``sage_window_hold``).
+        All are added before the finalize this constructor performs."""
         import torch
         self.win = win
         self.pyr = make_pyramid(win.cams[0], win.L)
@@ -538,6 +553,14 @@ class Window:
             gl = getattr(win, "link_geo_loss", None)     # optional per-link Cauchy parameters (mapper.cpp:367-373)
             if gl is not None and gl[r] > 0:
                 _chk(L.sage_window_set_link_geo_loss(self.h, r, C.c_float(gl[r])), "sage_window_set_link_geo_loss")
+        kp_links = [tuple(l) for l in (keypoint_links or [])]
+        for a, b in kp_links:
+            r = self.add_keypoint_link(a, b)
+            if r < 0:
+                raise SageError(r, "sage_window_add_keypoint_link")
+        self.links = [(min(a, b), max(a, b)) for a, b in list(win.links) + kp_links]
+        for kf, what in sorted((holds or {}).items()):
+            _chk(self.hold(kf, what), "sage_window_hold")
         self.keypoint_terms = list(keypoint_terms or [])
         for t in self.keypoint_terms:
             r = self.add_keypoint_term(t)
@@ -552,19 +575,36 @@ class Window:
         self.residuals_per_linearize = L.sage_window_residuals_per_linearize(self.h)
         self.bytes_per_linearize = L.sage_window_bytes_per_linearize(self.h)
 
+    def add_keypoint_link(self, a, b) -> int:
+        """``sage_window_add_keypoint_link`` -> link id, or the negative status code"""
+        return int(lib().sage_window_add_keypoint_link(self.h, int(a), int(b)))
+
+    def hold(self, kf, what) -> int:
+        """``sage_window_hold`` -> status code"""
+        return int(lib().sage_window_hold(self.h, int(kf), int(what)))
+
     def add_keypoint_term(self, t) -> int:
         """``sage_window_add_keypoint_term`` with the arrays of dict ``t`` uploaded for the call (the engine copies them);
         returns the term id, or the negative status code."""
         import torch
-        kind = {"reprojection": SAGE_KP_REPROJECTION, "match_geometry": SAGE_KP_MATCH_GEOMETRY}.get(t["kind"], t["kind"])
-        mg = "loc1" in t
-        N = int(np.asarray(t["loc0"]).shape[0])
-        dev = dict(loc0=_dev(t["loc0"], np.int32), homo0=_dev(t["homo0"], np.float32))
+        kind = KP_KINDS.get(t["kind"], t["kind"])
+        lmg = kind == SAGE_KP_LOOP_MG
+        mg = "loc1" in t and not lmg
+        N = int(np.asarray(t["homo0"]).shape[0])
+        dev = dict(homo0=_dev(t["homo0"], np.float32))
         kt = SageKeypointTerm()
         kt.kind = int(kind)
         kt.edge, kt.N = int(t["edge"]), N
-        kt.loc1d_0, kt.homo0 = dev["loc0"].data_ptr(), dev["homo0"].data_ptr()
-        if mg:
+        kt.homo0 = dev["homo0"].data_ptr()
+        if not lmg:
+            dev["loc0"] = _dev(t["loc0"], np.int32)
+            kt.loc1d_0 = dev["loc0"].data_ptr()
+        if lmg:                                           # (a missing array stays NULL: the engine answers SAGE_E_INVALID)
+            for key, field in (("homo1", "matched_homo1"), ("u0", "unscaled_dpts0"), ("u1", "matched_unscaled_dpts1")):
+                if t.get(key) is not None:
+                    dev[key] = _dev(t[key], np.float32)
+                    setattr(kt, field, dev[key].data_ptr())
+        elif mg:
             dev["loc1"] = _dev(t["loc1"], np.int32); dev["homo1"] = _dev(t["homo1"], np.float32)
             kt.matched_loc1d_1, kt.matched_homo1 = dev["loc1"].data_ptr(), dev["homo1"].data_ptr()
             loss = t.get("loss", "fair")
@@ -583,8 +623,7 @@ class Window:
         """host copy of term i's last linearize -> dict(AtA [D,D], Atb [D], error, num_inliers); with ``check=False`` the
         status code is returned next to the dict instead of raising."""
         kind = self.keypoint_terms[i]["kind"] if 0 <= i < len(self.keypoint_terms) else "reprojection"
-        mg = kind in ("match_geometry", SAGE_KP_MATCH_GEOMETRY)
-        D = 14 + 2 * self.win.CS if mg else 13 + self.win.CS
+        D = kp_term_dim(kind, self.win.CS)
         A = np.zeros((D, D), np.float32); b = np.zeros(D, np.float32)
         err = C.c_float(); nin = C.c_float()
         rc = lib().sage_window_get_keypoint_term(self.h, int(i), _fp(A), _fp(b), C.byref(err), C.byref(nin))
@@ -888,9 +927,13 @@ def shard_edges(nlinks: int, rank: int, world: int) -> List[int]:
 
 
 def edge_col(type_: int, role: int, bi: int, CS: int) -> int:
-    """B-index (pose 6, code CS, scale) -> column of the per-edge system (mirror of the assemble kernel)."""
+    """B-index (pose 6, code CS, scale) -> column of the per-edge system (mirror of the assemble kernel).  type 0: the
+    photometric edge's layout (and the reprojection term's), 1: the geometric edge's (match-geometry term's), 2: the loop-MG
+    term's D = 14 [pose0 pose1 scale0 scale1] -- code rows absent."""
     if bi < 6:
         return role * 6 + bi
+    if type_ == 2:
+        return 12 + role if bi == 6 + CS else -1
     if type_ == 0:
         if role == 1:
             return -1
@@ -902,14 +945,15 @@ def edge_col(type_: int, role: int, bi: int, CS: int) -> int:
 
 def assemble_packed(K: int, links: Sequence, CS: int, edge_results: dict) -> np.ndarray:
     """Sum per-edge normal equations into the packed block layout.
-    ``edge_results[(type, link, dir)] = dict(AtA, Atb, error, num_inliers)`` for the edges present."""
+    ``edge_results[(type, link, dir)] = dict(AtA, Atb, error, num_inliers)`` for the edges present; type as ``edge_col``
+    takes it (2: a loop-MG term's 14 x 14 result; its error and count go to the geometric slots of the tail)."""
     B = 7 + CS
     BB = B * B
     diag = np.zeros((K, B, B), np.float64)
     lnk = np.zeros((len(links), B, B), np.float64)
     g = np.zeros((K, B), np.float64)
     tail = np.zeros(4, np.float64)
-    cols = {(t, r): np.array([edge_col(t, r, bi, CS) for bi in range(B)]) for t in (0, 1) for r in (0, 1)}
+    cols = {(t, r): np.array([edge_col(t, r, bi, CS) for bi in range(B)]) for t in (0, 1, 2) for r in (0, 1)}
     for (t, l, d), res in edge_results.items():
         a, b = links[l]
         k0, k1 = (a, b) if d == 0 else (b, a)
@@ -924,8 +968,8 @@ def assemble_packed(K: int, links: Sequence, CS: int, edge_results: dict) -> np.
         ca, cb = cols[(t, ra)], cols[(t, rb)]
         ma, mb = ca >= 0, cb >= 0
         lnk[l][np.ix_(ma, mb)] += A[np.ix_(ca[ma], cb[mb])]
-        tail[t] += res["error"]
-        tail[2 + t] += res["num_inliers"]
+        tail[min(t, 1)] += res["error"]
+        tail[2 + min(t, 1)] += res["num_inliers"]
     return np.concatenate([diag.reshape(-1), lnk.reshape(-1), g.reshape(-1), tail])
 
 

@@ -5,11 +5,16 @@
 //
 //   A = H + P + damp * diag(H + P)     H: packed [K diag blocks | link blocks | gradient] (double), P: diagonal priors
 //
+// Held variables (sage_window_hold): a held row / column of A is the identity's -- no off-diagonal element in its diagonal
+// block or its link blocks, diagonal 1, right-hand side 0, no prior -- so its delta is exactly zero and the free rows see
+// the system with the held variables eliminated at their current values; the retraction copies held entries bit for bit.
+//
 // The three builders of A's block storage keep their own iteration (per block on the device, per keyframe and per link
 // with accumulation of duplicate links in sage_block_solve, local positions and ownership of priors in the shard); what
 // an element is and where it goes is decided here.
 #pragma once
 #include <cmath>
+#include <cstddef>
 
 #if defined(__HIPCC__)
 #define SAGE_HD __host__ __device__
@@ -86,6 +91,18 @@ SAGE_HD inline void pose_retract(const float *pose, const float *d, float *out)
   }
 }
 
+// ---- held variables: a keyframe's mask of SAGE_HOLD_POSE = 1, SAGE_HOLD_CODE = 2, SAGE_HOLD_SCALE = 4 ----
+enum : int { kHoldPose = 1, kHoldCode = 2, kHoldScale = 4, kHoldAll = 7 };
+
+// is row r of a keyframe's block (rows: pose 6, code CS, scale) held under `hold`?
+SAGE_HD inline bool row_held(int hold, int r, int CS)
+{
+  return (hold & (r < 6 ? kHoldPose : (r < 6 + CS ? kHoldCode : kHoldScale))) != 0;
+}
+
+// element (r, c) of a diagonal block where row r or column c is held
+SAGE_HD inline double held_diag_elem(int r, int c) { return r == c ? 1.0 : 0.0; }
+
 // ---- priors (a9): code prior on every keyframe (zero prior mean), scale / pose priors on keyframe 0 ----
 struct SolvePriors
 {
@@ -95,12 +112,14 @@ struct SolvePriors
 };
 
 // what the priors add to row r of keyframe kf (rows: pose 6, code CS, scale), given that keyframe's current variables:
-// da on the diagonal of H, ga on the gradient
+// da on the diagonal of H, ga on the gradient; nothing on a row held under the keyframe's mask `hold`
 SAGE_HD inline void prior_row(const SolvePriors &pri, int kf, int r, int CS, const float *pose, float scale,
-                              const float *code, double &da, double &ga)
+                              const float *code, double &da, double &ga, int hold = 0)
 {
   da = 0.0;
   ga = 0.0;
+  if (hold && row_held(hold, r, CS))
+    return;
   if (r >= 6 && r < 6 + CS)
   {
     da = pri.code_w;
@@ -143,5 +162,37 @@ SAGE_HD inline int stored_slot(int r, int c, int Bp) { return c * Bp + r; }
 
 // ... and comes from this element of the packed link block (a, b), a < b, which is [row in a][column in b]
 SAGE_HD inline int link_elem(bool row_is_a, int r, int c, int B) { return row_is_a ? r * B + c : c * B + r; }
+
+// ---- the held rule on a host copy of the packed system and its prior vectors, for the host block solve (the device
+//      path applies the same element rules while it scatters): hold [K] masks, links [nlinks][2] ----
+inline void hold_packed(double *packed, double *dadd, double *gadd, int K, int nlinks, const int *links, int B, int CS,
+                        const unsigned char *hold)
+{
+  const int BB = B * B;
+  double *lnk = packed + (size_t)K * BB, *g = lnk + (size_t)nlinks * BB;
+  for (int k = 0; k < K; ++k)
+  {
+    if (!hold[k])
+      continue;
+    double *D = packed + (size_t)k * BB;
+    for (int r = 0; r < B; ++r)
+      for (int c = 0; c < B; ++c)
+        if (row_held(hold[k], r, CS) || row_held(hold[k], c, CS))
+          D[r * B + c] = held_diag_elem(r, c);
+    for (int r = 0; r < B; ++r)
+      if (row_held(hold[k], r, CS))
+        g[(size_t)k * B + r] = dadd[(size_t)k * B + r] = gadd[(size_t)k * B + r] = 0.0;
+  }
+  for (int l = 0; l < nlinks; ++l)
+  {
+    const int ha = hold[links[2 * l]], hb = hold[links[2 * l + 1]];
+    if (!ha && !hb)
+      continue;
+    for (int r = 0; r < B; ++r) // [row in a][column in b]
+      for (int c = 0; c < B; ++c)
+        if (row_held(ha, r, CS) || row_held(hb, c, CS))
+          lnk[(size_t)l * BB + r * B + c] = 0.0;
+  }
+}
 
 } // namespace sage

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "sage_ba.h"
 
 namespace sage
@@ -70,7 +72,8 @@ hipError_t launch_match_geom(hipStream_t s, int mode, int CS, bool jac, const Mg
 constexpr int kKpChunk = 64; // keypoints whose weighted rows sit in LDS at a time
 
 // one term = one workgroup.  kind 0 reprojection (D = 13+CS, the photometric edge layout), 1 match geometry (D = 14+2CS,
-// the geometric edge layout).  All arrays engine-owned (copied at add / finalize), keyframe data the window's own.
+// the geometric edge layout), 2 loop-MG (D = 14: match geometry at fixed depths, poses and scales only).  All arrays
+// engine-owned (copied at add / finalize), keyframe data the window's own.
 struct KpTerm
 {
   int32_t kind, loss, N;
@@ -81,6 +84,7 @@ struct KpTerm
   const int32_t *loc0, *loc1;           // [N]; loc1: match geometry
   const float *homo0, *homo1, *matched; // [N,3], [N,3] (match geometry), [N,2] (reprojection)
   const float *bias0, *basis0, *bias1, *basis1;
+  const float *dpts0, *dpts1; // [N] each, unscaled (loop-MG)
 };
 
 struct KpBatchParams
@@ -90,19 +94,27 @@ struct KpBatchParams
   int VS;
   SageCamera cam;
   float eps;
-  float *AtA_r, *Atb_r, *AtA_m, *Atb_m; // per kind [n][D*D], [n][D] (linearize only)
+  float *AtA_r, *Atb_r, *AtA_m, *Atb_m, *AtA_l, *Atb_l; // per kind [n][D*D], [n][D] (linearize only)
   float *stats;                         // [n_terms][2] = {error, inliers}
 };
 
-// dynamic LDS of the batched kernel: the chunk's rows, stride padded to four floats
-inline size_t kp_batch_lds_bytes(int CS, bool any_match_geometry)
+// system size and rows per keypoint of a window term by kind (SAGE_KP_*)
+constexpr int kp_kind_dim(int kind, int CS) { return kind == 0 ? reproj_dim(0, CS) : (kind == 1 ? mg_dim(0, CS) : mg_dim(1, CS)); }
+constexpr int kp_kind_rows(int kind) { return kind == 0 ? kReprojRows : kMgRows; }
+constexpr int kKpKinds = 3;
+
+// dynamic LDS of the batched kernel: a chunk's rows, stride padded to four floats -- the largest over the kinds PRESENT
+// among the launch's terms (kinds: bit k = a term of kind k; CS = 32: 24 KB, 60 KB, 12 KB)
+inline size_t kp_batch_lds_bytes(int CS, unsigned kinds)
 {
-  const int D = any_match_geometry ? mg_dim(0, CS) : reproj_dim(0, CS), rpp = any_match_geometry ? kMgRows : kReprojRows;
-  return (size_t)kKpChunk * rpp * (size_t)((D + 1 + 3) / 4 * 4) * sizeof(float);
+  size_t bytes = 0;
+  for (int kind = 0; kind < kKpKinds; ++kind)
+    if (kinds & (1u << kind))
+      bytes = std::max(bytes, (size_t)kKpChunk * kp_kind_rows(kind) * (size_t)((kp_kind_dim(kind, CS) + 1 + 3) / 4 * 4) * sizeof(float));
+  return bytes;
 }
 
 // every local term of a window in ONE launch (a workgroup per term); jac = false: errors and inlier counts only
-hipError_t launch_keypoint_batch(hipStream_t s, int CS, bool jac, int n_terms, bool any_match_geometry,
-                                 const KpBatchParams &p);
+hipError_t launch_keypoint_batch(hipStream_t s, int CS, bool jac, int n_terms, unsigned kinds, const KpBatchParams &p);
 
 } // namespace sage

@@ -137,7 +137,11 @@ struct MatchGeomFactor
   static constexpr int D = mg_dim(MODE, CS), RPP = kMgRows;
   static constexpr bool kSmall = D * (D + 1) <= 256;
 
-  template <bool JAC, int LD = 0>
+  // FINE: the fair loss's error as n - log1p(n).  In fp32 `1 + n` rounds by 6e-8, which is all there is of n - log(1 + n)
+  // once n < 3e-4: an LM iteration on terms whose residuals vanish at the solution (a pose graph over exact depths) then
+  // compares rounding noise and stops 1e-5 short of it.  The window's loop-MG terms ask for it; the per-edge operators keep
+  // the reference's expression
+  template <bool JAC, int LD = 0, bool FINE = false>
   static __device__ __forceinline__ void rows(const Params &p, int idx)
   {
     constexpr int RS = LD ? LD : D + 1;
@@ -207,7 +211,7 @@ struct MatchGeomFactor
       for (int i = 0; i < 3; ++i)
       {
         const float n = fabsf(diff[i]) / sl;
-        err += n - logf(1.0f + n);
+        err += FINE ? n - log1pf(n) : n - logf(1.0f + n);
         sw[i] = sqrtf(1.0f / (p.loss_param * (1.0f + n)));
       }
       err *= 2.0f;
@@ -616,10 +620,10 @@ hipError_t launch_cycle_match(hipStream_t s, const float *desc0, const float *de
 // window terms (sage_window_add_keypoint_term): every local term of a window in ONE launch, a workgroup per term.
 // The per-edge operators above write the weighted rows to memory and contract them in a second launch (D workgroups);
 // here the rows of kKpChunk keypoints at a time stay in LDS (stride padded to four floats: 64 x 2 x 48 floats = 24 KB for
-// reprojection at CS = 32, 64 x 3 x 80 = 60 KB for match geometry) and are contracted into per-thread 4 x 4 register tiles of
+// reprojection at CS = 32, 64 x 3 x 80 = 60 KB for match geometry, 64 x 3 x 16 = 12 KB for loop-MG) and are contracted into per-thread 4 x 4 register tiles of
 // [AtA | Atb] that live across the chunks: two 16-byte LDS reads per 16 multiply-adds.  Only the tiles on and above the
-// diagonal are formed (CS = 32: 78 / 210 of them, so 256 / tiles row groups share a chunk's rows) and mirrored on the way
-// out.  Sums in double, every order fixed (rows ascending per group, groups ascending, lanes by shuffle): no atomics,
+// diagonal are formed (CS = 32: 78 / 210 of them, loop-MG: 10, so 256 / tiles row groups share a chunk's rows -- 3, 1 and
+// 25, threads 250-255 idle) and mirrored on the way out.  Sums in double, every order fixed (rows ascending per group, groups ascending, lanes by shuffle): no atomics,
 // bit-reproducible.  weight / n_inliers, the 10 * weight fallback and the statistics are folded in by the same workgroup.
 // The relative pose is formed here from the window's variable array, as the dense kernels do.
 // ------------------------------------------------------------------------------------------------
@@ -627,7 +631,8 @@ template <int CS, int KIND, bool JAC>
 __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams &prm, const float *s_pose, float *s_rows,
                                             float *s_err, float *s_val, double *s_red)
 {
-  using F = std::conditional_t<KIND == 0, ReprojFactor<CS, 0>, MatchGeomFactor<CS, 0>>;
+  // KIND 2: the loop variant (MatchGeomFactor mode 1) -- poses and scales from the window, depths from the term
+  using F = std::conditional_t<KIND == 0, ReprojFactor<CS, 0>, MatchGeomFactor<CS, KIND == 2 ? 1 : 0>>;
   constexpr int D = F::D, RPP = F::RPP;
   constexpr int LD = (D + 1 + 3) / 4 * 4;
   constexpr int NT = LD / 4;               // tiles per side (rows past D are dropped on the way out)
@@ -651,7 +656,7 @@ __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams
     mp.R10 = s_pose; mp.t10 = s_pose + 9; mp.R0 = x0; mp.t0 = x0 + 9; mp.R1 = x1; mp.t1 = x1 + 9;
     mp.bias0 = T.bias0; mp.bias1 = T.bias1; mp.basis0 = T.basis0; mp.basis1 = T.basis1;
     mp.code0 = x0 + 13; mp.code1 = x1 + 13; mp.scale0 = x0[12]; mp.scale1 = x1[12];
-    mp.loss_param = T.loss_param; mp.weight = T.weight; mp.loss = T.loss;
+    mp.loss_param = T.loss_param; mp.weight = T.weight; mp.loss = KIND == 2 ? 0 : T.loss;
     mp.rows = s_rows; mp.serr = s_err; mp.sval = s_val;
   }
   // this thread's tile (ti <= tj) and row group
@@ -686,9 +691,17 @@ __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams
       }
       else
       {
-        mp.loc0 = T.loc0 + c0; mp.loc1 = T.loc1 + c0; mp.homo0 = T.homo0 + (size_t)3 * c0; mp.homo1 = T.homo1 + (size_t)3 * c0;
+        if (KIND == 2)
+        {
+          mp.dpts0 = T.dpts0 + c0; mp.dpts1 = T.dpts1 + c0;
+        }
+        else
+        {
+          mp.loc0 = T.loc0 + c0; mp.loc1 = T.loc1 + c0;
+        }
+        mp.homo0 = T.homo0 + (size_t)3 * c0; mp.homo1 = T.homo1 + (size_t)3 * c0;
         mp.N = cnt;
-        MatchGeomFactor<CS, 0>::template rows<JAC, LD>(mp, tid);
+        MatchGeomFactor<CS, KIND == 2 ? 1 : 0>::template rows<JAC, LD, KIND == 2>(mp, tid);
       }
       if (JAC)
         for (int r = 0; r < RPP; ++r) // the padding columns take part in the tiles: keep them finite
@@ -764,8 +777,8 @@ __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams
   }
   if (grp != 0)
     return;
-  float *AtA = (KIND == 0 ? prm.AtA_r : prm.AtA_m) + (size_t)T.out * D * D;
-  float *Atb = (KIND == 0 ? prm.Atb_r : prm.Atb_m) + (size_t)T.out * D;
+  float *AtA = (KIND == 0 ? prm.AtA_r : (KIND == 1 ? prm.AtA_m : prm.AtA_l)) + (size_t)T.out * D * D;
+  float *Atb = (KIND == 0 ? prm.Atb_r : (KIND == 1 ? prm.Atb_m : prm.Atb_l)) + (size_t)T.out * D;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -806,15 +819,17 @@ __global__ __launch_bounds__(256) void keypoint_batch_kernel(const KpBatchParams
   __syncthreads();
   if (T.kind == SAGE_KP_REPROJECTION)
     kp_term_run<CS, 0, JAC>(T, prm, s_pose, s_dyn, s_err, s_val, s_red);
-  else
+  else if (T.kind == SAGE_KP_MATCH_GEOMETRY)
     kp_term_run<CS, 1, JAC>(T, prm, s_pose, s_dyn, s_err, s_val, s_red);
+  else
+    kp_term_run<CS, 2, JAC>(T, prm, s_pose, s_dyn, s_err, s_val, s_red);
 }
 
-hipError_t launch_keypoint_batch(hipStream_t s, int CS, bool jac, int n_terms, bool any_match_geometry, const KpBatchParams &p)
+hipError_t launch_keypoint_batch(hipStream_t s, int CS, bool jac, int n_terms, unsigned kinds, const KpBatchParams &p)
 {
   if (n_terms <= 0)
     return hipSuccess;
-  const size_t lds = jac ? kp_batch_lds_bytes(CS, any_match_geometry) : 0; // (the error variant forms no rows)
+  const size_t lds = jac ? kp_batch_lds_bytes(CS, kinds) : 0; // (the error variant forms no rows)
   if (CS == 32)
   {
     if (jac)

@@ -203,8 +203,9 @@ namespace sage
 {
 struct AdjEntry // one (edge, role) incidence of a keyframe
 {
-  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1)
-  int32_t edge; // local edge index; types 2 / 3: index among the local terms of the kind
+  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1); 4 loop-MG term
+                // (its own column map: poses and scales only)
+  int32_t edge; // local edge index; types 2 / 3 / 4: index among the local terms of the kind
   int32_t role; // 0: keyframe is the edge's source ("0"), 1: destination ("1")
 };
 
@@ -228,16 +229,16 @@ struct AssembleParams
   const int32_t *blocks;   // optional: the output blocks to assemble (ids 0..K-1 keyframes, K..K+nlinks-1 links, K+nlinks tail)
   // keypoint terms (null / 0 without them): per-kind results, {error, inliers} of all local terms (reprojection first), and
   // per link the terms on its two directions (AdjEntry::role = direction)
-  const float *AtA_kr, *Atb_kr, *AtA_km, *Atb_km, *stats_k;
+  const float *AtA_kr, *Atb_kr, *AtA_km, *Atb_km, *AtA_kl, *Atb_kl, *stats_k;
   const int32_t *link_kp_start; // [nlinks+1]
   const AdjEntry *link_kp;
-  int n_kr, n_km;
+  int n_kr, n_km, n_kl;
 };
 
-struct KpTotals // error pass: the local terms' {error, inliers}, reprojection first
+struct KpTotals // error pass: the local terms' {error, inliers}: reprojection, match geometry, loop-MG
 {
   const float *stats;
-  int n_kr, n_km;
+  int n_kr, n_km, n_kl;
 };
 
 struct ErrorTotalsSide
@@ -265,10 +266,15 @@ struct SageWindow
   HostVars hv;                      // host variables of both sets, their initial values
   std::vector<float> link_geo_loss; // per link: the geometric factors' Cauchy parameter, 0 = cfg.geo_loss_param
   std::vector<std::pair<int, int>> links; // (a, b) with a < b
+  std::vector<char> link_dense;           // per link: 1 = carries the dense factors (sage_window_add_link), 0 = keypoint
+                                          // terms only (sage_window_add_keypoint_link)
+  std::vector<uint8_t> hold;              // per keyframe: mask of held variables (sage_window_hold), empty = none
   std::vector<int> local_links;           // indices into links (links with at least one local directed edge)
-  std::vector<int> local_edges;           // this rank's directed edges, global ids 2 * link + direction, ascending (local edge
-                                          // index = position in this list; a single-rank window: the identity)
-  int n_edges = 0;                        // local directed edges per factor type (= 2 * local links)
+  std::vector<int> owned_edges;           // this rank's directed edges, global ids 2 * link + direction, ascending: whose
+                                          // keypoint terms it evaluates
+  std::vector<int> local_edges;           // ... those of them that carry dense factors (plan::dense_edges; local edge index
+                                          // = position in this list; a single-rank window of dense links: the identity)
+  int n_edges = 0;                        // local DENSE directed edges per factor type
   // device
   DevBuf vars[2];                       // [K][VS]: pose 12, scale 1, code CS
   DevBuf sorted_loc, sorted_homo;       // raster-ordered copies of the keyframes' sampled locations
@@ -309,14 +315,18 @@ struct SageWindow
     int32_t kind, edge, N, loss;
     float loss_param, weight;
     std::vector<int32_t> loc0, loc1;
-    std::vector<float> homo0, second; // second: matched_2d [N,2] (reprojection) or matched_homo1 [N,3] (match geometry)
+    std::vector<float> homo0, second; // second: matched_2d [N,2] (reprojection) or matched_homo1 [N,3] (match geometry, loop-MG)
+    std::vector<float> dpts0, dpts1;  // loop-MG: the unscaled depths [N]
   };
   std::vector<KeypointTermHost> kp_added;
   std::vector<int> kp_local;            // per term id: index among this rank's terms, -1 = another rank's
-  int n_kr = 0, n_km = 0;               // local reprojection / match-geometry terms
+  int n_kr = 0, n_km = 0, n_kl = 0;     // local reprojection / match-geometry / loop-MG terms
+  int n_terms() const { return n_kr + n_km + n_kl; }
+  unsigned kp_kinds() const { return (n_kr > 0 ? 1u : 0u) | (n_km > 0 ? 2u : 0u) | (n_kl > 0 ? 4u : 0u); }
   bool kp_lin = false;                  // the terms have been linearized at least once
   DevBuf kp_pool, kp_table, kp_link_start, kp_link;
-  DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, stats_k; // stats_k: [2][n_kr + n_km][2] -- last linearize, last error pass
+  DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, AtA_kl, Atb_kl; // per kind [n][D * D], [n][D]
+  DevBuf stats_k;                       // [2][n_terms][2] -- last linearize, last error pass; reprojection, match geometry, loop-MG
   // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
   // (all K keyframes) they were evaluated at
   struct FactorCache
@@ -354,7 +364,9 @@ static int upload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
 }
 // window.hip
 int window_upload_vars(SageWindow *w, int set);
-int window_local_edge(const SageWindow *w, int global_edge); // local index of directed edge 2 * link + dir, or -1
+int window_local_edge(const SageWindow *w, int global_edge); // local index of DENSE directed edge 2 * link + dir, or -1
+bool window_owns_edge(const SageWindow *w, int global_edge);  // is directed edge 2 * link + dir this rank's?
+bool window_has_holds(const SageWindow *w);
 std::vector<int32_t> window_link_pairs(const SageWindow *w);  // [nlinks][2]: the links as the host solvers take them
 // window_eval.hip
 int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false);

@@ -277,6 +277,8 @@ struct SolvePriors; // damped_system.h
 int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
                   hipStream_t stream);
 void solver_destroy(DeviceSolver *S);
+// held variables of the window ([K] masks of SAGE_HOLD_*): applied by every later solver_run
+int solver_set_holds(DeviceSolver *S, const std::vector<uint8_t> &hold, hipStream_t stream);
 int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, const float *vars0, float *vars1, int CS,
                double damp, const SolvePriors &pri);
 // valid after the stream has been synchronised

@@ -43,6 +43,7 @@ struct SolvePlan
   const int32_t *blk_row, *blk_col, *blk_src; // [nblk]; src = link index (bit 30: the row keyframe is the link's first
                                                // end) or -1
   const int32_t *perm, *pos; // elimination order: perm[position] = keyframe, pos[keyframe] = position
+  const int32_t *hold;       // [K] masks of held variables (sage_window_hold), or null: nothing is held
 };
 
 // Head of the pinned result block; the candidate variables [K*VS floats] and the delta [K*B doubles] follow it.
@@ -85,6 +86,7 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
     if (src < 0 && i != j)
       continue; // structural fill-in: the host zeroes it at its first touch (BlockEnvelope::fill) -- nothing to deliver
     const int kf = P.perm[i]; // keyframe of this block row
+    const int hold_r = P.hold ? P.hold[kf] : 0, hold_c = P.hold ? P.hold[P.perm[j]] : 0; // (damped_system.h: held variables)
     const double *diag = packed + (size_t)kf * BB;
     const double *lnk = packed + (size_t)P.K * BB + (size_t)(src < 0 ? 0 : src) * BB;
     const double *g = packed + (size_t)P.K * BB + (size_t)P.nlinks * BB + (size_t)kf * B;
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
       if (tid < B)
       {
         double da, ga;
-        prior_row(pri, kf, tid, CS, var, var[12], var + 13, da, ga);
+        prior_row(pri, kf, tid, CS, var, var[12], var + 13, da, ga, hold_r);
         s_dadd[tid] = da;
         s_gadd[tid] = ga;
       }
@@ -106,15 +108,17 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
     {
       const int c = o / Bp, r = o - c * Bp; // o == stored_slot(r, c, Bp)
       double v = 0.0;
+      const bool held = (hold_r | hold_c) && r < B && c < B && (row_held(hold_r, r, CS) || row_held(hold_c, c, CS));
       if (i == j)
-        v = (r < B && c < B) ? damped_diag_elem(diag, B, r, c, s_dadd[r], damp) : damped_pad_elem(r, c, damp);
-      else if (r < B && c < B)
+        v = (r < B && c < B) ? (held ? held_diag_elem(r, c) : damped_diag_elem(diag, B, r, c, s_dadd[r], damp))
+                             : damped_pad_elem(r, c, damp);
+      else if (r < B && c < B && !held)
         v = lnk[link_elem(row_is_a, r, c, B)];
       out[o] = v;
     }
     if (i == j)
       for (int r = tid; r < Bp; r += blockDim.x)
-        y[(size_t)i * Bp + r] = r < B ? damped_rhs_elem(g[r], s_gadd[r]) : 0.0;
+        y[(size_t)i * Bp + r] = (r < B && !(hold_r && row_held(hold_r, r, CS))) ? damped_rhs_elem(g[r], s_gadd[r]) : 0.0;
     // the block (and its rhs rows) are visible to the host before the ticket is: the workgroup barrier orders every
     // lane's stores before lane 0's system-scope release (one cache write-back per block instead of one per wave)
     __syncthreads();
@@ -135,6 +139,7 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
 // sequential reads per thread)
 __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__restrict__ x, int K, int B, int Bp, int CS,
                                                             int VS, const int32_t *__restrict__ pos,
+                                                            const int32_t *__restrict__ hold,
                                                             const float *__restrict__ vars0,
                                                             float *__restrict__ vars1, float *__restrict__ h_vars,
                                                             double *__restrict__ h_delta, SolveResult *h_res,
@@ -185,14 +190,15 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
   for (int idx = tid; idx < K * B; idx += blockDim.x)
   {
     const int k = idx / B, r = idx - k * B;
-    const double d = x[(size_t)pos[k] * Bp + r]; // x is in elimination order
+    const bool held = hold && row_held(hold[k], r, CS); // delta exactly zero, the entry copied bit for bit
+    const double d = held ? 0.0 : x[(size_t)pos[k] * Bp + r]; // x is in elimination order
     h_delta[idx] = d;
     nrm += d * d;
     const float *v0 = vars0 + (size_t)k * VS;
     if (r >= 6)
     {
       const int slot = r < 6 + CS ? 13 + r - 6 : 12; // code entries, then the scale
-      const float v = v0[slot] + (float)d;
+      const float v = held ? v0[slot] : v0[slot] + (float)d; // (x + -0.0f may flip a sign bit)
       vars1[(size_t)k * VS + slot] = v;
       h_vars[(size_t)k * VS + slot] = v;
     }
@@ -205,7 +211,11 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
     for (int i = 0; i < 6; ++i)
       d6[i] = (float)xk[i];
     float *o = vars1 + (size_t)k * VS; // the device candidate; the host mirror gets its copy
-    pose_retract(v0, d6, o);
+    if (hold && (hold[k] & kHoldPose)) // (se3_exp of a zero delta is not the identity in fp32)
+      for (int i = 0; i < 12; ++i)
+        o[i] = v0[i];
+    else
+      pose_retract(v0, d6, o);
     for (int i = 0; i < 12; ++i)
       h_vars[(size_t)k * VS + i] = o[i];
   }
@@ -231,6 +241,7 @@ struct DeviceSolver
 {
   int K = 0, B = 0, Bp = 0, nblk = 0, nlinks = 0, VS = 0;
   void *d_int = nullptr;    // all int tables in one allocation
+  void *d_hold = nullptr;   // [K] masks of held variables (solver_set_holds), or null
   void *h_pinned = nullptr; // [SolveResult | K*VS floats | K*B doubles]
   void *h_T = nullptr;      // pinned, one allocation: block storage, then the right-hand side, then the tickets
   double *h_y = nullptr;
@@ -249,6 +260,8 @@ struct DeviceSolver
   {
     if (d_int)
       (void)hipFree(d_int);
+    if (d_hold)
+      (void)hipFree(d_hold);
     if (h_pinned)
       (void)hipHostFree(h_pinned);
     if (h_T)
@@ -345,6 +358,21 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
 
 void solver_destroy(DeviceSolver *S) { delete S; }
 
+// the window's held variables: [K] masks (damped_system.h); the scatter and the retract apply them from the next solve on
+int solver_set_holds(DeviceSolver *S, const std::vector<uint8_t> &hold, hipStream_t stream)
+{
+  if ((int)hold.size() != S->K)
+    return SAGE_E_INVALID;
+  const std::vector<int32_t> masks(hold.begin(), hold.end());
+  if (!S->d_hold && hipMalloc(&S->d_hold, masks.size() * sizeof(int32_t)) != hipSuccess)
+    return (int)hipErrorOutOfMemory;
+  if (hipMemcpyAsync(S->d_hold, masks.data(), masks.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return (int)hipErrorUnknown;
+  S->plan.hold = reinterpret_cast<const int32_t *>(S->d_hold);
+  return SAGE_OK;
+}
+
 // enqueue scatter and retract, factorise on the host in between (the retract waits on the device for the host's word);
 // the candidate's host mirror is valid once the stream has drained (or a later kernel's ticket has been seen).
 // The dependency chain of the factorisation runs on host cores, everything around it stays on the device: the scatter
@@ -377,7 +405,7 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   if (S->go_epoch == 0)
     S->go_epoch = 1;
   hipLaunchKernelGGL(solve_retract_kernel, dim3(1), dim3(1024), 0, stream, S->h_y, S->K, S->B, S->Bp, CS, S->VS,
-                     S->plan.pos, vars0, vars1, S->host_vars(), S->host_delta(), S->result(), S->go_epoch);
+                     S->plan.pos, S->plan.hold, vars0, vars1, S->host_vars(), S->host_delta(), S->result(), S->go_epoch);
   if ((eh = hipGetLastError()) != hipSuccess)
     return (int)eh;
   struct GoGuard // whatever happens below, the waiting kernel gets its word

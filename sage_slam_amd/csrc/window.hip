@@ -33,6 +33,16 @@ int window_local_edge(const SageWindow *w, int global_edge)
   return it != w->local_edges.end() && *it == global_edge ? (int)(it - w->local_edges.begin()) : -1;
 }
 
+bool window_owns_edge(const SageWindow *w, int global_edge)
+{
+  return std::binary_search(w->owned_edges.begin(), w->owned_edges.end(), global_edge);
+}
+
+bool window_has_holds(const SageWindow *w)
+{
+  return std::any_of(w->hold.begin(), w->hold.end(), [](uint8_t h) { return h != 0; });
+}
+
 int window_upload_vars(SageWindow *w, int set)
 {
   if (w->dpt_set == set)

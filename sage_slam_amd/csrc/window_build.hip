@@ -74,7 +74,36 @@ extern "C" int sage_window_add_link(SageWindow *w, int a, int b)
     return SAGE_E_INVALID;
   w->links.emplace_back(std::min(a, b), std::max(a, b));
   w->link_geo_loss.push_back(0.f);
+  w->link_dense.push_back(1);
   return (int)w->links.size() - 1;
+}
+
+// a link without dense factors: part of the solver's structure and of the packed buffer, no row of the dense edge tables
+extern "C" int sage_window_add_keypoint_link(SageWindow *w, int a, int b)
+{
+  if (!w)
+    return SAGE_E_INVALID;
+  if (w->finalized)
+    return SAGE_E_STATE;
+  if (a == b || a < 0 || b < 0 || a >= w->K || b >= w->K)
+    return SAGE_E_INVALID;
+  w->links.emplace_back(std::min(a, b), std::max(a, b));
+  w->link_geo_loss.push_back(0.f);
+  w->link_dense.push_back(0);
+  return (int)w->links.size() - 1;
+}
+
+extern "C" int sage_window_hold(SageWindow *w, int kf, int what)
+{
+  if (!w)
+    return SAGE_E_INVALID;
+  if (w->finalized)
+    return SAGE_E_STATE;
+  if (kf < 0 || kf >= w->K || what < 0 || what > (SAGE_HOLD_POSE | SAGE_HOLD_CODE | SAGE_HOLD_SCALE))
+    return SAGE_E_INVALID;
+  w->hold.resize(w->K, 0); // (keyframes added since the last call: free)
+  w->hold[kf] = (uint8_t)what;
+  return SAGE_OK;
 }
 
 extern "C" int sage_window_set_link_geo_loss(SageWindow *w, int link, float loss_param)
@@ -95,24 +124,27 @@ extern "C" int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTe
     return SAGE_E_INVALID;
   if (w->finalized)
     return SAGE_E_STATE;
-  const bool rep = t->kind == SAGE_KP_REPROJECTION, mg = t->kind == SAGE_KP_MATCH_GEOMETRY;
-  if ((!rep && !mg) || t->edge < 0 || t->edge >= 2 * (int)w->links.size() || t->N < 1 || t->N > (1 << 20) || !t->loc1d_0 ||
-      !t->homo0 || !(t->weight >= 0.f))
+  const bool rep = t->kind == SAGE_KP_REPROJECTION, mg = t->kind == SAGE_KP_MATCH_GEOMETRY, lmg = t->kind == SAGE_KP_LOOP_MG;
+  if ((!rep && !mg && !lmg) || t->edge < 0 || t->edge >= 2 * (int)w->links.size() || t->N < 1 || t->N > (1 << 20) ||
+      (!lmg && !t->loc1d_0) || !t->homo0 || !(t->weight >= 0.f))
     return SAGE_E_INVALID;
   if (rep && (!t->matched_2d || !(t->loss_param > 0.f)))
     return SAGE_E_INVALID;
   if (mg && (!t->matched_loc1d_1 || !t->matched_homo1 || t->loss < SAGE_LOSS_FAIR || t->loss > SAGE_LOSS_UNBIASED ||
              (t->loss != SAGE_LOSS_L2 && !(t->loss_param > 0.f))))
     return SAGE_E_INVALID;
+  if (lmg && (!t->matched_homo1 || !t->unscaled_dpts0 || !t->matched_unscaled_dpts1 || !(t->loss_param > 0.f)))
+    return SAGE_E_INVALID;
   SageWindow::KeypointTermHost h;
   h.kind = t->kind; h.edge = t->edge; h.N = t->N; h.loss = mg ? t->loss : 0;
   h.loss_param = t->loss_param; h.weight = t->weight;
   const size_t N = (size_t)t->N;
-  h.loc0.resize(N);
+  h.loc0.resize(lmg ? 0 : N);
   h.homo0.resize(3 * N);
   h.second.resize((rep ? 2 : 3) * N);
   SAGE_HIP(hipStreamSynchronize(w->stream)); // (the caller may have filled the arrays on the window's stream)
-  SAGE_HIP(hipMemcpy(h.loc0.data(), t->loc1d_0, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!lmg)
+    SAGE_HIP(hipMemcpy(h.loc0.data(), t->loc1d_0, N * sizeof(int32_t), hipMemcpyDeviceToHost));
   SAGE_HIP(hipMemcpy(h.homo0.data(), t->homo0, 3 * N * sizeof(float), hipMemcpyDeviceToHost));
   SAGE_HIP(hipMemcpy(h.second.data(), rep ? t->matched_2d : t->matched_homo1, h.second.size() * sizeof(float),
                      hipMemcpyDeviceToHost));
@@ -120,6 +152,13 @@ extern "C" int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTe
   {
     h.loc1.resize(N);
     SAGE_HIP(hipMemcpy(h.loc1.data(), t->matched_loc1d_1, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (lmg)
+  {
+    h.dpts0.resize(N);
+    h.dpts1.resize(N);
+    SAGE_HIP(hipMemcpy(h.dpts0.data(), t->unscaled_dpts0, N * sizeof(float), hipMemcpyDeviceToHost));
+    SAGE_HIP(hipMemcpy(h.dpts1.data(), t->matched_unscaled_dpts1, N * sizeof(float), hipMemcpyDeviceToHost));
   }
   const int32_t HW = (int32_t)w->cfg.pyr.cam[0].h * (int32_t)w->cfg.pyr.cam[0].w;
   for (int32_t v : h.loc0)
@@ -145,14 +184,16 @@ extern "C" int sage_window_get_keypoint_term(const SageWindow *w, int term, floa
     return SAGE_E_INVALID; // another rank's
   if (!w->kp_lin)
     return SAGE_E_STATE;
-  const bool rep = w->kp_added[term].kind == SAGE_KP_REPROJECTION;
-  const size_t D = rep ? 13 + w->cfg.CS : 14 + 2 * w->cfg.CS;
-  const size_t out = rep ? (size_t)lt : (size_t)(lt - w->n_kr);
+  const int kind = w->kp_added[term].kind;
+  const size_t D = (size_t)kp_kind_dim(kind, w->cfg.CS);
+  const size_t out = (size_t)(lt - (kind >= 1 ? w->n_kr : 0) - (kind >= 2 ? w->n_km : 0)); // index within the kind
+  const DevBuf &A = kind == 0 ? w->AtA_kr : (kind == 1 ? w->AtA_km : w->AtA_kl);
+  const DevBuf &b = kind == 0 ? w->Atb_kr : (kind == 1 ? w->Atb_km : w->Atb_kl);
   SAGE_HIP(hipStreamSynchronize(w->stream));
   if (AtA)
-    SAGE_HIP(hipMemcpy(AtA, (rep ? w->AtA_kr : w->AtA_km).as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
+    SAGE_HIP(hipMemcpy(AtA, A.as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
   if (Atb)
-    SAGE_HIP(hipMemcpy(Atb, (rep ? w->Atb_kr : w->Atb_km).as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
+    SAGE_HIP(hipMemcpy(Atb, b.as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
   float s2[2];
   SAGE_HIP(hipMemcpy(s2, w->stats_k.as<float>() + (size_t)lt * 2, 2 * sizeof(float), hipMemcpyDeviceToHost));
   if (err)
@@ -162,22 +203,25 @@ extern "C" int sage_window_get_keypoint_term(const SageWindow *w, int term, floa
   return SAGE_OK;
 }
 
-// finalize: this rank's terms (those of its directed edges), reprojection first, each kind in the order of the add calls
-static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjEntry>> &adjv, double *residuals)
+// finalize: this rank's terms (those of its directed edges), by kind (reprojection, match geometry, loop-MG), each kind in the
+// order of the add calls; link_terms [nlinks]: does the link carry a local term?
+static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjEntry>> &adjv, std::vector<char> &link_terms,
+                                     double *residuals)
 {
   const int CS = w->cfg.CS, nterms = (int)w->kp_added.size();
   w->kp_local.assign(nterms, -1);
-  w->n_kr = w->n_km = 0;
+  w->n_kr = w->n_km = w->n_kl = 0;
+  link_terms.assign(w->links.size(), 0);
   if (nterms == 0)
     return SAGE_OK;
   std::vector<int> order;
-  for (int kind = 0; kind < 2; ++kind)
+  for (int kind = 0; kind < kKpKinds; ++kind)
     for (int i = 0; i < nterms; ++i)
-      if (w->kp_added[i].kind == kind && window_local_edge(w, w->kp_added[i].edge) >= 0)
+      if (w->kp_added[i].kind == kind && window_owns_edge(w, w->kp_added[i].edge))
       {
         w->kp_local[i] = (int)order.size();
         order.push_back(i);
-        (kind == 0 ? w->n_kr : w->n_km) += 1;
+        (kind == 0 ? w->n_kr : (kind == 1 ? w->n_km : w->n_kl)) += 1;
       }
   const int nloc = (int)order.size();
   if (nloc == 0)
@@ -192,16 +236,18 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
   };
   struct Offs
   {
-    size_t loc0, loc1, homo0, second;
+    size_t loc0, loc1, homo0, second, dpts0, dpts1;
   };
   std::vector<Offs> offs(nloc);
   for (int t = 0; t < nloc; ++t)
   {
     const SageWindow::KeypointTermHost &h = w->kp_added[order[t]];
-    offs[t].loc0 = put(h.loc0.data(), h.loc0.size());
+    offs[t].loc0 = h.loc0.empty() ? 0 : put(h.loc0.data(), h.loc0.size());
     offs[t].loc1 = h.loc1.empty() ? 0 : put(h.loc1.data(), h.loc1.size());
     offs[t].homo0 = put(h.homo0.data(), h.homo0.size());
     offs[t].second = put(h.second.data(), h.second.size());
+    offs[t].dpts0 = h.dpts0.empty() ? 0 : put(h.dpts0.data(), h.dpts0.size());
+    offs[t].dpts1 = h.dpts1.empty() ? 0 : put(h.dpts1.data(), h.dpts1.size());
   }
   int rc;
   if ((rc = upload(w->kp_pool, pool, w->stream)))
@@ -216,18 +262,23 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
     const int k0 = dir == 0 ? w->links[l].first : w->links[l].second, k1 = dir == 0 ? w->links[l].second : w->links[l].first;
     KpTerm kt{};
     kt.kind = h.kind; kt.loss = h.loss; kt.N = h.N;
-    kt.out = h.kind == 0 ? t : t - w->n_kr;
+    kt.out = t - (h.kind >= 1 ? w->n_kr : 0) - (h.kind >= 2 ? w->n_km : 0);
     kt.stat = t;
     kt.k0 = k0; kt.k1 = k1;
     kt.loss_param = h.loss_param; kt.weight = h.weight;
-    kt.loc0 = reinterpret_cast<const int32_t *>(base + offs[t].loc0);
+    if (h.kind != SAGE_KP_LOOP_MG)
+      kt.loc0 = reinterpret_cast<const int32_t *>(base + offs[t].loc0);
     kt.homo0 = reinterpret_cast<const float *>(base + offs[t].homo0);
     if (h.kind == 0)
       kt.matched = reinterpret_cast<const float *>(base + offs[t].second);
     else
-    {
-      kt.loc1 = reinterpret_cast<const int32_t *>(base + offs[t].loc1);
       kt.homo1 = reinterpret_cast<const float *>(base + offs[t].second);
+    if (h.kind == SAGE_KP_MATCH_GEOMETRY)
+      kt.loc1 = reinterpret_cast<const int32_t *>(base + offs[t].loc1);
+    if (h.kind == SAGE_KP_LOOP_MG)
+    {
+      kt.dpts0 = reinterpret_cast<const float *>(base + offs[t].dpts0);
+      kt.dpts1 = reinterpret_cast<const float *>(base + offs[t].dpts1);
     }
     kt.bias0 = w->views[k0].bias; kt.basis0 = w->views[k0].basis;
     kt.bias1 = w->views[k1].bias; kt.basis1 = w->views[k1].basis;
@@ -235,7 +286,8 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
     adjv[k0].push_back(AdjEntry{2 + h.kind, kt.out, 0});
     adjv[k1].push_back(AdjEntry{2 + h.kind, kt.out, 1});
     per_link[l].push_back(AdjEntry{2 + h.kind, kt.out, dir});
-    *residuals += (h.kind == 0 ? 2.0 : 3.0) * h.N;
+    link_terms[l] = 1;
+    *residuals += (double)kp_kind_rows(h.kind) * h.N;
   }
   std::vector<int32_t> lstart(w->links.size() + 1, 0);
   std::vector<AdjEntry> lkp;
@@ -245,13 +297,15 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
     lkp.insert(lkp.end(), per_link[l].begin(), per_link[l].end());
   }
   lstart[w->links.size()] = (int32_t)lkp.size();
-  const size_t Dp = 13 + CS, Dg = 14 + 2 * CS;
+  const size_t Dp = kp_kind_dim(0, CS), Dg = kp_kind_dim(1, CS), Dl = kp_kind_dim(2, CS);
   if ((rc = upload(w->kp_table, table, w->stream)) || (rc = upload(w->kp_link_start, lstart, w->stream)) ||
       (rc = upload(w->kp_link, lkp, w->stream)) ||
       (rc = w->AtA_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * Dp * sizeof(float))) ||
       (rc = w->Atb_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * sizeof(float))) ||
       (rc = w->AtA_km.reserve(std::max<size_t>(1, w->n_km) * Dg * Dg * sizeof(float))) ||
       (rc = w->Atb_km.reserve(std::max<size_t>(1, w->n_km) * Dg * sizeof(float))) ||
+      (rc = w->AtA_kl.reserve(std::max<size_t>(1, w->n_kl) * Dl * Dl * sizeof(float))) ||
+      (rc = w->Atb_kl.reserve(std::max<size_t>(1, w->n_kl) * Dl * sizeof(float))) ||
       (rc = w->stats_k.reserve((size_t)2 * nloc * 2 * sizeof(float))))
     return rc;
   SAGE_HIP(hipMemsetAsync(w->stats_k.p, 0, (size_t)2 * nloc * 2 * sizeof(float), w->stream));
@@ -315,7 +369,8 @@ struct FinalizeState
   std::vector<size_t> px_off;              // [n_edges + 1]: source pixels before local edge e (rows of geo_px)
   std::vector<int> Nedge;                  // samples (slots) per local directed edge
   std::vector<std::vector<AdjEntry>> adjv; // [K]: the keyframe's (edge, role) incidences, keypoint terms included
-  std::vector<LinkEdges> le;               // per link: its local edges
+  std::vector<LinkEdges> le;               // per link: its local dense edges
+  std::vector<char> link_terms;            // per link: it carries a local keypoint term
   double residuals = 0, bytes = 0;         // per linearize
 };
 
@@ -338,7 +393,8 @@ static int finalize_variables(SageWindow *w)
   return SAGE_OK;
 }
 
-// 2. leaves local_edges / local_links (plan::owned_edges), fs.needed, n_depth and the depth items of both variable sets.
+// 2. leaves owned_edges / local_links (plan::owned_edges), local_edges (plan::dense_edges), fs.needed (the keyframes this
+//    rank's DENSE edges touch), n_depth and the depth items of both variable sets.
 //    Whole links on request (SAGE_SHARD_BY_LINK) and for windows whose domain-decomposed solve derives its domains from them
 static int finalize_ownership(SageWindow *w, FinalizeState &fs)
 {
@@ -346,11 +402,12 @@ static int finalize_ownership(SageWindow *w, FinalizeState &fs)
   int rc;
   const bool by_link = sage::env_flag("SAGE_SHARD_BY_LINK") || fs.domain_solve;
   plan::Ownership own = plan::owned_edges((int)w->links.size(), w->rank, w->world, by_link);
-  w->local_edges = std::move(own.edges);
+  w->owned_edges = std::move(own.edges);
   w->local_links = std::move(own.links);
+  w->local_edges = plan::dense_edges(w->owned_edges, w->link_dense);
   fs.needed.assign(K, 0);
-  for (int l : w->local_links)
-    fs.needed[w->links[l].first] = fs.needed[w->links[l].second] = 1;
+  for (int ge : w->local_edges)
+    fs.needed[w->links[ge / 2].first] = fs.needed[w->links[ge / 2].second] = 1;
   w->n_depth = 0;
   for (int k = 0; k < K; ++k)
     w->n_depth += fs.needed[k];
@@ -681,13 +738,14 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
   if ((rc = w->packed.reserve(sage_window_packed_count(w) * sizeof(double))) || (rc = w->errbuf.reserve(4 * sizeof(double))))
     return rc;
   {
-    // the output blocks this rank's edges contribute to (everything, on a single-rank window)
+    // the output blocks this rank's edges and keypoint terms contribute to (everything, on a single-rank window; a link block
+    // that only local terms write to is listed too: it would keep the zeros of this stage on a sharded window)
     std::vector<int32_t> ids;
     for (int k = 0; k < K; ++k)
       if (!fs.adjv[k].empty())
         ids.push_back(k);
     for (size_t l = 0; l < fs.le.size(); ++l)
-      if (fs.le[l].e_ab >= 0 || fs.le[l].e_ba >= 0)
+      if (fs.le[l].e_ab >= 0 || fs.le[l].e_ba >= 0 || fs.link_terms[l])
         ids.push_back(K + (int32_t)l);
     ids.push_back(K + (int32_t)w->links.size()); // the tail
     w->dist.n_asm_blocks = (int)ids.size();
@@ -714,6 +772,8 @@ static int finalize_solver(SageWindow *w, const FinalizeState &fs)
   int rc = solver_create(&w->solver, w->K, w->B, w->VS, w->links, w->stream);
   if (rc != SAGE_OK && rc != SAGE_E_UNSUPPORTED)
     return rc;
+  if (w->solver && window_has_holds(w) && (rc = solver_set_holds(w->solver, w->hold, w->stream)))
+    return rc; // (without a device solver the host block solve masks its copy: window_solve.hip)
   if (!fs.domain_solve)
     return SAGE_OK;
   const std::vector<int32_t> lk = window_link_pairs(w);
@@ -734,10 +794,13 @@ extern "C" int sage_window_finalize(SageWindow *w)
   FinalizeState fs;
   const char *schur = getenv("SAGE_SHARD_SCHUR"); // the request: 0 / 1
   fs.domain_solve = plan::uses_domain_solve(w->world, w->K, schur ? atoi(schur) != 0 : -1);
+  w->hold.resize(w->K, 0);
+  if (fs.domain_solve && window_has_holds(w))
+    return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables)
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||
-      (rc = window_finalize_keypoints(w, fs.adjv, &fs.residuals))) // 7. this rank's keypoint terms: pool, table, result buffers
+      (rc = window_finalize_keypoints(w, fs.adjv, fs.link_terms, &fs.residuals))) // 7. this rank's keypoint terms: pool, table, result buffers
     return rc;
   w->residuals_per_lin = fs.residuals;
   w->bytes_per_lin = fs.bytes;

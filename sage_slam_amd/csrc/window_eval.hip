@@ -7,11 +7,14 @@
 namespace sage
 {
 
-// B-index (0..6+CS: pose 6, code CS, scale) -> column of the per-edge system, or -1 if absent
+// B-index (0..6+CS: pose 6, code CS, scale) -> column of the per-edge system, or -1 if absent.  type: the column map --
+// 0 the photometric edge's, 1 the geometric edge's, 2 the loop-MG term's [pose0 pose1 scale0 scale1]
 __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 {
   if (bi < 6)
     return role * 6 + bi;
+  if (type == 2)
+    return bi == 6 + CS ? 12 + role : -1; // no code row
   if (type == 0)
   {
     if (role == 1)
@@ -24,8 +27,14 @@ __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 }
 
 // one workgroup per output block; thread per element; contributions summed in a fixed order (deterministic)
-// KP: the window carries keypoint terms (AdjEntry::type 2 / 3, the link lists, their share of the tail); windows without them
-// run the instantiation that knows nothing of them
+// column map of an adjacency entry's type: keypoint terms of types 2 / 3 share the dense layouts, type 4 has its own
+__device__ __forceinline__ int adj_col_map(int type) { return type == 4 ? 2 : (type & 1); }
+// a keypoint term's results by column map
+__device__ __forceinline__ const float *kp_AtA(const AssembleParams &p, int lt) { return lt == 0 ? p.AtA_kr : (lt == 1 ? p.AtA_km : p.AtA_kl); }
+__device__ __forceinline__ const float *kp_Atb(const AssembleParams &p, int lt) { return lt == 0 ? p.Atb_kr : (lt == 1 ? p.Atb_km : p.Atb_kl); }
+
+// KP: the window carries keypoint terms (AdjEntry::type 2 / 3 / 4, the link lists, their share of the tail); windows without
+// them run the instantiation that knows nothing of them
 template <bool KP>
 __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
 {
@@ -65,11 +74,11 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     for (int a = a0; a < a1; ++a)
     {
       const AdjEntry ae = p.adj[a];
-      const int lt = KP ? (ae.type & 1) : ae.type; // column map: keypoint terms (types 2 / 3) share the dense layouts
+      const int lt = KP ? adj_col_map(ae.type) : ae.type;
       const bool kp = KP && ae.type >= 2;
-      const int D = lt == 0 ? Dp : Dg;
-      const float *A = kp ? (lt == 0 ? p.AtA_kr : p.AtA_km) : (lt == 0 ? p.AtA_p : p.AtA_g);
-      const float *b = kp ? (lt == 0 ? p.Atb_kr : p.Atb_km) : (lt == 0 ? p.Atb_p : p.Atb_g);
+      const int D = lt == 0 ? Dp : (lt == 1 ? Dg : 14);
+      const float *A = kp ? kp_AtA(p, lt) : (lt == 0 ? p.AtA_p : p.AtA_g);
+      const float *b = kp ? kp_Atb(p, lt) : (lt == 0 ? p.Atb_p : p.Atb_g);
 #pragma unroll
       for (int s = 0; s < S; ++s)
       {
@@ -131,8 +140,8 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
         for (int a = p.link_kp_start[l]; a < p.link_kp_start[l + 1]; ++a)
         {
           const AdjEntry ae = p.link_kp[a];
-          const int lt = ae.type & 1, D = lt == 0 ? Dp : Dg;
-          const float *A = lt == 0 ? p.AtA_kr : p.AtA_km;
+          const int lt = adj_col_map(ae.type), D = lt == 0 ? Dp : (lt == 1 ? Dg : 14);
+          const float *A = kp_AtA(p, lt);
           const int ci = edge_col(lt, ae.role, bi, p.CS), cj = edge_col(lt, 1 - ae.role, bj, p.CS); // (role = direction)
           if (ci >= 0 && cj >= 0)
             acc += (double)A[(size_t)ae.edge * D * D + (size_t)ci * D + cj];
@@ -154,10 +163,10 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     if (st && wave < 4)
       for (int e = lane; e < n; e += 64)
         acc += (double)st[2 * e + which];
-    if (KP && p.stats_k && wave < 2) // the terms' errors: reprojection in the photometric slot, match geometry in the geometric one
-    {
+    if (KP && p.stats_k && wave < 2) // the terms' errors: reprojection in the photometric slot, match geometry and loop-MG
+    {                                // (behind it in stats_k) in the geometric one
       const float *sk = p.stats_k + (photo ? 0 : 2 * (size_t)p.n_kr);
-      const int nk = photo ? p.n_kr : p.n_km;
+      const int nk = photo ? p.n_kr : p.n_km + p.n_kl;
       for (int t = lane; t < nk; t += 64)
         acc += (double)sk[2 * t];
     }
@@ -259,7 +268,7 @@ __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSid
   if (KP && kp.stats && which == 0) // keypoint terms (written by the batched kernel before this one): same slots as the linearize tail
   {
     const float *sk = kp.stats + (photo ? 0 : 2 * (size_t)kp.n_kr);
-    const int nk = photo ? kp.n_kr : kp.n_km;
+    const int nk = photo ? kp.n_kr : kp.n_km + kp.n_kl;
     for (int t = lane; t < nk; t += 64)
       acc += (double)sk[2 * t];
   }
@@ -347,10 +356,12 @@ static AssembleParams window_assemble_params(SageWindow *w)
   ap.n_edges_g = w->n_edges;
   ap.split = 1;
   ap.blocks = nullptr;
-  if (w->n_kr + w->n_km > 0)
+  if (w->n_terms() > 0)
   {
     ap.AtA_kr = w->AtA_kr.as<float>(); ap.Atb_kr = w->Atb_kr.as<float>();
     ap.AtA_km = w->AtA_km.as<float>(); ap.Atb_km = w->Atb_km.as<float>();
+    ap.AtA_kl = w->AtA_kl.as<float>(); ap.Atb_kl = w->Atb_kl.as<float>();
+    ap.n_kl = w->n_kl;
     ap.stats_k = w->stats_k.as<float>();
     ap.link_kp_start = w->kp_link_start.as<int32_t>();
     ap.link_kp = w->kp_link.as<AdjEntry>();
@@ -363,7 +374,7 @@ static AssembleParams window_assemble_params(SageWindow *w)
 // the batched kernel over this rank's terms at variable set `set`; linearize -> stats_k[0], error pass -> stats_k[1]
 static int window_launch_keypoints(SageWindow *w, int set, bool jac)
 {
-  const int nloc = w->n_kr + w->n_km;
+  const int nloc = w->n_terms();
   if (nloc == 0)
     return SAGE_OK;
   KpBatchParams kp{};
@@ -374,12 +385,13 @@ static int window_launch_keypoints(SageWindow *w, int set, bool jac)
   kp.eps = w->cfg.eps;
   kp.AtA_r = w->AtA_kr.as<float>(); kp.Atb_r = w->Atb_kr.as<float>();
   kp.AtA_m = w->AtA_km.as<float>(); kp.Atb_m = w->Atb_km.as<float>();
+  kp.AtA_l = w->AtA_kl.as<float>(); kp.Atb_l = w->Atb_kl.as<float>();
   kp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * nloc);
   LaunchCommon lc{};
   prof_attach(w, jac ? 4 : 5, lc);
   if (lc.ev_start)
     (void)hipEventRecord(lc.ev_start, w->stream);
-  SAGE_HIP(launch_keypoint_batch(w->stream, w->cfg.CS, jac, nloc, w->n_km > 0, kp));
+  SAGE_HIP(launch_keypoint_batch(w->stream, w->cfg.CS, jac, nloc, w->kp_kinds(), kp));
   if (lc.ev_stop)
     (void)hipEventRecord(lc.ev_stop, w->stream);
   if (jac)
@@ -398,7 +410,12 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     return SAGE_E_STATE;
   const SageWindowConfig &c = w->cfg;
   const int H = (int)c.pyr.cam[0].h, W = (int)c.pyr.cam[0].w;
-  if (w->n_edges > 0)
+  // a rank -- or a whole window -- whose links all carry keypoint terms only has no dense edge: no depth batch, no dense
+  // kernel and no per-edge finalize then (a launch with a zero grid is an error); its terms are linearized all the same
+  const bool dense = w->n_edges > 0;
+  LaunchCommon lcg{}, lcp{};
+  merge = merge && w->merge_ok;
+  if (dense)
   {
     // depth maps of every keyframe at the current variables: both factor types read their sample depths from them
     // (an accepted candidate's maps from the error pass are still valid: only the gradients are missing then)
@@ -408,10 +425,10 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->dpt_set = set;
     w->dgrad_valid = true;
     // main kernels only (stage 1), then ONE finalize launch for both factor types (window_finalize_kernel)
-    LaunchCommon lcg = window_lc(w, kGeo), lcp = window_lc(w, kPhoto, true);
+    lcg = window_lc(w, kGeo);
+    lcp = window_lc(w, kPhoto, true);
     lcg.stage = 1;
     lcp.stage = 1;
-    merge = merge && w->merge_ok;
     lcg.merge_geo_weight = lcp.merge_geo_weight = merge ? c.geo_weight : 0.f;
     if (c.use_geo)
     {
@@ -425,11 +442,14 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
       SAGE_HIP(launch_photo_linearize(w->stream, c.CS, c.FS, nullptr, w->dense[kPhoto].tab[set].as<PhotoEdge>(), lcp, c.pyr,
                                       c.photo_weights, c.eps, w->dense[kPhoto].out()));
     }
-    {
-      const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
-      if (rck)
-        return rck;
-    }
+  }
+  {
+    const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
+    if (rck)
+      return rck;
+  }
+  if (dense)
+  {
     WindowFinalizeParams fp{};
     fp.n_p = c.use_photo ? w->n_edges : 0;
     fp.n_g = c.use_geo ? w->n_edges : 0;
@@ -461,7 +481,7 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     ap.blocks = w->dist.asm_blocks.as<int32_t>();
     nblocks = w->dist.n_asm_blocks;
   }
-  if (w->n_kr + w->n_km > 0)
+  if (w->n_terms() > 0)
     hipLaunchKernelGGL(assemble_kernel<true>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
   else
     hipLaunchKernelGGL(assemble_kernel<false>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
@@ -550,13 +570,13 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     ge = error_totals_side(lc, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kOwnRecord);
   }
   KpTotals kpt{};
-  if (w->n_kr + w->n_km > 0)
+  if (w->n_terms() > 0)
   {
     // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
     const int rck = window_launch_keypoints(w, which, false);
     if (rck)
       return rck;
-    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * (w->n_kr + w->n_km), w->n_kr, w->n_km};
+    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * w->n_terms(), w->n_kr, w->n_km, w->n_kl};
   }
   w->mirror.err_epoch += 1;
   double *const mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kError : nullptr;

@@ -1,5 +1,5 @@
 // window_plan.h -- the build-time policy of the window engine as pure integer arithmetic: which directed edges a rank owns,
-// whether a window uses the domain-decomposed solve, the run lengths of the two work lists.  Standard library only -- no HIP, no
+// which of them are dense, whether a window uses the domain-decomposed solve, the run lengths of the two work lists.  Standard library only -- no HIP, no
 // environment: the runtime applies its overrides to the results (window_build.hip), and tests/test_window_plan.py compiles
 // this header with a host compiler.  An edge's length is its number of SUB-TILES (ceil(samples / kTile)) throughout.
 #pragma once
@@ -48,6 +48,18 @@ inline Ownership owned_edges(int nlinks, int rank, int world, bool by_link)
     if (o.links.empty() || o.links.back() != ge / 2)
       o.links.push_back(ge / 2);
   return o;
+}
+
+// which of a rank's owned directed edges carry the dense factors: those of links added with both factor types
+// (link_is_dense[l] != 0); the others carry keypoint terms only -- no row of the dense edge tables, work lists or per-edge
+// results.  The order of `owned` is kept: a dense edge's local index is its position in the answer.
+inline std::vector<int> dense_edges(const std::vector<int> &owned, const std::vector<char> &link_is_dense)
+{
+  std::vector<int> out;
+  for (int ge : owned)
+    if (ge >= 0 && (size_t)(ge / 2) < link_is_dense.size() && link_is_dense[ge / 2])
+      out.push_back(ge);
+  return out;
 }
 
 // does the window use the domain-decomposed solve (shard_solve.cpp)?  Sharded windows only: on by request or for long windows,

@@ -63,11 +63,12 @@ static void window_priors(const SageWindow *w, std::vector<double> &dadd, std::v
   for (int k = 0; k < K; ++k)
     for (int r = 0; r < B; ++r)
       sage::prior_row(pri, k, r, CS, &w->hv.pose[0][(size_t)k * 12], w->hv.scale[0][k], &w->hv.code[0][(size_t)k * CS],
-                      dadd[(size_t)k * B + r], gadd[(size_t)k * B + r]);
+                      dadd[(size_t)k * B + r], gadd[(size_t)k * B + r], w->hold.empty() ? 0 : w->hold[k]);
 }
 
 // candidate = retract(current, delta).  local_only (sharded windows): only the keyframes this rank touches, the others
-// keep their (stale) current values
+// keep their (stale) current values.  Held entries are copied bit for bit, as solve_retract_kernel does (se3_exp of a zero
+// delta is not the identity in fp32, x + -0.0f may flip a sign bit)
 static void window_retract_candidate(SageWindow *w, bool local_only)
 {
   const int K = w->K, B = w->B, CS = w->cfg.CS;
@@ -77,13 +78,19 @@ static void window_retract_candidate(SageWindow *w, bool local_only)
   {
     if (local_only && !sage_shard_keyframe_is_local(w->dist.shard, k))
       continue;
+    const int hold = w->hold.empty() ? 0 : w->hold[k];
     float d6[6];
     for (int i = 0; i < 6; ++i)
       d6[i] = (float)w->delta[(size_t)k * B + i];
-    sage_pose_retract(&w->hv.pose[0][(size_t)k * 12], d6, &w->hv.pose[1][(size_t)k * 12]);
+    if (hold & sage::kHoldPose)
+      std::copy_n(&w->hv.pose[0][(size_t)k * 12], 12, &w->hv.pose[1][(size_t)k * 12]);
+    else
+      sage_pose_retract(&w->hv.pose[0][(size_t)k * 12], d6, &w->hv.pose[1][(size_t)k * 12]);
     for (int i = 0; i < CS; ++i)
-      w->hv.code[1][(size_t)k * CS + i] = w->hv.code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
-    w->hv.scale[1][k] = w->hv.scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
+      w->hv.code[1][(size_t)k * CS + i] =
+          (hold & sage::kHoldCode) ? w->hv.code[0][(size_t)k * CS + i]
+                                   : w->hv.code[0][(size_t)k * CS + i] + (float)w->delta[(size_t)k * B + 6 + i];
+    w->hv.scale[1][k] = (hold & sage::kHoldScale) ? w->hv.scale[0][k] : w->hv.scale[0][k] + (float)w->delta[(size_t)k * B + 6 + CS];
   }
 }
 
@@ -149,10 +156,18 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
   std::vector<double> dadd, gadd;
   window_priors(w, dadd, gadd);
   const std::vector<int32_t> lk = window_link_pairs(w);
+  const bool holds = window_has_holds(w);
+  if (holds) // the held rule on the host copy (damped_system.h); `packed` itself is untouched
+    sage::hold_packed(w->host_packed.data(), dadd.data(), gadd.data(), K, (int)w->links.size(), lk.data(), B, CS, w->hold.data());
   int rcs = sage_block_solve(w->host_packed.data(), K, (int)w->links.size(), lk.data(), B, damp, dadd.data(),
                              gadd.data(), w->delta.data()); // (writes delta only on success)
   if (rcs)
     return rcs;
+  if (holds) // exactly zero, whatever sign the substitution left
+    for (int k = 0; k < K; ++k)
+      for (int r = 0; r < B; ++r)
+        if (sage::row_held(w->hold[k], r, CS))
+          w->delta[(size_t)k * B + r] = 0.0;
   auto t_d = tnow();
   double nrm = 0;
   for (double v : w->delta)

@@ -356,3 +356,41 @@ def make_match_geometry_matches(w: Window, k0: int, k1: int, n: int, seed: int, 
     y = np.clip(np.rint(px[:, 1]), 0, w.H - 1).astype(np.int64)
     homo1 = np.stack([(x - float(cam.cx)) / float(cam.fx), (y - float(cam.cy)) / float(cam.fy), np.ones(n)], 1)
     return dict(kind="match_geometry", loc0=loc0, homo0=homo0, loc1=(y * w.W + x).astype(np.int32), homo1=homo1.astype(F32))
+
+
+# --------------------------------------------------------------------------- loop-MG terms (fixed depths, D = 14)
+def _unscaled_depths(kf: Keyframe, loc: np.ndarray, code: np.ndarray) -> np.ndarray:
+    """``bias[loc] + basis[loc] . code`` in fp32: the depths a loop-closure graph fixes when it is built
+    (``matched_unscaled_dpts``, ``core/deepfactors.cpp:388-575``)."""
+    loc = np.asarray(loc, np.int64)
+    return (kf.bias[loc].astype(F32) + kf.basis[loc].astype(F32) @ np.asarray(code, F32)).astype(F32)
+
+
+def make_loop_mg_terms_from_matches(w: Window, k0: int, k1: int, n: int, seed: int, noise_px: float = 1.0,
+                                    outlier_share: float = 0.1) -> dict:
+    """A loop-MG term on the directed edge k0 -> k1 from the matches of ``make_match_geometry_matches``: the two depth
+    arrays are formed at the window's INITIAL codes, ``u0 = bias0[loc0] + basis0[loc0] . code0`` and
+    ``u1 = bias1[loc1] + basis1[loc1] . code1`` (fp32) -> dict(kind, loc0, loc1, homo0 [n,3], homo1 [n,3], u0 [n], u1 [n]).
+    With pixel noise and outliers the residuals are large: data for parity checks, not for a recovery test."""
+    m = make_match_geometry_matches(w, k0, k1, n, seed, noise_px, outlier_share)
+    a, b = w.keyframes[k0], w.keyframes[k1]
+    return dict(kind="loop_mg", loc0=m["loc0"], loc1=m["loc1"], homo0=m["homo0"], homo1=m["homo1"],
+                u0=_unscaled_depths(a, m["loc0"], a.code), u1=_unscaled_depths(b, m["loc1"], b.code))
+
+
+def make_loop_mg_exact(w: Window, k0: int, k1: int, n: int, seed: int) -> dict:
+    """A loop-MG term whose residual vanishes at the window's TRUE poses and scales: n points of keyframe k0's samples with
+    ``u0`` from the true code; the matched ray and depth are the exact true point in k1, ``homo1 = X1 / X1.z`` and
+    ``u1 = X1.z / scale_true(k1)`` (no pixel rounding) -> dict(kind, loc0, homo0, homo1, u0, u1).  Deterministic per
+    (seed, k0, k1, n)."""
+    a, b = w.keyframes[k0], w.keyframes[k1]
+    rng = np.random.default_rng([seed, k0, k1, n, 14])
+    pick = rng.choice(a.loc1d.size, size=n, replace=n > a.loc1d.size)
+    loc0 = a.loc1d[pick].astype(np.int64)
+    homo0 = a.homo[pick].astype(F32)
+    u0 = _unscaled_depths(a, loc0, a.code_true)
+    d = float(a.scale_true) * u0.astype(np.float64)
+    Xw = (a.R_true.astype(np.float64) @ (d[:, None] * homo0.astype(np.float64)).T).T + a.t_true.astype(np.float64)
+    X1 = (b.R_true.astype(np.float64).T @ (Xw - b.t_true.astype(np.float64)).T).T
+    return dict(kind="loop_mg", loc0=loc0.astype(np.int32), homo0=homo0, homo1=(X1 / X1[:, 2:3]).astype(F32),
+                u0=u0, u1=(X1[:, 2] / float(b.scale_true)).astype(F32))
