@@ -376,7 +376,14 @@ int sage_window_add_keypoint_link(SageWindow *w, int kf_a, int kf_b);
  * are untouched: every factor is still evaluated, and the prior ERROR terms of held variables stay in the total (constants).
  * sage_window_set_keyframe on a held keyframe still sets it.  Before finalize (SAGE_E_STATE afterwards); SAGE_E_INVALID for
  * a bad keyframe or mask.  A window that uses the domain-decomposed solve and holds anything answers SAGE_E_UNSUPPORTED at
- * finalize. */
+ * finalize.
+ * Solver rows: a group (pose, code or scale) that EVERY keyframe of the window holds is left out of the damped system
+ * altogether -- the solver then works on blocks of the remaining groups' rows, in block order pose / code / scale
+ * (sage_window_solver_block_size: 7 when all codes are held, 6 with codes and scales, 1 + CS with all poses), instead of
+ * carrying identity rows: less to stream to the host, less to factorise.  A group that a single keyframe leaves free is
+ * kept whole, its held rows as identity rows inside the smaller block; a window that holds nothing, or everything, solves at
+ * B.  The step is the same either way; sage_window_block_size, the packed buffer and sage_window_get_delta keep the layout
+ * of B rows per keyframe, dropped rows with delta 0. */
 enum { SAGE_HOLD_POSE = 1, SAGE_HOLD_CODE = 2, SAGE_HOLD_SCALE = 4 };
 int sage_window_hold(SageWindow *w, int kf, int what);
 /* edge sharding for multi-GPU: this process evaluates the contiguous range [rank*2n/world, (rank+1)*2n/world) of the 2n
@@ -391,6 +398,8 @@ int sage_window_finalize(SageWindow *w);
 int sage_window_num_keyframes(const SageWindow *w);
 int sage_window_num_links(const SageWindow *w);
 int sage_window_block_size(const SageWindow *w);       /* B = 7 + CS: [pose6, code CS, scale] */
+int sage_window_solver_block_size(const SageWindow *w); /* Bs <= B: rows per keyframe in the solver (sage_window_hold); 0
+                                                          * before finalize or for NULL */
 /* packed normal-equation buffer (device, DOUBLE), the all-reduce payload:
  *   [ diag blocks K*B*B | link blocks nlinks*B*B (row = older kf, col = newer kf) | g K*B | err_photo err_geo n_photo n_geo ]
  * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry and loop-MG terms';

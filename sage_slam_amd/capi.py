@@ -112,7 +112,7 @@ SYMBOLS = [
     "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
-    "sage_window_block_size", "sage_window_packed_count", "sage_window_packed_dev",
+    "sage_window_block_size", "sage_window_solver_block_size", "sage_window_packed_count", "sage_window_packed_dev",
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
     "sage_window_error", "sage_window_tune_runs", "sage_window_set_runs", "sage_window_error_dev", "sage_window_solve", "sage_window_total_error",
     "sage_window_accept", "sage_window_reset", "sage_window_get_keyframe", "sage_window_set_keyframe", "sage_window_get_delta",
@@ -149,7 +149,8 @@ def lib():
         L.sage_window_bytes_per_linearize.restype = C.c_double
         for name in ("sage_window_packed_count", "sage_window_packed_dev", "sage_window_error_dev",
                      "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize",
-                     "sage_window_num_keyframes", "sage_window_num_links", "sage_window_block_size"):
+                     "sage_window_num_keyframes", "sage_window_num_links", "sage_window_block_size",
+                     "sage_window_solver_block_size"):
             getattr(L, name).argtypes = [C.c_void_p]
         _lib = L
     return _lib
@@ -570,6 +571,7 @@ class Window:
         _chk(L.sage_window_finalize(self.h), "sage_window_finalize")
         self.K = L.sage_window_num_keyframes(self.h)
         self.B = L.sage_window_block_size(self.h)
+        self.Bs = L.sage_window_solver_block_size(self.h)   # rows per keyframe in the solver (sage_window_hold)
         self.nlinks = L.sage_window_num_links(self.h)
         self.packed_count = L.sage_window_packed_count(self.h)
         self.residuals_per_linearize = L.sage_window_residuals_per_linearize(self.h)

@@ -823,12 +823,18 @@ static inline __attribute__((always_inline)) void block_schur_rows(const BlockEn
 }
 
 // ---- entry points.  Every template above is inlined into the multi-versioned functions this macro generates (a v8d must
-// not cross a call, see SAGE_LOADU): NAME_40 / NAME_24 for the two padded block sizes and NAME_bp, which picks by Bp.
+// not cross a call, see SAGE_LOADU): NAME_40 / NAME_24 / NAME_8 for the three padded block sizes (block_kernels_for) and
+// NAME_bp, which picks by Bp.
 #define SAGE_ARGS(...) __VA_ARGS__
 #define SAGE_BLOCK_ENTRY(RET, NAME, PARAMS, ARGS)                                                                          \
   __attribute__((target_clones("avx512f", "avx2", "default"))) static RET NAME##_40 PARAMS { return NAME<5> ARGS; }        \
   __attribute__((target_clones("avx512f", "avx2", "default"))) static RET NAME##_24 PARAMS { return NAME<3> ARGS; }        \
-  static inline RET NAME##_bp(int Bp, SAGE_ARGS PARAMS) { return Bp == 40 ? NAME##_40 ARGS : NAME##_24 ARGS; }
+  __attribute__((target_clones("avx512f", "avx2", "default"))) static RET NAME##_8 PARAMS { return NAME<1> ARGS; }         \
+  static inline RET NAME##_bp(int Bp, SAGE_ARGS PARAMS)                                                                    \
+  {                                                                                                                        \
+    return Bp == 40 ? NAME##_40 ARGS : Bp == 24 ? NAME##_24 ARGS : NAME##_8 ARGS;                                          \
+  }
+static inline bool block_kernels_for(int Bp) { return Bp == 40 || Bp == 24 || Bp == 8; }
 
 #define SAGE_ROWS_PARAMS (const BlockEnvelope &E, double *T, double *X, double *y, int lo, int hi)
 SAGE_BLOCK_ENTRY(int, factor_rows, SAGE_ROWS_PARAMS, (E, T, X, y, lo, hi))
@@ -1672,7 +1678,7 @@ int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool may_s
 
 int block_chol_partial(const BlockEnvelope &E, double *T, double *X, double *y, int nI)
 {
-  if ((E.Bp != 40 && E.Bp != 24) || E.a_cnt)
+  if (!block_kernels_for(E.Bp) || E.a_cnt)
     return -1;
   const int rc = block_chol_range(E, T, X, y, 0, nI); // interior rows: factor + forward substitution
   if (rc)
@@ -1683,14 +1689,14 @@ int block_chol_partial(const BlockEnvelope &E, double *T, double *X, double *y, 
 
 int block_chol_partial_back(const BlockEnvelope &E, double *T, double *X, double *y, int nI)
 {
-  if ((E.Bp != 40 && E.Bp != 24) || E.a_cnt)
+  if (!block_kernels_for(E.Bp) || E.a_cnt)
     return -1;
   return block_back_range(E, T, X, y, 0, nI); // x_i for the interior rows, y[nI..K) holding the separators' x
 }
 
 int block_chol_solve_tr(const BlockEnvelope &E0, double *T, double *X, double *y)
 {
-  if (E0.Bp != 40 && E0.Bp != 24)
+  if (!block_kernels_for(E0.Bp))
     return -1;
   const int K = E0.K;
   if (E0.n1 <= 0 || E0.n2 <= 0)

@@ -13,14 +13,15 @@
 namespace sage
 {
 // Padded block size of the fixed-block Cholesky for B unknowns per keyframe: the B x B blocks are padded with identity
-// rows to 24 or 40.  0: B outside 1..40, no block kernel for it.
-inline int padded_block(int B) { return B < 1 ? 0 : B <= 24 ? 24 : B <= 40 ? 40 : 0; }
+// rows to 8, 24 or 40 (8: the pose-scale systems of windows that hold every code, window_plan.h: solver_rows).  0: B
+// outside 1..40, no block kernel for it.
+inline int padded_block(int B) { return B < 1 ? 0 : B <= 8 ? 8 : B <= 24 ? 24 : B <= 40 ? 40 : 0; }
 
 // Block-envelope Cholesky solve on the storage the device scatter kernel produces (solve_kernels.hip).  Row i keeps
 // the blocks of columns B = [row_first[i], i] at T + (row_off[i] + j - row_first[i]) * Bp*Bp and, optionally, a
 // second range A = [a_first[i], a_first[i] + a_cnt[i]) (all < row_first[i]) at T + (a_off[i] + j - a_first[i]) * Bp*Bp;
 // columns between the two ranges are structurally zero in the factor.  Every block holds the TRANSPOSED block
-// ([c][r] = A[i*Bp + r][j*Bp + c]); Bp is 40 or 24.
+// ([c][r] = A[i*Bp + r][j*Bp + c]); Bp is 40, 24 or 8.
 // n1/n2 > 0 declare that rows [0,n1) and [n1,n1+n2) do not reference each other (two halves of a window split at a
 // separator, solve_kernels.hip solver_create): they are factorised concurrently on two cores when a helper thread is
 // armed (block_chol_arm, host_threads.h), otherwise one after the other.

@@ -8,6 +8,8 @@
 // Held variables (sage_window_hold): a held row / column of A is the identity's -- no off-diagonal element in its diagonal
 // block or its link blocks, diagonal 1, right-hand side 0, no prior -- so its delta is exactly zero and the free rows see
 // the system with the held variables eliminated at their current values; the retraction copies held entries bit for bit.
+// A group (pose, code, scale) that EVERY keyframe holds is not carried as identity rows at all: the system is built from the
+// kept rows only (solver rows, below; which groups those are is window_plan.h's rule).
 //
 // The three builders of A's block storage keep their own iteration (per block on the device, per keyframe and per link
 // with accumulation of duplicate links in sage_block_solve, local positions and ownership of priors in the shard); what
@@ -162,6 +164,53 @@ SAGE_HD inline int stored_slot(int r, int c, int Bp) { return c * Bp + r; }
 
 // ... and comes from this element of the packed link block (a, b), a < b, which is [row in a][column in b]
 SAGE_HD inline int link_elem(bool row_is_a, int r, int c, int B) { return row_is_a ? r * B + c : c * B + r; }
+
+// ---- solver rows: a window in which every keyframe holds a whole group (window_plan.h: solver_rows) solves blocks of the
+//      Bs kept rows only.  to_block[s] is the block row behind solver row s (null: every row is kept, s itself).  An element
+//      of the compact system IS the element of the full system at the mapped rows -- the held rule, the symmetrisation, the
+//      prior and the damping are those above, evaluated at block rows -- so the two builders below say only where to look.
+SAGE_HD inline int block_row(const int *to_block, int s) { return to_block ? to_block[s] : s; }
+
+// is element (solver row r of a keyframe held under hold_r, solver column c of one held under hold_c) a held one?
+SAGE_HD inline bool solver_elem_held(int hold_r, int hold_c, const int *to_block, int r, int c, int CS)
+{
+  return (hold_r | hold_c) && (row_held(hold_r, block_row(to_block, r), CS) || row_held(hold_c, block_row(to_block, c), CS));
+}
+
+// element (r, c) in solver rows of a keyframe's diagonal block D [B x B]; prior: of block row to_block[r]
+SAGE_HD inline double solver_diag_elem(const double *D, int B, const int *to_block, int r, int c, double prior, double damp)
+{
+  return damped_diag_elem(D, B, block_row(to_block, r), block_row(to_block, c), prior, damp);
+}
+
+// ... and where element (r in the row keyframe, c in the column keyframe) of a link block sits in the packed block [B x B]
+SAGE_HD inline int solver_link_elem(bool row_is_a, const int *to_block, int r, int c, int B)
+{
+  return link_elem(row_is_a, block_row(to_block, r), block_row(to_block, c), B);
+}
+
+// the host builder: a packed system at B (the held rule already applied: hold_packed) and its prior vectors -> the packed
+// system of the kept rows, [K diag | nlinks link | g] at Bs, and its priors [K][Bs].  Dropped rows are held rows: what is
+// left behind is rows of the identity, nothing a kept row couples to.
+inline void compact_packed(const double *packed, const double *dadd, const double *gadd, int K, int nlinks, int B, int Bs,
+                           const int *to_block, double *packed_s, double *dadd_s, double *gadd_s)
+{
+  const size_t BB = (size_t)B * B, BBs = (size_t)Bs * Bs;
+  const double *g = packed + (size_t)(K + nlinks) * BB;
+  double *g_s = packed_s + (size_t)(K + nlinks) * BBs;
+  for (int b = 0; b < K + nlinks; ++b) // diagonal and link blocks alike: [row][column], both through the map
+    for (int r = 0; r < Bs; ++r)
+      for (int c = 0; c < Bs; ++c)
+        packed_s[b * BBs + (size_t)r * Bs + c] = packed[b * BB + (size_t)block_row(to_block, r) * B + block_row(to_block, c)];
+  for (int k = 0; k < K; ++k)
+    for (int r = 0; r < Bs; ++r)
+    {
+      const size_t from = (size_t)k * B + block_row(to_block, r), to = (size_t)k * Bs + r;
+      g_s[to] = g[from];
+      dadd_s[to] = dadd[from];
+      gadd_s[to] = gadd[from];
+    }
+}
 
 // ---- the held rule on a host copy of the packed system and its prior vectors, for the host block solve (the device
 //      path applies the same element rules while it scatters): hold [K] masks, links [nlinks][2] ----

@@ -52,6 +52,7 @@ extern "C"
 #include "sage_ba.h"
 #include "sage_internal.h"
 #include "keypoint_batch.h"
+#include "window_plan.h" // SolverRows
 
 using namespace sage;
 
@@ -269,6 +270,7 @@ struct SageWindow
   std::vector<char> link_dense;           // per link: 1 = carries the dense factors (sage_window_add_link), 0 = keypoint
                                           // terms only (sage_window_add_keypoint_link)
   std::vector<uint8_t> hold;              // per keyframe: mask of held variables (sage_window_hold), empty = none
+  sage::plan::SolverRows rows;            // (finalize) the rows of a keyframe's block the solver keeps: window_plan.h
   std::vector<int> local_links;           // indices into links (links with at least one local directed edge)
   std::vector<int> owned_edges;           // this rank's directed edges, global ids 2 * link + direction, ascending: whose
                                           // keypoint terms it evaluates

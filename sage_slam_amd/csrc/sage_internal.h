@@ -272,10 +272,15 @@ hipError_t launch_gaussian_pyramid_with_grad(hipStream_t s, float *pyr, float *g
 // device retract ----
 struct DeviceSolver;
 struct SolvePriors; // damped_system.h
-// SAGE_E_UNSUPPORTED when the block solver has no kernels for B (padded_block) or the links hold a duplicate (the caller
-// keeps the host solver, which accumulates duplicate links)
-int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
-                  hipStream_t stream);
+namespace plan
+{
+struct SolverRows; // window_plan.h
+}
+// rows: the B rows of a keyframe's block in the packed buffer and the Bs of them the solver keeps (all of them unless every
+// keyframe holds a whole group).  SAGE_E_UNSUPPORTED when the block solver has no kernels for Bs (padded_block) or the links
+// hold a duplicate (the caller keeps the host solver, which accumulates duplicate links)
+int solver_create(DeviceSolver **out, int K, const plan::SolverRows &rows, int VS,
+                  const std::vector<std::pair<int, int>> &links, hipStream_t stream);
 void solver_destroy(DeviceSolver *S);
 // held variables of the window ([K] masks of SAGE_HOLD_*): applied by every later solver_run
 int solver_set_holds(DeviceSolver *S, const std::vector<uint8_t> &hold, hipStream_t stream);

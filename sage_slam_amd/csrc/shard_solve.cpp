@@ -55,7 +55,7 @@ struct SageShardPlan
   std::vector<int> int_pos;        // keyframe -> position among interior, or -1
   bool have_factor = false;        // eliminate() has left a factor for solve()
   bool assembled = false;          // domains of one assembled system (sage_shard_plan_create_domains)
-  // local block system on the fixed-block kernels of the window solve (block size padded to Bp = 24 / 40): the interior
+  // local block system on the fixed-block kernels of the window solve (block size padded to Bp = 8 / 24 / 40): the interior
   // keyframes at positions [0, nI) (elimination order) and this rank's separators at [nI, nI + nS)
   int Bp = 0, nloc = 0, nblk = 0;
   std::vector<int32_t> row_first, row_off;

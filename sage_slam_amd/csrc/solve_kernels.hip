@@ -8,7 +8,8 @@
 //
 //   scatter   packed [K diag blocks | link blocks | gradient] (double, HBM)  ->  block-envelope storage of the lower
 //             triangle (+ priors, LM damping, identity padding to Bp rows: damped_system.h), streamed into pinned host
-//             memory in the order the factorisation consumes it, a ticket per block
+//             memory in the order the factorisation consumes it, a ticket per block.  The blocks hold the SOLVER rows
+//             only: Bs <= B of them when every keyframe holds a whole group (window_plan.h: solver_rows)
 //   factor    fixed-block Cholesky + substitutions on host cores (block_solver.cpp: block_chol_solve_tr -- two halves and
 //             a separator, each half as two pipelined stages)
 //   retract   candidate variables = retract(current, delta), read zero-copy from the host's solution
@@ -31,19 +32,21 @@
 #include "host_math.h"
 #include "sage_device.h"
 #include "sage_internal.h"
+#include "window_plan.h"
 
 namespace sage
 {
 
 struct SolvePlan
 {
-  int K, B, Bp, nblk, nlinks;
+  int K, B, Bs, Bp, nblk, nlinks; // B rows per keyframe in the packed buffer, Bs of them in the solver, padded to Bp
   const int32_t *row_first; // [K] first block column of block row i
   const int32_t *row_off;   // [K] index of block (i, row_first[i]) in the block storage
   const int32_t *blk_row, *blk_col, *blk_src; // [nblk]; src = link index (bit 30: the row keyframe is the link's first
                                                // end) or -1
   const int32_t *perm, *pos; // elimination order: perm[position] = keyframe, pos[keyframe] = position
   const int32_t *hold;       // [K] masks of held variables (sage_window_hold), or null: nothing is held
+  const int32_t *to_block, *to_solver; // [Bs] solver row -> block row, [B] block row -> solver row or -1 (dropped)
 };
 
 // Head of the pinned result block; the candidate variables [K*VS floats] and the delta [K*B doubles] follow it.
@@ -75,8 +78,12 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
                                                             unsigned epoch)
 {
   const int tid = threadIdx.x;
-  const int B = P.B, Bp = P.Bp, BB = B * B;
-  __shared__ double s_dadd[64], s_gadd[64];
+  const int B = P.B, Bs = P.Bs, Bp = P.Bp, BB = B * B;
+  __shared__ double s_dadd[64], s_gadd[64]; // per solver row (Bs <= Bp <= 40)
+  __shared__ int s_row[64];                 // the block row behind it (damped_system.h: solver rows)
+  if (tid < Bs)
+    s_row[tid] = P.to_block[tid];
+  __syncthreads();
   for (int it = blockIdx.x; it < P.nblk; it += gridDim.x)
   {
     const int b = order[it];
@@ -94,10 +101,10 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
     if (i == j)
     {
       const float *var = vars0 + (size_t)kf * VS; // pose 12, scale, code CS
-      if (tid < B)
+      if (tid < Bs)
       {
         double da, ga;
-        prior_row(pri, kf, tid, CS, var, var[12], var + 13, da, ga, hold_r);
+        prior_row(pri, kf, s_row[tid], CS, var, var[12], var + 13, da, ga, hold_r);
         s_dadd[tid] = da;
         s_gadd[tid] = ga;
       }
@@ -108,17 +115,19 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
     {
       const int c = o / Bp, r = o - c * Bp; // o == stored_slot(r, c, Bp)
       double v = 0.0;
-      const bool held = (hold_r | hold_c) && r < B && c < B && (row_held(hold_r, r, CS) || row_held(hold_c, c, CS));
+      const bool in = r < Bs && c < Bs;
+      const bool held = in && solver_elem_held(hold_r, hold_c, s_row, r, c, CS);
       if (i == j)
-        v = (r < B && c < B) ? (held ? held_diag_elem(r, c) : damped_diag_elem(diag, B, r, c, s_dadd[r], damp))
-                             : damped_pad_elem(r, c, damp);
-      else if (r < B && c < B && !held)
-        v = lnk[link_elem(row_is_a, r, c, B)];
+        v = in ? (held ? held_diag_elem(r, c) : solver_diag_elem(diag, B, s_row, r, c, s_dadd[r], damp))
+               : damped_pad_elem(r, c, damp);
+      else if (in && !held)
+        v = lnk[solver_link_elem(row_is_a, s_row, r, c, B)];
       out[o] = v;
     }
     if (i == j)
       for (int r = tid; r < Bp; r += blockDim.x)
-        y[(size_t)i * Bp + r] = (r < B && !(hold_r && row_held(hold_r, r, CS))) ? damped_rhs_elem(g[r], s_gadd[r]) : 0.0;
+        y[(size_t)i * Bp + r] =
+            (r < Bs && !(hold_r && row_held(hold_r, s_row[r], CS))) ? damped_rhs_elem(g[s_row[r]], s_gadd[r]) : 0.0;
     // the block (and its rhs rows) are visible to the host before the ticket is: the workgroup barrier orders every
     // lane's stores before lane 0's system-scope release (one cache write-back per block instead of one per wave)
     __syncthreads();
@@ -140,6 +149,7 @@ __global__ __launch_bounds__(256) void solve_scatter_kernel(const SolvePlan P, c
 __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__restrict__ x, int K, int B, int Bp, int CS,
                                                             int VS, const int32_t *__restrict__ pos,
                                                             const int32_t *__restrict__ hold,
+                                                            const int32_t *__restrict__ to_solver,
                                                             const float *__restrict__ vars0,
                                                             float *__restrict__ vars1, float *__restrict__ h_vars,
                                                             double *__restrict__ h_delta, SolveResult *h_res,
@@ -190,8 +200,9 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
   for (int idx = tid; idx < K * B; idx += blockDim.x)
   {
     const int k = idx / B, r = idx - k * B;
-    const bool held = hold && row_held(hold[k], r, CS); // delta exactly zero, the entry copied bit for bit
-    const double d = held ? 0.0 : x[(size_t)pos[k] * Bp + r]; // x is in elimination order
+    // delta exactly zero, the entry copied bit for bit (a row the solver dropped is a row every keyframe holds)
+    const bool held = hold && row_held(hold[k], r, CS);
+    const double d = held ? 0.0 : x[(size_t)pos[k] * Bp + to_solver[r]]; // x: elimination order, solver rows
     h_delta[idx] = d;
     nrm += d * d;
     const float *v0 = vars0 + (size_t)k * VS;
@@ -207,15 +218,17 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
   {
     const double *xk = x + (size_t)pos[k] * Bp;
     const float *v0 = vars0 + (size_t)k * VS;
-    float d6[6];
-    for (int i = 0; i < 6; ++i)
-      d6[i] = (float)xk[i];
     float *o = vars1 + (size_t)k * VS; // the device candidate; the host mirror gets its copy
     if (hold && (hold[k] & kHoldPose)) // (se3_exp of a zero delta is not the identity in fp32)
       for (int i = 0; i < 12; ++i)
         o[i] = v0[i];
     else
+    {
+      float d6[6];
+      for (int i = 0; i < 6; ++i)
+        d6[i] = (float)xk[to_solver[i]];
       pose_retract(v0, d6, o);
+    }
     for (int i = 0; i < 12; ++i)
       h_vars[(size_t)k * VS + i] = o[i];
   }
@@ -239,7 +252,7 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
 // ------------------------------------------------------------------------------------------------
 struct DeviceSolver
 {
-  int K = 0, B = 0, Bp = 0, nblk = 0, nlinks = 0, VS = 0;
+  int K = 0, B = 0, Bs = 0, Bp = 0, nblk = 0, nlinks = 0, VS = 0;
   void *d_int = nullptr;    // all int tables in one allocation
   void *d_hold = nullptr;   // [K] masks of held variables (solver_set_holds), or null
   void *h_pinned = nullptr; // [SolveResult | K*VS floats | K*B doubles]
@@ -272,11 +285,12 @@ struct DeviceSolver
   double *host_delta() const { return reinterpret_cast<double *>(reinterpret_cast<char *>(h_pinned) + result_delta_offset(K, VS)); }
 };
 
-int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<std::pair<int, int>> &links,
-                  hipStream_t stream)
+int solver_create(DeviceSolver **out, int K, const plan::SolverRows &rows, int VS,
+                  const std::vector<std::pair<int, int>> &links, hipStream_t stream)
 {
   *out = nullptr;
-  const int Bp = sage::padded_block(B);
+  const int B = rows.B, Bs = rows.Bs;
+  const int Bp = sage::padded_block(Bs);
   if (Bp == 0 || K < 1)
     return SAGE_E_UNSUPPORTED;
   BlockPlan bp;
@@ -288,7 +302,7 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
                              &a_cnt = bp.a_cnt, &a_off = bp.a_off, &blk_row = bp.blk_row, &blk_col = bp.blk_col,
                              &blk_src = bp.blk_src;
   std::unique_ptr<DeviceSolver> S(new DeviceSolver); // (an early return releases what has been allocated so far)
-  S->K = K; S->B = B; S->Bp = Bp; S->nblk = nblk; S->nlinks = (int)links.size(); S->VS = VS;
+  S->K = K; S->B = B; S->Bs = Bs; S->Bp = Bp; S->nblk = nblk; S->nlinks = (int)links.size(); S->VS = VS;
   // one allocation for the int tables
   std::vector<int32_t> all;
   auto put = [&](const std::vector<int32_t> &v) {
@@ -324,6 +338,7 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
     for (int i = 0; i < K; ++i)
       push_row(i);
   const size_t o_ord = put(order);
+  const size_t o_tb = put(rows.to_block), o_ts = put(rows.to_solver);
   if (hipMalloc(&S->d_int, all.size() * sizeof(int32_t)) != hipSuccess)
     return (int)hipErrorOutOfMemory;
   if (hipMemcpyAsync(S->d_int, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess)
@@ -344,9 +359,10 @@ int solver_create(DeviceSolver **out, int K, int B, int VS, const std::vector<st
   std::memset(S->h_pinned, 0, h_bytes);
   const int32_t *base = reinterpret_cast<const int32_t *>(S->d_int);
   SolvePlan &P = S->plan;
-  P.K = K; P.B = B; P.Bp = Bp; P.nblk = nblk; P.nlinks = (int)links.size();
+  P.K = K; P.B = B; P.Bs = Bs; P.Bp = Bp; P.nblk = nblk; P.nlinks = (int)links.size();
   P.row_first = base + o_rf; P.row_off = base + o_ro;
   P.blk_row = base + o_br; P.blk_col = base + o_bc; P.blk_src = base + o_bs; P.perm = base + o_pm; P.pos = base + o_ps;
+  P.to_block = base + o_tb; P.to_solver = base + o_ts;
   S->d_order = base + o_ord;
   S->h_fill.assign((size_t)nblk, 0);
   for (int b = 0; b < nblk; ++b)
@@ -405,7 +421,8 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   if (S->go_epoch == 0)
     S->go_epoch = 1;
   hipLaunchKernelGGL(solve_retract_kernel, dim3(1), dim3(1024), 0, stream, S->h_y, S->K, S->B, S->Bp, CS, S->VS,
-                     S->plan.pos, S->plan.hold, vars0, vars1, S->host_vars(), S->host_delta(), S->result(), S->go_epoch);
+                     S->plan.pos, S->plan.hold, S->plan.to_solver, vars0, vars1, S->host_vars(), S->host_delta(),
+                     S->result(), S->go_epoch);
   if ((eh = hipGetLastError()) != hipSuccess)
     return (int)eh;
   struct GoGuard // whatever happens below, the waiting kernel gets its word

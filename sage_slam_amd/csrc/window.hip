@@ -7,6 +7,7 @@
 extern "C" int sage_window_num_keyframes(const SageWindow *w) { return w ? w->K : 0; }
 extern "C" int sage_window_num_links(const SageWindow *w) { return w ? (int)w->links.size() : 0; }
 extern "C" int sage_window_block_size(const SageWindow *w) { return w ? w->B : 0; }
+extern "C" int sage_window_solver_block_size(const SageWindow *w) { return w && w->finalized ? w->rows.Bs : 0; }
 extern "C" size_t sage_window_packed_count(const SageWindow *w)
 {
   if (!w)

@@ -769,7 +769,7 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
 //     solve, the shard plan with its separator buffers
 static int finalize_solver(SageWindow *w, const FinalizeState &fs)
 {
-  int rc = solver_create(&w->solver, w->K, w->B, w->VS, w->links, w->stream);
+  int rc = solver_create(&w->solver, w->K, w->rows, w->VS, w->links, w->stream);
   if (rc != SAGE_OK && rc != SAGE_E_UNSUPPORTED)
     return rc;
   if (w->solver && window_has_holds(w) && (rc = solver_set_holds(w->solver, w->hold, w->stream)))
@@ -797,6 +797,7 @@ extern "C" int sage_window_finalize(SageWindow *w)
   w->hold.resize(w->K, 0);
   if (fs.domain_solve && window_has_holds(w))
     return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables)
+  w->rows = plan::solver_rows(w->hold.data(), w->K, w->cfg.CS);
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||

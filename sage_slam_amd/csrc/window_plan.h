@@ -1,5 +1,6 @@
 // window_plan.h -- the build-time policy of the window engine as pure integer arithmetic: which directed edges a rank owns,
-// which of them are dense, whether a window uses the domain-decomposed solve, the run lengths of the two work lists.  Standard library only -- no HIP, no
+// which of them are dense, whether a window uses the domain-decomposed solve, which rows of a keyframe's block the solver keeps,
+// the run lengths of the two work lists.  Standard library only -- no HIP, no
 // environment: the runtime applies its overrides to the results (window_build.hip), and tests/test_window_plan.py compiles
 // this header with a host compiler.  An edge's length is its number of SUB-TILES (ceil(samples / kTile)) throughout.
 #pragma once
@@ -69,6 +70,40 @@ inline std::vector<int> dense_edges(const std::vector<int> &owned, const std::ve
 inline bool uses_domain_solve(int world, int K, int requested)
 {
   return world > 1 && (requested >= 0 ? requested != 0 : K >= 256);
+}
+
+// ---- solver rows.  A keyframe's block has B = 7 + CS rows in three groups: pose 6, code CS, scale 1 (hold-mask bits 1, 2, 4:
+//      sage_window_hold).  A group that EVERY keyframe of the window holds is left out of the damped system altogether: the
+//      window then solves blocks of Bs < B rows, the kept groups in block order.  Holds inside a kept group stay rows of the
+//      identity inside the smaller block (damped_system.h).  Nothing dropped, or everything: the window solves at B as ever.
+struct SolverRows
+{
+  int B = 0, Bs = 0;          // rows of a keyframe's block / of its block in the solver
+  int kept = 7;               // mask of the groups the solver keeps
+  std::vector<int> to_block;  // [Bs] solver row -> block row
+  std::vector<int> to_solver; // [B] block row -> solver row, -1: dropped
+  bool compact() const { return Bs != B; }
+};
+
+inline SolverRows solver_rows(const unsigned char *hold, int K, int CS)
+{
+  const int first[3] = {0, 6, 6 + CS}, size[3] = {6, CS, 1};
+  SolverRows s;
+  s.B = 7 + CS;
+  int all = K > 0 ? 7 : 0; // the groups every keyframe holds
+  for (int k = 0; k < K; ++k)
+    all &= hold ? hold[k] : 0;
+  s.kept = (all == 7) ? 7 : (7 & ~all);
+  s.to_solver.assign(s.B, -1);
+  for (int grp = 0; grp < 3; ++grp)
+    if (s.kept & (1 << grp))
+      for (int r = first[grp]; r < first[grp] + size[grp]; ++r)
+      {
+        s.to_solver[r] = (int)s.to_block.size();
+        s.to_block.push_back(r);
+      }
+  s.Bs = (int)s.to_block.size();
+  return s;
 }
 
 // ---- run lengths of the work lists

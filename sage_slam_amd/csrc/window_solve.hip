@@ -159,9 +159,25 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
   const bool holds = window_has_holds(w);
   if (holds) // the held rule on the host copy (damped_system.h); `packed` itself is untouched
     sage::hold_packed(w->host_packed.data(), dadd.data(), gadd.data(), K, (int)w->links.size(), lk.data(), B, CS, w->hold.data());
-  int rcs = sage_block_solve(w->host_packed.data(), K, (int)w->links.size(), lk.data(), B, damp, dadd.data(),
-                             gadd.data(), w->delta.data()); // (writes delta only on success)
-  if (rcs)
+  int rcs;
+  if (w->rows.compact())
+  {
+    // every keyframe holds a whole group: the system of the kept rows only (damped_system.h: solver rows), solved at Bs;
+    // the delta keeps its [K][B] layout, zeros on the dropped rows
+    const int Bs = w->rows.Bs, nl = (int)w->links.size();
+    std::vector<double> ps((size_t)(K + nl) * Bs * Bs + (size_t)K * Bs);
+    std::vector<double> ds((size_t)K * Bs), gs((size_t)K * Bs), xs((size_t)K * Bs);
+    sage::compact_packed(w->host_packed.data(), dadd.data(), gadd.data(), K, nl, B, Bs, w->rows.to_block.data(), ps.data(),
+                         ds.data(), gs.data());
+    if ((rcs = sage_block_solve(ps.data(), K, nl, lk.data(), Bs, damp, ds.data(), gs.data(), xs.data())))
+      return rcs;
+    std::fill(w->delta.begin(), w->delta.end(), 0.0);
+    for (int k = 0; k < K; ++k)
+      for (int s = 0; s < Bs; ++s)
+        w->delta[(size_t)k * B + w->rows.to_block[s]] = xs[(size_t)k * Bs + s];
+  }
+  else if ((rcs = sage_block_solve(w->host_packed.data(), K, (int)w->links.size(), lk.data(), B, damp, dadd.data(),
+                                   gadd.data(), w->delta.data()))) // (writes delta only on success)
     return rcs;
   if (holds) // exactly zero, whatever sign the substitution left
     for (int k = 0; k < K; ++k)

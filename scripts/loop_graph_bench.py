@@ -6,8 +6,9 @@ closures of BASELINE config 5 as KEYPOINT links -- no dense edge at all --, one 
 
 Prints the ms per LM step (median of the steady iterations of sage_window_lm_run_timed) and its phase split on the stream's
 timeline (sage_window_get_phase_time: linearize = the one keypoint launch + assembly, solve = scatter + host factorisation +
-retract, error pass), the batched kernel's own time per launch, and one JSON line.  The block size stays B = 7 + CS with CS
-identity rows per keyframe: the solve is expected to cost about what config 5's costs.
+retract, error pass), the batched kernel's own time per launch, and one JSON line.  Every keyframe holds its code, so the
+solver works on the pose and scale rows only: blocks of Bs = 7 rows (padded to Bp = 8) out of the B = 7 + CS of the packed
+buffer (sage_window_solver_block_size).  profiles/loop_graph_bench.txt has the measurement.
 
     python scripts/loop_graph_bench.py [--keyframes 512 --height 64 --width 80 --points 128 --no-loops --out FILE]
 """
@@ -90,6 +91,8 @@ def main():
     holds = {k: capi.SAGE_HOLD_CODE for k in range(K)}
     holds[0] = capi.SAGE_HOLD_POSE | capi.SAGE_HOLD_CODE | capi.SAGE_HOLD_SCALE
     win = capi.Window(dataclasses.replace(w, links=[]), keypoint_links=links, keypoint_terms=terms, holds=holds)
+    Bs = win.Bs
+    Bp = 8 if Bs <= 8 else 24 if Bs <= 24 else 40                     # block_solver.h: padded_block
     step_ms, n_steps = lm_step_ms(capi, win)
     phases, (lin_us, err_us), dense_launches = phase_split_ms(capi, win)
     st = capi.SageLmState(); st.damp = 1e-3
@@ -97,7 +100,7 @@ def main():
     tr = win.lm_run(st, lm_cfg(capi), 6)
     win.close()
     other = step_ms - sum(phases.values())
-    lines = [f"loop_graph_bench: K {K}, {args.height} x {args.width}, CS 32 (B = 39), {len(links)} keypoint links "
+    lines = [f"loop_graph_bench: K {K}, {args.height} x {args.width}, CS 32 (B = {win.B}, solver rows Bs = {Bs}, padded Bp = {Bp}), {len(links)} keypoint links "
              f"({'no' if args.no_loops else len(links) - len(w.links)} loop closures), {len(terms)} loop-MG terms of {args.points} "
              f"points, all codes and keyframe 0 held; device {torch.cuda.get_device_name(0)}",
              f"LM step                                    {step_ms:8.3f} ms   (median of {n_steps} steady iterations)",
@@ -115,7 +118,7 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(text + "\n")
-    print(json.dumps(dict(keyframes=K, links=len(links), terms=len(terms), points=args.points, step_ms=step_ms, phases_ms=phases,
+    print(json.dumps(dict(keyframes=K, links=len(links), terms=len(terms), points=args.points, B=win.B, Bs=Bs, Bp=Bp, step_ms=step_ms, phases_ms=phases,
                           kernel_linearize_us=lin_us, kernel_error_us=err_us, dense_launches=dense_launches)))
     return 0
 
