@@ -333,6 +333,15 @@ static int upload_work_list(DenseSide &sd, const WorkList &wl, hipStream_t s)
   return SAGE_OK;
 }
 
+// what was assembled or evaluated under the previous photometric plan is not this plan's: another run length sums in another
+// fp32 order, so `packed`, the error kept for the linearize-at-candidate sequence and the depth maps' booking are dropped
+static void window_invalidate_plan_results(SageWindow *w)
+{
+  w->have_lin = false;
+  w->spec_err_valid = false;
+  w->dpt_set = -1;
+}
+
 // (re)build the photometric work list for runs of `tpb` sub-tiles and upload it; the partial-record buffer grows to fit
 static int window_plan_photo_runs(SageWindow *w, int tpb, int flush)
 {
@@ -815,14 +824,18 @@ extern "C" int sage_window_finalize(SageWindow *w)
 }
 
 // the run length a previous sage_window_tune_runs found for this window geometry (an embedder tunes once per image size / mask / window
-// length and re-applies the result to the windows it builds afterwards: the tuning costs 20-40 ms, a window lives for a few LM steps)
+// length and re-applies the result to the windows it builds afterwards: the tuning costs 20-40 ms, a window lives for a few LM steps).
+// A system assembled before the call belongs to the previous plan and is dropped: a linearize must follow (sage_window_lm_step
+// does its own; sage_window_solve answers SAGE_E_STATE until then), so that results stay bit-reproducible for the run length
 extern "C" int sage_window_set_runs(SageWindow *w, int tpb)
 {
   if (!w || !w->finalized)
     return SAGE_E_STATE;
   if (tpb < 1 || tpb > 64)
     return SAGE_E_INVALID;
-  return window_plan_photo_runs(w, tpb, photo_flush_for_runs(tpb));
+  const int rc = window_plan_photo_runs(w, tpb, photo_flush_for_runs(tpb));
+  window_invalidate_plan_results(w);
+  return rc;
 }
 
 // r06 -- run-length tuning of the photometric kernels, measured on the window itself.  The time of the photometric linearize
@@ -834,6 +847,8 @@ extern "C" int sage_window_set_runs(SageWindow *w, int tpb)
 // the rule's choice by >= 4 % (so that equal candidates do not flip between calls: results are bit-reproducible for a given run
 // length, not across run lengths).  Opt-in: an explicit call, or SAGE_AUTOTUNE=1 at sage_window_finalize; SAGE_PHOTO_TPB pins
 // the run length and disables it.  Single-rank windows only (a sharded window's linearize contains a collective).
+// The timed evaluations leave `packed` assembled under whichever plan was measured last, not necessarily the one kept: it is
+// dropped at the end, and a linearize must follow (as after sage_window_set_runs).
 extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_out, float *ms_rule_out, float *ms_best_out)
 {
   if (!w || !w->finalized)
@@ -905,6 +920,7 @@ extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_
   if (!rc && !(best_ms < 0.96 * rule_ms))
     best = rule;
   const int rc2 = window_plan_photo_runs(w, rc ? rule : best, photo_flush_for_runs(rc ? rule : best));
+  window_invalidate_plan_results(w);
   if (tpb_out)
     *tpb_out = w->dense[kPhoto].tpb;
   if (ms_rule_out)

@@ -73,11 +73,40 @@ def pose_local(origin, other):
     return np.concatenate([other[9:] - Rr @ origin[9:], k * np.array([Rr[2, 1] - Rr[1, 2], Rr[0, 2] - Rr[2, 0], Rr[1, 0] - Rr[0, 1]])])
 
 
-def prior_vectors(w, CS, code_w=1e-3, codes=None, pose0=None, scale0=None):
+def _se3_exp(d6, prec):
+    """exp of the twist [v, omega] by the oracle's statement of the reference formula (mapping_utils.h:316-346) -> (dR, dt)"""
+    from oracle import oracle as orc
+    return orc.se3_exp(d6[3:], d6[:3], prec=prec)
+
+
+def retract_ref(pose12, d6):
+    """The window's pose retraction in fp64: the left update exp([v, omega]) * pose (gtsam_traits.h:45-70,
+    camera_tracker.cpp:491-512) of a pose [R row-major | t].  The twist is the fp32-rounded `d6`, as the retract kernel
+    casts the fp64 solution before it takes the exponential; everything after that rounding is double."""
+    pose = np.asarray(pose12, np.float64).reshape(12)
+    dR, dt = _se3_exp(np.asarray(d6, np.float32).astype(np.float64), "f64")
+    return np.concatenate([(dR @ pose[:9].reshape(3, 3)).reshape(9), dR @ pose[9:] + dt])
+
+
+def retract_ref_f32(pose12, d6):
+    """fp32 twin of retract_ref, the "fp32 oracle" of the retraction: the oracle's fp32 exponential and a composition in
+    numpy float32 with the products summed left to right, as damped_system.h pose_retract writes them."""
+    pose = np.asarray(pose12, np.float32).reshape(12)
+    dR, dt = _se3_exp(np.asarray(d6, np.float32), "f32")
+    R, t = pose[:9].reshape(3, 3), pose[9:]
+    Ro = (dR[:, 0:1] * R[0:1, :] + dR[:, 1:2] * R[1:2, :]) + dR[:, 2:3] * R[2:3, :]
+    to = ((dR[:, 0] * t[0] + dR[:, 1] * t[1]) + dR[:, 2] * t[2]) + dt
+    out = np.concatenate([Ro.reshape(9), to])
+    assert out.dtype == np.float32
+    return out
+
+
+def prior_vectors(w, CS, code_w=1e-3, codes=None, pose0=None, scale0=None, pose_w=1e4, scale_w=1e4):
     """Diagonal and gradient additions of the engine's default priors (SageWindowConfig): code prior `code_w` towards zero on
-    every keyframe, scale and pose prior 1e4 on keyframe 0 (code_factor.cpp:55-56,99-104; scale_factor.cpp:122-124;
-    df_work.cpp:24-34).  The initial values are the window's; `codes` [K, CS], `pose0` [R row-major | t] and `scale0` are the
-    current ones where they have moved (after an accepted step): the scale and pose priors then have a gradient."""
+    every keyframe, scale and pose prior 1e4 (`scale_w`, `pose_w`) on keyframe 0 (code_factor.cpp:55-56,99-104;
+    scale_factor.cpp:122-124; df_work.cpp:24-34).  The initial values are the window's; `codes` [K, CS], `pose0`
+    [R row-major | t] and `scale0` are the current ones where they have moved (after an accepted step): the scale and pose
+    priors then have a gradient.  The engine holds its weights as floats: a bar below 1e-7 wants `code_w` as float32(1e-3)."""
     K, B = len(w.keyframes), 7 + CS
     dadd = np.zeros(K * B); gadd = np.zeros(K * B)
     for k, kf in enumerate(w.keyframes):
@@ -87,11 +116,11 @@ def prior_vectors(w, CS, code_w=1e-3, codes=None, pose0=None, scale0=None):
     kf0 = w.keyframes[0]
     s_init = float(kf0.scale)
     s = s_init if scale0 is None else float(scale0)
-    dadd[6 + CS] += 1e4 / (s * s)
-    dadd[:6] += 1e4
+    dadd[6 + CS] += scale_w / (s * s)
+    dadd[:6] += pose_w
     if scale0 is not None:
-        gadd[6 + CS] += 1e4 / s * (np.log(s_init) - np.log(s))
+        gadd[6 + CS] += scale_w / s * (np.log(s_init) - np.log(s))
     if pose0 is not None:
         init = np.concatenate([np.asarray(kf0.R, np.float32).ravel(), np.asarray(kf0.t, np.float32).ravel()])
-        gadd[:6] += 1e4 * pose_local(pose0, init)
+        gadd[:6] += pose_w * pose_local(pose0, init)
     return dadd, gadd

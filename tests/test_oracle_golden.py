@@ -236,6 +236,25 @@ def test_se3_exp_and_retraction_match_reference_python(orc, prec):
         assert np.allclose(upd[13:], c["code0"] + sol[7:], rtol=1e-6, atol=1e-7)
 
 
+def test_retraction_references_match_reference_python(orc):
+    """tests/helpers.py retract_ref (fp64) and retract_ref_f32 (its fp32 twin), the references the device retraction is
+    measured against in tests/test_gpu_window_candidate.py, against DiffBundleAdjustment.update_variables on the same
+    fixture and by the same tolerances as the product's host helper above."""
+    from sage_slam_amd import capi
+    from tests.helpers import retract_ref, retract_ref_f32
+    c = load("diffba_retract")
+    pose0 = np.concatenate([c["R0"].reshape(-1), c["t0"]]).astype(np.float32)
+    for sol, upd in zip(c["sol"], c["updated"]):
+        d6 = np.concatenate([sol[3:6], sol[0:3]])                               # [v, omega]
+        for fn, dtype in ((retract_ref, np.float64), (retract_ref_f32, np.float32)):
+            out = fn(pose0, d6)
+            assert out.dtype == dtype and out.shape == (12,)
+            assert rel(out[:9], upd[:9]) < 3e-6 and rel(out[9:], upd[9:12]) < 1e-5
+        # the product's host helper is the fp32 twin's arithmetic (damped_system.h pose_retract)
+        host, twin = capi.pose_retract(pose0, d6), retract_ref_f32(pose0, d6)
+        assert rel(host[:9], twin[:9]) < 3e-6 and rel(host[9:], twin[9:]) < 1e-5
+
+
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_multilevel_photometric_error_matches_reference_python(orc, prec):
     """The multi-level coordinate rule and level weighting (a2/a3): compute_photo_error (diff_ba.py:1853-1939) over a
