@@ -402,7 +402,7 @@ int sage_window_solver_block_size(const SageWindow *w); /* Bs <= B: rows per key
                                                           * before finalize or for NULL */
 /* packed normal-equation buffer (device, DOUBLE), the all-reduce payload:
  *   [ diag blocks K*B*B | link blocks nlinks*B*B (row = older kf, col = newer kf) | g K*B | err_photo err_geo n_photo n_geo ]
- * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry and loop-MG terms';
+ * (windows with keypoint terms: err_photo also carries the reprojection terms' errors, err_geo the match-geometry, loop-MG and graph terms';
  * the two inlier counts stay dense-only -- see sage_window_add_keypoint_term)
  * fp32 per-edge results are summed in double, like the reference widens AtA/Atb to double before gtsam adds
  * the factors (core/gtsam/photometric_factor.cpp:305-306); keeping the payload in double keeps the sum exact
@@ -410,7 +410,7 @@ int sage_window_solver_block_size(const SageWindow *w); /* Bs <= B: rows per key
 size_t sage_window_packed_count(const SageWindow *w);
 double *sage_window_packed_dev(SageWindow *w);
 /* number of residuals one linearize evaluates on this shard (E_photo*L*N*FS + E_geo*N, + 2N / 3N per reprojection /
- * match-geometry / loop-MG term) and its algorithmic bytes (dense factors) */
+ * match-geometry / loop-MG term, + 7 / 6 / 1 per graph term) and its algorithmic bytes (dense factors) */
 double sage_window_residuals_per_linearize(const SageWindow *w);
 double sage_window_bytes_per_linearize(const SageWindow *w);
 
@@ -501,6 +501,55 @@ int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTerm *t);
 int sage_window_num_keypoint_terms(const SageWindow *w);
 int sage_window_get_keypoint_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err, float *n_in);
 
+/* Pose-graph terms of a window: the factors of the graph the reference solves after every accepted global loop,
+ * DeepFactors::LoopClosurePoseScaleEstimate (core/deepfactors.cpp:58-386; called at :1134 and :1208).  That graph holds no
+ * keypoint: it is RelPoseScaleFactors on both directions of every link, a pose prior and a ScaleFactor on the first keyframe
+ * and two ScaleFactors on the newest loop's keyframes.  With R10 = R1^T R0, t10 = R1^T (t0 - t1) of the window's poses and
+ * (Rt, tt, ts0, ts1) the term's target, the residuals r = target - current are
+ *   kind SAGE_GRAPH_REL_POSE_SCALE  tt / ts0 - t10 / s0 (3), sqrt(rot_weight) (log Rt - log R10) (3),
+ *                                   sqrt(scale_weight) (log(ts1 / ts0) - log(s1 / s0)) (1)   (rel_pose_scale_factor.cpp:207-344)
+ *   kind SAGE_GRAPH_REL_POSE        tt - t10 (3), sqrt(rot_weight) (log Rt - log R10) (3)     (rel_pose_factor.cpp:150-262)
+ *   kind SAGE_GRAPH_SCALE_PRIOR     log(ts0) - log(s) of keyframe `kf` (1)                    (scale_factor.cpp:102-129)
+ * and error = weight |r|^2, AtA = weight J^T J, Atb = weight J^T r with J = d current / d [delta0 delta1 s0 s1] under the
+ * window's left retraction.  The error is the reference's as written; J is its exact derivative, which differs from the
+ * reference's matrix in two places: rel_pose_scale_factor.cpp:288 / rel_pose_factor.cpp:229 form d pose10 / d pose1^-1 as
+ * kron(pose0, I3) where the derivative is kron(pose0^T, I3) (its pose1 columns are off by 0.5 to 2 on unit-size inputs; with
+ * the transpose the pose1 block is exactly minus the pose0 block), and rel_pose_scale_factor.cpp:320 uses the TARGET's
+ * translation in the scale0 column (-tt / s0^2) where the derivative is -t10 / s0^2.  There is no "as written" mode.  log R
+ * and its derivative are accurate from the identity (bit-exact zero) to a relative rotation of 2.5 rad; the neighbourhood of
+ * pi is outside the reference's formula and outside this one.  No NearestPsd on the window path, as for every other term.
+ * `edge` = 2 * link + direction as sage_window_get_edge numbers them; keyframe "0" is the direction's source.  Add after the
+ * edge's link (a dense or a keypoint link) and before sage_window_finalize (SAGE_E_STATE afterwards); any number of terms per
+ * edge; SAGE_E_INVALID for a bad kind / edge / keyframe, a weight or a target scale of the kind that is not positive, a negative
+ * rot_weight / scale_weight, or a target that is not finite.  Host data only, copied by the call.  Returns the
+ * term id >= 0 (ids count the graph terms of the window, apart from the keypoint terms').
+ * The terms are evaluated in one launch per linearize / error pass and summed into the same packed system and totals as
+ * everything else -- only pose and scale rows receive anything; their errors ride in the geometric slot behind the loop-MG
+ * terms'; sage_window_residuals_per_linearize counts 7 / 6 / 1 per term.  sage_window_solve, the LM entry points, holds, solver
+ * rows and the reduced (sharded) sequences see them without knowing.  On a sharded window a binary term belongs to the rank
+ * that owns its directed edge and a scale prior to rank 0; a window of the domain-decomposed solve with a graph term answers
+ * SAGE_E_UNSUPPORTED at finalize.
+ * get_graph_term: host copy of the term's last linearize in the D = 14 layout [pose0 pose1 scale0 scale1] for every kind
+ * (AtA [14,14], Atb [14], error; columns a kind does not have read zero -- a scale prior sits at [12]); SAGE_E_STATE before
+ * the first linearize, SAGE_E_INVALID for a term of another rank.
+ * LoopClosurePoseScaleEstimate as a window: keypoint links for the graph's links, every code held, keyframe 0's pose held (the
+ * sigma = 1e-4 prior), scale_prior_weight = 0 and a weight-100 SAGE_GRAPH_SCALE_PRIOR on keyframe 0 at its scale, two
+ * REL_POSE_SCALE terms per link (the second with the inverse target and the scales swapped), SCALE_PRIORs on the newest loop's
+ * two keyframes. */
+enum { SAGE_GRAPH_REL_POSE_SCALE = 0, SAGE_GRAPH_REL_POSE = 1, SAGE_GRAPH_SCALE_PRIOR = 2 };
+typedef struct SageGraphTerm /* host data only, copied by the call */
+{
+  int32_t kind;
+  int32_t edge;                       /* binary kinds: 2*link + direction; keyframe "0" = the direction's source */
+  int32_t kf;                         /* SCALE_PRIOR: the keyframe */
+  float target_pose10[12];            /* target of pose1^-1 * pose0, R row-major then t */
+  float target_scale0, target_scale1; /* > 0; SCALE_PRIOR uses target_scale0 */
+  float weight, rot_weight, scale_weight;
+} SageGraphTerm;
+int sage_window_add_graph_term(SageWindow *w, const SageGraphTerm *t); /* term id >= 0 */
+int sage_window_num_graph_terms(const SageWindow *w);
+int sage_window_get_graph_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err);
+
 /* f2 (core/gtsam/photometric_factor.cpp:72-219, geometric_factor.cpp:41-233, mapper.cpp:544-551): the
  * batched per-Values prepass behind the gtsam factors.  ISAM2 calls linearize(values) / error(values) factor by factor
  * with the same Values; the adapter's factor hands the window's values over and the engine evaluates the WHOLE window
@@ -535,7 +584,8 @@ int sage_factor_cut_blocks(int type, int CS, const double *C, const float *Atb, 
 
 /* kernel timing with HIP events on the engine's own stream (bench.py's roofline): when enabled every launch of
  * the hot kernels is bracketed by an event pair.  which: 0 photometric linearize, 1 geometric linearize,
- * 2 photometric error, 3 geometric error, 4 keypoint-term linearize, 5 keypoint-term error.  get_kernel_time synchronises, returns the accumulated milliseconds and
+ * 2 photometric error, 3 geometric error, 4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term
+ * error.  get_kernel_time synchronises, returns the accumulated milliseconds and
  * launch count since the last reset, and resets them. */
 /* on: 0 off, 1 every hot kernel + the phase marks, 2 the photometric linearize only (two event records per iteration
  * instead of eleven: each record is a few microseconds of the stream's time). */

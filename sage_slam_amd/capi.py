@@ -88,6 +88,32 @@ def kp_term_dim(kind, CS: int) -> int:
     return {SAGE_KP_REPROJECTION: 13 + CS, SAGE_KP_MATCH_GEOMETRY: 14 + 2 * CS, SAGE_KP_LOOP_MG: 14}[kind]
 
 
+SAGE_GRAPH_REL_POSE_SCALE, SAGE_GRAPH_REL_POSE, SAGE_GRAPH_SCALE_PRIOR = 0, 1, 2
+GRAPH_KINDS = {"rel_pose_scale": SAGE_GRAPH_REL_POSE_SCALE, "rel_pose": SAGE_GRAPH_REL_POSE, "scale_prior": SAGE_GRAPH_SCALE_PRIOR}
+GRAPH_TERM_DIM = 14                      # [pose0 pose1 scale0 scale1] for every kind
+GRAPH_KIND_ROWS = {SAGE_GRAPH_REL_POSE_SCALE: 7, SAGE_GRAPH_REL_POSE: 6, SAGE_GRAPH_SCALE_PRIOR: 1}
+
+
+class SageGraphTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("edge", C.c_int32), ("kf", C.c_int32), ("target_pose10", C.c_float * 12),
+                ("target_scale0", C.c_float), ("target_scale1", C.c_float), ("weight", C.c_float), ("rot_weight", C.c_float),
+                ("scale_weight", C.c_float)]
+
+
+def graph_term_struct(t) -> SageGraphTerm:
+    """dict -> ``SageGraphTerm``: kind (a GRAPH_KINDS name or SAGE_GRAPH_*), edge or kf, target_pose10 [12] (R row-major, t),
+    target_scale0 / target_scale1, weight, rot_weight, scale_weight; what a kind does not use may be left out."""
+    gt = SageGraphTerm()
+    gt.kind = int(GRAPH_KINDS.get(t["kind"], t["kind"]))
+    gt.edge, gt.kf = int(t.get("edge", 0)), int(t.get("kf", 0))
+    tp = np.asarray(t.get("target_pose10", [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]), np.float32).reshape(12)
+    for i in range(12):
+        gt.target_pose10[i] = float(tp[i])
+    gt.target_scale0, gt.target_scale1 = float(t.get("target_scale0", 1.0)), float(t.get("target_scale1", 1.0))
+    gt.weight, gt.rot_weight, gt.scale_weight = float(t["weight"]), float(t.get("rot_weight", 1.0)), float(t.get("scale_weight", 1.0))
+    return gt
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -116,7 +142,7 @@ SYMBOLS = [
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
     "sage_window_error", "sage_window_tune_runs", "sage_window_set_runs", "sage_window_error_dev", "sage_window_solve", "sage_window_total_error",
     "sage_window_accept", "sage_window_reset", "sage_window_get_keyframe", "sage_window_set_keyframe", "sage_window_get_delta",
-    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_factor_psd", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
+    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_add_graph_term", "sage_window_num_graph_terms", "sage_window_get_graph_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_factor_psd", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
     "sage_valid_locations", "sage_shuffle_indices", "sage_sample_locations",
     "sage_reprojection_jac_error_calculate", "sage_reprojection_error_calculate",
     "sage_tracker_reproj_jac_error_calculate", "sage_tracker_reproj_error_calculate",
@@ -509,7 +535,7 @@ class Window:
 
     def __init__(self, win, rank: int = 0, world: int = 1, stream=None, use_photo=True, use_geo=True,
                  code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None,
-                 keypoint_links=None, holds=None):
+                 keypoint_links=None, holds=None, graph_terms=None):
         """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches`` /
         ``make_loop_mg_*``, or by hand): kind ("reprojection" | "match_geometry" | "loop_mg"), edge (2 * link + direction),
         loc0 [N] int32, homo0 [N,3], matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry,
@@ -518,6 +544,8 @@ class Window:
         they are added after the window's dense links, so their ids start at ``len(win.links)`` (``self.links`` lists both;
         a ``win`` with ``links=[]`` gives a window without a dense edge).
         ``holds``: optional dict keyframe -> mask of SAGE_HOLD_* (``sage_window_hold``).
+        ``graph_terms``: optional list of dicts as ``graph_term_struct`` takes them (``synth.make_pose_graph`` makes the
+        reference's loop-closure graph), added with ``sage_window_add_graph_term``.
         All are added before the finalize this constructor performs."""
         import torch
         self.win = win
@@ -567,6 +595,11 @@ class Window:
             r = self.add_keypoint_term(t)
             if r < 0:
                 raise SageError(r, "sage_window_add_keypoint_term")
+        self.graph_terms = list(graph_terms or [])
+        for t in self.graph_terms:
+            r = self.add_graph_term(t)
+            if r < 0:
+                raise SageError(r, "sage_window_add_graph_term")
         _chk(L.sage_window_set_shard(self.h, rank, world), "sage_window_set_shard")
         _chk(L.sage_window_finalize(self.h), "sage_window_finalize")
         self.K = L.sage_window_num_keyframes(self.h)
@@ -633,6 +666,26 @@ class Window:
         if not check:
             return rc, out
         _chk(rc, "sage_window_get_keypoint_term")
+        return out
+
+    def add_graph_term(self, t) -> int:
+        """``sage_window_add_graph_term`` of dict ``t`` (``graph_term_struct``) -> term id, or the negative status code"""
+        gt = graph_term_struct(t)
+        return int(lib().sage_window_add_graph_term(self.h, C.byref(gt)))
+
+    def num_graph_terms(self) -> int:
+        return int(lib().sage_window_num_graph_terms(self.h))
+
+    def get_graph_term(self, i, check=True):
+        """host copy of graph term i's last linearize -> dict(AtA [14,14], Atb [14], error); with ``check=False`` the status
+        code is returned next to the dict instead of raising."""
+        A = np.zeros((GRAPH_TERM_DIM, GRAPH_TERM_DIM), np.float32); b = np.zeros(GRAPH_TERM_DIM, np.float32)
+        err = C.c_float()
+        rc = lib().sage_window_get_graph_term(self.h, int(i), _fp(A), _fp(b), C.byref(err))
+        out = dict(AtA=A, Atb=b, error=err.value)
+        if not check:
+            return rc, out
+        _chk(rc, "sage_window_get_graph_term")
         return out
 
     # raw-pointer views for torch.distributed (plumbing only)
@@ -806,7 +859,7 @@ class Window:
 
     def kernel_time(self, which: int):
         """(total_ms, launches) of hot kernel `which` since the last call (0 photo lin, 1 geo lin, 2 photo err, 3 geo err,
-        4 keypoint-term linearize, 5 keypoint-term error)."""
+        4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term error)."""
         ms = C.c_double(); n = C.c_int()
         _chk(lib().sage_window_get_kernel_time(self.h, which, C.byref(ms), C.byref(n)), "sage_window_get_kernel_time")
         return ms.value, n.value

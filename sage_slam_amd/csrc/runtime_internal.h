@@ -52,6 +52,7 @@ extern "C"
 #include "sage_ba.h"
 #include "sage_internal.h"
 #include "keypoint_batch.h"
+#include "graph_batch.h"
 #include "window_plan.h" // SolverRows
 
 using namespace sage;
@@ -204,9 +205,9 @@ namespace sage
 {
 struct AdjEntry // one (edge, role) incidence of a keyframe
 {
-  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1); 4 loop-MG term
-                // (its own column map: poses and scales only)
-  int32_t edge; // local edge index; types 2 / 3 / 4: index among the local terms of the kind
+  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1); 4 loop-MG or graph
+                // term (its own column map: poses and scales only)
+  int32_t edge; // local edge index; types 2 / 3 / 4: index among the local terms of the kind (graph terms behind the loop-MG ones)
   int32_t role; // 0: keyframe is the edge's source ("0"), 1: destination ("1")
 };
 
@@ -233,10 +234,10 @@ struct AssembleParams
   const float *AtA_kr, *Atb_kr, *AtA_km, *Atb_km, *AtA_kl, *Atb_kl, *stats_k;
   const int32_t *link_kp_start; // [nlinks+1]
   const AdjEntry *link_kp;
-  int n_kr, n_km, n_kl;
+  int n_kr, n_km, n_kl; // (n_kl: loop-MG and graph terms, which share the D = 14 buffers and the geometric error slot)
 };
 
-struct KpTotals // error pass: the local terms' {error, inliers}: reprojection, match geometry, loop-MG
+struct KpTotals // error pass: the local terms' {error, inliers}: reprojection, match geometry, loop-MG + graph
 {
   const float *stats;
   int n_kr, n_km, n_kl;
@@ -323,12 +324,20 @@ struct SageWindow
   std::vector<KeypointTermHost> kp_added;
   std::vector<int> kp_local;            // per term id: index among this rank's terms, -1 = another rank's
   int n_kr = 0, n_km = 0, n_kl = 0;     // local reprojection / match-geometry / loop-MG terms
-  int n_terms() const { return n_kr + n_km + n_kl; }
+  int n_kp() const { return n_kr + n_km + n_kl; }    // ... together: what the keypoint kernel is launched over
+  // pose-graph terms (sage_window_add_graph_term): host copies as added, then (finalize) this rank's in one device table.
+  // They are D = 14 systems like the loop-MG terms' and live behind them: results in AtA_kl / Atb_kl from entry n_kl on,
+  // {error, residuals} in stats_k from entry n_kp() on, AdjEntry::type 4
+  std::vector<SageGraphTerm> gt_added;
+  std::vector<int> gt_local;            // per term id: index among this rank's graph terms, -1 = another rank's
+  int n_gt = 0;
+  DevBuf gt_table;
+  int n_terms() const { return n_kp() + n_gt; }      // every local term with an entry of stats_k
   unsigned kp_kinds() const { return (n_kr > 0 ? 1u : 0u) | (n_km > 0 ? 2u : 0u) | (n_kl > 0 ? 4u : 0u); }
   bool kp_lin = false;                  // the terms have been linearized at least once
   DevBuf kp_pool, kp_table, kp_link_start, kp_link;
   DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, AtA_kl, Atb_kl; // per kind [n][D * D], [n][D]
-  DevBuf stats_k;                       // [2][n_terms][2] -- last linearize, last error pass; reprojection, match geometry, loop-MG
+  DevBuf stats_k;                       // [2][n_terms][2] -- last linearize, last error pass; reprojection, match geometry, loop-MG, graph
   // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
   // (all K keyframes) they were evaluated at
   struct FactorCache

@@ -203,8 +203,65 @@ extern "C" int sage_window_get_keypoint_term(const SageWindow *w, int term, floa
   return SAGE_OK;
 }
 
+// ---- pose-graph terms ------------------------------------------------------------------------------------------------
+// add: host data only -- validated and copied, no device call; finalize lays this rank's terms out in one device table
+extern "C" int sage_window_add_graph_term(SageWindow *w, const SageGraphTerm *t)
+{
+  if (!w || !t)
+    return SAGE_E_INVALID;
+  if (w->finalized)
+    return SAGE_E_STATE;
+  const bool rps = t->kind == SAGE_GRAPH_REL_POSE_SCALE, rp = t->kind == SAGE_GRAPH_REL_POSE, sp = t->kind == SAGE_GRAPH_SCALE_PRIOR;
+  if ((!rps && !rp && !sp) || !(t->weight > 0.f) || !std::isfinite(t->weight))
+    return SAGE_E_INVALID;
+  auto positive = [](float v) { return v > 0.f && std::isfinite(v); };
+  if (sp)
+  {
+    if (t->kf < 0 || t->kf >= w->K || !positive(t->target_scale0))
+      return SAGE_E_INVALID;
+  }
+  else
+  {
+    if (t->edge < 0 || t->edge >= 2 * (int)w->links.size() || !(t->rot_weight >= 0.f) || !std::isfinite(t->rot_weight))
+      return SAGE_E_INVALID;
+    for (float v : t->target_pose10)
+      if (!std::isfinite(v))
+        return SAGE_E_INVALID;
+    if (rps && (!positive(t->target_scale0) || !positive(t->target_scale1) || !(t->scale_weight >= 0.f) ||
+                !std::isfinite(t->scale_weight)))
+      return SAGE_E_INVALID;
+  }
+  w->gt_added.push_back(*t);
+  return (int)w->gt_added.size() - 1;
+}
+
+extern "C" int sage_window_num_graph_terms(const SageWindow *w) { return w ? (int)w->gt_added.size() : 0; }
+
+extern "C" int sage_window_get_graph_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err)
+{
+  if (!w || term < 0 || term >= (int)w->gt_added.size())
+    return SAGE_E_INVALID;
+  if (!w->finalized)
+    return SAGE_E_STATE;
+  const int lt = w->gt_local[term];
+  if (lt < 0)
+    return SAGE_E_INVALID; // another rank's
+  if (!w->kp_lin)
+    return SAGE_E_STATE;
+  const size_t D = kGraphD, out = (size_t)w->n_kl + lt, stat = (size_t)w->n_kp() + lt;
+  SAGE_HIP(hipStreamSynchronize(w->stream));
+  if (AtA)
+    SAGE_HIP(hipMemcpy(AtA, w->AtA_kl.as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
+  if (Atb)
+    SAGE_HIP(hipMemcpy(Atb, w->Atb_kl.as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
+  if (err)
+    SAGE_HIP(hipMemcpy(err, w->stats_k.as<float>() + stat * 2, sizeof(float), hipMemcpyDeviceToHost));
+  return SAGE_OK;
+}
+
 // finalize: this rank's terms (those of its directed edges), by kind (reprojection, match geometry, loop-MG), each kind in the
-// order of the add calls; link_terms [nlinks]: does the link carry a local term?
+// order of the add calls, then its pose-graph terms (a binary one: the rank of its directed edge; a scale prior: rank 0) in the
+// order of theirs; link_terms [nlinks]: does the link carry a local term?
 static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjEntry>> &adjv, std::vector<char> &link_terms,
                                      double *residuals)
 {
@@ -212,7 +269,18 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
   w->kp_local.assign(nterms, -1);
   w->n_kr = w->n_km = w->n_kl = 0;
   link_terms.assign(w->links.size(), 0);
-  if (nterms == 0)
+  const int ngraph = (int)w->gt_added.size();
+  w->gt_local.assign(ngraph, -1);
+  w->n_gt = 0;
+  std::vector<int> gorder;
+  for (int i = 0; i < ngraph; ++i)
+    if (w->gt_added[i].kind == SAGE_GRAPH_SCALE_PRIOR ? w->rank == 0 : window_owns_edge(w, w->gt_added[i].edge))
+    {
+      w->gt_local[i] = (int)gorder.size();
+      gorder.push_back(i);
+    }
+  w->n_gt = (int)gorder.size();
+  if (nterms == 0 && w->n_gt == 0)
     return SAGE_OK;
   std::vector<int> order;
   for (int kind = 0; kind < kKpKinds; ++kind)
@@ -224,7 +292,7 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
         (kind == 0 ? w->n_kr : (kind == 1 ? w->n_km : w->n_kl)) += 1;
       }
   const int nloc = (int)order.size();
-  if (nloc == 0)
+  if (nloc + w->n_gt == 0)
     return SAGE_OK;
   // pool: 4-byte words, every array 16-byte aligned
   std::vector<uint32_t> pool;
@@ -289,6 +357,35 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
     link_terms[l] = 1;
     *residuals += (double)kp_kind_rows(h.kind) * h.N;
   }
+  std::vector<GraphTerm> gtable(w->n_gt);
+  for (int g = 0; g < w->n_gt; ++g)
+  {
+    const SageGraphTerm &h = w->gt_added[gorder[g]];
+    GraphTerm gt{};
+    gt.kind = h.kind;
+    gt.out = w->n_kl + g;
+    gt.stat = nloc + g;
+    std::memcpy(gt.target, h.target_pose10, sizeof(gt.target));
+    gt.ts0 = h.target_scale0; gt.ts1 = h.target_scale1;
+    gt.weight = h.weight; gt.rot_weight = h.rot_weight; gt.scale_weight = h.scale_weight;
+    if (h.kind == SAGE_GRAPH_SCALE_PRIOR) // one keyframe: an adjacency entry, no link entry
+    {
+      gt.k0 = gt.k1 = h.kf;
+      adjv[h.kf].push_back(AdjEntry{4, gt.out, 0});
+    }
+    else
+    {
+      const int l = h.edge / 2, dir = h.edge % 2;
+      gt.k0 = dir == 0 ? w->links[l].first : w->links[l].second;
+      gt.k1 = dir == 0 ? w->links[l].second : w->links[l].first;
+      adjv[gt.k0].push_back(AdjEntry{4, gt.out, 0});
+      adjv[gt.k1].push_back(AdjEntry{4, gt.out, 1});
+      per_link[l].push_back(AdjEntry{4, gt.out, dir});
+      link_terms[l] = 1;
+    }
+    gtable[g] = gt;
+    *residuals += (double)graph_kind_rows(h.kind);
+  }
   std::vector<int32_t> lstart(w->links.size() + 1, 0);
   std::vector<AdjEntry> lkp;
   for (size_t l = 0; l < w->links.size(); ++l)
@@ -298,17 +395,19 @@ static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjE
   }
   lstart[w->links.size()] = (int32_t)lkp.size();
   const size_t Dp = kp_kind_dim(0, CS), Dg = kp_kind_dim(1, CS), Dl = kp_kind_dim(2, CS);
-  if ((rc = upload(w->kp_table, table, w->stream)) || (rc = upload(w->kp_link_start, lstart, w->stream)) ||
+  const int n_d14 = w->n_kl + w->n_gt, nstat = nloc + w->n_gt; // (the graph terms' share of the loop-MG buffers and of stats_k)
+  if ((rc = upload(w->kp_table, table, w->stream)) || (rc = upload(w->gt_table, gtable, w->stream)) ||
+      (rc = upload(w->kp_link_start, lstart, w->stream)) ||
       (rc = upload(w->kp_link, lkp, w->stream)) ||
       (rc = w->AtA_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * Dp * sizeof(float))) ||
       (rc = w->Atb_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * sizeof(float))) ||
       (rc = w->AtA_km.reserve(std::max<size_t>(1, w->n_km) * Dg * Dg * sizeof(float))) ||
       (rc = w->Atb_km.reserve(std::max<size_t>(1, w->n_km) * Dg * sizeof(float))) ||
-      (rc = w->AtA_kl.reserve(std::max<size_t>(1, w->n_kl) * Dl * Dl * sizeof(float))) ||
-      (rc = w->Atb_kl.reserve(std::max<size_t>(1, w->n_kl) * Dl * sizeof(float))) ||
-      (rc = w->stats_k.reserve((size_t)2 * nloc * 2 * sizeof(float))))
+      (rc = w->AtA_kl.reserve(std::max<size_t>(1, n_d14) * Dl * Dl * sizeof(float))) ||
+      (rc = w->Atb_kl.reserve(std::max<size_t>(1, n_d14) * Dl * sizeof(float))) ||
+      (rc = w->stats_k.reserve((size_t)2 * nstat * 2 * sizeof(float))))
     return rc;
-  SAGE_HIP(hipMemsetAsync(w->stats_k.p, 0, (size_t)2 * nloc * 2 * sizeof(float), w->stream));
+  SAGE_HIP(hipMemsetAsync(w->stats_k.p, 0, (size_t)2 * nstat * 2 * sizeof(float), w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream)); // (the host vectors go out of scope)
   return SAGE_OK;
 }
@@ -804,13 +903,13 @@ extern "C" int sage_window_finalize(SageWindow *w)
   const char *schur = getenv("SAGE_SHARD_SCHUR"); // the request: 0 / 1
   fs.domain_solve = plan::uses_domain_solve(w->world, w->K, schur ? atoi(schur) != 0 : -1);
   w->hold.resize(w->K, 0);
-  if (fs.domain_solve && window_has_holds(w))
-    return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables)
+  if (fs.domain_solve && (window_has_holds(w) || !w->gt_added.empty()))
+    return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables, and no term on a single keyframe)
   w->rows = plan::solver_rows(w->hold.data(), w->K, w->cfg.CS);
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||
-      (rc = window_finalize_keypoints(w, fs.adjv, fs.link_terms, &fs.residuals))) // 7. this rank's keypoint terms: pool, table, result buffers
+      (rc = window_finalize_keypoints(w, fs.adjv, fs.link_terms, &fs.residuals))) // 7. this rank's keypoint and pose-graph terms: pool, tables, result buffers
     return rc;
   w->residuals_per_lin = fs.residuals;
   w->bytes_per_lin = fs.bytes;

@@ -27,7 +27,8 @@ __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 }
 
 // one workgroup per output block; thread per element; contributions summed in a fixed order (deterministic)
-// column map of an adjacency entry's type: keypoint terms of types 2 / 3 share the dense layouts, type 4 has its own
+// column map of an adjacency entry's type: keypoint terms of types 2 / 3 share the dense layouts, type 4 (loop-MG and
+// pose-graph terms) has its own
 __device__ __forceinline__ int adj_col_map(int type) { return type == 4 ? 2 : (type & 1); }
 // a keypoint term's results by column map
 __device__ __forceinline__ const float *kp_AtA(const AssembleParams &p, int lt) { return lt == 0 ? p.AtA_kr : (lt == 1 ? p.AtA_km : p.AtA_kl); }
@@ -361,7 +362,7 @@ static AssembleParams window_assemble_params(SageWindow *w)
     ap.AtA_kr = w->AtA_kr.as<float>(); ap.Atb_kr = w->Atb_kr.as<float>();
     ap.AtA_km = w->AtA_km.as<float>(); ap.Atb_km = w->Atb_km.as<float>();
     ap.AtA_kl = w->AtA_kl.as<float>(); ap.Atb_kl = w->Atb_kl.as<float>();
-    ap.n_kl = w->n_kl;
+    ap.n_kl = w->n_kl + w->n_gt; // (graph terms: behind the loop-MG ones in the D = 14 buffers and in stats_k)
     ap.stats_k = w->stats_k.as<float>();
     ap.link_kp_start = w->kp_link_start.as<int32_t>();
     ap.link_kp = w->kp_link.as<AdjEntry>();
@@ -374,7 +375,7 @@ static AssembleParams window_assemble_params(SageWindow *w)
 // the batched kernel over this rank's terms at variable set `set`; linearize -> stats_k[0], error pass -> stats_k[1]
 static int window_launch_keypoints(SageWindow *w, int set, bool jac)
 {
-  const int nloc = w->n_terms();
+  const int nloc = w->n_kp();
   if (nloc == 0)
     return SAGE_OK;
   KpBatchParams kp{};
@@ -386,12 +387,38 @@ static int window_launch_keypoints(SageWindow *w, int set, bool jac)
   kp.AtA_r = w->AtA_kr.as<float>(); kp.Atb_r = w->Atb_kr.as<float>();
   kp.AtA_m = w->AtA_km.as<float>(); kp.Atb_m = w->Atb_km.as<float>();
   kp.AtA_l = w->AtA_kl.as<float>(); kp.Atb_l = w->Atb_kl.as<float>();
-  kp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * nloc);
+  kp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * w->n_terms());
   LaunchCommon lc{};
   prof_attach(w, jac ? 4 : 5, lc);
   if (lc.ev_start)
     (void)hipEventRecord(lc.ev_start, w->stream);
   SAGE_HIP(launch_keypoint_batch(w->stream, w->cfg.CS, jac, nloc, w->kp_kinds(), kp));
+  if (lc.ev_stop)
+    (void)hipEventRecord(lc.ev_stop, w->stream);
+  if (jac)
+    w->kp_lin = true;
+  return SAGE_OK;
+}
+
+// the batched kernel over this rank's pose-graph terms at variable set `set`: results behind the loop-MG terms', {error,
+// residuals} behind every keypoint term's (linearize -> stats_k[0], error pass -> stats_k[1])
+static int window_launch_graph_terms(SageWindow *w, int set, bool jac)
+{
+  if (w->n_gt == 0)
+    return SAGE_OK;
+  GraphBatchParams gp{};
+  gp.terms = w->gt_table.as<GraphTerm>();
+  gp.n = w->n_gt;
+  gp.vars = w->vars[set].as<float>();
+  gp.VS = w->VS;
+  gp.AtA = w->AtA_kl.as<float>();
+  gp.Atb = w->Atb_kl.as<float>();
+  gp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * w->n_terms());
+  LaunchCommon lc{};
+  prof_attach(w, jac ? 6 : 7, lc);
+  if (lc.ev_start)
+    (void)hipEventRecord(lc.ev_start, w->stream);
+  SAGE_HIP(launch_graph_terms(w->stream, jac, gp));
   if (lc.ev_stop)
     (void)hipEventRecord(lc.ev_stop, w->stream);
   if (jac)
@@ -447,6 +474,9 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
     if (rck)
       return rck;
+    const int rcg = window_launch_graph_terms(w, set, true); // ... and every pose-graph term: one more
+    if (rcg)
+      return rcg;
   }
   if (dense)
   {
@@ -576,7 +606,10 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     const int rck = window_launch_keypoints(w, which, false);
     if (rck)
       return rck;
-    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * w->n_terms(), w->n_kr, w->n_km, w->n_kl};
+    const int rcg = window_launch_graph_terms(w, which, false);
+    if (rcg)
+      return rcg;
+    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * w->n_terms(), w->n_kr, w->n_km, w->n_kl + w->n_gt};
   }
   w->mirror.err_epoch += 1;
   double *const mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kError : nullptr;

@@ -155,10 +155,10 @@ struct WindowProfiler
   int phase_n = 0;
   bool profiling = false;
   int prof_level = 0; // 1: all hot kernels + phase marks, 2: the photometric linearize only
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6]; // (4 / 5: keypoint-term linearize / error launch)
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[8]; // (4 / 5: keypoint-term linearize / error launch, 6 / 7: graph-term)
   std::vector<hipEvent_t> ev_free; // recycled events (creating / destroying one per mark costs API time inside the region being profiled)
-  double prof_ms[6] = {0, 0, 0, 0, 0, 0};
-  int prof_n[6] = {0, 0, 0, 0, 0, 0};
+  double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int prof_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   WindowProfiler() = default;
   WindowProfiler(const WindowProfiler &) = delete;
   WindowProfiler &operator=(const WindowProfiler &) = delete;

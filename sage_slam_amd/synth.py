@@ -394,3 +394,69 @@ def make_loop_mg_exact(w: Window, k0: int, k1: int, n: int, seed: int) -> dict:
     X1 = (b.R_true.astype(np.float64).T @ (Xw - b.t_true.astype(np.float64)).T).T
     return dict(kind="loop_mg", loc0=loc0.astype(np.int32), homo0=homo0, homo1=(X1 / X1[:, 2:3]).astype(F32),
                 u0=u0, u1=(X1[:, 2] / float(b.scale_true)).astype(F32))
+
+
+# --------------------------------------------------------------------------- pose-graph terms (the reference's live loop-closure graph)
+def _pose12(R, t) -> np.ndarray:
+    return np.concatenate([np.asarray(R, np.float64).reshape(-1), np.asarray(t, np.float64).reshape(-1)])
+
+
+def _rel12(p0: np.ndarray, p1: np.ndarray) -> np.ndarray:
+    """``pose1^-1 * pose0`` of two poses [R row-major | t] in fp64"""
+    R0, R1 = p0[:9].reshape(3, 3), p1[:9].reshape(3, 3)
+    return np.concatenate([(R1.T @ R0).reshape(-1), R1.T @ (p0[9:] - p1[9:])])
+
+
+def make_pose_graph(w: Window, links, loops=(), local_targets: str = "start", drift: float = 0.0, seed: int = 0,
+                    local_weight: float = 1.0, global_weight: float = 5.0, rot_weight: float = 1.0, scale_weight: float = 3.0,
+                    anchor_weight: float = 100.0, scale_prior_weight: float = 50.0):
+    """The graph of ``DeepFactors::LoopClosurePoseScaleEstimate`` (``core/deepfactors.cpp:58-386``) on the keyframes of ``w``
+    as window graph terms (``capi.Window(graph_terms=...)``); default weights are ``configs/slam_run.flags:63-67``.
+
+    * start: ``w``'s current estimates, or -- ``drift > 0`` -- the TRUE poses and scales under a drift that accumulates along
+      the keyframes (per keyframe a world-side twist ~ N(0, drift^2)_6 and a log-scale step ~ N(0, drift^2); keyframe 0 exact);
+    * local ``links``: two ``rel_pose_scale`` terms each (the second with the inverse target and the scales swapped) whose
+      target is the relative pose and the scales of the start (``local_targets="start"``: on target, as the reference builds
+      them, ``deepfactors.cpp:126-183``) or of the truth (``"truth"``);
+    * ``loops``: links appended behind the local ones, terms of ``global_weight`` whose target is the TRUE relative pose and
+      scales (the tracker's measurement: it disagrees with a drifted chain, ``:236-272``);
+    * a ``scale_prior`` of ``anchor_weight`` on keyframe 0 at its start scale (``:119``) and, with loops, two of
+      ``scale_prior_weight`` on the first loop's keyframes at their true scales (``:277-282``).
+
+    -> (window with the start variables and no dense link, all links, terms, holds): every code held, keyframe 0's pose held
+    (the reference's sigma = 1e-4 pose prior).  Deterministic per ``seed``."""
+    import dataclasses
+    assert local_targets in ("start", "truth")
+    rng = np.random.default_rng([seed, len(w.keyframes), 77])
+    truth = [(_pose12(kf.R_true, kf.t_true), float(kf.scale_true)) for kf in w.keyframes]
+    start = [(_pose12(kf.R, kf.t), float(kf.scale)) for kf in w.keyframes]
+    if drift > 0:
+        DR, Dt, ds = np.eye(3), np.zeros(3), 1.0
+        start = []
+        for k, (p, s) in enumerate(truth):
+            if k > 0:
+                xi = rng.normal(0.0, drift, 6)
+                dR = so3_exp(xi[3:])
+                DR, Dt, ds = dR @ DR, dR @ Dt + xi[:3], ds * float(np.exp(rng.normal(0.0, drift)))
+            start.append((_pose12(DR @ p[:9].reshape(3, 3), DR @ p[9:] + Dt), s * ds))
+    # (what the engine holds is fp32: targets "on the start" are formed from the rounded variables)
+    start = [(p.astype(F32).astype(np.float64), float(F32(s))) for p, s in start]
+    kfs = [dataclasses.replace(kf, R=p[:9].reshape(3, 3).astype(F32), t=p[9:].astype(F32), scale=s)
+           for kf, (p, s) in zip(w.keyframes, start)]
+    all_links = [(min(a, b), max(a, b)) for a, b in list(links) + list(loops)]
+    terms = []
+    for l, (a, b) in enumerate(all_links):
+        is_loop = l >= len(links)
+        src = truth if (is_loop or local_targets == "truth") else start
+        for d, (k0, k1) in enumerate(((a, b), (b, a))):
+            terms.append(dict(kind="rel_pose_scale", edge=2 * l + d, target_pose10=_rel12(src[k0][0], src[k1][0]).astype(F32),
+                              target_scale0=float(F32(src[k0][1])), target_scale1=float(F32(src[k1][1])),
+                              weight=global_weight if is_loop else local_weight, rot_weight=rot_weight, scale_weight=scale_weight))
+    terms.append(dict(kind="scale_prior", kf=0, target_scale0=start[0][1], weight=anchor_weight))
+    if loops:
+        a, b = all_links[len(links)]
+        for k in (a, b):
+            terms.append(dict(kind="scale_prior", kf=k, target_scale0=float(F32(truth[k][1])), weight=scale_prior_weight))
+    holds = {k: 2 for k in range(len(kfs))}       # SAGE_HOLD_CODE
+    holds[0] = 1 | 2                              # ... and keyframe 0's pose
+    return dataclasses.replace(w, keyframes=kfs, links=[]), all_links, terms, holds
