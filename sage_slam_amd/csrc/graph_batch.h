@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "graph_terms.h"
+#include "term_results.h"
 
 namespace sage
 {
@@ -19,8 +20,7 @@ struct GraphBatchParams
   int n;
   const float *vars; // [K][VS]: pose 12, scale, code CS -- the variable set being evaluated
   int VS;
-  float *AtA, *Atb; // the D = 14 result buffers [..][196], [..][14], indexed by GraphTerm::out (linearize only)
-  float *stats;     // [..][2] = {error, residuals}, indexed by GraphTerm::stat
+  TermResults out;   // AtA / Atb (linearize only) of every kind's group by GraphTerm::out, {error, residuals} by GraphTerm::stat
 };
 
 // every local graph term of a window in ONE launch; jac = false: errors only

@@ -34,16 +34,18 @@ __global__ __launch_bounds__(kGraphBlock) void graph_terms_kernel(const GraphBat
   {
     float row[kGraphD], b;
     graph_normal_row(J, r, t.weight, lane, row, b);
-    float *A = p.AtA + (size_t)t.out * (kGraphD * kGraphD) + lane * kGraphD;
+    constexpr int G = plan::graph_kind_group(0); // (every kind's)
+    static_assert(TermResults::dim(G, 0) == kGraphD, "the graph terms' group");
+    float *A = p.out.AtA(G) + (size_t)t.out * (kGraphD * kGraphD) + lane * kGraphD;
 #pragma unroll
     for (int j = 0; j < kGraphD; ++j)
       A[j] = row[j];
-    p.Atb[(size_t)t.out * kGraphD + lane] = b;
+    p.out.Atb(G)[(size_t)t.out * kGraphD + lane] = b;
   }
   if (lane == kGraphLanes - 1)
   {
-    p.stats[2 * (size_t)t.stat + 0] = err;
-    p.stats[2 * (size_t)t.stat + 1] = (float)graph_kind_rows(t.kind);
+    p.out.stats[2 * (size_t)t.stat + 0] = err;
+    p.out.stats[2 * (size_t)t.stat + 1] = (float)graph_kind_rows(t.kind);
   }
 }
 

@@ -37,8 +37,8 @@ struct GraphTerm
 {
   int32_t kind;
   int32_t k0, k1; // keyframes "0" and "1" of the directed edge; a scale prior: k0 = k1 = its keyframe
-  int32_t out;    // where AtA / Atb go (the D = 14 result buffers, behind the loop-MG terms)
-  int32_t stat;   // where {error, residuals} go (behind every keypoint term)
+  int32_t out;    // where AtA / Atb go in the pose-scale group, where {error, residuals} go: plan::term_layout
+  int32_t stat;
   float target[12]; // of pose1^-1 * pose0: R row-major, then t
   float ts0, ts1;   // target scales; a scale prior uses ts0
   float weight, rot_weight, scale_weight;

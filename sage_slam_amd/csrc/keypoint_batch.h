@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "sage_ba.h"
+#include "term_results.h"
 
 namespace sage
 {
@@ -77,8 +78,8 @@ constexpr int kKpChunk = 64; // keypoints whose weighted rows sit in LDS at a ti
 struct KpTerm
 {
   int32_t kind, loss, N;
-  int32_t out;    // index among the local terms of its kind: where AtA / Atb go
-  int32_t stat;   // index among all local terms (reprojection first): where {error, inliers} go
+  int32_t out;    // where AtA / Atb go in the kind's group, where {error, inliers} go: plan::term_layout
+  int32_t stat;
   int32_t k0, k1; // keyframes "0" and "1" of the directed edge
   float loss_param, weight;
   const int32_t *loc0, *loc1;           // [N]; loc1: match geometry
@@ -94,14 +95,13 @@ struct KpBatchParams
   int VS;
   SageCamera cam;
   float eps;
-  float *AtA_r, *Atb_r, *AtA_m, *Atb_m, *AtA_l, *Atb_l; // per kind [n][D*D], [n][D] (linearize only)
-  float *stats;                         // [n_terms][2] = {error, inliers}
+  TermResults out;   // AtA / Atb: linearize only
 };
 
 // system size and rows per keypoint of a window term by kind (SAGE_KP_*)
 constexpr int kp_kind_dim(int kind, int CS) { return kind == 0 ? reproj_dim(0, CS) : (kind == 1 ? mg_dim(0, CS) : mg_dim(1, CS)); }
 constexpr int kp_kind_rows(int kind) { return kind == 0 ? kReprojRows : kMgRows; }
-constexpr int kKpKinds = 3;
+constexpr int kKpKinds = plan::kKeypointKinds;
 
 // dynamic LDS of the batched kernel: a chunk's rows, stride padded to four floats -- the largest over the kinds PRESENT
 // among the launch's terms (kinds: bit k = a term of kind k; CS = 32: 24 KB, 60 KB, 12 KB)

@@ -751,8 +751,8 @@ __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams
   const double sc = ninl > 0.0 ? (double)T.weight / ninl : 0.0;
   if (tid == 0)
   {
-    prm.stats[2 * (size_t)T.stat + 0] = ninl > 0.0 ? (float)(sc * s_red[1]) : T.weight * 10.0f;
-    prm.stats[2 * (size_t)T.stat + 1] = (float)ninl;
+    prm.out.stats[2 * (size_t)T.stat + 0] = ninl > 0.0 ? (float)(sc * s_red[1]) : T.weight * 10.0f;
+    prm.out.stats[2 * (size_t)T.stat + 1] = (float)ninl;
   }
   if (!JAC)
     return;
@@ -777,8 +777,10 @@ __device__ __forceinline__ void kp_term_run(const KpTerm &T, const KpBatchParams
   }
   if (grp != 0)
     return;
-  float *AtA = (KIND == 0 ? prm.AtA_r : (KIND == 1 ? prm.AtA_m : prm.AtA_l)) + (size_t)T.out * D * D;
-  float *Atb = (KIND == 0 ? prm.Atb_r : (KIND == 1 ? prm.Atb_m : prm.Atb_l)) + (size_t)T.out * D;
+  constexpr int G = plan::keypoint_kind_group(KIND);
+  static_assert(TermResults::dim(G, CS) == D, "the kind's group");
+  float *AtA = prm.out.AtA(G) + (size_t)T.out * D * D;
+  float *Atb = prm.out.Atb(G) + (size_t)T.out * D;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll

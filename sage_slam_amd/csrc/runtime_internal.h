@@ -8,10 +8,11 @@
 //   window_lm.hip       the LM iteration: one policy around three sequences (classic, schur, at_candidate)
 //   window_profile.hip  optional kernel timing of a window: event pool, per-kernel event pairs, phase marks
 //   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
+//   window_terms.hip    keypoint and pose-graph terms: add / get, their finalize stage, their two launches
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
-// window_state.h holds the parts SageWindow is made of (host variables, dense factor side, totals mirror, distributed
-// state, profiler); DevBuf owns its allocation
+// window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, totals mirror,
+// distributed state, profiler); DevBuf owns its allocation
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,7 +54,7 @@ extern "C"
 #include "sage_internal.h"
 #include "keypoint_batch.h"
 #include "graph_batch.h"
-#include "window_plan.h" // SolverRows
+#include "window_plan.h" // SolverRows, TermLayout
 
 using namespace sage;
 
@@ -205,9 +206,8 @@ namespace sage
 {
 struct AdjEntry // one (edge, role) incidence of a keyframe
 {
-  int32_t type; // 0 photo, 1 geo; 2 reprojection term, 3 match-geometry term (column maps of types 0 / 1); 4 loop-MG or graph
-                // term (its own column map: poses and scales only)
-  int32_t edge; // local edge index; types 2 / 3 / 4: index among the local terms of the kind (graph terms behind the loop-MG ones)
+  int32_t type; // 0 photo, 1 geo; a term: plan::term_adj_type(its group)
+  int32_t edge; // local edge index; a term: its index in the group's result buffers
   int32_t role; // 0: keyframe is the edge's source ("0"), 1: destination ("1")
 };
 
@@ -229,18 +229,11 @@ struct AssembleParams
   int K, nlinks, CS, n_edges_p, n_edges_g;
   int split;               // > 1: every output block is shared by `split` consecutive workgroups (small workgroups)
   const int32_t *blocks;   // optional: the output blocks to assemble (ids 0..K-1 keyframes, K..K+nlinks-1 links, K+nlinks tail)
-  // keypoint terms (null / 0 without them): per-kind results, {error, inliers} of all local terms (reprojection first), and
-  // per link the terms on its two directions (AdjEntry::role = direction)
-  const float *AtA_kr, *Atb_kr, *AtA_km, *Atb_km, *AtA_kl, *Atb_kl, *stats_k;
-  const int32_t *link_kp_start; // [nlinks+1]
-  const AdjEntry *link_kp;
-  int n_kr, n_km, n_kl; // (n_kl: loop-MG and graph terms, which share the D = 14 buffers and the geometric error slot)
-};
-
-struct KpTotals // error pass: the local terms' {error, inliers}: reprojection, match geometry, loop-MG + graph
-{
-  const float *stats;
-  int n_kr, n_km, n_kl;
+  // keypoint and graph terms (zero without them): per link the terms on its two directions (AdjEntry::role = direction),
+  // and their results
+  const int32_t *link_terms_start; // [nlinks+1]
+  const AdjEntry *link_terms;
+  TermResults terms;
 };
 
 struct ErrorTotalsSide
@@ -311,33 +304,7 @@ struct SageWindow
   double spec_error = 0.0;                // total error at that linearisation point (priors included)
   DevBuf packed_save;                     // linearize-at-candidate: the candidate's (reduced) system is formed here; an accepted
                                           // candidate swaps it with `packed` (which always is the current estimate's system)
-  // matched-keypoint terms (sage_window_add_keypoint_term): host copies as added, then (finalize) this rank's terms in one
-  // device pool + table, reprojection terms first
-  struct KeypointTermHost
-  {
-    int32_t kind, edge, N, loss;
-    float loss_param, weight;
-    std::vector<int32_t> loc0, loc1;
-    std::vector<float> homo0, second; // second: matched_2d [N,2] (reprojection) or matched_homo1 [N,3] (match geometry, loop-MG)
-    std::vector<float> dpts0, dpts1;  // loop-MG: the unscaled depths [N]
-  };
-  std::vector<KeypointTermHost> kp_added;
-  std::vector<int> kp_local;            // per term id: index among this rank's terms, -1 = another rank's
-  int n_kr = 0, n_km = 0, n_kl = 0;     // local reprojection / match-geometry / loop-MG terms
-  int n_kp() const { return n_kr + n_km + n_kl; }    // ... together: what the keypoint kernel is launched over
-  // pose-graph terms (sage_window_add_graph_term): host copies as added, then (finalize) this rank's in one device table.
-  // They are D = 14 systems like the loop-MG terms' and live behind them: results in AtA_kl / Atb_kl from entry n_kl on,
-  // {error, residuals} in stats_k from entry n_kp() on, AdjEntry::type 4
-  std::vector<SageGraphTerm> gt_added;
-  std::vector<int> gt_local;            // per term id: index among this rank's graph terms, -1 = another rank's
-  int n_gt = 0;
-  DevBuf gt_table;
-  int n_terms() const { return n_kp() + n_gt; }      // every local term with an entry of stats_k
-  unsigned kp_kinds() const { return (n_kr > 0 ? 1u : 0u) | (n_km > 0 ? 2u : 0u) | (n_kl > 0 ? 4u : 0u); }
-  bool kp_lin = false;                  // the terms have been linearized at least once
-  DevBuf kp_pool, kp_table, kp_link_start, kp_link;
-  DevBuf AtA_kr, Atb_kr, AtA_km, Atb_km, AtA_kl, Atb_kl; // per kind [n][D * D], [n][D]
-  DevBuf stats_k;                       // [2][n_terms][2] -- last linearize, last error pass; reprojection, match geometry, loop-MG, graph
+  TermSide terms;                         // keypoint and pose-graph terms: as added, this rank's layout, device tables, results
   // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
   // (all K keyframes) they were evaluated at
   struct FactorCache
@@ -379,6 +346,22 @@ int window_local_edge(const SageWindow *w, int global_edge); // local index of D
 bool window_owns_edge(const SageWindow *w, int global_edge);  // is directed edge 2 * link + dir this rank's?
 bool window_has_holds(const SageWindow *w);
 std::vector<int32_t> window_link_pairs(const SageWindow *w);  // [nlinks][2]: the links as the host solvers take them
+// window_build.hip: what the stages of sage_window_finalize hand to one another; on the host for the length of the call
+struct FinalizeState
+{
+  bool domain_solve = false;               // plan::uses_domain_solve, asked once: ownership granularity and the shard plan
+  std::vector<char> needed;                // [K]: keyframes this rank's links touch
+  std::vector<size_t> f0s_off;             // [K + 1]: floats of pre-sampled source features before keyframe k
+  std::vector<size_t> px_off;              // [n_edges + 1]: source pixels before local edge e (rows of geo_px)
+  std::vector<int> Nedge;                  // samples (slots) per local directed edge
+  std::vector<std::vector<AdjEntry>> adjv; // [K]: the keyframe's (edge, role) incidences, the terms' included
+  std::vector<LinkEdges> le;               // per link: its local dense edges
+  std::vector<char> link_terms;            // per link: it carries a local term
+  double residuals = 0, bytes = 0;         // per linearize
+};
+// window_terms.hip
+int finalize_terms(SageWindow *w, FinalizeState &fs);  // stage 7 of sage_window_finalize
+int window_launch_terms(SageWindow *w, int set, bool jac); // the keypoint kernel, then the graph kernel, over this rank's terms
 // window_eval.hip
 int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false);
 int window_error_pass(SageWindow *w, int which, bool speculate_gradients);

@@ -1,5 +1,5 @@
-// window_build.hip -- the build-time half of the window engine: create / destroy, keyframes, links and keypoint terms as they are
-// added, sage_window_finalize as a list of stages (its policy: window_plan.h), the photometric run plan and its tuning.  Host
+// window_build.hip -- the build-time half of the window engine: create / destroy, keyframes and links as they are added (terms:
+// window_terms.hip), sage_window_finalize as a list of stages (its policy: window_plan.h), the photometric run plan and its tuning.  Host
 // code only: kernels are reached through the launch_* wrappers; what runs on a finalized window is window_eval / _reduce / _solve / _lm.hip.
 #include "runtime_internal.h"
 #include "window_plan.h"
@@ -68,29 +68,21 @@ extern "C" int sage_window_add_keyframe(SageWindow *w, const SageKeyframeView *v
   return w->K++;
 }
 
-extern "C" int sage_window_add_link(SageWindow *w, int a, int b)
+// a link: part of the solver's structure and of the packed buffer; dense = 0: keypoint terms only, no row of the dense edge tables
+static int add_link(SageWindow *w, int a, int b, char dense)
 {
-  if (!w || w->finalized || a == b || a < 0 || b < 0 || a >= w->K || b >= w->K)
-    return SAGE_E_INVALID;
-  w->links.emplace_back(std::min(a, b), std::max(a, b));
-  w->link_geo_loss.push_back(0.f);
-  w->link_dense.push_back(1);
-  return (int)w->links.size() - 1;
-}
-
-// a link without dense factors: part of the solver's structure and of the packed buffer, no row of the dense edge tables
-extern "C" int sage_window_add_keypoint_link(SageWindow *w, int a, int b)
-{
-  if (!w)
-    return SAGE_E_INVALID;
-  if (w->finalized)
-    return SAGE_E_STATE;
   if (a == b || a < 0 || b < 0 || a >= w->K || b >= w->K)
     return SAGE_E_INVALID;
   w->links.emplace_back(std::min(a, b), std::max(a, b));
   w->link_geo_loss.push_back(0.f);
-  w->link_dense.push_back(0);
+  w->link_dense.push_back(dense);
   return (int)w->links.size() - 1;
+}
+
+extern "C" int sage_window_add_link(SageWindow *w, int a, int b) { return !w || w->finalized ? SAGE_E_INVALID : add_link(w, a, b, 1); }
+extern "C" int sage_window_add_keypoint_link(SageWindow *w, int a, int b)
+{
+  return !w ? SAGE_E_INVALID : (w->finalized ? SAGE_E_STATE : add_link(w, a, b, 0));
 }
 
 extern "C" int sage_window_hold(SageWindow *w, int kf, int what)
@@ -111,304 +103,6 @@ extern "C" int sage_window_set_link_geo_loss(SageWindow *w, int link, float loss
   if (!w || w->finalized || link < 0 || link >= (int)w->links.size() || !(loss_param >= 0.f))
     return w && w->finalized ? SAGE_E_STATE : SAGE_E_INVALID;
   w->link_geo_loss[link] = loss_param;
-  return SAGE_OK;
-}
-
-// ---- matched-keypoint terms ------------------------------------------------------------------------------------------
-// add: arguments first (no device is touched for a bad call), then the caller's device arrays are copied to the host -- the
-// locations are validated there (the kernel indexes bias / basis rows with them unchecked) -- and finalize lays this rank's
-// terms out in one device pool behind one table: what lets a single launch serve them all
-extern "C" int sage_window_add_keypoint_term(SageWindow *w, const SageKeypointTerm *t)
-{
-  if (!w || !t)
-    return SAGE_E_INVALID;
-  if (w->finalized)
-    return SAGE_E_STATE;
-  const bool rep = t->kind == SAGE_KP_REPROJECTION, mg = t->kind == SAGE_KP_MATCH_GEOMETRY, lmg = t->kind == SAGE_KP_LOOP_MG;
-  if ((!rep && !mg && !lmg) || t->edge < 0 || t->edge >= 2 * (int)w->links.size() || t->N < 1 || t->N > (1 << 20) ||
-      (!lmg && !t->loc1d_0) || !t->homo0 || !(t->weight >= 0.f))
-    return SAGE_E_INVALID;
-  if (rep && (!t->matched_2d || !(t->loss_param > 0.f)))
-    return SAGE_E_INVALID;
-  if (mg && (!t->matched_loc1d_1 || !t->matched_homo1 || t->loss < SAGE_LOSS_FAIR || t->loss > SAGE_LOSS_UNBIASED ||
-             (t->loss != SAGE_LOSS_L2 && !(t->loss_param > 0.f))))
-    return SAGE_E_INVALID;
-  if (lmg && (!t->matched_homo1 || !t->unscaled_dpts0 || !t->matched_unscaled_dpts1 || !(t->loss_param > 0.f)))
-    return SAGE_E_INVALID;
-  SageWindow::KeypointTermHost h;
-  h.kind = t->kind; h.edge = t->edge; h.N = t->N; h.loss = mg ? t->loss : 0;
-  h.loss_param = t->loss_param; h.weight = t->weight;
-  const size_t N = (size_t)t->N;
-  h.loc0.resize(lmg ? 0 : N);
-  h.homo0.resize(3 * N);
-  h.second.resize((rep ? 2 : 3) * N);
-  SAGE_HIP(hipStreamSynchronize(w->stream)); // (the caller may have filled the arrays on the window's stream)
-  if (!lmg)
-    SAGE_HIP(hipMemcpy(h.loc0.data(), t->loc1d_0, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-  SAGE_HIP(hipMemcpy(h.homo0.data(), t->homo0, 3 * N * sizeof(float), hipMemcpyDeviceToHost));
-  SAGE_HIP(hipMemcpy(h.second.data(), rep ? t->matched_2d : t->matched_homo1, h.second.size() * sizeof(float),
-                     hipMemcpyDeviceToHost));
-  if (mg)
-  {
-    h.loc1.resize(N);
-    SAGE_HIP(hipMemcpy(h.loc1.data(), t->matched_loc1d_1, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (lmg)
-  {
-    h.dpts0.resize(N);
-    h.dpts1.resize(N);
-    SAGE_HIP(hipMemcpy(h.dpts0.data(), t->unscaled_dpts0, N * sizeof(float), hipMemcpyDeviceToHost));
-    SAGE_HIP(hipMemcpy(h.dpts1.data(), t->matched_unscaled_dpts1, N * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  const int32_t HW = (int32_t)w->cfg.pyr.cam[0].h * (int32_t)w->cfg.pyr.cam[0].w;
-  for (int32_t v : h.loc0)
-    if (v < 0 || v >= HW)
-      return SAGE_E_INVALID;
-  for (int32_t v : h.loc1)
-    if (v < 0 || v >= HW)
-      return SAGE_E_INVALID;
-  w->kp_added.push_back(std::move(h));
-  return (int)w->kp_added.size() - 1;
-}
-
-extern "C" int sage_window_num_keypoint_terms(const SageWindow *w) { return w ? (int)w->kp_added.size() : 0; }
-
-extern "C" int sage_window_get_keypoint_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err, float *n_in)
-{
-  if (!w || term < 0 || term >= (int)w->kp_added.size())
-    return SAGE_E_INVALID;
-  if (!w->finalized)
-    return SAGE_E_STATE;
-  const int lt = w->kp_local[term];
-  if (lt < 0)
-    return SAGE_E_INVALID; // another rank's
-  if (!w->kp_lin)
-    return SAGE_E_STATE;
-  const int kind = w->kp_added[term].kind;
-  const size_t D = (size_t)kp_kind_dim(kind, w->cfg.CS);
-  const size_t out = (size_t)(lt - (kind >= 1 ? w->n_kr : 0) - (kind >= 2 ? w->n_km : 0)); // index within the kind
-  const DevBuf &A = kind == 0 ? w->AtA_kr : (kind == 1 ? w->AtA_km : w->AtA_kl);
-  const DevBuf &b = kind == 0 ? w->Atb_kr : (kind == 1 ? w->Atb_km : w->Atb_kl);
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  if (AtA)
-    SAGE_HIP(hipMemcpy(AtA, A.as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
-  if (Atb)
-    SAGE_HIP(hipMemcpy(Atb, b.as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
-  float s2[2];
-  SAGE_HIP(hipMemcpy(s2, w->stats_k.as<float>() + (size_t)lt * 2, 2 * sizeof(float), hipMemcpyDeviceToHost));
-  if (err)
-    *err = s2[0];
-  if (n_in)
-    *n_in = s2[1];
-  return SAGE_OK;
-}
-
-// ---- pose-graph terms ------------------------------------------------------------------------------------------------
-// add: host data only -- validated and copied, no device call; finalize lays this rank's terms out in one device table
-extern "C" int sage_window_add_graph_term(SageWindow *w, const SageGraphTerm *t)
-{
-  if (!w || !t)
-    return SAGE_E_INVALID;
-  if (w->finalized)
-    return SAGE_E_STATE;
-  const bool rps = t->kind == SAGE_GRAPH_REL_POSE_SCALE, rp = t->kind == SAGE_GRAPH_REL_POSE, sp = t->kind == SAGE_GRAPH_SCALE_PRIOR;
-  if ((!rps && !rp && !sp) || !(t->weight > 0.f) || !std::isfinite(t->weight))
-    return SAGE_E_INVALID;
-  auto positive = [](float v) { return v > 0.f && std::isfinite(v); };
-  if (sp)
-  {
-    if (t->kf < 0 || t->kf >= w->K || !positive(t->target_scale0))
-      return SAGE_E_INVALID;
-  }
-  else
-  {
-    if (t->edge < 0 || t->edge >= 2 * (int)w->links.size() || !(t->rot_weight >= 0.f) || !std::isfinite(t->rot_weight))
-      return SAGE_E_INVALID;
-    for (float v : t->target_pose10)
-      if (!std::isfinite(v))
-        return SAGE_E_INVALID;
-    if (rps && (!positive(t->target_scale0) || !positive(t->target_scale1) || !(t->scale_weight >= 0.f) ||
-                !std::isfinite(t->scale_weight)))
-      return SAGE_E_INVALID;
-  }
-  w->gt_added.push_back(*t);
-  return (int)w->gt_added.size() - 1;
-}
-
-extern "C" int sage_window_num_graph_terms(const SageWindow *w) { return w ? (int)w->gt_added.size() : 0; }
-
-extern "C" int sage_window_get_graph_term(const SageWindow *w, int term, float *AtA, float *Atb, float *err)
-{
-  if (!w || term < 0 || term >= (int)w->gt_added.size())
-    return SAGE_E_INVALID;
-  if (!w->finalized)
-    return SAGE_E_STATE;
-  const int lt = w->gt_local[term];
-  if (lt < 0)
-    return SAGE_E_INVALID; // another rank's
-  if (!w->kp_lin)
-    return SAGE_E_STATE;
-  const size_t D = kGraphD, out = (size_t)w->n_kl + lt, stat = (size_t)w->n_kp() + lt;
-  SAGE_HIP(hipStreamSynchronize(w->stream));
-  if (AtA)
-    SAGE_HIP(hipMemcpy(AtA, w->AtA_kl.as<float>() + out * D * D, D * D * sizeof(float), hipMemcpyDeviceToHost));
-  if (Atb)
-    SAGE_HIP(hipMemcpy(Atb, w->Atb_kl.as<float>() + out * D, D * sizeof(float), hipMemcpyDeviceToHost));
-  if (err)
-    SAGE_HIP(hipMemcpy(err, w->stats_k.as<float>() + stat * 2, sizeof(float), hipMemcpyDeviceToHost));
-  return SAGE_OK;
-}
-
-// finalize: this rank's terms (those of its directed edges), by kind (reprojection, match geometry, loop-MG), each kind in the
-// order of the add calls, then its pose-graph terms (a binary one: the rank of its directed edge; a scale prior: rank 0) in the
-// order of theirs; link_terms [nlinks]: does the link carry a local term?
-static int window_finalize_keypoints(SageWindow *w, std::vector<std::vector<AdjEntry>> &adjv, std::vector<char> &link_terms,
-                                     double *residuals)
-{
-  const int CS = w->cfg.CS, nterms = (int)w->kp_added.size();
-  w->kp_local.assign(nterms, -1);
-  w->n_kr = w->n_km = w->n_kl = 0;
-  link_terms.assign(w->links.size(), 0);
-  const int ngraph = (int)w->gt_added.size();
-  w->gt_local.assign(ngraph, -1);
-  w->n_gt = 0;
-  std::vector<int> gorder;
-  for (int i = 0; i < ngraph; ++i)
-    if (w->gt_added[i].kind == SAGE_GRAPH_SCALE_PRIOR ? w->rank == 0 : window_owns_edge(w, w->gt_added[i].edge))
-    {
-      w->gt_local[i] = (int)gorder.size();
-      gorder.push_back(i);
-    }
-  w->n_gt = (int)gorder.size();
-  if (nterms == 0 && w->n_gt == 0)
-    return SAGE_OK;
-  std::vector<int> order;
-  for (int kind = 0; kind < kKpKinds; ++kind)
-    for (int i = 0; i < nterms; ++i)
-      if (w->kp_added[i].kind == kind && window_owns_edge(w, w->kp_added[i].edge))
-      {
-        w->kp_local[i] = (int)order.size();
-        order.push_back(i);
-        (kind == 0 ? w->n_kr : (kind == 1 ? w->n_km : w->n_kl)) += 1;
-      }
-  const int nloc = (int)order.size();
-  if (nloc + w->n_gt == 0)
-    return SAGE_OK;
-  // pool: 4-byte words, every array 16-byte aligned
-  std::vector<uint32_t> pool;
-  auto put = [&pool](const void *src, size_t words) {
-    const size_t off = pool.size();
-    pool.resize(off + (words + 3) / 4 * 4, 0u);
-    std::memcpy(pool.data() + off, src, words * sizeof(uint32_t));
-    return off;
-  };
-  struct Offs
-  {
-    size_t loc0, loc1, homo0, second, dpts0, dpts1;
-  };
-  std::vector<Offs> offs(nloc);
-  for (int t = 0; t < nloc; ++t)
-  {
-    const SageWindow::KeypointTermHost &h = w->kp_added[order[t]];
-    offs[t].loc0 = h.loc0.empty() ? 0 : put(h.loc0.data(), h.loc0.size());
-    offs[t].loc1 = h.loc1.empty() ? 0 : put(h.loc1.data(), h.loc1.size());
-    offs[t].homo0 = put(h.homo0.data(), h.homo0.size());
-    offs[t].second = put(h.second.data(), h.second.size());
-    offs[t].dpts0 = h.dpts0.empty() ? 0 : put(h.dpts0.data(), h.dpts0.size());
-    offs[t].dpts1 = h.dpts1.empty() ? 0 : put(h.dpts1.data(), h.dpts1.size());
-  }
-  int rc;
-  if ((rc = upload(w->kp_pool, pool, w->stream)))
-    return rc;
-  const uint32_t *base = w->kp_pool.as<uint32_t>();
-  std::vector<KpTerm> table(nloc);
-  std::vector<std::vector<AdjEntry>> per_link(w->links.size());
-  for (int t = 0; t < nloc; ++t)
-  {
-    const SageWindow::KeypointTermHost &h = w->kp_added[order[t]];
-    const int l = h.edge / 2, dir = h.edge % 2;
-    const int k0 = dir == 0 ? w->links[l].first : w->links[l].second, k1 = dir == 0 ? w->links[l].second : w->links[l].first;
-    KpTerm kt{};
-    kt.kind = h.kind; kt.loss = h.loss; kt.N = h.N;
-    kt.out = t - (h.kind >= 1 ? w->n_kr : 0) - (h.kind >= 2 ? w->n_km : 0);
-    kt.stat = t;
-    kt.k0 = k0; kt.k1 = k1;
-    kt.loss_param = h.loss_param; kt.weight = h.weight;
-    if (h.kind != SAGE_KP_LOOP_MG)
-      kt.loc0 = reinterpret_cast<const int32_t *>(base + offs[t].loc0);
-    kt.homo0 = reinterpret_cast<const float *>(base + offs[t].homo0);
-    if (h.kind == 0)
-      kt.matched = reinterpret_cast<const float *>(base + offs[t].second);
-    else
-      kt.homo1 = reinterpret_cast<const float *>(base + offs[t].second);
-    if (h.kind == SAGE_KP_MATCH_GEOMETRY)
-      kt.loc1 = reinterpret_cast<const int32_t *>(base + offs[t].loc1);
-    if (h.kind == SAGE_KP_LOOP_MG)
-    {
-      kt.dpts0 = reinterpret_cast<const float *>(base + offs[t].dpts0);
-      kt.dpts1 = reinterpret_cast<const float *>(base + offs[t].dpts1);
-    }
-    kt.bias0 = w->views[k0].bias; kt.basis0 = w->views[k0].basis;
-    kt.bias1 = w->views[k1].bias; kt.basis1 = w->views[k1].basis;
-    table[t] = kt;
-    adjv[k0].push_back(AdjEntry{2 + h.kind, kt.out, 0});
-    adjv[k1].push_back(AdjEntry{2 + h.kind, kt.out, 1});
-    per_link[l].push_back(AdjEntry{2 + h.kind, kt.out, dir});
-    link_terms[l] = 1;
-    *residuals += (double)kp_kind_rows(h.kind) * h.N;
-  }
-  std::vector<GraphTerm> gtable(w->n_gt);
-  for (int g = 0; g < w->n_gt; ++g)
-  {
-    const SageGraphTerm &h = w->gt_added[gorder[g]];
-    GraphTerm gt{};
-    gt.kind = h.kind;
-    gt.out = w->n_kl + g;
-    gt.stat = nloc + g;
-    std::memcpy(gt.target, h.target_pose10, sizeof(gt.target));
-    gt.ts0 = h.target_scale0; gt.ts1 = h.target_scale1;
-    gt.weight = h.weight; gt.rot_weight = h.rot_weight; gt.scale_weight = h.scale_weight;
-    if (h.kind == SAGE_GRAPH_SCALE_PRIOR) // one keyframe: an adjacency entry, no link entry
-    {
-      gt.k0 = gt.k1 = h.kf;
-      adjv[h.kf].push_back(AdjEntry{4, gt.out, 0});
-    }
-    else
-    {
-      const int l = h.edge / 2, dir = h.edge % 2;
-      gt.k0 = dir == 0 ? w->links[l].first : w->links[l].second;
-      gt.k1 = dir == 0 ? w->links[l].second : w->links[l].first;
-      adjv[gt.k0].push_back(AdjEntry{4, gt.out, 0});
-      adjv[gt.k1].push_back(AdjEntry{4, gt.out, 1});
-      per_link[l].push_back(AdjEntry{4, gt.out, dir});
-      link_terms[l] = 1;
-    }
-    gtable[g] = gt;
-    *residuals += (double)graph_kind_rows(h.kind);
-  }
-  std::vector<int32_t> lstart(w->links.size() + 1, 0);
-  std::vector<AdjEntry> lkp;
-  for (size_t l = 0; l < w->links.size(); ++l)
-  {
-    lstart[l] = (int32_t)lkp.size();
-    lkp.insert(lkp.end(), per_link[l].begin(), per_link[l].end());
-  }
-  lstart[w->links.size()] = (int32_t)lkp.size();
-  const size_t Dp = kp_kind_dim(0, CS), Dg = kp_kind_dim(1, CS), Dl = kp_kind_dim(2, CS);
-  const int n_d14 = w->n_kl + w->n_gt, nstat = nloc + w->n_gt; // (the graph terms' share of the loop-MG buffers and of stats_k)
-  if ((rc = upload(w->kp_table, table, w->stream)) || (rc = upload(w->gt_table, gtable, w->stream)) ||
-      (rc = upload(w->kp_link_start, lstart, w->stream)) ||
-      (rc = upload(w->kp_link, lkp, w->stream)) ||
-      (rc = w->AtA_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * Dp * sizeof(float))) ||
-      (rc = w->Atb_kr.reserve(std::max<size_t>(1, w->n_kr) * Dp * sizeof(float))) ||
-      (rc = w->AtA_km.reserve(std::max<size_t>(1, w->n_km) * Dg * Dg * sizeof(float))) ||
-      (rc = w->Atb_km.reserve(std::max<size_t>(1, w->n_km) * Dg * sizeof(float))) ||
-      (rc = w->AtA_kl.reserve(std::max<size_t>(1, n_d14) * Dl * Dl * sizeof(float))) ||
-      (rc = w->Atb_kl.reserve(std::max<size_t>(1, n_d14) * Dl * sizeof(float))) ||
-      (rc = w->stats_k.reserve((size_t)2 * nstat * 2 * sizeof(float))))
-    return rc;
-  SAGE_HIP(hipMemsetAsync(w->stats_k.p, 0, (size_t)2 * nstat * 2 * sizeof(float), w->stream));
-  SAGE_HIP(hipStreamSynchronize(w->stream)); // (the host vectors go out of scope)
   return SAGE_OK;
 }
 
@@ -468,20 +162,7 @@ static std::vector<int> edge_tiles(const std::vector<int> &Nedge)
 
 // ---- sage_window_finalize: stages in stream order.  Every stage returns SAGE_OK, a SAGE_E_* code or a hipError_t, synchronises
 //      the stream before a host vector it uploaded from dies, and can run again after a finalize that failed.  What the stages
-//      hand to one another stays on the host for the length of the call:
-struct FinalizeState
-{
-  bool domain_solve = false;               // plan::uses_domain_solve, asked once: ownership granularity and the shard plan
-  std::vector<char> needed;                // [K]: keyframes this rank's links touch
-  std::vector<size_t> f0s_off;             // [K + 1]: floats of pre-sampled source features before keyframe k
-  std::vector<size_t> px_off;              // [n_edges + 1]: source pixels before local edge e (rows of geo_px)
-  std::vector<int> Nedge;                  // samples (slots) per local directed edge
-  std::vector<std::vector<AdjEntry>> adjv; // [K]: the keyframe's (edge, role) incidences, keypoint terms included
-  std::vector<LinkEdges> le;               // per link: its local dense edges
-  std::vector<char> link_terms;            // per link: it carries a local keypoint term
-  double residuals = 0, bytes = 0;         // per linearize
-};
-
+//      hand to one another is FinalizeState (runtime_internal.h); stage 7, the terms, is window_terms.hip's finalize_terms
 static int image_pixels(const SageWindow *w) { return (int)w->cfg.pyr.cam[0].h * (int)w->cfg.pyr.cam[0].w; }
 
 // 1. leaves both variable sets on the device and room for every keyframe's depth map and its gradients
@@ -903,13 +584,13 @@ extern "C" int sage_window_finalize(SageWindow *w)
   const char *schur = getenv("SAGE_SHARD_SCHUR"); // the request: 0 / 1
   fs.domain_solve = plan::uses_domain_solve(w->world, w->K, schur ? atoi(schur) != 0 : -1);
   w->hold.resize(w->K, 0);
-  if (fs.domain_solve && (window_has_holds(w) || !w->gt_added.empty()))
+  if (fs.domain_solve && (window_has_holds(w) || !w->terms.gt_added.empty()))
     return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables, and no term on a single keyframe)
   w->rows = plan::solver_rows(w->hold.data(), w->K, w->cfg.CS);
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||
-      (rc = window_finalize_keypoints(w, fs.adjv, fs.link_terms, &fs.residuals))) // 7. this rank's keypoint and pose-graph terms: pool, tables, result buffers
+      (rc = finalize_terms(w, fs)))
     return rc;
   w->residuals_per_lin = fs.residuals;
   w->bytes_per_lin = fs.bytes;

@@ -1,14 +1,14 @@
-// window_eval.hip -- evaluate a finalized window's factors at a variable set: the linearize (dense kernels, keypoint terms, one
-// per-edge finalize launch, deterministic assembly into the block-sparse packed system) and the error pass with its totals
-// kernel.  Everything here enqueues on the window's stream and returns; who waits for the totals is window_reduce.hip.
+// window_eval.hip -- evaluate a finalized window's factors at a variable set: the linearize (dense kernels, the terms' launches
+// of window_terms.hip, one per-edge finalize launch, deterministic assembly into the block-sparse packed system) and the error
+// pass with its totals kernel.  Everything here enqueues on the window's stream and returns; who waits for the totals is window_reduce.hip.
 #include "runtime_internal.h"
 #include "finalize_bodies.h"
 
 namespace sage
 {
 
-// B-index (0..6+CS: pose 6, code CS, scale) -> column of the per-edge system, or -1 if absent.  type: the column map --
-// 0 the photometric edge's, 1 the geometric edge's, 2 the loop-MG term's [pose0 pose1 scale0 scale1]
+// B-index (0..6+CS: pose 6, code CS, scale) -> column of the per-edge system, or -1 if absent.  type: the column map = the
+// group (window_plan.h) -- 0 the photometric edge's, 1 the geometric edge's, 2 poses and scales only [pose0 pose1 scale0 scale1]
 __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
 {
   if (bi < 6)
@@ -26,21 +26,25 @@ __device__ __forceinline__ int edge_col(int type, int role, int bi, int CS)
   return 12 + 2 * CS + role;
 }
 
-// one workgroup per output block; thread per element; contributions summed in a fixed order (deterministic)
-// column map of an adjacency entry's type: keypoint terms of types 2 / 3 share the dense layouts, type 4 (loop-MG and
-// pose-graph terms) has its own
-__device__ __forceinline__ int adj_col_map(int type) { return type == 4 ? 2 : (type & 1); }
-// a keypoint term's results by column map
-__device__ __forceinline__ const float *kp_AtA(const AssembleParams &p, int lt) { return lt == 0 ? p.AtA_kr : (lt == 1 ? p.AtA_km : p.AtA_kl); }
-__device__ __forceinline__ const float *kp_Atb(const AssembleParams &p, int lt) { return lt == 0 ? p.Atb_kr : (lt == 1 ? p.Atb_km : p.Atb_kl); }
+// the terms' share of an error total: `acc` plus, lane-strided in a fixed order, the errors of the stat array's run that rides
+// in the slot -- the leading (reprojection) entries in the photometric one, every other entry in the geometric one
+__device__ __forceinline__ double add_term_errors(double acc, const TermResults &r, bool photo, int lane)
+{
+  const float *sk = r.stats + (photo ? 0 : 2 * (size_t)r.n_photo_stats());
+  const int nk = photo ? r.n_photo_stats() : r.n_geo_stats();
+  for (int t = lane; t < nk; t += 64)
+    acc += (double)sk[2 * t];
+  return acc;
+}
 
-// KP: the window carries keypoint terms (AdjEntry::type 2 / 3 / 4, the link lists, their share of the tail); windows without
+// one workgroup per output block; thread per element; contributions summed in a fixed order (deterministic)
+// KP: the window carries terms (AdjEntry::type >= 2, the link lists, their share of the tail); windows without
 // them run the instantiation that knows nothing of them
 template <bool KP>
 __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
 {
   const int B = 7 + p.CS, BB = B * B;
-  const int Dp = 13 + p.CS, Dg = 14 + 2 * p.CS;
+  const int Dp = TermResults::dim(0, p.CS), Dg = TermResults::dim(1, p.CS);
   const int split = p.split > 1 ? p.split : 1;
   const int part = (int)blockIdx.x % split, bslot = (int)blockIdx.x / split;
   const int blk = p.blocks ? p.blocks[bslot] : bslot;
@@ -75,11 +79,11 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     for (int a = a0; a < a1; ++a)
     {
       const AdjEntry ae = p.adj[a];
-      const int lt = KP ? adj_col_map(ae.type) : ae.type;
+      const int lt = KP ? adj_group(ae.type) : ae.type;
       const bool kp = KP && ae.type >= 2;
-      const int D = lt == 0 ? Dp : (lt == 1 ? Dg : 14);
-      const float *A = kp ? kp_AtA(p, lt) : (lt == 0 ? p.AtA_p : p.AtA_g);
-      const float *b = kp ? kp_Atb(p, lt) : (lt == 0 ? p.Atb_p : p.Atb_g);
+      const int D = TermResults::dim(lt, p.CS);
+      const float *A = kp ? p.terms.AtA(lt) : (lt == 0 ? p.AtA_p : p.AtA_g);
+      const float *b = kp ? p.terms.Atb(lt) : (lt == 0 ? p.Atb_p : p.Atb_g);
 #pragma unroll
       for (int s = 0; s < S; ++s)
       {
@@ -137,12 +141,12 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
             acc += Wd ? Wd[(size_t)le.e_ba * ws + (size_t)ci * D + cj] : (double)A[(size_t)le.e_ba * D * D + (size_t)ci * D + cj];
         }
       }
-      if (KP && p.link_kp_start) // keypoint terms of the link's two directions, in the order they were added (per kind)
-        for (int a = p.link_kp_start[l]; a < p.link_kp_start[l + 1]; ++a)
+      if (KP && p.link_terms_start) // the terms on the link's two directions
+        for (int a = p.link_terms_start[l]; a < p.link_terms_start[l + 1]; ++a)
         {
-          const AdjEntry ae = p.link_kp[a];
-          const int lt = adj_col_map(ae.type), D = lt == 0 ? Dp : (lt == 1 ? Dg : 14);
-          const float *A = kp_AtA(p, lt);
+          const AdjEntry ae = p.link_terms[a];
+          const int lt = adj_group(ae.type), D = TermResults::dim(lt, p.CS);
+          const float *A = p.terms.AtA(lt);
           const int ci = edge_col(lt, ae.role, bi, p.CS), cj = edge_col(lt, 1 - ae.role, bj, p.CS); // (role = direction)
           if (ci >= 0 && cj >= 0)
             acc += (double)A[(size_t)ae.edge * D * D + (size_t)ci * D + cj];
@@ -164,13 +168,8 @@ __global__ __launch_bounds__(1024) void assemble_kernel(const AssembleParams p)
     if (st && wave < 4)
       for (int e = lane; e < n; e += 64)
         acc += (double)st[2 * e + which];
-    if (KP && p.stats_k && wave < 2) // the terms' errors: reprojection in the photometric slot, match geometry and loop-MG
-    {                                // (behind it in stats_k) in the geometric one
-      const float *sk = p.stats_k + (photo ? 0 : 2 * (size_t)p.n_kr);
-      const int nk = photo ? p.n_kr : p.n_km + p.n_kl;
-      for (int t = lane; t < nk; t += 64)
-        acc += (double)sk[2 * t];
-    }
+    if (KP && p.terms.stats && wave < 2)
+      acc = add_term_errors(acc, p.terms, photo, lane);
     for (int off = 32; off > 0; off >>= 1)
       acc += __shfl_down(acc, off);
     if (lane == 0 && wave < 4)
@@ -211,7 +210,7 @@ __global__ __launch_bounds__(kFinalizeBlock) void window_finalize_kernel(const W
 // (a wave-parallel sum in a fixed lane order) -- same summation orders, three launches and their gaps less on the step's critical path.
 template <bool KP>
 __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSide ph, const ErrorTotalsSide ge, double *out,
-                                                            double *mirror, double epoch, const KpTotals kp)
+                                                            double *mirror, double epoch, const TermResults terms)
 {
   for (int idx = threadIdx.x; idx < ph.n_edges + ge.n_edges; idx += blockDim.x)
   {
@@ -266,13 +265,8 @@ __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSid
       if (e0 + 64 * u < sd.n_edges)
         acc += (double)v[u];
   }
-  if (KP && kp.stats && which == 0) // keypoint terms (written by the batched kernel before this one): same slots as the linearize tail
-  {
-    const float *sk = kp.stats + (photo ? 0 : 2 * (size_t)kp.n_kr);
-    const int nk = photo ? kp.n_kr : kp.n_km + kp.n_kl;
-    for (int t = lane; t < nk; t += 64)
-      acc += (double)sk[2 * t];
-  }
+  if (KP && terms.stats && which == 0) // (written by the batched kernels before this one): same slots as the linearize tail
+    acc = add_term_errors(acc, terms, photo, lane);
   for (int off = 32; off > 0; off >>= 1)
     acc += __shfl_down(acc, off);
   if (lane == 0)
@@ -357,73 +351,10 @@ static AssembleParams window_assemble_params(SageWindow *w)
   ap.n_edges_g = w->n_edges;
   ap.split = 1;
   ap.blocks = nullptr;
-  if (w->n_terms() > 0)
-  {
-    ap.AtA_kr = w->AtA_kr.as<float>(); ap.Atb_kr = w->Atb_kr.as<float>();
-    ap.AtA_km = w->AtA_km.as<float>(); ap.Atb_km = w->Atb_km.as<float>();
-    ap.AtA_kl = w->AtA_kl.as<float>(); ap.Atb_kl = w->Atb_kl.as<float>();
-    ap.n_kl = w->n_kl + w->n_gt; // (graph terms: behind the loop-MG ones in the D = 14 buffers and in stats_k)
-    ap.stats_k = w->stats_k.as<float>();
-    ap.link_kp_start = w->kp_link_start.as<int32_t>();
-    ap.link_kp = w->kp_link.as<AdjEntry>();
-    ap.n_kr = w->n_kr;
-    ap.n_km = w->n_km;
-  }
+  ap.terms = w->terms.results(true); // (all zero without terms)
+  ap.link_terms_start = w->terms.link_start.as<int32_t>();
+  ap.link_terms = w->terms.link.as<AdjEntry>();
   return ap;
-}
-
-// the batched kernel over this rank's terms at variable set `set`; linearize -> stats_k[0], error pass -> stats_k[1]
-static int window_launch_keypoints(SageWindow *w, int set, bool jac)
-{
-  const int nloc = w->n_kp();
-  if (nloc == 0)
-    return SAGE_OK;
-  KpBatchParams kp{};
-  kp.terms = w->kp_table.as<KpTerm>();
-  kp.vars = w->vars[set].as<float>();
-  kp.VS = w->VS;
-  kp.cam = w->cfg.pyr.cam[0];
-  kp.eps = w->cfg.eps;
-  kp.AtA_r = w->AtA_kr.as<float>(); kp.Atb_r = w->Atb_kr.as<float>();
-  kp.AtA_m = w->AtA_km.as<float>(); kp.Atb_m = w->Atb_km.as<float>();
-  kp.AtA_l = w->AtA_kl.as<float>(); kp.Atb_l = w->Atb_kl.as<float>();
-  kp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * w->n_terms());
-  LaunchCommon lc{};
-  prof_attach(w, jac ? 4 : 5, lc);
-  if (lc.ev_start)
-    (void)hipEventRecord(lc.ev_start, w->stream);
-  SAGE_HIP(launch_keypoint_batch(w->stream, w->cfg.CS, jac, nloc, w->kp_kinds(), kp));
-  if (lc.ev_stop)
-    (void)hipEventRecord(lc.ev_stop, w->stream);
-  if (jac)
-    w->kp_lin = true;
-  return SAGE_OK;
-}
-
-// the batched kernel over this rank's pose-graph terms at variable set `set`: results behind the loop-MG terms', {error,
-// residuals} behind every keypoint term's (linearize -> stats_k[0], error pass -> stats_k[1])
-static int window_launch_graph_terms(SageWindow *w, int set, bool jac)
-{
-  if (w->n_gt == 0)
-    return SAGE_OK;
-  GraphBatchParams gp{};
-  gp.terms = w->gt_table.as<GraphTerm>();
-  gp.n = w->n_gt;
-  gp.vars = w->vars[set].as<float>();
-  gp.VS = w->VS;
-  gp.AtA = w->AtA_kl.as<float>();
-  gp.Atb = w->Atb_kl.as<float>();
-  gp.stats = w->stats_k.as<float>() + (jac ? 0 : (size_t)2 * w->n_terms());
-  LaunchCommon lc{};
-  prof_attach(w, jac ? 6 : 7, lc);
-  if (lc.ev_start)
-    (void)hipEventRecord(lc.ev_start, w->stream);
-  SAGE_HIP(launch_graph_terms(w->stream, jac, gp));
-  if (lc.ev_stop)
-    (void)hipEventRecord(lc.ev_stop, w->stream);
-  if (jac)
-    w->kp_lin = true;
-  return SAGE_OK;
 }
 
 // linearize every local edge at variable set `set` (0 = current estimate, 1 = candidate) and assemble the packed system
@@ -470,14 +401,8 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
                                       c.photo_weights, c.eps, w->dense[kPhoto].out()));
     }
   }
-  {
-    const int rck = window_launch_keypoints(w, set, true); // every keypoint term of this rank: one launch
-    if (rck)
-      return rck;
-    const int rcg = window_launch_graph_terms(w, set, true); // ... and every pose-graph term: one more
-    if (rcg)
-      return rcg;
-  }
+  if (const int rct = window_launch_terms(w, set, true)) // every keypoint term of this rank: one launch; every graph term: one more
+    return rct;
   if (dense)
   {
     WindowFinalizeParams fp{};
@@ -511,7 +436,7 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     ap.blocks = w->dist.asm_blocks.as<int32_t>();
     nblocks = w->dist.n_asm_blocks;
   }
-  if (w->n_terms() > 0)
+  if (ap.terms.stats)
     hipLaunchKernelGGL(assemble_kernel<true>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
   else
     hipLaunchKernelGGL(assemble_kernel<false>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
@@ -599,18 +524,10 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
                               c.geo_loss_param, c.geo_weight, w->dense[kGeo].stats.as<float>()));
     ge = error_totals_side(lc, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kOwnRecord);
   }
-  KpTotals kpt{};
-  if (w->n_terms() > 0)
-  {
-    // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
-    const int rck = window_launch_keypoints(w, which, false);
-    if (rck)
-      return rck;
-    const int rcg = window_launch_graph_terms(w, which, false);
-    if (rcg)
-      return rcg;
-    kpt = KpTotals{w->stats_k.as<float>() + (size_t)2 * w->n_terms(), w->n_kr, w->n_km, w->n_kl + w->n_gt};
-  }
+  // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
+  if (const int rct = window_launch_terms(w, which, false))
+    return rct;
+  const TermResults kpt = w->terms.results(false);
   w->mirror.err_epoch += 1;
   double *const mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kError : nullptr;
   if (kpt.stats)

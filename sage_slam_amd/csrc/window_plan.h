@@ -1,6 +1,6 @@
 // window_plan.h -- the build-time policy of the window engine as pure integer arithmetic: which directed edges a rank owns,
 // which of them are dense, whether a window uses the domain-decomposed solve, which rows of a keyframe's block the solver keeps,
-// the run lengths of the two work lists.  Standard library only -- no HIP, no
+// where a window's terms live, the run lengths of the two work lists.  Standard library only -- no HIP, no
 // environment: the runtime applies its overrides to the results (window_build.hip), and tests/test_window_plan.py compiles
 // this header with a host compiler.  An edge's length is its number of SUB-TILES (ceil(samples / kTile)) throughout.
 #pragma once
@@ -104,6 +104,60 @@ inline SolverRows solver_rows(const unsigned char *hold, int K, int CS)
       }
   s.Bs = (int)s.to_block.size();
   return s;
+}
+
+// ---- terms.  A window's keypoint terms (kinds 0 / 1 / 2: reprojection, match geometry, loop-MG) and pose-graph terms (every
+//      kind) put their AtA / Atb into the result buffers of a GROUP -- what a term's system looks like -- and their
+//      {error, inliers} into one array.  AdjEntry::type of a term is 2 + group.
+enum : int { kGroupPhoto = 0, kGroupGeo = 1, kGroupPoseScale = 2, kTermGroups = 3 };
+constexpr int kKeypointKinds = 3;
+// columns of a group's systems: the photometric edge's column map, the geometric edge's, poses and scales only
+constexpr int term_group_dim(int group, int CS) { return group == kGroupPhoto ? 13 + CS : (group == kGroupGeo ? 14 + 2 * CS : 14); }
+constexpr int keypoint_kind_group(int kind) { return kind; }
+constexpr int graph_kind_group(int) { return kGroupPoseScale; }
+constexpr int term_adj_type(int group) { return 2 + group; }
+
+struct TermKey // a term as added: its kind, and whether this rank owns it (the runtime's rule)
+{
+  int kind;
+  bool owned;
+};
+// where a term lives: its index in its family's device table (= launch position), its group, its index in the group's AtA / Atb
+// buffers and in the {error, inliers} array; all -1 for a term of another rank
+struct TermSlot
+{
+  int local = -1, group = -1, out = -1, stat = -1;
+};
+struct TermLayout
+{
+  std::vector<TermSlot> kp, graph;        // per term id (add order)
+  std::vector<int> kp_order, graph_order; // launch order: term ids by `local`
+  int count[kTermGroups] = {0, 0, 0};     // entries of each group's result buffers
+  int n_keypoint() const { return (int)kp_order.size(); } // the keypoint kernel's terms = the leading entries of the stat array
+  int n_graph() const { return (int)graph_order.size(); }
+  int n_stats() const { return n_keypoint() + n_graph(); }
+  int n_photo_stats() const { return count[kGroupPhoto]; } // leading stat entries (reprojection): the photometric total's
+};
+
+// both families in add order -> keypoint terms kind-major, each kind in add order, then the graph terms in add order: that is
+// the stat array and the two launch orders; in a group's buffers the graph terms stand behind the loop-MG terms
+inline TermLayout term_layout(const std::vector<TermKey> &kp, const std::vector<TermKey> &graph)
+{
+  TermLayout L;
+  L.kp.assign(kp.size(), TermSlot());
+  L.graph.assign(graph.size(), TermSlot());
+  auto place = [&L](TermSlot &s, size_t id, std::vector<int> &order, int group) {
+    s = TermSlot{(int)order.size(), group, L.count[group]++, L.n_stats()};
+    order.push_back((int)id);
+  };
+  for (int kind = 0; kind < kKeypointKinds; ++kind)
+    for (size_t i = 0; i < kp.size(); ++i)
+      if (kp[i].kind == kind && kp[i].owned)
+        place(L.kp[i], i, L.kp_order, keypoint_kind_group(kind));
+  for (size_t i = 0; i < graph.size(); ++i)
+    if (graph[i].owned)
+      place(L.graph[i], i, L.graph_order, graph_kind_group(graph[i].kind));
+  return L;
 }
 
 // ---- run lengths of the work lists

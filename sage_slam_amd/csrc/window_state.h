@@ -1,5 +1,5 @@
 // window_state.h -- the parts SageWindow (runtime_internal.h) is made of, one struct per owner: the host variables, a dense
-// factor type's device state, the totals mirror, the distributed state, the profiler.  Included from runtime_internal.h
+// factor type's device state, the terms, the totals mirror, the distributed state, the profiler.  Included from runtime_internal.h
 // (after DevBuf); host code only.
 #pragma once
 
@@ -60,6 +60,58 @@ struct DenseSide
         (rc = stats.reserve(ne * 2 * sizeof(float))) || (rc = wide.reserve(ne * (D * D + D) * sizeof(double))))
       return rc;
     return 0;
+  }
+};
+
+// ---- the window's keypoint and pose-graph terms: host copies as added, then (finalize) this rank's on the device ----
+struct KeypointTermHost
+{
+  int32_t kind, edge, N, loss;
+  float loss_param, weight;
+  std::vector<int32_t> loc0, loc1;
+  std::vector<float> homo0, second; // second: matched_2d [N,2] (reprojection) or matched_homo1 [N,3] (match geometry, loop-MG)
+  std::vector<float> dpts0, dpts1;  // loop-MG: the unscaled depths [N]
+};
+struct TermSide
+{
+  std::vector<KeypointTermHost> kp_added; // sage_window_add_keypoint_term
+  std::vector<SageGraphTerm> gt_added;    // sage_window_add_graph_term
+  plan::TermLayout layout;                // which of them are this rank's and where each one lives
+  DevBuf pool, kp_table, gt_table;        // the keypoint terms' arrays behind their table (KpTerm); the graph terms' (GraphTerm)
+  DevBuf link_start, link;                // per link the terms on its two directions (AdjEntry::role = direction)
+  DevBuf AtA[plan::kTermGroups], Atb[plan::kTermGroups]; // per group [count][D * D], [count][D]
+  DevBuf stats;                           // [2][n_stats][2]: {error, inliers} of the last linearize, of the last error pass
+  bool linearized = false;                // ... at least once: there is something to read
+  int n_keypoint() const { return layout.n_keypoint(); } // local terms of the keypoint kernel, of the graph kernel, of both
+  int n_graph() const { return layout.n_graph(); }
+  int n_stats() const { return layout.n_stats(); }
+  // mask of the keypoint kinds present among the local terms (the keypoint kernel's LDS size)
+  unsigned keypoint_kinds() const
+  {
+    unsigned m = 0;
+    for (int id : layout.kp_order)
+      m |= 1u << kp_added[id].kind;
+    return m;
+  }
+  // the results of the linearize (jac) or of the error pass: the same systems, each pass its half of `stats`
+  TermResults results(bool jac) const
+  {
+    float *st = n_stats() ? stats.as<float>() + (jac ? 0 : (size_t)2 * n_stats()) : nullptr; // (all zero without terms)
+    return TermResults{AtA[0].as<float>(), Atb[0].as<float>(), AtA[1].as<float>(), Atb[1].as<float>(), AtA[2].as<float>(),
+                       Atb[2].as<float>(), st, layout.count[0], layout.count[1], layout.count[2]};
+  }
+  // room for every group's systems and for `stats`, zeroed on stream s
+  int reserve_results(int CS, hipStream_t s)
+  {
+    const size_t bytes = (size_t)2 * n_stats() * 2 * sizeof(float);
+    int rc = stats.reserve(bytes);
+    for (int g = 0; g < plan::kTermGroups && !rc; ++g)
+    {
+      const size_t n = std::max(1, layout.count[g]), D = TermResults::dim(g, CS);
+      if (!(rc = AtA[g].reserve(n * D * D * sizeof(float))))
+        rc = Atb[g].reserve(n * D * sizeof(float));
+    }
+    return rc ? rc : (int)hipMemsetAsync(stats.p, 0, bytes, s);
   }
 };
 

@@ -275,6 +275,60 @@ def test_graph_terms_next_to_dense_factors_and_loop_mg_terms(capi):
     win.close(); plain.close()
 
 
+@pytest.mark.parametrize("CS", [32, 16])
+def test_every_group_and_the_graph_terms_populated_at_once(capi, CS):
+    """a four-keyframe window with its dense links, one reprojection, one match-geometry (N = 65: a full chunk and a remainder)
+    and one loop-MG term, one graph term of each kind -- every group's buffers, the graph terms' place behind the loop-MG term
+    and both runs of the {error, inliers} array are non-empty, so every offset of the layout is non-zero.  The kinds are added
+    out of their layout order; the match-geometry and the loop-MG term, and the two binary graph terms, sit on one link in
+    opposite directions.  Every term reads bit for bit what it reads on a window that holds it alone"""
+    w = base_window(CS, K=4)
+    rng = np.random.default_rng(11)
+    kfs = lambda e: w.links[e // 2] if e % 2 == 0 else w.links[e // 2][::-1]
+    bias2 = lambda e: float(0.1 * np.mean(np.square(w.keyframes[kfs(e)[0]].bias, dtype=np.float64)))
+    lmg = synth.make_loop_mg_terms_from_matches(w, *kfs(3), 64, 3003)
+    lmg.update(edge=3, weight=5.0, loss_param=bias2(3))
+    rep = synth.make_reprojection_matches(w, *kfs(0), 40, 1000)
+    rep.update(edge=0, weight=5.0, loss_param=0.1 * w.W * w.W)
+    mg = synth.make_match_geometry_matches(w, *kfs(2), 65, 2002)
+    mg.update(edge=2, weight=5.0, loss="fair", loss_param=bias2(2))
+    kp = [lmg, rep, mg]
+    gt = [dict(kind="scale_prior", kf=2, target_scale0=float(np.float32(w.keyframes[2].scale * 1.1)), weight=50.0),
+          term_on_edge(w, w.links, 9, "rel_pose", rng), term_on_edge(w, w.links, 8, "rel_pose_scale", rng)]
+    win, dense = capi.Window(w, keypoint_terms=kp, graph_terms=gt), capi.Window(w)
+    win.linearize(); dense.linearize()
+    a, b = win.packed_host().copy(), dense.packed_host()
+    same = lambda h, o: all(np.array_equal(h[k], o[k]) for k in o)
+    errs = []
+    for i, t in enumerate(kp):
+        alone = capi.Window(w, keypoint_terms=[t])
+        alone.linearize()
+        h, o = win.get_keypoint_term(i), alone.get_keypoint_term(0)
+        assert set(o) == {"AtA", "Atb", "error", "num_inliers"} and same(h, o), ("keypoint term", i)
+        assert o["AtA"].any() and o["error"] > 0
+        errs.append((t["kind"], float(h["error"])))
+        alone.close()
+    for i, t in enumerate(gt):
+        alone = capi.Window(w, graph_terms=[t])
+        alone.linearize()
+        h, o = win.get_graph_term(i), alone.get_graph_term(0)
+        assert set(o) == {"AtA", "Atb", "error"} and same(h, o), ("graph term", i)
+        assert o["AtA"].any() and o["error"] > 0
+        errs.append((t["kind"], float(h["error"])))
+        alone.close()
+    photo = sum(e for kind, e in errs if kind == "reprojection")
+    geo = sum(e for kind, e in errs if kind != "reprojection")
+    assert a[-4] == pytest.approx(b[-4] + photo, rel=TOL_TOTAL) and a[-3] == pytest.approx(b[-3] + geo, rel=TOL_TOTAL)
+    assert a[-4] > b[-4] and a[-3] > b[-3] and np.array_equal(a[-2:], b[-2:])       # the inlier slots stay dense-only
+    e_lin = win.total_error(True)
+    assert e_lin == pytest.approx(dense.total_error(True) + photo + geo, rel=TOL_TOTAL)
+    win.error(0)
+    assert win.total_error(False) == pytest.approx(e_lin, rel=TOL_TOTAL)
+    win.linearize()
+    assert np.array_equal(win.packed_host(), a)
+    win.close(); dense.close()
+
+
 # --------------------------------------------------------------------------------------------------------- 4. sharding
 def graph_only(capi, w, links, terms, **kw):
     return capi.Window(w, keypoint_links=links, graph_terms=terms, code_prior_weight=0.0, scale_prior_weight=0.0,
