@@ -321,6 +321,41 @@ int sage_track_frame(const SageLmConfig *cfg, int dof, const SageTrackProblem *p
                      float *pose12, float *scale, float *final_error, int *iters,
                      SageLmTraceEntry *trace, int trace_cap, int *trace_len);
 
+/* ---- overlap statistics of a tracked pose: CameraTracker::ComputeAreaInlierRatio (camera_tracker.cpp:95-169), what
+ *      TrackNewFrame (:1289) and TrackFrame (:1644) hand back besides the pose and what NewKeyframeRequired
+ *      (deepfactors.cpp:2028-2049) and the loop detector (loop_detector.cpp:130, 173-181, 276-339) decide from ----
+ * Over ALL M valid pixels of the keyframe (not the N sampled ones), per point i, in fp32 like the reference:
+ *   X = (depth_scale * d_i) * (R * h_i) + t,  pos = X.z > eps           (GenerateReproj2DLocationsNoClamp, mapping_utils.h:671-711)
+ *   x1 = X.x / X.z * fx + cx, y1 likewise (no clamping);  x0 = h_i.x * fx + cx, y0 likewise
+ *   mask tap = grid_sample(nearest, zeros, align_corners = true) at 2 * x1 / w - 1:  ix = nearbyint(((2 * x1 / w - 1) + 1) / 2 *
+ *   (w - 1)), half to even, iy likewise with h (the (w - 1) / w squeeze is the reference's); outside the image or not finite reads 0
+ *   in = pos && mask[iy, ix] > 0.5
+ * input_area = area of the convex hull of all M (x0, y0); warp_area = that of the (x1, y1) of the `in` points (0 with fewer
+ * than three distinct ones);  area_ratio = warp_area / input_area -- 0 / 0 is NaN, as in the reference (all points on one
+ * line: both areas 0);  inlier_ratio = n_in_mask / M;  average_motion = mean over `pos` of |(x1, y1) - (x0, y0)| / sqrt(w^2 +
+ * h^2) -- NaN without a `pos` point (torch's mean of an empty tensor).
+ * The device discards the points strictly inside a polygon of extreme points of their set (they cannot be hull vertices)
+ * and hands the host the rest: n_candidates, at most M per set.  Two calls on the same inputs return identical bytes. */
+typedef struct SageOverlapStats
+{
+  double input_area, warp_area;                   /* the two hull areas, px^2 */
+  float area_ratio, inlier_ratio, average_motion; /* the reference's three outputs */
+  int32_t n_points, n_pos_depth, n_in_mask;       /* M, |z1 > eps|, |mask & z1 > eps| */
+  int32_t n_candidates[2];                        /* points that reached the host hull: [input set, warped set] */
+} SageOverlapStats;
+/* R, t: HOST (row-major R10, t10).  dpts0_dev [M], homo_dev [M,3], mask_dev [h,w] of `cam`: device.  depth_scale multiplies
+ * every depth first (1 for TrackNewFrame; guess_scale / dpt_scale_0 for TrackFrame, camera_tracker.cpp:1644).
+ * SAGE_E_INVALID (nothing is launched) for a NULL pointer, M <= 0, fx / fy not finite or not positive, w / h < 1.
+ * One wait on the workspace's ticket; no blocking copy. */
+int sage_track_overlap(SageWorkspace *ws, const float *R, const float *t, const float *dpts0_dev, float depth_scale,
+                       const float *homo_dev, int M, const SageCamera *cam, const float *mask_dev, float eps,
+                       SageOverlapStats *out);
+/* Stateless host math: area of the convex hull of n 2-D points (xy interleaved, [n,2]) in double arithmetic; 0 for fewer
+ * than three distinct points or a collinear set.  The points are ordered first: any permutation of a set gives the
+ * identical double.  Points with a non-finite coordinate are left out.  n_vertices (optional): corners of the hull,
+ * collinear boundary points not counted (0 when the area is 0).  SAGE_E_INVALID for a NULL `area`, n < 0, or NULL xy with n > 0. */
+int sage_convex_hull_area(const float *xy, int n, double *area, int *n_vertices);
+
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)
  * ===================================================================== */

@@ -135,7 +135,7 @@ SYMBOLS = [
     "sage_tracker_photo_jac_error_calculate", "sage_tracker_photo_error_calculate",
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
-    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame",
+    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame", "sage_track_overlap", "sage_convex_hull_area",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
     "sage_window_block_size", "sage_window_solver_block_size", "sage_window_packed_count", "sage_window_packed_dev",
@@ -354,6 +354,41 @@ def track_frame(cfg: SageLmConfig, dof: int, prob: "SageTrackProblem", pose12, s
     trace = [dict(damp=tr[i].damp, error=tr[i].error, candidate_error=tr[i].candidate_error,
                   accepted=tr[i].accepted, relinearized=tr[i].relinearized) for i in range(tl.value)]
     return rc, p, sc.value, fe.value, it.value, trace
+
+
+class SageOverlapStats(C.Structure):
+    _fields_ = [("input_area", C.c_double), ("warp_area", C.c_double), ("area_ratio", C.c_float),
+                ("inlier_ratio", C.c_float), ("average_motion", C.c_float), ("n_points", C.c_int32),
+                ("n_pos_depth", C.c_int32), ("n_in_mask", C.c_int32), ("n_candidates", C.c_int32 * 2)]
+
+
+def track_overlap_raw(ws_handle, R, t, dpts0_ptr, depth_scale, homo_ptr, M, cam_ptr, mask_ptr, eps, out_ptr) -> int:
+    """``sage_track_overlap`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_track_overlap
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                  C.c_float, C.c_void_p]
+    return int(f(ws_handle, R, t, dpts0_ptr, depth_scale, homo_ptr, int(M), cam_ptr, mask_ptr, eps, out_ptr))
+
+
+def track_overlap(ws: "Workspace", R, t, dpts0, homo, cam, mask, eps, depth_scale: float = 1.0) -> SageOverlapStats:
+    """``CameraTracker::ComputeAreaInlierRatio`` through ``sage_track_overlap``.  R [3,3], t [3]: host arrays; dpts0 [M],
+    homo [M,3], mask [h,w]: contiguous float32 cuda tensors; cam: anything with fx, fy, cx, cy, w, h."""
+    Rh = _f32(R).reshape(9); th = _f32(t).reshape(3)
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    M = int(homo.shape[0])
+    assert dpts0.numel() == M and tuple(mask.shape) == (int(c.h), int(c.w))
+    out = SageOverlapStats()
+    _chk(track_overlap_raw(ws.h, Rh.ctypes.data, th.ctypes.data, dptr(dpts0), float(depth_scale), dptr(homo), M,
+                           C.addressof(c), dptr(mask), float(eps), C.addressof(out)), "sage_track_overlap")
+    return out
+
+
+def convex_hull_area(xy):
+    """``sage_convex_hull_area`` of [n,2] points -> (area, n_vertices)"""
+    p = _f32(xy).reshape(-1, 2)
+    area = C.c_double(); nv = C.c_int()
+    _chk(lib().sage_convex_hull_area(_fp(p), int(p.shape[0]), C.byref(area), C.byref(nv)), "sage_convex_hull_area")
+    return area.value, nv.value
 
 
 class Workspace:

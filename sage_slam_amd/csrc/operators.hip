@@ -32,6 +32,8 @@ extern "C" void sage_workspace_destroy(SageWorkspace *ws)
     (void)hipHostFree(ws->host_stats);
   if (ws->trk_host)
     (void)hipHostFree(ws->trk_host);
+  if (ws->ov_host)
+    (void)hipHostFree(ws->ov_host);
   delete ws; // (its device buffers go with it: DevBuf)
 }
 

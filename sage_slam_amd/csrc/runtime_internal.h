@@ -1,6 +1,7 @@
 // runtime_internal.h -- shared by the host-runtime translation units behind the C ABI (include/sage_ba.h):
 //   operators.hip       workspaces, the per-edge operator API (df::*_calculate mirrors), the producer entry points
 //   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame)
+//   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
 //   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
@@ -185,6 +186,11 @@ struct SageWorkspace
   float *stats_ptr = nullptr;
   DevBuf trk_dpts, trk_kp_dpts;      // dof 7: depths scaled for the evaluation
   float *trk_host = nullptr;         // pinned: [pose 12 | pad 4 | photo AtA 49 Atb 7 | keypoint AtA 49 Atb 7 | stats 2 + 2]
+  // overlap statistics (sage_track_overlap, overlap.hip): per-workgroup partials + survivor counters, the survivors of
+  // both hull sets, and the pinned region the finish kernel publishes into; all grow with M and go with the workspace
+  DevBuf ov_part, ov_surv;
+  void *ov_host = nullptr;           // pinned: [header | survivors of the input set [cap][2] | of the warped set [cap][2]]
+  size_t ov_host_cap = 0;            // points per set the pinned region holds
 };
 
 // where an operator's kernels put {error, inliers}: the tracker's evaluation buffer, or the workspace's pinned mirror (the

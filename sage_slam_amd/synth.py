@@ -460,3 +460,28 @@ def make_pose_graph(w: Window, links, loops=(), local_targets: str = "start", dr
     holds = {k: 2 for k in range(len(kfs))}       # SAGE_HOLD_CODE
     holds[0] = 1 | 2                              # ... and keyframe 0's pose
     return dataclasses.replace(w, keyframes=kfs, links=[]), all_links, terms, holds
+
+
+# --------------------------------------------------------------------------- overlap statistics of a tracked pose
+OVERLAP_POSES = {              # name -> (rotation vector, translation): near, far, and mostly behind the camera
+    "small": ((0.02, -0.03, 0.05), (0.05, -0.02, 0.03)),
+    "big": ((0.1, 0.25, 0.4), (0.4, 0.1, -0.2)),
+    "behind": ((0.0, 0.9, 0.0), (0.2, 0.0, -0.9)),
+}
+
+
+def make_overlap_problem(H: int, W: int, rot=(0.0, 0.0, 0.0), trans=(0.0, 0.0, 0.0), seed: int = 0) -> dict:
+    """Inputs of ``sage_track_overlap`` (``CameraTracker::ComputeAreaInlierRatio``): the valid set of a keyframe under an
+    elliptical video mask ``((x - cx) / 0.48 W)^2 + ((y - cy) / 0.47 H)^2 < 1``, in raster order as
+    ``mapping_utils.h:254-287`` enumerates it, camera ``fx = fy = 0.9 W`` centred on the image, depths
+    ``1 + 0.3 sin(x / 7) + 0.2 U(0, 1)``, and the pose ``(so3_exp(rot), trans)``.
+    -> dict(cam, mask [H,W], dpts0 [M], homo [M,3], R [3,3], t [3], eps, M), everything fp32.  Deterministic per ``seed``."""
+    cam = Camera(F32(0.9 * W), F32(0.9 * W), F32(0.5 * (W - 1)), F32(0.5 * (H - 1)), F32(W), F32(H))
+    ys, xs = np.mgrid[0:H, 0:W]
+    mask = ((((xs - float(cam.cx)) / (0.48 * W)) ** 2 + ((ys - float(cam.cy)) / (0.47 * H)) ** 2) < 1.0).astype(F32)
+    vy, vx = np.nonzero(mask > 0.5)
+    rng = np.random.default_rng([seed, H, W, 411])
+    dpts0 = (1.0 + 0.3 * np.sin(vx / 7.0) + 0.2 * rng.random(vx.size)).astype(F32)
+    homo = np.stack([(vx.astype(F32) - cam.cx) / cam.fx, (vy.astype(F32) - cam.cy) / cam.fy, np.ones(vx.size, F32)], 1).astype(F32)
+    return dict(cam=cam, mask=mask, dpts0=dpts0, homo=homo, R=so3_exp(np.asarray(rot, np.float64)).astype(F32),
+                t=np.asarray(trans, F32), eps=F32(1e-4), M=int(vx.size))
