@@ -13,61 +13,45 @@ extern "C" int sage_workspace_create(void *hip_stream, SageWorkspace **out)
     return (int)hipErrorNoDevice;
   SageWorkspace *ws = new SageWorkspace();
   ws->stream = reinterpret_cast<hipStream_t>(hip_stream);
-  hipError_t e = hipHostMalloc((void **)&ws->host_stats, 16 * sizeof(float), hipHostMallocDefault);
-  if (e != hipSuccess)
+  const int rc = ws->host_stats.reserve(sizeof(WsHostStats));
+  if (rc)
   {
     delete ws;
-    return (int)e;
+    return rc;
   }
-  std::memset(ws->host_stats, 0, 16 * sizeof(float));
+  std::memset(ws->hs(), 0, sizeof(WsHostStats));
   *out = ws;
   return SAGE_OK;
 }
 
-extern "C" void sage_workspace_destroy(SageWorkspace *ws)
-{
-  if (!ws)
-    return;
-  if (ws->host_stats)
-    (void)hipHostFree(ws->host_stats);
-  if (ws->trk_host)
-    (void)hipHostFree(ws->trk_host);
-  if (ws->ov_host)
-    (void)hipHostFree(ws->ov_host);
-  delete ws; // (its device buffers go with it: DevBuf)
-}
+extern "C" void sage_workspace_destroy(SageWorkspace *ws) { delete ws; } // (its buffers go with it: DevBuf, PinnedBuf)
 
-static int ws_prepare(SageWorkspace *ws, int N, size_t partial_floats, LaunchCommon *lc)
+// the work list of ONE edge of N samples in the workspace's buffers, bound into lc with room for `partial_floats` per work
+// item.  Built and uploaded when the workspace holds another list (kind, N); N == 0 is one empty workgroup, so that the
+// finalize sees zeros
+static int ws_bind_work(SageWorkspace *ws, WorkKind kind, int N, size_t partial_floats, LaunchCommon *lc)
 {
-  if (!ws || N < 0)
+  if (!ws || (N < 0 && kind == WorkKind::dense)) // (the tracker's entry points have never refused N < 0: the list of N == 0)
     return SAGE_E_INVALID;
-  if (ws->cached_N != N)
+  int rc;
+  if (ws->list_kind != kind || ws->list_N != N)
   {
     WorkList wl;
-    wl.build(std::vector<int>{N});
+    wl.build(std::vector<int>{N}, kind == WorkKind::tracker ? 1 : 0);
     if (wl.work.empty())
-      wl.work.push_back(WorkItem{0, 0}); // N == 0: one empty workgroup so the finalize sees zeros
+      wl.work.push_back(WorkItem{0, 0});
     if (wl.edge_tiles[0] == 0)
       wl.edge_tiles[0] = 1;
-    int rc;
-    if ((rc = ws->work.reserve(wl.work.size() * sizeof(WorkItem))))
+    ws->list_kind = WorkKind::none; // (until all three arrays are the new list's)
+    if ((rc = upload(ws->work, wl.work, ws->stream)) || (rc = upload(ws->edge_first, wl.edge_first, ws->stream)) ||
+        (rc = upload(ws->edge_tiles, wl.edge_tiles, ws->stream)))
       return rc;
-    if ((rc = ws->edge_first.reserve(sizeof(int32_t))))
-      return rc;
-    if ((rc = ws->edge_tiles.reserve(sizeof(int32_t))))
-      return rc;
-    SAGE_HIP(hipMemcpyAsync(ws->work.p, wl.work.data(), wl.work.size() * sizeof(WorkItem), hipMemcpyHostToDevice,
-                            ws->stream));
-    SAGE_HIP(hipMemcpyAsync(ws->edge_first.p, wl.edge_first.data(), sizeof(int32_t), hipMemcpyHostToDevice,
-                            ws->stream));
-    SAGE_HIP(hipMemcpyAsync(ws->edge_tiles.p, wl.edge_tiles.data(), sizeof(int32_t), hipMemcpyHostToDevice,
-                            ws->stream));
     SAGE_HIP(hipStreamSynchronize(ws->stream)); // wl goes out of scope
-    ws->cached_N = N;
+    ws->list_kind = kind;
+    ws->list_N = N;
     ws->n_work = (int)wl.work.size();
     ws->tiles_per_block = wl.tiles_per_block;
   }
-  int rc;
   if ((rc = ws->partials.reserve((size_t)ws->n_work * partial_floats * sizeof(float))))
     return rc;
   lc->work = ws->work.as<WorkItem>();
@@ -88,37 +72,28 @@ __global__ void ticket_kernel(volatile unsigned *ticket, unsigned epoch)
 
 int ws_ticket_wait(SageWorkspace *ws)
 {
-  volatile unsigned *ticket = reinterpret_cast<volatile unsigned *>(ws->host_stats + 8);
+  volatile unsigned *ticket = &ws->hs()->ticket;
   if (++ws->ticket_epoch == 0)
     ws->ticket_epoch = 1;
   const unsigned epoch = ws->ticket_epoch;
   hipLaunchKernelGGL(ticket_kernel, dim3(1), dim3(1), 0, ws->stream, ticket, epoch);
   SAGE_HIP(hipGetLastError());
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned spins = 0;
-  while (*ticket != epoch)
-  {
-    __builtin_ia32_pause();
-    if ((++spins & 0x3ff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
-    {
-      SAGE_HIP(hipStreamSynchronize(ws->stream)); // (a long queue ahead of this operator: wait the ordinary way)
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  if (!spin_until([=] { return *ticket == epoch; }))
+    SAGE_HIP(hipStreamSynchronize(ws->stream)); // (a long queue ahead of this operator: wait the ordinary way)
   return SAGE_OK;
 }
 
-// the operator's kernels have written {error, inliers} into the pinned mirror themselves (ws_stats): wait for them
-static int ws_fetch_stats(SageWorkspace *ws, float *error_host, float *num_inliers_host)
+// the public entry points' half of an operator: its kernels have been enqueued (rc) with the workspace's own stats slot as
+// their destination; wait for them and hand {error, inliers} to the caller
+static float *ws_own_stats(SageWorkspace *ws) { return ws ? ws->hs()->stats : nullptr; }
+static int ws_fetch_stats(int rc, SageWorkspace *ws, float *error_host, float *num_inliers_host)
 {
-  const int rc = ws_ticket_wait(ws);
-  if (rc)
+  if (rc || (rc = ws_ticket_wait(ws)))
     return rc;
   if (error_host)
-    *error_host = ws->host_stats[0];
+    *error_host = ws->hs()->stats[0];
   if (num_inliers_host)
-    *num_inliers_host = ws->host_stats[1];
+    *num_inliers_host = ws->hs()->stats[1];
   return SAGE_OK;
 }
 
@@ -144,20 +119,26 @@ static int operator_depths(SageWorkspace *ws, int CS, const float *bias0, const 
 // =====================================================================================================
 // per-edge operator API
 // =====================================================================================================
-extern "C" int sage_photometric_jac_error_calculate(
-    SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host, float *num_inliers_host,
-    const float *R10, const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
-    const float *bias0, const float *basis0, const float *code0, const float *mask1, const int64_t *loc1d,
-    const float *homo, const float *feat0, const float *feat1, const float *grad1, float scale0,
-    const SagePyramid *pyr, float eps, const float *weights_host, int N, int FS, int CS)
+// Every operator family is an enqueue function -- validate, reserve, launch; its kernels write {error, inliers} to `stats`
+// and nobody waits -- and the public entry points: the enqueue with the workspace's own stats slot, then ws_fetch_stats.
+// The jac and the error variant of a family share the enqueue; where their rules differ (which pointers may be NULL) it
+// says so.
+static int photo_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, float *stats, const float *R10,
+                         const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
+                         const float *bias0, const float *basis0, const float *code0, const float *mask1,
+                         const int64_t *loc1d, const float *homo, const float *feat0, const float *feat1,
+                         const float *grad1, float scale0, const SagePyramid *pyr, float eps, const float *weights_host,
+                         int N, int FS, int CS)
 {
-  if (!ws || !AtA_dev || !Atb_dev || !pyr || !weights_host || !R0 || !t0 || !R1 || !t1 || !bias0 || !basis0 ||
-      !code0 || !mask1 || !loc1d || !homo || !feat0 || !feat1 || !grad1)
+  if (!ws || !pyr || !weights_host || !bias0 || !basis0 || !code0 || !mask1 || !loc1d || !homo || !feat0 || !feat1)
+    return SAGE_E_INVALID;
+  // jac: the absolute poses, R10 / t10 optional (the kernel forms them); error: the relative pose only
+  if (jac ? (!AtA || !Atb || !R0 || !t0 || !R1 || !t1 || !grad1) : (!R10 || !t10))
     return SAGE_E_INVALID;
   if (!supported(CS, FS) || pyr->levels < 1 || pyr->levels > SAGE_MAX_LEVELS)
     return SAGE_E_UNSUPPORTED;
   LaunchCommon lc;
-  int rc = ws_prepare(ws, N, photo_partial_floats(CS), &lc);
+  int rc = ws_bind_work(ws, WorkKind::dense, N, jac ? photo_partial_floats(CS) : 2, &lc);
   if (rc)
     return rc;
   // depth map of the source keyframe at (code0, scale0): the kernel reads its sample depths from it
@@ -169,9 +150,24 @@ extern "C" int sage_photometric_jac_error_calculate(
   e.homo = homo; e.loc = loc1d; e.loc_is_i64 = 1;
   e.R0 = R0; e.t0 = t0; e.R1 = R1; e.t1 = t1; e.R10 = R10; e.t10 = R10 ? t10 : nullptr;
   e.code0 = code0; e.scale0 = nullptr; e.scale0_val = scale0; e.N = N;
-  EdgeOut out{AtA_dev, Atb_dev, ws_stats(ws)};
-  SAGE_HIP(launch_photo_linearize(ws->stream, CS, FS, &e, nullptr, lc, *pyr, weights_host, eps, out));
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+  if (jac)
+    SAGE_HIP(launch_photo_linearize(ws->stream, CS, FS, &e, nullptr, lc, *pyr, weights_host, eps, EdgeOut{AtA, Atb, stats}));
+  else
+    SAGE_HIP(launch_photo_error(ws->stream, CS, FS, &e, nullptr, lc, *pyr, weights_host, eps, stats));
+  return SAGE_OK;
+}
+
+extern "C" int sage_photometric_jac_error_calculate(
+    SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host, float *num_inliers_host,
+    const float *R10, const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
+    const float *bias0, const float *basis0, const float *code0, const float *mask1, const int64_t *loc1d,
+    const float *homo, const float *feat0, const float *feat1, const float *grad1, float scale0,
+    const SagePyramid *pyr, float eps, const float *weights_host, int N, int FS, int CS)
+{
+  return ws_fetch_stats(photo_enqueue(ws, true, AtA_dev, Atb_dev, ws_own_stats(ws), R10, t10, R0, t0, R1, t1, bias0, basis0,
+                                      code0, mask1, loc1d, homo, feat0, feat1, grad1, scale0, pyr, eps, weights_host, N, FS,
+                                      CS),
+                        ws, error_host, num_inliers_host);
 }
 
 extern "C" int sage_photometric_error_calculate(
@@ -180,31 +176,15 @@ extern "C" int sage_photometric_error_calculate(
     const float *homo, const float *feat0, const float *feat1, float scale0, const SagePyramid *pyr, float eps,
     const float *weights_host, int N, int FS, int CS)
 {
-  if (!ws || !pyr || !weights_host || !R10 || !t10 || !bias0 || !basis0 || !code0 || !mask1 || !loc1d || !homo ||
-      !feat0 || !feat1)
-    return SAGE_E_INVALID;
-  if (!supported(CS, FS) || pyr->levels < 1 || pyr->levels > SAGE_MAX_LEVELS)
-    return SAGE_E_UNSUPPORTED;
-  LaunchCommon lc;
-  int rc = ws_prepare(ws, N, 2, &lc);
-  if (rc)
-    return rc;
-  // depth map of the source keyframe at (code0, scale0): the kernel reads its sample depths from it
-  if ((rc = operator_depths(ws, CS, bias0, basis0, code0, scale0, loc1d, 1, N, (int)pyr->cam[0].h, (int)pyr->cam[0].w)))
-    return rc;
-  PhotoEdge e{};
-  e.dpt0 = ws->dpt0.as<float>();
-  e.feat0 = feat0; e.feat1 = feat1; e.grad1 = nullptr; e.bias0 = bias0; e.basis0 = basis0; e.mask1 = mask1;
-  e.homo = homo; e.loc = loc1d; e.loc_is_i64 = 1;
-  e.R10 = R10; e.t10 = t10; e.code0 = code0; e.scale0 = nullptr; e.scale0_val = scale0; e.N = N;
-  SAGE_HIP(launch_photo_error(ws->stream, CS, FS, &e, nullptr, lc, *pyr, weights_host, eps, ws_stats(ws)));
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+  return ws_fetch_stats(photo_enqueue(ws, false, nullptr, nullptr, ws_own_stats(ws), R10, t10, nullptr, nullptr, nullptr,
+                                      nullptr, bias0, basis0, code0, mask1, loc1d, homo, feat0, feat1, nullptr, scale0, pyr,
+                                      eps, weights_host, N, FS, CS),
+                        ws, error_host, num_inliers_host);
 }
 
-static int track_common(SageWorkspace *ws, bool jac, int dof, float *AtA, float *Atb, float *error_host,
-                        float *num_inliers_host, const float *R, const float *t, const float *mask1,
-                        const float *dpts0, const float *homo, const float *feat0s, const float *feat1,
-                        const float *grad1, const SagePyramid *pyr, float scale0, float eps,
+int track_photo_enqueue(SageWorkspace *ws, bool jac, int dof, float *AtA, float *Atb, float *stats, const float *R,
+                        const float *t, const float *mask1, const float *dpts0, const float *homo, const float *feat0s,
+                        const float *feat1, const float *grad1, const SagePyramid *pyr, float scale0, float eps,
                         const float *weights_dev, int N, int FS)
 {
   if (!ws || !pyr || !R || !t || !mask1 || !dpts0 || !homo || !feat0s || !feat1 || !weights_dev ||
@@ -212,43 +192,18 @@ static int track_common(SageWorkspace *ws, bool jac, int dof, float *AtA, float 
     return SAGE_E_INVALID;
   if ((FS != 16 && FS != 32) || pyr->levels < 1 || pyr->levels > SAGE_MAX_LEVELS)
     return SAGE_E_UNSUPPORTED;
-  // tracker kernels process exactly one kTile per workgroup
-  if (ws->cached_N != -(N + 2))
-  {
-    std::vector<WorkItem> work;
-    for (int tl = 0; tl < std::max(1, (N + kTile - 1) / kTile); ++tl)
-      work.push_back(WorkItem{0, tl});
-    int rc;
-    if ((rc = ws->work.reserve(work.size() * sizeof(WorkItem))))
-      return rc;
-    SAGE_HIP(hipMemcpyAsync(ws->work.p, work.data(), work.size() * sizeof(WorkItem), hipMemcpyHostToDevice,
-                            ws->stream));
-    SAGE_HIP(hipStreamSynchronize(ws->stream));
-    ws->cached_N = -(N + 2);
-    ws->n_work = (int)work.size();
-  }
-  int rc;
-  if ((rc = ws->partials.reserve((size_t)ws->n_work * kTrackScalars * sizeof(float))))
-    return rc;
   LaunchCommon lc{};
-  lc.work = ws->work.as<WorkItem>();
-  lc.n_work = ws->n_work;
-  lc.n_edges = 1;
-  lc.partials = ws->partials.as<float>();
-  lc.tiles_per_block = 1;
+  const int rc = ws_bind_work(ws, WorkKind::tracker, N, kTrackScalars, &lc);
+  if (rc)
+    return rc;
   TrackEdge e{};
   e.feat0s = feat0s; e.feat1 = feat1; e.grad1 = grad1; e.mask1 = mask1; e.homo = homo; e.dpts0 = dpts0;
   e.R = R; e.t = t; e.weights = weights_dev; e.scale0 = scale0; e.N = N;
   if (jac)
-  {
-    EdgeOut out{AtA, Atb, ws_stats(ws)};
-    SAGE_HIP(launch_track_linearize(ws->stream, dof, FS, e, lc, *pyr, eps, out));
-  }
+    SAGE_HIP(launch_track_linearize(ws->stream, dof, FS, e, lc, *pyr, eps, EdgeOut{AtA, Atb, stats}));
   else
-    SAGE_HIP(launch_track_error(ws->stream, FS, e, lc, *pyr, eps, ws_stats(ws)));
-  if (ws->defer_fetch)
-    return SAGE_OK;
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+    SAGE_HIP(launch_track_error(ws->stream, FS, e, lc, *pyr, eps, stats));
+  return SAGE_OK;
 }
 
 extern "C" int sage_tracker_photo_jac_error_calculate(
@@ -259,8 +214,9 @@ extern "C" int sage_tracker_photo_jac_error_calculate(
 {
   if (dof != 6 && dof != 7)
     return SAGE_E_INVALID;
-  return track_common(ws, true, dof, AtA_dev, Atb_dev, error_host, num_inliers_host, R, t, mask1, dpts0, homo,
-                      feat0s, feat1, grad1, pyr, scale0, eps, weights_dev, N, FS);
+  return ws_fetch_stats(track_photo_enqueue(ws, true, dof, AtA_dev, Atb_dev, ws_own_stats(ws), R, t, mask1, dpts0, homo,
+                                            feat0s, feat1, grad1, pyr, scale0, eps, weights_dev, N, FS),
+                        ws, error_host, num_inliers_host);
 }
 
 extern "C" int sage_tracker_photo_error_calculate(
@@ -268,24 +224,27 @@ extern "C" int sage_tracker_photo_error_calculate(
     const float *mask1, const float *dpts0, const float *homo, const float *feat0s, const float *feat1,
     const SagePyramid *pyr, float eps, const float *weights_dev, int N, int FS)
 {
-  return track_common(ws, false, 6, nullptr, nullptr, error_host, num_inliers_host, R, t, mask1, dpts0, homo,
-                      feat0s, feat1, nullptr, pyr, 1.0f, eps, weights_dev, N, FS);
+  return ws_fetch_stats(track_photo_enqueue(ws, false, 6, nullptr, nullptr, ws_own_stats(ws), R, t, mask1, dpts0, homo,
+                                            feat0s, feat1, nullptr, pyr, 1.0f, eps, weights_dev, N, FS),
+                        ws, error_host, num_inliers_host);
 }
 
-extern "C" int sage_geometric_jac_error_calculate(
-    SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host, float *num_inliers_host,
-    const float *R10, const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
-    const float *bias0, const float *basis0, const float *code0, const float *dpt1, const float *dgrad1,
-    const float *basis1, const float *mask1, const int32_t *loc1d, const float *homo, float scale0, float scale1,
-    const SageCamera *cam, float eps, float loss_param, float weight, int N, int CS)
+static int geo_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, float *stats, const float *R10,
+                       const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
+                       const float *bias0, const float *basis0, const float *code0, const float *dpt1,
+                       const float *dgrad1, const float *basis1, const float *mask1, const int32_t *loc1d,
+                       const float *homo, float scale0, float scale1, const SageCamera *cam, float eps, float loss_param,
+                       float weight, int N, int CS)
 {
-  if (!ws || !AtA_dev || !Atb_dev || !cam || !R0 || !t0 || !R1 || !t1 || !bias0 || !basis0 || !code0 || !dpt1 ||
-      !dgrad1 || !basis1 || !mask1 || !loc1d || !homo)
+  if (!ws || !cam || !bias0 || !basis0 || !code0 || !dpt1 || !mask1 || !loc1d || !homo)
+    return SAGE_E_INVALID;
+  // jac: the absolute poses, R10 / t10 optional (the kernel forms them); error: the relative pose only
+  if (jac ? (!AtA || !Atb || !R0 || !t0 || !R1 || !t1 || !dgrad1 || !basis1) : (!R10 || !t10))
     return SAGE_E_INVALID;
   if (CS != 16 && CS != 32)
     return SAGE_E_UNSUPPORTED;
   LaunchCommon lc;
-  int rc = ws_prepare(ws, N, geo_partial_floats(CS), &lc);
+  int rc = ws_bind_work(ws, WorkKind::dense, N, jac ? geo_partial_floats(CS) : 2, &lc);
   if (rc)
     return rc;
   // depth map of the source keyframe at (code0, scale0): the kernel reads its sample depths from it
@@ -297,9 +256,24 @@ extern "C" int sage_geometric_jac_error_calculate(
   e.homo = homo; e.loc = loc1d; e.loc_is_i64 = 0;
   e.R0 = R0; e.t0 = t0; e.R1 = R1; e.t1 = t1; e.R10 = R10; e.t10 = R10 ? t10 : nullptr;
   e.code0 = code0; e.scale0 = nullptr; e.scale1 = nullptr; e.scale0_val = scale0; e.scale1_val = scale1; e.N = N;
-  EdgeOut out{AtA_dev, Atb_dev, ws_stats(ws)};
-  SAGE_HIP(launch_geo_linearize(ws->stream, CS, &e, nullptr, lc, *cam, eps, loss_param, weight, out));
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+  if (jac)
+    SAGE_HIP(launch_geo_linearize(ws->stream, CS, &e, nullptr, lc, *cam, eps, loss_param, weight, EdgeOut{AtA, Atb, stats}));
+  else
+    SAGE_HIP(launch_geo_error(ws->stream, CS, &e, nullptr, lc, *cam, eps, loss_param, weight, stats));
+  return SAGE_OK;
+}
+
+extern "C" int sage_geometric_jac_error_calculate(
+    SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host, float *num_inliers_host,
+    const float *R10, const float *t10, const float *R0, const float *t0, const float *R1, const float *t1,
+    const float *bias0, const float *basis0, const float *code0, const float *dpt1, const float *dgrad1,
+    const float *basis1, const float *mask1, const int32_t *loc1d, const float *homo, float scale0, float scale1,
+    const SageCamera *cam, float eps, float loss_param, float weight, int N, int CS)
+{
+  return ws_fetch_stats(geo_enqueue(ws, true, AtA_dev, Atb_dev, ws_own_stats(ws), R10, t10, R0, t0, R1, t1, bias0, basis0,
+                                    code0, dpt1, dgrad1, basis1, mask1, loc1d, homo, scale0, scale1, cam, eps, loss_param,
+                                    weight, N, CS),
+                        ws, error_host, num_inliers_host);
 }
 
 extern "C" int sage_geometric_error_calculate(
@@ -308,22 +282,10 @@ extern "C" int sage_geometric_error_calculate(
     const int32_t *loc1d, const float *homo, float scale0, const SageCamera *cam, float eps, float loss_param,
     float weight, int N, int CS)
 {
-  if (!ws || !cam || !R10 || !t10 || !bias0 || !basis0 || !code0 || !dpt1 || !mask1 || !loc1d || !homo)
-    return SAGE_E_INVALID;
-  if (CS != 16 && CS != 32)
-    return SAGE_E_UNSUPPORTED;
-  LaunchCommon lc;
-  int rc = ws_prepare(ws, N, 2, &lc);
-  if (rc)
-    return rc;
-  if ((rc = operator_depths(ws, CS, bias0, basis0, code0, scale0, loc1d, 0, N, (int)cam->h, (int)cam->w)))
-    return rc;
-  GeoEdge e{};
-  e.dpt0 = ws->dpt0.as<float>();
-  e.bias0 = bias0; e.basis0 = basis0; e.dpt1 = dpt1; e.mask1 = mask1; e.homo = homo; e.loc = loc1d;
-  e.loc_is_i64 = 0; e.R10 = R10; e.t10 = t10; e.code0 = code0; e.scale0_val = scale0; e.scale1_val = 1.f; e.N = N;
-  SAGE_HIP(launch_geo_error(ws->stream, CS, &e, nullptr, lc, *cam, eps, loss_param, weight, ws_stats(ws)));
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+  return ws_fetch_stats(geo_enqueue(ws, false, nullptr, nullptr, ws_own_stats(ws), R10, t10, nullptr, nullptr, nullptr,
+                                    nullptr, bias0, basis0, code0, dpt1, nullptr, nullptr, mask1, loc1d, homo, scale0, 1.f,
+                                    cam, eps, loss_param, weight, N, CS),
+                        ws, error_host, num_inliers_host);
 }
 
 extern "C" int sage_depth_and_grad(SageWorkspace *ws, float *dpt, float *grad, const float *bias, const float *basis,
@@ -338,8 +300,8 @@ extern "C" int sage_depth_and_grad(SageWorkspace *ws, float *dpt, float *grad, c
 }
 
 // ---- sparse reprojection factor (keypoint_kernels.hip) ----
-static int reproj_common(SageWorkspace *ws, bool tracker, bool jac, float *AtA, float *Atb, float *error_host,
-                         float *num_inliers_host, ReprojParams p, const SageCamera *cam, int CS)
+static int reproj_enqueue(SageWorkspace *ws, bool tracker, bool jac, float *AtA, float *Atb, float *stats, ReprojParams p,
+                          const SageCamera *cam, int CS)
 {
   const int N = p.N;
   if (!ws || !cam || N < 0 || !p.R10 || !p.t10 || (N > 0 && (!p.homo || !p.matched)) || (jac && (!AtA || !Atb)))
@@ -354,10 +316,8 @@ static int reproj_common(SageWorkspace *ws, bool tracker, bool jac, float *AtA, 
   int rc;
   if ((rc = ws->misc.reserve(kp_scratch_floats(kReprojRows, N, reproj_dim(tracker ? 1 : 0, CS)) * sizeof(float))))
     return rc;
-  SAGE_HIP(launch_reproj(ws->stream, CS, tracker, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, ws_stats(ws)}));
-  if (ws->defer_fetch)
-    return SAGE_OK;
-  return ws_fetch_stats(ws, error_host, num_inliers_host);
+  SAGE_HIP(launch_reproj(ws->stream, CS, tracker, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, stats}));
+  return SAGE_OK;
 }
 
 extern "C" int sage_reprojection_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host,
@@ -372,7 +332,8 @@ extern "C" int sage_reprojection_jac_error_calculate(SageWorkspace *ws, float *A
   p.R10 = R10; p.t10 = t10; p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1;
   p.bias0 = bias0; p.basis0 = basis0; p.code0 = code0; p.loc = loc1d; p.homo = homo; p.matched = matched_2d;
   p.scale0 = scale0; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
-  return reproj_common(ws, false, true, AtA_dev, Atb_dev, error_host, num_inliers_host, p, cam, CS);
+  return ws_fetch_stats(reproj_enqueue(ws, false, true, AtA_dev, Atb_dev, ws_own_stats(ws), p, cam, CS), ws, error_host,
+                        num_inliers_host);
 }
 
 extern "C" int sage_reprojection_error_calculate(SageWorkspace *ws, float *error_host, float *num_inliers_host,
@@ -386,7 +347,18 @@ extern "C" int sage_reprojection_error_calculate(SageWorkspace *ws, float *error
   p.R10 = R10; p.t10 = t10;
   p.bias0 = bias0; p.basis0 = basis0; p.code0 = code0; p.loc = loc1d; p.homo = homo; p.matched = matched_2d;
   p.scale0 = scale0; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
-  return reproj_common(ws, false, false, nullptr, nullptr, error_host, num_inliers_host, p, cam, CS);
+  return ws_fetch_stats(reproj_enqueue(ws, false, false, nullptr, nullptr, ws_own_stats(ws), p, cam, CS), ws, error_host,
+                        num_inliers_host);
+}
+
+int track_reproj_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, float *stats, const float *R, const float *t,
+                         const float *sampled_dpts0, const float *homo, const float *matched_2d, const SageCamera *cam,
+                         float eps, float loss_param, float weight, int N)
+{
+  ReprojParams p{}; // tracker: R10 / t10 = the relative pose, depths handed over
+  p.R10 = R; p.t10 = t; p.dpts0 = sampled_dpts0; p.homo = homo; p.matched = matched_2d;
+  p.scale0 = 1.f; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
+  return reproj_enqueue(ws, true, jac, AtA, Atb, stats, p, cam, 16);
 }
 
 extern "C" int sage_tracker_reproj_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev,
@@ -395,10 +367,9 @@ extern "C" int sage_tracker_reproj_jac_error_calculate(SageWorkspace *ws, float 
                                                        const float *matched_2d, const SageCamera *cam, float eps,
                                                        float loss_param, float weight, int N)
 {
-  ReprojParams p{}; // tracker: R10 / t10 = the relative pose, depths handed over
-  p.R10 = R; p.t10 = t; p.dpts0 = sampled_dpts0; p.homo = homo; p.matched = matched_2d;
-  p.scale0 = 1.f; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
-  return reproj_common(ws, true, true, AtA_dev, Atb_dev, error_host, num_inliers_host, p, cam, 16);
+  return ws_fetch_stats(track_reproj_enqueue(ws, true, AtA_dev, Atb_dev, ws_own_stats(ws), R, t, sampled_dpts0, homo,
+                                             matched_2d, cam, eps, loss_param, weight, N),
+                        ws, error_host, num_inliers_host);
 }
 
 extern "C" int sage_tracker_reproj_error_calculate(SageWorkspace *ws, float *error_host, float *num_inliers_host,
@@ -406,15 +377,13 @@ extern "C" int sage_tracker_reproj_error_calculate(SageWorkspace *ws, float *err
                                                    const float *homo, const float *matched_2d, const SageCamera *cam,
                                                    float eps, float loss_param, float weight, int N)
 {
-  ReprojParams p{}; // tracker: R10 / t10 = the relative pose, depths handed over
-  p.R10 = R; p.t10 = t; p.dpts0 = sampled_dpts0; p.homo = homo; p.matched = matched_2d;
-  p.scale0 = 1.f; p.eps = eps; p.loss_param = loss_param; p.weight = weight; p.N = N;
-  return reproj_common(ws, true, false, nullptr, nullptr, error_host, num_inliers_host, p, cam, 16);
+  return ws_fetch_stats(track_reproj_enqueue(ws, false, nullptr, nullptr, ws_own_stats(ws), R, t, sampled_dpts0, homo,
+                                             matched_2d, cam, eps, loss_param, weight, N),
+                        ws, error_host, num_inliers_host);
 }
 
 // ---- match-geometry factors (keypoint_kernels.hip) ----
-static int mg_common(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *error_host, const MgParams &p,
-                     int CS)
+static int mg_enqueue(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *stats, const MgParams &p, int CS)
 {
   if (!ws || p.N < 1 || !p.R10 || !p.t10 || !p.homo0 || !p.homo1 || (jac && (!AtA || !Atb)))
     return SAGE_E_INVALID;
@@ -431,10 +400,8 @@ static int mg_common(SageWorkspace *ws, int mode, bool jac, float *AtA, float *A
   int rc;
   if ((rc = ws->misc.reserve(kp_scratch_floats(kMgRows, p.N, mg_dim(mode, CS)) * sizeof(float))))
     return rc;
-  SAGE_HIP(launch_match_geom(ws->stream, mode, CS, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, ws_stats(ws)}));
-  if (ws->defer_fetch)
-    return SAGE_OK;
-  return ws_fetch_stats(ws, error_host, nullptr);
+  SAGE_HIP(launch_match_geom(ws->stream, mode, CS, jac, p, ws->misc.as<float>(), KpOut{AtA, Atb, stats}));
+  return SAGE_OK;
 }
 
 extern "C" int sage_match_geometry_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev,
@@ -453,7 +420,7 @@ extern "C" int sage_match_geometry_jac_error_calculate(SageWorkspace *ws, float 
   p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1;
   p.bias0 = bias0; p.bias1 = bias1; p.basis0 = basis0; p.basis1 = basis1; p.code0 = code0; p.code1 = code1;
   p.loc0 = loc1d_0; p.loc1 = matched_loc1d_1;
-  return mg_common(ws, 0, true, AtA_dev, Atb_dev, error_host, p, CS);
+  return ws_fetch_stats(mg_enqueue(ws, 0, true, AtA_dev, Atb_dev, ws_own_stats(ws), p, CS), ws, error_host, nullptr);
 }
 
 extern "C" int sage_match_geometry_error_calculate(SageWorkspace *ws, float *error_host, const float *R10,
@@ -468,7 +435,7 @@ extern "C" int sage_match_geometry_error_calculate(SageWorkspace *ws, float *err
   p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = loss; p.N = N;
   p.bias0 = bias0; p.bias1 = bias1; p.basis0 = basis0; p.basis1 = basis1; p.code0 = code0; p.code1 = code1;
   p.loc0 = loc1d_0; p.loc1 = matched_loc1d_1;
-  return mg_common(ws, 0, false, nullptr, nullptr, error_host, p, CS);
+  return ws_fetch_stats(mg_enqueue(ws, 0, false, nullptr, nullptr, ws_own_stats(ws), p, CS), ws, error_host, nullptr);
 }
 
 extern "C" int sage_loop_mg_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev, float *error_host,
@@ -482,7 +449,7 @@ extern "C" int sage_loop_mg_jac_error_calculate(SageWorkspace *ws, float *AtA_de
   p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
   p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
   p.R0 = R0; p.t0 = t0; p.R1 = R1; p.t1 = t1; p.dpts0 = unscaled_dpts0; p.dpts1 = matched_unscaled_dpts1;
-  return mg_common(ws, 1, true, AtA_dev, Atb_dev, error_host, p, 16);
+  return ws_fetch_stats(mg_enqueue(ws, 1, true, AtA_dev, Atb_dev, ws_own_stats(ws), p, 16), ws, error_host, nullptr);
 }
 
 extern "C" int sage_loop_mg_error_calculate(SageWorkspace *ws, float *error_host, const float *R10, const float *t10,
@@ -494,7 +461,19 @@ extern "C" int sage_loop_mg_error_calculate(SageWorkspace *ws, float *error_host
   p.R10 = R10; p.t10 = t10; p.homo0 = homo0; p.homo1 = matched_homo1;
   p.scale0 = scale0; p.scale1 = scale1; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
   p.dpts0 = unscaled_dpts0; p.dpts1 = matched_unscaled_dpts1;
-  return mg_common(ws, 1, false, nullptr, nullptr, error_host, p, 16);
+  return ws_fetch_stats(mg_enqueue(ws, 1, false, nullptr, nullptr, ws_own_stats(ws), p, 16), ws, error_host, nullptr);
+}
+
+// tracker: R10 / t10 = the relative pose, depths handed over; mode 2 = pose only, 3 = pose and scale
+int track_match_geom_enqueue(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *stats, const float *R,
+                             const float *t, const float *sampled_dpts0, const float *matched_dpts1, const float *homo0,
+                             const float *matched_homo1, float scale0, float loss_param, float weight, int N)
+{
+  MgParams p{};
+  p.R10 = R; p.t10 = t; p.homo0 = homo0; p.homo1 = matched_homo1;
+  p.scale0 = scale0; p.scale1 = 1.f; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
+  p.dpts0 = sampled_dpts0; p.dpts1 = matched_dpts1;
+  return mg_enqueue(ws, mode, jac, AtA, Atb, stats, p, 16);
 }
 
 extern "C" int sage_tracker_match_geom_jac_error_calculate(SageWorkspace *ws, float *AtA_dev, float *Atb_dev,
@@ -503,11 +482,10 @@ extern "C" int sage_tracker_match_geom_jac_error_calculate(SageWorkspace *ws, fl
                                                            const float *homo0, const float *matched_homo1, float scale0,
                                                            float loss_param, float weight, int with_scale, int N)
 {
-  MgParams p{};
-  p.R10 = R; p.t10 = t; p.homo0 = homo0; p.homo1 = matched_homo1;
-  p.scale0 = scale0; p.scale1 = 1.f; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
-  p.dpts0 = sampled_dpts0; p.dpts1 = matched_dpts1;
-  return mg_common(ws, with_scale ? 3 : 2, true, AtA_dev, Atb_dev, error_host, p, 16);
+  return ws_fetch_stats(track_match_geom_enqueue(ws, with_scale ? 3 : 2, true, AtA_dev, Atb_dev, ws_own_stats(ws), R, t,
+                                                 sampled_dpts0, matched_dpts1, homo0, matched_homo1, scale0, loss_param,
+                                                 weight, N),
+                        ws, error_host, nullptr);
 }
 
 extern "C" int sage_tracker_match_geom_error_calculate(SageWorkspace *ws, float *error_host, const float *R,
@@ -515,11 +493,9 @@ extern "C" int sage_tracker_match_geom_error_calculate(SageWorkspace *ws, float 
                                                        const float *matched_dpts1, const float *homo0,
                                                        const float *matched_homo1, float loss_param, float weight, int N)
 {
-  MgParams p{};
-  p.R10 = R; p.t10 = t; p.homo0 = homo0; p.homo1 = matched_homo1;
-  p.scale0 = 1.f; p.scale1 = 1.f; p.loss_param = loss_param; p.weight = weight; p.loss = SAGE_LOSS_FAIR; p.N = N;
-  p.dpts0 = sampled_dpts0; p.dpts1 = matched_dpts1;
-  return mg_common(ws, 2, false, nullptr, nullptr, error_host, p, 16);
+  return ws_fetch_stats(track_match_geom_enqueue(ws, 2, false, nullptr, nullptr, ws_own_stats(ws), R, t, sampled_dpts0,
+                                                 matched_dpts1, homo0, matched_homo1, 1.f, loss_param, weight, N),
+                        ws, error_host, nullptr);
 }
 
 extern "C" int sage_cycle_match(SageWorkspace *ws, const float *desc0, const float *desc1, const int64_t *kp_loc1d_0,

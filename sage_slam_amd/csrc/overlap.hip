@@ -342,15 +342,9 @@ extern "C" int sage_track_overlap(SageWorkspace *ws, const float *R, const float
   int rc;
   if ((rc = ws->ov_part.reserve(kOvPartBytes)) || (rc = ws->ov_surv.reserve((size_t)M * 4 * sizeof(float))))
     return rc;
-  if (ws->ov_host_cap < (size_t)M)
-  {
-    if (ws->ov_host)
-      (void)hipHostFree(ws->ov_host); // (every earlier call has been waited for: nobody writes it)
-    ws->ov_host = nullptr;
-    ws->ov_host_cap = 0;
-    SAGE_HIP(hipHostMalloc(&ws->ov_host, sizeof(OvHeader) + (size_t)M * 4 * sizeof(float), hipHostMallocDefault));
-    ws->ov_host_cap = (size_t)M;
-  }
+  // (every earlier call has been waited for: nobody writes the pinned region while it is replaced by a larger one)
+  if ((rc = ws->ov_host.reserve(sizeof(OvHeader) + (size_t)M * 4 * sizeof(float))))
+    return rc;
   OvParams P;
   std::memcpy(P.R, R, sizeof(P.R));
   std::memcpy(P.t, t, sizeof(P.t));
@@ -365,7 +359,7 @@ extern "C" int sage_track_overlap(SageWorkspace *ws, const float *R, const float
   P.part_ext = reinterpret_cast<float *>(P.n_surv + 4);
   P.surv[0] = ws->ov_surv.as<float>();
   P.surv[1] = P.surv[0] + (size_t)M * 2;
-  OvHeader *head = static_cast<OvHeader *>(ws->ov_host);
+  OvHeader *head = ws->ov_host.as<OvHeader>();
   P.host_head = head;
   P.host_surv[0] = reinterpret_cast<float *>(head + 1);
   P.host_surv[1] = P.host_surv[0] + (size_t)M * 2;

@@ -1,6 +1,7 @@
 // runtime_internal.h -- shared by the host-runtime translation units behind the C ABI (include/sage_ba.h):
-//   operators.hip       workspaces, the per-edge operator API (df::*_calculate mirrors), the producer entry points
-//   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame)
+//   operators.hip       workspaces (work-list cache, ticket wait), the per-edge operator API (df::*_calculate mirrors): an
+//                       enqueue function per family + the public wrappers that wait; the producer entry points
+//   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame): one evaluation over the enqueue functions
 //   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
@@ -13,7 +14,8 @@
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
 // window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, totals mirror,
-// distributed state, profiler); DevBuf owns its allocation
+// distributed state, profiler); device_buffers.h holds the owners of device and pinned allocations (DevBuf, PinnedBuf: also
+// included by solve_kernels.hip); the layouts of the workspace's pinned regions (WsHostStats, TrackHost) are below
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,6 +26,7 @@
 #include <sched.h>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -49,6 +52,7 @@ extern "C"
 }
 #endif
 
+#include "device_buffers.h" // DevBuf, PinnedBuf
 #include "host_math.h"
 #include "host_threads.h" // placement, shutdown (the window units do not touch the block solver itself)
 #include "sage_ba.h"
@@ -69,51 +73,6 @@ using namespace sage;
 
 namespace sage_rt
 {
-
-// a device allocation and its owner: released when it goes out of scope; moves, never copies
-struct DevBuf
-{
-  void *p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept { swap(o); }
-  DevBuf &operator=(DevBuf &&o) noexcept
-  {
-    DevBuf(std::move(o)).swap(*this); // (what this one held goes with the temporary)
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  void swap(DevBuf &o) noexcept
-  {
-    std::swap(p, o.p);
-    std::swap(cap, o.cap);
-  }
-  int reserve(size_t bytes)
-  {
-    if (bytes <= cap)
-      return 0;
-    release();
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess)
-    {
-      p = nullptr;
-      return (int)e;
-    }
-    cap = bytes;
-    return 0;
-  }
-  void release()
-  {
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 inline int pick_tiles_per_block(long long total_tiles)
 {
@@ -164,42 +123,96 @@ struct WorkList
   }
 };
 
+// spin until done() holds (a ticket a kernel posts into pinned memory), looking at the clock every 1024 spins; false: 0.05 s
+// have passed and done() still does not hold -- the caller waits the ordinary way
+template <class Pred>
+inline bool spin_until(Pred done)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned spins = 0;
+  while (!done())
+  {
+    __builtin_ia32_pause();
+    if ((++spins & 0x3ff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
+      return false;
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return true;
+}
+
 } // namespace sage_rt
 using namespace sage_rt;
 
 // =====================================================================================================
 // workspace
 // =====================================================================================================
+// the workspace's pinned regions as the device sees them; the kernels write them over PCIe themselves (no device-to-host
+// copy afterwards)
+struct WsHostStats // SageWorkspace::host_stats
+{
+  float stats[4]; // the operator's {error, inliers}, written by its kernels
+  float pad[4];
+  unsigned ticket; // ws_ticket_wait
+  unsigned tail[7];
+};
+static_assert(offsetof(WsHostStats, ticket) == 8 * sizeof(float) && sizeof(WsHostStats) == 16 * sizeof(float), "device-visible layout");
+
+struct TrackHost // SageWorkspace::trk_host: one tracker evaluation (tracker.hip)
+{
+  float pose[12]; // what the kernels read: R [9], t [3]
+  float pad[4];
+  float photo_AtA[49], photo_Atb[7];
+  float kp_AtA[49], kp_Atb[7];
+  float stats[4]; // {error, inliers} of the photometric term, then of the keypoint term
+  float tail[12];
+};
+static_assert(offsetof(TrackHost, photo_AtA) == 16 * sizeof(float) && offsetof(TrackHost, photo_Atb) == (16 + 49) * sizeof(float) &&
+                  offsetof(TrackHost, kp_AtA) == (16 + 56) * sizeof(float) && offsetof(TrackHost, kp_Atb) == (16 + 56 + 49) * sizeof(float) &&
+                  offsetof(TrackHost, stats) == (16 + 112) * sizeof(float) && sizeof(TrackHost) == (16 + 112 + 4 + 12) * sizeof(float),
+              "device-visible layout");
+
+enum class WorkKind { none, dense, tracker }; // dense: pick_tiles_per_block's run length; tracker: one kTile per workgroup
+
 struct SageWorkspace
 {
   hipStream_t stream = nullptr;
   DevBuf work, edge_first, edge_tiles, partials, misc, dpt0;
-  float *host_stats = nullptr; // pinned, 16 floats: [0, 4) the operator's {error, inliers}, written by its kernels; [8] the ticket
+  PinnedBuf host_stats; // WsHostStats, from sage_workspace_create on
   unsigned ticket_epoch = 0;
-  int cached_N = -1;
+  // the one-edge work list `work` / `edge_first` / `edge_tiles` hold (ws_bind_work)
+  WorkKind list_kind = WorkKind::none;
+  int list_N = 0;
   int n_work = 0;
   int tiles_per_block = 1;
-  // tracker wiring (sage_track_frame): one evaluation = several operator launches that leave their statistics on the
-  // device (defer_fetch: no D2H + stream synchronise per operator; stats_ptr: where this operator's {error, inliers} go),
-  // then ONE copy of everything into pinned memory and one synchronise.  Buffers persist across frames.
-  bool defer_fetch = false;
-  float *stats_ptr = nullptr;
-  DevBuf trk_dpts, trk_kp_dpts;      // dof 7: depths scaled for the evaluation
-  float *trk_host = nullptr;         // pinned: [pose 12 | pad 4 | photo AtA 49 Atb 7 | keypoint AtA 49 Atb 7 | stats 2 + 2]
+  // tracker wiring (sage_track_frame): one evaluation = several operator launches that write their results into trk_host,
+  // then one ticket.  Buffers persist across frames.
+  DevBuf trk_dpts, trk_kp_dpts; // dof 7: depths scaled for the evaluation
+  PinnedBuf trk_host;           // TrackHost, from the first tracked frame on
   // overlap statistics (sage_track_overlap, overlap.hip): per-workgroup partials + survivor counters, the survivors of
   // both hull sets, and the pinned region the finish kernel publishes into; all grow with M and go with the workspace
   DevBuf ov_part, ov_surv;
-  void *ov_host = nullptr;           // pinned: [header | survivors of the input set [cap][2] | of the warped set [cap][2]]
-  size_t ov_host_cap = 0;            // points per set the pinned region holds
+  PinnedBuf ov_host; // [header | survivors of the input set [M][2] | of the warped set [M][2]]
+
+  WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
+  TrackHost *trk() const { return trk_host.as<TrackHost>(); }
 };
 
-// where an operator's kernels put {error, inliers}: the tracker's evaluation buffer, or the workspace's pinned mirror (the
-// kernels write it over PCIe themselves: no device-to-host copy afterwards)
-static inline float *ws_stats(SageWorkspace *ws) { return ws->stats_ptr ? ws->stats_ptr : ws->host_stats; }
+// operators.hip
 // enqueue a one-lane kernel that posts a ticket behind everything in the workspace's stream and spin until it shows up
-// (instead of a blocking hipStreamSynchronize: operators.hip)
+// (instead of a blocking hipStreamSynchronize)
 int ws_ticket_wait(SageWorkspace *ws);
-
+// the tracker's operators, enqueued only: they validate, reserve and launch; the kernels write {error, inliers} to `stats`
+// and nobody waits.  The public entry points are these with the workspace's own stats slot, then a ticket wait
+int track_photo_enqueue(SageWorkspace *ws, bool jac, int dof, float *AtA, float *Atb, float *stats, const float *R,
+                        const float *t, const float *mask1, const float *dpts0, const float *homo, const float *feat0s,
+                        const float *feat1, const float *grad1, const SagePyramid *pyr, float scale0, float eps,
+                        const float *weights_dev, int N, int FS);
+int track_reproj_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, float *stats, const float *R, const float *t,
+                         const float *sampled_dpts0, const float *homo, const float *matched_2d, const SageCamera *cam,
+                         float eps, float loss_param, float weight, int N);
+int track_match_geom_enqueue(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *stats, const float *R,
+                             const float *t, const float *sampled_dpts0, const float *matched_dpts1, const float *homo0,
+                             const float *matched_homo1, float scale0, float loss_param, float weight, int N);
 
 // instantiated (CS, FS) combinations of the factor kernels
 static inline bool supported(int CS, int FS)

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "block_solver.h"
+#include "device_buffers.h"
 #include "damped_system.h"
 #include "host_math.h"
 #include "sage_device.h"
@@ -253,10 +254,10 @@ __global__ __launch_bounds__(1024) void solve_retract_kernel(const double *__res
 struct DeviceSolver
 {
   int K = 0, B = 0, Bs = 0, Bp = 0, nblk = 0, nlinks = 0, VS = 0;
-  void *d_int = nullptr;    // all int tables in one allocation
-  void *d_hold = nullptr;   // [K] masks of held variables (solver_set_holds), or null
-  void *h_pinned = nullptr; // [SolveResult | K*VS floats | K*B doubles]
-  void *h_T = nullptr;      // pinned, one allocation: block storage, then the right-hand side, then the tickets
+  sage_rt::DevBuf d_int;       // all int tables in one allocation
+  sage_rt::DevBuf d_hold;      // [K] masks of held variables (solver_set_holds), or empty
+  sage_rt::PinnedBuf h_pinned; // [SolveResult | K*VS floats | K*B doubles]
+  sage_rt::PinnedBuf h_T;      // one allocation: block storage, then the right-hand side, then the tickets
   double *h_y = nullptr;
   unsigned *h_flags = nullptr; // a ticket (the epoch of the solve that wrote it) per block
   unsigned epoch = 0, go_epoch = 0;
@@ -266,23 +267,10 @@ struct DeviceSolver
   BlockPlan host_plan;              // elimination order and block storage (what the host factorisation reads)
   std::vector<uint8_t> h_fill;      // per block: structural fill-in (not delivered by the scatter kernel: BlockEnvelope::fill)
 
-  DeviceSolver() = default;
-  DeviceSolver(const DeviceSolver &) = delete;
-  DeviceSolver &operator=(const DeviceSolver &) = delete;
-  ~DeviceSolver()
-  {
-    if (d_int)
-      (void)hipFree(d_int);
-    if (d_hold)
-      (void)hipFree(d_hold);
-    if (h_pinned)
-      (void)hipHostFree(h_pinned);
-    if (h_T)
-      (void)hipHostFree(h_T);
-  }
-  SolveResult *result() const { return reinterpret_cast<SolveResult *>(h_pinned); }
-  float *host_vars() const { return reinterpret_cast<float *>(reinterpret_cast<char *>(h_pinned) + result_vars_offset()); }
-  double *host_delta() const { return reinterpret_cast<double *>(reinterpret_cast<char *>(h_pinned) + result_delta_offset(K, VS)); }
+  double *h_blocks() const { return h_T.as<double>(); }
+  SolveResult *result() const { return h_pinned.as<SolveResult>(); }
+  float *host_vars() const { return reinterpret_cast<float *>(h_pinned.as<char>() + result_vars_offset()); }
+  double *host_delta() const { return reinterpret_cast<double *>(h_pinned.as<char>() + result_delta_offset(K, VS)); }
 };
 
 int solver_create(DeviceSolver **out, int K, const plan::SolverRows &rows, int VS,
@@ -339,25 +327,24 @@ int solver_create(DeviceSolver **out, int K, const plan::SolverRows &rows, int V
       push_row(i);
   const size_t o_ord = put(order);
   const size_t o_tb = put(rows.to_block), o_ts = put(rows.to_solver);
-  if (hipMalloc(&S->d_int, all.size() * sizeof(int32_t)) != hipSuccess)
+  if (S->d_int.reserve(all.size() * sizeof(int32_t)))
     return (int)hipErrorOutOfMemory;
-  if (hipMemcpyAsync(S->d_int, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess)
+  if (hipMemcpyAsync(S->d_int.p, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess)
     return (int)hipErrorUnknown;
   if (hipStreamSynchronize(stream) != hipSuccess)
     return (int)hipErrorUnknown;
   const size_t ty_doubles = (size_t)nblk * Bp * Bp + (size_t)K * Bp;
-  if (hipHostMalloc(&S->h_T, ty_doubles * sizeof(double) + (size_t)nblk * sizeof(unsigned), hipHostMallocDefault) !=
-      hipSuccess)
+  if (S->h_T.reserve(ty_doubles * sizeof(double) + (size_t)nblk * sizeof(unsigned)))
     return (int)hipErrorOutOfMemory;
-  S->h_y = reinterpret_cast<double *>(S->h_T) + (size_t)nblk * Bp * Bp;
-  S->h_flags = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(S->h_T) + ty_doubles);
+  S->h_y = S->h_blocks() + (size_t)nblk * Bp * Bp;
+  S->h_flags = reinterpret_cast<unsigned *>(S->h_blocks() + ty_doubles);
   std::memset(S->h_flags, 0, (size_t)nblk * sizeof(unsigned));
   S->h_X.assign((size_t)K * Bp * Bp, 0.0);
   const size_t h_bytes = result_delta_offset(K, VS) + (size_t)K * B * sizeof(double);
-  if (hipHostMalloc(&S->h_pinned, h_bytes, hipHostMallocDefault) != hipSuccess)
+  if (S->h_pinned.reserve(h_bytes))
     return (int)hipErrorOutOfMemory;
-  std::memset(S->h_pinned, 0, h_bytes);
-  const int32_t *base = reinterpret_cast<const int32_t *>(S->d_int);
+  std::memset(S->h_pinned.p, 0, h_bytes);
+  const int32_t *base = S->d_int.as<int32_t>();
   SolvePlan &P = S->plan;
   P.K = K; P.B = B; P.Bs = Bs; P.Bp = Bp; P.nblk = nblk; P.nlinks = (int)links.size();
   P.row_first = base + o_rf; P.row_off = base + o_ro;
@@ -380,12 +367,12 @@ int solver_set_holds(DeviceSolver *S, const std::vector<uint8_t> &hold, hipStrea
   if ((int)hold.size() != S->K)
     return SAGE_E_INVALID;
   const std::vector<int32_t> masks(hold.begin(), hold.end());
-  if (!S->d_hold && hipMalloc(&S->d_hold, masks.size() * sizeof(int32_t)) != hipSuccess)
+  if (S->d_hold.reserve(masks.size() * sizeof(int32_t)))
     return (int)hipErrorOutOfMemory;
-  if (hipMemcpyAsync(S->d_hold, masks.data(), masks.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
+  if (hipMemcpyAsync(S->d_hold.p, masks.data(), masks.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
     return (int)hipErrorUnknown;
-  S->plan.hold = reinterpret_cast<const int32_t *>(S->d_hold);
+  S->plan.hold = S->d_hold.as<int32_t>();
   return SAGE_OK;
 }
 
@@ -411,7 +398,7 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   if (S->epoch == 0) // wrapped: 0 is the "never written" value
     S->epoch = 1;
   hipLaunchKernelGGL(solve_scatter_kernel, dim3(std::min(kScatterWorkgroups, S->nblk)), dim3(256), 0, stream, S->plan,
-                     packed_dev, vars0, S->VS, CS, pri, damp, reinterpret_cast<double *>(S->h_T), S->h_y, S->d_order,
+                     packed_dev, vars0, S->VS, CS, pri, damp, S->h_blocks(), S->h_y, S->d_order,
                      S->h_flags, S->epoch);
   if ((eh = hipGetLastError()) != hipSuccess)
     return (int)eh;
@@ -438,7 +425,7 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   const auto t1 = std::chrono::steady_clock::now();
   env.ready = S->h_flags; env.epoch = S->epoch;
   env.fill = S->h_fill.data();
-  const int bad = block_chol_solve_tr(env, reinterpret_cast<double *>(S->h_T), S->h_X.data(), S->h_y);
+  const int bad = block_chol_solve_tr(env, S->h_blocks(), S->h_X.data(), S->h_y);
   const auto t2 = std::chrono::steady_clock::now();
   if (dbgt)
     fprintf(stderr, "[sage hybrid solve] wait for the system + host cholesky %.3f ms\n",

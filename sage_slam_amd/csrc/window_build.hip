@@ -546,7 +546,9 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
   SAGE_HIP(hipMemsetAsync(w->errbuf.p, 0, 4 * sizeof(double), w->stream));
   if (!w->mirror.h)
   {
-    SAGE_HIP(hipHostMalloc(reinterpret_cast<void **>(&w->mirror.h), TotalsMirror::kDoubles * sizeof(double), hipHostMallocDefault));
+    if ((rc = w->mirror.mem.reserve(TotalsMirror::kDoubles * sizeof(double))))
+      return rc;
+    w->mirror.h = w->mirror.mem.as<double>();
     std::memset(w->mirror.h, 0, TotalsMirror::kDoubles * sizeof(double));
   }
   w->host_packed.assign(sage_window_packed_count(w), 0.0);

@@ -128,17 +128,10 @@ struct TotalsMirror
   // slot groups of h[kDoubles]: the linearize tail {err_photo, err_geo, n_photo, n_geo}, the error pass's totals (same
   // order), the tickets of error_totals_kernel, the tickets of mirror_totals_kernel
   enum : int { kTail = 0, kError = 4, kErrorTickets = 8, kMirrorTickets = 12, kDoubles = 16 };
-  double *h = nullptr;       // hipHostMalloc'd by finalize, freed here
+  PinnedBuf mem;             // allocated and zeroed by finalize
+  double *h = nullptr;       // = mem, once it is there
   uint64_t err_epoch = 0;    // ticket value of the last error pass
   uint64_t mirror_epoch = 0; // ticket value of the last mirror_totals_kernel
-  TotalsMirror() = default;
-  TotalsMirror(const TotalsMirror &) = delete;
-  TotalsMirror &operator=(const TotalsMirror &) = delete;
-  ~TotalsMirror()
-  {
-    if (h)
-      (void)hipHostFree(h);
-  }
   // spin until the four tickets of `ticket_group` (kErrorTickets / kMirrorTickets) show `epoch`: what their kernel wrote before
   // them is in h then, and everything enqueued ahead of that kernel has landed.  Instead of a stream synchronise: a host
   // thread blocked there for more than a few dozen microseconds wakes up through an interrupt, 20-30 us after the kernel
@@ -152,17 +145,7 @@ struct TotalsMirror
       __atomic_load(t + i, &v, __ATOMIC_ACQUIRE); // (a plain load on x86; the device is the writer)
       return v;
     };
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (!(ticket(0) == want && ticket(1) == want && ticket(2) == want && ticket(3) == want))
-    {
-      __builtin_ia32_pause();
-      if ((++spins & 0x3ff) == 0 &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
-        return false;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return true;
+    return spin_until([&] { return ticket(0) == want && ticket(1) == want && ticket(2) == want && ticket(3) == want; });
   }
 };
 
