@@ -356,6 +356,48 @@ int sage_track_overlap(SageWorkspace *ws, const float *R, const float *t, const 
  * collinear boundary points not counted (0 when the area is 0).  SAGE_E_INVALID for a NULL `area`, n < 0, or NULL xy with n > 0. */
 int sage_convex_hull_area(const float *xy, int n, double *area, int *n_vertices);
 
+/* ---- the mapper's depth-scale correction: Mapper::CorrectDepthScale (mapper.cpp:237-309, every new keyframe) and the loop
+ *      detector's df::CorrectDepthScale (mapping_utils.h:797-865, every accepted global loop: its result is the query
+ *      scale of the loop-closure pose-scale graph); sage_median_f32 is the torch::median Mapper::InitOneFrame normalises
+ *      the first keyframe by (mapper.cpp:181-185) ----
+ * Over all M valid pixels of keyframe 0 (the reference keyframe), per point i, in fp32 like the reference:
+ *   X = d_i * (R10 * h_i) + t10,  pos = X.z > eps,  x = X.x / X.z * fx + cx, y likewise
+ *   grid coordinate gx = (x + 0.5) * (2 / w) - 1, un-normalised by grid_sample (align_corners = false): ix = ((gx + 1) * W - 1) / 2
+ *   D1 = bilinear tap of bias1 at (ix, iy), zeros outside, taps summed nw, ne, sw, se (an in-bounds NaN texel gives NaN
+ *        whatever its weight);  m = nearest tap of the mask at (nearbyint(ix), nearbyint(iy)), half to even, 0 outside
+ *   valid = m * pos,  selected = valid > 0.5,  ratio_i = (X.z * valid) / D1   (inf for D1 == 0 is a value and sorts last)
+ * ratio = the LOWER median (element (n_used - 1) / 2 of the sorted values) of the selected ratios, found by an exact radix
+ * selection on the device: no sort, nothing of size M crosses PCIe.  Two calls on the same inputs return identical bytes. */
+typedef struct SageDepthScaleStats
+{
+  float ratio;          /* the reference's return value; NaN when n_used == 0, and when !drop_nan and n_nan > 0 */
+  int32_t n_points;     /* M */
+  int32_t n_pos_depth;  /* |X.z > eps| */
+  int32_t n_selected;   /* |valid > 0.5| */
+  int32_t n_nan;        /* NaN ratios among the selected */
+  int32_t n_used;       /* values the median ran over: n_selected, minus n_nan when drop_nan */
+} SageDepthScaleStats;
+/* R10, t10: HOST (row-major).
+ * dpt0_dev: keyframe 0's depth map [h*w], read at loc1d0_dev [M] (int64, the reference's valid_locations_1d; a location
+ *           outside the map reads NaN: the point is not selected), or, with loc1d0_dev == NULL, the M depths already gathered.
+ * homo0_dev [M,3]; bias1_dev [h,w]: dpt_map_bias of the keyframe to scale (the BIAS, not its depth map: mapper.cpp:286);
+ * mask_dev [h,w]; cam: level 0.
+ * drop_nan = 0: Mapper::CorrectDepthScale (a NaN among the selected ratios makes the result NaN, as torch::median does).
+ * drop_nan = 1: df::CorrectDepthScale of the loop detector (NaN ratios are removed first, mapping_utils.h:857).
+ * ratios_out_dev [M] float, selected_out_dev [M] int32: optional device outputs, the per-point ratio and whether it was selected.
+ * SAGE_E_INVALID (nothing is launched) for a NULL required pointer, M <= 0, fx / fy not finite or not positive, w / h < 1.
+ * n_used == 0 (e.g. everything behind the camera) is no error: ratio = NaN, SAGE_OK.  One wait on the workspace's ticket. */
+int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const float *t10, const float *dpt0_dev,
+                           const int64_t *loc1d0_dev, const float *homo0_dev, int M, const SageCamera *cam,
+                           const float *bias1_dev, const float *mask_dev, float eps, int drop_nan,
+                           float *ratios_out_dev, int32_t *selected_out_dev, SageDepthScaleStats *out);
+/* torch::median of n device floats (values_dev[loc1d_dev[i]] when loc1d_dev != NULL: mapper.cpp:182): the LOWER median,
+ * element (n_used - 1) / 2 of the sorted values (-0 before +0); NaN when a NaN is present and !drop_nan, and when
+ * n_used == 0.  Every location must lie inside values_dev (it is not checked).  n_used_host, n_nan_host: optional.  SAGE_E_INVALID (nothing is launched) for a NULL ws, values_dev or
+ * median_host, and n <= 0. */
+int sage_median_f32(SageWorkspace *ws, const float *values_dev, const int64_t *loc1d_dev, int n, int drop_nan,
+                    float *median_host, int *n_used_host, int *n_nan_host);
+
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)
  * ===================================================================== */

@@ -135,7 +135,7 @@ SYMBOLS = [
     "sage_tracker_photo_jac_error_calculate", "sage_tracker_photo_error_calculate",
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
-    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame", "sage_track_overlap", "sage_convex_hull_area",
+    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame", "sage_track_overlap", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
     "sage_window_block_size", "sage_window_solver_block_size", "sage_window_packed_count", "sage_window_packed_dev",
@@ -389,6 +389,69 @@ def convex_hull_area(xy):
     area = C.c_double(); nv = C.c_int()
     _chk(lib().sage_convex_hull_area(_fp(p), int(p.shape[0]), C.byref(area), C.byref(nv)), "sage_convex_hull_area")
     return area.value, nv.value
+
+
+class SageDepthScaleStats(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("n_points", C.c_int32), ("n_pos_depth", C.c_int32), ("n_selected", C.c_int32),
+                ("n_nan", C.c_int32), ("n_used", C.c_int32)]
+
+
+def depth_scale_ratio_raw(ws_handle, R10, t10, dpt0_ptr, loc_ptr, homo_ptr, M, cam_ptr, bias1_ptr, mask_ptr, eps, drop_nan,
+                          ratios_ptr, selected_ptr, out_ptr) -> int:
+    """``sage_depth_scale_ratio`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_depth_scale_ratio
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, R10, t10, dpt0_ptr, loc_ptr, homo_ptr, int(M), cam_ptr, bias1_ptr, mask_ptr, eps, int(drop_nan),
+                 ratios_ptr, selected_ptr, out_ptr))
+
+
+def depth_scale_ratio(ws: "Workspace", R10, t10, dpt0, homo0, cam, bias1, mask, eps, drop_nan: bool = False, loc1d0=None,
+                      per_point: bool = False):
+    """``Mapper::CorrectDepthScale`` (``drop_nan`` False) / the loop detector's ``df::CorrectDepthScale`` (True) through
+    ``sage_depth_scale_ratio``.  R10 [3,3], t10 [3]: host arrays; homo0 [M,3], bias1 [h,w], mask [h,w]: contiguous float32
+    cuda tensors; dpt0: keyframe 0's depth map [h,w] with ``loc1d0`` [M] (int64 cuda tensor), or the M gathered depths
+    without.  -> ``SageDepthScaleStats``, or with ``per_point`` (stats, ratios [M] float32, selected [M] int32) -- the last
+    two cuda tensors."""
+    import torch
+    Rh = _f32(R10).reshape(9); th = _f32(t10).reshape(3)
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    M = int(homo0.shape[0])
+    hw = (int(c.h), int(c.w))
+    assert tuple(mask.shape) == hw and tuple(bias1.shape) == hw
+    if loc1d0 is None:
+        assert dpt0.numel() == M
+    else:
+        assert loc1d0.dtype == torch.int64 and loc1d0.numel() == M and dpt0.numel() == hw[0] * hw[1]
+    ratios = torch.empty(M, dtype=torch.float32, device=homo0.device) if per_point else None
+    selected = torch.empty(M, dtype=torch.int32, device=homo0.device) if per_point else None
+    out = SageDepthScaleStats()
+    _chk(depth_scale_ratio_raw(ws.h, Rh.ctypes.data, th.ctypes.data, dptr(dpt0), dptr(loc1d0), dptr(homo0), M, C.addressof(c),
+                               dptr(bias1), dptr(mask), float(eps), int(bool(drop_nan)), dptr(ratios), dptr(selected),
+                               C.addressof(out)), "sage_depth_scale_ratio")
+    return (out, ratios, selected) if per_point else out
+
+
+def median_f32_raw(ws_handle, values_ptr, loc_ptr, n, drop_nan, median_ptr, n_used_ptr, n_nan_ptr) -> int:
+    """``sage_median_f32`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_median_f32
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, values_ptr, loc_ptr, int(n), int(drop_nan), median_ptr, n_used_ptr, n_nan_ptr))
+
+
+def median_f32(ws: "Workspace", values, loc1d=None, drop_nan: bool = False):
+    """``torch::median`` (the lower median) of a contiguous float32 cuda tensor, or of ``values[loc1d]`` (int64 cuda tensor),
+    through ``sage_median_f32`` -> (median as np.float32, n_used, n_nan)"""
+    import torch
+    assert values.dtype == torch.float32
+    n = int(values.numel())
+    if loc1d is not None:
+        assert loc1d.dtype == torch.int64
+        n = int(loc1d.numel())
+    med = C.c_float(); n_used = C.c_int(); n_nan = C.c_int()
+    _chk(median_f32_raw(ws.h, dptr(values), dptr(loc1d), n, int(bool(drop_nan)), C.addressof(med), C.addressof(n_used),
+                        C.addressof(n_nan)), "sage_median_f32")
+    return np.float32(med.value), n_used.value, n_nan.value
 
 
 class Workspace:

@@ -3,6 +3,8 @@
 //                       enqueue function per family + the public wrappers that wait; the producer entry points
 //   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame): one evaluation over the enqueue functions
 //   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
+//   depth_scale.hip     the mapper's depth-scale correction and device medians (sage_depth_scale_ratio, sage_median_f32):
+//                       the per-point kernel and the exact radix selection
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
 //   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
@@ -192,6 +194,11 @@ struct SageWorkspace
   // both hull sets, and the pinned region the finish kernel publishes into; all grow with M and go with the workspace
   DevBuf ov_part, ov_surv;
   PinnedBuf ov_host; // [header | survivors of the input set [M][2] | of the warped set [M][2]]
+  // exact selection (sage_depth_scale_ratio, sage_median_f32: depth_scale.hip): the keys [M] (grow with M), the histograms,
+  // counts and hand-over state of the passes, and the pinned record the finish kernel publishes
+  DevBuf sel_keys, sel_scratch;
+  PinnedBuf sel_host;
+  bool sel_scratch_zero = false; // the last call's finish kernel has run: the scratch is zero again
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }

@@ -485,3 +485,56 @@ def make_overlap_problem(H: int, W: int, rot=(0.0, 0.0, 0.0), trans=(0.0, 0.0, 0
     homo = np.stack([(vx.astype(F32) - cam.cx) / cam.fx, (vy.astype(F32) - cam.cy) / cam.fy, np.ones(vx.size, F32)], 1).astype(F32)
     return dict(cam=cam, mask=mask, dpts0=dpts0, homo=homo, R=so3_exp(np.asarray(rot, np.float64)).astype(F32),
                 t=np.asarray(trans, F32), eps=F32(1e-4), M=int(vx.size))
+
+
+# --------------------------------------------------------------------------- the mapper's depth-scale correction
+DEPTH_SCALE_VARIANTS = ("plain", "zero_patch", "nan_texel")
+
+
+def make_depth_scale_problem(H: int, W: int, pose="small", seed: int = 0, true_scale: float = 1.7, variant: str = "plain") -> dict:
+    """Inputs of ``sage_depth_scale_ratio`` (``Mapper::CorrectDepthScale``) with a known answer.  Keyframe 0 is the scene of
+    ``make_overlap_problem`` (valid set, depths, homo, elliptical mask, camera); ``pose`` is a name of ``OVERLAP_POSES`` or a
+    (rotation vector, translation) pair.  Keyframe 1's ``bias1`` is the depth of that scene seen from pose 1, divided by
+    ``true_scale``: keyframe 0's points are warped in fp64, their depths splatted into the pixel they land in (the nearest
+    one wins a shared pixel), and the pixels no point reached are filled from their filled 3x3 neighbours' mean, ring by
+    ring -- a depth map as good as the scene's sampling allows, so the median ratio is ``true_scale`` up to that
+    interpolation error.  Without a point in front of the camera (``behind``) ``bias1`` is 1 everywhere.
+    ``variant``: "zero_patch" zeroes a 6x6 patch of ``bias1`` at the image centre (ratios of +inf), "nan_texel" plants one
+    NaN next to it (NaN ratios among the selected).
+    -> the overlap problem's dict + dpt0_map [H,W] (keyframe 0's depth map, 0 outside the valid set), loc1d0 [M] int64,
+    bias1 [H,W], true_scale, variant.  Deterministic per ``seed``."""
+    assert variant in DEPTH_SCALE_VARIANTS
+    rot, trans = OVERLAP_POSES[pose] if isinstance(pose, str) else pose
+    prob = make_overlap_problem(H, W, rot, trans, seed)
+    cam = prob["cam"]
+    vy, vx = np.nonzero(prob["mask"] > 0.5)
+    loc1d0 = (vy * W + vx).astype(np.int64)
+    dpt0_map = np.zeros((H, W), F32)
+    dpt0_map.reshape(-1)[loc1d0] = prob["dpts0"]
+    X = prob["dpts0"].astype(np.float64)[:, None] * (prob["homo"].astype(np.float64) @ prob["R"].astype(np.float64).T) \
+        + prob["t"].astype(np.float64)
+    front = X[:, 2] > 1e-3
+    depth = np.full((H, W), np.inf)
+    px = np.rint(X[front, 0] / X[front, 2] * float(cam.fx) + float(cam.cx)).astype(np.int64)
+    py = np.rint(X[front, 1] / X[front, 2] * float(cam.fy) + float(cam.cy)).astype(np.int64)
+    inside = (px >= 0) & (px < W) & (py >= 0) & (py < H)
+    np.minimum.at(depth, (py[inside], px[inside]), X[front, 2][inside])
+    filled = np.isfinite(depth)
+    if not filled.any():
+        depth[:], filled[:] = 1.0, True
+    for _ in range(H + W):                      # every ring fills the holes next to a filled pixel
+        if filled.all():
+            break
+        d, f = np.pad(np.where(filled, depth, 0.0), 1), np.pad(filled, 1).astype(np.float64)
+        s = sum(d[1 + a:1 + a + H, 1 + b:1 + b + W] for a in (-1, 0, 1) for b in (-1, 0, 1))
+        n = sum(f[1 + a:1 + a + H, 1 + b:1 + b + W] for a in (-1, 0, 1) for b in (-1, 0, 1))
+        new = ~filled & (n > 0)
+        depth[new] = s[new] / n[new]
+        filled |= new
+    bias1 = (depth / float(true_scale)).astype(F32)
+    cy, cx = H // 2, W // 2
+    if variant == "zero_patch":
+        bias1[cy - 3:cy + 3, cx - 3:cx + 3] = 0.0
+    elif variant == "nan_texel":
+        bias1[cy, cx + 5] = np.nan
+    return dict(prob, dpt0_map=dpt0_map, loc1d0=loc1d0, bias1=bias1, true_scale=float(true_scale), variant=variant)
