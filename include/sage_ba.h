@@ -398,6 +398,98 @@ int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const float *t10
 int sage_median_f32(SageWorkspace *ws, const float *values_dev, const int64_t *loc1d_dev, int n, int drop_nan,
                     float *median_host, int *n_used_host, int *n_nan_host);
 
+/* ---- the loop detector's bag of words: LoopDetector::AddKeyframe (core/system/loop_detector.cpp:20-42) turns the
+ *      descriptors of all valid pixels of a new keyframe into a DBoW2 bag-of-words vector, DetectLoop (:53-111) scores it
+ *      against the temporal neighbours and queries the database with it ----
+ * Vocabulary (TemplatedTensorVocabulary::load, core/system/tensor_vocabulary.cpp:49-128): node 0 is the root; every other
+ * node has a parent, a C-float descriptor and a double weight; a node without children is a leaf and carries a word id.
+ * Transform of M points (transform / subset_transform, tensor_vocabulary.cpp:131-245): every point starts at the root; at a
+ * node with children c_0..c_{n-1} it goes to argmin_j d_j, d_j = sum_ch (F[ch,i] - desc[c_j][ch])^2 in fp32 (the
+ * difference form), the first smallest wins, a NaN distance counts as smallest and the first NaN wins (torch.argmin), until
+ * it stands on a leaf.  Every leaf reached by at least one point, with weight > 0, contributes exactly once
+ * v[word] = weight * M -- M the number of ALL points, not of those on the leaf (:204-208 multiplies by features.size(1));
+ * a leaf with weight <= 0 contributes nothing.  The vector is then L1-normalised in double the way BowVector::normalize
+ * does (thirdparty/DBoW2/src/BowVector.cpp:79-101): |v| summed in ascending word order, then every entry divided.  The
+ * values are a function of the SET of leaves reached alone.
+ * Score (L1Scoring::score, DBoW2/src/ScoringObject.cpp:23-68): over the words both vectors hold, in ascending word order,
+ * s += |v - w| - |v| - |w|; the score is -s / 2.
+ * Database (TemplatedDatabase::add, queryL1, DBoW2/include/DBoW2/TemplatedDatabase.h:604-675): entries get zero-based ids
+ * in the order they are added; a query accumulates the same three-term value per entry over the query's words in
+ * ascending order, skips entries with id >= max_id unless max_id == -1, sorts ascending by the accumulated value, cuts to
+ * max_results when max_results > 0 and turns every kept value into -value / 2; entries that share no word with the query do
+ * not appear.  The reference's std::sort leaves the order of tied values open: HERE TIES GO BY ASCENDING ENTRY ID.
+ * Only L1 scoring is implemented (what the shipped vocabulary uses); the TF and TF_IDF weightings give the same transform,
+ * the weights live in the nodes. */
+#define SAGE_BOW_L1 0 /* DBoW2::ScoringType, in its order */
+#define SAGE_BOW_L2 1
+#define SAGE_BOW_CHI_SQUARE 2
+#define SAGE_BOW_KL 3
+#define SAGE_BOW_BHATTACHARYYA 4
+#define SAGE_BOW_DOT_PRODUCT 5
+typedef struct SageVocabulary SageVocabulary;   /* immutable after creation: any number of workspaces and host threads may share one */
+typedef struct SageBowDatabase SageBowDatabase; /* host only */
+typedef struct SageVocabularyDesc /* HOST arrays */
+{
+  int32_t n_nodes;          /* the root counts */
+  int32_t C;                /* floats per descriptor */
+  const int32_t *parent;    /* [n_nodes]; parent[0] = -1 */
+  const float *descriptors; /* [n_nodes * C]; the root's row is ignored */
+  const double *weight;     /* [n_nodes] */
+  const int32_t *word_id;   /* [n_nodes]; -1 for an inner node */
+  int32_t scoring;          /* SAGE_BOW_* */
+} SageVocabularyDesc;
+/* A node's children are ordered by ascending node index (the order a DBoW2-built file lists them in).  SAGE_E_INVALID,
+ * without touching the device, unless 0 <= parent[i] < i for every i > 0, a node has a word id exactly when it has no
+ * children, the word ids are a permutation of 0..n_words-1 and there is at least one word below the root; also for a NULL
+ * pointer, C < 1 and a scoring that is no SAGE_BOW_* value.  SAGE_E_UNSUPPORTED for C > 64, a node with more than 64
+ * children, a leaf deeper than 8, more than 2^20 words, a scoring other than SAGE_BOW_L1.  Ragged trees are legal: any
+ * number of children per node, leaves at different depths (DBoW2's k-means makes them).  The device copy (nodes renumbered
+ * breadth-first, descriptor rows padded to 4 floats) lives on the device that is current at creation. */
+int sage_vocabulary_create(const SageVocabularyDesc *desc, SageVocabulary **out);
+void sage_vocabulary_destroy(SageVocabulary *voc);
+int sage_vocabulary_num_nodes(const SageVocabulary *voc);    /* these six: -1 for a NULL vocabulary */
+int sage_vocabulary_num_words(const SageVocabulary *voc);
+int sage_vocabulary_channels(const SageVocabulary *voc);
+int sage_vocabulary_depth(const SageVocabulary *voc);        /* of the deepest leaf; the root is at depth 0 */
+int sage_vocabulary_max_fanout(const SageVocabulary *voc);
+int sage_vocabulary_staged_nodes(const SageVocabulary *voc); /* nodes of the whole top levels the walk keeps in LDS */
+typedef struct SageBowStats
+{
+  int32_t n_points;          /* M */
+  int32_t n_words;           /* entries written to word_ids_host / values_host */
+  int32_t n_leaves_hit;      /* leaves reached by at least one point */
+  int32_t n_zero_weight;     /* ... of them left out for a weight <= 0 */
+  int32_t n_inner_nodes_hit; /* inner nodes at least one point passed, the root among them: the reference evaluates one
+                                index / subtract / sum / argmin sequence for each */
+} SageBowStats;
+/* The bag-of-words vector of M points.  desc_dev [C, P] channel-major (feat_desc reshaped to {C, -1}), read at
+ * loc1d_dev [M] (int64, the reference's valid_locations_1d) -- or, with loc1d_dev == NULL, desc_dev is [C, M] with P == M:
+ * the descriptors already gathered.  THE LOCATIONS ARE NOT RANGE-CHECKED: every one must lie in [0, P).
+ * word_ids_host / values_host [capacity]: the vector, ascending word ids, values L1-normalised (they sum to 1; nothing is
+ * written when every leaf reached has weight <= 0: n_words = 0, SAGE_OK).  word_of_point_out_dev [M] int32: optional, the
+ * word every point reached.  SAGE_E_INVALID (nothing is launched) for a NULL required pointer, M <= 0, P < 1, P != M without
+ * locations, capacity < min(M, n_words of the vocabulary).  One kernel walks the tree (its top levels in LDS), one compacts
+ * the words reached into pinned memory: one wait on the workspace's ticket, no blocking copy, nothing of size M crosses
+ * PCIe.  Two calls on the same inputs return identical bytes. */
+int sage_bow_transform(SageWorkspace *ws, const SageVocabulary *voc, const float *desc_dev, const int64_t *loc1d_dev, int M,
+                       int P, int32_t *word_ids_host, double *values_host, int capacity, int32_t *word_of_point_out_dev,
+                       SageBowStats *out);
+/* L1 score of two vectors (strictly ascending word ids; values finite).  SAGE_E_INVALID otherwise, and for a NULL score or a
+ * NULL array with n > 0.  Host only. */
+int sage_bow_score(const int32_t *ids1, const double *vals1, int n1, const int32_t *ids2, const double *vals2, int n2,
+                   double *score);
+/* The database: an inverted file, one row per word.  add and query may be called from several threads (one mutex). */
+int sage_bow_db_create(int n_words, SageBowDatabase **out);
+void sage_bow_db_destroy(SageBowDatabase *db);
+/* -> the new entry's id (>= 0), or SAGE_E_INVALID: ids not strictly ascending or outside [0, n_words), a value that is
+ * not finite.  n == 0 adds an entry without words, as the reference does for an empty vector. */
+int sage_bow_db_add(SageBowDatabase *db, const int32_t *ids, const double *vals, int n);
+int sage_bow_db_size(const SageBowDatabase *db); /* entries; -1 for NULL */
+/* entry_ids / scores [capacity]: best first; *n_out: how many there are.  More results than capacity: SAGE_E_INVALID,
+ * *n_out tells how many, nothing else is written.  An empty database or an empty query: *n_out = 0, SAGE_OK. */
+int sage_bow_db_query(const SageBowDatabase *db, const int32_t *ids, const double *vals, int n, int max_results, int max_id,
+                      int32_t *entry_ids, double *scores, int capacity, int *n_out);
+
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)
  * ===================================================================== */

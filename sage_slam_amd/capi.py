@@ -136,6 +136,8 @@ SYMBOLS = [
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
     "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame", "sage_track_overlap", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
+    "sage_vocabulary_create", "sage_vocabulary_destroy", "sage_vocabulary_num_nodes", "sage_vocabulary_num_words", "sage_vocabulary_channels", "sage_vocabulary_depth", "sage_vocabulary_max_fanout", "sage_vocabulary_staged_nodes",
+    "sage_bow_transform", "sage_bow_score", "sage_bow_db_create", "sage_bow_db_destroy", "sage_bow_db_add", "sage_bow_db_size", "sage_bow_db_query",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
     "sage_window_block_size", "sage_window_solver_block_size", "sage_window_packed_count", "sage_window_packed_dev",
@@ -465,6 +467,173 @@ class Workspace:
     def close(self):
         if self.h:
             lib().sage_workspace_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------- the loop detector's bag of words
+SAGE_BOW_L1, SAGE_BOW_L2, SAGE_BOW_CHI_SQUARE, SAGE_BOW_KL, SAGE_BOW_BHATTACHARYYA, SAGE_BOW_DOT_PRODUCT = range(6)
+
+
+class SageVocabularyDesc(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("C", C.c_int32), ("parent", C.c_void_p), ("descriptors", C.c_void_p),
+                ("weight", C.c_void_p), ("word_id", C.c_void_p), ("scoring", C.c_int32)]
+
+
+class SageBowStats(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_points", "n_words", "n_leaves_hit", "n_zero_weight", "n_inner_nodes_hit")]
+
+
+def vocabulary_create_raw(parent, descriptors, weight, word_id, scoring=SAGE_BOW_L1):
+    """``sage_vocabulary_create`` on host arrays as given (parent [n] int32, descriptors [n, C] float32, weight [n] float64,
+    word_id [n] int32) -> (status code, handle)"""
+    parent = np.ascontiguousarray(parent, np.int32); word_id = np.ascontiguousarray(word_id, np.int32)
+    descriptors = np.ascontiguousarray(descriptors, np.float32); weight = np.ascontiguousarray(weight, np.float64)
+    n = int(parent.shape[0])
+    assert descriptors.ndim == 2 and descriptors.shape[0] == n and weight.shape == (n,) and word_id.shape == (n,)
+    d = SageVocabularyDesc(n, int(descriptors.shape[1]), parent.ctypes.data, descriptors.ctypes.data, weight.ctypes.data,
+                           word_id.ctypes.data, int(scoring))
+    h = C.c_void_p()
+    f = lib().sage_vocabulary_create
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    return int(f(C.addressof(d), C.addressof(h))), h
+
+
+class Vocabulary:
+    """``SageVocabulary``: the vocabulary tree on the device, immutable; ``voc`` is a dict with parent, descriptors, weight,
+    word_id (and optionally scoring) as ``vocabulary.load_opencv_yaml`` and ``synth.make_vocabulary`` return it."""
+
+    def __init__(self, voc: dict):
+        rc, self.h = vocabulary_create_raw(voc["parent"], voc["descriptors"], voc["weight"], voc["word_id"],
+                                           voc.get("scoring", SAGE_BOW_L1))
+        _chk(rc, "sage_vocabulary_create")
+        L = lib()
+        for name in ("num_nodes", "num_words", "channels", "depth", "max_fanout", "staged_nodes"):
+            fn = getattr(L, "sage_vocabulary_" + name)
+            fn.argtypes = [C.c_void_p]
+            setattr(self, name, int(fn(self.h)))
+
+    def close(self):
+        if self.h:
+            f = lib().sage_vocabulary_destroy
+            f.argtypes = [C.c_void_p]; f.restype = None
+            f(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bow_transform_raw(ws_handle, voc_handle, desc_ptr, loc_ptr, M, P, ids_ptr, vals_ptr, capacity, word_out_ptr, out_ptr) -> int:
+    """``sage_bow_transform`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_bow_transform
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                  C.c_void_p]
+    return int(f(ws_handle, voc_handle, desc_ptr, loc_ptr, int(M), int(P), ids_ptr, vals_ptr, int(capacity), word_out_ptr, out_ptr))
+
+
+def bow_transform(ws: "Workspace", voc: Vocabulary, desc, loc1d=None, per_point: bool = False):
+    """``TemplatedTensorVocabulary::transform`` of ``LoopDetector::AddKeyframe`` through ``sage_bow_transform``.  desc: a
+    contiguous float32 cuda tensor [C, P] (``feat_desc`` reshaped) read at ``loc1d`` [M] (int64 cuda tensor), or [C, M]
+    already gathered without.  -> (word ids int32 [n], values float64 [n], ``SageBowStats``) and, with ``per_point``, the
+    word of every point (int32 cuda tensor [M])."""
+    import torch
+    assert desc.dtype == torch.float32 and desc.dim() == 2 and int(desc.shape[0]) == voc.channels
+    P = int(desc.shape[1])
+    M = P if loc1d is None else int(loc1d.numel())
+    assert loc1d is None or loc1d.dtype == torch.int64
+    cap = min(M, voc.num_words)
+    ids = np.empty(cap, np.int32); vals = np.empty(cap, np.float64)
+    words = torch.empty(M, dtype=torch.int32, device=desc.device) if per_point else None
+    out = SageBowStats()
+    _chk(bow_transform_raw(ws.h, voc.h, dptr(desc), dptr(loc1d), M, P, ids.ctypes.data, vals.ctypes.data, cap, dptr(words),
+                           C.addressof(out)), "sage_bow_transform")
+    r = (ids[:out.n_words].copy(), vals[:out.n_words].copy(), out)
+    return r + (words,) if per_point else r
+
+
+def _bow_vec(ids, vals):
+    ids = np.ascontiguousarray(ids, np.int32); vals = np.ascontiguousarray(vals, np.float64)
+    assert ids.ndim == 1 and ids.shape == vals.shape
+    return ids, vals
+
+
+def bow_score_raw(ids1, vals1, ids2, vals2):
+    """``sage_bow_score`` -> (status code, score)"""
+    ids1, vals1 = _bow_vec(ids1, vals1); ids2, vals2 = _bow_vec(ids2, vals2)
+    f = lib().sage_bow_score
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    s = C.c_double(float("nan"))
+    rc = int(f(ids1.ctypes.data, vals1.ctypes.data, len(ids1), ids2.ctypes.data, vals2.ctypes.data, len(ids2), C.addressof(s)))
+    return rc, s.value
+
+
+def bow_score(ids1, vals1, ids2, vals2) -> float:
+    """``L1Scoring::score`` of two bag-of-words vectors (ascending word ids) through ``sage_bow_score``"""
+    rc, s = bow_score_raw(ids1, vals1, ids2, vals2)
+    _chk(rc, "sage_bow_score")
+    return s
+
+
+class BowDatabase:
+    """``SageBowDatabase``: DBoW2's inverted-file database with L1 scoring (host only)."""
+
+    def __init__(self, n_words: int):
+        self.h = C.c_void_p()
+        f = lib().sage_bow_db_create
+        f.argtypes = [C.c_int, C.c_void_p]
+        _chk(int(f(int(n_words), C.addressof(self.h))), "sage_bow_db_create")
+
+    def add_raw(self, ids, vals) -> int:
+        """-> the entry id, or a negative status code"""
+        ids, vals = _bow_vec(ids, vals)
+        f = lib().sage_bow_db_add
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        return int(f(self.h, ids.ctypes.data, vals.ctypes.data, len(ids)))
+
+    def add(self, ids, vals) -> int:
+        e = self.add_raw(ids, vals)
+        if e < 0:
+            raise SageError(e, "sage_bow_db_add")
+        return e
+
+    def __len__(self) -> int:
+        f = lib().sage_bow_db_size
+        f.argtypes = [C.c_void_p]
+        return int(f(self.h))
+
+    def query_raw(self, ids, vals, max_results: int = 0, max_id: int = -1, capacity: Optional[int] = None):
+        """-> (status code, entry ids int32 [n], scores float64 [n], n as the library reported it)"""
+        ids, vals = _bow_vec(ids, vals)
+        cap = len(self) if capacity is None else int(capacity)
+        entries = np.empty(max(cap, 1), np.int32); scores = np.empty(max(cap, 1), np.float64)
+        n = C.c_int(-1)
+        f = lib().sage_bow_db_query
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        rc = int(f(self.h, ids.ctypes.data, vals.ctypes.data, len(ids), int(max_results), int(max_id), entries.ctypes.data,
+                   scores.ctypes.data, cap, C.addressof(n)))
+        k = n.value if rc == 0 else 0
+        return rc, entries[:k].copy(), scores[:k].copy(), n.value
+
+    def query(self, ids, vals, max_results: int = 0, max_id: int = -1):
+        """``TemplatedDatabase::query`` -> (entry ids, scores), best first, ties by ascending entry id"""
+        rc, entries, scores, _ = self.query_raw(ids, vals, max_results, max_id)
+        _chk(rc, "sage_bow_db_query")
+        return entries, scores
+
+    def close(self):
+        if self.h:
+            f = lib().sage_bow_db_destroy
+            f.argtypes = [C.c_void_p]; f.restype = None
+            f(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

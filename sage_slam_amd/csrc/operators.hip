@@ -70,17 +70,27 @@ __global__ void ticket_kernel(volatile unsigned *ticket, unsigned epoch)
   *ticket = epoch;
 }
 
-int ws_ticket_wait(SageWorkspace *ws)
+unsigned ws_ticket_next(SageWorkspace *ws)
 {
-  volatile unsigned *ticket = &ws->hs()->ticket;
   if (++ws->ticket_epoch == 0)
     ws->ticket_epoch = 1;
-  const unsigned epoch = ws->ticket_epoch;
-  hipLaunchKernelGGL(ticket_kernel, dim3(1), dim3(1), 0, ws->stream, ticket, epoch);
-  SAGE_HIP(hipGetLastError());
+  return ws->ticket_epoch;
+}
+
+int ws_ticket_await(SageWorkspace *ws, unsigned epoch)
+{
+  volatile unsigned *ticket = &ws->hs()->ticket;
   if (!spin_until([=] { return *ticket == epoch; }))
     SAGE_HIP(hipStreamSynchronize(ws->stream)); // (a long queue ahead of this operator: wait the ordinary way)
   return SAGE_OK;
+}
+
+int ws_ticket_wait(SageWorkspace *ws)
+{
+  const unsigned epoch = ws_ticket_next(ws);
+  hipLaunchKernelGGL(ticket_kernel, dim3(1), dim3(1), 0, ws->stream, &ws->hs()->ticket, epoch);
+  SAGE_HIP(hipGetLastError());
+  return ws_ticket_await(ws, epoch);
 }
 
 // the public entry points' half of an operator: its kernels have been enqueued (rc) with the workspace's own stats slot as

@@ -5,6 +5,9 @@
 //   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
 //   depth_scale.hip     the mapper's depth-scale correction and device medians (sage_depth_scale_ratio, sage_median_f32):
 //                       the per-point kernel and the exact radix selection
+//   bow.hip             the loop detector's bag of words (sage_vocabulary_*, sage_bow_transform): the vocabulary's device
+//                       layout, the tree walk, the compaction of the words reached, the host finish
+//   bow_database.cpp    (no HIP) the L1 score of two bag-of-words vectors and the inverted-file database
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
 //   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
@@ -199,6 +202,11 @@ struct SageWorkspace
   DevBuf sel_keys, sel_scratch;
   PinnedBuf sel_host;
   bool sel_scratch_zero = false; // the last call's finish kernel has run: the scratch is zero again
+  // bag of words (sage_bow_transform, bow.hip): one flag per word of the vocabulary (rounded up to the compaction's tile),
+  // and the pinned record the compact kernel publishes: [count, pad x 3 | the word ids reached, ascending]
+  DevBuf bow_hit;
+  PinnedBuf bow_host;
+  bool bow_hit_zero = false; // the last call's compact kernel has run: every flag is zero again
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }
@@ -208,6 +216,10 @@ struct SageWorkspace
 // enqueue a one-lane kernel that posts a ticket behind everything in the workspace's stream and spin until it shows up
 // (instead of a blocking hipStreamSynchronize)
 int ws_ticket_wait(SageWorkspace *ws);
+// the two halves of it, for an operator whose last kernel posts the ticket itself (into hs()->ticket, behind a
+// __threadfence_system()): the epoch to post, and the spin until it shows up
+unsigned ws_ticket_next(SageWorkspace *ws);
+int ws_ticket_await(SageWorkspace *ws, unsigned epoch);
 // the tracker's operators, enqueued only: they validate, reserve and launch; the kernels write {error, inliers} to `stats`
 // and nobody waits.  The public entry points are these with the workspace's own stats slot, then a ticket wait
 int track_photo_enqueue(SageWorkspace *ws, bool jac, int dof, float *AtA, float *Atb, float *stats, const float *R,

@@ -538,3 +538,78 @@ def make_depth_scale_problem(H: int, W: int, pose="small", seed: int = 0, true_s
     elif variant == "nan_texel":
         bias1[cy, cx + 5] = np.nan
     return dict(prob, dpt0_map=dpt0_map, loc1d0=loc1d0, bias1=bias1, true_scale=float(true_scale), variant=variant)
+
+
+# --------------------------------------------------------------------------- the loop detector's bag of words
+BOW_KINDS = ("iid", "nodes", "constant", "nan")
+
+
+def make_vocabulary(k: int, L: int, C: int, seed: int = 0, ragged: bool = False) -> dict:
+    """A vocabulary tree in the arrays ``sage_vocabulary_create`` takes (what ``vocabulary.load_opencv_yaml`` returns).
+
+    Nodes are numbered the way DBoW2's hierarchical k-means numbers them -- a node's children get consecutive ids when the
+    node is split, before any of them is split itself -- so the numbering is NOT breadth-first below level 2.  A child's
+    descriptor is its parent's plus Gaussian noise of sigma 0.3 / 2^level (the root's row is zero), a leaf's weight is drawn
+    from [0.5, 3), an inner node's is 0 as in a DBoW2 file.
+    ``ragged`` False: every inner node has k children, every leaf is at depth L, word ids ascend with the node id.
+    ``ragged`` True: 1..k children per inner node, a node above depth L is a leaf with probability 0.3 (leaves at depths
+    1..L), about one leaf weight in five is 0, and the word ids are a random permutation.
+    -> dict(parent, descriptors [n, C], weight, word_id, k, L, scoring = 0 (L1), weighting = 0, n_nodes, n_words, C).
+    Deterministic per ``seed``."""
+    rng = np.random.default_rng(seed)
+    parent, level = [-1], [0]
+    desc = [np.zeros(C, np.float64)]
+    is_leaf = [False]
+
+    def split(node: int):
+        lvl = level[node] + 1
+        n = int(rng.integers(1, k + 1)) if ragged else k
+        kids = list(range(len(parent), len(parent) + n))
+        for _ in kids:
+            parent.append(node)
+            level.append(lvl)
+            desc.append(desc[node] + rng.normal(0.0, 0.3 / 2.0 ** (lvl - 1), C))
+            is_leaf.append(lvl >= L or (ragged and rng.random() < 0.3))
+        for c in kids:
+            if not is_leaf[c]:
+                split(c)
+
+    split(0)
+    n = len(parent)
+    leaves = np.nonzero(np.array(is_leaf))[0]
+    words = rng.permutation(len(leaves)) if ragged else np.arange(len(leaves))
+    word_id = np.full(n, -1, np.int32)
+    word_id[leaves] = words
+    weight = np.zeros(n, np.float64)
+    weight[leaves] = rng.uniform(0.5, 3.0, len(leaves))
+    if ragged:
+        weight[leaves[rng.random(len(leaves)) < 0.2]] = 0.0
+    return dict(parent=np.array(parent, np.int32), descriptors=np.array(desc).astype(F32), weight=weight, word_id=word_id, k=k, L=L,
+                scoring=0, weighting=0, n_nodes=n, n_words=int(len(leaves)), C=C)
+
+
+def make_bow_problem(H: int, W: int, C: int, seed: int = 0, kind: str = "iid", voc: dict = None) -> dict:
+    """Inputs of ``sage_bow_transform`` (``LoopDetector::AddKeyframe``): a descriptor map ``desc`` [C, H*W] (``feat_desc``
+    reshaped to {C, -1}) and the valid locations ``loc1d`` [M] (int64, ascending) of the eroded mask of ``make_window`` (8
+    pixels off every border: M = (H - 16)(W - 16)).
+    ``kind``: "iid": Gaussian descriptors of sigma 0.3 (few words of a trained vocabulary); "nodes": the descriptor of a
+    random non-root node of ``voc`` plus noise of sigma 0.15 (most words); "constant": one descriptor at every pixel (one
+    word); "nan": "iid" with channel 0 NaN at every pixel (every distance is NaN: child 0 at every level).
+    -> dict(desc, mask [H, W] bool, loc1d, M, P, H, W, C, kind).  Deterministic per ``seed``."""
+    assert kind in BOW_KINDS and H > 16 and W > 16
+    rng = np.random.default_rng(seed)
+    P = H * W
+    if kind == "nodes":
+        assert voc is not None and voc["C"] == C
+        pick = rng.integers(1, voc["n_nodes"], P)
+        desc = voc["descriptors"][pick].T.astype(np.float64) + rng.normal(0.0, 0.15, (C, P))
+    elif kind == "constant":
+        desc = np.repeat(rng.normal(0.0, 0.3, (C, 1)), P, axis=1)
+    else:
+        desc = rng.normal(0.0, 0.3, (C, P))
+        if kind == "nan":
+            desc[0] = np.nan
+    mask = np.zeros((H, W), bool)
+    mask[8:H - 8, 8:W - 8] = True
+    loc1d = np.nonzero(mask.reshape(-1))[0].astype(np.int64)
+    return dict(desc=np.ascontiguousarray(desc, F32), mask=mask, loc1d=loc1d, M=int(loc1d.size), P=P, H=H, W=W, C=C, kind=kind)
