@@ -490,6 +490,93 @@ int sage_bow_db_size(const SageBowDatabase *db); /* entries; -1 for NULL */
 int sage_bow_db_query(const SageBowDatabase *db, const int32_t *ids, const double *vals, int n, int max_results, int max_id,
                       int32_t *entry_ids, double *scores, int capacity, int *n_out);
 
+/* ---- robust registration of keypoint matches: the step between sage_cycle_match and the keypoint factors ----
+ * CameraTracker::FeatureMatchingGeo (core/system/camera_tracker.cpp:575-768, :770-947), MatchGeometryFactor's constructor
+ * (core/gtsam/match_geometry_factor.cpp:98-190) and the loop-MG factor's gather two 3-D point sets from the cycle-consistent
+ * matches, build per-point noise bounds max(mult * d / f, 5e-4), call teaser::RobustRegistrationSolver::solve(src, dst,
+ * noise_bounds) and keep getTranslationInliers().  Here: sage_match_points (the gather), sage_robust_registration (the solve
+ * in the reference's shipped configuration: inlier_selection_mode none, chain TIMs for the rotation, GNC-TLS,
+ * estimate_scaling).  What the solver does there (thirdparty/TEASER-plusplus/teaser/src/registration.cc):
+ *   1. every pair i < j, in the order i * N - i (i + 1) / 2 + (j - i - 1), gives a scale measurement in fp64:
+ *      v1 = |src_j - src_i|, v2 = |dst_j - dst_i|, X = v2 / v1, r = ((nb_i + nb_j) * sqrt(cbar2)) * (1 / v1), w = 1 / r^2
+ *   2. the truncated-least-squares vote (ScalarTLSEstimator::estimate, :21-88): the 2 * pairs interval endpoints X - r
+ *      (entering) and X + r (leaving) sorted; running sums of e, e w, e w X, e r, e X, e X^2 (e = +1 / -1) over them; at every
+ *      endpoint x = sum wX / sum w and cost = card x^2 + sum X^2 - 2 x sum X + (sum of all r - sum e r); the scale is x at the
+ *      first smallest cost.  ON THE DEVICE: a pair kernel, a bitonic sort of (key, payload), a three-phase fp64 scan fused
+ *      with the cost and the argmin, a count of the pairs with |X - scale| <= r
+ *   3. the rotation: GNC-TLS over the N chain TIMs (:596-657, :990-1101) with svdRot (utils.h:121-136), on the host in fp64
+ *   4. the translation: three scalar votes over N values (:361-388) and the AND of their masks, on the host in fp64
+ * THE ONE DELIBERATE DIFFERENCE: a pair with v1 == 0 (coincident src points; also a pair whose X or r is not finite, or r <= 0) has no
+ * defined behaviour in the reference -- NaN keys go into std::sort.  Here such a pair leaves the vote and is counted in
+ * n_degenerate_pairs.  The reference's std::sort leaves the order of tied endpoints open: here ties go by pair, entering
+ * first.  The device sums run in a fixed tree order, not sequentially: scale agrees with the sequential sum within the bound
+ * of a reordered sum (tests/test_gpu_registration.py), and two calls on the same inputs return identical bytes.
+ * Workspace bytes (device, kept by the workspace, grow with N): with pairs = N (N - 1) / 2 and P = the power of two
+ * >= max(2 * pairs, 4096):  12 P (keys 8, payloads 4) + 16 pairs (X, r) + 160 (P / 2048) + 80 (per-tile sums,
+ * offsets and minima, the two counters); N = 512: 5.2 MB, N = 1024: 21 MB.  Pinned: 64 + 32 N. */
+#define SAGE_REG_MAX_POINTS 1024 /* 523 776 pairs; 1 047 552 endpoints */
+enum { SAGE_REG_CHAIN = 0, SAGE_REG_COMPLETE = 1 };                                                  /* rotation_tim_graph */
+enum { SAGE_REG_SELECT_PMC_EXACT = 0, SAGE_REG_SELECT_PMC_HEU = 1, SAGE_REG_SELECT_KCORE_HEU = 2, SAGE_REG_SELECT_NONE = 3 }; /* teaser's order */
+enum { SAGE_REG_GNC_TLS = 0, SAGE_REG_FGR = 1 };                                                     /* rotation_algorithm */
+typedef struct SageRegistrationParams /* teaser::RobustRegistrationSolver::Params, the fields the shipped path reads */
+{
+  double noise_bound;              /* scalar bound: only the GNC's mu initialisation reads it (registration.cc:648-650, :1022-1050) */
+  double cbar2;                    /* 1 */
+  int rotation_max_iterations;     /* 20 */
+  double rotation_cost_threshold;  /* 1e-4 */
+  double rotation_gnc_factor;      /* 1.4 */
+  int rotation_tim_graph;          /* SAGE_REG_CHAIN only; COMPLETE -> SAGE_E_UNSUPPORTED */
+  int inlier_selection_mode;       /* SAGE_REG_SELECT_NONE only; the clique modes -> SAGE_E_UNSUPPORTED */
+  int rotation_algorithm;          /* SAGE_REG_GNC_TLS only; FGR -> SAGE_E_UNSUPPORTED */
+} SageRegistrationParams;
+typedef struct SageRegistrationResult /* host */
+{
+  int valid;                       /* 0: N < 2, or no pair left in the vote (nothing else is meaningful then) */
+  double scale, R[9] /* row-major */, t[3];
+  int n_inliers;                   /* = getTranslationInliers().size() */
+  int n_pairs, n_degenerate_pairs, n_scale_inlier_pairs;
+  int rotation_iterations;         /* the GNC's loop index at its exit (0: it left at the mu <= 0 test); max_iterations when it ran out */
+  int n_rotation_inliers;          /* chain TIMs with a final weight >= 0.5 */
+  double scale_cost;               /* the vote's minimum */
+} SageRegistrationResult;
+/* src_dev, dst_dev [N][3], noise_bounds_dev [N]: fp32 device arrays (the reference widens fp32 tensors to double before the
+ * solve); everything from the pair measurements on is fp64.  inliers_host / inliers_dev [N] (each may be NULL): the
+ * translation inliers, ascending; n_inliers entries are written, on return also on the device.  SAGE_E_INVALID (nothing is
+ * launched) for a NULL required pointer, N < 0 or N > SAGE_REG_MAX_POINTS, cbar2 / noise_bound / gnc factor not positive and
+ * finite (factor <= 1), rotation_max_iterations < 0, a mode that is no SAGE_REG_* value; SAGE_E_UNSUPPORTED for the modes
+ * named above.  N < 2: SAGE_OK, valid = 0, n_inliers = 0 (the reference never calls the solver there).  The last kernel
+ * publishes scale, the counts and the N points with their bounds into pinned memory and posts the workspace's ticket: one
+ * wait, no blocking copy (one more wait when inliers_dev is asked for). */
+int sage_robust_registration(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev, int N,
+                             const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                             int32_t *inliers_dev);
+/* host, fp64: ScalarTLSEstimator::estimate as written (a stable sort of the endpoints by value, the sequential sums, the first
+ * smallest cost).  estimate, inliers [n] (1: |X - estimate| <= range): each may be NULL.  SAGE_E_INVALID for a NULL X or
+ * ranges or n < 1.  Used by the translation step and by tests. */
+int sage_tls_estimate(const double *X, const double *ranges, int n, double *estimate, uint8_t *inliers);
+/* host, fp64: steps 3 and 4 for a given scale (what sage_robust_registration runs after the device vote; one entry point more
+ * than the vote needs: tests and a caller with its own scale use it).  src, dst [N][3], noise_bounds [N]: HOST fp32 arrays,
+ * N >= 2.  Fills R, t, n_inliers, rotation_iterations, n_rotation_inliers of *res (scale is stored as given, valid = 1);
+ * inliers_host [N] and rotation_mask [N] (1: the chain TIM i -> i + 1 kept its weight) may be NULL. */
+int sage_registration_finish(const float *src, const float *dst, const float *noise_bounds, int N, double scale,
+                             const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                             uint8_t *rotation_mask);
+/* The gather in front of the solver (camera_tracker.cpp:654-714, :849-909; match_geometry_factor.cpp:97-158).  All arrays on
+ * the device.  cyc_inlier_flags [K] (from sage_cycle_match), raw_matched_loc1d_1 [K], dpts0 [K] and homo0 [K][3]: per
+ * keypoint.  The flagged keypoints are compacted in ascending order (torch::nonzero); per kept keypoint, in fp32 and in the
+ * reference's order of operations (true divisions, as torch evaluates them on the CPU):
+ *   pts0 = (d0 / depth_divisor0) * homo0;   x = fmod((float)loc, (float)W), y = floor((float)loc / (float)W)
+ *   homo1 = ((x - cx) / fx, (y - cy) / fy, 1);   dpts1 = dpt_map_1[loc];   pts1 = dpts1 * homo1
+ *   noise_bounds = max((noise_multiplier * d) / ((fx + fy) / 2), 5e-4), d = d0 (noise_from 0) or dpts1 (noise_from 1)
+ * kept [K]: the keypoints' positions in 0..K-1.  *M_host: how many were kept (0: nothing else is written);
+ * *mean_noise_depth_host (may be NULL): the mean of d, summed in fp64 and rounded once -- NOT pinned to torch::mean's
+ * reduction order.  A location outside [0, cam->w * cam->h) reads a NaN depth.  SAGE_E_INVALID for a NULL pointer other than
+ * mean_noise_depth_host, K < 1, W < 1, fx / fy not positive and finite, noise_from not 0 or 1.  One kernel, one wait. */
+int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const int64_t *raw_matched_loc1d_1, const float *dpts0,
+                      const float *homo0, float depth_divisor0, const float *dpt_map_1, const SageCamera *cam, int K, int W,
+                      float noise_multiplier, int noise_from, float *pts0, float *pts1, float *noise_bounds, float *homo1,
+                      float *dpts1, int32_t *kept, int *M_host, float *mean_noise_depth_host);
+
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)
  * ===================================================================== */
@@ -844,7 +931,8 @@ int sage_tracker_match_geom_error_calculate(SageWorkspace *ws, float *error_host
  * core/system/camera_tracker.cpp:608-633: for K keypoints of frame 0 (flat indices kp_loc1d_0, int64) the best match in
  * desc1 [C,H,W] under -sum_c (d0 - d1)^2, the best match of THAT descriptor back in desc0, and the inlier flag
  * |kp - cyc|_2 <= cyc_thresh (pixels).  The K x H*W response maps are never materialised.  Outputs are device arrays
- * of K entries; *n_inliers_host receives the number of flags set (synchronises).  TEASER++ filtering stays on the host. */
+ * of K entries; *n_inliers_host receives the number of flags set (synchronises).  The gather and the robust registration that
+ * follow it: sage_match_points, sage_robust_registration above. */
 int sage_cycle_match(SageWorkspace *ws, const float *desc0_dev, const float *desc1_dev, const int64_t *kp_loc1d_0,
                      int K, int C, int H, int W, float cyc_thresh, int64_t *raw_matched_loc1d_1,
                      int64_t *cyc_matched_loc1d_0, int32_t *inlier_flags, int *n_inliers_host);

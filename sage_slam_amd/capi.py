@@ -151,6 +151,7 @@ SYMBOLS = [
     "sage_match_geometry_jac_error_calculate", "sage_match_geometry_error_calculate",
     "sage_loop_mg_jac_error_calculate", "sage_loop_mg_error_calculate",
     "sage_tracker_match_geom_jac_error_calculate", "sage_tracker_match_geom_error_calculate", "sage_cycle_match",
+    "sage_robust_registration", "sage_tls_estimate", "sage_registration_finish", "sage_match_points",
 ]
 
 
@@ -1507,6 +1508,142 @@ def cycle_match(ws, desc0, desc1, kp_loc0, H, W, cyc_thresh):
     _chk(lib().sage_cycle_match(ws.h, _dptr(desc0), _dptr(desc1), _dptr(kp_loc0), K, Cc, H, W, C.c_float(cyc_thresh),
                                 _dptr(m1), _dptr(c0), _dptr(fl), C.byref(n)), "sage_cycle_match")
     return m1[:K], c0[:K], fl[:K], n.value
+
+
+# --------------------------------------------------------------------------- robust registration of keypoint matches
+SAGE_REG_MAX_POINTS = 1024
+SAGE_REG_CHAIN, SAGE_REG_COMPLETE = 0, 1
+SAGE_REG_SELECT_PMC_EXACT, SAGE_REG_SELECT_PMC_HEU, SAGE_REG_SELECT_KCORE_HEU, SAGE_REG_SELECT_NONE = range(4)
+SAGE_REG_GNC_TLS, SAGE_REG_FGR = 0, 1
+
+
+class SageRegistrationParams(C.Structure):
+    _fields_ = [("noise_bound", C.c_double), ("cbar2", C.c_double), ("rotation_max_iterations", C.c_int),
+                ("rotation_cost_threshold", C.c_double), ("rotation_gnc_factor", C.c_double), ("rotation_tim_graph", C.c_int),
+                ("inlier_selection_mode", C.c_int), ("rotation_algorithm", C.c_int)]
+
+
+class SageRegistrationResult(C.Structure):
+    _fields_ = [("valid", C.c_int), ("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("n_inliers", C.c_int),
+                ("n_pairs", C.c_int), ("n_degenerate_pairs", C.c_int), ("n_scale_inlier_pairs", C.c_int),
+                ("rotation_iterations", C.c_int), ("n_rotation_inliers", C.c_int), ("scale_cost", C.c_double)]
+
+
+def registration_params(params=None, **kw) -> SageRegistrationParams:
+    """a dict (``synth.registration_params``) and / or keywords -> ``SageRegistrationParams``; the reference's shipped values
+    (configs/slam_run.flags:76-85) where nothing is given, noise_bound 0.01"""
+    d = dict(noise_bound=0.01, cbar2=1.0, rotation_max_iterations=20, rotation_cost_threshold=1e-4, rotation_gnc_factor=1.4,
+             rotation_tim_graph=SAGE_REG_CHAIN, inlier_selection_mode=SAGE_REG_SELECT_NONE, rotation_algorithm=SAGE_REG_GNC_TLS)
+    d.update(params or {})
+    d.update(kw)
+    return SageRegistrationParams(**d)
+
+
+def _reg_result(res: SageRegistrationResult) -> dict:
+    out = {name: getattr(res, name) for name, _ in SageRegistrationResult._fields_ if name not in ("R", "t")}
+    out["R"] = np.array(list(res.R), np.float64).reshape(3, 3)
+    out["t"] = np.array(list(res.t), np.float64)
+    return out
+
+
+def robust_registration_raw(ws_handle, src_ptr, dst_ptr, nb_ptr, N, params_ptr, res_ptr, inliers_host_ptr, inliers_dev_ptr) -> int:
+    """``sage_robust_registration`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_robust_registration
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, src_ptr, dst_ptr, nb_ptr, int(N), params_ptr, res_ptr, inliers_host_ptr, inliers_dev_ptr))
+
+
+def robust_registration(ws: "Workspace", src, dst, noise_bounds, params=None, device_inliers: bool = False) -> dict:
+    """``teaser::RobustRegistrationSolver::solve(src, dst, noise_bounds)`` in the reference's shipped configuration through
+    ``sage_robust_registration``.  src, dst [N, 3], noise_bounds [N]: contiguous float32 cuda tensors; params: a dict, a
+    ``SageRegistrationParams`` or None.  -> the fields of ``SageRegistrationResult`` (R [3, 3], t [3] float64 arrays) and
+    ``inliers`` (int32 array, ascending); with ``device_inliers`` also ``inliers_dev`` (int32 cuda tensor [n_inliers])."""
+    import torch
+    N = int(src.shape[0])
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and noise_bounds.dtype == torch.float32
+    assert tuple(dst.shape) == (N, 3) and noise_bounds.numel() == N
+    p = params if isinstance(params, SageRegistrationParams) else registration_params(params)
+    res = SageRegistrationResult()
+    inl = np.zeros(max(N, 1), np.int32)
+    inl_dev = torch.zeros(max(N, 1), dtype=torch.int32, device=src.device) if device_inliers else None
+    _chk(robust_registration_raw(ws.h, dptr(src), dptr(dst), dptr(noise_bounds), N, C.addressof(p), C.addressof(res),
+                                 inl.ctypes.data, dptr(inl_dev)), "sage_robust_registration")
+    out = _reg_result(res)
+    out["inliers"] = inl[:res.n_inliers].copy()
+    if device_inliers:
+        out["inliers_dev"] = inl_dev[:res.n_inliers]
+    return out
+
+
+def tls_estimate_raw(X_ptr, ranges_ptr, n, estimate_ptr, inliers_ptr) -> int:
+    f = lib().sage_tls_estimate
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    return int(f(X_ptr, ranges_ptr, int(n), estimate_ptr, inliers_ptr))
+
+
+def tls_estimate(X, ranges):
+    """``ScalarTLSEstimator::estimate`` through ``sage_tls_estimate`` (host, float64) -> (estimate, inliers [n] bool)"""
+    X = np.ascontiguousarray(X, np.float64); ranges = np.ascontiguousarray(ranges, np.float64)
+    assert X.ndim == 1 and X.shape == ranges.shape
+    est = C.c_double()
+    inl = np.zeros(max(X.size, 1), np.uint8)
+    _chk(tls_estimate_raw(X.ctypes.data, ranges.ctypes.data, X.size, C.addressof(est), inl.ctypes.data), "sage_tls_estimate")
+    return est.value, inl[:X.size].astype(bool)
+
+
+def registration_finish_raw(src_ptr, dst_ptr, nb_ptr, N, scale, params_ptr, res_ptr, inliers_ptr, rotation_mask_ptr) -> int:
+    f = lib().sage_registration_finish
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(src_ptr, dst_ptr, nb_ptr, int(N), float(scale), params_ptr, res_ptr, inliers_ptr, rotation_mask_ptr))
+
+
+def registration_finish(src, dst, noise_bounds, scale: float, params=None) -> dict:
+    """The solve's host finish for a given scale (chain TIMs, GNC-TLS rotation, translation votes) through
+    ``sage_registration_finish``.  src, dst [N, 3], noise_bounds [N]: host arrays (taken as float32).  -> the result's fields,
+    ``inliers`` (int32, ascending) and ``rotation_mask`` [N] bool"""
+    src = _f32(src); dst = _f32(dst); nb = _f32(noise_bounds)
+    N = int(src.shape[0])
+    p = params if isinstance(params, SageRegistrationParams) else registration_params(params)
+    res = SageRegistrationResult()
+    inl = np.zeros(max(N, 1), np.int32); rot = np.zeros(max(N, 1), np.uint8)
+    _chk(registration_finish_raw(src.ctypes.data, dst.ctypes.data, nb.ctypes.data, N, scale, C.addressof(p), C.addressof(res),
+                                 inl.ctypes.data, rot.ctypes.data), "sage_registration_finish")
+    out = _reg_result(res)
+    out["inliers"] = inl[:res.n_inliers].copy()
+    out["rotation_mask"] = rot[:N].astype(bool)
+    return out
+
+
+def match_points_raw(ws_handle, flags, loc1, dpts0, homo0, divisor0, dpt_map_1, cam_ptr, K, W, mult, noise_from, pts0, pts1, nb,
+                     homo1, dpts1, kept, M_ptr, mean_ptr) -> int:
+    """``sage_match_points`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_match_points
+    f.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 8
+    return int(f(ws_handle, flags, loc1, dpts0, homo0, float(divisor0), dpt_map_1, cam_ptr, int(K), int(W), float(mult),
+                 int(noise_from), pts0, pts1, nb, homo1, dpts1, kept, M_ptr, mean_ptr))
+
+
+def match_points(ws: "Workspace", flags, raw_matched_loc1, dpts0, homo0, depth_divisor0, dpt_map_1, cam, W, noise_multiplier,
+                 noise_from: int = 1) -> dict:
+    """The gather between ``sage_cycle_match`` and the solver through ``sage_match_points``.  flags [K] int32, raw_matched_loc1
+    [K] int64, dpts0 [K], homo0 [K, 3], dpt_map_1 [H*W]: contiguous cuda tensors; cam: anything with fx, fy, cx, cy, w, h.
+    -> dict(M, mean_depth, pts0, pts1 [M, 3], noise_bounds, dpts1 [M], homo1 [M, 3], kept [M] int32): cuda tensors cut to M."""
+    import torch
+    K = int(flags.numel())
+    assert flags.dtype == torch.int32 and raw_matched_loc1.dtype == torch.int64
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    dev = flags.device
+    f3 = lambda: torch.zeros(max(K, 1), 3, dtype=torch.float32, device=dev)
+    f1 = lambda: torch.zeros(max(K, 1), dtype=torch.float32, device=dev)
+    pts0, pts1, homo1, nb, dpts1 = f3(), f3(), f3(), f1(), f1()
+    kept = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+    M = C.c_int(); mean = C.c_float()
+    _chk(match_points_raw(ws.h, dptr(flags), dptr(raw_matched_loc1), dptr(dpts0), dptr(homo0), depth_divisor0, dptr(dpt_map_1),
+                          C.addressof(c), K, W, noise_multiplier, noise_from, dptr(pts0), dptr(pts1), dptr(nb), dptr(homo1),
+                          dptr(dpts1), dptr(kept), C.addressof(M), C.addressof(mean)), "sage_match_points")
+    m = M.value
+    return dict(M=m, mean_depth=np.float32(mean.value), pts0=pts0[:m], pts1=pts1[:m], noise_bounds=nb[:m], homo1=homo1[:m],
+                dpts1=dpts1[:m], kept=kept[:m])
 
 
 # ----------------------------------------------------------------------------------------------------------------------

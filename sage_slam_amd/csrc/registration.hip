@@ -1,0 +1,752 @@
+// registration.hip -- robust registration of keypoint matches: sage_robust_registration and sage_match_points.
+// teaser::RobustRegistrationSolver::solve(src, dst, noise_bounds) in the reference's shipped configuration spends almost all of
+// its time in the scale vote over the N (N - 1) / 2 pairs (registration.cc:395-485, :297-313, :21-88): 130 816 pairs at
+// N = 512, a std::sort of twice as many interval endpoints and one sequential pass of six running sums.  Here the vote is
+//
+//   reg_pair_kernel        one lane per pair (i < j), the reference's pair order: in fp64 X = |dst_j - dst_i| / |src_j - src_i|,
+//                          r = ((nb_i + nb_j) sqrt(cbar2)) (1 / |src_j - src_i|); writes (X, r) and the two endpoints X - r
+//                          (entering), X + r (leaving) as order-preserving 64-bit keys with the payload 2 pair + leaving.  A
+//                          pair without a usable measurement (v1 == 0; X or r not finite; r <= 0) writes padding instead and
+//                          is counted.  The slots up to P, the power of two the sort runs over, are padded as well
+//   reg_sort_tile_kernel,  a bitonic sort of (key, payload) pairs by key, ties by payload: all stages with a distance below a
+//   reg_sort_stage_kernel, tile of 1024 endpoints run in LDS (12 KiB), the others two per launch (a lane per four endpoints; an
+//   reg_sort_stage2_kernel odd one out alone).  Chosen over a radix sort for what it does not need: no histograms, no second
+//                          copy of the endpoints, no order among workgroups; the result is a function of the multiset of
+//                          (key, payload) alone
+//   reg_tile_sums_kernel,  the running sums of e w, e w X, e r, e X, e X^2, the entering r and e (e = +1 entering, -1 leaving)
+//   reg_tile_offsets_kernel, in fp64 over the sorted endpoints in three phases: per-tile totals, one workgroup's exclusive scan
+//   reg_cost_kernel        of them, and per tile the inclusive sums with, fused, the vote's cost at every endpoint and the
+//                          tile's first smallest one.  Every sum runs in a fixed order (lane-sequential, then a wave scan,
+//                          then the waves, then the tiles): the same inputs give the same bytes on any workspace
+//   reg_count_kernel       the first smallest cost over the tiles gives the scale; one lane per pair counts |X - scale| <= r
+//   reg_publish_kernel     one workgroup: scale, cost and the counts, and the N points with their bounds (what the host
+//                          finish reads), into the workspace's pinned record; posts the ticket
+// then registration_host.cpp's finish on the host (O(N), fp64).  No float atomics (two integer counters), no workgroup
+// waits for another, every loop is bounded by N, the tile or the number of tiles.  All stores are plain C++.
+#include "runtime_internal.h"
+
+namespace
+{
+constexpr int kRegTile = 2048;                  // endpoints per workgroup of the scan
+constexpr int kSortTileMax = 4096;              // endpoints per workgroup of the sort's LDS stages: 1024, 2048 or 4096
+constexpr int kSortTileDefault = 1024;          // (12 bytes of LDS each.  Measured at N = 512: 0.307 / 0.329 / 0.440 ms per call with 1024 /
+                                                // 2048 / 4096 -- the LDS stages are what takes the time, and small tiles spread them over
+                                                // more CUs; SAGE_REG_SORT_TILE picks another: scripts/registration_bench.py)
+constexpr int kRegPerLane = kRegTile / kBlock;  // 8 consecutive endpoints per lane of the scan
+constexpr int kRegQ = 7;                        // scanned quantities: e w, e w X, e r, e X, e X^2, [entering] r, e
+constexpr int kRegRow = 8;                      // doubles per tile row (kRegQ + 1 unused: 64-byte rows)
+constexpr uint32_t kRegPadPayload = 0xffffffffu;
+constexpr uint64_t kRegPadKey = ~0ull;
+constexpr int kRegNoIndex = 0x7fffffff;
+
+struct RegHost // the pinned record
+{
+  double scale, scale_cost;
+  int32_t n_pairs, n_degenerate, n_scale_inliers, vote_valid;
+  int32_t M;         // sage_match_points: keypoints kept ...
+  float mean_depth;  // ... and the mean of the depths the bounds were made from
+  int32_t pad[6];
+  float pts[1]; // src [N][3], dst [N][3], noise bounds [N]; then the translation inliers [N] int32 (written by the host)
+};
+static_assert(offsetof(RegHost, pts) == 64, "device-visible layout");
+
+struct RegMin // a tile's (or the vote's) first smallest cost
+{
+  double cost, x;
+  int idx; // position among the sorted endpoints; kRegNoIndex: none
+};
+
+struct RegTileMin // RegMin as stored per tile: 32 bytes
+{
+  double cost, x;
+  long long idx;
+  long long pad;
+};
+
+__device__ __forceinline__ uint64_t reg_key(double v)
+{
+  if (v == 0.0)
+    v = 0.0; // (-0 and +0 are one value)
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ int reg_row_start(int i, int N) { return i * N - i * (i + 1) / 2; }
+
+__global__ __launch_bounds__(kBlock) void reg_pair_kernel(const float *__restrict__ src, const float *__restrict__ dst,
+                                                          const float *__restrict__ nb, int N, int n_pairs, int half_P,
+                                                          double sqrt_cbar2, uint64_t *keys, uint32_t *payload, double2 *pairs,
+                                                          int *counters)
+{
+#pragma clang fp contract(off) // the reference's operations one by one: no fused multiply-add
+  const int p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= half_P)
+    return;
+  uint64_t k0 = kRegPadKey, k1 = kRegPadKey;
+  uint32_t q0 = kRegPadPayload, q1 = kRegPadPayload;
+  if (p < n_pairs)
+  {
+    // the row i with row_start(i) <= p < row_start(i + 1): the closed form, then the neighbours (the square root may be off)
+    const double b = 2.0 * N - 1.0;
+    int i = (int)((b - sqrt(fmax(b * b - 8.0 * (double)p, 0.0))) * 0.5);
+    i = min(max(i, 0), N - 2);
+    while (i > 0 && reg_row_start(i, N) > p)
+      --i;
+    while (i < N - 2 && reg_row_start(i + 1, N) <= p)
+      ++i;
+    const int j = p - reg_row_start(i, N) + i + 1;
+    const double sx = (double)src[3 * j + 0] - (double)src[3 * i + 0], sy = (double)src[3 * j + 1] - (double)src[3 * i + 1],
+                 sz = (double)src[3 * j + 2] - (double)src[3 * i + 2];
+    const double dx = (double)dst[3 * j + 0] - (double)dst[3 * i + 0], dy = (double)dst[3 * j + 1] - (double)dst[3 * i + 1],
+                 dz = (double)dst[3 * j + 2] - (double)dst[3 * i + 2];
+    const double v1 = sqrt(sx * sx + sy * sy + sz * sz), v2 = sqrt(dx * dx + dy * dy + dz * dz);
+    const double X = v2 / v1;
+    const double r = (((double)nb[j] + (double)nb[i]) * sqrt_cbar2) * (1.0 / v1);
+    const bool ok = v1 > 0.0 && isfinite(X) && isfinite(r) && r > 0.0 && isfinite(1.0 / (r * r));
+    if (ok)
+    {
+      k0 = reg_key(X - r);
+      k1 = reg_key(X + r);
+      q0 = 2u * (uint32_t)p;
+      q1 = q0 + 1u;
+      pairs[p] = make_double2(X, r);
+    }
+    else
+    {
+      const double nan = __longlong_as_double(0x7ff8000000000000ll);
+      pairs[p] = make_double2(nan, nan);
+      atomicAdd(&counters[0], 1); // (rare)
+    }
+  }
+  reinterpret_cast<ulonglong2 *>(keys)[p] = make_ulonglong2(k0, k1);
+  reinterpret_cast<uint2 *>(payload)[p] = make_uint2(q0, q1);
+}
+
+__device__ __forceinline__ bool reg_after(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb)
+{
+  return ka > kb || (ka == kb && pa > pb);
+}
+
+// the bitonic network's stages k_first .. k_last (powers of two), each from the distance min(k / 2, kSortTile / 2) down to 1, on
+// one tile in LDS.  The direction of a compare-exchange comes from the endpoint's global position
+template <int kSortTile>
+__global__ __launch_bounds__(kBlock) void reg_sort_tile_kernel(uint64_t *keys, uint32_t *payload, int k_first, int k_last)
+{
+  __shared__ uint64_t s_k[kSortTile];
+  __shared__ uint32_t s_p[kSortTile];
+  const int tid = threadIdx.x, base = blockIdx.x * kSortTile;
+  for (int q = tid; q < kSortTile; q += kBlock)
+  {
+    s_k[q] = keys[base + q];
+    s_p[q] = payload[base + q];
+  }
+  __syncthreads();
+  for (int k = k_first; k <= k_last; k <<= 1)
+    for (int j = min(k >> 1, kSortTile >> 1); j > 0; j >>= 1)
+    {
+      for (int t = tid; t < kSortTile / 2; t += kBlock)
+      {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const bool up = ((base + lo) & k) == 0;
+        const uint64_t ka = s_k[lo], kb = s_k[hi];
+        const uint32_t pa = s_p[lo], pb = s_p[hi];
+        if (reg_after(ka, pa, kb, pb) == up)
+        {
+          s_k[lo] = kb;
+          s_k[hi] = ka;
+          s_p[lo] = pb;
+          s_p[hi] = pa;
+        }
+      }
+      __syncthreads();
+    }
+  for (int q = tid; q < kSortTile; q += kBlock)
+  {
+    keys[base + q] = s_k[q];
+    payload[base + q] = s_p[q];
+  }
+}
+
+// one stage (k, j) across tiles: a lane per compare-exchange
+__global__ __launch_bounds__(kBlock) void reg_sort_stage_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int half_P)
+{
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= half_P)
+    return;
+  const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+  const bool up = (lo & k) == 0;
+  const uint64_t ka = keys[lo], kb = keys[hi];
+  const uint32_t pa = payload[lo], pb = payload[hi];
+  if (reg_after(ka, pa, kb, pb) == up)
+  {
+    keys[lo] = kb;
+    keys[hi] = ka;
+    payload[lo] = pb;
+    payload[hi] = pa;
+  }
+}
+
+// two stages (k, j) and (k, j / 2) across tiles: a lane per four endpoints i0, i0 + j / 2, i0 + j, i0 + j + j / 2
+// (i0: the lane's index with two zero bits inserted at j / 2 and j; k > j, so the four share a direction)
+__global__ __launch_bounds__(kBlock) void reg_sort_stage2_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int quarter_P)
+{
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= quarter_P)
+    return;
+  const int h = j >> 1;
+  const int i0 = ((t & ~(h - 1)) << 2) | (t & (h - 1));
+  const bool up = (i0 & k) == 0;
+  const int at[4] = {i0, i0 + h, i0 + j, i0 + j + h};
+  uint64_t kk[4];
+  uint32_t pp[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    kk[q] = keys[at[q]];
+    pp[q] = payload[at[q]];
+  }
+  auto exchange = [&](int a, int b) {
+    if (reg_after(kk[a], pp[a], kk[b], pp[b]) == up)
+    {
+      const uint64_t tk = kk[a];
+      kk[a] = kk[b];
+      kk[b] = tk;
+      const uint32_t tp = pp[a];
+      pp[a] = pp[b];
+      pp[b] = tp;
+    }
+  };
+  exchange(0, 2); // distance j
+  exchange(1, 3);
+  exchange(0, 1); // distance j / 2
+  exchange(2, 3);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    keys[at[q]] = kk[q];
+    payload[at[q]] = pp[q];
+  }
+}
+
+// what one sorted endpoint adds to the running sums
+__device__ __forceinline__ void reg_term(uint32_t pl, const double2 *__restrict__ pairs, double (&q)[kRegQ])
+{
+#pragma clang fp contract(off)
+  if (pl == kRegPadPayload)
+  {
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      q[c] = 0.0;
+    return;
+  }
+  const double2 m = pairs[pl >> 1];
+  const double X = m.x, r = m.y;
+  const bool entering = (pl & 1u) == 0u;
+  const double e = entering ? 1.0 : -1.0;
+  const double ew = e * (1.0 / (r * r));
+  q[0] = ew;
+  q[1] = ew * X;
+  q[2] = e * r;
+  q[3] = e * X;
+  q[4] = (e * X) * X;
+  q[5] = entering ? r : 0.0;
+  q[6] = e;
+}
+
+// v: this lane's totals.  -> excl: the totals of the lanes before it in the workgroup; total: the workgroup's.  Fixed order:
+// an inclusive wave scan (log steps), then the waves in turn.  s_wave [kWaves][kRegQ]; ends behind a barrier
+__device__ __forceinline__ void reg_block_scan(const double (&v)[kRegQ], double (&excl)[kRegQ], double (&total)[kRegQ],
+                                               double (*s_wave)[kRegQ])
+{
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double before[kRegQ];
+#pragma unroll
+  for (int c = 0; c < kRegQ; ++c)
+  {
+    double inc = v[c];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+      const double t = __shfl_up(inc, o, 64);
+      if (lane >= o)
+        inc += t;
+    }
+    const double prev = __shfl_up(inc, 1, 64);
+    before[c] = lane ? prev : 0.0;
+    if (lane == 63)
+      s_wave[wave][c] = inc;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < kRegQ; ++c)
+  {
+    double off = 0.0, tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+    {
+      if (w < wave)
+        off += s_wave[w][c];
+      tot += s_wave[w][c];
+    }
+    excl[c] = off + before[c];
+    total[c] = tot;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kBlock) void reg_tile_sums_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                                               double *tile_sums)
+{
+#pragma clang fp contract(off)
+  __shared__ double s_wave[kWaves][kRegQ];
+  const int at = blockIdx.x * kRegTile + threadIdx.x * kRegPerLane;
+  double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < kRegPerLane; ++e)
+  {
+    double q[kRegQ];
+    reg_term(payload[at + e], pairs, q);
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      v[c] += q[c];
+  }
+  double excl[kRegQ], total[kRegQ];
+  reg_block_scan(v, excl, total, s_wave);
+  if (threadIdx.x == 0)
+  {
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      tile_sums[(size_t)blockIdx.x * kRegRow + c] = total[c];
+  }
+}
+
+// one workgroup: tile_offs[t] = the sums of the tiles before t, tile_offs[n_tiles] = the sums of all
+__global__ __launch_bounds__(kBlock) void reg_tile_offsets_kernel(const double *__restrict__ tile_sums, double *tile_offs, int n_tiles)
+{
+#pragma clang fp contract(off)
+  __shared__ double s_wave[kWaves][kRegQ];
+  const int per = (n_tiles + kBlock - 1) / kBlock;
+  const int t0 = min(threadIdx.x * per, n_tiles), t1 = min(t0 + per, n_tiles);
+  double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
+  for (int t = t0; t < t1; ++t)
+  {
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      v[c] += tile_sums[(size_t)t * kRegRow + c];
+  }
+  double run[kRegQ], total[kRegQ];
+  reg_block_scan(v, run, total, s_wave);
+  for (int t = t0; t < t1; ++t)
+  {
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+    {
+      tile_offs[(size_t)t * kRegRow + c] = run[c];
+      run[c] += tile_sums[(size_t)t * kRegRow + c];
+    }
+  }
+  if (threadIdx.x == 0)
+  {
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      tile_offs[(size_t)n_tiles * kRegRow + c] = total[c];
+  }
+}
+
+__device__ __forceinline__ bool reg_min_before(const RegMin &a, const RegMin &b) // a wins over b: smaller cost, then earlier
+{
+  return a.cost < b.cost || (a.cost == b.cost && a.idx < b.idx);
+}
+
+// the workgroup's first smallest; valid in every thread.  s_min [kWaves]; ends behind a barrier
+__device__ __forceinline__ RegMin reg_block_min(RegMin m, RegMin *s_min)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    RegMin other;
+    other.cost = __shfl_down(m.cost, o, 64);
+    other.x = __shfl_down(m.x, o, 64);
+    other.idx = __shfl_down(m.idx, o, 64);
+    if (reg_min_before(other, m))
+      m = other;
+  }
+  if ((threadIdx.x & 63) == 0)
+    s_min[threadIdx.x >> 6] = m;
+  __syncthreads();
+  RegMin best = s_min[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w)
+    if (reg_min_before(s_min[w], best))
+      best = s_min[w];
+  __syncthreads();
+  return best;
+}
+
+// per tile: the inclusive running sums at every endpoint, the vote's cost there, the tile's first smallest cost.  A NaN cost
+// (an empty consensus set: 0 / 0) never wins
+__global__ __launch_bounds__(kBlock) void reg_cost_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                                          const double *__restrict__ tile_offs, int n_tiles, RegTileMin *tile_min)
+{
+#pragma clang fp contract(off)
+  __shared__ double s_wave[kWaves][kRegQ];
+  __shared__ RegMin s_min[kWaves];
+  const int at = blockIdx.x * kRegTile + threadIdx.x * kRegPerLane;
+  uint32_t pl[kRegPerLane];
+  double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < kRegPerLane; ++e)
+  {
+    pl[e] = payload[at + e];
+    double q[kRegQ];
+    reg_term(pl[e], pairs, q);
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      v[c] += q[c];
+  }
+  double run[kRegQ], total[kRegQ];
+  reg_block_scan(v, run, total, s_wave);
+#pragma unroll
+  for (int c = 0; c < kRegQ; ++c)
+    run[c] = tile_offs[(size_t)blockIdx.x * kRegRow + c] + run[c];
+  const double r_all = tile_offs[(size_t)n_tiles * kRegRow + 5];
+  RegMin best;
+  best.cost = __longlong_as_double(0x7ff0000000000000ll); // +inf
+  best.x = 0.0;
+  best.idx = kRegNoIndex;
+#pragma unroll
+  for (int e = 0; e < kRegPerLane; ++e)
+  {
+    double q[kRegQ];
+    reg_term(pl[e], pairs, q);
+#pragma unroll
+    for (int c = 0; c < kRegQ; ++c)
+      run[c] += q[c];
+    if (pl[e] != kRegPadPayload)
+    {
+      const double x = run[1] / run[0];
+      const double residual = (run[6] * x) * x + run[4] - (2.0 * run[3]) * x;
+      const double cost = residual + (r_all - run[2]);
+      if (cost < best.cost) // (false for a NaN; the first of equal costs stays)
+      {
+        best.cost = cost;
+        best.x = x;
+        best.idx = at + e;
+      }
+    }
+  }
+  best = reg_block_min(best, s_min);
+  if (threadIdx.x == 0)
+  {
+    RegTileMin out;
+    out.cost = best.cost;
+    out.x = best.x;
+    out.idx = best.idx;
+    out.pad = 0;
+    tile_min[blockIdx.x] = out;
+  }
+}
+
+// the first smallest cost over the tiles; valid in every thread
+__device__ __forceinline__ RegMin reg_vote_min(const RegTileMin *__restrict__ tile_min, int n_tiles, RegMin *s_min)
+{
+  RegMin m;
+  m.cost = __longlong_as_double(0x7ff0000000000000ll);
+  m.x = 0.0;
+  m.idx = kRegNoIndex;
+  for (int t = threadIdx.x; t < n_tiles; t += kBlock)
+  {
+    RegMin o;
+    o.cost = tile_min[t].cost;
+    o.x = tile_min[t].x;
+    o.idx = (int)tile_min[t].idx;
+    if (reg_min_before(o, m))
+      m = o;
+  }
+  return reg_block_min(m, s_min);
+}
+
+__global__ __launch_bounds__(kBlock) void reg_count_kernel(const double2 *__restrict__ pairs, int n_pairs,
+                                                           const RegTileMin *__restrict__ tile_min, int n_tiles, int *counters)
+{
+  __shared__ RegMin s_min[kWaves];
+  const RegMin vote = reg_vote_min(tile_min, n_tiles, s_min);
+  if (vote.idx == kRegNoIndex)
+    return; // (uniform)
+  const int p = blockIdx.x * kBlock + threadIdx.x;
+  bool in = false;
+  if (p < n_pairs)
+  {
+    const double2 m = pairs[p];
+    in = fabs(m.x - vote.x) <= m.y; // (false for a pair that left the vote: NaN)
+  }
+  const int n = __popcll(__ballot(in));
+  if ((threadIdx.x & 63) == 0 && n)
+    atomicAdd(&counters[1], n);
+}
+
+__global__ __launch_bounds__(kBlock) void reg_publish_kernel(const float *__restrict__ src, const float *__restrict__ dst,
+                                                             const float *__restrict__ nb, int N, int n_pairs,
+                                                             const RegTileMin *__restrict__ tile_min, int n_tiles,
+                                                             const int *__restrict__ counters, RegHost *host,
+                                                             volatile unsigned *ticket, unsigned epoch)
+{
+  __shared__ RegMin s_min[kWaves];
+  const RegMin vote = reg_vote_min(tile_min, n_tiles, s_min);
+  const int tid = threadIdx.x;
+  for (int q = tid; q < 3 * N; q += kBlock)
+  {
+    host->pts[q] = src[q];
+    host->pts[3 * N + q] = dst[q];
+  }
+  for (int q = tid; q < N; q += kBlock)
+    host->pts[6 * N + q] = nb[q];
+  if (tid == 0)
+  {
+    host->scale = vote.x;
+    host->scale_cost = vote.cost;
+    host->n_pairs = n_pairs;
+    host->n_degenerate = counters[0];
+    host->n_scale_inliers = counters[1];
+    host->vote_valid = vote.idx != kRegNoIndex;
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (tid == 0)
+  {
+    __threadfence_system();
+    *ticket = epoch;
+  }
+}
+
+struct MatchPointsParams
+{
+  const int32_t *flags;
+  const int64_t *loc1;
+  const float *dpts0, *homo0, *dpt_map_1;
+  float divisor0, cx, cy, fx, fy, Wf, focal, mult;
+  long long HW;
+  int K, noise_from;
+  float *pts0, *pts1, *noise_bounds, *homo1, *dpts1;
+  int32_t *kept;
+};
+
+// one workgroup: compacts the flagged keypoints in ascending order (a wave scan of the flags per 256 keypoints) and evaluates
+// the gather's fp32 expressions for each; the depths' sum in fp64 (per lane, then the workgroup's tree)
+__global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPointsParams P, RegHost *host, volatile unsigned *ticket,
+                                                                  unsigned epoch)
+{
+#pragma clang fp contract(off)
+  __shared__ int s_cnt[kWaves];
+  __shared__ double s_sum[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int total = 0; // the same in every thread
+  double dsum = 0.0;
+  for (int base = 0; base < P.K; base += kBlock)
+  {
+    const int k = base + tid;
+    const bool keep = k < P.K && P.flags[k] != 0;
+    int inc = keep ? 1 : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+      const int t = __shfl_up(inc, o, 64);
+      if (lane >= o)
+        inc += t;
+    }
+    if (lane == 63)
+      s_cnt[wave] = inc;
+    __syncthreads();
+    int before = total, tile = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+    {
+      if (w < wave)
+        before += s_cnt[w];
+      tile += s_cnt[w];
+    }
+    if (keep)
+    {
+      const int m = before + inc - 1;
+      const float d0 = P.dpts0[k];
+      const float s0 = d0 / P.divisor0;
+      const float h0x = P.homo0[3 * k + 0], h0y = P.homo0[3 * k + 1], h0z = P.homo0[3 * k + 2];
+      P.pts0[3 * m + 0] = s0 * h0x;
+      P.pts0[3 * m + 1] = s0 * h0y;
+      P.pts0[3 * m + 2] = s0 * h0z;
+      const long long loc = P.loc1[k];
+      const float lf = (float)loc;
+      const float x = fmodf(lf, P.Wf), y = floorf(lf / P.Wf);
+      const float hx = (x - P.cx) / P.fx, hy = (y - P.cy) / P.fy;
+      const float d1 = (loc >= 0 && loc < P.HW) ? P.dpt_map_1[loc] : __int_as_float(0x7fc00000);
+      P.homo1[3 * m + 0] = hx;
+      P.homo1[3 * m + 1] = hy;
+      P.homo1[3 * m + 2] = 1.0f;
+      P.dpts1[m] = d1;
+      P.pts1[3 * m + 0] = d1 * hx;
+      P.pts1[3 * m + 1] = d1 * hy;
+      P.pts1[3 * m + 2] = d1 * 1.0f;
+      const float d = P.noise_from ? d1 : d0;
+      const float b = (P.mult * d) / P.focal;
+      P.noise_bounds[m] = b != b ? b : fmaxf(b, 5.0e-4f); // (clamp_min keeps a NaN)
+      P.kept[m] = k;
+      dsum += (double)d;
+    }
+    total += tile;
+    __syncthreads(); // (s_cnt is written again)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    dsum += __shfl_down(dsum, o, 64);
+  if (lane == 0)
+    s_sum[wave] = dsum;
+  __syncthreads();
+  if (tid == 0)
+  {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+      s += s_sum[w];
+    host->M = total;
+    host->mean_depth = total ? (float)(s / (double)total) : 0.0f;
+    __threadfence_system();
+    *ticket = epoch;
+  }
+}
+} // namespace
+
+extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev,
+                                        int N, const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                                        int32_t *inliers_dev)
+{
+  if (!ws || !src_dev || !dst_dev || !noise_bounds_dev || !p || !res || N < 0 || N > SAGE_REG_MAX_POINTS)
+    return SAGE_E_INVALID;
+  int rc;
+  if ((rc = registration_check_params(p)))
+    return rc;
+  std::memset(res, 0, sizeof(*res));
+  if (N < 2)
+    return SAGE_OK; // (valid = 0: the reference never calls the solver there)
+
+  const int n_pairs = N * (N - 1) / 2;
+  int tile = kSortTileDefault;
+  if (const char *env = std::getenv("SAGE_REG_SORT_TILE")) // measurement: scripts/registration_bench.py times the three sizes
+  {
+    const int v = std::atoi(env);
+    if (v == 1024 || v == 2048 || v == 4096)
+      tile = v;
+  }
+  const auto sort_tile = tile == 1024 ? reg_sort_tile_kernel<1024> : tile == 2048 ? reg_sort_tile_kernel<2048> : reg_sort_tile_kernel<4096>;
+  int P = kSortTileMax; // (whatever the tile: the workspace's sizes do not depend on the measurement switch)
+  while (P < 2 * n_pairs)
+    P <<= 1;
+  const int n_tiles = (2 * n_pairs + kRegTile - 1) / kRegTile; // tiles that hold an endpoint (the padding sorts behind them)
+  // reg_tiles: [n_tiles] sums | [n_tiles + 1] offsets | [n_tiles] minima | counters
+  const size_t sums_bytes = (size_t)n_tiles * kRegRow * sizeof(double), offs_bytes = (size_t)(n_tiles + 1) * kRegRow * sizeof(double),
+               min_bytes = (size_t)n_tiles * sizeof(RegTileMin);
+  if ((rc = ws->reg_keys.reserve((size_t)P * sizeof(uint64_t))) || (rc = ws->reg_payload.reserve((size_t)P * sizeof(uint32_t))) ||
+      (rc = ws->reg_pairs.reserve((size_t)n_pairs * sizeof(double2))) ||
+      (rc = ws->reg_tiles.reserve(sums_bytes + offs_bytes + min_bytes + 4 * sizeof(int))) ||
+      (rc = ws->reg_host.reserve(offsetof(RegHost, pts) + (size_t)N * (7 * sizeof(float) + sizeof(int32_t))))) // (every earlier call has been waited for)
+    return rc;
+  uint64_t *keys = ws->reg_keys.as<uint64_t>();
+  uint32_t *payload = ws->reg_payload.as<uint32_t>();
+  double2 *pairs = ws->reg_pairs.as<double2>();
+  char *tiles = ws->reg_tiles.as<char>();
+  double *tile_sums = reinterpret_cast<double *>(tiles);
+  double *tile_offs = reinterpret_cast<double *>(tiles + sums_bytes);
+  RegTileMin *tile_min = reinterpret_cast<RegTileMin *>(tiles + sums_bytes + offs_bytes);
+  int *counters = reinterpret_cast<int *>(tiles + sums_bytes + offs_bytes + min_bytes);
+  RegHost *h = ws->reg_host.as<RegHost>();
+  hipStream_t s = ws->stream;
+
+  SAGE_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(int), s));
+  const int half_P = P / 2, half_blocks = (half_P + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(reg_pair_kernel, dim3(half_blocks), dim3(kBlock), 0, s, src_dev, dst_dev, noise_bounds_dev, N, n_pairs, half_P,
+                     std::sqrt(p->cbar2), keys, payload, pairs, counters);
+  hipLaunchKernelGGL(sort_tile, dim3(P / tile), dim3(kBlock), 0, s, keys, payload, 2, tile);
+  const int quarter_P = P / 4, quarter_blocks = (quarter_P + kBlock - 1) / kBlock;
+  for (int k = 2 * tile; k <= P; k <<= 1)
+  {
+    // the distances k / 2 .. tile across tiles: an odd one out first, then two per launch; the rest on the tiles in LDS
+    int j = k >> 1, n_global = 0;
+    for (int q = j; q >= tile; q >>= 1)
+      ++n_global;
+    if (n_global & 1)
+    {
+      hipLaunchKernelGGL(reg_sort_stage_kernel, dim3(half_blocks), dim3(kBlock), 0, s, keys, payload, k, j, half_P);
+      j >>= 1;
+    }
+    for (; j >= 2 * tile; j >>= 2)
+      hipLaunchKernelGGL(reg_sort_stage2_kernel, dim3(quarter_blocks), dim3(kBlock), 0, s, keys, payload, k, j, quarter_P);
+    hipLaunchKernelGGL(sort_tile, dim3(P / tile), dim3(kBlock), 0, s, keys, payload, k, k);
+  }
+  hipLaunchKernelGGL(reg_tile_sums_kernel, dim3(n_tiles), dim3(kBlock), 0, s, payload, pairs, tile_sums);
+  hipLaunchKernelGGL(reg_tile_offsets_kernel, dim3(1), dim3(kBlock), 0, s, tile_sums, tile_offs, n_tiles);
+  hipLaunchKernelGGL(reg_cost_kernel, dim3(n_tiles), dim3(kBlock), 0, s, payload, pairs, tile_offs, n_tiles, tile_min);
+  hipLaunchKernelGGL(reg_count_kernel, dim3((n_pairs + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pairs, n_pairs, tile_min, n_tiles,
+                     counters);
+  const unsigned epoch = ws_ticket_next(ws);
+  hipLaunchKernelGGL(reg_publish_kernel, dim3(1), dim3(kBlock), 0, s, src_dev, dst_dev, noise_bounds_dev, N, n_pairs, tile_min, n_tiles,
+                     counters, h, &ws->hs()->ticket, epoch);
+  SAGE_HIP(hipGetLastError());
+  if ((rc = ws_ticket_await(ws, epoch)))
+    return rc;
+
+  res->n_pairs = h->n_pairs;
+  res->n_degenerate_pairs = h->n_degenerate;
+  if (!h->vote_valid)
+    return SAGE_OK; // (valid = 0: no pair was left in the vote)
+  const double scale = h->scale, scale_cost = h->scale_cost;
+  const int n_scale_inliers = h->n_scale_inliers, n_degenerate = h->n_degenerate;
+  int32_t *inl = reinterpret_cast<int32_t *>(h->pts + 7 * (size_t)N); // (pinned: the source of the copy below)
+  if ((rc = sage_registration_finish(h->pts, h->pts + 3 * (size_t)N, h->pts + 6 * (size_t)N, N, scale, p, res, inl, nullptr)))
+    return rc;
+  res->n_pairs = n_pairs;
+  res->n_degenerate_pairs = n_degenerate;
+  res->n_scale_inlier_pairs = n_scale_inliers;
+  res->scale_cost = scale_cost;
+  if (inliers_host)
+    std::memcpy(inliers_host, inl, (size_t)res->n_inliers * sizeof(int32_t));
+  if (inliers_dev && res->n_inliers > 0)
+  {
+    SAGE_HIP(hipMemcpyAsync(inliers_dev, inl, (size_t)res->n_inliers * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if ((rc = ws_ticket_wait(ws)))
+      return rc;
+  }
+  return SAGE_OK;
+}
+
+extern "C" int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const int64_t *raw_matched_loc1d_1,
+                                 const float *dpts0, const float *homo0, float depth_divisor0, const float *dpt_map_1,
+                                 const SageCamera *cam, int K, int W, float noise_multiplier, int noise_from, float *pts0, float *pts1,
+                                 float *noise_bounds, float *homo1, float *dpts1, int32_t *kept, int *M_host,
+                                 float *mean_noise_depth_host)
+{
+  if (!ws || !cyc_inlier_flags || !raw_matched_loc1d_1 || !dpts0 || !homo0 || !dpt_map_1 || !cam || !pts0 || !pts1 || !noise_bounds ||
+      !homo1 || !dpts1 || !kept || !M_host || K < 1 || W < 1 || !(cam->fx > 0) || !(cam->fy > 0) || !std::isfinite(cam->fx) ||
+      !std::isfinite(cam->fy) || (noise_from != 0 && noise_from != 1))
+    return SAGE_E_INVALID;
+  int rc;
+  if ((rc = ws->reg_host.reserve(offsetof(RegHost, pts) + sizeof(float))))
+    return rc;
+  MatchPointsParams P;
+  P.flags = cyc_inlier_flags; P.loc1 = raw_matched_loc1d_1; P.dpts0 = dpts0; P.homo0 = homo0; P.dpt_map_1 = dpt_map_1;
+  P.divisor0 = depth_divisor0; P.cx = cam->cx; P.cy = cam->cy; P.fx = cam->fx; P.fy = cam->fy; P.Wf = (float)W;
+  P.focal = (float)((cam->fx + cam->fy) / 2.0); // float focal_length = (fx + fy) / 2.0
+  P.mult = noise_multiplier;
+  P.HW = (long long)cam->w * (long long)cam->h;
+  P.K = K; P.noise_from = noise_from;
+  P.pts0 = pts0; P.pts1 = pts1; P.noise_bounds = noise_bounds; P.homo1 = homo1; P.dpts1 = dpts1; P.kept = kept;
+  RegHost *h = ws->reg_host.as<RegHost>();
+  const unsigned epoch = ws_ticket_next(ws);
+  hipLaunchKernelGGL(reg_match_points_kernel, dim3(1), dim3(kBlock), 0, ws->stream, P, h, &ws->hs()->ticket, epoch);
+  SAGE_HIP(hipGetLastError());
+  if ((rc = ws_ticket_await(ws, epoch)))
+    return rc;
+  *M_host = h->M;
+  if (mean_noise_depth_host)
+    *mean_noise_depth_host = h->mean_depth;
+  return SAGE_OK;
+}

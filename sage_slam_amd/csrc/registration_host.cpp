@@ -1,0 +1,353 @@
+// registration_host.cpp -- (no HIP) the host side of robust registration (include/sage_ba.h): sage_tls_estimate and
+// sage_registration_finish.  teaser::RobustRegistrationSolver::solve for the chain graph without inlier selection
+// (thirdparty/TEASER-plusplus/teaser/src/registration.cc:586-690), from the scale on:
+//   the chain TIMs i -> i + 1 (the last one wraps to 0), their bounds nb_leaf + nb_root, both dst side and bounds over scale
+//   the GNC's scalar bound: noise_bound * (2 / scale) (:648-650), squared, < 1e-16 -> 1e-2 (:1022-1025)
+//   GNC-TLS with per-TIM bounds as written (:990-1101): svdRot with the weights, squared residuals, at iteration 0
+//     mu = 1 / (2 max / bound^2 - 1) and the exit at mu <= 0, the closed-form weights, the cost of the PREVIOUS weights, the
+//     exit at |cost - previous| < threshold; the mask is weight >= 0.5
+//   the translation: per axis one scalar vote (ScalarTLSEstimator::estimate, :21-88) over dst - scale R src with the bounds
+//     nb sqrt(cbar2) (:361-388), and the AND of the three masks
+// All in fp64, sums sequential in the reference's order.  svdRot's 3x3 SVD is a one-sided Jacobi here (Eigen's JacobiSVD
+// there): V diag(1, 1, det U det V) U^T is the same matrix whenever H has rank >= 2; at rank 1 (N = 2: the two chain TIMs
+// are antiparallel) the rotation about the one direction is open in both, and each picks its own.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <limits>
+#include <utility>
+#include <vector>
+
+#include "sage_ba.h"
+
+namespace
+{
+struct Mat3
+{
+  double m[3][3];
+};
+
+inline void cross3(const double *a, const double *b, double *c)
+{
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+inline double det3(const Mat3 &A)
+{
+  return A.m[0][0] * (A.m[1][1] * A.m[2][2] - A.m[1][2] * A.m[2][1]) - A.m[0][1] * (A.m[1][0] * A.m[2][2] - A.m[1][2] * A.m[2][0]) +
+         A.m[0][2] * (A.m[1][0] * A.m[2][1] - A.m[1][1] * A.m[2][0]);
+}
+
+// H = U S V^T by one-sided Jacobi on the columns of A = H (A V' = U S): columns ordered by descending norm; U's columns of a
+// vanishing singular value are completed to a right-handed frame (det U = +1 whenever a column is completed)
+void svd3(const Mat3 &H, Mat3 &U, Mat3 &V)
+{
+  double A[3][3], Vm[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      A[r][c] = H.m[r][c];
+  for (int sweep = 0; sweep < 60; ++sweep)
+  {
+    double off = 0.0;
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q)
+      {
+        double alpha = 0, beta = 0, gamma = 0;
+        for (int r = 0; r < 3; ++r)
+        {
+          alpha += A[r][p] * A[r][p];
+          beta += A[r][q] * A[r][q];
+          gamma += A[r][p] * A[r][q];
+        }
+        if (gamma == 0.0 || std::fabs(gamma) <= 1e-300)
+          continue;
+        off = std::max(off, std::fabs(gamma) / std::sqrt(alpha * beta));
+        const double zeta = (beta - alpha) / (2.0 * gamma);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+        for (int r = 0; r < 3; ++r)
+        {
+          const double ap = A[r][p], aq = A[r][q];
+          A[r][p] = c * ap - s * aq;
+          A[r][q] = s * ap + c * aq;
+          const double vp = Vm[r][p], vq = Vm[r][q];
+          Vm[r][p] = c * vp - s * vq;
+          Vm[r][q] = s * vp + c * vq;
+        }
+      }
+    if (!(off > 1e-16)) // (also leaves on a NaN)
+      break;
+  }
+  double sv[3];
+  int order[3] = {0, 1, 2};
+  for (int c = 0; c < 3; ++c)
+    sv[c] = std::sqrt(A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c]);
+  std::stable_sort(order, order + 3, [&](int a, int b) { return sv[a] > sv[b]; });
+  double u[3][3]; // u[k]: the k-th left vector
+  const double tiny = sv[order[0]] * 1e-13;
+  int rank = 0;
+  for (int k = 0; k < 3; ++k)
+  {
+    const int c = order[k];
+    for (int r = 0; r < 3; ++r)
+      V.m[r][k] = Vm[r][c];
+    if (sv[c] > tiny && sv[c] > 0.0 && rank == k)
+    {
+      for (int r = 0; r < 3; ++r)
+        u[k][r] = A[r][c] / sv[c];
+      rank = k + 1;
+    }
+  }
+  if (rank == 0)
+  {
+    u[0][0] = 1; u[0][1] = 0; u[0][2] = 0;
+    u[1][0] = 0; u[1][1] = 1; u[1][2] = 0;
+  }
+  else if (rank == 1)
+  {
+    // any unit vector perpendicular to u[0]: Gram-Schmidt on the axis u[0] is least aligned with
+    int ax = 0;
+    for (int r = 1; r < 3; ++r)
+      if (std::fabs(u[0][r]) < std::fabs(u[0][ax]))
+        ax = r;
+    double e[3] = {0, 0, 0};
+    e[ax] = 1.0;
+    const double d = u[0][ax];
+    double n = 0;
+    for (int r = 0; r < 3; ++r)
+    {
+      u[1][r] = e[r] - d * u[0][r];
+      n += u[1][r] * u[1][r];
+    }
+    n = std::sqrt(n);
+    for (int r = 0; r < 3; ++r)
+      u[1][r] /= n;
+  }
+  if (rank < 3)
+    cross3(u[0], u[1], u[2]);
+  for (int k = 0; k < 3; ++k)
+    for (int r = 0; r < 3; ++r)
+      U.m[r][k] = u[k][r];
+}
+
+// utils.h:121-136: H = X diag(W) Y^T, R = V U^T with V's last column negated when det U det V < 0
+Mat3 svd_rot(const std::vector<double> &X, const std::vector<double> &Y, const std::vector<double> &W, int n)
+{
+  Mat3 H;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+    {
+      double s = 0.0;
+      for (int i = 0; i < n; ++i)
+        s += (X[3 * i + r] * W[i]) * Y[3 * i + c];
+      H.m[r][c] = s;
+    }
+  Mat3 U, V;
+  svd3(H, U, V);
+  if (det3(U) * det3(V) < 0)
+    for (int r = 0; r < 3; ++r)
+      V.m[r][2] = -V.m[r][2];
+  Mat3 R;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      R.m[r][c] = V.m[r][0] * U.m[c][0] + V.m[r][1] * U.m[c][1] + V.m[r][2] * U.m[c][2];
+  return R;
+}
+
+bool params_ok(const SageRegistrationParams *p)
+{
+  return p && std::isfinite(p->noise_bound) && p->noise_bound > 0 && std::isfinite(p->cbar2) && p->cbar2 > 0 &&
+         p->rotation_max_iterations >= 0 && std::isfinite(p->rotation_cost_threshold) && std::isfinite(p->rotation_gnc_factor) &&
+         p->rotation_gnc_factor > 1 && p->rotation_tim_graph >= SAGE_REG_CHAIN && p->rotation_tim_graph <= SAGE_REG_COMPLETE &&
+         p->inlier_selection_mode >= SAGE_REG_SELECT_PMC_EXACT && p->inlier_selection_mode <= SAGE_REG_SELECT_NONE &&
+         p->rotation_algorithm >= SAGE_REG_GNC_TLS && p->rotation_algorithm <= SAGE_REG_FGR;
+}
+} // namespace
+
+// SAGE_OK, SAGE_E_INVALID or SAGE_E_UNSUPPORTED for a parameter set (shared with registration.hip: runtime_internal.h)
+int registration_check_params(const SageRegistrationParams *p)
+{
+  if (!params_ok(p))
+    return SAGE_E_INVALID;
+  if (p->rotation_tim_graph != SAGE_REG_CHAIN || p->inlier_selection_mode != SAGE_REG_SELECT_NONE ||
+      p->rotation_algorithm != SAGE_REG_GNC_TLS)
+    return SAGE_E_UNSUPPORTED;
+  return SAGE_OK;
+}
+
+extern "C" int sage_tls_estimate(const double *X, const double *ranges, int n, double *estimate, uint8_t *inliers)
+{
+  if (!X || !ranges || n < 1)
+    return SAGE_E_INVALID;
+  std::vector<std::pair<double, int>> h;
+  h.reserve(2 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+  {
+    h.push_back(std::make_pair(X[i] - ranges[i], i + 1));
+    h.push_back(std::make_pair(X[i] + ranges[i], -i - 1));
+  }
+  // (std::sort there: the order of equal values is open; stable here.  The comparison sees the values alone, as there)
+  std::stable_sort(h.begin(), h.end(), [](const std::pair<double, int> &a, const std::pair<double, int> &b) { return a.first < b.first; });
+  double ranges_inverse_sum = 0.0;
+  for (int i = 0; i < n; ++i)
+    ranges_inverse_sum += ranges[i];
+  double dot_X_weights = 0, dot_weights_consensus = 0, sum_xi = 0, sum_xi_square = 0;
+  int consensus_set_cardinal = 0;
+  double best_cost = std::numeric_limits<double>::quiet_NaN(), best_x = std::numeric_limits<double>::quiet_NaN();
+  bool have = false;
+  for (size_t k = 0; k < h.size(); ++k)
+  {
+    const int idx = std::abs(h[k].second) - 1;
+    const int epsilon = h[k].second > 0 ? 1 : -1;
+    const double weight = 1.0 / (ranges[idx] * ranges[idx]);
+    consensus_set_cardinal += epsilon;
+    dot_weights_consensus += epsilon * weight;
+    dot_X_weights += epsilon * weight * X[idx];
+    ranges_inverse_sum -= epsilon * ranges[idx];
+    sum_xi += epsilon * X[idx];
+    sum_xi_square += epsilon * X[idx] * X[idx];
+    const double x_hat = dot_X_weights / dot_weights_consensus;
+    const double residual = consensus_set_cardinal * x_hat * x_hat + sum_xi_square - 2 * sum_xi * x_hat;
+    const double cost = residual + ranges_inverse_sum;
+    // minCoeff: the first smallest; a NaN never wins (all NaN: the estimate is NaN)
+    if (cost == cost && (!have || cost < best_cost))
+    {
+      best_cost = cost;
+      best_x = x_hat;
+      have = true;
+    }
+  }
+  if (estimate)
+    *estimate = best_x;
+  if (inliers)
+    for (int i = 0; i < n; ++i)
+      inliers[i] = std::fabs(X[i] - best_x) <= ranges[i] ? 1 : 0;
+  return SAGE_OK;
+}
+
+extern "C" int sage_registration_finish(const float *src_f, const float *dst_f, const float *nb_f, int N, double scale,
+                                        const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                                        uint8_t *rotation_mask)
+{
+  if (!src_f || !dst_f || !nb_f || !res || N < 2 || N > SAGE_REG_MAX_POINTS)
+    return SAGE_E_INVALID;
+  if (int rc = registration_check_params(p))
+    return rc;
+  const int n = N;
+  std::vector<double> src(3 * (size_t)n), dst(3 * (size_t)n), nb(n);
+  for (int i = 0; i < 3 * n; ++i)
+  {
+    src[i] = (double)src_f[i];
+    dst[i] = (double)dst_f[i];
+  }
+  for (int i = 0; i < n; ++i)
+    nb[i] = (double)nb_f[i];
+
+  // the chain TIMs, scale removed from the dst side (pruned_dst_tims_ *= 1 / scale)
+  const double inv_scale = 1 / scale;
+  std::vector<double> ts(3 * (size_t)n), td(3 * (size_t)n), tb(n), bsq(n);
+  for (int i = 0; i < n; ++i)
+  {
+    const int leaf = i != n - 1 ? i + 1 : 0;
+    for (int c = 0; c < 3; ++c)
+    {
+      ts[3 * i + c] = src[3 * leaf + c] - src[3 * i + c];
+      td[3 * i + c] = (dst[3 * leaf + c] - dst[3 * i + c]) * inv_scale;
+    }
+    tb[i] = (nb[leaf] + nb[i]) * inv_scale;
+    bsq[i] = tb[i] * tb[i];
+  }
+  const double gnc_bound = p->noise_bound * (2 / scale);
+  double noise_bound_sq = std::pow(gnc_bound, 2);
+  if (noise_bound_sq < 1e-16)
+    noise_bound_sq = 1e-2;
+
+  std::vector<double> weights(n, 1.0), residuals_sq(n);
+  Mat3 R = {{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}};
+  double mu = 1, prev_cost = std::numeric_limits<double>::infinity();
+  int it = 0;
+  for (; it < p->rotation_max_iterations; ++it)
+  {
+    R = svd_rot(ts, td, weights, n);
+    for (int j = 0; j < n; ++j)
+    {
+      double s = 0.0;
+      for (int r = 0; r < 3; ++r)
+      {
+        const double d = td[3 * j + r] - (R.m[r][0] * ts[3 * j + 0] + R.m[r][1] * ts[3 * j + 1] + R.m[r][2] * ts[3 * j + 2]);
+        s += d * d;
+      }
+      residuals_sq[j] = s;
+    }
+    if (it == 0)
+    {
+      const double max_residual = *std::max_element(residuals_sq.begin(), residuals_sq.end());
+      mu = 1 / (2 * max_residual / noise_bound_sq - 1);
+      if (mu <= 0)
+        break;
+    }
+    double cost = 0;
+    for (int j = 0; j < n; ++j)
+    {
+      const double th1 = (mu + 1) / mu * bsq[j], th2 = mu / (mu + 1) * bsq[j];
+      cost += weights[j] * residuals_sq[j];
+      if (residuals_sq[j] >= th1)
+        weights[j] = 0;
+      else if (residuals_sq[j] <= th2)
+        weights[j] = 1;
+      else
+        weights[j] = std::sqrt(bsq[j] * mu * (mu + 1) / residuals_sq[j]) - mu;
+    }
+    const double cost_diff = std::fabs(cost - prev_cost);
+    mu = mu * p->rotation_gnc_factor;
+    prev_cost = cost;
+    if (cost_diff < p->rotation_cost_threshold)
+      break;
+  }
+  int n_rot = 0;
+  for (int i = 0; i < n; ++i)
+  {
+    const uint8_t in = weights[i] >= 0.5 ? 1 : 0;
+    n_rot += in;
+    if (rotation_mask)
+      rotation_mask[i] = in;
+  }
+
+  // the translation: dst - scale R src per axis
+  std::vector<double> raw(n), alphas(n);
+  std::vector<uint8_t> mask(n, 1), axis_mask(n);
+  const double sq = std::sqrt(p->cbar2);
+  for (int i = 0; i < n; ++i)
+    alphas[i] = nb[i] * sq;
+  Mat3 sR;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      sR.m[r][c] = scale * R.m[r][c];
+  for (int r = 0; r < 3; ++r)
+  {
+    for (int i = 0; i < n; ++i)
+      raw[i] = dst[3 * i + r] - (sR.m[r][0] * src[3 * i + 0] + sR.m[r][1] * src[3 * i + 1] + sR.m[r][2] * src[3 * i + 2]);
+    sage_tls_estimate(raw.data(), alphas.data(), n, &res->t[r], axis_mask.data());
+    for (int i = 0; i < n; ++i)
+      mask[i] = mask[i] & axis_mask[i];
+  }
+  int n_in = 0;
+  for (int i = 0; i < n; ++i)
+    if (mask[i])
+    {
+      if (inliers_host)
+        inliers_host[n_in] = i;
+      ++n_in;
+    }
+  res->valid = 1;
+  res->scale = scale;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      res->R[3 * r + c] = R.m[r][c];
+  res->n_inliers = n_in;
+  res->rotation_iterations = it;
+  res->n_rotation_inliers = n_rot;
+  return SAGE_OK;
+}

@@ -8,6 +8,9 @@
 //   bow.hip             the loop detector's bag of words (sage_vocabulary_*, sage_bow_transform): the vocabulary's device
 //                       layout, the tree walk, the compaction of the words reached, the host finish
 //   bow_database.cpp    (no HIP) the L1 score of two bag-of-words vectors and the inverted-file database
+//   registration.hip    robust registration of keypoint matches (sage_robust_registration, sage_match_points): the pair
+//                       kernel, the endpoint sort, the scan fused with the vote's cost and argmin, the hand-over
+//   registration_host.cpp  (no HIP) the scalar TLS vote and the finish of the solve: chain TIMs, GNC-TLS rotation, translation
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
 //   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
@@ -207,6 +210,12 @@ struct SageWorkspace
   DevBuf bow_hit;
   PinnedBuf bow_host;
   bool bow_hit_zero = false; // the last call's compact kernel has run: every flag is zero again
+  // robust registration (sage_robust_registration, sage_match_points: registration.hip): the endpoints' keys and payloads [P],
+  // the pairs' measurements (X, r) [pairs], the scan's per-tile sums, offsets and minima with the two counters, and the
+  // pinned record the last kernel publishes (RegHost; also where sage_match_points leaves its count and mean).  All grow
+  // with N and go with the workspace
+  DevBuf reg_keys, reg_payload, reg_pairs, reg_tiles;
+  PinnedBuf reg_host;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }
@@ -232,6 +241,9 @@ int track_reproj_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, fl
 int track_match_geom_enqueue(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *stats, const float *R,
                              const float *t, const float *sampled_dpts0, const float *matched_dpts1, const float *homo0,
                              const float *matched_homo1, float scale0, float loss_param, float weight, int N);
+
+// registration_host.cpp: SAGE_OK, SAGE_E_INVALID or SAGE_E_UNSUPPORTED for a parameter set
+int registration_check_params(const SageRegistrationParams *p);
 
 // instantiated (CS, FS) combinations of the factor kernels
 static inline bool supported(int CS, int FS)

@@ -613,3 +613,58 @@ def make_bow_problem(H: int, W: int, C: int, seed: int = 0, kind: str = "iid", v
     mask[8:H - 8, 8:W - 8] = True
     loc1d = np.nonzero(mask.reshape(-1))[0].astype(np.int64)
     return dict(desc=np.ascontiguousarray(desc, F32), mask=mask, loc1d=loc1d, M=int(loc1d.size), P=P, H=H, W=W, C=C, kind=kind)
+
+
+REG_VARIANTS = ("plain", "all_outliers", "noise_free", "coincident_dst", "coincident_src", "clamp")
+
+
+def registration_params(noise_bound: float) -> dict:
+    """The reference's shipped solver parameters (configs/slam_run.flags:76-85) around a scalar ``noise_bound``"""
+    return dict(noise_bound=float(noise_bound), cbar2=1.0, rotation_max_iterations=20, rotation_cost_threshold=1e-4,
+                rotation_gnc_factor=1.4, rotation_tim_graph=0, inlier_selection_mode=3, rotation_algorithm=0)
+
+
+def make_registration_problem(N: int, seed: int = 0, outlier_rate: float = 0.3, noise: float = 0.3, variant: str = "plain") -> dict:
+    """Inputs of ``sage_robust_registration`` as ``CameraTracker::FeatureMatchingGeo`` builds them: ``src`` [N, 3] are points
+    d * (x, y, 1) of a camera with focal length 200 (depths 0.5 .. 3, |x|, |y| <= 0.5), ``dst`` = s R src + t plus, per axis,
+    uniform noise of ``noise`` times the point's bound; ``noise_bounds`` [N] = max(2 * dst_z / 200, 5e-4) in fp32; a share
+    ``outlier_rate`` of the dst points is replaced by points drawn like src.  ``variant``: "plain"; "all_outliers" (every dst
+    point replaced); "noise_free" (no noise, no outliers: the GNC leaves at iteration 0); "coincident_dst" (every 8th dst
+    point repeats its predecessor: pairs with X = 0); "coincident_src" (every 8th src point repeats its predecessor: pairs
+    with v1 = 0); "clamp" (depths 0.01 .. 0.04: every bound sits at the 5e-4 clamp).
+    -> dict(src, dst, noise_bounds (float32), params (``registration_params``), scale, R, t (the plant), outlier [N] bool).
+    Deterministic per (N, seed, outlier_rate, noise, variant)."""
+    assert variant in REG_VARIANTS and N >= 2
+    rng = np.random.default_rng([seed, N, REG_VARIANTS.index(variant)])
+    mult, focal = 2.0, 200.0
+    dlo, dhi = (0.01, 0.04) if variant == "clamp" else (0.5, 3.0)
+
+    def cloud(n):
+        d = rng.uniform(dlo, dhi, n)
+        return np.stack([d * rng.uniform(-0.5, 0.5, n), d * rng.uniform(-0.5, 0.5, n), d], 1)
+
+    src = cloud(N)
+    s = float(rng.uniform(0.7, 1.4))
+    R = so3_exp(rng.normal(0.0, 0.15, 3))
+    t = rng.normal(0.0, 0.05, 3) * (0.02 if variant == "clamp" else 1.0)
+    if variant == "coincident_src":
+        src[7::8] = src[6::8][:len(src[7::8])]
+    dst = s * src @ R.T + t
+    if variant == "noise_free":
+        outlier_rate, noise = 0.0, 0.0
+    if variant == "all_outliers":
+        outlier_rate = 1.0
+    n_out = int(round(outlier_rate * N))
+    outlier = np.zeros(N, bool)
+    outlier[rng.permutation(N)[:n_out]] = True
+    repl = cloud(N)
+    dst[outlier] = repl[outlier]
+    nb = np.maximum((np.float32(mult) * dst[:, 2].astype(F32)) / np.float32(focal), np.float32(5e-4)).astype(F32)
+    dst = dst + noise * nb[:, None].astype(np.float64) * rng.uniform(-1.0, 1.0, (N, 3))
+    if variant == "coincident_dst":
+        dst[7::8] = dst[6::8][:len(dst[7::8])]
+    src32, dst32 = np.ascontiguousarray(src, F32), np.ascontiguousarray(dst, F32)
+    nb = np.maximum((np.float32(mult) * dst32[:, 2]) / np.float32(focal), np.float32(5e-4)).astype(F32)
+    noise_bound = float(np.float32(mult) * np.float32(dst32[:, 2].astype(np.float64).mean()) / np.float32(focal))
+    return dict(src=src32, dst=dst32, noise_bounds=nb, params=registration_params(noise_bound), scale=s, R=R, t=t,
+                outlier=outlier, N=N, variant=variant)
