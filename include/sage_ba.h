@@ -577,6 +577,73 @@ int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const 
                       float noise_multiplier, int noise_from, float *pts0, float *pts1, float *noise_bounds, float *homo1,
                       float *dpts1, int32_t *kept, int *M_host, float *mean_noise_depth_host);
 
+/* ---- the loop detector's candidates: one query keyframe against B candidates in one call ----
+ * LoopDetector::DetectLoop (core/system/loop_detector.cpp:143-163) and DetectLocalLoop (:282-319) run
+ * CameraTracker::MatchGeoCheck on the query keyframe against up to loop_max_candidates = 20 (loop_local_active_window = 9)
+ * candidates one after the other: "pre check ... for computation speedup".
+ *
+ * sage_cycle_match_batch: row b of raw_matched_loc1d, cyc_matched_loc1d, inlier_flags (device, [B][K]) and n_inliers_host
+ * (HOST, [B]) is what sage_cycle_match(ws, desc_query_dev, desc_cand_dev[b], kp_loc1d_dev[b], ...) writes, bit for bit, for every
+ * value of pixel_slices.  desc_cand_dev and kp_loc1d_dev are HOST arrays of B device pointers ([C,H,W] maps; [K] pixels of
+ * the query map: per candidate the keypoint set is its own -- camera_tracker.cpp:589-608 shuffles the query's valid locations
+ * with the candidate's id as seed; that shuffle stays with the caller, sage_shuffle_indices).  The grid runs over (pixel
+ * slice, group of 8 queries, candidate); a slice is a contiguous pixel range of the target map and the winner over the
+ * slices is the maximum under one total order (larger response, then smaller pixel), so the split never shows in the result.
+ * pixel_slices 0: chosen from the device's CU count, as many as it takes to put two workgroups on every CU and none shorter
+ * than 512 pixels; >= 1: forced (clamped to H*W and to 8192; the slices' winners take 16 B K slices bytes of the workspace).
+ * Three launches whatever B; the counts reach the host through pinned memory and the workspace's ticket: one wait, no copy.
+ * SAGE_E_INVALID, before anything touches the device, for: NULL ws; B < 0 or B > SAGE_MATCH_MAX_BATCH; K < 0 (or K > 524 280);
+ * C < 1 or C > 1024; H or W < 1 (or H*W >= 2^31); pixel_slices < 0; NULL n_inliers_host with B > 0; with B > 0 and K > 0 a
+ * NULL map, output, pointer array or entry of a pointer array.  B = 0 or K = 0: SAGE_OK, the counts zeroed, nothing launched. */
+#define SAGE_MATCH_MAX_BATCH 32
+int sage_cycle_match_batch(SageWorkspace *ws, const float *desc_query_dev, const float *const *desc_cand_dev,
+                           const int64_t *const *kp_loc1d_dev, int B, int K, int C, int H, int W, float cyc_thresh,
+                           int pixel_slices, int64_t *raw_matched_loc1d, int64_t *cyc_matched_loc1d, int32_t *inlier_flags,
+                           int32_t *n_inliers_host);
+/* the number of pixel slices the workspace's last sage_cycle_match_batch ran with (0: none yet, or NULL ws) */
+int sage_cycle_match_batch_slices(const SageWorkspace *ws);
+
+/* sage_loop_precheck: the detector's loop body up to the ratio test (MatchGeoCheck -> the first FeatureMatchingGeo overload,
+ * camera_tracker.cpp:575-768) for all B candidates.  A host composition, no arithmetic of its own: one
+ * sage_cycle_match_batch (pixel_slices 0); then, in candidate order, every candidate that can still pass goes through
+ * sage_match_points (depth_divisor0 = query_depth_divisor, noise_from 1, scratch outputs of the workspace) and
+ * sage_robust_registration (src = pts0, dst = pts1; p->noise_bound is NOT read: it is replaced by
+ * (noise_multiplier * mean_noise_depth) / ((cam->fx + cam->fy) / 2) evaluated in fp32 and widened).  Per candidate the fields
+ * of the result equal those three calls on the same inputs.
+ * The prune: a candidate with (float)n_cycle / (float)K < min_desc_inlier_ratio gets registered = 0, both ratios 0 and no
+ * further launch.  That is exact: the reference's desc_match_inlier_ratio is |translation inliers| / K and the translation
+ * inliers are among the cycle-consistent matches, so the detector's `continue` (loop_detector.cpp:159, :314) is taken either
+ * way; pass max(cfg.min_desc_inlier_ratio, base_desc_ratio).  n_cycle = 0 is the reference's early return (:642-652) and
+ * skips the solve whatever the threshold; so do n_matched < 2 and a bound that is not positive and finite (NaN depths).
+ * inlier_kp_dev [B][K]: row b holds, in its first reg.n_inliers entries, kept[inliers[i]] ascending -- positions among the K
+ * keypoints, what TrackFrame(..., match_geom_pre_checked = true) gathers homo and depths with, next to row b of
+ * raw_matched_loc1d.  raw_matched_loc1d, inlier_flags: device [B][K], as sage_cycle_match_batch writes them.
+ * SAGE_E_INVALID (nothing is launched) as for sage_cycle_match_batch, and for NULL cands, cam, p or results, a NULL member of a
+ * candidate, fx / fy not positive and finite, K > SAGE_REG_MAX_POINTS; the registration's parameter checks answer as in
+ * sage_robust_registration (noise_bound apart).  B = 0 or K = 0: SAGE_OK, the results zeroed.  Waits: one for the batch, two
+ * per survivor, one at the end when any inlier was written. */
+typedef struct SageLoopCandidate /* device pointers */
+{
+  const float *desc_dev;           /* kf->feat_desc [C,H,W] */
+  const float *dpt_map_dev;        /* kf->dpt_map [H*W] */
+  const int64_t *kp_loc1d_dev;     /* [K] query pixels of this candidate's keypoints */
+  const float *kp_dpts0_dev;       /* [K] the query's depths at them */
+  const float *kp_homo0_dev;       /* [K][3] the query's homogeneous coordinates at them */
+} SageLoopCandidate;
+typedef struct SageLoopPrecheckResult /* host */
+{
+  int32_t n_cycle;                 /* cycle-consistent matches */
+  int32_t n_matched;               /* M of sage_match_points (0: pruned) */
+  int32_t registered;              /* 1 when the solve ran */
+  float relative_desc_match_inlier_ratio, desc_match_inlier_ratio; /* camera_tracker.cpp:740-741 */
+  float mean_noise_depth;
+  SageRegistrationResult reg;
+} SageLoopPrecheckResult;
+int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float query_depth_divisor, const SageLoopCandidate *cands,
+                       int B, int K, int C, int H, int W, const SageCamera *cam, float cyc_thresh, float noise_multiplier,
+                       float min_desc_inlier_ratio, const SageRegistrationParams *p, SageLoopPrecheckResult *results,
+                       int64_t *raw_matched_loc1d, int32_t *inlier_flags, int32_t *inlier_kp_dev);
+
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)
  * ===================================================================== */

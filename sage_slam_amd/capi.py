@@ -152,6 +152,7 @@ SYMBOLS = [
     "sage_loop_mg_jac_error_calculate", "sage_loop_mg_error_calculate",
     "sage_tracker_match_geom_jac_error_calculate", "sage_tracker_match_geom_error_calculate", "sage_cycle_match",
     "sage_robust_registration", "sage_tls_estimate", "sage_registration_finish", "sage_match_points",
+    "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck",
 ]
 
 
@@ -1644,6 +1645,99 @@ def match_points(ws: "Workspace", flags, raw_matched_loc1, dpts0, homo0, depth_d
     m = M.value
     return dict(M=m, mean_depth=np.float32(mean.value), pts0=pts0[:m], pts1=pts1[:m], noise_bounds=nb[:m], homo1=homo1[:m],
                 dpts1=dpts1[:m], kept=kept[:m])
+
+
+# --------------------------------------------------------------------------- the loop detector's candidates in one call
+SAGE_MATCH_MAX_BATCH = 32
+
+
+class SageLoopCandidate(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("desc_dev", "dpt_map_dev", "kp_loc1d_dev", "kp_dpts0_dev", "kp_homo0_dev")]
+
+
+class SageLoopPrecheckResult(C.Structure):
+    _fields_ = [("n_cycle", C.c_int32), ("n_matched", C.c_int32), ("registered", C.c_int32),
+                ("relative_desc_match_inlier_ratio", C.c_float), ("desc_match_inlier_ratio", C.c_float),
+                ("mean_noise_depth", C.c_float), ("reg", SageRegistrationResult)]
+
+
+def cycle_match_batch_raw(ws_handle, desc_q, cand_ptrs, kp_ptrs, B, K, Cc, H, W, cyc_thresh, pixel_slices, raw, cyc, flags,
+                          counts_ptr) -> int:
+    """``sage_cycle_match_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_cycle_match_batch
+    f.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int] + [C.c_void_p] * 4
+    return int(f(ws_handle, desc_q, cand_ptrs, kp_ptrs, int(B), int(K), int(Cc), int(H), int(W), float(cyc_thresh),
+                 int(pixel_slices), raw, cyc, flags, counts_ptr))
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * max(len(tensors), 1))(*[int(t.data_ptr()) for t in tensors])
+
+
+def cycle_match_batch(ws, desc_q, desc_cands, kp_locs, H, W, cyc_thresh, pixel_slices: int = 0):
+    """One query map against B candidate maps through ``sage_cycle_match_batch``.  desc_q [C,H,W] and every desc_cands[b]:
+    contiguous cuda float tensors; kp_locs[b]: int64 cuda tensor [K] (candidate b's keypoints, pixels of the query map).
+    -> (raw_matched [B,K], cyc_matched [B,K], flags [B,K] int32, counts [B] numpy int32, the number of pixel slices used);
+    row b is what ``cycle_match(ws, desc_q, desc_cands[b], kp_locs[b], ...)`` returns."""
+    import torch
+    B = len(desc_cands)
+    assert len(kp_locs) == B
+    K = int(kp_locs[0].shape[0]) if B else 0
+    Cc = int(desc_q.shape[0])
+    for d, k in zip(desc_cands, kp_locs):
+        assert d.is_contiguous() and k.is_contiguous() and k.dtype == torch.int64 and int(k.shape[0]) == K and tuple(d.shape) == tuple(desc_q.shape)
+    raw = torch.zeros(max(B, 1), max(K, 1), dtype=torch.int64, device="cuda"); cyc = torch.zeros_like(raw)
+    fl = torch.zeros(max(B, 1), max(K, 1), dtype=torch.int32, device="cuda")
+    counts = np.zeros(max(B, 1), np.int32)
+    _chk(cycle_match_batch_raw(ws.h, dptr(desc_q), _ptr_array(desc_cands), _ptr_array(kp_locs), B, K, Cc, H, W, cyc_thresh,
+                               pixel_slices, dptr(raw), dptr(cyc), dptr(fl), counts.ctypes.data), "sage_cycle_match_batch")
+    f = lib().sage_cycle_match_batch_slices
+    f.argtypes = [C.c_void_p]
+    return raw[:B, :K], cyc[:B, :K], fl[:B, :K], counts[:B], int(f(ws.h))
+
+
+def loop_precheck_raw(ws_handle, desc_q, divisor, cands_ptr, B, K, Cc, H, W, cam_ptr, cyc_thresh, mult, min_ratio, params_ptr,
+                      results_ptr, raw, flags, inlier_kp) -> int:
+    """``sage_loop_precheck`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_loop_precheck
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] + [C.c_float] * 3 + [C.c_void_p] * 5
+    return int(f(ws_handle, desc_q, float(divisor), cands_ptr, int(B), int(K), int(Cc), int(H), int(W), cam_ptr, float(cyc_thresh),
+                 float(mult), float(min_ratio), params_ptr, results_ptr, raw, flags, inlier_kp))
+
+
+def loop_precheck(ws, desc_q, query_depth_divisor, cands, H, W, cam, cyc_thresh, noise_multiplier, min_desc_inlier_ratio,
+                  params=None):
+    """The loop detector's pre-check of B candidates through ``sage_loop_precheck``.  desc_q [C,H,W]; cands: a list of dicts with
+    the contiguous cuda tensors ``desc`` [C,H,W], ``dpt_map`` [H*W], ``kp_loc`` [K] int64, ``kp_dpts0`` [K], ``kp_homo0`` [K,3];
+    cam: anything with fx, fy, cx, cy, w, h; params: a dict, a ``SageRegistrationParams`` or None (noise_bound is not read).
+    -> a list of B dicts: n_cycle, n_matched, registered, the two ratios, mean_noise_depth, ``reg`` (the fields of
+    ``SageRegistrationResult``), ``raw_matched`` [K] int64, ``flags`` [K] int32, ``inlier_kp`` [reg.n_inliers] int32 (cuda)."""
+    import torch
+    B = len(cands)
+    K = int(cands[0]["kp_loc"].shape[0]) if B else 0
+    Cc = int(desc_q.shape[0])
+    arr = (SageLoopCandidate * max(B, 1))()
+    for b, c in enumerate(cands):
+        assert c["kp_loc"].dtype == torch.int64 and int(c["kp_loc"].shape[0]) == K and tuple(c["kp_homo0"].shape) == (K, 3)
+        arr[b] = SageLoopCandidate(*[dptr(c[n]).value for n in ("desc", "dpt_map", "kp_loc", "kp_dpts0", "kp_homo0")])
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    p = params if isinstance(params, SageRegistrationParams) else registration_params(params)
+    res = (SageLoopPrecheckResult * max(B, 1))()
+    raw = torch.zeros(max(B, 1), max(K, 1), dtype=torch.int64, device="cuda")
+    fl = torch.zeros(max(B, 1), max(K, 1), dtype=torch.int32, device="cuda")
+    ikp = torch.zeros(max(B, 1), max(K, 1), dtype=torch.int32, device="cuda")
+    _chk(loop_precheck_raw(ws.h, dptr(desc_q), query_depth_divisor, C.addressof(arr), B, K, Cc, H, W, C.addressof(c), cyc_thresh,
+                           noise_multiplier, min_desc_inlier_ratio, C.addressof(p), C.addressof(res), dptr(raw), dptr(fl), dptr(ikp)),
+         "sage_loop_precheck")
+    out = []
+    for b in range(B):
+        r = res[b]
+        out.append(dict(n_cycle=r.n_cycle, n_matched=r.n_matched, registered=r.registered,
+                        relative_desc_match_inlier_ratio=np.float32(r.relative_desc_match_inlier_ratio),
+                        desc_match_inlier_ratio=np.float32(r.desc_match_inlier_ratio),
+                        mean_noise_depth=np.float32(r.mean_noise_depth), reg=_reg_result(r.reg), raw_matched=raw[b, :K],
+                        flags=fl[b, :K], inlier_kp=ikp[b, :r.reg.n_inliers]))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------

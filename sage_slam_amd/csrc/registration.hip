@@ -750,3 +750,102 @@ extern "C" int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_fl
     *mean_noise_depth_host = h->mean_depth;
   return SAGE_OK;
 }
+
+// ---- the loop detector's pre-check: sage_cycle_match_batch, then per surviving candidate the two calls above ----
+namespace
+{
+__global__ void pre_inlier_keypoints_kernel(const int32_t *__restrict__ kept, const int32_t *inliers /* pinned */, int n,
+                                            int32_t *__restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    out[i] = kept[inliers[i]];
+}
+} // namespace
+
+extern "C" int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float query_depth_divisor,
+                                  const SageLoopCandidate *cands, int B, int K, int C, int H, int W, const SageCamera *cam,
+                                  float cyc_thresh, float noise_multiplier, float min_desc_inlier_ratio,
+                                  const SageRegistrationParams *p, SageLoopPrecheckResult *results, int64_t *raw_matched_loc1d,
+                                  int32_t *inlier_flags, int32_t *inlier_kp_dev)
+{
+  if (!ws || !cands || !cam || !p || !results || B < 0 || B > SAGE_MATCH_MAX_BATCH || K < 0 || K > SAGE_REG_MAX_POINTS || C < 1 ||
+      C > 1024 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffll)
+    return SAGE_E_INVALID;
+  if (B > 0 && K > 0)
+  {
+    if (!desc_query_dev || !raw_matched_loc1d || !inlier_flags || !inlier_kp_dev || !(cam->fx > 0) || !(cam->fy > 0) ||
+        !std::isfinite(cam->fx) || !std::isfinite(cam->fy))
+      return SAGE_E_INVALID;
+    for (int b = 0; b < B; ++b)
+      if (!cands[b].desc_dev || !cands[b].dpt_map_dev || !cands[b].kp_loc1d_dev || !cands[b].kp_dpts0_dev || !cands[b].kp_homo0_dev)
+        return SAGE_E_INVALID;
+  }
+  int rc;
+  SageRegistrationParams pp = *p;
+  pp.noise_bound = 1.0; // (replaced per candidate below: the caller's value is not read)
+  if ((rc = registration_check_params(&pp)))
+    return rc;
+  for (int b = 0; b < B; ++b)
+    std::memset(&results[b], 0, sizeof(results[b]));
+  if (B == 0 || K == 0)
+    return SAGE_OK;
+
+  // scratch: the way back [B][K] | pts0 [K][3] | pts1 [K][3] | homo1 [K][3] | noise bounds [K] | dpts1 [K] | kept [K]
+  const size_t cyc_bytes = (size_t)B * K * sizeof(int64_t);
+  if ((rc = ws->pre_scratch.reserve(cyc_bytes + (size_t)K * (11 * sizeof(float) + sizeof(int32_t)))) ||
+      (rc = ws->reg_host.reserve(offsetof(RegHost, pts) + (size_t)K * (7 * sizeof(float) + sizeof(int32_t))))) // (no solve below moves it)
+    return rc;
+  int64_t *cyc = ws->pre_scratch.as<int64_t>();
+  float *pts0 = reinterpret_cast<float *>(ws->pre_scratch.as<char>() + cyc_bytes);
+  float *pts1 = pts0 + 3 * (size_t)K, *homo1 = pts1 + 3 * (size_t)K, *bounds = homo1 + 3 * (size_t)K, *dpts1 = bounds + K;
+  int32_t *kept = reinterpret_cast<int32_t *>(dpts1 + K);
+
+  const float *desc[SAGE_MATCH_MAX_BATCH];
+  const int64_t *kp[SAGE_MATCH_MAX_BATCH];
+  int32_t n_cycle[SAGE_MATCH_MAX_BATCH];
+  for (int b = 0; b < B; ++b)
+  {
+    desc[b] = cands[b].desc_dev;
+    kp[b] = cands[b].kp_loc1d_dev;
+  }
+  if ((rc = sage_cycle_match_batch(ws, desc_query_dev, desc, kp, B, K, C, H, W, cyc_thresh, 0, raw_matched_loc1d, cyc, inlier_flags,
+                                   n_cycle)))
+    return rc;
+
+  bool gathered = false;
+  for (int b = 0; b < B; ++b)
+  {
+    SageLoopPrecheckResult &r = results[b];
+    r.n_cycle = n_cycle[b];
+    // |translation inliers| <= n_cycle: a candidate below the ratio here is below it after the solve as well
+    if (n_cycle[b] <= 0 || (float)n_cycle[b] / (float)K < min_desc_inlier_ratio)
+      continue;
+    int M = 0;
+    if ((rc = sage_match_points(ws, inlier_flags + (size_t)b * K, raw_matched_loc1d + (size_t)b * K, cands[b].kp_dpts0_dev,
+                                cands[b].kp_homo0_dev, query_depth_divisor, cands[b].dpt_map_dev, cam, K, W, noise_multiplier, 1, pts0,
+                                pts1, bounds, homo1, dpts1, kept, &M, &r.mean_noise_depth)))
+      return rc;
+    r.n_matched = M;
+    const float nb = (noise_multiplier * r.mean_noise_depth) / ((cam->fx + cam->fy) / 2.0f);
+    if (M < 2 || !(nb > 0) || !std::isfinite(nb))
+      continue; // (no solve: one match, or depths the bound cannot be made from)
+    pp.noise_bound = (double)nb;
+    if ((rc = sage_robust_registration(ws, pts0, pts1, bounds, M, &pp, &r.reg, nullptr, nullptr)))
+      return rc;
+    r.registered = 1;
+    r.relative_desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)M;
+    r.desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)K;
+    if (r.reg.n_inliers > 0)
+    {
+      // the inliers are where the solve's finish left them in the pinned record; the next write to them comes behind a later
+      // ticket of this stream
+      const int32_t *inl = reinterpret_cast<const int32_t *>(ws->reg_host.as<RegHost>()->pts + 7 * (size_t)M);
+      hipLaunchKernelGGL(pre_inlier_keypoints_kernel, dim3((r.reg.n_inliers + kBlock - 1) / kBlock), dim3(kBlock), 0, ws->stream, kept,
+                         inl, r.reg.n_inliers, inlier_kp_dev + (size_t)b * K);
+      SAGE_HIP(hipGetLastError());
+      gathered = true;
+    }
+  }
+  return gathered ? ws_ticket_wait(ws) : SAGE_OK;
+}

@@ -9,7 +9,10 @@
 //                       layout, the tree walk, the compaction of the words reached, the host finish
 //   bow_database.cpp    (no HIP) the L1 score of two bag-of-words vectors and the inverted-file database
 //   registration.hip    robust registration of keypoint matches (sage_robust_registration, sage_match_points): the pair
-//                       kernel, the endpoint sort, the scan fused with the vote's cost and argmin, the hand-over
+//                       kernel, the endpoint sort, the scan fused with the vote's cost and argmin, the hand-over; the loop
+//                       detector's pre-check of B candidates (sage_loop_precheck), a host composition
+//   match_batch.hip     one query descriptor map against B candidate maps (sage_cycle_match_batch): the sliced match kernel,
+//                       the merge of the slices' winners, flags and counts
 //   registration_host.cpp  (no HIP) the scalar TLS vote and the finish of the solve: chain TIMs, GNC-TLS rotation, translation
 //   window.hip          a finalized window's accessors, keyframe variables in and out, helpers the window units share
 //   window_eval.hip     evaluating the factors at a variable set: linearize + assembly, error pass (the window's big kernels)
@@ -216,6 +219,14 @@ struct SageWorkspace
   // with N and go with the workspace
   DevBuf reg_keys, reg_payload, reg_pairs, reg_tiles;
   PinnedBuf reg_host;
+  // batched cycle match (sage_cycle_match_batch: match_batch.hip): the slices' (response, pixel) pairs of both passes
+  // [2][B][S][K], the counter of finished workgroups (zero between calls), the pinned counts [SAGE_MATCH_MAX_BATCH]; the
+  // device's CU count (0: not asked yet) and the number of slices of the last call
+  DevBuf mb_part, mb_done;
+  PinnedBuf mb_host;
+  int mb_cus = 0, mb_slices = 0;
+  // loop pre-check (sage_loop_precheck: registration.hip): the way back [B][K], then one candidate's gathered points
+  DevBuf pre_scratch;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }

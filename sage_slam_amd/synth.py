@@ -668,3 +668,74 @@ def make_registration_problem(N: int, seed: int = 0, outlier_rate: float = 0.3, 
     noise_bound = float(np.float32(mult) * np.float32(dst32[:, 2].astype(np.float64).mean()) / np.float32(focal))
     return dict(src=src32, dst=dst32, noise_bounds=nb, params=registration_params(noise_bound), scale=s, R=R, t=t,
                 outlier=outlier, N=N, variant=variant)
+
+
+LOOP_CANDIDATE_KINDS = ("planted", "self", "unrelated")
+
+
+def make_loop_candidates(seed: int, B: int, H: int = 48, W: int = 64, C: int = 16, K: int = 117, kinds=None, n_wrong: int = 8) -> dict:
+    """Inputs of ``sage_cycle_match_batch`` / ``sage_loop_precheck``: one query keyframe and B loop-closure candidates.
+    The query has a descriptor map [C, H, W] (iid normal), a smooth depth map [H*W] and the pixels of a 4-pixel grid 8 pixels
+    inside the border as possible keypoints; the camera has focal length 0.94 W.  Every candidate draws its own K keypoints from
+    that grid (all of them, in raster order, when the grid has exactly K; the reference shuffles the query's valid locations
+    with the candidate's id as seed).  ``kinds[b]`` (default: "planted", "self", "unrelated", "planted", ... in turn):
+      "planted"    the candidate sees the keypoints under its own similarity (s, R, t): each keypoint's descriptor is planted at
+                   the pixel its point projects to (rounded), with that point's depth in the candidate's depth map, in an
+                   otherwise unrelated map; ``n_wrong`` keypoints are planted at a wrong pixel with a wrong depth
+      "self"       the query's own maps
+      "unrelated"  an iid map of half the query's spread and iid depths (two iid maps of ONE distribution are mutual nearest
+                   neighbours for about a third of the keypoints at C = 16, which is where the detector's ratio test sits;
+                   at half the spread about a tenth of the cycles close)
+    -> dict(H, W, C, K, cam, desc_q, dmap_q, depth_divisor (1.0), cands): per candidate dict(kind, desc, dpt_map, kp_loc [K]
+    int64, kp_dpts0 [K], kp_homo0 [K, 3], loc1 [K] (where each keypoint was planted; "self": kp_loc; "unrelated": None),
+    wrong (sorted positions among the K), s, R, t).  Deterministic per argument set."""
+    rng = np.random.default_rng([seed, B, H, W, C, K])
+    fx = fy = 0.9375 * W
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    gy, gx = np.meshgrid(np.arange(8, H - 7, 4), np.arange(8, W - 7, 4), indexing="ij")
+    gx, gy = gx.reshape(-1), gy.reshape(-1)
+    assert 2 <= K <= gx.size and 0 <= n_wrong <= K, (K, gx.size)
+    kinds = list(kinds) if kinds is not None else [("planted", "self", "unrelated", "planted")[b % 4] for b in range(B)]
+    assert len(kinds) == B and all(k in LOOP_CANDIDATE_KINDS for k in kinds)
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    dmap_q = (1.5 + 0.3 * np.sin(xx * (7.0 / W)) + 0.2 * np.cos(yy * (7.0 / H))).astype(F32).reshape(-1)
+    desc_q = rng.normal(0, 1, (C, H, W)).astype(F32)
+    free = np.array([y * W + x for y in range(2, H - 2) for x in range(2, W - 2) if (x % 4 == 1 and y % 4 == 1)], np.int64)
+    cands = []
+    for b in range(B):
+        sel = np.arange(K) if gx.size == K else rng.permutation(gx.size)[:K]
+        xs, ys = gx[sel], gy[sel]
+        kp = (ys * W + xs).astype(np.int64)
+        d0 = dmap_q[kp]
+        homo0 = np.stack([(xs - cx) / fx, (ys - cy) / fy, np.ones(K)], 1).astype(F32)
+        c = dict(kind=kinds[b], kp_loc=kp, kp_dpts0=d0, kp_homo0=homo0, loc1=None, wrong=np.zeros(0, np.int64), s=1.0, R=np.eye(3),
+                 t=np.zeros(3))
+        if kinds[b] == "self":
+            c.update(desc=desc_q.copy(), dpt_map=dmap_q.copy(), loc1=kp.copy())
+        elif kinds[b] == "unrelated":
+            c.update(desc=rng.normal(0, 0.5, (C, H, W)).astype(F32), dpt_map=rng.uniform(1.0, 3.0, H * W).astype(F32))
+        else:
+            s = float(rng.uniform(0.9, 1.25))
+            R = so3_exp(np.clip(rng.normal(0.0, 0.01, 3), -0.015, 0.015))   # (with t: less than the 8 pixels to the border)
+            t = np.clip(rng.normal(0.0, 0.015, 3), -0.02, 0.02)
+            p1 = s * (d0[:, None].astype(np.float64) * homo0) @ R.T + t
+            u1 = np.rint(p1[:, 0] / p1[:, 2] * fx + cx).astype(np.int64)
+            v1 = np.rint(p1[:, 1] / p1[:, 2] * fy + cy).astype(np.int64)
+            assert u1.min() >= 0 and u1.max() < W and v1.min() >= 0 and v1.max() < H
+            wrong = np.sort(rng.permutation(K)[:n_wrong])
+            keep = np.ones(K, bool)
+            keep[wrong] = False
+            pool = np.setdiff1d(free, (v1 * W + u1)[keep])
+            pick = pool[rng.permutation(pool.size)[:n_wrong]]
+            u1[wrong], v1[wrong] = pick % W, pick // W
+            loc1 = v1 * W + u1
+            assert np.unique(loc1).size == K
+            desc = rng.normal(0, 1, (C, H, W)).astype(F32)
+            desc[:, v1, u1] = desc_q[:, ys, xs]
+            dmap = np.full(H * W, 2.0, F32)
+            dmap[loc1] = p1[:, 2].astype(F32)
+            dmap[loc1[wrong]] = rng.uniform(1.0, 3.0, n_wrong).astype(F32)
+            c.update(desc=desc, dpt_map=dmap, loc1=loc1, wrong=wrong, s=s, R=R, t=t)
+        cands.append(c)
+    return dict(H=H, W=W, C=C, K=K, cam=Camera(fx, fy, cx, cy, float(W), float(H)), desc_q=desc_q, dmap_q=dmap_q, depth_divisor=1.0,
+                cands=cands)
