@@ -1017,7 +1017,7 @@ int sage_cycle_match(SageWorkspace *ws, const float *desc0_dev, const float *des
  *   the shuffled list the reference keeps (mapper.cpp:1326-1340) the photometric kernels are 5-7x slower than on the
  *   sorted one.  The window engine (sage_window_finalize) does this internally; callers of the per-edge operators
  *   should sort once per keyframe.  *sorted_host = 0 (outputs = copy of the inputs) when a pixel is listed twice;
- *   SAGE_E_INVALID for a location outside H*W.  Synchronises the stream. */
+ *   SAGE_E_INVALID for a location outside H*W.  n = 0: *sorted_host = 1, the arrays may be NULL.  Synchronises the stream. */
 int sage_sort_locations(SageWorkspace *ws, const int64_t *loc1d_dev, const float *homo_dev, int n, int H, int W,
                         int64_t *loc1d_out_dev, float *homo_out_dev, int *sorted_host);
 int sage_valid_locations(SageWorkspace *ws, const float *mask_dev, const SageCamera *cam, int64_t *loc1d_dev,

@@ -570,9 +570,16 @@ extern "C" int sage_sample_locations(SageWorkspace *ws, const int64_t *valid_loc
 extern "C" int sage_sort_locations(SageWorkspace *ws, const int64_t *loc1d_dev, const float *homo_dev, int n, int H,
                                    int W, int64_t *loc1d_out_dev, float *homo_out_dev, int *sorted_host)
 {
-  if (!ws || !loc1d_dev || !homo_dev || n < 0 || H < 1 || W < 1 || !loc1d_out_dev || !homo_out_dev || !sorted_host ||
-      loc1d_out_dev == loc1d_dev || homo_out_dev == homo_dev)
+  // (an empty list has no arrays: n = 0 is answered "sorted" whatever the pointers are)
+  if (!ws || n < 0 || H < 1 || W < 1 || !sorted_host ||
+      (n > 0 && (!loc1d_dev || !homo_dev || !loc1d_out_dev || !homo_out_dev || loc1d_out_dev == loc1d_dev ||
+                 homo_out_dev == homo_dev)))
     return SAGE_E_INVALID;
+  if (n == 0)
+  {
+    *sorted_host = 1;
+    return SAGE_OK;
+  }
   const int HW = H * W;
   // scratch: [item | status (2 ints) | mark plane]
   const size_t off_status = (sizeof(SortItem) + 15) / 16 * 16, off_mark = off_status + 16;

@@ -15,9 +15,9 @@ def pack_pose(R, t):
 class HostScene:
     """frame 0 (tracked) -> frame 1 (reference keyframe) of a synthetic window, plus NK matched keypoints"""
 
-    def __init__(self, orc, seed=31, NK=160, kp_noise_px=0.4, kp_noise_depth=0.002):
+    def __init__(self, orc, seed=31, NK=160, kp_noise_px=0.4, kp_noise_depth=0.002, H=64, W=80, FS=16, L=4, n_samples=3072):
         self.orc = orc
-        w = synth.make_window(K=2, H=64, W=80, FS=16, CS=32, L=4, n_samples=3072, seed=seed, pose_noise=0.0)
+        w = synth.make_window(K=2, H=H, W=W, FS=FS, CS=32, L=L, n_samples=n_samples, seed=seed, pose_noise=0.0)
         self.w = w
         a, b = w.keyframes[0], w.keyframes[1]
         self.a, self.b = a, b
