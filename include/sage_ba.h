@@ -285,6 +285,23 @@ int sage_track_lm(const SageLmConfig *cfg, int dof, SageTrackLinearizeFn lin, Sa
                   float *pose12, float *scale, float *final_error, int *iters,
                   SageLmTraceEntry *trace, int trace_cap, int *trace_len);
 
+/* B runs of the same policy in lock-step (the loop detector tracks every surviving candidate against the query keyframe:
+ * loop_detector.cpp:165, :321).  sage_track_lm and this call drive ONE definition of the policy (a resumable stepper); per
+ * problem the outputs are those of sage_track_lm with callbacks that return the same values.
+ * A round: every problem that is not done asks for exactly one evaluation -- the linearisation (want_jac 1: AtA dof x dof
+ * row-major at stride 49, Atb at stride 7, error) or the error alone (want_jac 0) at (pose12, scale) -- and `eval` is called
+ * once with all n of them, `problem` ascending.  It is not called for a round without requests; a problem that finishes
+ * drops out; the call returns when all are done.  A non-zero return of `eval` ends the call with that code (no output is
+ * written then).  pose12 [B][12] and scale [B] are in / out; final_error, iters, trace_len ([B], optional); status [B]:
+ * SAGE_OK or SAGE_E_NO_OVERLAP; trace (optional) [B][trace_cap].
+ * SAGE_E_INVALID for NULL cfg / eval / pose12 / status, dof not 6 or 7, dof 7 with NULL scale, B < 0 or
+ * B > SAGE_TRACK_MAX_BATCH (32, defined next to SAGE_MATCH_MAX_BATCH).  B = 0: SAGE_OK, nothing is called. */
+typedef int (*SageTrackBatchEvalFn)(void *ctx, int n, const int32_t *problem, const int32_t *want_jac, const float *pose12,
+                                    const float *scale, float *AtA, float *Atb, float *error);
+int sage_track_lm_batch(const SageLmConfig *cfg, int dof, int B, SageTrackBatchEvalFn eval, void *ctx, float *pose12,
+                        float *scale, float *final_error, int *iters, int *status, SageLmTraceEntry *trace, int trace_cap,
+                        int *trace_len);
+
 /* product wiring of the two callbacks to the HIP kernels: CameraTracker::TrackNewFrame (dof 6) / TrackFrame (dof 7)
  * with the reference's term composition (camera_tracker.cpp:220-374):
  *   dof 6: error / AtA / Atb = photometric (tracker_photo_*)            [use_photo]
@@ -320,6 +337,24 @@ typedef struct SageTrackProblem
 int sage_track_frame(const SageLmConfig *cfg, int dof, const SageTrackProblem *prob,
                      float *pose12, float *scale, float *final_error, int *iters,
                      SageLmTraceEntry *trace, int trace_cap, int *trace_len);
+/* B problems tracked in lock-step: sage_track_lm_batch wired to batched kernels.  Per round (one evaluation of every problem
+ * that is not done): (dof 7) one scale pass that forms scale * unscaled depths for every problem and term of the round, at
+ * most two photometric launches (linearize, error-only: different kernels) over a flattened list of (problem, 256-pixel
+ * tile) items with a finalize each, at most two keypoint launches (a workgroup per problem), one ticket and one wait --
+ * whatever B.  A problem whose keypoint rows do not fit one workgroup's LDS (the single call's own test: NK > 571 at dof 7,
+ * NK > 927 at dof 6) goes through the single call's launches inside the round.
+ * CONTRACT: for every b, pose12[b], scale[b], final_error[b], iters[b], status[b] and the trace are byte-identical to
+ * sage_track_frame(cfg, dof, &probs[b], ...) on the same workspace and inputs, for every B, every order of the problems and
+ * whatever the other problems of the batch do (the per-pixel body and the keypoint contraction are the single call's code;
+ * per-tile partials are summed in tile order by one workgroup per problem).
+ * probs [B]; pose12 [B][12], scale [B] in / out; final_error, iters, trace_len [B] (optional); status [B]: SAGE_OK or
+ * SAGE_E_NO_OVERLAP per problem; trace (optional) [B][trace_cap].
+ * SAGE_E_INVALID before any launch: what sage_track_lm_batch and sage_track_frame refuse (per problem), NULL probs with
+ * B > 0, and problems that do not share ws, FS, use_photo, use_keypoints, eps and a pyr with equal levels and cameras.
+ * B = 0: SAGE_OK, nothing launched. */
+int sage_track_frame_batch(const SageLmConfig *cfg, int dof, const SageTrackProblem *probs, int B, float *pose12,
+                           float *scale, float *final_error, int *iters, int *status, SageLmTraceEntry *trace,
+                           int trace_cap, int *trace_len);
 
 /* ---- overlap statistics of a tracked pose: CameraTracker::ComputeAreaInlierRatio (camera_tracker.cpp:95-169), what
  *      TrackNewFrame (:1289) and TrackFrame (:1644) hand back besides the pose and what NewKeyframeRequired
@@ -596,6 +631,7 @@ int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const 
  * C < 1 or C > 1024; H or W < 1 (or H*W >= 2^31); pixel_slices < 0; NULL n_inliers_host with B > 0; with B > 0 and K > 0 a
  * NULL map, output, pointer array or entry of a pointer array.  B = 0 or K = 0: SAGE_OK, the counts zeroed, nothing launched. */
 #define SAGE_MATCH_MAX_BATCH 32
+#define SAGE_TRACK_MAX_BATCH 32 /* sage_track_lm_batch, sage_track_frame_batch, sage_loop_verify */
 int sage_cycle_match_batch(SageWorkspace *ws, const float *desc_query_dev, const float *const *desc_cand_dev,
                            const int64_t *const *kp_loc1d_dev, int B, int K, int C, int H, int W, float cyc_thresh,
                            int pixel_slices, int64_t *raw_matched_loc1d, int64_t *cyc_matched_loc1d, int32_t *inlier_flags,
@@ -643,6 +679,68 @@ int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float que
                        int B, int K, int C, int H, int W, const SageCamera *cam, float cyc_thresh, float noise_multiplier,
                        float min_desc_inlier_ratio, const SageRegistrationParams *p, SageLoopPrecheckResult *results,
                        int64_t *raw_matched_loc1d, int32_t *inlier_flags, int32_t *inlier_kp_dev);
+
+/* sage_loop_verify: the detector's loop body after the ratio test -- TrackFrame(*curr_kf, true, use_match_geom, ...,
+ * match_geom_pre_checked = true) of loop_detector.cpp:165 / :321 (camera_tracker.cpp:1312-1672) for every survivor of
+ * sage_loop_precheck at once.  The accept / sort / redundancy filtering of loop_detector.cpp:173-229 stays with the caller.
+ * Survivors: pre[b].registered == 1 and pre[b].reg.n_inliers > 3 (camera_tracker.cpp:1407).  cands, pre, raw_matched_loc1d
+ * and inlier_kp_dev are sage_loop_precheck's arrays as they are.
+ * A host composition around ONE kernel of its own:
+ *   1. one gather launch over (survivor, inlier) builds every survivor's keypoint term (camera_tracker.cpp:1415-1424,
+ *      :654-678) into kp_gathered_dev [B][8 K], row b = homo0 [K][3] | unscaled dpts0 [K] | homo1 [K][3] | dpts1 [K], the first
+ *      reg.n_inliers entries of each written.  With i = inlier_kp_dev[b][j], loc = raw_matched_loc1d[b][i]:
+ *        homo0 = cands[b].kp_homo0_dev[i];  unscaled dpts0 = cands[b].kp_dpts0_dev[i] / query_depth_divisor (a true division)
+ *        homo1 = ((fmod((float)loc, W) - cx) / fx, (floor((float)loc / W) - cy) / fy, 1);  dpts1 = cands[b].dpt_map_dev[loc]
+ *      -- sage_match_points' expressions, from the same device function (a location outside the map reads a NaN depth);
+ *      cam = query->pyr.cam[0], W = cam.w;
+ *   2. start values from the registration (:750-761): pose12 = (float)reg.R, (float)reg.t; scale = (float)reg.scale;
+ *   3. kp_weight = pre[b].desc_match_inlier_ratio * match_geom_factor_weight (:414, :742), kp_loss_param from the candidate
+ *      (match_geom_loss_param_factor * avg_squared_dpt_bias of that keyframe, :409); cfg->no_overlap_error is not read: the
+ *      check is off with the match-geometry term (:1515);
+ *   4. one sage_track_frame_batch (dof 7, photometric + match geometry) over the survivors: the query's photometric side is
+ *      shared, feat1 / grad1 / mask1 are the candidate's;
+ *   5. per tracked survivor one sage_track_overlap with depth_scale = scale_b / query_depth_divisor (:1644), one after the
+ *      other.
+ * Per candidate the result equals sage_track_frame + sage_track_overlap on the gathered inputs, byte for byte.  A candidate
+ * that is no survivor gets tracked = 0 (the rest of its result zeroed) and no launch beyond the gather, which skips it.
+ * SAGE_E_INVALID (nothing is launched) for: NULL ws, cfg, query, results; B < 0 or B > SAGE_TRACK_MAX_BATCH; K < 0 or
+ * K > SAGE_REG_MAX_POINTS; with B > 0: NULL cands, vcands, pre, raw_matched_loc1d, inlier_kp_dev or kp_gathered_dev, a
+ * query with N < 1, M < 1, FS not 16 / 32, pyr.levels outside 1..SAGE_MAX_LEVELS, a NULL array, fx / fy of pyr.cam[0] not
+ * positive and finite; a divisor that is not positive and finite; for a survivor: a NULL member of cands[b] / vcands[b],
+ * reg.n_inliers > K.  B = 0 or no survivor: SAGE_OK, the results zeroed.
+ * Waits: the rounds of sage_track_frame_batch (one each), then one per tracked survivor (the overlap). */
+typedef struct SageLoopVerifyQuery /* device pointers: the query keyframe's side of every survivor's problem */
+{
+  int32_t N, FS;                    /* sampled pixels, feature channels */
+  const float *homo_dev;            /* [N,3] */
+  const float *unscaled_dpts0_dev;  /* [N] dpt_map_0 / dpt_scale_0 at the samples */
+  const float *feat0s_dev;          /* [L,N,FS] pre-sampled source features */
+  const float *weights_dev;         /* [L] */
+  SagePyramid pyr;
+  float eps;
+  int32_t M;                        /* valid pixels of the query (sage_track_overlap) */
+  const float *valid_homo_dev;      /* [M,3] */
+  const float *valid_dpts0_dev;     /* [M] dpt_map_0 at them (scaled: depth_scale divides by query_depth_divisor) */
+  const float *mask_dev;            /* [h,w] the mask of sage_track_overlap */
+} SageLoopVerifyQuery;
+typedef struct SageLoopVerifyCandidate /* device pointers, next to cands[b] */
+{
+  const float *feat1_dev, *grad1_dev, *mask1_dev; /* [FS,P], [2,FS,P], [h,w] of the candidate keyframe */
+  float kp_loss_param;
+} SageLoopVerifyCandidate;
+typedef struct SageLoopVerifyResult /* host */
+{
+  int32_t tracked;                  /* 0: not a survivor, nothing else is meaningful */
+  int32_t status;                   /* SAGE_OK (the match-geometry term switches the no-overlap exit off) */
+  float pose12[12], scale, error;
+  int32_t iters;
+  float area_ratio, inlier_ratio, average_motion; /* sage_track_overlap's three */
+  float area_inlier_ratio;          /* area_ratio * inlier_ratio (fp32) */
+} SageLoopVerifyResult;
+int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, const SageLoopVerifyQuery *query, float query_depth_divisor,
+                     const SageLoopCandidate *cands, const SageLoopVerifyCandidate *vcands, const SageLoopPrecheckResult *pre,
+                     int B, int K, const int64_t *raw_matched_loc1d, const int32_t *inlier_kp_dev,
+                     float match_geom_factor_weight, float *kp_gathered_dev, SageLoopVerifyResult *results);
 
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)

@@ -135,7 +135,7 @@ SYMBOLS = [
     "sage_tracker_photo_jac_error_calculate", "sage_tracker_photo_error_calculate",
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
-    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_frame", "sage_track_overlap", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
+    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_lm_batch", "sage_track_frame", "sage_track_frame_batch", "sage_track_overlap", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
     "sage_vocabulary_create", "sage_vocabulary_destroy", "sage_vocabulary_num_nodes", "sage_vocabulary_num_words", "sage_vocabulary_channels", "sage_vocabulary_depth", "sage_vocabulary_max_fanout", "sage_vocabulary_staged_nodes",
     "sage_bow_transform", "sage_bow_score", "sage_bow_db_create", "sage_bow_db_destroy", "sage_bow_db_add", "sage_bow_db_size", "sage_bow_db_query",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
@@ -152,7 +152,7 @@ SYMBOLS = [
     "sage_loop_mg_jac_error_calculate", "sage_loop_mg_error_calculate",
     "sage_tracker_match_geom_jac_error_calculate", "sage_tracker_match_geom_error_calculate", "sage_cycle_match",
     "sage_robust_registration", "sage_tls_estimate", "sage_registration_finish", "sage_match_points",
-    "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck",
+    "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck", "sage_loop_verify",
 ]
 
 
@@ -346,7 +346,95 @@ def track_lm(cfg: SageLmConfig, dof: int, lin_fn, err_fn, pose12, scale: float, 
     return pose, sc.value, fe.value, it.value, tr
 
 
+SAGE_TRACK_MAX_BATCH = 32
+TRACK_BATCH_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float))
+
+
+def _trace_dicts(tr, n):
+    return [dict(damp=tr[i].damp, error=tr[i].error, candidate_error=tr[i].candidate_error, accepted=tr[i].accepted,
+                 relinearized=tr[i].relinearized) for i in range(n)]
+
+
+def track_lm_batch_raw(cfg_ptr, dof, B, eval_cb, pose_ptr, scale_ptr, err_ptr, iters_ptr, status_ptr, trace_ptr, trace_cap,
+                       trace_len_ptr) -> int:
+    """``sage_track_lm_batch`` with the arguments as given (pointers may be None) -> status code"""
+    f = lib().sage_track_lm_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+    return int(f(cfg_ptr, int(dof), int(B), C.cast(eval_cb, C.c_void_p) if eval_cb is not None else None, None, pose_ptr,
+                 scale_ptr, err_ptr, iters_ptr, status_ptr, trace_ptr, int(trace_cap), trace_len_ptr))
+
+
+def _batch_outputs(B, poses, scales, trace_cap):
+    n = max(B, 1)
+    p = np.zeros((n, 12), np.float32); s = np.ones(n, np.float32)
+    if B:
+        p[:B] = _f32(poses).reshape(B, 12); s[:B] = _f32(scales).reshape(B)
+    return (p, s, np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32),
+            (SageLmTraceEntry * (n * max(trace_cap, 1)))(), np.zeros(n, np.int32))
+
+
+def _batch_result(rc, B, out, trace_cap):
+    p, s, fe, it, st, tr, tl = out
+    traces = [_trace_dicts((SageLmTraceEntry * max(trace_cap, 1)).from_buffer(tr, b * trace_cap * C.sizeof(SageLmTraceEntry)),
+                           int(tl[b])) for b in range(B)]
+    return rc, p[:B], s[:B], fe[:B], it[:B], st[:B], traces
+
+
+def track_lm_batch(cfg: SageLmConfig, dof: int, eval_fn, poses, scales, trace_cap: int = 256):
+    """B runs of the tracker LM policy in lock-step (``sage_track_lm_batch``).  ``eval_fn(problems, want_jac, poses [n,12],
+    scales [n])`` is called once per round and returns one answer per request: ``(AtA, Atb, error)`` where want_jac, else
+    ``error``.  poses [B,12], scales [B].  -> (rc, poses, scales, errors, iters, status, traces), arrays of B (float32 /
+    int32), traces: B lists of dicts."""
+    B = len(poses)
+
+    def _eval(ctx, n, problem, want_jac, p, s, AtA, Atb, err):
+        probs = [int(problem[i]) for i in range(n)]
+        wj = [bool(want_jac[i]) for i in range(n)]
+        ans = eval_fn(probs, wj, np.ctypeslib.as_array(p, (n, 12)).copy(), np.ctypeslib.as_array(s, (n,)).copy())
+        for i in range(n):
+            if wj[i]:
+                A, b, e = ans[i]
+                A = _f32(A).reshape(-1); b = _f32(b).reshape(-1)
+                for k in range(dof * dof):
+                    AtA[49 * i + k] = A[k]
+                for k in range(dof):
+                    Atb[7 * i + k] = b[k]
+                err[i] = e
+            else:
+                err[i] = ans[i]
+        return 0
+
+    out = _batch_outputs(B, poses, scales, trace_cap)
+    cb = TRACK_BATCH_EVAL_FN(_eval)
+    rc = track_lm_batch_raw(C.addressof(cfg), dof, B, cb, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data,
+                            out[3].ctypes.data, out[4].ctypes.data, C.addressof(out[5]), trace_cap, out[6].ctypes.data)
+    return _batch_result(rc, B, out, trace_cap)
+
+
 # --------------------------------------------------------------------------- device side
+def track_frame_batch_raw(cfg_ptr, dof, probs_ptr, B, pose_ptr, scale_ptr, err_ptr, iters_ptr, status_ptr, trace_ptr, trace_cap,
+                          trace_len_ptr) -> int:
+    """``sage_track_frame_batch`` with the arguments as given (pointers may be None) -> status code"""
+    f = lib().sage_track_frame_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+    return int(f(cfg_ptr, int(dof), probs_ptr, int(B), pose_ptr, scale_ptr, err_ptr, iters_ptr, status_ptr, trace_ptr,
+                 int(trace_cap), trace_len_ptr))
+
+
+def track_frame_batch(cfg: SageLmConfig, dof: int, probs, poses, scales, trace_cap: int = 256):
+    """``sage_track_frame_batch``: B ``SageTrackProblem`` s tracked in lock-step on the HIP kernels.  poses [B,12], scales [B].
+    -> (rc, poses, scales, errors, iters, status, traces) as ``track_lm_batch``; row b is what ``track_frame`` returns for
+    probs[b], bit for bit."""
+    B = len(probs)
+    arr = (SageTrackProblem * max(B, 1))(*probs)
+    out = _batch_outputs(B, poses, scales, trace_cap)
+    rc = track_frame_batch_raw(C.addressof(cfg), dof, C.addressof(arr), B, out[0].ctypes.data, out[1].ctypes.data,
+                               out[2].ctypes.data, out[3].ctypes.data, out[4].ctypes.data, C.addressof(out[5]), trace_cap,
+                               out[6].ctypes.data)
+    return _batch_result(rc, B, out, trace_cap)
+
+
 def track_frame(cfg: SageLmConfig, dof: int, prob: "SageTrackProblem", pose12, scale: float, trace_cap: int = 256):
     """sage_track_frame: the tracker LM wired to the HIP kernels.  Returns (rc, pose12, scale, final_error, iters, trace)."""
     L = lib()
@@ -1738,6 +1826,56 @@ def loop_precheck(ws, desc_q, query_depth_divisor, cands, H, W, cam, cyc_thresh,
                         mean_noise_depth=np.float32(r.mean_noise_depth), reg=_reg_result(r.reg), raw_matched=raw[b, :K],
                         flags=fl[b, :K], inlier_kp=ikp[b, :r.reg.n_inliers]))
     return out
+
+
+class SageLoopVerifyQuery(C.Structure):
+    _fields_ = [("N", C.c_int32), ("FS", C.c_int32), ("homo_dev", C.c_void_p), ("unscaled_dpts0_dev", C.c_void_p),
+                ("feat0s_dev", C.c_void_p), ("weights_dev", C.c_void_p), ("pyr", SagePyramid), ("eps", C.c_float), ("M", C.c_int32),
+                ("valid_homo_dev", C.c_void_p), ("valid_dpts0_dev", C.c_void_p), ("mask_dev", C.c_void_p)]
+
+
+class SageLoopVerifyCandidate(C.Structure):
+    _fields_ = [("feat1_dev", C.c_void_p), ("grad1_dev", C.c_void_p), ("mask1_dev", C.c_void_p), ("kp_loss_param", C.c_float)]
+
+
+class SageLoopVerifyResult(C.Structure):
+    _fields_ = [("tracked", C.c_int32), ("status", C.c_int32), ("pose12", C.c_float * 12), ("scale", C.c_float),
+                ("error", C.c_float), ("iters", C.c_int32), ("area_ratio", C.c_float), ("inlier_ratio", C.c_float),
+                ("average_motion", C.c_float), ("area_inlier_ratio", C.c_float)]
+
+
+def loop_verify_raw(ws_handle, cfg_ptr, query_ptr, divisor, cands_ptr, vcands_ptr, pre_ptr, B, K, raw, inlier_kp, mg_weight, gathered,
+                    results_ptr) -> int:
+    """``sage_loop_verify`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_loop_verify
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                  C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, cfg_ptr, query_ptr, float(divisor), cands_ptr, vcands_ptr, pre_ptr, int(B), int(K), raw, inlier_kp,
+                 float(mg_weight), gathered, results_ptr))
+
+
+def loop_verify(ws, cfg: SageLmConfig, query: SageLoopVerifyQuery, query_depth_divisor, cands, vcands, pre, raw_matched, inlier_kp,
+                match_geom_factor_weight):
+    """The loop detector's body after the ratio test through ``sage_loop_verify``.  cands: the dicts of ``loop_precheck``;
+    vcands: dicts with the cuda tensors ``feat1``, ``grad1``, ``mask1`` and the float ``kp_loss_param``; pre: a ctypes array of
+    ``SageLoopPrecheckResult`` [B]; raw_matched [B,K] int64, inlier_kp [B,K] int32: cuda tensors as the pre-check wrote them.
+    -> (a ctypes array of B ``SageLoopVerifyResult``, the gathered keypoint terms: a [B, 8 K] cuda tensor, row b = homo0 [K,3] |
+    unscaled dpts0 [K] | homo1 [K,3] | dpts1 [K])."""
+    import torch
+    B = len(cands)
+    K = int(raw_matched.shape[1]) if B else 0
+    arr = (SageLoopCandidate * max(B, 1))()
+    varr = (SageLoopVerifyCandidate * max(B, 1))()
+    for b, (c, v) in enumerate(zip(cands, vcands)):
+        arr[b] = SageLoopCandidate(*[dptr(c[n]).value for n in ("desc", "dpt_map", "kp_loc", "kp_dpts0", "kp_homo0")])
+        varr[b] = SageLoopVerifyCandidate(dptr(v["feat1"]).value, dptr(v["grad1"]).value, dptr(v["mask1"]).value,
+                                          float(v["kp_loss_param"]))
+    res = (SageLoopVerifyResult * max(B, 1))()
+    gathered = torch.zeros(max(B, 1), 8 * max(K, 1), dtype=torch.float32, device="cuda")
+    _chk(loop_verify_raw(ws.h, C.addressof(cfg), C.addressof(query), query_depth_divisor, C.addressof(arr), C.addressof(varr),
+                         C.addressof(pre), B, K, dptr(raw_matched), dptr(inlier_kp), match_geom_factor_weight, dptr(gathered),
+                         C.addressof(res)), "sage_loop_verify")
+    return res, gathered
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -929,74 +929,126 @@ static bool lm_converged(const SageLmConfig &cfg, int dof, const float *pose, fl
 
 } // namespace sage
 
-extern "C" int sage_track_lm(const SageLmConfig *cfgp, int dof, SageTrackLinearizeFn lin, SageTrackErrorFn errf,
-                             void *ctx, float *pose12, float *scale, float *final_error, int *iters,
-                             SageLmTraceEntry *trace, int trace_cap, int *trace_len)
+namespace sage
 {
-  if (!cfgp || !lin || !errf || !pose12 || (dof != 6 && dof != 7) || (dof == 7 && !scale))
-    return SAGE_E_INVALID;
-  const SageLmConfig cfg = *cfgp;
-  float AtA[49], Atb[7], sol[7] = {0, 0, 0, 0, 0, 0, 0};
+
+// The tracker's LM policy (camera_tracker.cpp:1156-1279) as a resumable stepper: the state is what the reference's loop keeps
+// between two evaluations, and the loop's body is cut where it evaluates.  start() and feed() answer with what the policy
+// needs next -- the linearisation at (req_pose, req_scale), the error there, or nothing more (done, `status`) -- and feed()
+// takes the answer.  sage_track_lm drives one stepper with its two callbacks, sage_track_lm_batch B of them in lock-step:
+// one definition of the policy.
+struct LmStepper
+{
+  enum Ask { kLinearize, kError, kDone };
+  SageLmConfig cfg;
+  int dof = 6;
+  float AtA[49], Atb[7], sol[7];
   float guess[12], cand[12];
-  std::memcpy(guess, pose12, sizeof(guess));
-  float guess_scale = scale ? *scale : 1.0f, cand_scale = guess_scale;
+  float guess_scale = 1.f, cand_scale = 1.f;
   bool update_jac = true;
   float prev_error = 0.f, curr_error = 1.f, cand_error = 0.f;
   long curr_iter = 0;
-  float damp = cfg.init_damp;
-  int ntrace = 0;
-  auto clampd = [&](float d) { return std::min(std::max(cfg.min_damp, d), cfg.max_damp); };
-  int rc = 0;
-  while (true)
+  float damp = 0.f;
+  SageLmTraceEntry *trace = nullptr;
+  int trace_cap = 0, ntrace = 0;
+  Ask ask = kDone;
+  int status = 0;    // done: SAGE_OK or SAGE_E_NO_OVERLAP; `failed`: the code of the damped solve
+  bool failed = false; // done on a failed solve: the caller returns `status` and writes no outputs
+  const float *req_pose = nullptr;
+  float req_scale = 1.f;
+
+  void init(const SageLmConfig &c, int dof_, const float *pose12, const float *scale, SageLmTraceEntry *tr, int cap)
   {
-    // skip the Jacobian when the last step changed the error too little (:1159)
-    if (std::fabs(curr_error - prev_error) / prev_error > cfg.jac_update_err_inc_threshold)
+    cfg = c;
+    dof = dof_;
+    for (int i = 0; i < 7; ++i)
+      sol[i] = 0.f;
+    std::memcpy(guess, pose12, sizeof(guess));
+    guess_scale = scale ? *scale : 1.0f;
+    cand_scale = guess_scale;
+    damp = cfg.init_damp;
+    trace = tr;
+    trace_cap = cap;
+  }
+  float clampd(float d) const { return std::min(std::max(cfg.min_damp, d), cfg.max_damp); }
+  Ask done(int st, bool fail = false)
+  {
+    status = st;
+    failed = fail;
+    return ask = kDone;
+  }
+  Ask want(Ask what, const float *pose, float scale)
+  {
+    req_pose = pose;
+    req_scale = scale;
+    return ask = what;
+  }
+  Ask start() { return top(); }
+  // the answer to the last request.  kLinearize: A [dof x dof], b [dof] (may be this stepper's own AtA / Atb) and the error;
+  // kError: the error alone
+  Ask feed(const float *A, const float *b, float error)
+  {
+    if (ask == kLinearize)
     {
-      float lin_error = 0.f;
-      if ((rc = lin(ctx, guess, guess_scale, AtA, Atb, &lin_error)) != 0)
-        return rc;
+      if (A != AtA)
+        std::memcpy(AtA, A, sizeof(float) * dof * dof);
+      if (b != Atb)
+        std::memcpy(Atb, b, sizeof(float) * dof);
       if (curr_iter == 0) // update_error only on the first pass (:1166, :1491); later the accepted candidate's error stands
-        curr_error = lin_error;
+        curr_error = error;
       update_jac = true;
+      return after_linearize();
     }
-    else
-      update_jac = false;
+    if (ask != kError)
+      return ask;
+    cand_error = error;
+    if (cand_error < curr_error)
+      return after_inner(true);
+    if (damp < cfg.max_damp) // the inner damping retry
+    {
+      damp = clampd(damp * cfg.damp_inc_factor);
+      const int rc = sage_damped_solve_qr_f32(AtA, Atb, dof, damp, sol);
+      if (rc != 0)
+        return done(rc, true);
+      return propose();
+    }
+    return after_inner(false);
+  }
+
+private:
+  Ask top()
+  {
+    // skip the Jacobian when the last step changed the error too little (:1159): from accept straight to the next solve
+    if (std::fabs(curr_error - prev_error) / prev_error > cfg.jac_update_err_inc_threshold)
+      return want(kLinearize, guess, guess_scale);
+    update_jac = false;
+    return after_linearize();
+  }
+  Ask after_linearize()
+  {
     // TrackFrame without the match-geometry term: "no overlap" ends the tracking with a failure (:1515-1519)
     if (cfg.no_overlap_error > 0.f && curr_error >= cfg.no_overlap_error)
-    {
-      rc = SAGE_E_NO_OVERLAP;
-      break;
-    }
+      return done(SAGE_E_NO_OVERLAP);
     curr_iter += 1;
-    if ((rc = sage_damped_solve_qr_f32(AtA, Atb, dof, damp, sol)) != 0)
-      return rc;
-    if (sage::lm_converged(cfg, dof, guess, guess_scale, Atb, sol))
-      break;
-    bool accepted = false;
-    while (true)
-    {
-      sage_pose_retract(guess, sol, cand); // UpdateVariables (:467-512)
-      cand_scale = dof == 7 ? guess_scale + sol[6] : guess_scale;
-      if ((rc = errf(ctx, cand, cand_scale, &cand_error)) != 0)
-        return rc;
-      if (cand_error < curr_error)
-      {
-        accepted = true;
-        break;
-      }
-      else if (damp < cfg.max_damp)
-      {
-        damp = clampd(damp * cfg.damp_inc_factor);
-        if ((rc = sage_damped_solve_qr_f32(AtA, Atb, dof, damp, sol)) != 0)
-          return rc;
-      }
-      else
-        break;
-    }
+    const int rc = sage_damped_solve_qr_f32(AtA, Atb, dof, damp, sol);
+    if (rc != 0)
+      return done(rc, true);
+    if (lm_converged(cfg, dof, guess, guess_scale, Atb, sol))
+      return done(SAGE_OK);
+    return propose();
+  }
+  Ask propose()
+  {
+    sage_pose_retract(guess, sol, cand); // UpdateVariables (:467-512)
+    cand_scale = dof == 7 ? guess_scale + sol[6] : guess_scale;
+    return want(kError, cand, cand_scale);
+  }
+  Ask after_inner(bool accepted)
+  {
     if (trace && ntrace < trace_cap)
       trace[ntrace++] = SageLmTraceEntry{damp, curr_error, cand_error, accepted ? 1 : 0, update_jac ? 1 : 0};
     if (cand_error >= curr_error && damp >= cfg.max_damp)
-      break;
+      return done(SAGE_OK);
     std::memcpy(guess, cand, sizeof(guess));
     guess_scale = cand_scale;
     if (update_jac)
@@ -1004,16 +1056,102 @@ extern "C" int sage_track_lm(const SageLmConfig *cfgp, int dof, SageTrackLineari
     curr_error = cand_error;
     damp = clampd(damp / cfg.damp_dec_factor);
     if (curr_iter >= cfg.max_num_iters)
-      break;
+      return done(SAGE_OK);
+    return top();
   }
-  std::memcpy(pose12, guess, sizeof(guess));
-  if (scale)
-    *scale = guess_scale;
-  if (final_error)
-    *final_error = curr_error;
-  if (iters)
-    *iters = (int)curr_iter;
-  if (trace_len)
-    *trace_len = ntrace;
-  return rc;
+
+public:
+  void results(float *pose12, float *scale, float *final_error, int *iters, int *trace_len) const
+  {
+    std::memcpy(pose12, guess, sizeof(guess));
+    if (scale)
+      *scale = guess_scale;
+    if (final_error)
+      *final_error = curr_error;
+    if (iters)
+      *iters = (int)curr_iter;
+    if (trace_len)
+      *trace_len = ntrace;
+  }
+};
+
+} // namespace sage
+
+extern "C" int sage_track_lm(const SageLmConfig *cfgp, int dof, SageTrackLinearizeFn lin, SageTrackErrorFn errf,
+                             void *ctx, float *pose12, float *scale, float *final_error, int *iters,
+                             SageLmTraceEntry *trace, int trace_cap, int *trace_len)
+{
+  if (!cfgp || !lin || !errf || !pose12 || (dof != 6 && dof != 7) || (dof == 7 && !scale))
+    return SAGE_E_INVALID;
+  sage::LmStepper st;
+  st.init(*cfgp, dof, pose12, scale, trace, trace_cap);
+  sage::LmStepper::Ask ask = st.start();
+  while (ask != sage::LmStepper::kDone)
+  {
+    float e = ask == sage::LmStepper::kLinearize ? 0.f : st.cand_error;
+    const int rc = ask == sage::LmStepper::kLinearize ? lin(ctx, st.req_pose, st.req_scale, st.AtA, st.Atb, &e)
+                                                      : errf(ctx, st.req_pose, st.req_scale, &e);
+    if (rc != 0)
+      return rc;
+    ask = st.feed(st.AtA, st.Atb, e);
+  }
+  if (st.failed)
+    return st.status;
+  st.results(pose12, scale, final_error, iters, trace_len);
+  return st.status;
+}
+
+extern "C" int sage_track_lm_batch(const SageLmConfig *cfgp, int dof, int B, SageTrackBatchEvalFn eval, void *ctx,
+                                   float *pose12, float *scale, float *final_error, int *iters, int *status,
+                                   SageLmTraceEntry *trace, int trace_cap, int *trace_len)
+{
+  if (!cfgp || !eval || !pose12 || !status || (dof != 6 && dof != 7) || (dof == 7 && !scale) || B < 0 ||
+      B > SAGE_TRACK_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B == 0)
+    return SAGE_OK;
+  using Ask = sage::LmStepper::Ask;
+  std::vector<sage::LmStepper> st((size_t)B);
+  for (int b = 0; b < B; ++b)
+  {
+    st[b].init(*cfgp, dof, pose12 + 12 * (size_t)b, scale ? scale + b : nullptr,
+               trace ? trace + (size_t)b * (trace_cap > 0 ? trace_cap : 0) : nullptr, trace_cap);
+    st[b].start();
+  }
+  // one round: every problem that is not done asks for exactly one evaluation, in ascending problem order
+  int32_t problem[SAGE_TRACK_MAX_BATCH], want_jac[SAGE_TRACK_MAX_BATCH];
+  std::vector<float> rp((size_t)B * 12), rs((size_t)B), A((size_t)B * 49), g((size_t)B * 7), e((size_t)B);
+  while (true)
+  {
+    int n = 0;
+    for (int b = 0; b < B; ++b)
+    {
+      if (st[b].ask == Ask::kDone)
+      {
+        if (st[b].failed)
+          return st[b].status;
+        continue;
+      }
+      problem[n] = b;
+      want_jac[n] = st[b].ask == Ask::kLinearize ? 1 : 0;
+      std::memcpy(&rp[(size_t)n * 12], st[b].req_pose, 12 * sizeof(float));
+      rs[n] = st[b].req_scale;
+      e[n] = want_jac[n] ? 0.f : st[b].cand_error;
+      ++n;
+    }
+    if (n == 0)
+      break;
+    const int rc = eval(ctx, n, problem, want_jac, rp.data(), rs.data(), A.data(), g.data(), e.data());
+    if (rc != 0)
+      return rc;
+    for (int i = 0; i < n; ++i)
+      st[problem[i]].feed(&A[(size_t)i * 49], &g[(size_t)i * 7], e[i]);
+  }
+  for (int b = 0; b < B; ++b)
+  {
+    st[b].results(pose12 + 12 * (size_t)b, scale ? scale + b : nullptr, final_error ? final_error + b : nullptr,
+                  iters ? iters + b : nullptr, trace_len ? trace_len + b : nullptr);
+    status[b] = st[b].status;
+  }
+  return SAGE_OK;
 }

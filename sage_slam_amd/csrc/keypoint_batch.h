@@ -66,6 +66,32 @@ struct KpOut
   float *stats;     // {error, num_inliers}
 };
 
+// the one-workgroup contraction (small_kernel): its dynamic LDS -- the working set, then 256 partial sums in double -- and
+// what a workgroup may ask for
+constexpr size_t kKpSmallLdsMax = 60 * 1024;
+constexpr size_t kp_small_lds_bytes(int rpp, int N, int D) { return (kp_rows_floats(rpp, N, D) + 2) * sizeof(float) + (size_t)256 * sizeof(double); }
+// (N = 512 matches at D = 7: (3 * 512 * 8 + 1024 + 2) * 4 + 2048 = 55 304 bytes -- the loop detector's NK <= 512 stays on the
+// one-launch path, in sage_track_frame and in a batch alike)
+
+// one problem of a batched tracker call (sage_track_frame_batch), in the call's pinned table: written once per call, scale0
+// before every round the problem takes part in
+struct KpTrackProblem
+{
+  const float *R, *t;        // the pose slot of the problem's TrackHost
+  const float *dpts0, *homo0; // [N], [N,3]: the caller's metric depths (dof 6) or the problem's slice of the round's scaled ones
+  const float *matched_2d;   // dof 6: [N,2]
+  const float *dpts1, *homo1; // dof 7: [N], [N,3]
+  float scale0;              // per round: the scale being evaluated
+  float loss_param, weight;
+  int32_t N, loss;           // loss: SAGE_LOSS_FAIR -- read from the table like every other parameter, so that the rows'
+                             // code is compiled as in small_kernel (a constant here would prune and re-fuse it)
+  float *AtA, *Atb, *stats;  // the keypoint slots of the problem's TrackHost
+};
+// dof 6: reprojection, dof 7: match geometry (mode 3 with jac, mode 2 without, as sage_track_frame evaluates them); a
+// workgroup per request; lds_bytes: the largest kp_small_lds_bytes among them
+hipError_t launch_kp_track_batch(hipStream_t s, int dof, bool jac, const KpTrackProblem *probs, const int32_t *requests,
+                                 int n_requests, size_t lds_bytes, const SageCamera &cam, float eps);
+
 // scratch: kp_scratch_floats(rows per keypoint, N, D) floats
 hipError_t launch_reproj(hipStream_t s, int CS, bool tracker, bool jac, const ReprojParams &p, float *scratch, const KpOut &out);
 hipError_t launch_match_geom(hipStream_t s, int mode, int CS, bool jac, const MgParams &p, float *scratch, const KpOut &out);

@@ -347,14 +347,14 @@ __global__ __launch_bounds__(256) void rows_kernel(const typename F::Params p)
 // interleaved rows in double, folded in a fixed order -- instead of rows to memory + a D-workgroup reduce launch.  A tracker
 // evaluation is launch-latency bound: one launch less per keypoint term and evaluation.
 //   dynamic LDS: the working set of kp_place, then the partial sums
+// (the body: small_kernel runs it for the one factor of its arguments, small_batch_kernel for the problem of its workgroup)
 template <class F, bool JAC>
-__global__ __launch_bounds__(256) void small_kernel(typename F::Params p, const KpOut out)
+__device__ __forceinline__ void small_body(typename F::Params &p, const KpOut &out, float *s_dyn)
 {
   constexpr int D = F::D;
   constexpr int NENT = D * (D + 1); // (a, j): a < D, j <= D (j == D: the residual column -> Atb)
   constexpr int NGRP = 256 / NENT;  // row groups (D = 6: 6, D = 7: 4, D = 14: 1)
   static_assert(F::kSmall && NGRP >= 1, "system too large for the one-workgroup contraction");
-  extern __shared__ __attribute__((aligned(16))) float s_dyn[];
   const int tid = threadIdx.x;
   kp_place(p, s_dyn, F::RPP, D);
   for (int idx = tid; idx < p.N; idx += 256)
@@ -394,6 +394,65 @@ __global__ __launch_bounds__(256) void small_kernel(typename F::Params p, const 
   }
   if (tid == 0)
     kp_store_stats<true>(out.stats, p.weight, s);
+}
+
+template <class F, bool JAC>
+__global__ __launch_bounds__(256) void small_kernel(typename F::Params p, const KpOut out)
+{
+  extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+  small_body<F, JAC>(p, out, s_dyn);
+}
+
+// ---- batched tracker (sage_track_frame_batch): the keypoint term of every problem that asked for this kind of evaluation
+// in the round, ONE launch, workgroup i = problem requests[i].  small_kernel's contraction on the problem's own rows: the
+// same F::rows, the same fold order, the same LDS layout (the launch's dynamic LDS is the largest problem's)
+template <class F, bool JAC>
+__global__ __launch_bounds__(256) void small_batch_kernel(const KpTrackProblem *probs, const int32_t *requests, const SageCamera cam,
+                                                          const float eps)
+{
+  extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+  const KpTrackProblem &P = probs[requests[blockIdx.x]];
+  typename F::Params p{};
+  if constexpr (std::is_same<typename F::Params, ReprojParams>::value)
+  {
+    p.R10 = P.R; p.t10 = P.t; p.dpts0 = P.dpts0; p.homo = P.homo0; p.matched = P.matched_2d;
+    p.scale0 = 1.f; p.cam = cam; p.eps = eps; p.loss_param = P.loss_param; p.weight = P.weight; p.N = P.N;
+  }
+  else
+  {
+    p.R10 = P.R; p.t10 = P.t; p.homo0 = P.homo0; p.homo1 = P.homo1;
+    p.scale0 = JAC ? P.scale0 : 1.f; p.scale1 = 1.f; p.loss_param = P.loss_param; p.weight = P.weight; p.loss = P.loss; p.N = P.N;
+    p.dpts0 = P.dpts0; p.dpts1 = P.dpts1;
+  }
+  small_body<F, JAC>(p, KpOut{P.AtA, P.Atb, P.stats}, s_dyn);
+}
+
+hipError_t launch_kp_track_batch(hipStream_t s, int dof, bool jac, const KpTrackProblem *probs, const int32_t *requests,
+                                 int n_requests, size_t lds_bytes, const SageCamera &cam, float eps)
+{
+  if (n_requests < 1 || lds_bytes > kKpSmallLdsMax)
+    return hipErrorInvalidValue;
+  using R = ReprojFactor<16, 1>;
+  using M2 = MatchGeomFactor<16, 2>;
+  using M3 = MatchGeomFactor<16, 3>;
+  const dim3 g(n_requests), b(256);
+  if (dof == 6)
+  {
+    if (jac)
+      hipLaunchKernelGGL((small_batch_kernel<R, true>), g, b, lds_bytes, s, probs, requests, cam, eps);
+    else
+      hipLaunchKernelGGL((small_batch_kernel<R, false>), g, b, lds_bytes, s, probs, requests, cam, eps);
+  }
+  else if (dof == 7) // (the tracker's modes: 3 = pose and scale for the linearize, 2 = pose only for the error)
+  {
+    if (jac)
+      hipLaunchKernelGGL((small_batch_kernel<M3, true>), g, b, lds_bytes, s, probs, requests, cam, eps);
+    else
+      hipLaunchKernelGGL((small_batch_kernel<M2, false>), g, b, lds_bytes, s, probs, requests, cam, eps);
+  }
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
 // workgroup a: AtA[a][:] and Atb[a] = (weight/n) sum_rows J[row][a] * [J[row][:] | r[row]] in double; workgroup 0 also
@@ -440,8 +499,8 @@ static hipError_t impl(hipStream_t s, typename F::Params p, bool jac, float *scr
   const int N = p.N, grid = (N + 255) / 256;
   if constexpr (F::kSmall)
   {
-    const size_t small_lds = (kp_rows_floats(RPP, N, D) + 2) * sizeof(float) + (size_t)256 * sizeof(double);
-    if (N > 0 && small_lds <= 60 * 1024)
+    const size_t small_lds = kp_small_lds_bytes(RPP, N, D);
+    if (N > 0 && small_lds <= kKpSmallLdsMax)
     {
       if (jac)
         hipLaunchKernelGGL((small_kernel<F, true>), dim3(1), dim3(256), small_lds, s, p, out);

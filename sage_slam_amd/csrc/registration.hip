@@ -532,6 +532,20 @@ struct MatchPointsParams
   int32_t *kept;
 };
 
+// a matched pixel of frame 1 -> its homogeneous coordinates and its depth (camera_tracker.cpp:654-678), in fp32 and in the
+// reference's order of operations; a location outside the map reads a NaN depth.  Shared by the gather in front of the
+// solver (reg_match_points_kernel) and the one in front of the tracker (verify_gather_kernel)
+__device__ __forceinline__ void matched_point(long long loc, float Wf, float cx, float cy, float fx, float fy, long long HW,
+                                              const float *__restrict__ dpt_map_1, float *hx, float *hy, float *d1)
+{
+#pragma clang fp contract(off)
+  const float lf = (float)loc;
+  const float x = fmodf(lf, Wf), y = floorf(lf / Wf);
+  *hx = (x - cx) / fx;
+  *hy = (y - cy) / fy;
+  *d1 = (loc >= 0 && loc < HW) ? dpt_map_1[loc] : __int_as_float(0x7fc00000);
+}
+
 // one workgroup: compacts the flagged keypoints in ascending order (a wave scan of the flags per 256 keypoints) and evaluates
 // the gather's fp32 expressions for each; the depths' sum in fp64 (per lane, then the workgroup's tree)
 __global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPointsParams P, RegHost *host, volatile unsigned *ticket,
@@ -575,11 +589,8 @@ __global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPoi
       P.pts0[3 * m + 0] = s0 * h0x;
       P.pts0[3 * m + 1] = s0 * h0y;
       P.pts0[3 * m + 2] = s0 * h0z;
-      const long long loc = P.loc1[k];
-      const float lf = (float)loc;
-      const float x = fmodf(lf, P.Wf), y = floorf(lf / P.Wf);
-      const float hx = (x - P.cx) / P.fx, hy = (y - P.cy) / P.fy;
-      const float d1 = (loc >= 0 && loc < P.HW) ? P.dpt_map_1[loc] : __int_as_float(0x7fc00000);
+      float hx, hy, d1;
+      matched_point(P.loc1[k], P.Wf, P.cx, P.cy, P.fx, P.fy, P.HW, P.dpt_map_1, &hx, &hy, &d1);
       P.homo1[3 * m + 0] = hx;
       P.homo1[3 * m + 1] = hy;
       P.homo1[3 * m + 2] = 1.0f;
@@ -848,4 +859,163 @@ extern "C" int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev
     }
   }
   return gathered ? ws_ticket_wait(ws) : SAGE_OK;
+}
+
+// ---- the loop body after the ratio test: every survivor of the pre-check tracked against the query in one batch ----
+namespace
+{
+struct VerifyGatherItem // one survivor
+{
+  const float *kp_homo0, *kp_dpts0, *dpt_map;
+  const int64_t *raw;      // row b of raw_matched_loc1d
+  const int32_t *inlier_kp; // row b of inlier_kp_dev
+  float *out;              // row b of kp_gathered_dev: homo0 [K][3] | unscaled dpts0 [K] | homo1 [K][3] | dpts1 [K]
+  int32_t n, pad;
+};
+struct VerifyGatherParams
+{
+  VerifyGatherItem item[SAGE_TRACK_MAX_BATCH];
+  float divisor0, cx, cy, fx, fy, Wf;
+  long long HW;
+  int K;
+};
+
+// grid (ceil(K / 256), survivors): inlier j of survivor blockIdx.y
+__global__ __launch_bounds__(kBlock) void verify_gather_kernel(const VerifyGatherParams P)
+{
+#pragma clang fp contract(off)
+  const VerifyGatherItem &it = P.item[blockIdx.y];
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= it.n)
+    return;
+  const int i = it.inlier_kp[j];
+  const size_t K = (size_t)P.K;
+  float *homo0 = it.out, *dpts0 = homo0 + 3 * K, *homo1 = dpts0 + K, *dpts1 = homo1 + 3 * K;
+  if (i < 0 || i >= P.K) // (not a position among the K keypoints: nothing is read through it, the term turns NaN)
+  {
+    const float nan = __int_as_float(0x7fc00000);
+    homo0[3 * j + 0] = homo0[3 * j + 1] = homo0[3 * j + 2] = dpts0[j] = nan;
+    homo1[3 * j + 0] = homo1[3 * j + 1] = homo1[3 * j + 2] = dpts1[j] = nan;
+    return;
+  }
+  homo0[3 * j + 0] = it.kp_homo0[3 * i + 0];
+  homo0[3 * j + 1] = it.kp_homo0[3 * i + 1];
+  homo0[3 * j + 2] = it.kp_homo0[3 * i + 2];
+  dpts0[j] = it.kp_dpts0[i] / P.divisor0;
+  float hx, hy, d1;
+  matched_point(it.raw[i], P.Wf, P.cx, P.cy, P.fx, P.fy, P.HW, it.dpt_map, &hx, &hy, &d1);
+  homo1[3 * j + 0] = hx;
+  homo1[3 * j + 1] = hy;
+  homo1[3 * j + 2] = 1.0f;
+  dpts1[j] = d1;
+}
+} // namespace
+
+extern "C" int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, const SageLoopVerifyQuery *query,
+                                float query_depth_divisor, const SageLoopCandidate *cands, const SageLoopVerifyCandidate *vcands,
+                                const SageLoopPrecheckResult *pre, int B, int K, const int64_t *raw_matched_loc1d,
+                                const int32_t *inlier_kp_dev, float match_geom_factor_weight, float *kp_gathered_dev,
+                                SageLoopVerifyResult *results)
+{
+  if (!ws || !cfg || !query || !results || B < 0 || B > SAGE_TRACK_MAX_BATCH || K < 0 || K > SAGE_REG_MAX_POINTS)
+    return SAGE_E_INVALID;
+  int surv[SAGE_TRACK_MAX_BATCH], ns = 0;
+  if (B > 0)
+  {
+    const SageCamera &cam = query->pyr.cam[0];
+    if (!cands || !vcands || !pre || !raw_matched_loc1d || !inlier_kp_dev || !kp_gathered_dev || query->N < 1 || query->M < 1 ||
+        (query->FS != 16 && query->FS != 32) || query->pyr.levels < 1 || query->pyr.levels > SAGE_MAX_LEVELS || !query->homo_dev ||
+        !query->unscaled_dpts0_dev || !query->feat0s_dev || !query->weights_dev || !query->valid_homo_dev ||
+        !query->valid_dpts0_dev || !query->mask_dev || !(cam.fx > 0) || !(cam.fy > 0) || !std::isfinite(cam.fx) ||
+        !std::isfinite(cam.fy) || cam.w < 1 || cam.h < 1 || !(query_depth_divisor > 0) || !std::isfinite(query_depth_divisor))
+      return SAGE_E_INVALID;
+    for (int b = 0; b < B; ++b)
+    {
+      if (pre[b].registered != 1 || pre[b].reg.n_inliers <= 3) // camera_tracker.cpp:1407
+        continue;
+      if (pre[b].reg.n_inliers > K || !cands[b].dpt_map_dev || !cands[b].kp_dpts0_dev || !cands[b].kp_homo0_dev ||
+          !vcands[b].feat1_dev || !vcands[b].grad1_dev || !vcands[b].mask1_dev)
+        return SAGE_E_INVALID;
+      surv[ns++] = b;
+    }
+  }
+  for (int b = 0; b < B; ++b)
+    std::memset(&results[b], 0, sizeof(results[b]));
+  if (ns == 0)
+    return SAGE_OK;
+
+  // 1. the survivors' keypoint terms: one launch
+  const SageCamera &cam = query->pyr.cam[0];
+  VerifyGatherParams G{};
+  G.divisor0 = query_depth_divisor; G.cx = cam.cx; G.cy = cam.cy; G.fx = cam.fx; G.fy = cam.fy; G.Wf = (float)(int)cam.w;
+  G.HW = (long long)cam.w * (long long)cam.h;
+  G.K = K;
+  int max_n = 0;
+  for (int s = 0; s < ns; ++s)
+  {
+    const int b = surv[s];
+    VerifyGatherItem &it = G.item[s];
+    it.kp_homo0 = cands[b].kp_homo0_dev; it.kp_dpts0 = cands[b].kp_dpts0_dev; it.dpt_map = cands[b].dpt_map_dev;
+    it.raw = raw_matched_loc1d + (size_t)b * K; it.inlier_kp = inlier_kp_dev + (size_t)b * K;
+    it.out = kp_gathered_dev + (size_t)b * 8 * K; it.n = pre[b].reg.n_inliers;
+    max_n = std::max(max_n, it.n);
+  }
+  hipLaunchKernelGGL(verify_gather_kernel, dim3((max_n + kBlock - 1) / kBlock, ns), dim3(kBlock), 0, ws->stream, G);
+  SAGE_HIP(hipGetLastError());
+
+  // 2.-4. start values, weights, one batch over the survivors (the gather is ahead of its launches in the stream)
+  SageLmConfig lm = *cfg;
+  lm.no_overlap_error = 0.f; // use_match_geom: the no-overlap exit is off (camera_tracker.cpp:1515)
+  SageTrackProblem probs[SAGE_TRACK_MAX_BATCH];
+  float pose12[SAGE_TRACK_MAX_BATCH * 12], scale[SAGE_TRACK_MAX_BATCH], err[SAGE_TRACK_MAX_BATCH];
+  int iters[SAGE_TRACK_MAX_BATCH], status[SAGE_TRACK_MAX_BATCH];
+  for (int s = 0; s < ns; ++s)
+  {
+    const int b = surv[s];
+    const SageRegistrationResult &reg = pre[b].reg;
+    const float *g = kp_gathered_dev + (size_t)b * 8 * K;
+    SageTrackProblem &p = probs[s];
+    std::memset(&p, 0, sizeof(p));
+    p.ws = ws;
+    p.use_photo = 1;
+    p.mask1_dev = vcands[b].mask1_dev; p.dpts0_dev = query->unscaled_dpts0_dev; p.homo_dev = query->homo_dev;
+    p.feat0s_dev = query->feat0s_dev; p.feat1_dev = vcands[b].feat1_dev; p.grad1_dev = vcands[b].grad1_dev;
+    p.weights_dev = query->weights_dev; p.pyr = query->pyr; p.eps = query->eps; p.N = query->N; p.FS = query->FS;
+    p.use_keypoints = 1; p.NK = reg.n_inliers;
+    p.kp_homo0_dev = g; p.kp_dpts0_dev = g + 3 * (size_t)K; p.kp_matched_homo1_dev = g + 4 * (size_t)K;
+    p.kp_matched_dpts1_dev = g + 7 * (size_t)K;
+    p.kp_loss_param = vcands[b].kp_loss_param;
+    p.kp_weight = pre[b].desc_match_inlier_ratio * match_geom_factor_weight; // :414, :742
+    for (int i = 0; i < 9; ++i)
+      pose12[12 * s + i] = (float)reg.R[i];
+    for (int i = 0; i < 3; ++i)
+      pose12[12 * s + 9 + i] = (float)reg.t[i];
+    scale[s] = (float)reg.scale; // :750-761
+  }
+  int rc;
+  if ((rc = sage_track_frame_batch(&lm, 7, probs, ns, pose12, scale, err, iters, status, nullptr, 0, nullptr)))
+    return rc;
+
+  // 5. overlap statistics of every tracked survivor, one after the other
+  for (int s = 0; s < ns; ++s)
+  {
+    SageLoopVerifyResult &r = results[surv[s]];
+    r.tracked = 1;
+    r.status = status[s];
+    std::memcpy(r.pose12, pose12 + 12 * s, sizeof(r.pose12));
+    r.scale = scale[s];
+    r.error = err[s];
+    r.iters = iters[s];
+    if (status[s] != SAGE_OK)
+      continue;
+    SageOverlapStats ov;
+    if ((rc = sage_track_overlap(ws, r.pose12, r.pose12 + 9, query->valid_dpts0_dev, scale[s] / query_depth_divisor,
+                                 query->valid_homo_dev, query->M, &cam, query->mask_dev, query->eps, &ov)))
+      return rc;
+    r.area_ratio = ov.area_ratio;
+    r.inlier_ratio = ov.inlier_ratio;
+    r.average_motion = ov.average_motion;
+    r.area_inlier_ratio = ov.area_ratio * ov.inlier_ratio;
+  }
+  return SAGE_OK;
 }

@@ -1,7 +1,8 @@
 // runtime_internal.h -- shared by the host-runtime translation units behind the C ABI (include/sage_ba.h):
 //   operators.hip       workspaces (work-list cache, ticket wait), the per-edge operator API (df::*_calculate mirrors): an
 //                       enqueue function per family + the public wrappers that wait; the producer entry points
-//   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame): one evaluation over the enqueue functions
+//   tracker.hip         tracker wiring of the LM callbacks (sage_track_frame): one evaluation over the enqueue functions; B
+//                       problems in lock-step (sage_track_frame_batch): one round over the batched launches
 //   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
 //   depth_scale.hip     the mapper's depth-scale correction and device medians (sage_depth_scale_ratio, sage_median_f32):
 //                       the per-point kernel and the exact radix selection
@@ -198,7 +199,12 @@ struct SageWorkspace
   // tracker wiring (sage_track_frame): one evaluation = several operator launches that write their results into trk_host,
   // then one ticket.  Buffers persist across frames.
   DevBuf trk_dpts, trk_kp_dpts; // dof 7: depths scaled for the evaluation
-  PinnedBuf trk_host;           // TrackHost, from the first tracked frame on
+  PinnedBuf trk_host;           // TrackHost, from the first tracked frame on; [B] of them from a batch of B on
+  // batched tracker (sage_track_frame_batch): the call's pinned tables (TrackBatchProblem [B] | KpTrackProblem [B] | the
+  // rounds' request lists | the round's scale items | the rounds' work items), the problems' partial records, and (dof 7)
+  // the round's scaled depths: per problem its samples' [N], then its keypoints' [NK]
+  PinnedBuf trk_table;
+  DevBuf trk_bpart, trk_bdpts;
   // overlap statistics (sage_track_overlap, overlap.hip): per-workgroup partials + survivor counters, the survivors of
   // both hull sets, and the pinned region the finish kernel publishes into; all grow with M and go with the workspace
   DevBuf ov_part, ov_surv;

@@ -121,6 +121,37 @@ struct WorkItem
   int32_t tile;
 };
 
+// Batched tracker (sage_track_frame_batch): one problem of the call's table.  The table sits in pinned memory the kernels
+// read through scalar loads: written once per call, E.scale0 before every round the problem takes part in.
+struct TrackBatchProblem
+{
+  TrackEdge E;           // R, t: the pose slot of the problem's TrackHost; scale0: the scale being evaluated; dpts0: the
+                         // caller's depths (dof 6) or the problem's slice of the round's scaled depths (dof 7)
+  int32_t n_tiles;       // 256-pixel tiles = partial records of the problem
+  int32_t partial_first; // its first record, in records of kTrackScalars floats
+  float *AtA, *Atb, *stats; // the photometric slots of the problem's TrackHost
+};
+
+struct ScaleBatchItem // one array of the batched scale pass (dof 7): out[i] = mult * in[i], i < n
+{
+  const float *in;
+  float *out;
+  float mult;
+  int32_t n;
+};
+
+struct TrackBatchParams
+{
+  const TrackBatchProblem *probs;
+  const WorkItem *work;      // the launch's items: (problem, tile), a problem's tiles ascending
+  const int32_t *requests;   // the problems the launch evaluates, ascending: one finalize workgroup each
+  float *partials;
+  SagePyramid pyr;
+  float eps;
+  int dof;
+  int exact_coord;           // set by the launch (pyramid_is_dyadic)
+};
+
 // partial-sum layouts (floats per workgroup)
 //   photometric: 40 scalars (37 used) + NT tiles of 16x16 MFMA accumulators (raw [tile][reg][lane])
 //     CS=32: tiles {cc00, cc01, cc11, X_lo, X_hi};  CS=16: {cc00, X_lo}
@@ -208,6 +239,11 @@ hipError_t launch_track_linearize(hipStream_t s, int dof, int FS, const TrackEdg
                                   const SagePyramid &pyr, float eps, const EdgeOut &out);
 hipError_t launch_track_error(hipStream_t s, int FS, const TrackEdge &edge, const LaunchCommon &lc,
                               const SagePyramid &pyr, float eps, float *stats);
+// the photometric term of a round of a batched tracker call: the main kernel over n_work items, then one finalize workgroup
+// per request; jac chooses linearize or error-only (dof is read by the linearize alone)
+hipError_t launch_track_batch(hipStream_t s, bool jac, int FS, TrackBatchParams p, int n_work, int n_requests);
+// out[i] = mult * in[i] for every item of a (pinned) table in one launch; max_n: the longest item
+hipError_t launch_scale_batch(hipStream_t s, const ScaleBatchItem *items, int n_items, int max_n);
 hipError_t launch_depth_and_grad(hipStream_t s, int CS, float *dpt, float *grad, const float *bias,
                                  const float *basis, const float *code, const float *scale_dev, float scale,
                                  int H, int W);

@@ -23,21 +23,20 @@ struct TrackParams
 
 __device__ __forceinline__ int sidx7(int i, int j) { return i * 7 - (i * (i - 1)) / 2 + (j - i); } // i<=j<7
 
+// One 256-pixel tile of one tracker edge: the per-pixel body and the workgroup's sums -> `record` (37 floats with JAC, else
+// 2).  Shared by the one-edge kernel (track_kernel: E in the kernel arguments) and the batched one (track_batch_kernel: E
+// from the call's problem table)
 template <int FS, bool JAC>
-__global__ __launch_bounds__(kBlock) void track_kernel(const TrackParams prm)
+__device__ __forceinline__ void track_tile(const TrackEdge &E, int tile, const SagePyramid &pyr, float eps, int dof_,
+                                           int exact_coord, float *record)
 {
   __shared__ float s_red[kWaves * kTrackScalars];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  WorkItem wi = prm.work[blockIdx.x];
-  wi.tile = uni(wi.tile);
-  const TrackEdge &E = prm.E; // kernel argument: already in SGPRs
   const int N = E.N;
-  const int n = wi.tile * kTile + tid;
+  const int n = tile * kTile + tid;
   const bool in_range = n < N;
   const int nn = in_range ? n : 0;
   const Pose p10 = load_pose2(E.R, E.t);
-  const SagePyramid &pyr = prm.pyr;
-  const int exact_coord = prm.exact_coord;
   const float fx0 = pyr.cam[0].fx, fy0 = pyr.cam[0].fy, cx0 = pyr.cam[0].cx, cy0 = pyr.cam[0].cy;
   const int W0 = (int)pyr.cam[0].w, H0 = (int)pyr.cam[0].h;
 
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void track_kernel(const TrackParams prm)
     rh[i] = p10.R[i * 3 + 0] * hm[0] + p10.R[i * 3 + 1] * hm[1] + p10.R[i * 3 + 2] * hm[2];
     X[i] = d * rh[i] + p10.t[i];
   }
-  const bool pos = X[2] > prm.eps;
+  const bool pos = X[2] > eps;
   const float inv_z = 1.0f / X[2];
   const float p = (X[0] / X[2]) * fx0 + cx0;
   const float q = (X[1] / X[2]) * fy0 + cy0;
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void track_kernel(const TrackParams prm)
     const float x_z = X[0] * inv_z, y_z = X[1] * inv_z;
     float Q[2][7] = {{inv_z, 0.f, -x_z * inv_z, -x_z * y_z, 1.f + x_z * x_z, -y_z, 0.f},
                      {0.f, inv_z, -y_z * inv_z, -(1.f + y_z * y_z), x_z * y_z, x_z, 0.f}};
-    if (prm.dof == 7)
+    if (dof_ == 7)
     {
       Q[0][6] = (rh[0] * inv_z - X[0] * rh[2] * inv_z * inv_z) * d / E.scale0;
       Q[1][6] = (rh[1] * inv_z - X[1] * rh[2] * inv_z * inv_z) * d / E.scale0;
@@ -174,15 +173,42 @@ __global__ __launch_bounds__(kBlock) void track_kernel(const TrackParams prm)
       s_red[wave * kTrackScalars + k] = s;
   }
   __syncthreads();
-  const int PP = JAC ? kTrackScalars : 2;
   if (tid < nsc)
   {
     float a = 0.f;
 #pragma unroll
     for (int w = 0; w < kWaves; ++w)
       a += s_red[w * kTrackScalars + tid];
-    prm.partials[(size_t)blockIdx.x * PP + tid] = a;
+    record[tid] = a;
   }
+}
+
+template <int FS, bool JAC>
+__global__ __launch_bounds__(kBlock) void track_kernel(const TrackParams prm)
+{
+  constexpr int PP = JAC ? kTrackScalars : 2;
+  WorkItem wi = prm.work[blockIdx.x];
+  wi.tile = uni(wi.tile);
+  // (prm.E: kernel argument, already in SGPRs)
+  track_tile<FS, JAC>(prm.E, wi.tile, prm.pyr, prm.eps, prm.dof, prm.exact_coord, prm.partials + (size_t)blockIdx.x * PP);
+}
+
+// ---- batched tracker (sage_track_frame_batch): one launch over the (problem, tile) items of every problem that asked for
+// this kind of evaluation in the round; the problem's edge comes from the call's table (pinned: written once per call, the
+// scale per round) through scalar loads -- 32 TrackEdges do not fit the kernel arguments.  Records of a problem sit at its
+// own offset, at the stride of the one-edge kernel
+template <int FS, bool JAC>
+__global__ __launch_bounds__(kBlock) void track_batch_kernel(const TrackBatchParams prm)
+{
+  constexpr int PP = JAC ? kTrackScalars : 2;
+  WorkItem wi = prm.work[blockIdx.x];
+  wi.edge = uni(wi.edge);
+  wi.tile = uni(wi.tile);
+  const TrackBatchProblem &P = prm.probs[wi.edge];
+  // (the edge's fields are read where they are used: copied into registers up front they do not fit the SGPR file next to
+  // the pyramid, and table loads, unlike kernel arguments, are not loaded again on demand)
+  track_tile<FS, JAC>(P.E, wi.tile, prm.pyr, prm.eps, prm.dof, prm.exact_coord,
+                      prm.partials + (size_t)P.partial_first * kTrackScalars + (size_t)wi.tile * PP);
 }
 
 struct TrackFinalizeParams
@@ -193,7 +219,8 @@ struct TrackFinalizeParams
   int n_tiles, dof, levels, jac;
 };
 
-__global__ void track_finalize_kernel(const TrackFinalizeParams prm)
+// sums an edge's records in ascending tile order (one workgroup) and normalises; shared by both finalize kernels
+__device__ __forceinline__ void track_finalize_body(const TrackFinalizeParams &prm)
 {
   __shared__ float s[kTrackScalars];
   const int tid = threadIdx.x;
@@ -231,6 +258,16 @@ __global__ void track_finalize_kernel(const TrackFinalizeParams prm)
   }
   if (tid < D)
     prm.Atb[tid] = ok ? s[28 + tid] / n_in : 0.f;
+}
+
+__global__ void track_finalize_kernel(const TrackFinalizeParams prm) { track_finalize_body(prm); }
+
+// one workgroup per request of the round: the problem's records -> its TrackHost
+__global__ void track_batch_finalize_kernel(const TrackBatchParams prm, int jac)
+{
+  const TrackBatchProblem &P = prm.probs[prm.requests[blockIdx.x]];
+  track_finalize_body(TrackFinalizeParams{prm.partials + (size_t)P.partial_first * kTrackScalars, P.E.weights, P.AtA, P.Atb, P.stats,
+                                          P.n_tiles, prm.dof, prm.pyr.levels, jac});
 }
 
 template <int FS>
@@ -273,6 +310,46 @@ hipError_t launch_track_error(hipStream_t s, int FS, const TrackEdge &edge, cons
     return track_impl<16>(s, false, 6, edge, lc, pyr, eps, nullptr, nullptr, stats);
   if (FS == 32)
     return track_impl<32>(s, false, 6, edge, lc, pyr, eps, nullptr, nullptr, stats);
+  return hipErrorInvalidValue;
+}
+
+template <int FS>
+static hipError_t track_batch_impl(hipStream_t s, bool jac, const TrackBatchParams &p, int n_work, int n_requests)
+{
+  if (jac)
+    hipLaunchKernelGGL((track_batch_kernel<FS, true>), dim3(n_work), dim3(kBlock), 0, s, p);
+  else
+    hipLaunchKernelGGL((track_batch_kernel<FS, false>), dim3(n_work), dim3(kBlock), 0, s, p);
+  hipLaunchKernelGGL(track_batch_finalize_kernel, dim3(n_requests), dim3(64), 0, s, p, jac ? 1 : 0);
+  return hipGetLastError();
+}
+
+// the depths of a round of a batched dof-7 call: out[i] = mult * in[i] per item (a problem's photometric samples, its
+// keypoints), ONE launch -- scale_array_kernel's product for every item of the round; grid (ceil(max n / 256), items)
+__global__ void scale_batch_kernel(const ScaleBatchItem *__restrict__ items)
+{
+  const ScaleBatchItem it = items[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < it.n)
+    it.out[i] = it.mult * it.in[i];
+}
+
+hipError_t launch_scale_batch(hipStream_t s, const ScaleBatchItem *items, int n_items, int max_n)
+{
+  if (n_items > 0 && max_n > 0)
+    hipLaunchKernelGGL(scale_batch_kernel, dim3((max_n + 255) / 256, n_items), dim3(256), 0, s, items);
+  return hipGetLastError();
+}
+
+hipError_t launch_track_batch(hipStream_t s, bool jac, int FS, TrackBatchParams p, int n_work, int n_requests)
+{
+  if ((p.dof != 6 && p.dof != 7) || n_work < 1 || n_requests < 1)
+    return hipErrorInvalidValue;
+  p.exact_coord = pyramid_is_dyadic(p.pyr) ? 0 : 1;
+  if (FS == 16)
+    return track_batch_impl<16>(s, jac, p, n_work, n_requests);
+  if (FS == 32)
+    return track_batch_impl<32>(s, jac, p, n_work, n_requests);
   return hipErrorInvalidValue;
 }
 

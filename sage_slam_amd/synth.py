@@ -673,10 +673,11 @@ def make_registration_problem(N: int, seed: int = 0, outlier_rate: float = 0.3, 
 LOOP_CANDIDATE_KINDS = ("planted", "self", "unrelated")
 
 
-def make_loop_candidates(seed: int, B: int, H: int = 48, W: int = 64, C: int = 16, K: int = 117, kinds=None, n_wrong: int = 8) -> dict:
+def make_loop_candidates(seed: int, B: int, H: int = 48, W: int = 64, C: int = 16, K: int = 117, kinds=None, n_wrong: int = 8,
+                         grid: int = 4) -> dict:
     """Inputs of ``sage_cycle_match_batch`` / ``sage_loop_precheck``: one query keyframe and B loop-closure candidates.
-    The query has a descriptor map [C, H, W] (iid normal), a smooth depth map [H*W] and the pixels of a 4-pixel grid 8 pixels
-    inside the border as possible keypoints; the camera has focal length 0.94 W.  Every candidate draws its own K keypoints from
+    The query has a descriptor map [C, H, W] (iid normal), a smooth depth map [H*W] and the pixels of a ``grid``-pixel grid (4; 2
+    for more keypoints than a small image has on that) 8 pixels inside the border as possible keypoints; the camera has focal length 0.94 W.  Every candidate draws its own K keypoints from
     that grid (all of them, in raster order, when the grid has exactly K; the reference shuffles the query's valid locations
     with the candidate's id as seed).  ``kinds[b]`` (default: "planted", "self", "unrelated", "planted", ... in turn):
       "planted"    the candidate sees the keypoints under its own similarity (s, R, t): each keypoint's descriptor is planted at
@@ -692,7 +693,7 @@ def make_loop_candidates(seed: int, B: int, H: int = 48, W: int = 64, C: int = 1
     rng = np.random.default_rng([seed, B, H, W, C, K])
     fx = fy = 0.9375 * W
     cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
-    gy, gx = np.meshgrid(np.arange(8, H - 7, 4), np.arange(8, W - 7, 4), indexing="ij")
+    gy, gx = np.meshgrid(np.arange(8, H - 7, grid), np.arange(8, W - 7, grid), indexing="ij")
     gx, gy = gx.reshape(-1), gy.reshape(-1)
     assert 2 <= K <= gx.size and 0 <= n_wrong <= K, (K, gx.size)
     kinds = list(kinds) if kinds is not None else [("planted", "self", "unrelated", "planted")[b % 4] for b in range(B)]
