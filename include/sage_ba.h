@@ -612,6 +612,70 @@ int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const 
                       float noise_multiplier, int noise_from, float *pts0, float *pts1, float *noise_bounds, float *homo1,
                       float *dpts1, int32_t *kept, int *M_host, float *mean_noise_depth_host);
 
+/* ---- B registrations in one call: the scale votes of all of them in one sort ----
+ * THE CONTRACT.  Row b of res, of inliers_host (row stride inliers_stride) and of probs[b].inliers_dev holds, byte for byte,
+ * what sage_robust_registration writes for problem b alone with p->noise_bound = probs[b].noise_bound (p->noise_bound itself
+ * is NOT read) -- whatever else is in the batch, in whatever order, and for every SAGE_REG_SORT_TILE.  Only the first
+ * n_inliers entries of an inlier row are written, as there.  sage_match_points_batch gives the same guarantee against
+ * sage_match_points (item b's six output arrays, M_host[b], mean_noise_depth_host[b]; M = 0: nothing else is written).
+ * Problems that do not vote: N < 2 gets the single call's answer (valid = 0, everything zero), takes no part in any launch
+ * and none of its pointers is read; a batch in which nothing votes launches nothing.  A problem whose vote is empty (every
+ * pair degenerate) gets valid = 0 with n_pairs and n_degenerate_pairs like the single call; its neighbours are unaffected.
+ * Layout: the voting problems are segments of one keys / payload / pairs allocation, ordered by descending P (the power of
+ * two >= max(2 pairs, 4096), as the single call chooses it), rows of equal P in the caller's order; the caller's row order
+ * never changes.  Every kernel of the vote runs once over (segment, block) items; a sort stage with distance k runs over the
+ * segments with P >= k.  LAUNCHES: those of the largest problem alone (sage_robust_registration: its sort's launches + 6) + 1
+ * -- the ticket is a launch of its own behind the per-problem publish -- whatever B and the other N; 0 when nothing votes.
+ * The one exception: a batch in which ONE problem votes takes sage_robust_registration's own path for it (the batched
+ * kernels with one segment measured 0.97 x the single call): its launches exactly, without the + 1.
+ * When an inliers_dev row with inliers is asked for: 2 more (one copy kernel over all such rows, one ticket).
+ * sage_robust_registration_batch_launches reports what the workspace's last batch spent, sage_robust_registration_batch_plan
+ * what a batch of given sizes will spend, without a device.
+ * Workspace bytes, with the sums over the voting problems: device Sum (12 P + 16 pairs + 160 (P / 2048) + 80), pinned
+ * Sum (64 + 32 N): B = 20 at N = 512: 105.2 MB and 0.33 MB; the cap, 32 x 1024: 673.5 MB and 1.05 MB.  Kept by the workspace.
+ * Waits: one for the votes; the finishes (sage_registration_finish, serial, in row order) run on the calling thread; one more
+ * wait when an inliers_dev row was written.
+ * SAGE_E_INVALID, before anything touches the device: NULL ws, probs, p or res with B > 0; B < 0 or B > SAGE_REG_MAX_BATCH; an
+ * N < 0 or > SAGE_REG_MAX_POINTS; for a problem with N >= 2 a NULL src_dev, dst_dev or noise_bounds_dev or a noise_bound that
+ * is not positive and finite; inliers_host given with inliers_stride below the largest N; the parameter checks of
+ * sage_robust_registration with the same codes (noise_bound apart), SAGE_E_UNSUPPORTED for the modes included.  B = 0:
+ * SAGE_OK, nothing is read, checked further or launched. */
+#define SAGE_REG_MAX_BATCH 32
+typedef struct SageRegistrationProblem /* device pointers; N may differ per problem */
+{
+  const float *src_dev, *dst_dev, *noise_bounds_dev; /* [N][3], [N][3], [N] */
+  int32_t N;                                         /* 0 .. SAGE_REG_MAX_POINTS */
+  double noise_bound;                                /* replaces p->noise_bound for this problem */
+  int32_t *inliers_dev;                              /* [N] or NULL */
+} SageRegistrationProblem;
+int sage_robust_registration_batch(SageWorkspace *ws, const SageRegistrationProblem *probs, int B, const SageRegistrationParams *p,
+                                   SageRegistrationResult *res /* [B] */, int32_t *inliers_host /* [B][inliers_stride] or NULL */,
+                                   int inliers_stride);
+/* host only, no device: what a batch of these sizes will do.  N [B]; every output may be NULL.  device_bytes, pinned_bytes:
+ * the formulas above; launches: of the votes (at the SAGE_REG_SORT_TILE in effect); order [B]: the rows of the voting
+ * problems in the order of their segments, then -1 for every problem that does not vote.  SAGE_E_INVALID for B out of range,
+ * NULL N with B > 0, an N out of range. */
+int sage_robust_registration_batch_plan(const int32_t *N, int B, int64_t *device_bytes, int64_t *pinned_bytes, int32_t *launches,
+                                        int32_t *order /* [B] or NULL */);
+/* the kernel launches of the workspace's last sage_robust_registration_batch (0: none yet, nothing voted, or NULL ws) */
+int sage_robust_registration_batch_launches(const SageWorkspace *ws);
+typedef struct SageMatchPointsItem /* device pointers: one problem's arrays of sage_match_points */
+{
+  const int32_t *cyc_inlier_flags;     /* [K] */
+  const int64_t *raw_matched_loc1d_1;  /* [K] */
+  const float *dpts0, *homo0;          /* [K], [K][3] */
+  const float *dpt_map_1;              /* [cam->w * cam->h] */
+  float *pts0, *pts1, *noise_bounds, *homo1, *dpts1; /* outputs: [K][3], [K][3], [K], [K][3], [K] */
+  int32_t *kept;                       /* output [K] */
+} SageMatchPointsItem;
+/* B gathers in one launch (one workgroup per problem; B = 1: sage_match_points itself) and one wait; K, W, the camera and the
+ * scalars are shared.  M_host [B];
+ * mean_noise_depth_host [B] or NULL.  SAGE_E_INVALID as sage_match_points per item, for B < 0 or B > SAGE_REG_MAX_BATCH and
+ * for NULL items or M_host with B > 0.  B = 0: SAGE_OK, nothing launched. */
+int sage_match_points_batch(SageWorkspace *ws, const SageMatchPointsItem *items, int B, float depth_divisor0, const SageCamera *cam,
+                            int K, int W, float noise_multiplier, int noise_from, int32_t *M_host /* [B] */,
+                            float *mean_noise_depth_host /* [B] or NULL */);
+
 /* ---- the loop detector's candidates: one query keyframe against B candidates in one call ----
  * LoopDetector::DetectLoop (core/system/loop_detector.cpp:143-163) and DetectLocalLoop (:282-319) run
  * CameraTracker::MatchGeoCheck on the query keyframe against up to loop_max_candidates = 20 (loop_local_active_window = 9)
@@ -641,11 +705,12 @@ int sage_cycle_match_batch_slices(const SageWorkspace *ws);
 
 /* sage_loop_precheck: the detector's loop body up to the ratio test (MatchGeoCheck -> the first FeatureMatchingGeo overload,
  * camera_tracker.cpp:575-768) for all B candidates.  A host composition, no arithmetic of its own: one
- * sage_cycle_match_batch (pixel_slices 0); then, in candidate order, every candidate that can still pass goes through
- * sage_match_points (depth_divisor0 = query_depth_divisor, noise_from 1, scratch outputs of the workspace) and
- * sage_robust_registration (src = pts0, dst = pts1; p->noise_bound is NOT read: it is replaced by
- * (noise_multiplier * mean_noise_depth) / ((cam->fx + cam->fy) / 2) evaluated in fp32 and widened).  Per candidate the fields
- * of the result equal those three calls on the same inputs.
+ * sage_cycle_match_batch (pixel_slices 0); then every candidate that can still pass goes through sage_match_points
+ * (depth_divisor0 = query_depth_divisor, noise_from 1, scratch outputs of the workspace: one sage_match_points_batch over all
+ * of them) and sage_robust_registration (src = pts0, dst = pts1; p->noise_bound is NOT read: it is replaced by
+ * (noise_multiplier * mean_noise_depth) / ((cam->fx + cam->fy) / 2) evaluated in fp32 and widened: one
+ * sage_robust_registration_batch over the survivors).  Per candidate the fields of the result equal those three calls on the
+ * same inputs.
  * The prune: a candidate with (float)n_cycle / (float)K < min_desc_inlier_ratio gets registered = 0, both ratios 0 and no
  * further launch.  That is exact: the reference's desc_match_inlier_ratio is |translation inliers| / K and the translation
  * inliers are among the cycle-consistent matches, so the detector's `continue` (loop_detector.cpp:159, :314) is taken either
@@ -656,8 +721,9 @@ int sage_cycle_match_batch_slices(const SageWorkspace *ws);
  * raw_matched_loc1d.  raw_matched_loc1d, inlier_flags: device [B][K], as sage_cycle_match_batch writes them.
  * SAGE_E_INVALID (nothing is launched) as for sage_cycle_match_batch, and for NULL cands, cam, p or results, a NULL member of a
  * candidate, fx / fy not positive and finite, K > SAGE_REG_MAX_POINTS; the registration's parameter checks answer as in
- * sage_robust_registration (noise_bound apart).  B = 0 or K = 0: SAGE_OK, the results zeroed.  Waits: one for the batch, two
- * per survivor, one at the end when any inlier was written. */
+ * sage_robust_registration (noise_bound apart).  B = 0 or K = 0: SAGE_OK, the results zeroed.  Waits: four whatever B -- one
+ * for the cycle-match batch, one for the gathers, one for the votes, one at the end when any inlier was written.  The
+ * workspace's scratch holds the B candidates' gathered points (48 K bytes each) and the batch of votes (above). */
 typedef struct SageLoopCandidate /* device pointers */
 {
   const float *desc_dev;           /* kf->feat_desc [C,H,W] */

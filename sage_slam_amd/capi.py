@@ -153,6 +153,8 @@ SYMBOLS = [
     "sage_tracker_match_geom_jac_error_calculate", "sage_tracker_match_geom_error_calculate", "sage_cycle_match",
     "sage_robust_registration", "sage_tls_estimate", "sage_registration_finish", "sage_match_points",
     "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck", "sage_loop_verify",
+    "sage_robust_registration_batch", "sage_robust_registration_batch_plan", "sage_robust_registration_batch_launches",
+    "sage_match_points_batch",
 ]
 
 
@@ -1733,6 +1735,124 @@ def match_points(ws: "Workspace", flags, raw_matched_loc1, dpts0, homo0, depth_d
     m = M.value
     return dict(M=m, mean_depth=np.float32(mean.value), pts0=pts0[:m], pts1=pts1[:m], noise_bounds=nb[:m], homo1=homo1[:m],
                 dpts1=dpts1[:m], kept=kept[:m])
+
+
+# --------------------------------------------------------------------------- B registrations in one call
+SAGE_REG_MAX_BATCH = 32
+
+
+class SageRegistrationProblem(C.Structure):
+    _fields_ = [("src_dev", C.c_void_p), ("dst_dev", C.c_void_p), ("noise_bounds_dev", C.c_void_p), ("N", C.c_int32),
+                ("noise_bound", C.c_double), ("inliers_dev", C.c_void_p)]
+
+
+class SageMatchPointsItem(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("cyc_inlier_flags", "raw_matched_loc1d_1", "dpts0", "homo0", "dpt_map_1", "pts0", "pts1",
+                                          "noise_bounds", "homo1", "dpts1", "kept")]
+
+
+def robust_registration_batch_raw(ws_handle, probs_ptr, B, params_ptr, res_ptr, inliers_host_ptr, inliers_stride) -> int:
+    """``sage_robust_registration_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_robust_registration_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    return int(f(ws_handle, probs_ptr, int(B), params_ptr, res_ptr, inliers_host_ptr, int(inliers_stride)))
+
+
+def robust_registration_batch_plan_raw(N_ptr, B, device_bytes_ptr, pinned_bytes_ptr, launches_ptr, order_ptr) -> int:
+    f = lib().sage_robust_registration_batch_plan
+    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    return int(f(N_ptr, int(B), device_bytes_ptr, pinned_bytes_ptr, launches_ptr, order_ptr))
+
+
+def robust_registration_batch_plan(N) -> dict:
+    """What a batch of problems with these point counts will do, through ``sage_robust_registration_batch_plan`` (host only).
+    -> dict(device_bytes, pinned_bytes, launches, order): ``order`` lists the rows of the voting problems (N >= 2) in the
+    order of their segments (descending P, stable)."""
+    n = np.ascontiguousarray(N, np.int32).reshape(-1)
+    dev, pin = C.c_int64(), C.c_int64()
+    launches = C.c_int32()
+    order = np.full(max(n.size, 1), -1, np.int32)
+    _chk(robust_registration_batch_plan_raw(n.ctypes.data if n.size else None, n.size, C.addressof(dev), C.addressof(pin),
+                                            C.addressof(launches), order.ctypes.data), "sage_robust_registration_batch_plan")
+    order = order[:n.size]
+    return dict(device_bytes=dev.value, pinned_bytes=pin.value, launches=launches.value, order=[int(b) for b in order if b >= 0])
+
+
+def robust_registration_batch_launches(ws: "Workspace") -> int:
+    """the kernel launches of the workspace's last ``robust_registration_batch``"""
+    f = lib().sage_robust_registration_batch_launches
+    f.argtypes = [C.c_void_p]
+    return int(f(ws.h))
+
+
+def robust_registration_batch(ws: "Workspace", problems, params=None, device_inliers: bool = False) -> list:
+    """B solves through ``sage_robust_registration_batch``.  problems: a list of dicts with ``src``, ``dst`` [N, 3],
+    ``noise_bounds`` [N] (contiguous float32 cuda tensors; N may be 0 or 1) and ``noise_bound`` (the scalar bound of that
+    problem); params: a dict, a ``SageRegistrationParams`` or None (its noise_bound is not read).  -> a list of B dicts as
+    ``robust_registration`` returns them; row b equals that call on problem b alone."""
+    import torch
+    B = len(problems)
+    p = params if isinstance(params, SageRegistrationParams) else registration_params(params)
+    arr = (SageRegistrationProblem * max(B, 1))()
+    res = (SageRegistrationResult * max(B, 1))()
+    stride = max([int(q["src"].shape[0]) for q in problems] + [1])
+    inl = np.zeros((max(B, 1), stride), np.int32)
+    inl_dev = []
+    for b, q in enumerate(problems):
+        N = int(q["src"].shape[0])
+        assert q["src"].dtype == torch.float32 and q["dst"].dtype == torch.float32 and q["noise_bounds"].dtype == torch.float32
+        assert tuple(q["dst"].shape) == (N, 3) and q["noise_bounds"].numel() == N
+        inl_dev.append(torch.zeros(max(N, 1), dtype=torch.int32, device="cuda") if device_inliers else None)
+        arr[b] = SageRegistrationProblem(dptr(q["src"]).value, dptr(q["dst"]).value, dptr(q["noise_bounds"]).value, N,
+                                         float(q["noise_bound"]), dptr(inl_dev[b]).value)
+    _chk(robust_registration_batch_raw(ws.h, C.addressof(arr), B, C.addressof(p), C.addressof(res), inl.ctypes.data, stride),
+         "sage_robust_registration_batch")
+    out = []
+    for b in range(B):
+        o = _reg_result(res[b])
+        o["inliers"] = inl[b, :res[b].n_inliers].copy()
+        if device_inliers:
+            o["inliers_dev"] = inl_dev[b][:res[b].n_inliers]
+        out.append(o)
+    return out
+
+
+def match_points_batch_raw(ws_handle, items_ptr, B, divisor0, cam_ptr, K, W, mult, noise_from, M_ptr, mean_ptr) -> int:
+    """``sage_match_points_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_match_points_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, items_ptr, int(B), float(divisor0), cam_ptr, int(K), int(W), float(mult), int(noise_from), M_ptr, mean_ptr))
+
+
+def match_points_batch(ws: "Workspace", problems, depth_divisor0, cam, W, noise_multiplier, noise_from: int = 1) -> list:
+    """B gathers through ``sage_match_points_batch``.  problems: a list of dicts with ``flags`` [K] int32, ``raw_matched_loc1``
+    [K] int64, ``dpts0`` [K], ``homo0`` [K, 3], ``dpt_map_1`` [H*W] (contiguous cuda tensors, one K for all).  -> a list of B
+    dicts as ``match_points`` returns them, and under ``full`` the uncut output tensors (zero where nothing was written)."""
+    import torch
+    B = len(problems)
+    K = int(problems[0]["flags"].numel()) if B else 1
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    items = (SageMatchPointsItem * max(B, 1))()
+    outs = []
+    for b, q in enumerate(problems):
+        assert q["flags"].dtype == torch.int32 and q["raw_matched_loc1"].dtype == torch.int64 and int(q["flags"].numel()) == K
+        dev = q["flags"].device
+        o = dict(pts0=torch.zeros(K, 3, dtype=torch.float32, device=dev), pts1=torch.zeros(K, 3, dtype=torch.float32, device=dev),
+                 noise_bounds=torch.zeros(K, dtype=torch.float32, device=dev), homo1=torch.zeros(K, 3, dtype=torch.float32, device=dev),
+                 dpts1=torch.zeros(K, dtype=torch.float32, device=dev), kept=torch.zeros(K, dtype=torch.int32, device=dev))
+        outs.append(o)
+        items[b] = SageMatchPointsItem(*[dptr(t).value for t in (q["flags"], q["raw_matched_loc1"], q["dpts0"], q["homo0"], q["dpt_map_1"],
+                                                                 o["pts0"], o["pts1"], o["noise_bounds"], o["homo1"], o["dpts1"], o["kept"])])
+    M = np.zeros(max(B, 1), np.int32); mean = np.zeros(max(B, 1), np.float32)
+    _chk(match_points_batch_raw(ws.h, C.addressof(items), B, depth_divisor0, C.addressof(c), K, W, noise_multiplier, noise_from,
+                                M.ctypes.data, mean.ctypes.data), "sage_match_points_batch")
+    res = []
+    for b in range(B):
+        m = int(M[b])
+        r = {k: v[:m] for k, v in outs[b].items()}
+        r.update(M=m, mean_depth=np.float32(mean[b]), full=outs[b])
+        res.append(r)
+    return res
 
 
 # --------------------------------------------------------------------------- the loop detector's candidates in one call

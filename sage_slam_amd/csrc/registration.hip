@@ -23,13 +23,17 @@
 //                          finish reads), into the workspace's pinned record; posts the ticket
 // then registration_host.cpp's finish on the host (O(N), fp64).  No float atomics (two integer counters), no workgroup
 // waits for another, every loop is bounded by N, the tile or the number of tiles.  All stores are plain C++.
+// Every kernel is a thin wrapper around a __device__ body that takes ONE problem's arrays and an index into them; the batched
+// kernels (sage_robust_registration_batch, sage_match_points_batch: "the batched vote" below) call the same bodies over
+// (problem, block) items, the problems lying as segments in the same allocations (the layout: registration_host.cpp).
 #include "runtime_internal.h"
 
 namespace
 {
 constexpr int kRegTile = 2048;                  // endpoints per workgroup of the scan
 constexpr int kSortTileMax = 4096;              // endpoints per workgroup of the sort's LDS stages: 1024, 2048 or 4096
-constexpr int kSortTileDefault = 1024;          // (12 bytes of LDS each.  Measured at N = 512: 0.307 / 0.329 / 0.440 ms per call with 1024 /
+                                                // the default, registration_sort_tile(), is 1024
+                                                // (12 bytes of LDS each.  Measured at N = 512: 0.307 / 0.329 / 0.440 ms per call with 1024 /
                                                 // 2048 / 4096 -- the LDS stages are what takes the time, and small tiles spread them over
                                                 // more CUs; SAGE_REG_SORT_TILE picks another: scripts/registration_bench.py)
 constexpr int kRegPerLane = kRegTile / kBlock;  // 8 consecutive endpoints per lane of the scan
@@ -73,13 +77,12 @@ __device__ __forceinline__ uint64_t reg_key(double v)
 
 __device__ __forceinline__ int reg_row_start(int i, int N) { return i * N - i * (i + 1) / 2; }
 
-__global__ __launch_bounds__(kBlock) void reg_pair_kernel(const float *__restrict__ src, const float *__restrict__ dst,
-                                                          const float *__restrict__ nb, int N, int n_pairs, int half_P,
-                                                          double sqrt_cbar2, uint64_t *keys, uint32_t *payload, double2 *pairs,
-                                                          int *counters)
+// pair p of one problem (keys, payload, pairs, counters: that problem's): its measurement, its two endpoints
+__device__ __forceinline__ void reg_pair_body(const float *__restrict__ src, const float *__restrict__ dst,
+                                              const float *__restrict__ nb, int N, int n_pairs, int half_P, double sqrt_cbar2,
+                                              uint64_t *keys, uint32_t *payload, double2 *pairs, int *counters, int p)
 {
 #pragma clang fp contract(off) // the reference's operations one by one: no fused multiply-add
-  const int p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= half_P)
     return;
   uint64_t k0 = kRegPadKey, k1 = kRegPadKey;
@@ -122,23 +125,31 @@ __global__ __launch_bounds__(kBlock) void reg_pair_kernel(const float *__restric
   reinterpret_cast<uint2 *>(payload)[p] = make_uint2(q0, q1);
 }
 
+__global__ __launch_bounds__(kBlock) void reg_pair_kernel(const float *__restrict__ src, const float *__restrict__ dst,
+                                                          const float *__restrict__ nb, int N, int n_pairs, int half_P,
+                                                          double sqrt_cbar2, uint64_t *keys, uint32_t *payload, double2 *pairs,
+                                                          int *counters)
+{
+  reg_pair_body(src, dst, nb, N, n_pairs, half_P, sqrt_cbar2, keys, payload, pairs, counters, blockIdx.x * kBlock + threadIdx.x);
+}
+
 __device__ __forceinline__ bool reg_after(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb)
 {
   return ka > kb || (ka == kb && pa > pb);
 }
 
 // the bitonic network's stages k_first .. k_last (powers of two), each from the distance min(k / 2, kSortTile / 2) down to 1, on
-// one tile in LDS.  The direction of a compare-exchange comes from the endpoint's global position
+// one tile in LDS (keys, payload: the tile's).  The direction of a compare-exchange comes from the endpoint's position in
+// its own problem: base is the tile's first
 template <int kSortTile>
-__global__ __launch_bounds__(kBlock) void reg_sort_tile_kernel(uint64_t *keys, uint32_t *payload, int k_first, int k_last)
+__device__ __forceinline__ void reg_sort_tile_body(uint64_t *keys, uint32_t *payload, int base, int k_first, int k_last, uint64_t *s_k,
+                                                   uint32_t *s_p)
 {
-  __shared__ uint64_t s_k[kSortTile];
-  __shared__ uint32_t s_p[kSortTile];
-  const int tid = threadIdx.x, base = blockIdx.x * kSortTile;
+  const int tid = threadIdx.x;
   for (int q = tid; q < kSortTile; q += kBlock)
   {
-    s_k[q] = keys[base + q];
-    s_p[q] = payload[base + q];
+    s_k[q] = keys[q];
+    s_p[q] = payload[q];
   }
   __syncthreads();
   for (int k = k_first; k <= k_last; k <<= 1)
@@ -162,19 +173,27 @@ __global__ __launch_bounds__(kBlock) void reg_sort_tile_kernel(uint64_t *keys, u
     }
   for (int q = tid; q < kSortTile; q += kBlock)
   {
-    keys[base + q] = s_k[q];
-    payload[base + q] = s_p[q];
+    keys[q] = s_k[q];
+    payload[q] = s_p[q];
   }
 }
 
-// one stage (k, j) across tiles: a lane per compare-exchange
-__global__ __launch_bounds__(kBlock) void reg_sort_stage_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int half_P)
+template <int kSortTile>
+__global__ __launch_bounds__(kBlock) void reg_sort_tile_kernel(uint64_t *keys, uint32_t *payload, int k_first, int k_last)
 {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= half_P)
-    return;
+  __shared__ uint64_t s_k[kSortTile];
+  __shared__ uint32_t s_p[kSortTile];
+  const int base = blockIdx.x * kSortTile;
+  reg_sort_tile_body<kSortTile>(keys + base, payload + base, base, k_first, k_last, s_k, s_p);
+}
+
+// one stage (k, j) across tiles: compare-exchange t.  top: k is the problem's own P, its last stage, which sorts upwards
+// wherever the problem lies (below its P the bit k of a position is the same in the problem and in the allocation: a
+// problem starts at a multiple of its P)
+__device__ __forceinline__ void reg_sort_stage_body(uint64_t *keys, uint32_t *payload, int k, int j, int t, bool top)
+{
   const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-  const bool up = (lo & k) == 0;
+  const bool up = top || (lo & k) == 0;
   const uint64_t ka = keys[lo], kb = keys[hi];
   const uint32_t pa = payload[lo], pb = payload[hi];
   if (reg_after(ka, pa, kb, pb) == up)
@@ -186,16 +205,21 @@ __global__ __launch_bounds__(kBlock) void reg_sort_stage_kernel(uint64_t *keys, 
   }
 }
 
-// two stages (k, j) and (k, j / 2) across tiles: a lane per four endpoints i0, i0 + j / 2, i0 + j, i0 + j + j / 2
-// (i0: the lane's index with two zero bits inserted at j / 2 and j; k > j, so the four share a direction)
-__global__ __launch_bounds__(kBlock) void reg_sort_stage2_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int quarter_P)
+__global__ __launch_bounds__(kBlock) void reg_sort_stage_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int half_P)
 {
   const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= quarter_P)
+  if (t >= half_P)
     return;
+  reg_sort_stage_body(keys, payload, k, j, t, false); // (lo < P: the bit P is clear)
+}
+
+// two stages (k, j) and (k, j / 2) across tiles: four endpoints i0, i0 + j / 2, i0 + j, i0 + j + j / 2
+// (i0: t with two zero bits inserted at j / 2 and j; k > j, so the four share a direction).  top: as above
+__device__ __forceinline__ void reg_sort_stage2_body(uint64_t *keys, uint32_t *payload, int k, int j, int t, bool top)
+{
   const int h = j >> 1;
   const int i0 = ((t & ~(h - 1)) << 2) | (t & (h - 1));
-  const bool up = (i0 & k) == 0;
+  const bool up = top || (i0 & k) == 0;
   const int at[4] = {i0, i0 + h, i0 + j, i0 + j + h};
   uint64_t kk[4];
   uint32_t pp[4];
@@ -226,6 +250,14 @@ __global__ __launch_bounds__(kBlock) void reg_sort_stage2_kernel(uint64_t *keys,
     keys[at[q]] = kk[q];
     payload[at[q]] = pp[q];
   }
+}
+
+__global__ __launch_bounds__(kBlock) void reg_sort_stage2_kernel(uint64_t *keys, uint32_t *payload, int k, int j, int quarter_P)
+{
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= quarter_P)
+    return;
+  reg_sort_stage2_body(keys, payload, k, j, t, false);
 }
 
 // what one sorted endpoint adds to the running sums
@@ -295,12 +327,12 @@ __device__ __forceinline__ void reg_block_scan(const double (&v)[kRegQ], double 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kBlock) void reg_tile_sums_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
-                                                               double *tile_sums)
+// tile `tile` of one problem (payload, pairs, tile_sums: that problem's): the totals of its 2048 endpoints
+__device__ __forceinline__ void reg_tile_sums_body(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                                   double *tile_sums, int tile, double (*s_wave)[kRegQ])
 {
 #pragma clang fp contract(off)
-  __shared__ double s_wave[kWaves][kRegQ];
-  const int at = blockIdx.x * kRegTile + threadIdx.x * kRegPerLane;
+  const int at = tile * kRegTile + threadIdx.x * kRegPerLane;
   double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int e = 0; e < kRegPerLane; ++e)
@@ -317,15 +349,22 @@ __global__ __launch_bounds__(kBlock) void reg_tile_sums_kernel(const uint32_t *_
   {
 #pragma unroll
     for (int c = 0; c < kRegQ; ++c)
-      tile_sums[(size_t)blockIdx.x * kRegRow + c] = total[c];
+      tile_sums[(size_t)tile * kRegRow + c] = total[c];
   }
 }
 
-// one workgroup: tile_offs[t] = the sums of the tiles before t, tile_offs[n_tiles] = the sums of all
-__global__ __launch_bounds__(kBlock) void reg_tile_offsets_kernel(const double *__restrict__ tile_sums, double *tile_offs, int n_tiles)
+__global__ __launch_bounds__(kBlock) void reg_tile_sums_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                                               double *tile_sums)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  reg_tile_sums_body(payload, pairs, tile_sums, blockIdx.x, s_wave);
+}
+
+// one workgroup per problem: tile_offs[t] = the sums of the tiles before t, tile_offs[n_tiles] = the sums of all
+__device__ __forceinline__ void reg_tile_offsets_body(const double *__restrict__ tile_sums, double *tile_offs, int n_tiles,
+                                                      double (*s_wave)[kRegQ])
 {
 #pragma clang fp contract(off)
-  __shared__ double s_wave[kWaves][kRegQ];
   const int per = (n_tiles + kBlock - 1) / kBlock;
   const int t0 = min(threadIdx.x * per, n_tiles), t1 = min(t0 + per, n_tiles);
   double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
@@ -352,6 +391,12 @@ __global__ __launch_bounds__(kBlock) void reg_tile_offsets_kernel(const double *
     for (int c = 0; c < kRegQ; ++c)
       tile_offs[(size_t)n_tiles * kRegRow + c] = total[c];
   }
+}
+
+__global__ __launch_bounds__(kBlock) void reg_tile_offsets_kernel(const double *__restrict__ tile_sums, double *tile_offs, int n_tiles)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  reg_tile_offsets_body(tile_sums, tile_offs, n_tiles, s_wave);
 }
 
 __device__ __forceinline__ bool reg_min_before(const RegMin &a, const RegMin &b) // a wins over b: smaller cost, then earlier
@@ -386,13 +431,12 @@ __device__ __forceinline__ RegMin reg_block_min(RegMin m, RegMin *s_min)
 
 // per tile: the inclusive running sums at every endpoint, the vote's cost there, the tile's first smallest cost.  A NaN cost
 // (an empty consensus set: 0 / 0) never wins
-__global__ __launch_bounds__(kBlock) void reg_cost_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
-                                                          const double *__restrict__ tile_offs, int n_tiles, RegTileMin *tile_min)
+__device__ __forceinline__ void reg_cost_body(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                              const double *__restrict__ tile_offs, int n_tiles, RegTileMin *tile_min, int tile,
+                                              double (*s_wave)[kRegQ], RegMin *s_min)
 {
 #pragma clang fp contract(off)
-  __shared__ double s_wave[kWaves][kRegQ];
-  __shared__ RegMin s_min[kWaves];
-  const int at = blockIdx.x * kRegTile + threadIdx.x * kRegPerLane;
+  const int at = tile * kRegTile + threadIdx.x * kRegPerLane;
   uint32_t pl[kRegPerLane];
   double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -409,7 +453,7 @@ __global__ __launch_bounds__(kBlock) void reg_cost_kernel(const uint32_t *__rest
   reg_block_scan(v, run, total, s_wave);
 #pragma unroll
   for (int c = 0; c < kRegQ; ++c)
-    run[c] = tile_offs[(size_t)blockIdx.x * kRegRow + c] + run[c];
+    run[c] = tile_offs[(size_t)tile * kRegRow + c] + run[c];
   const double r_all = tile_offs[(size_t)n_tiles * kRegRow + 5];
   RegMin best;
   best.cost = __longlong_as_double(0x7ff0000000000000ll); // +inf
@@ -444,8 +488,16 @@ __global__ __launch_bounds__(kBlock) void reg_cost_kernel(const uint32_t *__rest
     out.x = best.x;
     out.idx = best.idx;
     out.pad = 0;
-    tile_min[blockIdx.x] = out;
+    tile_min[tile] = out;
   }
+}
+
+__global__ __launch_bounds__(kBlock) void reg_cost_kernel(const uint32_t *__restrict__ payload, const double2 *__restrict__ pairs,
+                                                          const double *__restrict__ tile_offs, int n_tiles, RegTileMin *tile_min)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  __shared__ RegMin s_min[kWaves];
+  reg_cost_body(payload, pairs, tile_offs, n_tiles, tile_min, blockIdx.x, s_wave, s_min);
 }
 
 // the first smallest cost over the tiles; valid in every thread
@@ -467,14 +519,13 @@ __device__ __forceinline__ RegMin reg_vote_min(const RegTileMin *__restrict__ ti
   return reg_block_min(m, s_min);
 }
 
-__global__ __launch_bounds__(kBlock) void reg_count_kernel(const double2 *__restrict__ pairs, int n_pairs,
-                                                           const RegTileMin *__restrict__ tile_min, int n_tiles, int *counters)
+// pair p of one problem against that problem's vote
+__device__ __forceinline__ void reg_count_body(const double2 *__restrict__ pairs, int n_pairs, const RegTileMin *__restrict__ tile_min,
+                                               int n_tiles, int *counters, int p, RegMin *s_min)
 {
-  __shared__ RegMin s_min[kWaves];
   const RegMin vote = reg_vote_min(tile_min, n_tiles, s_min);
   if (vote.idx == kRegNoIndex)
     return; // (uniform)
-  const int p = blockIdx.x * kBlock + threadIdx.x;
   bool in = false;
   if (p < n_pairs)
   {
@@ -486,13 +537,19 @@ __global__ __launch_bounds__(kBlock) void reg_count_kernel(const double2 *__rest
     atomicAdd(&counters[1], n);
 }
 
-__global__ __launch_bounds__(kBlock) void reg_publish_kernel(const float *__restrict__ src, const float *__restrict__ dst,
-                                                             const float *__restrict__ nb, int N, int n_pairs,
-                                                             const RegTileMin *__restrict__ tile_min, int n_tiles,
-                                                             const int *__restrict__ counters, RegHost *host,
-                                                             volatile unsigned *ticket, unsigned epoch)
+__global__ __launch_bounds__(kBlock) void reg_count_kernel(const double2 *__restrict__ pairs, int n_pairs,
+                                                           const RegTileMin *__restrict__ tile_min, int n_tiles, int *counters)
 {
   __shared__ RegMin s_min[kWaves];
+  reg_count_body(pairs, n_pairs, tile_min, n_tiles, counters, blockIdx.x * kBlock + threadIdx.x, s_min);
+}
+
+// one workgroup per problem: its pinned record; ends behind a system fence and a barrier
+__device__ __forceinline__ void reg_publish_body(const float *__restrict__ src, const float *__restrict__ dst,
+                                                 const float *__restrict__ nb, int N, int n_pairs,
+                                                 const RegTileMin *__restrict__ tile_min, int n_tiles,
+                                                 const int *__restrict__ counters, RegHost *host, RegMin *s_min)
+{
   const RegMin vote = reg_vote_min(tile_min, n_tiles, s_min);
   const int tid = threadIdx.x;
   for (int q = tid; q < 3 * N; q += kBlock)
@@ -513,11 +570,170 @@ __global__ __launch_bounds__(kBlock) void reg_publish_kernel(const float *__rest
   }
   __threadfence_system();
   __syncthreads();
-  if (tid == 0)
+}
+
+__global__ __launch_bounds__(kBlock) void reg_publish_kernel(const float *__restrict__ src, const float *__restrict__ dst,
+                                                             const float *__restrict__ nb, int N, int n_pairs,
+                                                             const RegTileMin *__restrict__ tile_min, int n_tiles,
+                                                             const int *__restrict__ counters, RegHost *host,
+                                                             volatile unsigned *ticket, unsigned epoch)
+{
+  __shared__ RegMin s_min[kWaves];
+  reg_publish_body(src, dst, nb, N, n_pairs, tile_min, n_tiles, counters, host, s_min);
+  if (threadIdx.x == 0)
   {
     __threadfence_system();
     *ticket = epoch;
   }
+}
+
+// ---- the batched vote (sage_robust_registration_batch): the kernels above over (problem, block) items ----
+// The voting problems are segments of the keys / payload / pairs allocations, by descending P (registration_plan.h), so a
+// segment starts at a multiple of its own P and of every tile size: block b of a sort launch IS the allocation's tile b, and
+// the compare-exchange t of a cross-tile stage IS the allocation's; only the direction of the last stage (k = the
+// segment's own P) needs the segment.  A stage with k concerns the segments with P >= k, a prefix of the allocation, and
+// is launched over that prefix.  A workgroup finds its segment in the table below (a kernel argument; at most 32 rows,
+// the lookup is uniform)
+struct RegSegTable
+{
+  int n;
+  int start[SAGE_REG_MAX_BATCH + 1];   // first endpoint; [n]: the total
+  int tile0[SAGE_REG_MAX_BATCH + 1];   // scan tiles before the segment
+  int cblock0[SAGE_REG_MAX_BATCH + 1]; // 256-pair blocks before the segment
+  int pair0[SAGE_REG_MAX_BATCH], N[SAGE_REG_MAX_BATCH], n_pairs[SAGE_REG_MAX_BATCH], n_tiles[SAGE_REG_MAX_BATCH];
+  long long rows0[SAGE_REG_MAX_BATCH]; // the segment's tile rows, bytes into the tiles allocation
+};
+struct RegSegPoints // the problems' inputs and pinned records, in segment order
+{
+  const float *src[SAGE_REG_MAX_BATCH], *dst[SAGE_REG_MAX_BATCH], *nb[SAGE_REG_MAX_BATCH];
+  RegHost *host[SAGE_REG_MAX_BATCH];
+};
+
+// the s with first[s] <= v < first[s + 1]
+__device__ __forceinline__ int reg_segment_of(const int (&first)[SAGE_REG_MAX_BATCH + 1], int n, int v)
+{
+  int s = 0;
+  while (s + 1 < n && first[s + 1] <= v)
+    ++s;
+  return s;
+}
+
+struct RegSegRows // a segment's part of the tiles allocation
+{
+  double *sums, *offs;
+  RegTileMin *min;
+  int *counters;
+};
+__device__ __forceinline__ RegSegRows reg_segment_rows(const RegSegTable &T, int s, char *tiles)
+{
+  const size_t nt = (size_t)T.n_tiles[s];
+  RegSegRows r;
+  char *rows = tiles + T.rows0[s];
+  r.sums = reinterpret_cast<double *>(rows);
+  r.offs = reinterpret_cast<double *>(rows + nt * kRegRow * sizeof(double));
+  r.min = reinterpret_cast<RegTileMin *>(rows + (2 * nt + 1) * kRegRow * sizeof(double));
+  r.counters = reinterpret_cast<int *>(tiles) + 4 * s;
+  return r;
+}
+
+// grid: total endpoints / 512
+__global__ __launch_bounds__(kBlock) void reg_pair_batch_kernel(const RegSegTable T, const RegSegPoints Q, double sqrt_cbar2, uint64_t *keys,
+                                                                uint32_t *payload, double2 *pairs, char *tiles)
+{
+  const int s = reg_segment_of(T.start, T.n, blockIdx.x * (2 * kBlock));
+  const int start = T.start[s], half_P = (T.start[s + 1] - start) >> 1;
+  reg_pair_body(Q.src[s], Q.dst[s], Q.nb[s], T.N[s], T.n_pairs[s], half_P, sqrt_cbar2, keys + start, payload + start, pairs + T.pair0[s],
+                reinterpret_cast<int *>(tiles) + 4 * s, blockIdx.x * kBlock + threadIdx.x - (start >> 1));
+}
+
+// grid: (the endpoints of the segments with P >= k_last) / kSortTile
+template <int kSortTile>
+__global__ __launch_bounds__(kBlock) void reg_sort_tile_batch_kernel(const RegSegTable T, uint64_t *keys, uint32_t *payload, int k_first,
+                                                                     int k_last)
+{
+  __shared__ uint64_t s_k[kSortTile];
+  __shared__ uint32_t s_p[kSortTile];
+  const int base = blockIdx.x * kSortTile;
+  const int s = reg_segment_of(T.start, T.n, base);
+  reg_sort_tile_body<kSortTile>(keys + base, payload + base, base - T.start[s], k_first, k_last, s_k, s_p);
+}
+
+// grid: (the endpoints of the segments with P >= k) / 512
+__global__ __launch_bounds__(kBlock) void reg_sort_stage_batch_kernel(const RegSegTable T, uint64_t *keys, uint32_t *payload, int k, int j)
+{
+  const int s = reg_segment_of(T.start, T.n, blockIdx.x * (2 * kBlock));
+  reg_sort_stage_body(keys, payload, k, j, blockIdx.x * kBlock + threadIdx.x, T.start[s + 1] - T.start[s] == k);
+}
+
+// grid: (the endpoints of the segments with P >= k) / 1024
+__global__ __launch_bounds__(kBlock) void reg_sort_stage2_batch_kernel(const RegSegTable T, uint64_t *keys, uint32_t *payload, int k, int j)
+{
+  const int s = reg_segment_of(T.start, T.n, blockIdx.x * (4 * kBlock));
+  reg_sort_stage2_body(keys, payload, k, j, blockIdx.x * kBlock + threadIdx.x, T.start[s + 1] - T.start[s] == k);
+}
+
+// grid: the segments' scan tiles
+__global__ __launch_bounds__(kBlock) void reg_tile_sums_batch_kernel(const RegSegTable T, const uint32_t *__restrict__ payload,
+                                                                     const double2 *__restrict__ pairs, char *tiles)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  const int s = reg_segment_of(T.tile0, T.n, blockIdx.x);
+  reg_tile_sums_body(payload + T.start[s], pairs + T.pair0[s], reg_segment_rows(T, s, tiles).sums, blockIdx.x - T.tile0[s], s_wave);
+}
+
+// grid: the segments
+__global__ __launch_bounds__(kBlock) void reg_tile_offsets_batch_kernel(const RegSegTable T, char *tiles)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  const RegSegRows r = reg_segment_rows(T, blockIdx.x, tiles);
+  reg_tile_offsets_body(r.sums, r.offs, T.n_tiles[blockIdx.x], s_wave);
+}
+
+// grid: the segments' scan tiles
+__global__ __launch_bounds__(kBlock) void reg_cost_batch_kernel(const RegSegTable T, const uint32_t *__restrict__ payload,
+                                                                const double2 *__restrict__ pairs, char *tiles)
+{
+  __shared__ double s_wave[kWaves][kRegQ];
+  __shared__ RegMin s_min[kWaves];
+  const int s = reg_segment_of(T.tile0, T.n, blockIdx.x);
+  const RegSegRows r = reg_segment_rows(T, s, tiles);
+  reg_cost_body(payload + T.start[s], pairs + T.pair0[s], r.offs, T.n_tiles[s], r.min, blockIdx.x - T.tile0[s], s_wave, s_min);
+}
+
+// grid: the segments' 256-pair blocks
+__global__ __launch_bounds__(kBlock) void reg_count_batch_kernel(const RegSegTable T, const double2 *__restrict__ pairs, char *tiles)
+{
+  __shared__ RegMin s_min[kWaves];
+  const int s = reg_segment_of(T.cblock0, T.n, blockIdx.x);
+  const RegSegRows r = reg_segment_rows(T, s, tiles);
+  reg_count_body(pairs + T.pair0[s], T.n_pairs[s], r.min, T.n_tiles[s], r.counters, (blockIdx.x - T.cblock0[s]) * kBlock + threadIdx.x, s_min);
+}
+
+// grid: the segments.  The ticket comes behind this launch in the stream (ws_ticket_wait)
+__global__ __launch_bounds__(kBlock) void reg_publish_batch_kernel(const RegSegTable T, const RegSegPoints Q, char *tiles)
+{
+  __shared__ RegMin s_min[kWaves];
+  const int s = blockIdx.x;
+  const RegSegRows r = reg_segment_rows(T, s, tiles);
+  reg_publish_body(Q.src[s], Q.dst[s], Q.nb[s], T.N[s], T.n_pairs[s], r.min, T.n_tiles[s], r.counters, Q.host[s], s_min);
+}
+
+// rows of int32 out of pinned memory, one row per blockIdx.y: out[i] = map ? map[in[i]] : in[i].  The batch's inliers_dev rows
+// (map NULL) and the pre-check's inlier keypoints (map: kept)
+struct RegRowCopy
+{
+  const int32_t *in[SAGE_REG_MAX_BATCH];  // pinned
+  const int32_t *map[SAGE_REG_MAX_BATCH]; // device, or NULL
+  int32_t *out[SAGE_REG_MAX_BATCH];
+  int n[SAGE_REG_MAX_BATCH];
+};
+__global__ __launch_bounds__(kBlock) void reg_row_copy_kernel(const RegRowCopy R)
+{
+  const int b = blockIdx.y, i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= R.n[b])
+    return;
+  const int32_t v = R.in[b][i];
+  R.out[b][i] = R.map[b] ? R.map[b][v] : v;
 }
 
 struct MatchPointsParams
@@ -546,14 +762,12 @@ __device__ __forceinline__ void matched_point(long long loc, float Wf, float cx,
   *d1 = (loc >= 0 && loc < HW) ? dpt_map_1[loc] : __int_as_float(0x7fc00000);
 }
 
-// one workgroup: compacts the flagged keypoints in ascending order (a wave scan of the flags per 256 keypoints) and evaluates
-// the gather's fp32 expressions for each; the depths' sum in fp64 (per lane, then the workgroup's tree)
-__global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPointsParams P, RegHost *host, volatile unsigned *ticket,
-                                                                  unsigned epoch)
+// one workgroup per problem: compacts the flagged keypoints in ascending order (a wave scan of the flags per 256 keypoints) and
+// evaluates the gather's fp32 expressions for each; the depths' sum in fp64 (per lane, then the workgroup's tree).  Thread 0
+// leaves the count and the mean in the pinned record, behind a system fence
+__device__ __forceinline__ void reg_match_points_body(const MatchPointsParams &P, RegHost *host, int *s_cnt, double *s_sum)
 {
 #pragma clang fp contract(off)
-  __shared__ int s_cnt[kWaves];
-  __shared__ double s_sum[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int total = 0; // the same in every thread
   double dsum = 0.0;
@@ -622,32 +836,70 @@ __global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPoi
     host->M = total;
     host->mean_depth = total ? (float)(s / (double)total) : 0.0f;
     __threadfence_system();
-    *ticket = epoch;
   }
+}
+
+__global__ __launch_bounds__(kBlock) void reg_match_points_kernel(const MatchPointsParams P, RegHost *host, volatile unsigned *ticket,
+                                                                  unsigned epoch)
+{
+  __shared__ int s_cnt[kWaves];
+  __shared__ double s_sum[kWaves];
+  reg_match_points_body(P, host, s_cnt, s_sum);
+  if (threadIdx.x == 0)
+    *ticket = epoch;
+}
+
+struct MatchPointsBatch
+{
+  SageMatchPointsItem item[SAGE_REG_MAX_BATCH];
+  MatchPointsParams shared; // the scalars (the pointers are taken from the item)
+  RegHost *host;            // [B] records of 64 bytes: problem b's count and mean
+};
+static_assert(sizeof(MatchPointsBatch) <= 4096, "a kernel argument");
+
+// grid: the problems.  The ticket comes behind this launch in the stream (ws_ticket_wait)
+__global__ __launch_bounds__(kBlock) void reg_match_points_batch_kernel(const MatchPointsBatch G)
+{
+  __shared__ int s_cnt[kWaves];
+  __shared__ double s_sum[kWaves];
+  const SageMatchPointsItem &it = G.item[blockIdx.x];
+  MatchPointsParams P = G.shared;
+  P.flags = it.cyc_inlier_flags; P.loc1 = it.raw_matched_loc1d_1; P.dpts0 = it.dpts0; P.homo0 = it.homo0; P.dpt_map_1 = it.dpt_map_1;
+  P.pts0 = it.pts0; P.pts1 = it.pts1; P.noise_bounds = it.noise_bounds; P.homo1 = it.homo1; P.dpts1 = it.dpts1; P.kept = it.kept;
+  reg_match_points_body(P, reinterpret_cast<RegHost *>(reinterpret_cast<char *>(G.host) + 64 * (size_t)blockIdx.x), s_cnt, s_sum);
 }
 } // namespace
 
-extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev,
-                                        int N, const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
-                                        int32_t *inliers_dev)
+// a problem's published record -> its result (zeroed by the caller): the counts, then, if the vote was not empty, the host
+// finish, which leaves the translation inliers behind the points in the record
+static int reg_finish_record(RegHost *h, int N, const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host)
 {
-  if (!ws || !src_dev || !dst_dev || !noise_bounds_dev || !p || !res || N < 0 || N > SAGE_REG_MAX_POINTS)
-    return SAGE_E_INVALID;
-  int rc;
-  if ((rc = registration_check_params(p)))
+  res->n_pairs = h->n_pairs;
+  res->n_degenerate_pairs = h->n_degenerate;
+  if (!h->vote_valid)
+    return SAGE_OK; // (valid = 0: no pair was left in the vote)
+  const double scale = h->scale, scale_cost = h->scale_cost;
+  const int n_pairs = h->n_pairs, n_scale_inliers = h->n_scale_inliers, n_degenerate = h->n_degenerate;
+  int32_t *inl = reinterpret_cast<int32_t *>(h->pts + 7 * (size_t)N);
+  if (int rc = sage_registration_finish(h->pts, h->pts + 3 * (size_t)N, h->pts + 6 * (size_t)N, N, scale, p, res, inl, nullptr))
     return rc;
-  std::memset(res, 0, sizeof(*res));
-  if (N < 2)
-    return SAGE_OK; // (valid = 0: the reference never calls the solver there)
+  res->n_pairs = n_pairs;
+  res->n_degenerate_pairs = n_degenerate;
+  res->n_scale_inlier_pairs = n_scale_inliers;
+  res->scale_cost = scale_cost;
+  if (inliers_host)
+    std::memcpy(inliers_host, inl, (size_t)res->n_inliers * sizeof(int32_t));
+  return SAGE_OK;
+}
 
+// one problem's vote (N >= 2): reserve, launch, wait for the ticket the publish kernel posts; the record is then at the
+// start of ws->reg_host.  *launches (may be NULL): how many kernels that took
+static int reg_vote_single(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev, int N, double cbar2,
+                           int *launches)
+{
+  int rc;
   const int n_pairs = N * (N - 1) / 2;
-  int tile = kSortTileDefault;
-  if (const char *env = std::getenv("SAGE_REG_SORT_TILE")) // measurement: scripts/registration_bench.py times the three sizes
-  {
-    const int v = std::atoi(env);
-    if (v == 1024 || v == 2048 || v == 4096)
-      tile = v;
-  }
+  const int tile = registration_sort_tile(); // (SAGE_REG_SORT_TILE picks another: scripts/registration_bench.py times the three sizes)
   const auto sort_tile = tile == 1024 ? reg_sort_tile_kernel<1024> : tile == 2048 ? reg_sort_tile_kernel<2048> : reg_sort_tile_kernel<4096>;
   int P = kSortTileMax; // (whatever the tile: the workspace's sizes do not depend on the measurement switch)
   while (P < 2 * n_pairs)
@@ -675,7 +927,7 @@ extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev,
   SAGE_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(int), s));
   const int half_P = P / 2, half_blocks = (half_P + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(reg_pair_kernel, dim3(half_blocks), dim3(kBlock), 0, s, src_dev, dst_dev, noise_bounds_dev, N, n_pairs, half_P,
-                     std::sqrt(p->cbar2), keys, payload, pairs, counters);
+                     std::sqrt(cbar2), keys, payload, pairs, counters);
   hipLaunchKernelGGL(sort_tile, dim3(P / tile), dim3(kBlock), 0, s, keys, payload, 2, tile);
   const int quarter_P = P / 4, quarter_blocks = (quarter_P + kBlock - 1) / kBlock;
   for (int k = 2 * tile; k <= P; k <<= 1)
@@ -702,31 +954,220 @@ extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev,
   hipLaunchKernelGGL(reg_publish_kernel, dim3(1), dim3(kBlock), 0, s, src_dev, dst_dev, noise_bounds_dev, N, n_pairs, tile_min, n_tiles,
                      counters, h, &ws->hs()->ticket, epoch);
   SAGE_HIP(hipGetLastError());
-  if ((rc = ws_ticket_await(ws, epoch)))
-    return rc;
+  if (launches)
+    *launches = registration_sort_launches(P, tile) + kRegSingleFixedLaunches;
+  return ws_ticket_await(ws, epoch);
+}
 
-  res->n_pairs = h->n_pairs;
-  res->n_degenerate_pairs = h->n_degenerate;
-  if (!h->vote_valid)
-    return SAGE_OK; // (valid = 0: no pair was left in the vote)
-  const double scale = h->scale, scale_cost = h->scale_cost;
-  const int n_scale_inliers = h->n_scale_inliers, n_degenerate = h->n_degenerate;
-  int32_t *inl = reinterpret_cast<int32_t *>(h->pts + 7 * (size_t)N); // (pinned: the source of the copy below)
-  if ((rc = sage_registration_finish(h->pts, h->pts + 3 * (size_t)N, h->pts + 6 * (size_t)N, N, scale, p, res, inl, nullptr)))
+extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev,
+                                        int N, const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                                        int32_t *inliers_dev)
+{
+  if (!ws || !src_dev || !dst_dev || !noise_bounds_dev || !p || !res || N < 0 || N > SAGE_REG_MAX_POINTS)
+    return SAGE_E_INVALID;
+  int rc;
+  if ((rc = registration_check_params(p)))
     return rc;
-  res->n_pairs = n_pairs;
-  res->n_degenerate_pairs = n_degenerate;
-  res->n_scale_inlier_pairs = n_scale_inliers;
-  res->scale_cost = scale_cost;
-  if (inliers_host)
-    std::memcpy(inliers_host, inl, (size_t)res->n_inliers * sizeof(int32_t));
+  std::memset(res, 0, sizeof(*res));
+  if (N < 2)
+    return SAGE_OK; // (valid = 0: the reference never calls the solver there)
+  if ((rc = reg_vote_single(ws, src_dev, dst_dev, noise_bounds_dev, N, p->cbar2, nullptr)))
+    return rc;
+  RegHost *h = ws->reg_host.as<RegHost>();
+  hipStream_t s = ws->stream;
+  if ((rc = reg_finish_record(h, N, p, res, inliers_host)))
+    return rc;
   if (inliers_dev && res->n_inliers > 0)
   {
+    const int32_t *inl = reinterpret_cast<const int32_t *>(h->pts + 7 * (size_t)N); // (pinned: the source of the copy)
     SAGE_HIP(hipMemcpyAsync(inliers_dev, inl, (size_t)res->n_inliers * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if ((rc = ws_ticket_wait(ws)))
       return rc;
   }
   return SAGE_OK;
+}
+
+// the votes of a plan's segments (two or more): reserve, launch, one ticket behind the publish launch, wait.  record [plan.n]:
+// where each segment's pinned record is
+static int reg_vote_batch(SageWorkspace *ws, const RegBatchPlan &plan, const SageRegistrationProblem *probs, double cbar2,
+                          RegHost **record, int *launches_out)
+{
+  int rc;
+  if ((rc = ws->reg_keys.reserve((size_t)plan.keys_bytes)) || (rc = ws->reg_payload.reserve((size_t)plan.payload_bytes)) ||
+      (rc = ws->reg_pairs.reserve((size_t)plan.pairs_bytes)) || (rc = ws->reg_tiles.reserve((size_t)plan.tiles_bytes)) ||
+      (rc = ws->reg_host.reserve((size_t)plan.pinned_bytes))) // (every earlier call has been waited for)
+    return rc;
+  uint64_t *keys = ws->reg_keys.as<uint64_t>();
+  uint32_t *payload = ws->reg_payload.as<uint32_t>();
+  double2 *pairs = ws->reg_pairs.as<double2>();
+  char *tiles = ws->reg_tiles.as<char>();
+  char *records = ws->reg_host.as<char>();
+  hipStream_t s = ws->stream;
+
+  RegSegTable T{};
+  RegSegPoints Q{};
+  T.n = plan.n;
+  for (int i = 0; i < plan.n; ++i)
+  {
+    const RegBatchSegment &g = plan.seg[i];
+    T.start[i] = g.start; T.tile0[i] = g.tile0; T.cblock0[i] = g.cblock0; T.pair0[i] = g.pair0;
+    T.N[i] = g.N; T.n_pairs[i] = g.pairs; T.n_tiles[i] = g.n_tiles; T.rows0[i] = g.rows0;
+    Q.src[i] = probs[g.row].src_dev; Q.dst[i] = probs[g.row].dst_dev; Q.nb[i] = probs[g.row].noise_bounds_dev;
+    Q.host[i] = reinterpret_cast<RegHost *>(records + g.record0);
+  }
+  T.start[plan.n] = plan.endpoints; T.tile0[plan.n] = plan.tiles; T.cblock0[plan.n] = plan.cblocks;
+
+  int launches = 0;
+  const int tile = plan.sort_tile;
+  const auto sort_tile = tile == 1024   ? reg_sort_tile_batch_kernel<1024>
+                         : tile == 2048 ? reg_sort_tile_batch_kernel<2048>
+                                        : reg_sort_tile_batch_kernel<4096>;
+  SAGE_HIP(hipMemsetAsync(tiles, 0, 16 * (size_t)plan.n, s)); // the segments' counters
+  hipLaunchKernelGGL(reg_pair_batch_kernel, dim3(plan.endpoints / (2 * kBlock)), dim3(kBlock), 0, s, T, Q, std::sqrt(cbar2), keys, payload,
+                     pairs, tiles);
+  hipLaunchKernelGGL(sort_tile, dim3(plan.endpoints / tile), dim3(kBlock), 0, s, T, keys, payload, 2, tile);
+  launches += 2;
+  int n_k = plan.n; // the segments a stage with k concerns: those with P >= k, the first n_k
+  for (int k = 2 * tile; k <= plan.seg[0].P; k <<= 1)
+  {
+    while (plan.seg[n_k - 1].P < k)
+      --n_k;
+    const int ends = plan.seg[n_k - 1].start + plan.seg[n_k - 1].P; // (a multiple of 4096)
+    // the distances k / 2 .. tile across tiles: an odd one out first, then two per launch; the rest on the tiles in LDS
+    int j = k >> 1, n_global = 0;
+    for (int q = j; q >= tile; q >>= 1)
+      ++n_global;
+    if (n_global & 1)
+    {
+      hipLaunchKernelGGL(reg_sort_stage_batch_kernel, dim3(ends / (2 * kBlock)), dim3(kBlock), 0, s, T, keys, payload, k, j);
+      ++launches;
+      j >>= 1;
+    }
+    for (; j >= 2 * tile; j >>= 2, ++launches)
+      hipLaunchKernelGGL(reg_sort_stage2_batch_kernel, dim3(ends / (4 * kBlock)), dim3(kBlock), 0, s, T, keys, payload, k, j);
+    hipLaunchKernelGGL(sort_tile, dim3(ends / tile), dim3(kBlock), 0, s, T, keys, payload, k, k);
+    ++launches;
+  }
+  hipLaunchKernelGGL(reg_tile_sums_batch_kernel, dim3(plan.tiles), dim3(kBlock), 0, s, T, payload, pairs, tiles);
+  hipLaunchKernelGGL(reg_tile_offsets_batch_kernel, dim3(plan.n), dim3(kBlock), 0, s, T, tiles);
+  hipLaunchKernelGGL(reg_cost_batch_kernel, dim3(plan.tiles), dim3(kBlock), 0, s, T, payload, pairs, tiles);
+  hipLaunchKernelGGL(reg_count_batch_kernel, dim3(plan.cblocks), dim3(kBlock), 0, s, T, pairs, tiles);
+  hipLaunchKernelGGL(reg_publish_batch_kernel, dim3(plan.n), dim3(kBlock), 0, s, T, Q, tiles);
+  SAGE_HIP(hipGetLastError());
+  launches += 5 + 1; // (and the ticket's)
+  *launches_out = launches;
+  for (int i = 0; i < plan.n; ++i)
+    record[i] = Q.host[i];
+  return ws_ticket_wait(ws);
+}
+
+// the batch: plan, reserve, launch, wait once, finish per problem in row order, then the inliers_dev rows in one launch.
+// inlier_map (NULL, or [B] device arrays): row b of inliers_dev receives inlier_map[b][inlier] instead of the inlier (the
+// pre-check's keypoint positions)
+static int registration_batch(SageWorkspace *ws, const SageRegistrationProblem *probs, int B, const SageRegistrationParams *p,
+                              SageRegistrationResult *res, int32_t *inliers_host, int inliers_stride, const int32_t *const *inlier_map)
+{
+  if (B < 0 || B > SAGE_REG_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B == 0)
+    return SAGE_OK;
+  if (!ws || !probs || !p || !res)
+    return SAGE_E_INVALID;
+  int rc;
+  SageRegistrationParams pp = *p;
+  pp.noise_bound = 1.0; // (replaced per problem below: the caller's value is not read)
+  if ((rc = registration_check_params(&pp)))
+    return rc;
+  int32_t Ns[SAGE_REG_MAX_BATCH];
+  int max_N = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    const SageRegistrationProblem &q = probs[b];
+    if (q.N < 0 || q.N > SAGE_REG_MAX_POINTS)
+      return SAGE_E_INVALID;
+    if (q.N >= 2 && (!q.src_dev || !q.dst_dev || !q.noise_bounds_dev || !(q.noise_bound > 0) || !std::isfinite(q.noise_bound)))
+      return SAGE_E_INVALID;
+    Ns[b] = q.N;
+    max_N = std::max(max_N, (int)q.N);
+  }
+  if (inliers_host && inliers_stride < max_N)
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+    std::memset(&res[b], 0, sizeof(res[b]));
+  ws->reg_batch_launches = 0;
+
+  RegBatchPlan plan;
+  registration_batch_plan(Ns, B, registration_sort_tile(), &plan);
+  if (plan.n == 0)
+    return SAGE_OK; // (nothing votes: valid = 0 everywhere, no launch)
+  // a batch with ONE voting problem takes the single call's path (its publish kernel posts the ticket itself: one launch
+  // fewer, and the batch of one is then no slower than the call it replaces -- measured: scripts/registration_batch_bench.py)
+  RegHost *seg_record[SAGE_REG_MAX_BATCH];
+  if (plan.n == 1)
+  {
+    const SageRegistrationProblem &q = probs[plan.seg[0].row];
+    rc = reg_vote_single(ws, q.src_dev, q.dst_dev, q.noise_bounds_dev, q.N, p->cbar2, &ws->reg_batch_launches);
+    seg_record[0] = ws->reg_host.as<RegHost>();
+  }
+  else
+    rc = reg_vote_batch(ws, plan, probs, p->cbar2, seg_record, &ws->reg_batch_launches);
+  if (rc)
+    return rc;
+  hipStream_t s = ws->stream;
+
+  RegHost *record[SAGE_REG_MAX_BATCH] = {};
+  for (int i = 0; i < plan.n; ++i)
+    record[plan.seg[i].row] = seg_record[i];
+  RegRowCopy rows{};
+  int n_rows = 0, max_n = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    if (!record[b])
+      continue;
+    pp.noise_bound = probs[b].noise_bound;
+    if ((rc = reg_finish_record(record[b], probs[b].N, &pp, &res[b], inliers_host ? inliers_host + (size_t)b * inliers_stride : nullptr)))
+      return rc;
+    if (probs[b].inliers_dev && res[b].n_inliers > 0)
+    {
+      rows.in[n_rows] = reinterpret_cast<const int32_t *>(record[b]->pts + 7 * (size_t)probs[b].N);
+      rows.map[n_rows] = inlier_map ? inlier_map[b] : nullptr;
+      rows.out[n_rows] = probs[b].inliers_dev;
+      rows.n[n_rows] = res[b].n_inliers;
+      max_n = std::max(max_n, res[b].n_inliers);
+      ++n_rows;
+    }
+  }
+  if (n_rows)
+  {
+    hipLaunchKernelGGL(reg_row_copy_kernel, dim3((max_n + kBlock - 1) / kBlock, n_rows), dim3(kBlock), 0, s, rows);
+    SAGE_HIP(hipGetLastError());
+    ws->reg_batch_launches += 2;
+    if ((rc = ws_ticket_wait(ws)))
+      return rc;
+  }
+  return SAGE_OK;
+}
+
+extern "C" int sage_robust_registration_batch(SageWorkspace *ws, const SageRegistrationProblem *probs, int B,
+                                              const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                                              int inliers_stride)
+{
+  return registration_batch(ws, probs, B, p, res, inliers_host, inliers_stride, nullptr);
+}
+
+extern "C" int sage_robust_registration_batch_launches(const SageWorkspace *ws) { return ws ? ws->reg_batch_launches : 0; }
+
+// the scalars of a gather (the pointers are left to the caller)
+static MatchPointsParams match_points_scalars(float depth_divisor0, const SageCamera *cam, int K, int W, float noise_multiplier,
+                                              int noise_from)
+{
+  MatchPointsParams P{};
+  P.divisor0 = depth_divisor0; P.cx = cam->cx; P.cy = cam->cy; P.fx = cam->fx; P.fy = cam->fy; P.Wf = (float)W;
+  P.focal = (float)((cam->fx + cam->fy) / 2.0); // float focal_length = (fx + fy) / 2.0
+  P.mult = noise_multiplier;
+  P.HW = (long long)cam->w * (long long)cam->h;
+  P.K = K; P.noise_from = noise_from;
+  return P;
 }
 
 extern "C" int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_flags, const int64_t *raw_matched_loc1d_1,
@@ -742,13 +1183,8 @@ extern "C" int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_fl
   int rc;
   if ((rc = ws->reg_host.reserve(offsetof(RegHost, pts) + sizeof(float))))
     return rc;
-  MatchPointsParams P;
+  MatchPointsParams P = match_points_scalars(depth_divisor0, cam, K, W, noise_multiplier, noise_from);
   P.flags = cyc_inlier_flags; P.loc1 = raw_matched_loc1d_1; P.dpts0 = dpts0; P.homo0 = homo0; P.dpt_map_1 = dpt_map_1;
-  P.divisor0 = depth_divisor0; P.cx = cam->cx; P.cy = cam->cy; P.fx = cam->fx; P.fy = cam->fy; P.Wf = (float)W;
-  P.focal = (float)((cam->fx + cam->fy) / 2.0); // float focal_length = (fx + fy) / 2.0
-  P.mult = noise_multiplier;
-  P.HW = (long long)cam->w * (long long)cam->h;
-  P.K = K; P.noise_from = noise_from;
   P.pts0 = pts0; P.pts1 = pts1; P.noise_bounds = noise_bounds; P.homo1 = homo1; P.dpts1 = dpts1; P.kept = kept;
   RegHost *h = ws->reg_host.as<RegHost>();
   const unsigned epoch = ws_ticket_next(ws);
@@ -762,17 +1198,51 @@ extern "C" int sage_match_points(SageWorkspace *ws, const int32_t *cyc_inlier_fl
   return SAGE_OK;
 }
 
-// ---- the loop detector's pre-check: sage_cycle_match_batch, then per surviving candidate the two calls above ----
-namespace
+extern "C" int sage_match_points_batch(SageWorkspace *ws, const SageMatchPointsItem *items, int B, float depth_divisor0,
+                                       const SageCamera *cam, int K, int W, float noise_multiplier, int noise_from, int32_t *M_host,
+                                       float *mean_noise_depth_host)
 {
-__global__ void pre_inlier_keypoints_kernel(const int32_t *__restrict__ kept, const int32_t *inliers /* pinned */, int n,
-                                            int32_t *__restrict__ out)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    out[i] = kept[inliers[i]];
+  if (B < 0 || B > SAGE_REG_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B == 0)
+    return SAGE_OK;
+  if (!ws || !items || !cam || !M_host || K < 1 || W < 1 || !(cam->fx > 0) || !(cam->fy > 0) || !std::isfinite(cam->fx) ||
+      !std::isfinite(cam->fy) || (noise_from != 0 && noise_from != 1))
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+  {
+    const SageMatchPointsItem &it = items[b];
+    if (!it.cyc_inlier_flags || !it.raw_matched_loc1d_1 || !it.dpts0 || !it.homo0 || !it.dpt_map_1 || !it.pts0 || !it.pts1 ||
+        !it.noise_bounds || !it.homo1 || !it.dpts1 || !it.kept)
+      return SAGE_E_INVALID;
+  }
+  if (B == 1) // (the single call's path: its kernel posts the ticket itself, one launch fewer)
+    return sage_match_points(ws, items[0].cyc_inlier_flags, items[0].raw_matched_loc1d_1, items[0].dpts0, items[0].homo0, depth_divisor0,
+                             items[0].dpt_map_1, cam, K, W, noise_multiplier, noise_from, items[0].pts0, items[0].pts1, items[0].noise_bounds,
+                             items[0].homo1, items[0].dpts1, items[0].kept, M_host, mean_noise_depth_host);
+  int rc;
+  if ((rc = ws->reg_host.reserve(64 * (size_t)B + sizeof(RegHost))))
+    return rc;
+  MatchPointsBatch G{};
+  for (int b = 0; b < B; ++b)
+    G.item[b] = items[b];
+  G.shared = match_points_scalars(depth_divisor0, cam, K, W, noise_multiplier, noise_from);
+  G.host = ws->reg_host.as<RegHost>();
+  hipLaunchKernelGGL(reg_match_points_batch_kernel, dim3(B), dim3(kBlock), 0, ws->stream, G);
+  SAGE_HIP(hipGetLastError());
+  if ((rc = ws_ticket_wait(ws)))
+    return rc;
+  for (int b = 0; b < B; ++b)
+  {
+    const RegHost *h = reinterpret_cast<const RegHost *>(ws->reg_host.as<char>() + 64 * (size_t)b);
+    M_host[b] = h->M;
+    if (mean_noise_depth_host)
+      mean_noise_depth_host[b] = h->mean_depth;
+  }
+  return SAGE_OK;
 }
-} // namespace
+
+// ---- the loop detector's pre-check: sage_cycle_match_batch, then the two batched calls above over the survivors ----
 
 extern "C" int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float query_depth_divisor,
                                   const SageLoopCandidate *cands, int B, int K, int C, int H, int W, const SageCamera *cam,
@@ -802,15 +1272,12 @@ extern "C" int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev
   if (B == 0 || K == 0)
     return SAGE_OK;
 
-  // scratch: the way back [B][K] | pts0 [K][3] | pts1 [K][3] | homo1 [K][3] | noise bounds [K] | dpts1 [K] | kept [K]
-  const size_t cyc_bytes = (size_t)B * K * sizeof(int64_t);
-  if ((rc = ws->pre_scratch.reserve(cyc_bytes + (size_t)K * (11 * sizeof(float) + sizeof(int32_t)))) ||
-      (rc = ws->reg_host.reserve(offsetof(RegHost, pts) + (size_t)K * (7 * sizeof(float) + sizeof(int32_t))))) // (no solve below moves it)
+  // scratch: the way back [B][K] | per candidate: pts0 [K][3] | pts1 [K][3] | homo1 [K][3] | noise bounds [K] | dpts1 [K] | kept [K]
+  const size_t cyc_bytes = (size_t)B * K * sizeof(int64_t), cand_bytes = (size_t)K * (11 * sizeof(float) + sizeof(int32_t));
+  if ((rc = ws->pre_scratch.reserve(cyc_bytes + (size_t)B * cand_bytes)))
     return rc;
   int64_t *cyc = ws->pre_scratch.as<int64_t>();
-  float *pts0 = reinterpret_cast<float *>(ws->pre_scratch.as<char>() + cyc_bytes);
-  float *pts1 = pts0 + 3 * (size_t)K, *homo1 = pts1 + 3 * (size_t)K, *bounds = homo1 + 3 * (size_t)K, *dpts1 = bounds + K;
-  int32_t *kept = reinterpret_cast<int32_t *>(dpts1 + K);
+  char *gathered = ws->pre_scratch.as<char>() + cyc_bytes;
 
   const float *desc[SAGE_MATCH_MAX_BATCH];
   const int64_t *kp[SAGE_MATCH_MAX_BATCH];
@@ -824,41 +1291,62 @@ extern "C" int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev
                                    n_cycle)))
     return rc;
 
-  bool gathered = false;
+  // the gather of every candidate that passes the prune: one launch
+  static_assert(SAGE_MATCH_MAX_BATCH <= SAGE_REG_MAX_BATCH, "one batch holds every candidate");
+  SageMatchPointsItem items[SAGE_REG_MAX_BATCH];
+  int row[SAGE_REG_MAX_BATCH], n_items = 0; // the candidate of an item; later of a problem
   for (int b = 0; b < B; ++b)
   {
-    SageLoopPrecheckResult &r = results[b];
-    r.n_cycle = n_cycle[b];
+    results[b].n_cycle = n_cycle[b];
     // |translation inliers| <= n_cycle: a candidate below the ratio here is below it after the solve as well
     if (n_cycle[b] <= 0 || (float)n_cycle[b] / (float)K < min_desc_inlier_ratio)
       continue;
-    int M = 0;
-    if ((rc = sage_match_points(ws, inlier_flags + (size_t)b * K, raw_matched_loc1d + (size_t)b * K, cands[b].kp_dpts0_dev,
-                                cands[b].kp_homo0_dev, query_depth_divisor, cands[b].dpt_map_dev, cam, K, W, noise_multiplier, 1, pts0,
-                                pts1, bounds, homo1, dpts1, kept, &M, &r.mean_noise_depth)))
-      return rc;
-    r.n_matched = M;
-    const float nb = (noise_multiplier * r.mean_noise_depth) / ((cam->fx + cam->fy) / 2.0f);
-    if (M < 2 || !(nb > 0) || !std::isfinite(nb))
-      continue; // (no solve: one match, or depths the bound cannot be made from)
-    pp.noise_bound = (double)nb;
-    if ((rc = sage_robust_registration(ws, pts0, pts1, bounds, M, &pp, &r.reg, nullptr, nullptr)))
-      return rc;
-    r.registered = 1;
-    r.relative_desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)M;
-    r.desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)K;
-    if (r.reg.n_inliers > 0)
-    {
-      // the inliers are where the solve's finish left them in the pinned record; the next write to them comes behind a later
-      // ticket of this stream
-      const int32_t *inl = reinterpret_cast<const int32_t *>(ws->reg_host.as<RegHost>()->pts + 7 * (size_t)M);
-      hipLaunchKernelGGL(pre_inlier_keypoints_kernel, dim3((r.reg.n_inliers + kBlock - 1) / kBlock), dim3(kBlock), 0, ws->stream, kept,
-                         inl, r.reg.n_inliers, inlier_kp_dev + (size_t)b * K);
-      SAGE_HIP(hipGetLastError());
-      gathered = true;
-    }
+    float *pts0 = reinterpret_cast<float *>(gathered + (size_t)b * cand_bytes);
+    SageMatchPointsItem &it = items[n_items];
+    it.cyc_inlier_flags = inlier_flags + (size_t)b * K; it.raw_matched_loc1d_1 = raw_matched_loc1d + (size_t)b * K;
+    it.dpts0 = cands[b].kp_dpts0_dev; it.homo0 = cands[b].kp_homo0_dev; it.dpt_map_1 = cands[b].dpt_map_dev;
+    it.pts0 = pts0; it.pts1 = pts0 + 3 * (size_t)K; it.homo1 = pts0 + 6 * (size_t)K; it.noise_bounds = pts0 + 9 * (size_t)K;
+    it.dpts1 = pts0 + 10 * (size_t)K; it.kept = reinterpret_cast<int32_t *>(pts0 + 11 * (size_t)K);
+    row[n_items++] = b;
   }
-  return gathered ? ws_ticket_wait(ws) : SAGE_OK;
+  int32_t M[SAGE_REG_MAX_BATCH];
+  float mean[SAGE_REG_MAX_BATCH];
+  if ((rc = sage_match_points_batch(ws, items, n_items, query_depth_divisor, cam, K, W, noise_multiplier, 1, M, mean)))
+    return rc;
+
+  // the bound of every candidate that is left, and their solves: one batch
+  SageRegistrationProblem probs[SAGE_REG_MAX_BATCH];
+  const int32_t *kept[SAGE_REG_MAX_BATCH];
+  int n_probs = 0;
+  for (int i = 0; i < n_items; ++i)
+  {
+    SageLoopPrecheckResult &r = results[row[i]];
+    r.n_matched = M[i];
+    r.mean_noise_depth = mean[i];
+    const float nb = (noise_multiplier * r.mean_noise_depth) / ((cam->fx + cam->fy) / 2.0f);
+    if (M[i] < 2 || !(nb > 0) || !std::isfinite(nb))
+      continue; // (no solve: one match, or depths the bound cannot be made from)
+    SageRegistrationProblem &q = probs[n_probs];
+    q.src_dev = items[i].pts0; q.dst_dev = items[i].pts1; q.noise_bounds_dev = items[i].noise_bounds;
+    q.N = M[i];
+    q.noise_bound = (double)nb;
+    q.inliers_dev = inlier_kp_dev + (size_t)row[i] * K;
+    kept[n_probs] = items[i].kept;
+    row[n_probs++] = row[i]; // (n_probs <= i)
+  }
+  // (each survivor's inlier keypoints kept[inliers] are written from the pinned records in the batch's one copy launch)
+  SageRegistrationResult reg[SAGE_REG_MAX_BATCH];
+  if ((rc = registration_batch(ws, probs, n_probs, &pp, reg, nullptr, 0, kept)))
+    return rc;
+  for (int i = 0; i < n_probs; ++i)
+  {
+    SageLoopPrecheckResult &r = results[row[i]];
+    r.reg = reg[i];
+    r.registered = 1;
+    r.relative_desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)probs[i].N;
+    r.desc_match_inlier_ratio = (float)r.reg.n_inliers / (float)K;
+  }
+  return SAGE_OK;
 }
 
 // ---- the loop body after the ratio test: every survivor of the pre-check tracked against the query in one batch ----

@@ -1,5 +1,5 @@
-// registration_host.cpp -- (no HIP) the host side of robust registration (include/sage_ba.h): sage_tls_estimate and
-// sage_registration_finish.  teaser::RobustRegistrationSolver::solve for the chain graph without inlier selection
+// registration_host.cpp -- (no HIP) the host side of robust registration (include/sage_ba.h): sage_tls_estimate,
+// sage_registration_finish, and the layout of a batch of votes (registration_batch_plan, sage_robust_registration_batch_plan).  teaser::RobustRegistrationSolver::solve for the chain graph without inlier selection
 // (thirdparty/TEASER-plusplus/teaser/src/registration.cc:586-690), from the scale on:
 //   the chain TIMs i -> i + 1 (the last one wraps to 0), their bounds nb_leaf + nb_root, both dst side and bounds over scale
 //   the GNC's scalar bound: noise_bound * (2 / scale) (:648-650), squared, < 1e-16 -> 1e-2 (:1022-1025)
@@ -14,10 +14,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <limits>
 #include <utility>
 #include <vector>
 
+#include "registration_plan.h"
 #include "sage_ba.h"
 
 namespace
@@ -174,6 +176,101 @@ int registration_check_params(const SageRegistrationParams *p)
   if (p->rotation_tim_graph != SAGE_REG_CHAIN || p->inlier_selection_mode != SAGE_REG_SELECT_NONE ||
       p->rotation_algorithm != SAGE_REG_GNC_TLS)
     return SAGE_E_UNSUPPORTED;
+  return SAGE_OK;
+}
+
+// ---- the layout of a batch of votes (registration_plan.h) ----
+int registration_sort_tile()
+{
+  if (const char *env = std::getenv("SAGE_REG_SORT_TILE")) // measurement: scripts/registration_bench.py times the three sizes
+  {
+    const int v = std::atoi(env);
+    if (v == 1024 || v == 2048 || v == 4096)
+      return v;
+  }
+  return 1024;
+}
+
+int registration_sort_launches(int P, int tile)
+{
+  int n = 1; // the stages up to the tile, in LDS
+  for (int k = 2 * tile; k <= P; k <<= 1)
+  {
+    int n_global = 0; // the distances k / 2 .. tile: two per launch, an odd one out alone; then the tile's in LDS
+    for (int q = k >> 1; q >= tile; q >>= 1)
+      ++n_global;
+    n += (n_global + 1) / 2 + 1;
+  }
+  return n;
+}
+
+void registration_batch_plan(const int32_t *N, int B, int sort_tile, RegBatchPlan *plan)
+{
+  *plan = RegBatchPlan();
+  plan->sort_tile = sort_tile;
+  int n = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    if (N[b] < 2)
+      continue; // (does not vote: no segment, no record, no launch)
+    RegBatchSegment &s = plan->seg[n++];
+    s.row = b;
+    s.N = N[b];
+    s.pairs = N[b] * (N[b] - 1) / 2;
+    s.P = 4096;
+    while (s.P < 2 * s.pairs)
+      s.P <<= 1;
+    s.n_tiles = (2 * s.pairs + 2047) / 2048;
+  }
+  plan->n = n;
+  // descending P, rows of equal P in the caller's order: every segment then starts at a multiple of its own P
+  std::stable_sort(plan->seg, plan->seg + n, [](const RegBatchSegment &a, const RegBatchSegment &b) { return a.P > b.P; });
+  int64_t rows = 16 * (int64_t)n, record = 0;
+  for (int i = 0; i < n; ++i)
+  {
+    RegBatchSegment &s = plan->seg[i];
+    s.start = plan->endpoints;
+    s.pair0 = plan->pairs;
+    s.tile0 = plan->tiles;
+    s.cblock0 = plan->cblocks;
+    s.rows0 = rows;
+    s.record0 = record;
+    plan->endpoints += s.P;
+    plan->pairs += s.pairs;
+    plan->tiles += s.n_tiles;
+    plan->cblocks += (s.pairs + 255) / 256;
+    rows += 160 * (int64_t)(s.P / 2048) + 64;
+    record += 64 + 32 * (int64_t)s.N;
+  }
+  plan->keys_bytes = 8 * (int64_t)plan->endpoints;
+  plan->payload_bytes = 4 * (int64_t)plan->endpoints;
+  plan->pairs_bytes = 16 * (int64_t)plan->pairs;
+  plan->tiles_bytes = rows;
+  plan->device_bytes = plan->keys_bytes + plan->payload_bytes + plan->pairs_bytes + plan->tiles_bytes;
+  plan->pinned_bytes = record;
+  // (one voting problem: the single call's path, whose publish kernel posts the ticket)
+  plan->launches = n ? registration_sort_launches(plan->seg[0].P, sort_tile) + (n == 1 ? kRegSingleFixedLaunches : kRegBatchFixedLaunches) : 0;
+}
+
+extern "C" int sage_robust_registration_batch_plan(const int32_t *N, int B, int64_t *device_bytes, int64_t *pinned_bytes,
+                                                   int32_t *launches, int32_t *order)
+{
+  if (B < 0 || B > SAGE_REG_MAX_BATCH || (B > 0 && !N))
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+    if (N[b] < 0 || N[b] > SAGE_REG_MAX_POINTS)
+      return SAGE_E_INVALID;
+  RegBatchPlan plan;
+  registration_batch_plan(N, B, registration_sort_tile(), &plan);
+  if (device_bytes)
+    *device_bytes = plan.device_bytes;
+  if (pinned_bytes)
+    *pinned_bytes = plan.pinned_bytes;
+  if (launches)
+    *launches = plan.launches;
+  if (order)
+    for (int b = 0; b < B; ++b)
+      order[b] = b < plan.n ? plan.seg[b].row : -1;
   return SAGE_OK;
 }
 

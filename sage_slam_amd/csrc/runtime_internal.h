@@ -72,6 +72,7 @@ extern "C"
 #include "keypoint_batch.h"
 #include "graph_batch.h"
 #include "window_plan.h" // SolverRows, TermLayout
+#include "registration_plan.h" // RegBatchPlan
 
 using namespace sage;
 
@@ -222,16 +223,19 @@ struct SageWorkspace
   // robust registration (sage_robust_registration, sage_match_points: registration.hip): the endpoints' keys and payloads [P],
   // the pairs' measurements (X, r) [pairs], the scan's per-tile sums, offsets and minima with the two counters, and the
   // pinned record the last kernel publishes (RegHost; also where sage_match_points leaves its count and mean).  All grow
-  // with N and go with the workspace
+  // with N and go with the workspace.  A batch (sage_robust_registration_batch) holds all its voting problems in the same
+  // five: segments of the first three, per-segment rows of the fourth, one record per problem in the fifth;
+  // sage_match_points_batch leaves [B] counts and means there.  reg_batch_launches: what the last batch launched
   DevBuf reg_keys, reg_payload, reg_pairs, reg_tiles;
   PinnedBuf reg_host;
+  int reg_batch_launches = 0;
   // batched cycle match (sage_cycle_match_batch: match_batch.hip): the slices' (response, pixel) pairs of both passes
   // [2][B][S][K], the counter of finished workgroups (zero between calls), the pinned counts [SAGE_MATCH_MAX_BATCH]; the
   // device's CU count (0: not asked yet) and the number of slices of the last call
   DevBuf mb_part, mb_done;
   PinnedBuf mb_host;
   int mb_cus = 0, mb_slices = 0;
-  // loop pre-check (sage_loop_precheck: registration.hip): the way back [B][K], then one candidate's gathered points
+  // loop pre-check (sage_loop_precheck: registration.hip): the way back [B][K], then the B candidates' gathered points
   DevBuf pre_scratch;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
