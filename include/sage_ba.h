@@ -385,6 +385,37 @@ typedef struct SageOverlapStats
 int sage_track_overlap(SageWorkspace *ws, const float *R, const float *t, const float *dpts0_dev, float depth_scale,
                        const float *homo_dev, int M, const SageCamera *cam, const float *mask_dev, float eps,
                        SageOverlapStats *out);
+/* sage_track_overlap for B poses over ONE point set, camera and mask -- the tracked candidates of one loop query
+ * (loop_detector.cpp:165-183, :321-342 call ComputeAreaInlierRatio once per candidate).  Row b of `out` equals, byte for
+ * byte, what sage_track_overlap(ws, poses[b].R, poses[b].t, dpts0_dev, poses[b].depth_scale, homo_dev, M, cam, mask_dev, eps, .)
+ * returns, n_candidates included: a row keeps the single call's partition (min(ceil(M / 256), 32) workgroups, grid-strided),
+ * its sums in workgroup order and its device functions.
+ * Three launches whatever B (the row is a grid axis), one wait on the workspace's ticket, no blocking copy; the poses travel
+ * in the kernel arguments.  The input set does not depend on the pose: its extremes, filter pass and pinned copy happen
+ * once (row 0's workgroups), the host hulls it once and writes input_area and n_candidates[0] into every row -- B + 1 host
+ * hulls per call where B single calls make 2 B.
+ * Memory, shared with sage_track_overlap and kept by the workspace: device 12816 * B + 8 * M * (B + 1) bytes (per row the 32
+ * workgroups' partial records: 8 + 8 + 384 bytes each, and 16 bytes of append counters; then the survivors of the input
+ * set and of the B warped sets), pinned 32 * B + 8 * M * (B + 1) bytes (the rows' headers, then the same B + 1 sets).
+ * SAGE_E_INVALID, before anything touches the device: NULL ws; B < 0 or B > SAGE_OVERLAP_MAX_BATCH; with B > 0 a NULL
+ * pointer, M <= 0, or a camera sage_track_overlap refuses.  B = 0: SAGE_OK, nothing is read, launched or waited for.  On
+ * an error no row of `out` is meaningful. */
+#define SAGE_OVERLAP_MAX_BATCH 32 /* = SAGE_TRACK_MAX_BATCH */
+typedef struct SageOverlapPose /* host; row-major R10, t10 */
+{
+  float R[9], t[3];
+  float depth_scale;
+} SageOverlapPose;
+int sage_track_overlap_batch(SageWorkspace *ws, const SageOverlapPose *poses, int B, const float *dpts0_dev,
+                             const float *homo_dev, int M, const SageCamera *cam, const float *mask_dev, float eps,
+                             SageOverlapStats *out /* [B] */);
+/* Host only, no device: what a batch of B poses over M points reserves (the formulas above; 0 for B = 0) and launches (3; 0
+ * for B = 0), and the workgroups of one row.  Every output pointer may be NULL.  SAGE_E_INVALID for B out of range, or
+ * M <= 0 with B > 0. */
+int sage_track_overlap_batch_plan(int M, int B, int64_t *device_bytes, int64_t *pinned_bytes, int32_t *launches,
+                                  int32_t *workgroups_per_row);
+/* kernel launches of the workspace's last sage_track_overlap_batch (0: none yet, B = 0, or NULL ws) */
+int sage_track_overlap_batch_launches(const SageWorkspace *ws);
 /* Stateless host math: area of the convex hull of n 2-D points (xy interleaved, [n,2]) in double arithmetic; 0 for fewer
  * than three distinct points or a collinear set.  The points are ordered first: any permutation of a set gives the
  * identical double.  Points with a non-finite coordinate are left out.  n_vertices (optional): corners of the hull,
@@ -765,8 +796,8 @@ int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float que
  *      check is off with the match-geometry term (:1515);
  *   4. one sage_track_frame_batch (dof 7, photometric + match geometry) over the survivors: the query's photometric side is
  *      shared, feat1 / grad1 / mask1 are the candidate's;
- *   5. per tracked survivor one sage_track_overlap with depth_scale = scale_b / query_depth_divisor (:1644), one after the
- *      other.
+ *   5. one sage_track_overlap_batch over the survivors the tracker returned SAGE_OK for, in survivor order, with
+ *      depth_scale = scale_b / query_depth_divisor (:1644): three launches whatever their number.
  * Per candidate the result equals sage_track_frame + sage_track_overlap on the gathered inputs, byte for byte.  A candidate
  * that is no survivor gets tracked = 0 (the rest of its result zeroed) and no launch beyond the gather, which skips it.
  * SAGE_E_INVALID (nothing is launched) for: NULL ws, cfg, query, results; B < 0 or B > SAGE_TRACK_MAX_BATCH; K < 0 or
@@ -774,7 +805,7 @@ int sage_loop_precheck(SageWorkspace *ws, const float *desc_query_dev, float que
  * query with N < 1, M < 1, FS not 16 / 32, pyr.levels outside 1..SAGE_MAX_LEVELS, a NULL array, fx / fy of pyr.cam[0] not
  * positive and finite; a divisor that is not positive and finite; for a survivor: a NULL member of cands[b] / vcands[b],
  * reg.n_inliers > K.  B = 0 or no survivor: SAGE_OK, the results zeroed.
- * Waits: the rounds of sage_track_frame_batch (one each), then one per tracked survivor (the overlap). */
+ * Waits: the rounds of sage_track_frame_batch (one each), then one (the overlap batch). */
 typedef struct SageLoopVerifyQuery /* device pointers: the query keyframe's side of every survivor's problem */
 {
   int32_t N, FS;                    /* sampled pixels, feature channels */

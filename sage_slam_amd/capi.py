@@ -135,7 +135,7 @@ SYMBOLS = [
     "sage_tracker_photo_jac_error_calculate", "sage_tracker_photo_error_calculate",
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
-    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_lm_batch", "sage_track_frame", "sage_track_frame_batch", "sage_track_overlap", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
+    "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_lm_batch", "sage_track_frame", "sage_track_frame_batch", "sage_track_overlap", "sage_track_overlap_batch", "sage_track_overlap_batch_plan", "sage_track_overlap_batch_launches", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
     "sage_vocabulary_create", "sage_vocabulary_destroy", "sage_vocabulary_num_nodes", "sage_vocabulary_num_words", "sage_vocabulary_channels", "sage_vocabulary_depth", "sage_vocabulary_max_fanout", "sage_vocabulary_staged_nodes",
     "sage_bow_transform", "sage_bow_score", "sage_bow_db_create", "sage_bow_db_destroy", "sage_bow_db_add", "sage_bow_db_size", "sage_bow_db_query",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
@@ -475,6 +475,63 @@ def track_overlap(ws: "Workspace", R, t, dpts0, homo, cam, mask, eps, depth_scal
     _chk(track_overlap_raw(ws.h, Rh.ctypes.data, th.ctypes.data, dptr(dpts0), float(depth_scale), dptr(homo), M,
                            C.addressof(c), dptr(mask), float(eps), C.addressof(out)), "sage_track_overlap")
     return out
+
+
+OVERLAP_MAX_BATCH = 32
+
+
+class SageOverlapPose(C.Structure):
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("depth_scale", C.c_float)]
+
+
+def overlap_pose(R, t, depth_scale: float = 1.0) -> SageOverlapPose:
+    """R [3,3] (row-major R10), t [3], depth_scale -> one row of ``sage_track_overlap_batch``"""
+    return SageOverlapPose((C.c_float * 9)(*_f32(R).reshape(9)), (C.c_float * 3)(*_f32(t).reshape(3)), float(depth_scale))
+
+
+def track_overlap_batch_raw(ws_handle, poses_ptr, B, dpts0_ptr, homo_ptr, M, cam_ptr, mask_ptr, eps, out_ptr) -> int:
+    """``sage_track_overlap_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_track_overlap_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                  C.c_void_p]
+    return int(f(ws_handle, poses_ptr, int(B), dpts0_ptr, homo_ptr, int(M), cam_ptr, mask_ptr, eps, out_ptr))
+
+
+def track_overlap_batch(ws: "Workspace", poses, dpts0, homo, cam, mask, eps) -> list:
+    """``sage_track_overlap`` for every pose of ``poses`` (``SageOverlapPose``, or (R, t, depth_scale) triples) over one
+    point set, camera and mask, in three launches and one wait -> a list of ``SageOverlapStats``, row b what the single
+    call returns for poses[b], byte for byte."""
+    rows = [p if isinstance(p, SageOverlapPose) else overlap_pose(*p) for p in poses]
+    B = len(rows)
+    arr = (SageOverlapPose * max(B, 1))(*rows)
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    M = int(homo.shape[0])
+    assert dpts0.numel() == M and tuple(mask.shape) == (int(c.h), int(c.w))
+    out = (SageOverlapStats * max(B, 1))()
+    _chk(track_overlap_batch_raw(ws.h, C.addressof(arr), B, dptr(dpts0), dptr(homo), M, C.addressof(c), dptr(mask),
+                                 float(eps), C.addressof(out)), "sage_track_overlap_batch")
+    return [out[b] for b in range(B)]
+
+
+def track_overlap_batch_plan_raw(M, B, device_bytes_ptr, pinned_bytes_ptr, launches_ptr, workgroups_ptr) -> int:
+    f = lib().sage_track_overlap_batch_plan
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(int(M), int(B), device_bytes_ptr, pinned_bytes_ptr, launches_ptr, workgroups_ptr))
+
+
+def track_overlap_batch_plan(M: int, B: int) -> dict:
+    """What a batch of B poses over M points reserves and launches, through ``sage_track_overlap_batch_plan`` (host only)."""
+    dev = C.c_int64(); pin = C.c_int64(); launches = C.c_int32(); wgs = C.c_int32()
+    _chk(track_overlap_batch_plan_raw(M, B, C.addressof(dev), C.addressof(pin), C.addressof(launches), C.addressof(wgs)),
+         "sage_track_overlap_batch_plan")
+    return dict(device_bytes=dev.value, pinned_bytes=pin.value, launches=launches.value, workgroups_per_row=wgs.value)
+
+
+def track_overlap_batch_launches(ws: "Workspace") -> int:
+    """kernel launches of the workspace's last ``sage_track_overlap_batch``"""
+    f = lib().sage_track_overlap_batch_launches
+    f.argtypes = [C.c_void_p]
+    return int(f(ws.h if ws is not None else None))
 
 
 def convex_hull_area(xy):

@@ -1484,7 +1484,10 @@ extern "C" int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, cons
   if ((rc = sage_track_frame_batch(&lm, 7, probs, ns, pose12, scale, err, iters, status, nullptr, 0, nullptr)))
     return rc;
 
-  // 5. overlap statistics of every tracked survivor, one after the other
+  // 5. overlap statistics of every tracked survivor: one batch, a row per survivor whose tracker returned SAGE_OK
+  SageOverlapPose ov_pose[SAGE_TRACK_MAX_BATCH];
+  SageOverlapStats ov[SAGE_TRACK_MAX_BATCH];
+  int ov_of[SAGE_TRACK_MAX_BATCH], n_ov = 0;
   for (int s = 0; s < ns; ++s)
   {
     SageLoopVerifyResult &r = results[surv[s]];
@@ -1496,14 +1499,22 @@ extern "C" int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, cons
     r.iters = iters[s];
     if (status[s] != SAGE_OK)
       continue;
-    SageOverlapStats ov;
-    if ((rc = sage_track_overlap(ws, r.pose12, r.pose12 + 9, query->valid_dpts0_dev, scale[s] / query_depth_divisor,
-                                 query->valid_homo_dev, query->M, &cam, query->mask_dev, query->eps, &ov)))
-      return rc;
-    r.area_ratio = ov.area_ratio;
-    r.inlier_ratio = ov.inlier_ratio;
-    r.average_motion = ov.average_motion;
-    r.area_inlier_ratio = ov.area_ratio * ov.inlier_ratio;
+    SageOverlapPose &q = ov_pose[n_ov];
+    std::memcpy(q.R, r.pose12, sizeof(q.R));
+    std::memcpy(q.t, r.pose12 + 9, sizeof(q.t));
+    q.depth_scale = scale[s] / query_depth_divisor; // :1644
+    ov_of[n_ov++] = surv[s];
+  }
+  if ((rc = sage_track_overlap_batch(ws, ov_pose, n_ov, query->valid_dpts0_dev, query->valid_homo_dev, query->M, &cam,
+                                     query->mask_dev, query->eps, ov)))
+    return rc;
+  for (int i = 0; i < n_ov; ++i)
+  {
+    SageLoopVerifyResult &r = results[ov_of[i]];
+    r.area_ratio = ov[i].area_ratio;
+    r.inlier_ratio = ov[i].inlier_ratio;
+    r.average_motion = ov[i].average_motion;
+    r.area_inlier_ratio = ov[i].area_ratio * ov[i].inlier_ratio;
   }
   return SAGE_OK;
 }

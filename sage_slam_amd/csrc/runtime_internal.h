@@ -208,8 +208,10 @@ struct SageWorkspace
   DevBuf trk_bpart, trk_bdpts;
   // overlap statistics (sage_track_overlap, overlap.hip): per-workgroup partials + survivor counters, the survivors of
   // both hull sets, and the pinned region the finish kernel publishes into; all grow with M and go with the workspace
+  // A batch (sage_track_overlap_batch) holds B rows in the same three; ov_batch_launches: what the last batch launched
   DevBuf ov_part, ov_surv;
-  PinnedBuf ov_host; // [header | survivors of the input set [M][2] | of the warped set [M][2]]
+  PinnedBuf ov_host; // [header [B] | survivors of the input set [M][2] | of the warped set [M][2], per row]
+  int ov_batch_launches = 0;
   // exact selection (sage_depth_scale_ratio, sage_median_f32: depth_scale.hip): the keys [M] (grow with M), the histograms,
   // counts and hand-over state of the passes, and the pinned record the finish kernel publishes
   DevBuf sel_keys, sel_scratch;
