@@ -556,6 +556,119 @@ int sage_bow_db_size(const SageBowDatabase *db); /* entries; -1 for NULL */
 int sage_bow_db_query(const SageBowDatabase *db, const int32_t *ids, const double *vals, int n, int max_results, int max_id,
                       int32_t *entry_ids, double *scores, int capacity, int *n_out);
 
+/* ---- training the vocabulary: TemplatedVocabulary::create (thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:545-572)
+ *      as the reference's voc_builder tool runs it on FTensor descriptors: HKmeansStep (:627-815), initiateClustersKMpp
+ *      (:829-909), createWords (:914-934), setNodeWeights (:939-989), with FTensor::meanValue / distance
+ *      (core/system/dl_descriptor.cpp:6-28) ----
+ * Hierarchical k-means over M training descriptors of C floats, level by level; all nodes of a level in the same launches.
+ * A NODE's points are taken in ascending training order (the index into desc_dev's columns).  The root holds all M points
+ * and is at level 0; its children are at level 1.
+ *   n <= k points (:646-656): one child per point, child j carries point j's descriptor and holds that point alone.
+ *   n > k: kmeans++ seeding, then Lloyd rounds t = 1, 2, ...: round 1 assigns to the seeded centres, round t > 1 to the means
+ *     of round t-1's clusters.  A point goes to the centre with the smallest d2 = sum_ch (x - c)^2, accumulated in fp32 in
+ *     channel order exactly as sage_bow_transform's walk does; the first smallest wins (:719-730; descriptors must be
+ *     finite, a NaN is never smaller here).  The node stops at the first round t >= 2 with
+ *     (double)((float)mismatch / (float)n) < 1.0e-3, mismatch = the points whose cluster differs from round t-1's (:749-765).
+ *     Its children carry the centres that PRODUCED the final assignment (not the means after it) and hold its clusters.
+ *     max_iterations > 0: a node that has not stopped at round t = max_iterations stops there all the same, with that
+ *     round's centres and assignment, and is counted in SageVocabularyBuildStats::nodes_capped (the reference has no cap;
+ *     0 = none; max_iterations = 1 is legal: the seeded centres).
+ *   A child with more than one point is split again while its level is < L (:792-813); every other child is a leaf.
+ * Distance: d2 above decides every argmin.  Where the reference uses the value of F::distance (the L2 norm, not its square)
+ * -- kmeans++'s min_dists, its `> 0` test, dist_sum and the cut (:846-907) -- the value is (double)sqrtf(d2): the seeding is
+ * proportional to D, not to D^2, as in the reference.
+ * Seeding of a node (positions p = 0..n-1 in its order; u(j) = (double)(draw(j) >> 11) * 2^-53 in [0, 1), draw below):
+ *   centre 0 = point min(n - 1, (int64)(u(0) * (double)n))                                       [RandomInt(0, n-1)]
+ *   round r = 1..k-1: min_d[p] = dist(p, centre 0) for r = 1; afterwards, where min_d[p] > 0, the smaller of min_d[p] and
+ *     dist(p, centre r-1).  dist_sum = the sum of min_d: per TILE (256 consecutive positions of the node, the last one
+ *     partial) the fp64 sum of its values by the pairwise tree that adds lanes l and l + s for s = 1, 2, 4, ..., 128
+ *     (positions past the node's end count 0), then the tiles' sums added in tile order.  dist_sum == 0 ends the seeding:
+ *     the node has r centres (fewer than k children).  Otherwise cut = u(r + a k) * dist_sum for the first a = 0, 1, ...
+ *     with cut != 0 (the do-while of :884-887; after a = 63 cut = dist_sum) [RandomValue(0, dist_sum)], and centre r is the
+ *     point picked so: the first tile whose running sum S_t = S_{t-1} + (its sum) reaches cut (S_t >= cut); inside it, from
+ *     S_{t-1}, min_d is added position by position and the first position whose running sum reaches cut is taken; if none
+ *     does (the tree sum and the sequential sum round differently), the tile's last position with min_d > 0.
+ * draw(j) of a node = sage_vocabulary_build_draw(seed, path, depth, j): path = the child indices from the root to the node
+ *   (depth 0 for the root), with mix(z) = { z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *   z ^ (z >> 31) } and G = 0x9E3779B97F4A7C15 (splitmix64), all in uint64:
+ *     h = mix(seed + G); for i < depth: h = mix((h ^ (uint64)path[i]) + G); draw = mix(h + (uint64)(j + 1) * G).
+ *   (DBoW2 draws from libc rand() in recursion order; that stream cannot be reproduced by a level-synchronous build.)
+ * Centre update -- A DELIBERATE DEVIATION: per cluster and channel the sum of its points in fp64 -- per tile in ascending
+ *   position, then the tiles' sums in tile order --, divided by the cluster's size in fp64, rounded once to fp32.  The
+ *   reference adds fp32 tensors one by one and divides in fp32 (dl_descriptor.cpp:11-18); its rounding depends on the order
+ *   and is further from the exact mean.
+ * Emptied cluster -- THE SECOND DEVIATION: a cluster that loses all its points keeps its previous centre (and becomes a
+ *   leaf no point reaches).  The reference's meanValue reads descriptors[0] of an empty vector: undefined behaviour.
+ * Numbering (DBoW2's creation order): node 0 is the root; a node's children get consecutive ids when the node is finished,
+ *   then the children that are split are finished depth-first in child order.  Words are the leaves in ascending node id.
+ *   parent[i] < i holds.  With equal draws these are the arrays the reference would write.
+ * Weights: TF / BINARY: every word 1.  IDF / TF_IDF: Ni = the training documents with at least one point whose walk through
+ *   the finished tree (sage_bow_transform's own kernel) ends on word i; weight = log((double)NDocs / (double)Ni) on the host;
+ *   a word no document reaches keeps 0.  (The walk sends a point to the leaf the build holds it in, except duplicates inside
+ *   a node of n <= k points, which all walk to the first of them -- as in the reference.)
+ * Two builds of the same input give identical bytes: no float atomics, every sum has a fixed order. */
+#define SAGE_VOC_TF_IDF 0 /* DBoW2::WeightingType, in its order */
+#define SAGE_VOC_TF 1
+#define SAGE_VOC_IDF 2
+#define SAGE_VOC_BINARY 3
+#define SAGE_VOC_BUILD_MAX_LEVELS 8
+typedef struct SageVocabularyBuild SageVocabularyBuild;
+typedef struct SageVocabularyBuildConfig
+{
+  int32_t k, L;           /* branching factor, depth levels */
+  int32_t weighting;      /* SAGE_VOC_* */
+  int32_t scoring;        /* SAGE_BOW_* (recorded in the result; only SAGE_BOW_L1 can be created) */
+  int32_t max_iterations; /* Lloyd rounds per node; 0 = no cap */
+  uint64_t seed;
+} SageVocabularyBuildConfig;
+typedef struct SageVocabularyBuildStats
+{
+  int32_t levels;                                  /* levels that had a node to split (<= L) */
+  int32_t n_nodes, n_words;                        /* of the finished tree, the root counted */
+  int32_t nodes_capped;                            /* nodes stopped by max_iterations */
+  int32_t nodes[SAGE_VOC_BUILD_MAX_LEVELS];        /* [l]: nodes split at level l (the root: l = 0) ... */
+  int32_t kmeans_nodes[SAGE_VOC_BUILD_MAX_LEVELS]; /* ... of them with n > k */
+  int32_t seed_rounds[SAGE_VOC_BUILD_MAX_LEVELS];  /* seeding rounds run at level l: k - 1, or 0 without a k-means node */
+  int32_t rounds[SAGE_VOC_BUILD_MAX_LEVELS];       /* Lloyd rounds run at level l = those of its slowest node */
+  int32_t launches[SAGE_VOC_BUILD_MAX_LEVELS];     /* kernel launches of level l */
+  int32_t waits[SAGE_VOC_BUILD_MAX_LEVELS];        /* ticket waits of level l */
+} SageVocabularyBuildStats;
+/* k 10, L 4 (tools/voc_builder.cpp:33-34), SAGE_VOC_TF_IDF, SAGE_BOW_L1, max_iterations 100, seed 0 */
+void sage_vocabulary_build_config_default(SageVocabularyBuildConfig *cfg);
+/* desc_dev [C, M] channel-major on the device (sage_bow_transform's pre-gathered form); doc_begin_host [n_docs + 1]: document
+ * d holds the points doc_begin[d] .. doc_begin[d + 1] - 1; ascending (empty documents are legal), [0] = 0, [n_docs] = M.
+ * SAGE_E_INVALID, before anything touches the device: a NULL pointer, k < 2, L < 1, C < 1, M < 1, n_docs < 1, offsets that
+ * are not such a sequence, max_iterations < 0, a weighting that is no SAGE_VOC_* or a scoring that is no SAGE_BOW_* value.
+ * SAGE_E_UNSUPPORTED: C > 64, k > 64, L > 8, k^L > 2^20, M >= 2^31.
+ * Per level: one launch that seeds (centre 0, the n <= k nodes), k - 1 seeding rounds of launches_per_seed_round launches,
+ * Lloyd rounds of launches_per_lloyd_round launches and one ticket wait each -- nodes that stopped drop out of the round's
+ * work list --, then the level's end (centres and child sizes out, the stable partition of every node's points by child: two
+ * launches, a copy, the ticket) and one wait.  Then the leaf of every point, the walk and the document counts.  The launches of a round do not depend on the number of nodes. */
+int sage_vocabulary_build(SageWorkspace *ws, const SageVocabularyBuildConfig *cfg, const float *desc_dev, int C, int64_t M,
+                          const int64_t *doc_begin_host, int n_docs, SageVocabularyBuild **out);
+/* the finished tree, as sage_vocabulary_create takes it; the arrays belong to the build (inner nodes have weight 0) */
+int sage_vocabulary_build_desc(const SageVocabularyBuild *build, SageVocabularyDesc *desc);
+/* *ni [*n_words] (host, owned by the build): Ni of every word; all 0 under TF / BINARY, where it is not computed */
+int sage_vocabulary_build_docs_with_word(const SageVocabularyBuild *build, const int32_t **ni, int *n_words);
+/* *leaf_node_dev [M] (device, owned by the build): per training point the node id of the leaf that holds it */
+int sage_vocabulary_build_node_of_point(const SageVocabularyBuild *build, const int32_t **leaf_node_dev);
+int sage_vocabulary_build_stats(const SageVocabularyBuild *build, SageVocabularyBuildStats *stats);
+/* What a build allocates and launches, without a device.  With Cp = 4 ceil(C / 4), W = k^L,
+ * A = min(k^(L-1), max(1, M / 2)) (nodes split at one level), T = M / 256 + min(k^(L-1), max(1, M / (k + 1))) (tiles of the
+ * k-means nodes of one level), integer divisions:
+ *   device_bytes = M (4 Cp + 8 + 4 + 4 + 4 + 4 + 4) + 8 A k Cp + 4 A + T (8 k C + 4 k + 4 k + 4 + 8) + 4 W + 16 + 2^24
+ *     (rows | min_d | two orders, cluster, leaf, word of every point | both centre sets | centre counts | per tile: sums,
+ *      sizes, offsets, mismatches, seeding sum | Ni | counter | document flags); 8 (n_docs + 1) more for the offsets
+ *   pinned_bytes = 32 A + 8 T + 16 A + 4 A k + 4 A k + 4 A k Cp
+ *     (node records | work items | round results | picks | child sizes | centres)
+ *   launches_per_seed_round = 2, launches_per_lloyd_round = 2.
+ * SAGE_E_INVALID / SAGE_E_UNSUPPORTED as sage_vocabulary_build for C, M, k, L; every output pointer may be NULL. */
+int sage_vocabulary_build_plan(int C, int64_t M, int k, int L, int64_t *device_bytes, int64_t *pinned_bytes,
+                               int32_t *launches_per_seed_round, int32_t *launches_per_lloyd_round);
+/* draw j of the node at `path` [depth] (see above); path may be NULL with depth <= 0.  Host only. */
+uint64_t sage_vocabulary_build_draw(uint64_t seed, const int32_t *path, int depth, int j);
+void sage_vocabulary_build_destroy(SageVocabularyBuild *build);
+
 /* ---- robust registration of keypoint matches: the step between sage_cycle_match and the keypoint factors ----
  * CameraTracker::FeatureMatchingGeo (core/system/camera_tracker.cpp:575-768, :770-947), MatchGeometryFactor's constructor
  * (core/gtsam/match_geometry_factor.cpp:98-190) and the loop-MG factor's gather two 3-D point sets from the cycle-consistent

@@ -137,6 +137,7 @@ SYMBOLS = [
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
     "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_lm_batch", "sage_track_frame", "sage_track_frame_batch", "sage_track_overlap", "sage_track_overlap_batch", "sage_track_overlap_batch_plan", "sage_track_overlap_batch_launches", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
     "sage_vocabulary_create", "sage_vocabulary_destroy", "sage_vocabulary_num_nodes", "sage_vocabulary_num_words", "sage_vocabulary_channels", "sage_vocabulary_depth", "sage_vocabulary_max_fanout", "sage_vocabulary_staged_nodes",
+    "sage_vocabulary_build_config_default", "sage_vocabulary_build", "sage_vocabulary_build_desc", "sage_vocabulary_build_docs_with_word", "sage_vocabulary_build_node_of_point", "sage_vocabulary_build_stats", "sage_vocabulary_build_plan", "sage_vocabulary_build_draw", "sage_vocabulary_build_destroy",
     "sage_bow_transform", "sage_bow_score", "sage_bow_db_create", "sage_bow_db_destroy", "sage_bow_db_add", "sage_bow_db_size", "sage_bow_db_query",
     "sage_window_create", "sage_window_destroy", "sage_window_add_keyframe", "sage_window_add_link", "sage_window_add_keypoint_link", "sage_window_hold", "sage_window_set_link_geo_loss",
     "sage_window_set_shard", "sage_window_finalize", "sage_window_num_keyframes", "sage_window_num_links",
@@ -707,6 +708,122 @@ def bow_transform(ws: "Workspace", voc: Vocabulary, desc, loc1d=None, per_point:
                            C.addressof(out)), "sage_bow_transform")
     r = (ids[:out.n_words].copy(), vals[:out.n_words].copy(), out)
     return r + (words,) if per_point else r
+
+
+# --------------------------------------------------------------------------- training the vocabulary
+SAGE_VOC_TF_IDF, SAGE_VOC_TF, SAGE_VOC_IDF, SAGE_VOC_BINARY = range(4)
+SAGE_VOC_BUILD_MAX_LEVELS = 8
+
+
+class SageVocabularyBuildConfig(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32),
+                ("max_iterations", C.c_int32), ("seed", C.c_uint64)]
+
+
+class SageVocabularyBuildStats(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("nodes_capped", C.c_int32)] + \
+               [(n, C.c_int32 * SAGE_VOC_BUILD_MAX_LEVELS) for n in ("nodes", "kmeans_nodes", "seed_rounds", "rounds", "launches", "waits")]
+
+
+def vocabulary_build_config_default() -> SageVocabularyBuildConfig:
+    cfg = SageVocabularyBuildConfig()
+    f = lib().sage_vocabulary_build_config_default
+    f.argtypes = [C.c_void_p]; f.restype = None
+    f(C.addressof(cfg))
+    return cfg
+
+
+def vocabulary_build_draw(seed: int, path, j: int) -> int:
+    """``sage_vocabulary_build_draw``: draw j of the node at ``path`` (child indices from the root).  No device."""
+    path = np.ascontiguousarray(path, np.int32)
+    f = lib().sage_vocabulary_build_draw
+    f.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_int]; f.restype = C.c_uint64
+    return int(f(int(seed), path.ctypes.data if path.size else None, int(path.size), int(j)))
+
+
+def vocabulary_build_plan_raw(Cn, M, k, L):
+    """``sage_vocabulary_build_plan`` -> (status code, dict(device_bytes, pinned_bytes, launches_per_seed_round,
+    launches_per_lloyd_round)).  No device."""
+    db, pb = C.c_int64(-1), C.c_int64(-1)
+    ls, ll = C.c_int32(-1), C.c_int32(-1)
+    f = lib().sage_vocabulary_build_plan
+    f.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = int(f(int(Cn), int(M), int(k), int(L), C.addressof(db), C.addressof(pb), C.addressof(ls), C.addressof(ll)))
+    return rc, dict(device_bytes=db.value, pinned_bytes=pb.value, launches_per_seed_round=ls.value, launches_per_lloyd_round=ll.value)
+
+
+def vocabulary_build_raw(ws_handle, cfg_ptr, desc_ptr, Cn, M, doc_begin_ptr, n_docs, out_ptr) -> int:
+    """``sage_vocabulary_build`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_vocabulary_build
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    return int(f(ws_handle, cfg_ptr, desc_ptr, int(Cn), int(M), doc_begin_ptr, int(n_docs), out_ptr))
+
+
+class VocabularyBuild:
+    """``sage_vocabulary_build``: hierarchical k-means over ``desc`` (float32 cuda tensor [C, M], channel-major) whose
+    documents are the column ranges ``doc_begin`` [n_docs + 1].  Keyword arguments set ``SageVocabularyBuildConfig`` fields
+    (k, L, weighting, scoring, max_iterations, seed).
+    ``voc``: the finished tree as ``Vocabulary`` / ``vocabulary.save_opencv_yaml`` take it (host copies); ``docs_with_word``
+    [n_words]; ``stats``; ``node_of_point()``: int32 cuda tensor [M] (a copy), the leaf node of every training point."""
+
+    def __init__(self, ws: "Workspace", desc, doc_begin, **cfg_fields):
+        import torch
+        assert desc.dtype == torch.float32 and desc.dim() == 2
+        cfg = vocabulary_build_config_default()
+        for name, v in cfg_fields.items():
+            assert hasattr(cfg, name), name
+            setattr(cfg, name, int(v))
+        doc_begin = np.ascontiguousarray(doc_begin, np.int64)
+        self.M = int(desc.shape[1])
+        self.h = C.c_void_p()
+        _chk(vocabulary_build_raw(ws.h, C.addressof(cfg), dptr(desc), int(desc.shape[0]), self.M, doc_begin.ctypes.data,
+                                  doc_begin.size - 1, C.addressof(self.h)), "sage_vocabulary_build")
+        L = lib()
+        d = SageVocabularyDesc()
+        f = L.sage_vocabulary_build_desc; f.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(int(f(self.h, C.addressof(d))), "sage_vocabulary_build_desc")
+        n, Cn = int(d.n_nodes), int(d.C)
+
+        def arr(ptr, count, ctype, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (count,)).astype(dtype, copy=True)
+
+        word_id = arr(d.word_id, n, C.c_int32, np.int32)
+        self.voc = dict(parent=arr(d.parent, n, C.c_int32, np.int32), descriptors=arr(d.descriptors, n * Cn, C.c_float, np.float32).reshape(n, Cn),
+                        weight=arr(d.weight, n, C.c_double, np.float64), word_id=word_id, k=int(cfg.k), L=int(cfg.L),
+                        scoring=int(d.scoring), weighting=int(cfg.weighting), n_nodes=n, n_words=int((word_id >= 0).sum()), C=Cn)
+        ni, nw = C.c_void_p(), C.c_int()
+        f = L.sage_vocabulary_build_docs_with_word; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _chk(int(f(self.h, C.addressof(ni), C.addressof(nw))), "sage_vocabulary_build_docs_with_word")
+        self.docs_with_word = arr(ni, nw.value, C.c_int32, np.int32) if nw.value else np.zeros(0, np.int32)
+        self.stats = SageVocabularyBuildStats()
+        f = L.sage_vocabulary_build_stats; f.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(int(f(self.h, C.addressof(self.stats))), "sage_vocabulary_build_stats")
+
+    def node_of_point(self):
+        p = C.c_void_p()
+        f = lib().sage_vocabulary_build_node_of_point; f.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(int(f(self.h, C.addressof(p))), "sage_vocabulary_build_node_of_point")
+        import torch
+
+        class _Holder:
+            pass
+
+        view = _Holder()
+        view.__cuda_array_interface__ = dict(shape=(self.M,), typestr="<i4", data=(int(p.value), False), version=2)
+        return torch.as_tensor(view, device="cuda").clone()
+
+    def close(self):
+        if self.h:
+            f = lib().sage_vocabulary_build_destroy
+            f.argtypes = [C.c_void_p]; f.restype = None
+            f(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _bow_vec(ids, vals):

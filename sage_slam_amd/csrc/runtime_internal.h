@@ -9,6 +9,9 @@
 //   bow.hip             the loop detector's bag of words (sage_vocabulary_*, sage_bow_transform): the vocabulary's device
 //                       layout, the tree walk, the compaction of the words reached, the host finish
 //   bow_database.cpp    (no HIP) the L1 score of two bag-of-words vectors and the inverted-file database
+//   voc_build.hip       training the vocabulary (sage_vocabulary_build): the level loop, the seeding and Lloyd rounds of all
+//                       nodes of a level, the stable partition by child, the document counts
+//   voc_build_host.cpp  (no HIP) its draws, argument checks, plan, DBoW2's node numbering, the weights from the document counts
 //   registration.hip    robust registration of keypoint matches (sage_robust_registration, sage_match_points): the pair
 //                       kernel, the endpoint sort, the scan fused with the vote's cost and argmin, the hand-over; the loop
 //                       detector's pre-check of B candidates (sage_loop_precheck), a host composition

@@ -588,6 +588,30 @@ def make_vocabulary(k: int, L: int, C: int, seed: int = 0, ragged: bool = False)
                 scoring=0, weighting=0, n_nodes=n, n_words=int(len(leaves)), C=C)
 
 
+VOC_TRAINING_KINDS = ("planted", "iid")
+
+
+def make_voc_training_set(k: int, L: int, C: int, n_docs: int, per_doc: int, seed: int = 0, kind: str = "planted") -> dict:
+    """Training descriptors for ``sage_vocabulary_build``: ``n_docs`` documents of ``per_doc`` points each.
+    ``kind`` "planted": a hierarchy of well-separated centres -- level l's centres are their parent's plus Gaussian offsets
+    of sigma 4^-(l-1), k per node down to level L --, every point a uniformly drawn level-L centre plus noise of sigma
+    0.02 * 4^-(L-1): the clusters k-means should find are far apart next to their own spread at every level.
+    "iid": Gaussian descriptors of sigma 0.3 (no structure: many close decisions).
+    -> dict(desc [C, M] float32 channel-major, doc_begin [n_docs + 1] int64, M, C, n_docs, kind).  Deterministic per ``seed``."""
+    assert kind in VOC_TRAINING_KINDS and k >= 2 and L >= 1 and n_docs >= 1 and per_doc >= 1
+    rng = np.random.default_rng(seed)
+    M = n_docs * per_doc
+    if kind == "iid":
+        pts = rng.normal(0.0, 0.3, (M, C))
+    else:
+        centres = np.zeros((1, C))
+        for l in range(1, L + 1):
+            centres = (centres[:, None, :] + rng.normal(0.0, 4.0 ** -(l - 1), (centres.shape[0], k, C))).reshape(-1, C)
+        pts = centres[rng.integers(0, centres.shape[0], M)] + rng.normal(0.0, 0.02 * 4.0 ** -(L - 1), (M, C))
+    return dict(desc=np.ascontiguousarray(pts.T, F32), doc_begin=np.arange(n_docs + 1, dtype=np.int64) * per_doc, M=M, C=C,
+                n_docs=n_docs, kind=kind)
+
+
 def make_bow_problem(H: int, W: int, C: int, seed: int = 0, kind: str = "iid", voc: dict = None) -> dict:
     """Inputs of ``sage_bow_transform`` (``LoopDetector::AddKeyframe``): a descriptor map ``desc`` [C, H*W] (``feat_desc``
     reshaped to {C, -1}) and the valid locations ``loc1d`` [M] (int64, ascending) of the eroded mask of ``make_window`` (8
