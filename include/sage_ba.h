@@ -464,6 +464,53 @@ int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const float *t10
 int sage_median_f32(SageWorkspace *ws, const float *values_dev, const int64_t *loc1d_dev, int n, int drop_nan,
                     float *median_host, int *n_used_host, int *n_nan_host);
 
+/* sage_depth_scale_ratio_batch: B reference keyframes warped into ONE keyframe to scale -- the loop detector's case, one
+ * query keyframe and every accepted candidate (loop_detector.cpp:194 inside the loop of :143).  The rows differ in pose,
+ * point set and M; the bias, the mask and the camera of the keyframe to scale are shared.
+ * CONTRACT: out[b], and row b's optional per-point outputs, are byte-identical to sage_depth_scale_ratio on that row's
+ * inputs, whatever the other rows, their order and their sizes: the per-point arithmetic is the single call's device
+ * function and the selection only sums integers.  A row that selects nothing is no error (ratio NaN) and does not disturb
+ * its neighbours.
+ * Launches: 5 whatever B and the M_b (sage_depth_scale_ratio_batch_launches) -- the per-point kernel, two digit passes and
+ * the finish, each over a flat list of (row, workgroup) items, min(ceil(M_b / 256), 256) of them for row b as in the single
+ * call, then the ticket; one wait.  The rows' table travels as a kernel argument: no copy, no per-row launch or memset.
+ * (B = 1 runs the single call's kernels: the same five launches.)
+ * Memory, shared with the single calls and kept by the workspace: device 4 * sum(M_b) + 24608 * B bytes (the keys of all
+ * rows at row offsets; per row three histograms, the counters and the pass state), pinned 32 * B bytes (a record per row).
+ * Single and batched calls may be interleaved on one workspace in any order.
+ * SAGE_E_INVALID, before anything is launched: a NULL ws, rows, cam, bias1_dev, mask_dev or out; B < 0 or
+ * B > SAGE_DEPTH_SCALE_MAX_BATCH; a row with M <= 0 or a NULL dpt0_dev or homo0_dev; a camera sage_depth_scale_ratio
+ * refuses.  B = 0: SAGE_OK, nothing is launched. */
+#define SAGE_DEPTH_SCALE_MAX_BATCH 32 /* = SAGE_TRACK_MAX_BATCH */
+typedef struct SageDepthScaleRow /* one reference keyframe warped into the keyframe to scale */
+{
+  float R10[9], t10[3];         /* host values, row-major */
+  const float *dpt0_dev;        /* as in sage_depth_scale_ratio */
+  const int64_t *loc1d0_dev;    /* or NULL: dpt0_dev holds the M gathered depths */
+  const float *homo0_dev;       /* [M,3] */
+  int32_t M;
+  float *ratios_out_dev;        /* optional [M] */
+  int32_t *selected_out_dev;    /* optional [M] */
+} SageDepthScaleRow;
+int sage_depth_scale_ratio_batch(SageWorkspace *ws, const SageDepthScaleRow *rows, int B, const SageCamera *cam,
+                                 const float *bias1_dev, const float *mask_dev, float eps, int drop_nan,
+                                 SageDepthScaleStats *out /* [B] */);
+/* B medians in the same 5 launches: element b equals sage_median_f32(values_dev[b], loc1d_dev ? loc1d_dev[b] : NULL, n[b]),
+ * byte for byte.  loc1d_dev may be NULL, and so may any of its entries.  n_used_host, n_nan_host [B]: optional.
+ * SAGE_E_INVALID (nothing is launched) for a NULL ws; B out of range; with B > 0 a NULL values_dev, n or median_host, a NULL
+ * entry of values_dev, n[b] <= 0.  B = 0: SAGE_OK, nothing is launched. */
+int sage_median_f32_batch(SageWorkspace *ws, const float *const *values_dev, const int64_t *const *loc1d_dev,
+                          const int32_t *n, int B, int drop_nan, float *median_host, int32_t *n_used_host,
+                          int32_t *n_nan_host);
+/* Host only, no device: what a batch of B rows of M[b] points reserves (the formulas above), launches (5; 0 for B = 0) and
+ * the workgroups of its flat list.  Every output pointer may be NULL.  SAGE_E_INVALID for B out of range, a NULL M with
+ * B > 0, or a row with M <= 0. */
+int sage_depth_scale_ratio_batch_plan(const int32_t *M, int B, int64_t *device_bytes, int64_t *pinned_bytes,
+                                      int32_t *launches, int32_t *workgroups);
+/* kernel launches of the workspace's last sage_depth_scale_ratio_batch or sage_median_f32_batch (0: none yet, B = 0, or
+ * NULL ws) */
+int sage_depth_scale_ratio_batch_launches(const SageWorkspace *ws);
+
 /* ---- the loop detector's bag of words: LoopDetector::AddKeyframe (core/system/loop_detector.cpp:20-42) turns the
  *      descriptors of all valid pixels of a new keyframe into a DBoW2 bag-of-words vector, DetectLoop (:53-111) scores it
  *      against the temporal neighbours and queries the database with it ----
@@ -951,6 +998,67 @@ int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, const SageLoopV
                      const SageLoopCandidate *cands, const SageLoopVerifyCandidate *vcands, const SageLoopPrecheckResult *pre,
                      int B, int K, const int64_t *raw_matched_loc1d, const int32_t *inlier_kp_dev,
                      float match_geom_factor_weight, float *kp_gathered_dev, SageLoopVerifyResult *results);
+
+/* sage_loop_accept: the rest of the detector's loop body and what follows it (loop_detector.cpp:173-229) -- the accept
+ * test, the pose hand-over, df::CorrectDepthScale of every accepted candidate, the sort and the redundancy filter: from
+ * sage_loop_verify's results to the filtered LoopInfo list DetectLoop returns.  cands, pre and ver are the arrays of
+ * sage_loop_precheck and sage_loop_verify as they are.  A host composition; its only device work is ONE
+ * sage_depth_scale_ratio_batch (drop_nan = 1, no per-point outputs) over the accepted candidates.  All arithmetic is fp32.
+ *   Accepted (:165-183): ver[b].tracked, ver[b].status == SAGE_OK, ver[b].area_ratio >= min_area_ratio and
+ *     ver[b].inlier_ratio >= min_inlier_ratio (:173), metric = ver[b].area_inlier_ratio >= base_metric and
+ *     desc = pre[b].desc_match_inlier_ratio >= base_desc_ratio (:183).  A NaN fails every comparison.
+ *   Pose (camera_tracker.cpp:1651-1656, loop_detector.cpp:189-193): with R = pose12[0..8] (row-major), t = pose12[9..11] of
+ *     ver[b]: R_cur_ref = R^T (row-major); t_cur_ref[i] = ((-R[0][i]) * t[0] + (-R[1][i]) * t[1]) + (-R[2][i]) * t[2] without
+ *     contraction, then (t_cur_ref[i] * dpt_scale) / tracker_ref_scale, left to right.  Stated deviation: the reference
+ *     passes the rotation through a Sophus::SO3f quaternion and back; the library does not.
+ *   Scale (:194-196): query_scale = the ratio of row b of one batch over the accepted candidates in candidate order, with
+ *     R10 = R_cur_ref, t10 = the rescaled translation, dpt0_dev = cands[b].dpt_map_dev read at scands[b].valid_loc1d_dev,
+ *     homo0_dev = scands[b].valid_homo_dev, M = scands[b].M, the query's bias, mask and camera, eps = dpt_eps;
+ *     scale = that row's statistics; ref_scale = scands[b].dpt_scale; desc_inlier_ratio = desc; metric = metric;
+ *     id_ref = scands[b].id.
+ *   Sort (:207): the accepted candidates by desc_inlier_ratio, descending.  The reference's std::sort leaves the order of
+ *     equal ratios unspecified; here ties keep candidate order.
+ *   Redundancy filter (:210-228): the first of that order is kept; a later one is kept unless |id - id_kept| <
+ *     redundant_range for some candidate kept before it.  kept_order [B]: the kept candidates' indices in that order (the
+ *     rest -1); *n_kept: their number.
+ * infos [B] is in candidate order: a candidate that is not accepted has accepted = kept = 0 and the rest zeroed.
+ * No accepted candidate: SAGE_OK, *n_kept = 0, nothing is launched.
+ * SAGE_E_INVALID (nothing is launched) for: NULL ws, cfg, query, infos, kept_order or n_kept; B < 0 or
+ * B > SAGE_TRACK_MAX_BATCH; with B > 0 NULL cands, scands, pre or ver; for an accepted candidate: a NULL dpt_map_dev,
+ * valid_loc1d_dev or valid_homo_dev, M <= 0, a dpt_scale or tracker_ref_scale that is not positive and finite; with an
+ * accepted candidate: a NULL bias_dev or video_mask_dev, a camera sage_depth_scale_ratio refuses.  One wait. */
+typedef struct SageLoopAcceptConfig
+{
+  float min_area_ratio, min_inlier_ratio, base_metric, base_desc_ratio;
+  int64_t redundant_range;         /* cfg_.global_redundant_range */
+  float dpt_eps;
+} SageLoopAcceptConfig;
+typedef struct SageLoopScaleQuery /* the keyframe to scale: device pointers [h,w] and its level-0 camera */
+{
+  const float *bias_dev, *video_mask_dev;
+  SageCamera cam;
+} SageLoopScaleQuery;
+typedef struct SageLoopScaleCandidate /* next to cands[b]: the depth map is cands[b].dpt_map_dev */
+{
+  int64_t id;                      /* kf->id */
+  const int64_t *valid_loc1d_dev;  /* [M] kf->valid_locations_1d */
+  const float *valid_homo_dev;     /* [M,3] kf->valid_locations_homo */
+  int32_t M;
+  float dpt_scale;                 /* kf->dpt_scale */
+  float tracker_ref_scale;         /* GetRefScale() after this candidate's TrackFrame */
+} SageLoopScaleCandidate;
+typedef struct SageLoopInfo /* host */
+{
+  int32_t accepted, kept;
+  int64_t id_ref;
+  float R_cur_ref[9], t_cur_ref[3];
+  float query_scale, ref_scale, desc_inlier_ratio, metric;
+  SageDepthScaleStats scale;
+} SageLoopInfo;
+int sage_loop_accept(SageWorkspace *ws, const SageLoopAcceptConfig *cfg, const SageLoopScaleQuery *query,
+                     const SageLoopCandidate *cands, const SageLoopScaleCandidate *scands, const SageLoopPrecheckResult *pre,
+                     const SageLoopVerifyResult *ver, int B, SageLoopInfo *infos /* [B] in candidate order */,
+                     int32_t *kept_order /* [B] */, int32_t *n_kept);
 
 /* =====================================================================
  * Batched window engine (no reference counterpart; parity = sum of per-edge results)

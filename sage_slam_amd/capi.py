@@ -136,6 +136,7 @@ SYMBOLS = [
     "sage_geometric_jac_error_calculate", "sage_geometric_error_calculate", "sage_depth_and_grad",
     "sage_gaussian_pyramid_with_grad", "sage_se3_exp", "sage_pose_retract", "sage_nearest_psd", "sage_nearest_psd_reference", "sage_factor_block_count", "sage_factor_hessian_blocks",
     "sage_damped_solve_qr_f32", "sage_block_solve", "sage_solve_lookahead_count", "sage_lm_config_default", "sage_track_lm", "sage_track_lm_batch", "sage_track_frame", "sage_track_frame_batch", "sage_track_overlap", "sage_track_overlap_batch", "sage_track_overlap_batch_plan", "sage_track_overlap_batch_launches", "sage_convex_hull_area", "sage_depth_scale_ratio", "sage_median_f32",
+    "sage_depth_scale_ratio_batch", "sage_median_f32_batch", "sage_depth_scale_ratio_batch_plan", "sage_depth_scale_ratio_batch_launches",
     "sage_vocabulary_create", "sage_vocabulary_destroy", "sage_vocabulary_num_nodes", "sage_vocabulary_num_words", "sage_vocabulary_channels", "sage_vocabulary_depth", "sage_vocabulary_max_fanout", "sage_vocabulary_staged_nodes",
     "sage_vocabulary_build_config_default", "sage_vocabulary_build", "sage_vocabulary_build_desc", "sage_vocabulary_build_docs_with_word", "sage_vocabulary_build_node_of_point", "sage_vocabulary_build_stats", "sage_vocabulary_build_plan", "sage_vocabulary_build_draw", "sage_vocabulary_build_destroy",
     "sage_bow_transform", "sage_bow_score", "sage_bow_db_create", "sage_bow_db_destroy", "sage_bow_db_add", "sage_bow_db_size", "sage_bow_db_query",
@@ -153,7 +154,7 @@ SYMBOLS = [
     "sage_loop_mg_jac_error_calculate", "sage_loop_mg_error_calculate",
     "sage_tracker_match_geom_jac_error_calculate", "sage_tracker_match_geom_error_calculate", "sage_cycle_match",
     "sage_robust_registration", "sage_tls_estimate", "sage_registration_finish", "sage_match_points",
-    "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck", "sage_loop_verify",
+    "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck", "sage_loop_verify", "sage_loop_accept",
     "sage_robust_registration_batch", "sage_robust_registration_batch_plan", "sage_robust_registration_batch_launches",
     "sage_match_points_batch",
 ]
@@ -604,6 +605,96 @@ def median_f32(ws: "Workspace", values, loc1d=None, drop_nan: bool = False):
     _chk(median_f32_raw(ws.h, dptr(values), dptr(loc1d), n, int(bool(drop_nan)), C.addressof(med), C.addressof(n_used),
                         C.addressof(n_nan)), "sage_median_f32")
     return np.float32(med.value), n_used.value, n_nan.value
+
+
+DEPTH_SCALE_MAX_BATCH = 32
+
+
+class SageDepthScaleRow(C.Structure):
+    _fields_ = [("R10", C.c_float * 9), ("t10", C.c_float * 3), ("dpt0_dev", C.c_void_p), ("loc1d0_dev", C.c_void_p),
+                ("homo0_dev", C.c_void_p), ("M", C.c_int32), ("ratios_out_dev", C.c_void_p), ("selected_out_dev", C.c_void_p)]
+
+
+def depth_scale_ratio_batch_raw(ws_handle, rows_ptr, B, cam_ptr, bias1_ptr, mask_ptr, eps, drop_nan, out_ptr) -> int:
+    """``sage_depth_scale_ratio_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_depth_scale_ratio_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
+    return int(f(ws_handle, rows_ptr, int(B), cam_ptr, bias1_ptr, mask_ptr, eps, int(drop_nan), out_ptr))
+
+
+def depth_scale_row(R10, t10, dpt0, homo0, loc1d0=None, ratios=None, selected=None, M=None) -> SageDepthScaleRow:
+    """One row of a depth-scale batch from host R10 [3,3], t10 [3] and cuda tensors as in ``depth_scale_ratio``; ``M``: only
+    the first M points of ``homo0`` (and of ``loc1d0`` / the gathered ``dpt0``)"""
+    r = SageDepthScaleRow()
+    r.R10[:] = [float(v) for v in _f32(R10).reshape(9)]
+    r.t10[:] = [float(v) for v in _f32(t10).reshape(3)]
+    r.dpt0_dev, r.loc1d0_dev, r.homo0_dev = dptr(dpt0).value, dptr(loc1d0).value, dptr(homo0).value
+    r.M = int(homo0.shape[0]) if M is None else int(M)
+    r.ratios_out_dev, r.selected_out_dev = dptr(ratios).value, dptr(selected).value
+    return r
+
+
+def depth_scale_ratio_batch(ws: "Workspace", rows, cam, bias1, mask, eps, drop_nan: bool = False) -> list:
+    """``sage_depth_scale_ratio`` for every row of ``rows`` (``SageDepthScaleRow``: ``depth_scale_row``) against one keyframe
+    to scale (camera, bias, mask), in five launches and one wait -> a list of ``SageDepthScaleStats``, row b what the
+    single call returns on that row's inputs, byte for byte.  The caller keeps the rows' tensors alive."""
+    B = len(rows)
+    arr = (SageDepthScaleRow * max(B, 1))(*rows)
+    c = SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)])
+    hw = (int(c.h), int(c.w))
+    assert tuple(mask.shape) == hw and tuple(bias1.shape) == hw
+    out = (SageDepthScaleStats * max(B, 1))()
+    _chk(depth_scale_ratio_batch_raw(ws.h, C.addressof(arr), B, C.addressof(c), dptr(bias1), dptr(mask), float(eps),
+                                     int(bool(drop_nan)), C.addressof(out)), "sage_depth_scale_ratio_batch")
+    return [out[b] for b in range(B)]
+
+
+def median_f32_batch_raw(ws_handle, values_ptr, loc_ptr, n_ptr, B, drop_nan, median_ptr, n_used_ptr, n_nan_ptr) -> int:
+    """``sage_median_f32_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_median_f32_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, values_ptr, loc_ptr, n_ptr, int(B), int(drop_nan), median_ptr, n_used_ptr, n_nan_ptr))
+
+
+def median_f32_batch(ws: "Workspace", values, loc1d=None, drop_nan: bool = False) -> list:
+    """``median_f32`` of every tensor of ``values`` (``loc1d``: None, or a list with an int64 cuda tensor or None per
+    segment) through ``sage_median_f32_batch``: five launches, one wait -> a list of (median as np.float32, n_used, n_nan)"""
+    import torch
+    B = len(values)
+    locs = list(loc1d) if loc1d is not None else [None] * B
+    assert len(locs) == B and all(v.dtype == torch.float32 for v in values)
+    vp = (C.c_void_p * max(B, 1))(*[dptr(v).value for v in values])
+    lp = (C.c_void_p * max(B, 1))(*[dptr(l).value for l in locs])
+    n = (C.c_int32 * max(B, 1))(*[int(v.numel() if l is None else l.numel()) for v, l in zip(values, locs)])
+    med = (C.c_float * max(B, 1))(); n_used = (C.c_int32 * max(B, 1))(); n_nan = (C.c_int32 * max(B, 1))()
+    _chk(median_f32_batch_raw(ws.h, C.addressof(vp), C.addressof(lp) if loc1d is not None else None, C.addressof(n), B,
+                              int(bool(drop_nan)), C.addressof(med), C.addressof(n_used), C.addressof(n_nan)),
+         "sage_median_f32_batch")
+    return [(np.float32(med[b]), n_used[b], n_nan[b]) for b in range(B)]
+
+
+def depth_scale_ratio_batch_plan_raw(M_ptr, B, device_bytes_ptr, pinned_bytes_ptr, launches_ptr, workgroups_ptr) -> int:
+    f = lib().sage_depth_scale_ratio_batch_plan
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(M_ptr, int(B), device_bytes_ptr, pinned_bytes_ptr, launches_ptr, workgroups_ptr))
+
+
+def depth_scale_ratio_batch_plan(M) -> dict:
+    """What a batch of len(M) rows of M[b] points reserves and launches, through ``sage_depth_scale_ratio_batch_plan`` (host
+    only)."""
+    B = len(M)
+    arr = (C.c_int32 * max(B, 1))(*[int(m) for m in M])
+    dev = C.c_int64(); pin = C.c_int64(); launches = C.c_int32(); wgs = C.c_int32()
+    _chk(depth_scale_ratio_batch_plan_raw(C.addressof(arr), B, C.addressof(dev), C.addressof(pin), C.addressof(launches),
+                                          C.addressof(wgs)), "sage_depth_scale_ratio_batch_plan")
+    return dict(device_bytes=dev.value, pinned_bytes=pin.value, launches=launches.value, workgroups=wgs.value)
+
+
+def depth_scale_ratio_batch_launches(ws: "Workspace") -> int:
+    """kernel launches of the workspace's last ``sage_depth_scale_ratio_batch`` or ``sage_median_f32_batch``"""
+    f = lib().sage_depth_scale_ratio_batch_launches
+    f.argtypes = [C.c_void_p]
+    return int(f(ws.h if ws is not None else None))
 
 
 class Workspace:
@@ -2170,6 +2261,57 @@ def loop_verify(ws, cfg: SageLmConfig, query: SageLoopVerifyQuery, query_depth_d
                          C.addressof(pre), B, K, dptr(raw_matched), dptr(inlier_kp), match_geom_factor_weight, dptr(gathered),
                          C.addressof(res)), "sage_loop_verify")
     return res, gathered
+
+
+class SageLoopAcceptConfig(C.Structure):
+    _fields_ = [("min_area_ratio", C.c_float), ("min_inlier_ratio", C.c_float), ("base_metric", C.c_float),
+                ("base_desc_ratio", C.c_float), ("redundant_range", C.c_int64), ("dpt_eps", C.c_float)]
+
+
+class SageLoopScaleQuery(C.Structure):
+    _fields_ = [("bias_dev", C.c_void_p), ("video_mask_dev", C.c_void_p), ("cam", SageCamera)]
+
+
+class SageLoopScaleCandidate(C.Structure):
+    _fields_ = [("id", C.c_int64), ("valid_loc1d_dev", C.c_void_p), ("valid_homo_dev", C.c_void_p), ("M", C.c_int32),
+                ("dpt_scale", C.c_float), ("tracker_ref_scale", C.c_float)]
+
+
+class SageLoopInfo(C.Structure):
+    _fields_ = [("accepted", C.c_int32), ("kept", C.c_int32), ("id_ref", C.c_int64), ("R_cur_ref", C.c_float * 9),
+                ("t_cur_ref", C.c_float * 3), ("query_scale", C.c_float), ("ref_scale", C.c_float),
+                ("desc_inlier_ratio", C.c_float), ("metric", C.c_float), ("scale", SageDepthScaleStats)]
+
+
+def loop_accept_raw(ws_handle, cfg_ptr, query_ptr, cands_ptr, scands_ptr, pre_ptr, ver_ptr, B, infos_ptr, kept_ptr, n_kept_ptr) -> int:
+    """``sage_loop_accept`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_loop_accept
+    f.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3
+    return int(f(ws_handle, cfg_ptr, query_ptr, cands_ptr, scands_ptr, pre_ptr, ver_ptr, int(B), infos_ptr, kept_ptr, n_kept_ptr))
+
+
+def loop_accept(ws, cfg: SageLoopAcceptConfig, query_bias, query_mask, cam, cands, scands, pre, ver):
+    """The loop detector's accept test, pose hand-over, depth-scale correction, sort and redundancy filter through
+    ``sage_loop_accept``.  query_bias, query_mask [h,w]: cuda tensors of the keyframe to scale, cam: its level-0 camera; cands:
+    the dicts of ``loop_precheck`` (``dpt_map`` is read); scands: dicts with ``id``, the cuda tensors ``valid_loc1d`` [M] int64
+    and ``valid_homo`` [M,3], and the floats ``dpt_scale``, ``tracker_ref_scale``; pre, ver: the ctypes arrays of
+    ``SageLoopPrecheckResult`` / ``SageLoopVerifyResult`` [B].
+    -> (a ctypes array of B ``SageLoopInfo`` in candidate order, the kept candidates' indices in the reference's order)."""
+    B = len(cands)
+    arr = (SageLoopCandidate * max(B, 1))()
+    sarr = (SageLoopScaleCandidate * max(B, 1))()
+    for b, (c, s) in enumerate(zip(cands, scands)):
+        arr[b] = SageLoopCandidate(*[dptr(c.get(n)).value for n in ("desc", "dpt_map", "kp_loc", "kp_dpts0", "kp_homo0")])
+        sarr[b] = SageLoopScaleCandidate(int(s["id"]), dptr(s["valid_loc1d"]).value, dptr(s["valid_homo"]).value,
+                                         int(s["valid_homo"].shape[0]), float(s["dpt_scale"]), float(s["tracker_ref_scale"]))
+    q = SageLoopScaleQuery(dptr(query_bias).value, dptr(query_mask).value,
+                           SageCamera(*[float(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)]))
+    infos = (SageLoopInfo * max(B, 1))()
+    kept = (C.c_int32 * max(B, 1))()
+    n_kept = C.c_int32()
+    _chk(loop_accept_raw(ws.h, C.addressof(cfg), C.addressof(q), C.addressof(arr), C.addressof(sarr), C.addressof(pre),
+                         C.addressof(ver), B, C.addressof(infos), C.addressof(kept), C.addressof(n_kept)), "sage_loop_accept")
+    return infos, [int(kept[i]) for i in range(n_kept.value)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -17,39 +17,23 @@
 // sums of integers, the same whatever order they arrive in.  There is no floating-point sum anywhere in the selection,
 // so two calls on the same inputs return the same bytes.  No workgroup waits for another inside a kernel: the passes
 // are separate launches on the workspace's stream, every loop is bounded by M or by the bin count.
+//
+// sage_depth_scale_ratio_batch, sage_median_f32_batch: B rows in the same four launches and one ticket.  The bodies of the
+// four kernels are device functions of (a row's parameters, workgroup, workgroups of the row); the *_batch_kernel run them
+// over a flat list of (row, workgroup) items with the rows' table as a kernel argument, every row with its own keys,
+// scratch and pinned record, so row b returns the single call's bytes.  One row takes the single call's kernels.
 #include "runtime_internal.h"
 #include "sage_device.h"
+#include "depth_scale_plan.h"
 
 namespace
 {
-constexpr int kSelBins = 2048;           // bins of the widest digit
-constexpr int kSelPasses = 3;            // digits of 11 + 11 + 10 bits, from the top
-constexpr int kSelMaxBlocks = 256;       // workgroups of the per-point and the histogram passes; the rest is grid-strided
+// (kSelBins, kSelPasses, kSelMaxBlocks, SelState, SelHost, SelScratch: depth_scale_plan.h, shared with the host-only plan)
+static_assert(kSelBlock == kBlock, "a row's workgroups are counted on the host");
 constexpr uint32_t kSelNoKey = 0xffffffffu; // the image of a NaN's bit pattern: no value that takes part has this key
 
 __host__ __device__ constexpr int sel_shift(int pass) { return pass == 0 ? 21 : pass == 1 ? 10 : 0; }
 __host__ __device__ constexpr int sel_bins(int pass) { return pass == 2 ? 1024 : 2048; }
-
-struct SelState // what a pass hands to the next one
-{
-  uint32_t prefix; // the key's bits above the next digit
-  uint32_t rank;   // the wanted rank among the keys under that prefix
-};
-
-struct SelHost // the pinned record
-{
-  float value;
-  int32_t n_pos, n_selected, n_nan, n_used;
-  int32_t pad[3];
-};
-
-// device scratch of the selection: zero between calls (select_finish_kernel leaves it so)
-struct SelScratch
-{
-  uint32_t hist[kSelPasses][kSelBins];
-  int32_t cnt[4]; // |pos|, |selected|, NaNs among the selected
-  SelState state[2];
-};
 
 struct SelParams
 {
@@ -222,7 +206,9 @@ __device__ __forceinline__ DsPoint ds_point(const DsParams &P, int i)
   return o;
 }
 
-__global__ __launch_bounds__(kBlock) void depth_scale_point_kernel(const DsParams P, const SelParams S)
+// the bodies of the four kernels: workgroup `blk` of the `nblk` that share a row.  The single calls run them over a grid of
+// their own, a batch over its flat list of (row, workgroup) items: a row is the single call's partition
+__device__ __forceinline__ void ds_point_body(const DsParams &P, const SelParams &S, int blk, int nblk)
 {
   __shared__ uint32_t s_hist[kSelBins];
   __shared__ int s_cnt[4];
@@ -231,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void depth_scale_point_kernel(const DsParam
     s_cnt[tid] = 0;
   sel_hist_zero(s_hist);
   int n_pos = 0, n_sel = 0, n_nan = 0; // wave-uniform
-  for (long long base = (long long)blockIdx.x * kBlock; base < P.M; base += (long long)gridDim.x * kBlock) // (no int overflow near 2^31)
+  for (long long base = (long long)blk * kBlock; base < P.M; base += (long long)nblk * kBlock) // (no int overflow near 2^31)
   {
     const long long i = base + tid;
     const bool live = i < P.M;
@@ -257,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void depth_scale_point_kernel(const DsParam
 }
 
 // values[loc[i]] (or values[i]) -> keys; every value is "selected"
-__global__ __launch_bounds__(kBlock) void median_keys_kernel(const float *values, const int64_t *loc, const SelParams S)
+__device__ __forceinline__ void median_keys_body(const float *values, const int64_t *loc, const SelParams &S, int blk, int nblk)
 {
   __shared__ uint32_t s_hist[kSelBins];
   __shared__ int s_cnt[4];
@@ -266,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void median_keys_kernel(const float *values
     s_cnt[tid] = 0;
   sel_hist_zero(s_hist);
   int n_nan = 0, n_all = 0; // wave-uniform
-  for (long long base = (long long)blockIdx.x * kBlock; base < S.n; base += (long long)gridDim.x * kBlock)
+  for (long long base = (long long)blk * kBlock; base < S.n; base += (long long)nblk * kBlock)
   {
     const long long i = base + tid;
     const bool live = i < S.n;
@@ -287,7 +273,7 @@ __global__ __launch_bounds__(kBlock) void median_keys_kernel(const float *values
 }
 
 // pass 1 or 2: the bin of the pass before, then the histogram of this pass's digit under the prefix
-__global__ __launch_bounds__(kBlock) void select_hist_kernel(const SelParams S, int pass)
+__device__ __forceinline__ void select_hist_body(const SelParams &S, int pass, int blk, int nblk)
 {
   __shared__ uint32_t s_hist[kSelBins];
   __shared__ uint32_t s_sum[kBlock];
@@ -307,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const SelParams S, 
   uint32_t bin, rest;
   sel_scan<kSelBins>(S.scr->hist[pass - 1], rank, s_sum, s_pick, bin, rest); // (passes 0 and 1 both have 2048 bins)
   prefix = (prefix << 11) | bin;
-  if (blockIdx.x == 0 && tid == 0)
+  if (blk == 0 && tid == 0)
   {
     S.scr->state[pass - 1].prefix = prefix;
     S.scr->state[pass - 1].rank = rest;
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const SelParams S, 
   sel_hist_zero(s_hist);
   const int shift = sel_shift(pass), above = sel_shift(pass - 1);
   const uint32_t digit_mask = (uint32_t)sel_bins(pass) - 1u;
-  for (long long i = (long long)blockIdx.x * kBlock + tid; i < S.n; i += (long long)gridDim.x * kBlock)
+  for (long long i = (long long)blk * kBlock + tid; i < S.n; i += (long long)nblk * kBlock)
   {
     const uint32_t key = S.keys[i];
     if (key != kSelNoKey && (key >> above) == prefix)
@@ -324,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const SelParams S, 
   sel_hist_flush(s_hist, S.scr->hist[pass], sel_bins(pass));
 }
 
-__global__ __launch_bounds__(kBlock) void select_finish_kernel(const SelParams S)
+__device__ __forceinline__ void select_finish_body(const SelParams &S)
 {
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_pick[2];
@@ -348,23 +334,153 @@ __global__ __launch_bounds__(kBlock) void select_finish_kernel(const SelParams S
     z[i] = 0u;
 }
 
-int sel_blocks(int n) { return std::min((n + kBlock - 1) / kBlock, kSelMaxBlocks); }
+// ---- the single calls' kernels: one row, the grid is its workgroups ----
+__global__ __launch_bounds__(kBlock) void depth_scale_point_kernel(const DsParams P, const SelParams S)
+{
+  ds_point_body(P, S, blockIdx.x, gridDim.x);
+}
+// values[loc[i]] (or values[i]) -> keys; every value is "selected"
+__global__ __launch_bounds__(kBlock) void median_keys_kernel(const float *values, const int64_t *loc, const SelParams S)
+{
+  median_keys_body(values, loc, S, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kBlock) void select_hist_kernel(const SelParams S, int pass)
+{
+  select_hist_body(S, pass, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kBlock) void select_finish_kernel(const SelParams S) { select_finish_body(S); }
 
-// the workspace's selection buffers for n keys; the scratch is zeroed here when no finished call has left it so
+// ---- the batch's kernels: the same bodies over a flat list of (row, workgroup) items ----
+// Row b owns workgroups blk0[b] .. blk0[b + 1] - 1 of the grid (sel_blocks(n[b]) of them: the single call's partition), its
+// keys lie at keys + key0[b], its scratch and its pinned record are element b of scr and host.  A flat list keeps rows of
+// very different sizes from idling the device: a 2-D grid would launch the largest row's workgroups for every row.  The
+// table is a kernel argument (0.5 KB; 3.5 KB with the rows of the per-point kernel): it is read with scalar loads.
+struct SelBatch
+{
+  uint32_t *keys;
+  SelScratch *scr; // [B]
+  SelHost *host;   // [B]
+  int drop_nan, B;
+  int n[SAGE_DEPTH_SCALE_MAX_BATCH];
+  int blk0[SAGE_DEPTH_SCALE_MAX_BATCH + 1]; // (blk0[b] = the grid for b >= B)
+  long long key0[SAGE_DEPTH_SCALE_MAX_BATCH];
+};
+
+struct DsRow // what differs between the rows of a depth-scale batch
+{
+  float R[9], t[3];
+  const float *dpt0, *homo;
+  const int64_t *loc;
+  float *ratios_out;
+  int32_t *selected_out;
+};
+struct DsBatch
+{
+  DsParams shared; // bias, mask, eps, camera; the row's members are filled in from rows[b]
+  DsRow rows[SAGE_DEPTH_SCALE_MAX_BATCH];
+};
+static_assert(sizeof(DsBatch) + sizeof(SelBatch) <= 3840, "the per-point kernel's arguments stay under the 4 KB limit");
+
+// the row of workgroup blk: how many rows start at or before it (branch-free over the whole table)
+__device__ __forceinline__ int sel_row_of(const SelBatch &T, int blk)
+{
+  int b = 0;
+#pragma unroll
+  for (int r = 1; r < SAGE_DEPTH_SCALE_MAX_BATCH; ++r)
+    b += blk >= T.blk0[r] ? 1 : 0;
+  return b;
+}
+__device__ __forceinline__ SelParams sel_row(const SelBatch &T, int b)
+{
+  SelParams S;
+  S.keys = T.keys + T.key0[b];
+  S.scr = T.scr + b;
+  S.host = T.host + b;
+  S.n = T.n[b];
+  S.drop_nan = T.drop_nan;
+  return S;
+}
+
+__global__ __launch_bounds__(kBlock) void depth_scale_point_batch_kernel(const DsBatch G, const SelBatch T)
+{
+  const int b = sel_row_of(T, blockIdx.x);
+  DsParams P = G.shared;
+#pragma unroll
+  for (int i = 0; i < 9; ++i)
+    P.R[i] = G.rows[b].R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    P.t[i] = G.rows[b].t[i];
+  P.dpt0 = G.rows[b].dpt0; P.homo = G.rows[b].homo; P.loc = G.rows[b].loc;
+  P.ratios_out = G.rows[b].ratios_out; P.selected_out = G.rows[b].selected_out;
+  P.M = T.n[b];
+  ds_point_body(P, sel_row(T, b), blockIdx.x - T.blk0[b], T.blk0[b + 1] - T.blk0[b]);
+}
+
+struct MedianBatch
+{
+  const float *values[SAGE_DEPTH_SCALE_MAX_BATCH];
+  const int64_t *loc[SAGE_DEPTH_SCALE_MAX_BATCH]; // or null
+};
+__global__ __launch_bounds__(kBlock) void median_keys_batch_kernel(const MedianBatch V, const SelBatch T)
+{
+  const int b = sel_row_of(T, blockIdx.x);
+  median_keys_body(V.values[b], V.loc[b], sel_row(T, b), blockIdx.x - T.blk0[b], T.blk0[b + 1] - T.blk0[b]);
+}
+__global__ __launch_bounds__(kBlock) void select_hist_batch_kernel(const SelBatch T, int pass)
+{
+  const int b = sel_row_of(T, blockIdx.x);
+  select_hist_body(sel_row(T, b), pass, blockIdx.x - T.blk0[b], T.blk0[b + 1] - T.blk0[b]);
+}
+// grid: the rows
+__global__ __launch_bounds__(kBlock) void select_finish_batch_kernel(const SelBatch T) { select_finish_body(sel_row(T, blockIdx.x)); }
+
+// the workspace's selection buffers for `rows` rows of n_keys keys in all.  While sel_scratch_zero holds, the WHOLE scratch
+// allocation is zero (a finish kernel re-zeroes the rows its call counted in); it is zeroed here when the allocation is new
+// or a call did not reach its finish kernel
+int sel_reserve_rows(SageWorkspace *ws, size_t n_keys, int rows)
+{
+  int rc;
+  const size_t scratch_cap = ws->sel_scratch.cap; // (not the address: a larger block may come back at the old one)
+  if ((rc = ws->sel_keys.reserve(n_keys * sizeof(uint32_t))) || (rc = ws->sel_scratch.reserve((size_t)rows * sizeof(SelScratch))) ||
+      (rc = ws->sel_host.reserve((size_t)rows * sizeof(SelHost)))) // (every earlier call has been waited for)
+    return rc;
+  if (ws->sel_scratch.cap != scratch_cap)
+    ws->sel_scratch_zero = false;
+  if (!ws->sel_scratch_zero) // (a new allocation, or the call before did not reach its finish kernel)
+    SAGE_HIP(hipMemsetAsync(ws->sel_scratch.p, 0, ws->sel_scratch.cap, ws->stream));
+  ws->sel_scratch_zero = false; // (until this call's finish kernel has run)
+  return SAGE_OK;
+}
 int sel_reserve(SageWorkspace *ws, int n, int drop_nan, SelParams *S)
 {
   int rc;
-  if ((rc = ws->sel_keys.reserve((size_t)n * sizeof(uint32_t))) || (rc = ws->sel_scratch.reserve(sizeof(SelScratch))) ||
-      (rc = ws->sel_host.reserve(sizeof(SelHost)))) // (every earlier call has been waited for)
+  if ((rc = sel_reserve_rows(ws, (size_t)n, 1)))
     return rc;
-  if (!ws->sel_scratch_zero) // (a workspace's first call, or the call before did not reach its finish kernel)
-    SAGE_HIP(hipMemsetAsync(ws->sel_scratch.p, 0, sizeof(SelScratch), ws->stream));
-  ws->sel_scratch_zero = false; // (until this call's finish kernel has run)
   S->keys = ws->sel_keys.as<uint32_t>();
   S->scr = ws->sel_scratch.as<SelScratch>();
   S->host = ws->sel_host.as<SelHost>();
   S->n = n;
   S->drop_nan = drop_nan ? 1 : 0;
+  return SAGE_OK;
+}
+int sel_reserve_batch(SageWorkspace *ws, const SelBatchPlan &plan, int drop_nan, SelBatch *T)
+{
+  int rc;
+  if ((rc = sel_reserve_rows(ws, (size_t)plan.keys, plan.B)))
+    return rc;
+  T->keys = ws->sel_keys.as<uint32_t>();
+  T->scr = ws->sel_scratch.as<SelScratch>();
+  T->host = ws->sel_host.as<SelHost>();
+  T->drop_nan = drop_nan ? 1 : 0;
+  T->B = plan.B;
+  for (int b = 0; b < SAGE_DEPTH_SCALE_MAX_BATCH; ++b)
+  {
+    T->n[b] = plan.n[b];
+    T->key0[b] = plan.key0[b];
+  }
+  for (int b = 0; b <= SAGE_DEPTH_SCALE_MAX_BATCH; ++b)
+    T->blk0[b] = b < plan.B ? plan.blk0[b] : plan.workgroups;
   return SAGE_OK;
 }
 
@@ -383,6 +499,28 @@ int sel_run(SageWorkspace *ws, const SelParams &S)
   ws->sel_scratch_zero = true;
   return SAGE_OK;
 }
+int sel_run_batch(SageWorkspace *ws, const SelBatchPlan &plan, const SelBatch &T)
+{
+  hipStream_t s = ws->stream;
+  hipLaunchKernelGGL(select_hist_batch_kernel, dim3(plan.workgroups), dim3(kBlock), 0, s, T, 1);
+  hipLaunchKernelGGL(select_hist_batch_kernel, dim3(plan.workgroups), dim3(kBlock), 0, s, T, 2);
+  hipLaunchKernelGGL(select_finish_batch_kernel, dim3(plan.B), dim3(kBlock), 0, s, T);
+  SAGE_HIP(hipGetLastError());
+  int rc;
+  if ((rc = ws_ticket_wait(ws)))
+    return rc;
+  ws->sel_scratch_zero = true;
+  ws->sel_batch_launches = plan.launches;
+  return SAGE_OK;
+}
+
+void ds_shared_params(DsParams *P, const SageCamera *cam, const float *bias1_dev, const float *mask_dev, float eps)
+{
+  P->bias1 = bias1_dev; P->mask = mask_dev;
+  P->eps = eps;
+  P->fx = cam->fx; P->fy = cam->fy; P->cx = cam->cx; P->cy = cam->cy; P->w = cam->w; P->h = cam->h;
+  P->W = (int)cam->w; P->H = (int)cam->h;
+}
 } // namespace
 
 extern "C" int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const float *t10, const float *dpt0_dev,
@@ -392,8 +530,7 @@ extern "C" int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const
 {
   if (!ws || !R10 || !t10 || !dpt0_dev || !homo0_dev || !cam || !bias1_dev || !mask_dev || !out || M <= 0)
     return SAGE_E_INVALID;
-  if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !(cam->fx > 0.f) || !(cam->fy > 0.f) || !std::isfinite(cam->w) ||
-      !std::isfinite(cam->h) || !(cam->w >= 1.f) || !(cam->h >= 1.f) || cam->w > 32768.f || cam->h > 32768.f)
+  if (!depth_scale_camera_ok(cam))
     return SAGE_E_INVALID;
   int rc;
   SelParams S;
@@ -402,10 +539,9 @@ extern "C" int sage_depth_scale_ratio(SageWorkspace *ws, const float *R10, const
   DsParams P;
   std::memcpy(P.R, R10, sizeof(P.R));
   std::memcpy(P.t, t10, sizeof(P.t));
-  P.dpt0 = dpt0_dev; P.homo = homo0_dev; P.bias1 = bias1_dev; P.mask = mask_dev; P.loc = loc1d0_dev;
-  P.eps = eps;
-  P.fx = cam->fx; P.fy = cam->fy; P.cx = cam->cx; P.cy = cam->cy; P.w = cam->w; P.h = cam->h;
-  P.W = (int)cam->w; P.H = (int)cam->h; P.M = M;
+  ds_shared_params(&P, cam, bias1_dev, mask_dev, eps);
+  P.dpt0 = dpt0_dev; P.homo = homo0_dev; P.loc = loc1d0_dev;
+  P.M = M;
   P.ratios_out = ratios_out_dev; P.selected_out = selected_out_dev;
   hipLaunchKernelGGL(depth_scale_point_kernel, dim3(sel_blocks(M)), dim3(kBlock), 0, ws->stream, P, S);
   if ((rc = sel_run(ws, S)))
@@ -439,3 +575,114 @@ extern "C" int sage_median_f32(SageWorkspace *ws, const float *values_dev, const
     *n_nan_host = S.host->n_nan;
   return SAGE_OK;
 }
+
+extern "C" int sage_depth_scale_ratio_batch(SageWorkspace *ws, const SageDepthScaleRow *rows, int B, const SageCamera *cam,
+                                            const float *bias1_dev, const float *mask_dev, float eps, int drop_nan,
+                                            SageDepthScaleStats *out)
+{
+  if (!ws || !rows || !cam || !bias1_dev || !mask_dev || !out || B < 0 || B > SAGE_DEPTH_SCALE_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (!depth_scale_camera_ok(cam))
+    return SAGE_E_INVALID;
+  int32_t M[SAGE_DEPTH_SCALE_MAX_BATCH];
+  for (int b = 0; b < B; ++b)
+  {
+    if (rows[b].M <= 0 || !rows[b].dpt0_dev || !rows[b].homo0_dev)
+      return SAGE_E_INVALID;
+    M[b] = rows[b].M;
+  }
+  ws->sel_batch_launches = 0;
+  if (B == 0)
+    return SAGE_OK;
+  if (B == 1) // one row: the single call's kernels (the batch's measure 8 % slower with one row: profiles/depth_scale_batch_bench.txt)
+  {
+    const SageDepthScaleRow &r = rows[0];
+    const int rc1 = sage_depth_scale_ratio(ws, r.R10, r.t10, r.dpt0_dev, r.loc1d0_dev, r.homo0_dev, r.M, cam, bias1_dev, mask_dev, eps,
+                                           drop_nan, r.ratios_out_dev, r.selected_out_dev, out);
+    if (rc1 == SAGE_OK)
+      ws->sel_batch_launches = kSelFixedLaunches;
+    return rc1;
+  }
+  SelBatchPlan plan;
+  sel_batch_plan(M, B, &plan);
+  int rc;
+  SelBatch T;
+  if ((rc = sel_reserve_batch(ws, plan, drop_nan, &T)))
+    return rc;
+  DsBatch G;
+  std::memset(&G, 0, sizeof(G));
+  ds_shared_params(&G.shared, cam, bias1_dev, mask_dev, eps);
+  for (int b = 0; b < B; ++b)
+  {
+    DsRow &r = G.rows[b];
+    std::memcpy(r.R, rows[b].R10, sizeof(r.R));
+    std::memcpy(r.t, rows[b].t10, sizeof(r.t));
+    r.dpt0 = rows[b].dpt0_dev; r.homo = rows[b].homo0_dev; r.loc = rows[b].loc1d0_dev;
+    r.ratios_out = rows[b].ratios_out_dev; r.selected_out = rows[b].selected_out_dev;
+  }
+  hipLaunchKernelGGL(depth_scale_point_batch_kernel, dim3(plan.workgroups), dim3(kBlock), 0, ws->stream, G, T);
+  if ((rc = sel_run_batch(ws, plan, T)))
+    return rc;
+  for (int b = 0; b < B; ++b)
+  {
+    const SelHost &h = T.host[b];
+    out[b].ratio = h.value;
+    out[b].n_points = M[b];
+    out[b].n_pos_depth = h.n_pos;
+    out[b].n_selected = h.n_selected;
+    out[b].n_nan = h.n_nan;
+    out[b].n_used = h.n_used;
+  }
+  return SAGE_OK;
+}
+
+extern "C" int sage_median_f32_batch(SageWorkspace *ws, const float *const *values_dev, const int64_t *const *loc1d_dev,
+                                     const int32_t *n, int B, int drop_nan, float *median_host, int32_t *n_used_host,
+                                     int32_t *n_nan_host)
+{
+  if (!ws || B < 0 || B > SAGE_DEPTH_SCALE_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B > 0 && (!values_dev || !n || !median_host))
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+    if (!values_dev[b] || n[b] <= 0)
+      return SAGE_E_INVALID;
+  ws->sel_batch_launches = 0;
+  if (B == 0)
+    return SAGE_OK;
+  if (B == 1) // (as above)
+  {
+    const int rc1 = sage_median_f32(ws, values_dev[0], loc1d_dev ? loc1d_dev[0] : nullptr, n[0], drop_nan, median_host, n_used_host,
+                                    n_nan_host);
+    if (rc1 == SAGE_OK)
+      ws->sel_batch_launches = kSelFixedLaunches;
+    return rc1;
+  }
+  SelBatchPlan plan;
+  sel_batch_plan(n, B, &plan);
+  int rc;
+  SelBatch T;
+  if ((rc = sel_reserve_batch(ws, plan, drop_nan, &T)))
+    return rc;
+  MedianBatch V;
+  std::memset(&V, 0, sizeof(V));
+  for (int b = 0; b < B; ++b)
+  {
+    V.values[b] = values_dev[b];
+    V.loc[b] = loc1d_dev ? loc1d_dev[b] : nullptr;
+  }
+  hipLaunchKernelGGL(median_keys_batch_kernel, dim3(plan.workgroups), dim3(kBlock), 0, ws->stream, V, T);
+  if ((rc = sel_run_batch(ws, plan, T)))
+    return rc;
+  for (int b = 0; b < B; ++b)
+  {
+    median_host[b] = T.host[b].value;
+    if (n_used_host)
+      n_used_host[b] = T.host[b].n_used;
+    if (n_nan_host)
+      n_nan_host[b] = T.host[b].n_nan;
+  }
+  return SAGE_OK;
+}
+
+extern "C" int sage_depth_scale_ratio_batch_launches(const SageWorkspace *ws) { return ws ? ws->sel_batch_launches : 0; }

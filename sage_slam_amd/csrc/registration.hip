@@ -1518,3 +1518,69 @@ extern "C" int sage_loop_verify(SageWorkspace *ws, const SageLmConfig *cfg, cons
   }
   return SAGE_OK;
 }
+
+// the loop body behind the tracking stage and what follows the loop (loop_detector.cpp:173-229); the rules themselves are
+// host functions of loop_accept_host.cpp
+extern "C" int sage_loop_accept(SageWorkspace *ws, const SageLoopAcceptConfig *cfg, const SageLoopScaleQuery *query,
+                                const SageLoopCandidate *cands, const SageLoopScaleCandidate *scands,
+                                const SageLoopPrecheckResult *pre, const SageLoopVerifyResult *ver, int B, SageLoopInfo *infos,
+                                int32_t *kept_order, int32_t *n_kept)
+{
+  if (!ws || !cfg || !query || !infos || !kept_order || !n_kept || B < 0 || B > SAGE_TRACK_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B > 0 && (!cands || !scands || !pre || !ver))
+    return SAGE_E_INVALID;
+  int acc[SAGE_TRACK_MAX_BATCH], na = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    if (!loop_accept_test(*cfg, pre[b], ver[b]))
+      continue;
+    const SageLoopScaleCandidate &c = scands[b];
+    if (!cands[b].dpt_map_dev || !c.valid_loc1d_dev || !c.valid_homo_dev || c.M <= 0 || !(c.dpt_scale > 0.f) ||
+        !std::isfinite(c.dpt_scale) || !(c.tracker_ref_scale > 0.f) || !std::isfinite(c.tracker_ref_scale))
+      return SAGE_E_INVALID;
+    acc[na++] = b;
+  }
+  const SageCamera &cam = query->cam;
+  if (na > 0 && (!query->bias_dev || !query->video_mask_dev || !depth_scale_camera_ok(&cam)))
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+  {
+    std::memset(&infos[b], 0, sizeof(infos[b]));
+    kept_order[b] = -1;
+  }
+  *n_kept = 0;
+  if (na == 0)
+    return SAGE_OK;
+
+  // the accepted candidates' poses, then their depth-scale corrections: one batch, a row per accepted candidate
+  SageDepthScaleRow rows[SAGE_TRACK_MAX_BATCH];
+  SageDepthScaleStats stats[SAGE_TRACK_MAX_BATCH];
+  for (int a = 0; a < na; ++a)
+  {
+    const int b = acc[a];
+    SageLoopInfo &li = infos[b];
+    li.accepted = 1;
+    li.id_ref = scands[b].id;
+    loop_accept_pose(ver[b].pose12, scands[b].dpt_scale, scands[b].tracker_ref_scale, li.R_cur_ref, li.t_cur_ref);
+    li.ref_scale = scands[b].dpt_scale;
+    li.desc_inlier_ratio = pre[b].desc_match_inlier_ratio;
+    li.metric = ver[b].area_inlier_ratio;
+    SageDepthScaleRow &r = rows[a];
+    std::memset(&r, 0, sizeof(r));
+    std::memcpy(r.R10, li.R_cur_ref, sizeof(r.R10));
+    std::memcpy(r.t10, li.t_cur_ref, sizeof(r.t10));
+    r.dpt0_dev = cands[b].dpt_map_dev; r.loc1d0_dev = scands[b].valid_loc1d_dev; r.homo0_dev = scands[b].valid_homo_dev;
+    r.M = scands[b].M;
+  }
+  int rc;
+  if ((rc = sage_depth_scale_ratio_batch(ws, rows, na, &cam, query->bias_dev, query->video_mask_dev, cfg->dpt_eps, 1, stats)))
+    return rc;
+  for (int a = 0; a < na; ++a)
+  {
+    infos[acc[a]].query_scale = stats[a].ratio;
+    infos[acc[a]].scale = stats[a];
+  }
+  *n_kept = loop_accept_filter(infos, B, cfg->redundant_range, kept_order);
+  return SAGE_OK;
+}

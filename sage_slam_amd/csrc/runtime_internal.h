@@ -5,7 +5,9 @@
 //                       problems in lock-step (sage_track_frame_batch): one round over the batched launches
 //   overlap.hip         overlap statistics of a tracked pose (sage_track_overlap): its kernels and the host finish
 //   depth_scale.hip     the mapper's depth-scale correction and device medians (sage_depth_scale_ratio, sage_median_f32):
-//                       the per-point kernel and the exact radix selection
+//                       the per-point kernel and the exact radix selection; B rows of either in the launches of one
+//   depth_scale_host.cpp  (no HIP) the layout of such a batch
+//   loop_accept_host.cpp  (no HIP) sage_loop_accept's rules: accept test, pose hand-over, sort, redundancy filter
 //   bow.hip             the loop detector's bag of words (sage_vocabulary_*, sage_bow_transform): the vocabulary's device
 //                       layout, the tree walk, the compaction of the words reached, the host finish
 //   bow_database.cpp    (no HIP) the L1 score of two bag-of-words vectors and the inverted-file database
@@ -76,6 +78,8 @@ extern "C"
 #include "graph_batch.h"
 #include "window_plan.h" // SolverRows, TermLayout
 #include "registration_plan.h" // RegBatchPlan
+#include "depth_scale_plan.h"  // SelBatchPlan
+#include "loop_accept.h"       // sage_loop_accept's host rules
 
 using namespace sage;
 
@@ -220,6 +224,10 @@ struct SageWorkspace
   DevBuf sel_keys, sel_scratch;
   PinnedBuf sel_host;
   bool sel_scratch_zero = false; // the last call's finish kernel has run: the scratch is zero again
+  // A batch (sage_depth_scale_ratio_batch, sage_median_f32_batch) holds B rows in the same three: the keys of all rows, a
+  // scratch and a pinned record per row; sel_scratch_zero speaks of the whole scratch allocation.  sel_batch_launches:
+  // what the last batch launched
+  int sel_batch_launches = 0;
   // bag of words (sage_bow_transform, bow.hip): one flag per word of the vocabulary (rounded up to the compaction's tile),
   // and the pinned record the compact kernel publishes: [count, pad x 3 | the word ids reached, ascending]
   DevBuf bow_hit;
