@@ -1321,6 +1321,63 @@ int sage_factor_psd(int type, int CS, const float *AtA, int psd_mode, double *C_
 int sage_factor_cut_blocks(int type, int CS, const double *C, const float *Atb, double *G_out, double *g_out,
                            int32_t *dims_out, int32_t *nkeys_out);
 
+/* The projection of psd_mode 1 (sage_nearest_psd: the Higham projection) for n matrices at once on the device, one
+ * workgroup per matrix, everything in LDS and in fp64:
+ *   1. B = (M + M^T) / 2 from the fp32 row AtA_dev[i].  A non-finite entry: C_dev[i] = B as it is, status 2, done.
+ *   2. B = V diag(w) V^T by parallel cyclic two-sided Jacobi: a sweep is D - 1 rounds (D even) or D rounds (D odd), the
+ *      D / 2 disjoint pairs of a round (sage_jacobi_round_pairs) are rotated at once with the rotation of the host's
+ *      Jacobi fallback.  Before every sweep off = the off-diagonal and diag = the diagonal sum of squares are measured;
+ *      the sweeps end at off <= (2^-52)^2 diag, or after 30 sweeps with status 1.
+ *   3. H = V |w| V^T, A3 = (B + H) / 2 on one triangle, mirrored: C is symmetric bit for bit.
+ *   4. The acceptance test and bump loop of sage_nearest_psd: an unpivoted LDL^T (every pivot >= 0, a zero pivot zeroes
+ *      its column and, stricter than the host's test, fails when that column is not zero already; the device's own
+ *      summation order); while it fails, at most 60 times, max(-mn k + 1e-15, one ulp of
+ *      the largest |diagonal entry|) is added to the diagonal, k = 1, 2, 4, ..; mn = min_i (w_i + |w_i|) / 2, the
+ *      smallest eigenvalue of A3 up to rounding, plus the bumps so far.
+ * A matrix's result does not depend on the rest of the batch or on its place in it, byte for byte.  No atomics.
+ * SagePsdStats: status 0 ok, 1 sweep cap reached (C is the projection with the V and w reached), 2 non-finite input (sweeps,
+ * bump_rounds, min_eig, off_norm all 0), 3 the test still failed after the 60th bump (C as bumped; the host loop ends there
+ * too, without a word); sweeps, bump_rounds: as counted above; min_eig: the smallest w; off_norm: sqrt(off)
+ * as last measured.
+ * sage_factor_psd_batch: AtA_dev [n][D][D] float and C_dev [n][D][D] double on the device, stats_host [n] on the host or
+ * NULL.  The projection kernel and the workspace's ticket kernel, one wait, whatever n.  SAGE_E_INVALID, before anything
+ * touches the device: NULL ws, AtA_dev or C_dev; D < 1 or D > SAGE_PSD_MAX_DIM; n < 0.  n = 0: SAGE_OK, nothing launched.
+ * sage_factor_psd_batch_launches: what the workspace's last call launched.
+ * sage_factor_psd_batch_plan (host only; every output pointer may be NULL; SAGE_E_INVALID for D or n out of range), with
+ * Dc = D rounded up to a multiple of 16, the capacity the kernel is instantiated for:
+ *   lds_bytes    = 8 (2 Dc (Dc | 1) + 4 Dc + 64)    the two matrices at the widest row stride, four vectors, the sums' slots
+ *   device_bytes = 12 n D D                         the input and the output; the call itself reserves none
+ *   pinned_bytes = 32 n                             the records
+ *   launches     = 2, or 0 for n = 0
+ * Inside a workgroup the row stride is D | 1 doubles and a round's pairs take 16 lanes each: 8 Dc lanes.
+ * sage_jacobi_round_pairs (host only): the pairs of `round` as the kernel rotates them, pairs [2 (D / 2)] = p0 q0 p1 q1 ..
+ * with p < q; returns their number D / 2 (0 for D = 1), or SAGE_E_INVALID for D out of range, a round outside the sweep or
+ * NULL pairs. */
+#define SAGE_PSD_MAX_DIM 80
+typedef struct SagePsdStats
+{
+  int32_t status; /* 0 ok, 1 sweep cap reached, 2 non-finite input, 3 bump cap reached */
+  int32_t sweeps, bump_rounds;
+  double min_eig;  /* of B */
+  double off_norm; /* off-diagonal norm at exit */
+} SagePsdStats;
+int sage_factor_psd_batch(SageWorkspace *ws, int D, int n, const float *AtA_dev, double *C_dev, SagePsdStats *stats_host);
+int sage_factor_psd_batch_launches(const SageWorkspace *ws);
+int sage_factor_psd_batch_plan(int D, int n, int64_t *lds_bytes, int64_t *device_bytes, int64_t *pinned_bytes,
+                               int32_t *launches);
+int sage_jacobi_round_pairs(int D, int round, int32_t *pairs);
+/* sage_window_prepare_factors with psd_mode 1, on the device: every cached factor of the last recomputing prepass goes
+ * through the kernel of sage_factor_psd_batch -- one launch per factor type present, then one wait -- and the projected
+ * matrices land in the cache sage_window_factor with psd_mode 1 reads.  The kernel's input is the window's device AtA
+ * while that still is the linearisation the cache was pulled from; after another linearize the cached copy is uploaded
+ * first.  A factor whose status is not 0 is projected again on the host by sage_factor_psd, so bad inputs come out as
+ * sage_window_prepare_factors leaves them.  worst (optional): the record with the highest status, then the most sweeps,
+ * then the most bump rounds.  SAGE_E_STATE without a cached linearisation; SAGE_OK at once, nothing launched, when mode 1
+ * is prepared already (by either call).  The next recomputing prepass invalidates it, a sage_window_prepare_factors with
+ * another mode replaces it.  sage_window_prepare_factors_device_launches: kernels the last call launched. */
+int sage_window_prepare_factors_device(SageWindow *w, SagePsdStats *worst);
+int sage_window_prepare_factors_device_launches(const SageWindow *w);
+
 /* kernel timing with HIP events on the engine's own stream (bench.py's roofline): when enabled every launch of
  * the hot kernels is bracketed by an event pair.  which: 0 photometric linearize, 1 geometric linearize,
  * 2 photometric error, 3 geometric error, 4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term

@@ -36,8 +36,11 @@ public:
   };
 
   // keys[k]: the gtsam keys of window keyframe k (the order of sage_window_add_keyframe)
-  SageWindowCache(SageWindow *win, std::vector<Keys> keys, int code_size, int psd_mode /* 2 = NearestPsd as written */)
-      : win_(win), keys_(std::move(keys)), CS_(code_size), psd_mode_(psd_mode),
+  // device_psd (opt-in, psd_mode 1 only): the eager projection runs on the device (sage_window_prepare_factors_device)
+  // instead of on host threads; any other psd_mode ignores the switch
+  SageWindowCache(SageWindow *win, std::vector<Keys> keys, int code_size, int psd_mode /* 2 = NearestPsd as written */,
+                  bool device_psd = false)
+      : win_(win), keys_(std::move(keys)), CS_(code_size), psd_mode_(psd_mode), device_psd_(device_psd && psd_mode == 1),
         pose_(keys_.size() * 12), code_(keys_.size() * code_size), scale_(keys_.size())
   {
     for (size_t k = 0; k < keys_.size(); ++k) // start from the variables the keyframes were added with
@@ -79,9 +82,11 @@ public:
     {
       // a failed projection is not fatal here: the cache is marked unprepared by the engine and Linearize() projects the
       // factors it is asked for one by one (and reports their errors)
-      const int rcp = sage_window_prepare_factors(win_, psd_mode_, eager_psd_threads_);
+      const int rcp = device_psd_ ? sage_window_prepare_factors_device(win_, nullptr)
+                                  : sage_window_prepare_factors(win_, psd_mode_, eager_psd_threads_);
       if (rcp != SAGE_OK)
-        fprintf(stderr, "sage_window_prepare_factors: %s (falling back to per-factor projection)\n", sage_error_string(rcp));
+        fprintf(stderr, "%s: %s (falling back to per-factor projection)\n",
+                device_psd_ ? "sage_window_prepare_factors_device" : "sage_window_prepare_factors", sage_error_string(rcp));
     }
     return recomputed != 0;
   }
@@ -139,6 +144,7 @@ private:
   SageWindow *win_;
   std::vector<Keys> keys_;
   int CS_, psd_mode_;
+  bool device_psd_;
   std::vector<float> pose_, code_, scale_;
   std::mutex mutex_;
 

@@ -146,7 +146,7 @@ SYMBOLS = [
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
     "sage_window_error", "sage_window_tune_runs", "sage_window_set_runs", "sage_window_error_dev", "sage_window_solve", "sage_window_total_error",
     "sage_window_accept", "sage_window_reset", "sage_window_get_keyframe", "sage_window_set_keyframe", "sage_window_get_delta",
-    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_add_graph_term", "sage_window_num_graph_terms", "sage_window_get_graph_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_factor_psd", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
+    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_add_graph_term", "sage_window_num_graph_terms", "sage_window_get_graph_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_window_prepare_factors_device", "sage_window_prepare_factors_device_launches", "sage_factor_psd", "sage_factor_psd_batch", "sage_factor_psd_batch_launches", "sage_factor_psd_batch_plan", "sage_jacobi_round_pairs", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
     "sage_valid_locations", "sage_shuffle_indices", "sage_sample_locations",
     "sage_reprojection_jac_error_calculate", "sage_reprojection_error_calculate",
     "sage_tracker_reproj_jac_error_calculate", "sage_tracker_reproj_error_calculate",
@@ -269,6 +269,74 @@ def factor_hessian_blocks(type_: int, CS: int, AtA, Atb, psd_mode: int = 1):
             blocks[(i, j)] = G[o:o + dims[i] * dims[j]].reshape(dims[i], dims[j]); o += dims[i] * dims[j]
     offs = np.concatenate([[0], np.cumsum(dims)])
     return blocks, [g[offs[i]:offs[i + 1]] for i in range(nk.value)], dims
+
+
+PSD_MAX_DIM = 80
+
+
+class SagePsdStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("sweeps", C.c_int32), ("bump_rounds", C.c_int32), ("min_eig", C.c_double),
+                ("off_norm", C.c_double)]
+
+
+def factor_psd_batch_raw(ws_handle, D, n, AtA_ptr, C_ptr, stats_ptr) -> int:
+    """``sage_factor_psd_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_factor_psd_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws_handle, int(D), int(n), AtA_ptr, C_ptr, stats_ptr))
+
+
+def factor_psd_batch(ws: "Workspace", AtA):
+    """The Higham projection (``nearest_psd``, psd_mode 1) of every matrix of ``AtA`` -- a contiguous float32 cuda tensor
+    [n, D, D] -- on the device through ``sage_factor_psd_batch``: one projection launch and one wait -> (C: float64 cuda
+    tensor [n, D, D], a list of n ``SagePsdStats``)."""
+    import torch
+    assert AtA.dtype == torch.float32 and AtA.dim() == 3 and AtA.shape[1] == AtA.shape[2]
+    n, D = int(AtA.shape[0]), int(AtA.shape[1])
+    out = torch.empty((n, D, D), dtype=torch.float64, device=AtA.device)
+    stats = (SagePsdStats * max(n, 1))()
+    # (an empty tensor has no storage: the call checks its pointers before it looks at n)
+    ap = dptr(AtA) if n else C.c_void_p(8)
+    cp = dptr(out) if n else C.c_void_p(8)
+    _chk(factor_psd_batch_raw(ws.h, D, n, ap, cp, C.addressof(stats)), "sage_factor_psd_batch")
+    return out, [stats[i] for i in range(n)]
+
+
+def factor_psd_batch_launches(ws: "Workspace") -> int:
+    """kernel launches of the workspace's last ``sage_factor_psd_batch``"""
+    f = lib().sage_factor_psd_batch_launches
+    f.argtypes = [C.c_void_p]
+    return int(f(ws.h if ws is not None else None))
+
+
+def factor_psd_batch_plan_raw(D, n, lds_ptr, device_ptr, pinned_ptr, launches_ptr) -> int:
+    f = lib().sage_factor_psd_batch_plan
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(int(D), int(n), lds_ptr, device_ptr, pinned_ptr, launches_ptr))
+
+
+def factor_psd_batch_plan(D: int, n: int) -> dict:
+    """What a batch of n matrices of D columns takes, through ``sage_factor_psd_batch_plan`` (host only)."""
+    lds = C.c_int64(); dev = C.c_int64(); pin = C.c_int64(); launches = C.c_int32()
+    _chk(factor_psd_batch_plan_raw(D, n, C.addressof(lds), C.addressof(dev), C.addressof(pin), C.addressof(launches)),
+         "sage_factor_psd_batch_plan")
+    return dict(lds_bytes=lds.value, device_bytes=dev.value, pinned_bytes=pin.value, launches=launches.value)
+
+
+def jacobi_round_pairs_raw(D, round_, pairs_ptr) -> int:
+    f = lib().sage_jacobi_round_pairs
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    return int(f(int(D), int(round_), pairs_ptr))
+
+
+def jacobi_round_pairs(D: int, round_: int) -> list:
+    """The disjoint index pairs round ``round_`` of a Jacobi sweep rotates at once (``sage_jacobi_round_pairs``, host only)
+    -> a list of D // 2 tuples (p, q), p < q."""
+    pairs = (C.c_int32 * max(2 * (int(D) // 2), 2))()
+    n = jacobi_round_pairs_raw(D, round_, C.addressof(pairs))
+    if n < 0:
+        raise SageError(n, "sage_jacobi_round_pairs")
+    return [(int(pairs[2 * i]), int(pairs[2 * i + 1])) for i in range(n)]
 
 
 def damped_solve_qr_f32(A, b, damp):
@@ -1471,6 +1539,19 @@ class Window:
     def prepare_factors(self, psd_mode: int = 1, n_threads: int = 0):
         """f2: NearestPsd of every cached factor on host threads; factor(.., psd_mode) then only cuts blocks."""
         _chk(lib().sage_window_prepare_factors(self.h, psd_mode, n_threads), "sage_window_prepare_factors")
+
+    def prepare_factors_device(self) -> "SagePsdStats":
+        """f2: NearestPsd (psd_mode 1) of every cached factor on the device -- one launch per factor type, one wait;
+        factor(.., 1) then only cuts blocks -> the worst ``SagePsdStats`` record."""
+        worst = SagePsdStats()
+        _chk(lib().sage_window_prepare_factors_device(self.h, C.byref(worst)), "sage_window_prepare_factors_device")
+        return worst
+
+    def prepare_factors_device_launches(self) -> int:
+        """kernels the last ``prepare_factors_device`` launched (0: mode 1 was prepared already)"""
+        f = lib().sage_window_prepare_factors_device_launches
+        f.argtypes = [C.c_void_p]
+        return int(f(self.h))
 
     def factor_error(self, type_, e) -> float:
         v = C.c_double()

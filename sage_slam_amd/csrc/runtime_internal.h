@@ -250,6 +250,9 @@ struct SageWorkspace
   int mb_cus = 0, mb_slices = 0;
   // loop pre-check (sage_loop_precheck: registration.hip): the way back [B][K], then the B candidates' gathered points
   DevBuf pre_scratch;
+  // batched projection (sage_factor_psd_batch: psd_project.hip): the matrices' pinned records [n]; what the last call launched
+  PinnedBuf psd_host;
+  int psd_launches = 0;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }
@@ -275,6 +278,10 @@ int track_reproj_enqueue(SageWorkspace *ws, bool jac, float *AtA, float *Atb, fl
 int track_match_geom_enqueue(SageWorkspace *ws, int mode, bool jac, float *AtA, float *Atb, float *stats, const float *R,
                              const float *t, const float *sampled_dpts0, const float *matched_dpts1, const float *homo0,
                              const float *matched_homo1, float scale0, float loss_param, float weight, int N);
+
+// psd_project.hip: the batched Higham projection of n > 0 matrices of D columns, one launch on `s`, nobody waits; stats [n]
+// is device-visible memory (device or pinned)
+int psd_project_enqueue(hipStream_t s, int D, int n, const float *AtA_dev, double *C_dev, SagePsdStats *stats);
 
 // registration_host.cpp: SAGE_OK, SAGE_E_INVALID or SAGE_E_UNSUPPORTED for a parameter set
 int registration_check_params(const SageRegistrationParams *p);
@@ -403,7 +410,14 @@ struct SageWindow
       std::vector<double> C;
     } side[2];                    // [kPhoto], [kGeo]
     int psd_mode = -1;            // < 0: the projected matrices are not prepared for the cached linearisation
+    uint64_t dense_serial = 0;    // SageWindow::dense_serial when A was pulled: equal -> the device AtA still is this linearisation
   } fc;
+  // sage_window_prepare_factors_device (psd_project.hip's kernel): per factor type the uploaded AtA (only when the device's
+  // own has moved on), the projected matrices and the records; what the last call launched and its worst record
+  uint64_t dense_serial = 0;      // counts the linearizes that have written dense[].AtA
+  DevBuf psd_in[2], psd_out[2], psd_stats[2];
+  int psd_launches = 0;
+  SagePsdStats psd_worst{};
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an

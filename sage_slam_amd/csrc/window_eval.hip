@@ -383,6 +383,7 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->dpt_set = set;
     w->dgrad_valid = true;
     // main kernels only (stage 1), then ONE finalize launch for both factor types (window_finalize_kernel)
+    ++w->dense_serial; // the per-edge AtA are about to be rewritten (sage_window_prepare_factors_device)
     lcg = window_lc(w, kGeo);
     lcp = window_lc(w, kPhoto, true);
     lcg.stage = 1;

@@ -101,6 +101,8 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
     }
     SAGE_HIP(pull(fc.side[type].s, w->dense[type].stats, ne * 2));
   }
+  if (jacobians)
+    fc.dense_serial = w->dense_serial;
   fc.lin = jacobians != 0;
   fc.err = true;
   if (recomputed)
@@ -200,3 +202,84 @@ extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_th
   return SAGE_OK;
 }
 
+// The same preparation on the device, psd_mode 1 only: one launch of the batched Higham projection (psd_project.hip) per
+// factor type present, the projected matrices and their records copied back behind them, one wait.  The kernel reads the
+// window's own per-edge AtA while that still is the linearisation the cache was pulled from (dense_serial); after another
+// linearize the cached copy is uploaded instead.  A factor whose record is not clean (sweep cap, non-finite input) is
+// projected again on the host, so such inputs come out as sage_window_prepare_factors leaves them.
+extern "C" int sage_window_prepare_factors_device(SageWindow *w, SagePsdStats *worst)
+{
+  if (!w || !w->finalized)
+    return SAGE_E_INVALID;
+  SageWindow::FactorCache &fc = w->fc;
+  if (!fc.lin)
+    return SAGE_E_STATE;
+  w->psd_launches = 0;
+  if (fc.psd_mode == 1)
+  {
+    if (worst)
+      *worst = w->psd_worst;
+    return SAGE_OK;
+  }
+  const int CS = w->cfg.CS;
+  fc.psd_mode = -1; // (as above)
+  const bool fresh = fc.dense_serial == w->dense_serial;
+  size_t D[2], ne[2];
+  std::vector<SagePsdStats> rec[2];
+  int rc;
+  for (int type = kPhoto; type <= kGeo; ++type)
+  {
+    D[type] = dense_dim(type, CS);
+    ne[type] = fc.side[type].A.size() / (D[type] * D[type]);
+    fc.side[type].C.resize(ne[type] * D[type] * D[type]);
+    rec[type].resize(ne[type]);
+    if (!ne[type])
+      continue;
+    const size_t elems = ne[type] * D[type] * D[type];
+    const float *in = w->dense[type].AtA.as<float>();
+    if (!fresh)
+    {
+      if ((rc = w->psd_in[type].reserve(elems * sizeof(float))))
+        return rc;
+      SAGE_HIP(hipMemcpyAsync(w->psd_in[type].p, fc.side[type].A.data(), elems * sizeof(float), hipMemcpyHostToDevice, w->stream));
+      in = w->psd_in[type].as<float>();
+    }
+    if ((rc = w->psd_out[type].reserve(elems * sizeof(double))) || (rc = w->psd_stats[type].reserve(ne[type] * sizeof(SagePsdStats))))
+      return rc;
+    if ((rc = psd_project_enqueue(w->stream, (int)D[type], (int)ne[type], in, w->psd_out[type].as<double>(),
+                                  w->psd_stats[type].as<SagePsdStats>())))
+      return rc;
+    ++w->psd_launches;
+  }
+  for (int type = kPhoto; type <= kGeo; ++type)
+    if (ne[type])
+    {
+      SAGE_HIP(hipMemcpyAsync(fc.side[type].C.data(), w->psd_out[type].p, fc.side[type].C.size() * sizeof(double),
+                              hipMemcpyDeviceToHost, w->stream));
+      SAGE_HIP(hipMemcpyAsync(rec[type].data(), w->psd_stats[type].p, ne[type] * sizeof(SagePsdStats), hipMemcpyDeviceToHost,
+                              w->stream));
+    }
+  SAGE_HIP(hipStreamSynchronize(w->stream));
+  SagePsdStats worst_rec{};
+  bool any = false;
+  for (int type = kPhoto; type <= kGeo; ++type)
+    for (size_t i = 0; i < ne[type]; ++i)
+    {
+      const SagePsdStats &r = rec[type][i];
+      // the worst record: the highest status, then the most sweeps, then the most bump rounds
+      if (!any || r.status > worst_rec.status || (r.status == worst_rec.status && (r.sweeps > worst_rec.sweeps ||
+          (r.sweeps == worst_rec.sweeps && r.bump_rounds > worst_rec.bump_rounds))))
+        worst_rec = r;
+      any = true;
+      if (r.status != 0 && (rc = sage_factor_psd(type, CS, fc.side[type].A.data() + i * D[type] * D[type], 1,
+                                                 fc.side[type].C.data() + i * D[type] * D[type])))
+        return rc;
+    }
+  w->psd_worst = worst_rec;
+  if (worst)
+    *worst = worst_rec;
+  fc.psd_mode = 1;
+  return SAGE_OK;
+}
+
+extern "C" int sage_window_prepare_factors_device_launches(const SageWindow *w) { return w ? w->psd_launches : 0; }
