@@ -1219,8 +1219,8 @@ int sage_window_get_edge(const SageWindow *w, int type, int e, float *AtA, float
  * n_in = inliers for reprojection, N for match geometry and loop-MG); SAGE_E_STATE before the first linearize.
  * Totals: the terms' errors ride in the two error slots of the 4-double tails (packed buffer, error buffer) -- reprojection in
  * the photometric slot, match geometry and loop-MG in the geometric one: slot 0 + slot 1 = sum of dense + sum of keypoint
- * errors.  The inlier slots stay dense-only.  Not covered: the gtsam factor cache (sage_window_prepass / sage_window_factor
- * serve the dense factors only). */
+ * errors.  The inlier slots stay dense-only.  The gtsam factor cache serves the terms as well: sage_window_prepass caches
+ * them and sage_window_keypoint_factor hands out their HessianFactor blocks (below, next to sage_window_factor). */
 enum { SAGE_KP_REPROJECTION = 0, SAGE_KP_MATCH_GEOMETRY = 1, SAGE_KP_LOOP_MG = 2 };
 typedef struct SageKeypointTerm
 {
@@ -1321,6 +1321,47 @@ int sage_factor_psd(int type, int CS, const float *AtA, int psd_mode, double *C_
 int sage_factor_cut_blocks(int type, int CS, const double *C, const float *Atb, double *G_out, double *g_out,
                            int32_t *dims_out, int32_t *nkeys_out);
 
+/* The same for a window's terms: the reference's MatchGeometryFactor / ReprojectionFactor (mapper.cpp:346-374) and the
+ * loop-closure graphs' LoopMGFactor, RelPoseScaleFactor, RelPoseFactor and ScaleFactor project their own AtA in linearize()
+ * and cut it into G11..Gnn.  family: SAGE_TERM_KEYPOINT (kind SAGE_KP_*) or SAGE_TERM_GRAPH (kind SAGE_GRAPH_*).  The kind
+ * fixes the keys in push order, their dims, and the columns it owns of the layout sage_window_get_keypoint_term /
+ * sage_window_get_graph_term return:
+ *   keypoint REPROJECTION     p0 p1 c0 s0         6 6 CS 1        all 13+CS   (= type 0)
+ *   keypoint MATCH_GEOMETRY   p0 p1 c0 c1 s0 s1   6 6 CS CS 1 1   all 14+2CS  (= type 1)
+ *   keypoint LOOP_MG          p0 p1 s0 s1         6 6 1 1         all 14
+ *   graph    REL_POSE_SCALE   p0 p1 s0 s1         6 6 1 1         all 14
+ *   graph    REL_POSE         p0 p1               6 6             0..11 of 14
+ *   graph    SCALE_PRIOR      s                   1               12 of 14
+ * sage_term_factor_block_count: the doubles of G_out (SAGE_E_INVALID for a bad family / kind, CS < 1).
+ * sage_term_factor_blocks (host only): AtA [D,D], Atb [D] in the group's layout; the kind's own D_own x D_own sub-matrix is
+ * widened to double and projected per psd_mode as sage_factor_psd projects (a RelPoseFactor's 12 x 12, not a padded
+ * 14 x 14), its upper blocks are cut in push order into G_out, g_out [D_own] = the kind's columns of Atb widened.
+ * dims_out [<= 6], nkeys_out: optional.  SAGE_E_INVALID for a bad family / kind / mode, CS < 1 or a NULL array.
+ *   sage_window_keypoint_factor(win, term, psd_mode, G, g, f, dims, nkeys), sage_window_graph_factor(..)
+ *       the HessianFactor of term `term` (the id its add call returned) from the cache of the last linearising
+ *       sage_window_prepass, which on a window with terms also copies every term group's results to the host: blocks and g
+ *       as sage_term_factor_blocks cuts them from the cached system, bit for bit; *f = the term's error.  Every output
+ *       pointer but G_out and g_out may be NULL.  SAGE_E_STATE when the cache holds no linearisation, SAGE_E_INVALID for a
+ *       bad id or mode, a NULL G_out / g_out, or a term of another rank (as sage_window_get_keypoint_term answers).
+ *   sage_window_keypoint_factor_error(win, term, &err), sage_window_graph_factor_error(..)
+ *       the term's error from the cache (of a linearising prepass or of an error-only one); SAGE_E_STATE without either.
+ * Both eager projections cover the terms: sage_window_prepare_factors queues every term's own D_own x D_own matrix with the
+ * dense factors (longest jobs first), sage_window_prepare_factors_device adds one launch per term group that has entries, at
+ * the group's D.  There the D = 14 group is projected as it lies -- a REL_POSE or SCALE_PRIOR term inside its zero-padded
+ * 14 x 14, whose zero rows the sweeps skip and the acceptance test passes -- so such a term's blocks are a projection of
+ * the same matrix with another rotation order, within the parity bar of the batched projection at the kind's own D.  After
+ * either, a term's factor of the prepared mode is cut from the prepared matrix. */
+enum { SAGE_TERM_KEYPOINT = 0, SAGE_TERM_GRAPH = 1 };
+int sage_term_factor_block_count(int family, int kind, int CS);
+int sage_term_factor_blocks(int family, int kind, int CS, const float *AtA, const float *Atb, int psd_mode, double *G_out,
+                            double *g_out, int32_t *dims_out, int32_t *nkeys_out);
+int sage_window_keypoint_factor(const SageWindow *w, int term, int psd_mode, double *G_out, double *g_out, double *f_out,
+                                int32_t *dims_out, int32_t *nkeys_out);
+int sage_window_keypoint_factor_error(const SageWindow *w, int term, double *err_out);
+int sage_window_graph_factor(const SageWindow *w, int term, int psd_mode, double *G_out, double *g_out, double *f_out,
+                             int32_t *dims_out, int32_t *nkeys_out);
+int sage_window_graph_factor_error(const SageWindow *w, int term, double *err_out);
+
 /* The projection of psd_mode 1 (sage_nearest_psd: the Higham projection) for n matrices at once on the device, one
  * workgroup per matrix, everything in LDS and in fp64:
  *   1. B = (M + M^T) / 2 from the fp32 row AtA_dev[i].  A non-finite entry: C_dev[i] = B as it is, status 2, done.
@@ -1374,7 +1415,10 @@ int sage_jacobi_round_pairs(int D, int round, int32_t *pairs);
  * sage_window_prepare_factors leaves them.  worst (optional): the record with the highest status, then the most sweeps,
  * then the most bump rounds.  SAGE_E_STATE without a cached linearisation; SAGE_OK at once, nothing launched, when mode 1
  * is prepared already (by either call).  The next recomputing prepass invalidates it, a sage_window_prepare_factors with
- * another mode replaces it.  sage_window_prepare_factors_device_launches: kernels the last call launched. */
+ * another mode replaces it.  sage_window_prepare_factors_device_launches: kernels the last call launched -- the dense
+ * factor types present plus the term groups that have entries (2 on a dense window without terms, 5 with all three groups).
+ * `worst` ranges over dense factors and terms; a term whose record is not clean is projected on the host as
+ * sage_term_factor_blocks projects it. */
 int sage_window_prepare_factors_device(SageWindow *w, SagePsdStats *worst);
 int sage_window_prepare_factors_device_launches(const SageWindow *w);
 

@@ -14,6 +14,16 @@
 // recomputed count; then for type in {0,1}, edge in [0, 2*nlinks): int32 nkeys, uint64 keys[nkeys], int32 dims[nkeys],
 // double info[(D+1)^2] row-major (the augmented information matrix the HessianFactor assembled), double error from
 // SageWindowCache::Error at the same Values.
+//
+//   prepass_run <window.bin> <out.bin> <psd_mode> <terms.bin>
+//
+// also adds the terms of terms.bin to the window before it is finalized and appends their factors to out.bin.  terms.bin: int32
+// n_keypoint; per keypoint term int32 kind, edge, N, loss; float loss_param, weight; then its arrays -- reprojection: int32
+// loc0[N], float homo0[3N], matched_2d[2N]; match geometry: int32 loc0[N], float homo0[3N], int32 loc1[N], float homo1[3N];
+// loop-MG: float homo0[3N], homo1[3N], unscaled_dpts0[N], unscaled_dpts1[N]; int32 n_graph; per graph term int32 kind, edge,
+// kf; float target_pose10[12], target_scale0, target_scale1, weight, rot_weight, scale_weight.  Appended to out.bin, for the
+// keypoint terms and then the graph terms in their add order: the same record as a dense factor's, from
+// SageWindowCache::LinearizeTerm / ErrorTerm with the keys the reference's factor of that kind pushes.
 #include "../sage_gtsam_prepass.h"
 
 #include <hip/hip_runtime_api.h>
@@ -59,9 +69,9 @@ template <class T> static void wr(FILE *f, const T *p, size_t n) { fwrite(p, siz
 
 int main(int argc, char **argv)
 {
-  if (argc != 4)
+  if (argc != 4 && argc != 5)
   {
-    fprintf(stderr, "usage: prepass_run window.bin out.bin psd_mode\n");
+    fprintf(stderr, "usage: prepass_run window.bin out.bin psd_mode [terms.bin]\n");
     return 2;
   }
   FILE *f = fopen(argv[1], "rb");
@@ -108,6 +118,67 @@ int main(int argc, char **argv)
   for (int l = 0; l < nlinks; ++l)
     if (sage_window_add_link(win, links[2 * l], links[2 * l + 1]) != l)
       return 7;
+  // (optional) the window's terms: added before finalize, their kinds and places kept for the key lists below
+  struct TermInfo
+  {
+    int family, kind, edge, kf;
+  };
+  std::vector<TermInfo> terms;
+  if (argc == 5)
+  {
+    FILE *tf = fopen(argv[4], "rb");
+    if (!tf)
+      return 2;
+    const int nkp = rd<int32_t>(tf, 1)[0];
+    for (int i = 0; i < nkp; ++i)
+    {
+      auto ih = rd<int32_t>(tf, 4);
+      auto fh = rd<float>(tf, 2);
+      const size_t N = (size_t)ih[2];
+      SageKeypointTerm t{};
+      t.kind = ih[0]; t.edge = ih[1]; t.N = ih[2]; t.loss = ih[3];
+      t.loss_param = fh[0]; t.weight = fh[1];
+      if (t.kind == SAGE_KP_REPROJECTION)
+      {
+        t.loc1d_0 = up(rd<int32_t>(tf, N));
+        t.homo0 = up(rd<float>(tf, 3 * N));
+        t.matched_2d = up(rd<float>(tf, 2 * N));
+      }
+      else if (t.kind == SAGE_KP_MATCH_GEOMETRY)
+      {
+        t.loc1d_0 = up(rd<int32_t>(tf, N));
+        t.homo0 = up(rd<float>(tf, 3 * N));
+        t.matched_loc1d_1 = up(rd<int32_t>(tf, N));
+        t.matched_homo1 = up(rd<float>(tf, 3 * N));
+      }
+      else
+      {
+        t.homo0 = up(rd<float>(tf, 3 * N));
+        t.matched_homo1 = up(rd<float>(tf, 3 * N));
+        t.unscaled_dpts0 = up(rd<float>(tf, N));
+        t.matched_unscaled_dpts1 = up(rd<float>(tf, N));
+      }
+      if (sage_window_add_keypoint_term(win, &t) != i)
+        return 8;
+      terms.push_back({SAGE_TERM_KEYPOINT, t.kind, t.edge, -1});
+    }
+    const int ngt = rd<int32_t>(tf, 1)[0];
+    for (int i = 0; i < ngt; ++i)
+    {
+      auto ih = rd<int32_t>(tf, 3);
+      auto fh = rd<float>(tf, 17);
+      SageGraphTerm t{};
+      t.kind = ih[0]; t.edge = ih[1]; t.kf = ih[2];
+      for (int j = 0; j < 12; ++j)
+        t.target_pose10[j] = fh[j];
+      t.target_scale0 = fh[12]; t.target_scale1 = fh[13];
+      t.weight = fh[14]; t.rot_weight = fh[15]; t.scale_weight = fh[16];
+      if (sage_window_add_graph_term(win, &t) != i)
+        return 9;
+      terms.push_back({SAGE_TERM_GRAPH, t.kind, t.edge, t.kf});
+    }
+    fclose(tf);
+  }
   CHECK(sage_window_finalize(win));
 
   // the gtsam side: keys as the mapper would number them, Values holding Sophus::SE3f / gtsam::Vector / float
@@ -168,6 +239,37 @@ int main(int argc, char **argv)
       const double err = cache.Error(values, type, e);
       wr(o, &err, 1);
     }
+  int n_of_family[2] = {0, 0};
+  for (const TermInfo &ti : terms)
+  {
+    const int id = n_of_family[ti.family]++;
+    gtsam::FastVector<gtsam::Key> fk;
+    if (ti.family == SAGE_TERM_GRAPH && ti.kind == SAGE_GRAPH_SCALE_PRIOR)
+      fk = {sk(ti.kf)}; // ScaleFactor (scale_factor.cpp)
+    else
+    {
+      const int a = links[2 * (ti.edge / 2)], b = links[2 * (ti.edge / 2) + 1];
+      const int k0 = (ti.edge & 1) ? b : a, k1 = (ti.edge & 1) ? a : b;
+      if (ti.family == SAGE_TERM_KEYPOINT && ti.kind == SAGE_KP_REPROJECTION)
+        fk = {pk(k0), pk(k1), ck(k0), sk(k0)}; // ReprojectionFactor
+      else if (ti.family == SAGE_TERM_KEYPOINT && ti.kind == SAGE_KP_MATCH_GEOMETRY)
+        fk = {pk(k0), pk(k1), ck(k0), ck(k1), sk(k0), sk(k1)}; // MatchGeometryFactor
+      else if (ti.family == SAGE_TERM_GRAPH && ti.kind == SAGE_GRAPH_REL_POSE)
+        fk = {pk(k0), pk(k1)}; // RelPoseFactor
+      else
+        fk = {pk(k0), pk(k1), sk(k0), sk(k1)}; // LoopMGFactor, RelPoseScaleFactor
+    }
+    boost::shared_ptr<gtsam::HessianFactor> hf = cache.LinearizeTerm(values, ti.family, ti.kind, id, fk);
+    const int32_t nk = (int32_t)hf->keys().size();
+    wr(o, &nk, 1);
+    wr(o, hf->keys().data(), nk);
+    std::vector<int32_t> dims(hf->dims().begin(), hf->dims().end());
+    wr(o, dims.data(), nk);
+    const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor> info = hf->augmentedInformation();
+    wr(o, info.data(), (size_t)info.size());
+    const double err = cache.ErrorTerm(values, ti.family, id);
+    wr(o, &err, 1);
+  }
   fclose(o);
   sage_window_destroy(win);
   return 0;

@@ -7,8 +7,9 @@
 // (integration/compile_check, tests/test_adapter_compiles.py).  Everything below the
 // gtsam types -- value comparison, batched linearize / error pass, device-to-host copy of the per-edge results,
 // NearestPsd (as written or Higham), the cut into the reference's G11..Gnn / g1..gn order -- is engine code behind the
-// C ABI (sage_window_prepass / sage_window_factor / sage_window_factor_error, include/sage_ba.h) and is tested on the GPU
-// against the oracle (tests/test_gpu_factor_cache.py); this header is the ~80 lines of type conversion that remain.
+// C ABI (sage_window_prepass / sage_window_factor / sage_window_factor_error and, for the window's keypoint and graph terms,
+// sage_window_keypoint_factor / sage_window_graph_factor: include/sage_ba.h) and is tested on the GPU against the oracle
+// (tests/test_gpu_factor_cache.py, tests/test_gpu_term_factor_cache.py); this header is the type conversion that remains.
 //
 // Use: Mapper owns one SageWindowCache per active window (keyframes + links registered as in INTEGRATION.md s3) and
 // hands it to the factors it creates; the two factor classes replace the bodies of linearize() / error() as shown.
@@ -107,6 +108,78 @@ public:
       fprintf(stderr, "sage_window_factor: %s\n", sage_error_string(rc));
       exit(rc);
     }
+    return Assemble(factor_keys, G, g, dims, nkeys, f);
+  }
+
+  // PhotometricFactor::error / GeometricFactor::error (photometric_factor.cpp:72-101, geometric_factor.cpp:41-64)
+  double Error(const gtsam::Values &c, int type, int edge)
+  {
+    std::lock_guard<std::mutex> lock(mutex_);
+    Prepare(c, false);
+    double e = 0.0;
+    const int rc = sage_window_factor_error(win_, type, edge, &e);
+    if (rc != SAGE_OK)
+    {
+      fprintf(stderr, "sage_window_factor_error: %s\n", sage_error_string(rc));
+      exit(rc);
+    }
+    return e;
+  }
+
+  // The window's terms (sage_window_add_keypoint_term / sage_window_add_graph_term; `term` is the id the add call returned)
+  // behind the same cache and the same Prepare: family SAGE_TERM_KEYPOINT with kind SAGE_KP_* serves
+  // ReprojectionFactor::linearize (keys {p0,p1,c0,s0}), MatchGeometryFactor (keys {p0,p1,c0,c1,s0,s1}) and LoopMGFactor
+  // (keys {p0,p1,s0,s1}); family SAGE_TERM_GRAPH with kind SAGE_GRAPH_* serves RelPoseScaleFactor (keys {p0,p1,s0,s1}),
+  // RelPoseFactor (keys {p0,p1}) and ScaleFactor (key {s}).  Each is projected on its own matrix, as the reference's
+  // linearize() projects its own AtA (match_geometry_factor.cpp:295, reprojection_factor.cpp:245, loop_mg_factor.cpp:90,
+  // rel_pose_scale_factor.cpp:132, rel_pose_factor.cpp:110, scale_factor.cpp:68)
+  boost::shared_ptr<gtsam::HessianFactor> LinearizeTerm(const gtsam::Values &c, int family, int kind, int term,
+                                                        const gtsam::FastVector<gtsam::Key> &factor_keys)
+  {
+    std::lock_guard<std::mutex> lock(mutex_);
+    Prepare(c, true);
+    const int count = sage_term_factor_block_count(family, kind, CS_);
+    if (count < 0)
+    {
+      fprintf(stderr, "sage_term_factor_block_count: %s\n", sage_error_string(count));
+      exit(count);
+    }
+    std::vector<double> G(count), g(14 + 2 * CS_); // (the widest term)
+    int32_t dims[6], nkeys = 0;
+    double f = 0.0;
+    const int rc = family == SAGE_TERM_GRAPH ? sage_window_graph_factor(win_, term, psd_mode_, G.data(), g.data(), &f, dims, &nkeys)
+                                             : sage_window_keypoint_factor(win_, term, psd_mode_, G.data(), g.data(), &f, dims, &nkeys);
+    if (rc != SAGE_OK)
+    {
+      fprintf(stderr, "%s: %s\n", family == SAGE_TERM_GRAPH ? "sage_window_graph_factor" : "sage_window_keypoint_factor",
+              sage_error_string(rc));
+      exit(rc);
+    }
+    return Assemble(factor_keys, G, g, dims, nkeys, f);
+  }
+
+  double ErrorTerm(const gtsam::Values &c, int family, int term)
+  {
+    std::lock_guard<std::mutex> lock(mutex_);
+    Prepare(c, false);
+    double e = 0.0;
+    const int rc = family == SAGE_TERM_GRAPH ? sage_window_graph_factor_error(win_, term, &e)
+                                             : sage_window_keypoint_factor_error(win_, term, &e);
+    if (rc != SAGE_OK)
+    {
+      fprintf(stderr, "%s: %s\n", family == SAGE_TERM_GRAPH ? "sage_window_graph_factor_error" : "sage_window_keypoint_factor_error",
+              sage_error_string(rc));
+      exit(rc);
+    }
+    return e;
+  }
+
+private:
+  // the upper-triangular blocks and g as the engine packs them -> gtsam::HessianFactor(keys, Gs, gs, f)
+  static boost::shared_ptr<gtsam::HessianFactor> Assemble(const gtsam::FastVector<gtsam::Key> &factor_keys,
+                                                          const std::vector<double> &G, const std::vector<double> &g,
+                                                          const int *dims, int nkeys, double f)
+  {
     using RowMajor = Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>;
     std::vector<gtsam::Matrix> Gs;
     std::vector<gtsam::Vector> gs;
@@ -125,22 +198,6 @@ public:
     return boost::make_shared<gtsam::HessianFactor>(factor_keys, Gs, gs, f); // f = error_ (photometric_factor.cpp:218)
   }
 
-  // PhotometricFactor::error / GeometricFactor::error (photometric_factor.cpp:72-101, geometric_factor.cpp:41-64)
-  double Error(const gtsam::Values &c, int type, int edge)
-  {
-    std::lock_guard<std::mutex> lock(mutex_);
-    Prepare(c, false);
-    double e = 0.0;
-    const int rc = sage_window_factor_error(win_, type, edge, &e);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "sage_window_factor_error: %s\n", sage_error_string(rc));
-      exit(rc);
-    }
-    return e;
-  }
-
-private:
   SageWindow *win_;
   std::vector<Keys> keys_;
   int CS_, psd_mode_;
@@ -167,5 +224,34 @@ public:
 //   }
 //
 // with two new members (std::shared_ptr<SageWindowCache> cache_; int edge_) set by Mapper when it adds the link.
+//
+// The matched-keypoint factor of a link direction and the factors of the loop-closure graphs carry the id their term got from
+// sage_window_add_keypoint_term / sage_window_add_graph_term (int term_) instead of an edge; their bodies become
+//
+//   MatchGeometryFactor (core/gtsam/match_geometry_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_KEYPOINT, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_KEYPOINT, SAGE_KP_MATCH_GEOMETRY, term_,
+//                                              {pose0_key_, pose1_key_, code0_key_, code1_key_, scale0_key_, scale1_key_});
+//   ReprojectionFactor (reprojection_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_KEYPOINT, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_KEYPOINT, SAGE_KP_REPROJECTION, term_,
+//                                              {pose0_key_, pose1_key_, code0_key_, scale0_key_});
+//   LoopMGFactor (loop_mg_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_KEYPOINT, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_KEYPOINT, SAGE_KP_LOOP_MG, term_,
+//                                              {pose0_key_, pose1_key_, scale0_key_, scale1_key_});
+//   RelPoseScaleFactor (rel_pose_scale_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_GRAPH, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_GRAPH, SAGE_GRAPH_REL_POSE_SCALE, term_,
+//                                              {pose0_key_, pose1_key_, scale0_key_, scale1_key_});
+//   RelPoseFactor (rel_pose_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_GRAPH, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_GRAPH, SAGE_GRAPH_REL_POSE, term_, {pose0_key_, pose1_key_});
+//   ScaleFactor with a target (scale_factor.cpp):
+//     error:      return cache_->ErrorTerm(c, SAGE_TERM_GRAPH, term_);
+//     linearize:  return cache_->LinearizeTerm(c, SAGE_TERM_GRAPH, SAGE_GRAPH_SCALE_PRIOR, term_, {scale_key_});
+//
+// PoseFactor, CodeFactor and a ScaleFactor without a target are the window's priors: closed-form on the host, they stay as
+// the reference wrote them.
 
 } // namespace df

@@ -146,7 +146,7 @@ SYMBOLS = [
     "sage_window_residuals_per_linearize", "sage_window_bytes_per_linearize", "sage_window_linearize",
     "sage_window_error", "sage_window_tune_runs", "sage_window_set_runs", "sage_window_error_dev", "sage_window_solve", "sage_window_total_error",
     "sage_window_accept", "sage_window_reset", "sage_window_get_keyframe", "sage_window_set_keyframe", "sage_window_get_delta",
-    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_add_graph_term", "sage_window_num_graph_terms", "sage_window_get_graph_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_window_prepare_factors", "sage_window_prepare_factors_device", "sage_window_prepare_factors_device_launches", "sage_factor_psd", "sage_factor_psd_batch", "sage_factor_psd_batch_launches", "sage_factor_psd_batch_plan", "sage_jacobi_round_pairs", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
+    "sage_window_get_edge", "sage_window_add_keypoint_term", "sage_window_num_keypoint_terms", "sage_window_get_keypoint_term", "sage_window_add_graph_term", "sage_window_num_graph_terms", "sage_window_get_graph_term", "sage_window_prepass", "sage_window_factor", "sage_window_factor_error", "sage_term_factor_block_count", "sage_term_factor_blocks", "sage_window_keypoint_factor", "sage_window_keypoint_factor_error", "sage_window_graph_factor", "sage_window_graph_factor_error", "sage_window_prepare_factors", "sage_window_prepare_factors_device", "sage_window_prepare_factors_device_launches", "sage_factor_psd", "sage_factor_psd_batch", "sage_factor_psd_batch_launches", "sage_factor_psd_batch_plan", "sage_jacobi_round_pairs", "sage_factor_cut_blocks", "sage_window_set_profiling", "sage_window_get_kernel_time", "sage_window_get_phase_time", "sage_window_lm_step", "sage_window_lm_run", "sage_window_lm_run_timed", "sage_window_sync_variables", "sage_window_set_allreduce", "sage_shard_plan_create", "sage_shard_plan_create_domains", "sage_block_solve_domains", "sage_shard_plan_destroy", "sage_shard_sep_count", "sage_shard_num_separators", "sage_shard_num_interior", "sage_shard_keyframe_owner", "sage_shard_keyframe_is_local", "sage_shard_eliminate", "sage_shard_solve", "sage_rccl_unique_id", "sage_rccl_comm_create", "sage_rccl_comm_destroy", "sage_rccl_comm_info", "sage_window_use_rccl", "sage_window_emulate_peers", "sage_sort_locations", "sage_bind_thread_to_device", "sage_solver_helper_cpus", "sage_solver_placement_moves", "sage_placement_monitor", "sage_shutdown", "sage_host_threads_running",
     "sage_valid_locations", "sage_shuffle_indices", "sage_sample_locations",
     "sage_reprojection_jac_error_calculate", "sage_reprojection_error_calculate",
     "sage_tracker_reproj_jac_error_calculate", "sage_tracker_reproj_error_calculate",
@@ -269,6 +269,47 @@ def factor_hessian_blocks(type_: int, CS: int, AtA, Atb, psd_mode: int = 1):
             blocks[(i, j)] = G[o:o + dims[i] * dims[j]].reshape(dims[i], dims[j]); o += dims[i] * dims[j]
     offs = np.concatenate([[0], np.cumsum(dims)])
     return blocks, [g[offs[i]:offs[i + 1]] for i in range(nk.value)], dims
+
+
+TERM_KEYPOINT, TERM_GRAPH = 0, 1                      # SAGE_TERM_*: the family of a window term
+
+
+def _blocks_of(G, g, dims):
+    """the packed upper blocks and g of a factor -> (dict {(i, j): G_ij}, [g_i])"""
+    blocks, o = {}, 0
+    for i in range(len(dims)):
+        for j in range(i, len(dims)):
+            blocks[(i, j)] = G[o:o + dims[i] * dims[j]].reshape(dims[i], dims[j]); o += dims[i] * dims[j]
+    offs = np.concatenate([[0], np.cumsum(dims)]).astype(int)
+    return blocks, [g[offs[i]:offs[i + 1]] for i in range(len(dims))]
+
+
+def term_factor_block_count(family: int, kind: int, CS: int) -> int:
+    """``sage_term_factor_block_count``: doubles of a term factor's packed upper blocks, or the negative status code"""
+    return int(lib().sage_term_factor_block_count(int(family), int(kind), int(CS)))
+
+
+def term_factor_blocks_raw(family, kind, CS, AtA_ptr, Atb_ptr, psd_mode, G_ptr, g_ptr, dims_ptr, nkeys_ptr) -> int:
+    """``sage_term_factor_blocks`` with the arguments as given (pointers may be None) -> status code"""
+    f = lib().sage_term_factor_blocks
+    f.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(family, kind, CS, AtA_ptr, Atb_ptr, psd_mode, G_ptr, g_ptr, dims_ptr, nkeys_ptr))
+
+
+def term_factor_blocks(family: int, kind: int, CS: int, AtA, Atb, psd_mode: int = 1):
+    """``sage_term_factor_blocks`` of a term's system in its group's layout (what ``Window.get_keypoint_term`` /
+    ``get_graph_term`` return) -> (dict {(i, j): G_ij}, [g_i], dims): the term's HessianFactor blocks in push order."""
+    A = _f32(AtA); b = _f32(Atb)
+    n = term_factor_block_count(family, kind, CS)
+    if n < 0:
+        raise SageError(n, "sage_term_factor_block_count")
+    G = np.zeros(n, np.float64); g = np.zeros(b.size, np.float64)
+    dims = (C.c_int32 * 6)(); nk = C.c_int32()
+    _chk(term_factor_blocks_raw(family, kind, CS, A.ctypes.data, b.ctypes.data, psd_mode, G.ctypes.data, g.ctypes.data,
+                                C.addressof(dims), C.addressof(nk)), "sage_term_factor_blocks")
+    dims = [int(dims[i]) for i in range(nk.value)]
+    blocks, gs = _blocks_of(G, g[:sum(dims)], dims)
+    return blocks, gs, dims
 
 
 PSD_MAX_DIM = 80
@@ -1552,6 +1593,50 @@ class Window:
         f = lib().sage_window_prepare_factors_device_launches
         f.argtypes = [C.c_void_p]
         return int(f(self.h))
+
+    def _term_factor(self, graph: bool, i, psd_mode, check):
+        name = "sage_window_graph_factor" if graph else "sage_window_keypoint_factor"
+        f_ = getattr(lib(), name)
+        f_.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        D = 14 + 2 * self.win.CS                                    # the widest term factor
+        G = np.zeros(D * (D + 1) // 2 + D * D, np.float64); g = np.zeros(D, np.float64); f = C.c_double()
+        dims = (C.c_int32 * 6)(); nk = C.c_int32()
+        rc = int(f_(self.h, int(i), int(psd_mode), G.ctypes.data, g.ctypes.data, C.addressof(f), C.addressof(dims),
+                    C.addressof(nk)))
+        if rc != 0:
+            if check:
+                raise SageError(rc, name)
+            return rc, None
+        dims = [int(dims[k]) for k in range(nk.value)]
+        blocks, gs = _blocks_of(G, g[:sum(dims)].copy(), dims)
+        out = (blocks, gs, f.value, dims)
+        return out if check else (rc, out)
+
+    def keypoint_factor(self, i, psd_mode: int = 1, check=True):
+        """f2: the HessianFactor of keypoint term i from the prepass cache -> (blocks, gs, f, dims); with ``check=False``
+        (status code, that tuple or None) instead of raising."""
+        return self._term_factor(False, i, psd_mode, check)
+
+    def graph_factor(self, i, psd_mode: int = 1, check=True):
+        """f2: the HessianFactor of graph term i from the prepass cache -> (blocks, gs, f, dims); ``check`` as above."""
+        return self._term_factor(True, i, psd_mode, check)
+
+    def _term_factor_error(self, graph: bool, i, check):
+        name = "sage_window_graph_factor_error" if graph else "sage_window_keypoint_factor_error"
+        f_ = getattr(lib(), name)
+        f_.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        v = C.c_double()
+        rc = int(f_(self.h, int(i), C.addressof(v)))
+        if check:
+            _chk(rc, name)
+            return v.value
+        return rc, v.value
+
+    def keypoint_factor_error(self, i, check=True) -> float:
+        return self._term_factor_error(False, i, check)
+
+    def graph_factor_error(self, i, check=True) -> float:
+        return self._term_factor_error(True, i, check)
 
     def factor_error(self, type_, e) -> float:
         v = C.c_double()

@@ -409,13 +409,23 @@ struct SageWindow
       // host threads right after a prepass
       std::vector<double> C;
     } side[2];                    // [kPhoto], [kGeo]
+    // the terms of a window that has some, per term group: the group's AtA / Atb buffers as they lie on the device, and the
+    // projected matrices in the same [count][D][D] layout (a kind that owns fewer columns: its own sub-matrix, in place)
+    struct TermGroup
+    {
+      std::vector<float> A, b;
+      std::vector<double> C;
+    } term[plan::kTermGroups];
+    std::vector<float> term_s;    // [n_stats][2]: {error, inliers} of the pass the cache was pulled from
     int psd_mode = -1;            // < 0: the projected matrices are not prepared for the cached linearisation
     uint64_t dense_serial = 0;    // SageWindow::dense_serial when A was pulled: equal -> the device AtA still is this linearisation
+    uint64_t term_serial = 0;     // TermSide::serial when term[].A was pulled: the same for the terms' buffers
   } fc;
   // sage_window_prepare_factors_device (psd_project.hip's kernel): per factor type the uploaded AtA (only when the device's
   // own has moved on), the projected matrices and the records; what the last call launched and its worst record
   uint64_t dense_serial = 0;      // counts the linearizes that have written dense[].AtA
-  DevBuf psd_in[2], psd_out[2], psd_stats[2];
+  // (slots 0 / 1: the dense factor types, 2 + g: term group g)
+  DevBuf psd_in[2 + plan::kTermGroups], psd_out[2 + plan::kTermGroups], psd_stats[2 + plan::kTermGroups];
   int psd_launches = 0;
   SagePsdStats psd_worst{};
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)

@@ -82,6 +82,7 @@ struct TermSide
   DevBuf AtA[plan::kTermGroups], Atb[plan::kTermGroups]; // per group [count][D * D], [count][D]
   DevBuf stats;                           // [2][n_stats][2]: {error, inliers} of the last linearize, of the last error pass
   bool linearized = false;                // ... at least once: there is something to read
+  uint64_t serial = 0;                    // counts the linearizes that have written AtA / Atb (sage_window_prepare_factors_device)
   int n_keypoint() const { return layout.n_keypoint(); } // local terms of the keypoint kernel, of the graph kernel, of both
   int n_graph() const { return layout.n_graph(); }
   int n_stats() const { return layout.n_stats(); }

@@ -267,6 +267,8 @@ int window_launch_terms(SageWindow *w, int set, bool jac)
   const KpBatchParams kp{ts.kp_table.as<KpTerm>(), vars, w->VS, w->cfg.pyr.cam[0], w->cfg.eps, ts.results(jac)};
   const GraphBatchParams gp{ts.gt_table.as<GraphTerm>(), ts.n_graph(), vars, w->VS, ts.results(jac)};
   int rc = SAGE_OK;
+  if (jac && ts.n_stats() > 0)
+    ++ts.serial; // the groups' AtA are about to be rewritten
   if (ts.n_keypoint() > 0)
     rc = timed_launch(w, jac ? 4 : 5, [&] {
       return launch_keypoint_batch(w->stream, w->cfg.CS, jac, ts.n_keypoint(), ts.keypoint_kinds(), kp);
