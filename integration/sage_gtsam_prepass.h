@@ -71,12 +71,7 @@ public:
       scale_[k] = c.at<float>(keys_[k].scale);
     }
     int recomputed = 0;
-    const int rc = sage_window_prepass(win_, pose_.data(), code_.data(), scale_.data(), jacobians ? 1 : 0, &recomputed);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "sage_window_prepass: %s\n", sage_error_string(rc)); // the reference's gpuErrchk convention
-      exit(rc);
-    }
+    Check(sage_window_prepass(win_, pose_.data(), code_.data(), scale_.data(), jacobians ? 1 : 0, &recomputed), "sage_window_prepass");
     // the per-factor NearestPsd (the host cost of linearize(): an SVD of a 45 x 45 / 78 x 78 matrix each) for the whole
     // window at once on the host's cores; Linearize() below then only cuts blocks
     if (recomputed && jacobians && eager_psd_threads_ >= 0)
@@ -97,33 +92,15 @@ public:
   boost::shared_ptr<gtsam::HessianFactor> Linearize(const gtsam::Values &c, int type, int edge,
                                                     const gtsam::FastVector<gtsam::Key> &factor_keys)
   {
-    std::lock_guard<std::mutex> lock(mutex_); // factors are called from up to 4 host threads (deepfactors.cpp:1497-1505)
-    Prepare(c, true);
-    std::vector<double> G(sage_factor_block_count(type, CS_)), g(type == 0 ? 13 + CS_ : 14 + 2 * CS_);
-    int dims[6], nkeys = 0;
-    double f = 0.0;
-    const int rc = sage_window_factor(win_, type, edge, psd_mode_, G.data(), g.data(), &f, dims, &nkeys);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "sage_window_factor: %s\n", sage_error_string(rc));
-      exit(rc);
-    }
-    return Assemble(factor_keys, G, g, dims, nkeys, f);
+    return ServeLinearize(c, factor_keys, sage_factor_block_count(type, CS_), "sage_window_factor",
+                          [&](double *G, double *g, double *f, int32_t *dims, int32_t *nkeys)
+                          { return sage_window_factor(win_, type, edge, psd_mode_, G, g, f, dims, nkeys); });
   }
 
   // PhotometricFactor::error / GeometricFactor::error (photometric_factor.cpp:72-101, geometric_factor.cpp:41-64)
   double Error(const gtsam::Values &c, int type, int edge)
   {
-    std::lock_guard<std::mutex> lock(mutex_);
-    Prepare(c, false);
-    double e = 0.0;
-    const int rc = sage_window_factor_error(win_, type, edge, &e);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "sage_window_factor_error: %s\n", sage_error_string(rc));
-      exit(rc);
-    }
-    return e;
+    return ServeError(c, "sage_window_factor_error", [&](double *e) { return sage_window_factor_error(win_, type, edge, e); });
   }
 
   // The window's terms (sage_window_add_keypoint_term / sage_window_add_graph_term; `term` is the id the add call returned)
@@ -136,45 +113,56 @@ public:
   boost::shared_ptr<gtsam::HessianFactor> LinearizeTerm(const gtsam::Values &c, int family, int kind, int term,
                                                         const gtsam::FastVector<gtsam::Key> &factor_keys)
   {
-    std::lock_guard<std::mutex> lock(mutex_);
-    Prepare(c, true);
-    const int count = sage_term_factor_block_count(family, kind, CS_);
-    if (count < 0)
-    {
-      fprintf(stderr, "sage_term_factor_block_count: %s\n", sage_error_string(count));
-      exit(count);
-    }
-    std::vector<double> G(count), g(14 + 2 * CS_); // (the widest term)
-    int32_t dims[6], nkeys = 0;
-    double f = 0.0;
-    const int rc = family == SAGE_TERM_GRAPH ? sage_window_graph_factor(win_, term, psd_mode_, G.data(), g.data(), &f, dims, &nkeys)
-                                             : sage_window_keypoint_factor(win_, term, psd_mode_, G.data(), g.data(), &f, dims, &nkeys);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "%s: %s\n", family == SAGE_TERM_GRAPH ? "sage_window_graph_factor" : "sage_window_keypoint_factor",
-              sage_error_string(rc));
-      exit(rc);
-    }
-    return Assemble(factor_keys, G, g, dims, nkeys, f);
+    const bool graph = family == SAGE_TERM_GRAPH;
+    return ServeLinearize(c, factor_keys, sage_term_factor_block_count(family, kind, CS_),
+                          graph ? "sage_window_graph_factor" : "sage_window_keypoint_factor",
+                          [&](double *G, double *g, double *f, int32_t *dims, int32_t *nkeys)
+                          { return (graph ? sage_window_graph_factor : sage_window_keypoint_factor)(win_, term, psd_mode_, G, g, f, dims, nkeys); });
   }
 
   double ErrorTerm(const gtsam::Values &c, int family, int term)
   {
-    std::lock_guard<std::mutex> lock(mutex_);
-    Prepare(c, false);
-    double e = 0.0;
-    const int rc = family == SAGE_TERM_GRAPH ? sage_window_graph_factor_error(win_, term, &e)
-                                             : sage_window_keypoint_factor_error(win_, term, &e);
-    if (rc != SAGE_OK)
-    {
-      fprintf(stderr, "%s: %s\n", family == SAGE_TERM_GRAPH ? "sage_window_graph_factor_error" : "sage_window_keypoint_factor_error",
-              sage_error_string(rc));
-      exit(rc);
-    }
-    return e;
+    const bool graph = family == SAGE_TERM_GRAPH;
+    return ServeError(c, graph ? "sage_window_graph_factor_error" : "sage_window_keypoint_factor_error",
+                      [&](double *e) { return (graph ? sage_window_graph_factor_error : sage_window_keypoint_factor_error)(win_, term, e); });
   }
 
 private:
+  static void Check(int rc, const char *name) // the reference's gpuErrchk convention
+  {
+    if (rc == SAGE_OK)
+      return;
+    fprintf(stderr, "%s: %s\n", name, sage_error_string(rc));
+    exit(rc);
+  }
+
+  // one linearize(): the cache at these Values, room for `count` doubles of blocks (a negative count: the status of the
+  // block-count call), the engine's read `call` (named `name` in the message), the blocks as a HessianFactor
+  template <class Call>
+  boost::shared_ptr<gtsam::HessianFactor> ServeLinearize(const gtsam::Values &c, const gtsam::FastVector<gtsam::Key> &factor_keys,
+                                                         int count, const char *name, Call call)
+  {
+    std::lock_guard<std::mutex> lock(mutex_); // factors are called from up to 4 host threads (deepfactors.cpp:1497-1505)
+    Prepare(c, true);
+    Check(count < 0 ? count : SAGE_OK, "factor block count");
+    std::vector<double> G(count), g(14 + 2 * CS_); // (the widest factor)
+    int32_t dims[6], nkeys = 0;
+    double f = 0.0;
+    Check(call(G.data(), g.data(), &f, dims, &nkeys), name);
+    return Assemble(factor_keys, G, g, dims, nkeys, f);
+  }
+
+  // one error(): the same for the factor's error
+  template <class Call>
+  double ServeError(const gtsam::Values &c, const char *name, Call call)
+  {
+    std::lock_guard<std::mutex> lock(mutex_);
+    Prepare(c, false);
+    double e = 0.0;
+    Check(call(&e), name);
+    return e;
+  }
+
   // the upper-triangular blocks and g as the engine packs them -> gtsam::HessianFactor(keys, Gs, gs, f)
   static boost::shared_ptr<gtsam::HessianFactor> Assemble(const gtsam::FastVector<gtsam::Key> &factor_keys,
                                                           const std::vector<double> &G, const std::vector<double> &g,

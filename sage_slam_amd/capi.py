@@ -263,12 +263,8 @@ def factor_hessian_blocks(type_: int, CS: int, AtA, Atb, psd_mode: int = 1):
                                       g.ctypes.data_as(C.POINTER(C.c_double)), dims, C.byref(nk)),
          "sage_factor_hessian_blocks")
     dims = [int(dims[i]) for i in range(nk.value)]
-    blocks, o = {}, 0
-    for i in range(nk.value):
-        for j in range(i, nk.value):
-            blocks[(i, j)] = G[o:o + dims[i] * dims[j]].reshape(dims[i], dims[j]); o += dims[i] * dims[j]
-    offs = np.concatenate([[0], np.cumsum(dims)])
-    return blocks, [g[offs[i]:offs[i + 1]] for i in range(nk.value)], dims
+    blocks, gs = _blocks_of(G, g, dims)
+    return blocks, gs, dims
 
 
 TERM_KEYPOINT, TERM_GRAPH = 0, 1                      # SAGE_TERM_*: the family of a window term
@@ -1560,22 +1556,42 @@ class Window:
         _chk(lib().sage_window_prepass(self.h, _fp(P), _fp(Cd), _fp(S), int(jacobians), C.byref(rec)), "sage_window_prepass")
         return bool(rec.value)
 
+    # by the number of ids in front (1: a term, 2: a dense factor's type and edge): window, ids, [psd_mode,] output pointers
+    _FACTOR_ARGTYPES = {n: [C.c_void_p] + [C.c_int] * (n + 1) + [C.c_void_p] * 5 for n in (1, 2)}
+    _ERROR_ARGTYPES = {n: [C.c_void_p] + [C.c_int] * n + [C.c_void_p] for n in (1, 2)}
+
+    def _cached_factor(self, name, ids, psd_mode, check):
+        """one factor of the prepass cache through the C call ``name(window, *ids, psd_mode, G, g, f, dims, nkeys)`` ->
+        (blocks, gs, f, dims); with ``check=False`` (status code, that tuple or None) instead of raising."""
+        f_ = getattr(lib(), name)
+        f_.argtypes = self._FACTOR_ARGTYPES[len(ids)]
+        D = 14 + 2 * self.win.CS                                    # the widest factor
+        G = np.zeros(D * (D + 1) // 2 + D * D, np.float64); g = np.zeros(D, np.float64); f = C.c_double()
+        dims = (C.c_int32 * 6)(); nk = C.c_int32()
+        rc = int(f_(self.h, *ids, int(psd_mode), G.ctypes.data, g.ctypes.data, C.addressof(f), C.addressof(dims), C.addressof(nk)))
+        if rc != 0:
+            if check:
+                raise SageError(rc, name)
+            return rc, None
+        dims = [int(dims[k]) for k in range(nk.value)]
+        blocks, gs = _blocks_of(G, g[:sum(dims)].copy(), dims)
+        out = (blocks, gs, f.value, dims)
+        return out if check else (rc, out)
+
+    def _cached_error(self, name, ids, check):
+        """one factor's error through ``name(window, *ids, err)`` -> the error; ``check=False``: (status code, error)"""
+        f_ = getattr(lib(), name)
+        f_.argtypes = self._ERROR_ARGTYPES[len(ids)]
+        v = C.c_double()
+        rc = int(f_(self.h, *ids, C.addressof(v)))
+        if check:
+            _chk(rc, name)
+            return v.value
+        return rc, v.value
+
     def factor(self, type_, e, psd_mode: int = 1):
         """f2: the HessianFactor of directed edge e from the prepass cache -> (blocks, gs, f, dims)."""
-        L = lib(); CS = self.win.CS
-        n = L.sage_factor_block_count(type_, CS)
-        D = 13 + CS if type_ == 0 else 14 + 2 * CS
-        G = np.zeros(n, np.float64); g = np.zeros(D, np.float64); f = C.c_double()
-        dims = (C.c_int32 * 6)(); nk = C.c_int32()
-        _chk(L.sage_window_factor(self.h, type_, e, psd_mode, G.ctypes.data_as(C.POINTER(C.c_double)),
-                                  g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(f), dims, C.byref(nk)), "sage_window_factor")
-        dims = [int(dims[i]) for i in range(nk.value)]
-        blocks, o = {}, 0
-        for i in range(nk.value):
-            for j in range(i, nk.value):
-                blocks[(i, j)] = G[o:o + dims[i] * dims[j]].reshape(dims[i], dims[j]); o += dims[i] * dims[j]
-        offs = np.concatenate([[0], np.cumsum(dims)])
-        return blocks, [g[offs[i]:offs[i + 1]] for i in range(nk.value)], f.value, dims
+        return self._cached_factor("sage_window_factor", (int(type_), int(e)), psd_mode, True)
 
     def prepare_factors(self, psd_mode: int = 1, n_threads: int = 0):
         """f2: NearestPsd of every cached factor on host threads; factor(.., psd_mode) then only cuts blocks."""
@@ -1594,54 +1610,23 @@ class Window:
         f.argtypes = [C.c_void_p]
         return int(f(self.h))
 
-    def _term_factor(self, graph: bool, i, psd_mode, check):
-        name = "sage_window_graph_factor" if graph else "sage_window_keypoint_factor"
-        f_ = getattr(lib(), name)
-        f_.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        D = 14 + 2 * self.win.CS                                    # the widest term factor
-        G = np.zeros(D * (D + 1) // 2 + D * D, np.float64); g = np.zeros(D, np.float64); f = C.c_double()
-        dims = (C.c_int32 * 6)(); nk = C.c_int32()
-        rc = int(f_(self.h, int(i), int(psd_mode), G.ctypes.data, g.ctypes.data, C.addressof(f), C.addressof(dims),
-                    C.addressof(nk)))
-        if rc != 0:
-            if check:
-                raise SageError(rc, name)
-            return rc, None
-        dims = [int(dims[k]) for k in range(nk.value)]
-        blocks, gs = _blocks_of(G, g[:sum(dims)].copy(), dims)
-        out = (blocks, gs, f.value, dims)
-        return out if check else (rc, out)
-
     def keypoint_factor(self, i, psd_mode: int = 1, check=True):
         """f2: the HessianFactor of keypoint term i from the prepass cache -> (blocks, gs, f, dims); with ``check=False``
         (status code, that tuple or None) instead of raising."""
-        return self._term_factor(False, i, psd_mode, check)
+        return self._cached_factor("sage_window_keypoint_factor", (int(i),), psd_mode, check)
 
     def graph_factor(self, i, psd_mode: int = 1, check=True):
         """f2: the HessianFactor of graph term i from the prepass cache -> (blocks, gs, f, dims); ``check`` as above."""
-        return self._term_factor(True, i, psd_mode, check)
-
-    def _term_factor_error(self, graph: bool, i, check):
-        name = "sage_window_graph_factor_error" if graph else "sage_window_keypoint_factor_error"
-        f_ = getattr(lib(), name)
-        f_.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        v = C.c_double()
-        rc = int(f_(self.h, int(i), C.addressof(v)))
-        if check:
-            _chk(rc, name)
-            return v.value
-        return rc, v.value
+        return self._cached_factor("sage_window_graph_factor", (int(i),), psd_mode, check)
 
     def keypoint_factor_error(self, i, check=True) -> float:
-        return self._term_factor_error(False, i, check)
+        return self._cached_error("sage_window_keypoint_factor_error", (int(i),), check)
 
     def graph_factor_error(self, i, check=True) -> float:
-        return self._term_factor_error(True, i, check)
+        return self._cached_error("sage_window_graph_factor_error", (int(i),), check)
 
     def factor_error(self, type_, e) -> float:
-        v = C.c_double()
-        _chk(lib().sage_window_factor_error(self.h, type_, e, C.byref(v)), "sage_window_factor_error")
-        return v.value
+        return self._cached_error("sage_window_factor_error", (int(type_), int(e)), True)
 
     def set_profiling(self, on):
         """False / 0 off, True / 1 every hot kernel + phase marks, 2 the photometric linearize only."""

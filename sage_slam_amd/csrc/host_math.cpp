@@ -162,7 +162,10 @@ void sym_eig(std::vector<double> &A, int n, std::vector<double> &w, std::vector<
 // A = V diag(w) V^T as sym_eig at ~1/15 of the time for the 45 x 45 / 78 x 78 factor matrices (Higham projection of
 // sage_nearest_psd: the per-factor host cost of the gtsam path).  Returns false if QL does not converge (the caller falls
 // back to the Jacobi sweeps).  A is destroyed.
-static bool sym_eig_ql(std::vector<double> &A, int n, std::vector<double> &w, std::vector<double> &V)
+// (SAGE_HOT: starts on a 64-byte line.  Its loops run 4-7 % slower or faster with where they fall in a line, and a function
+// aligned to 16 bytes moves whenever a unit linked in front of it changes size)
+#define SAGE_HOT __attribute__((aligned(64)))
+SAGE_HOT static bool sym_eig_ql(std::vector<double> &A, int n, std::vector<double> &w, std::vector<double> &V)
 {
   std::vector<double> e(n, 0.0);
   w.assign(n, 0.0);
@@ -343,7 +346,7 @@ static bool is_psd(const std::vector<double> &M, int n)
 
 } // namespace sage
 
-extern "C" int sage_nearest_psd(const double *M, int n, double *out)
+extern "C" SAGE_HOT int sage_nearest_psd(const double *M, int n, double *out)
 {
   if (!M || !out || n < 1)
     return SAGE_E_INVALID;
@@ -599,217 +602,6 @@ extern "C" int sage_nearest_psd_reference(const double *M, int n, double *out)
   }
   std::memcpy(out, A3.data(), sizeof(double) * n * n);
   return SAGE_OK;
-}
-
-// ---------------------------------------------------------------- HessianFactor blocks (a6 / a7)
-static int factor_dims(int type, int CS, int dims[6])
-{
-  if (CS < 1 || (type != 0 && type != 1))
-    return 0;
-  if (type == 0)
-  {
-    const int d[4] = {6, 6, CS, 1};
-    std::copy(d, d + 4, dims);
-    return 4;
-  }
-  const int d[6] = {6, 6, CS, CS, 1, 1};
-  std::copy(d, d + 6, dims);
-  return 6;
-}
-
-extern "C" int sage_factor_block_count(int type, int CS)
-{
-  int dims[6];
-  const int nk = factor_dims(type, CS, dims);
-  if (!nk)
-    return SAGE_E_INVALID;
-  int total = 0;
-  for (int i = 0; i < nk; ++i)
-    for (int j = i; j < nk; ++j)
-      total += dims[i] * dims[j];
-  return total;
-}
-
-// widen to double and project: psd_mode 0 none, 1 Higham, 2 NearestPsd as the reference wrote it
-extern "C" int sage_factor_psd(int type, int CS, const float *AtA, int psd_mode, double *C_out)
-{
-  int dims[6];
-  const int nk = factor_dims(type, CS, dims);
-  if (!nk || !AtA || !C_out || psd_mode < 0 || psd_mode > 2)
-    return SAGE_E_INVALID;
-  int D = 0;
-  for (int i = 0; i < nk; ++i)
-    D += dims[i];
-  std::vector<double> M((size_t)D * D);
-  for (size_t i = 0; i < M.size(); ++i)
-    M[i] = (double)AtA[i]; // AtA_.cast<double>() (photometric_factor.cpp:305, :142)
-  if (psd_mode == 1)
-    return sage_nearest_psd(M.data(), D, C_out);
-  if (psd_mode == 2)
-    return sage_nearest_psd_reference(M.data(), D, C_out);
-  std::memcpy(C_out, M.data(), M.size() * sizeof(double));
-  return SAGE_OK;
-}
-
-// the upper-triangular blocks G11 G12 .. Gnn of a (projected) D x D matrix and g = Atb in the reference's push order
-extern "C" int sage_factor_cut_blocks(int type, int CS, const double *C, const float *Atb, double *G_out, double *g_out,
-                                      int32_t *dims_out, int32_t *nkeys_out)
-{
-  int dims[6];
-  const int nk = factor_dims(type, CS, dims);
-  if (!nk || !C || !Atb || !G_out || !g_out)
-    return SAGE_E_INVALID;
-  int D = 0, off[6];
-  for (int i = 0; i < nk; ++i)
-  {
-    off[i] = D;
-    D += dims[i];
-  }
-  double *o = G_out;
-  for (int i = 0; i < nk; ++i)
-    for (int j = i; j < nk; ++j)
-      for (int r = 0; r < dims[i]; ++r)
-        for (int c = 0; c < dims[j]; ++c)
-          *o++ = C[(size_t)(off[i] + r) * D + off[j] + c];
-  for (int i = 0; i < D; ++i)
-    g_out[i] = (double)Atb[i];
-  if (dims_out)
-    for (int i = 0; i < nk; ++i)
-      dims_out[i] = dims[i];
-  if (nkeys_out)
-    *nkeys_out = nk;
-  return SAGE_OK;
-}
-
-extern "C" int sage_factor_hessian_blocks(int type, int CS, const float *AtA, const float *Atb, int psd_mode,
-                                          double *G_out, double *g_out, int32_t *dims_out, int32_t *nkeys_out)
-{
-  int dims[6];
-  const int nk = factor_dims(type, CS, dims);
-  if (!nk || !AtA || !Atb || !G_out || !g_out || psd_mode < 0 || psd_mode > 2)
-    return SAGE_E_INVALID;
-  int D = 0;
-  for (int i = 0; i < nk; ++i)
-    D += dims[i];
-  std::vector<double> C((size_t)D * D);
-  const int rc = sage_factor_psd(type, CS, AtA, psd_mode, C.data());
-  if (rc)
-    return rc;
-  return sage_factor_cut_blocks(type, CS, C.data(), Atb, G_out, g_out, dims_out, nkeys_out);
-}
-
-// ---------------------------------------------------------------- HessianFactor blocks of a window's terms
-// A term's factor by family and kind: the keys in the reference's push order (MatchGeometryFactor, ReprojectionFactor,
-// LoopMGFactor, RelPoseScaleFactor, RelPoseFactor, ScaleFactor), the columns of the term group's layout it owns
-// ([first, first + D_own) of D_group) -- the reference projects a RelPoseFactor's 12 x 12 and a ScaleFactor's 1 x 1, not
-// the zero-padded 14 x 14 the window keeps them in
-sage::TermShape sage::term_shape(int family, int kind, int CS)
-{
-  TermShape s;
-  if (CS < 1 || (family != SAGE_TERM_KEYPOINT && family != SAGE_TERM_GRAPH))
-    return s;
-  auto set = [&s](std::initializer_list<int> d, int D_group, int first) {
-    for (int v : d)
-    {
-      s.dims[s.nk++] = v;
-      s.D_own += v;
-    }
-    s.D_group = D_group;
-    s.first = first;
-  };
-  if (family == SAGE_TERM_KEYPOINT)
-  {
-    if (kind == SAGE_KP_REPROJECTION)
-      set({6, 6, CS, 1}, 13 + CS, 0);
-    else if (kind == SAGE_KP_MATCH_GEOMETRY)
-      set({6, 6, CS, CS, 1, 1}, 14 + 2 * CS, 0);
-    else if (kind == SAGE_KP_LOOP_MG)
-      set({6, 6, 1, 1}, 14, 0);
-  }
-  else
-  {
-    if (kind == SAGE_GRAPH_REL_POSE_SCALE)
-      set({6, 6, 1, 1}, 14, 0);
-    else if (kind == SAGE_GRAPH_REL_POSE)
-      set({6, 6}, 14, 0);
-    else if (kind == SAGE_GRAPH_SCALE_PRIOR)
-      set({1}, 14, 12);
-  }
-  return s;
-}
-
-extern "C" int sage_term_factor_block_count(int family, int kind, int CS)
-{
-  const sage::TermShape s = sage::term_shape(family, kind, CS);
-  if (!s.nk)
-    return SAGE_E_INVALID;
-  int total = 0;
-  for (int i = 0; i < s.nk; ++i)
-    for (int j = i; j < s.nk; ++j)
-      total += s.dims[i] * s.dims[j];
-  return total;
-}
-
-// the kind's own D_own x D_own sub-matrix of a group-layout AtA, widened and projected per psd_mode (as sage_factor_psd)
-int sage::term_factor_psd(int family, int kind, int CS, const float *AtA, int psd_mode, double *C_out)
-{
-  const sage::TermShape s = sage::term_shape(family, kind, CS);
-  if (!s.nk || !AtA || !C_out || psd_mode < 0 || psd_mode > 2)
-    return SAGE_E_INVALID;
-  const int D = s.D_own;
-  std::vector<double> M((size_t)D * D);
-  for (int i = 0; i < D; ++i)
-    for (int j = 0; j < D; ++j)
-      M[(size_t)i * D + j] = (double)AtA[(size_t)(s.first + i) * s.D_group + s.first + j];
-  if (psd_mode == 1)
-    return sage_nearest_psd(M.data(), D, C_out);
-  if (psd_mode == 2)
-    return sage_nearest_psd_reference(M.data(), D, C_out);
-  std::memcpy(C_out, M.data(), M.size() * sizeof(double));
-  return SAGE_OK;
-}
-
-// the upper-triangular blocks of a (projected) matrix C with row stride ldc whose entry (0, 0) is the kind's first own
-// column, and g = the kind's columns of the group-layout Atb
-int sage::term_factor_cut(int family, int kind, int CS, const double *C, int ldc, const float *Atb, double *G_out,
-                          double *g_out, int32_t *dims_out, int32_t *nkeys_out)
-{
-  const sage::TermShape s = sage::term_shape(family, kind, CS);
-  if (!s.nk || !C || !Atb || !G_out || !g_out || ldc < s.D_own)
-    return SAGE_E_INVALID;
-  int off[6], D = 0;
-  for (int i = 0; i < s.nk; ++i)
-  {
-    off[i] = D;
-    D += s.dims[i];
-  }
-  double *o = G_out;
-  for (int i = 0; i < s.nk; ++i)
-    for (int j = i; j < s.nk; ++j)
-      for (int r = 0; r < s.dims[i]; ++r)
-        for (int c = 0; c < s.dims[j]; ++c)
-          *o++ = C[(size_t)(off[i] + r) * ldc + off[j] + c];
-  for (int i = 0; i < D; ++i)
-    g_out[i] = (double)Atb[s.first + i];
-  if (dims_out)
-    for (int i = 0; i < s.nk; ++i)
-      dims_out[i] = s.dims[i];
-  if (nkeys_out)
-    *nkeys_out = s.nk;
-  return SAGE_OK;
-}
-
-extern "C" int sage_term_factor_blocks(int family, int kind, int CS, const float *AtA, const float *Atb, int psd_mode,
-                                       double *G_out, double *g_out, int32_t *dims_out, int32_t *nkeys_out)
-{
-  const sage::TermShape s = sage::term_shape(family, kind, CS);
-  if (!s.nk || !AtA || !Atb || !G_out || !g_out || psd_mode < 0 || psd_mode > 2)
-    return SAGE_E_INVALID;
-  std::vector<double> C((size_t)s.D_own * s.D_own);
-  const int rc = sage::term_factor_psd(family, kind, CS, AtA, psd_mode, C.data());
-  if (rc)
-    return rc;
-  return sage::term_factor_cut(family, kind, CS, C.data(), s.D_own, Atb, G_out, g_out, dims_out, nkeys_out);
 }
 
 extern "C" int sage_damped_solve_qr_f32(const float *A, const float *b, int n, float damp, float *x)

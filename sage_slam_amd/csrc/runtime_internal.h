@@ -30,8 +30,9 @@
 //   window_terms.hip    keypoint and pose-graph terms: add / get, their finalize stage, their two launches
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
-// window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, totals mirror,
-// distributed state, profiler); device_buffers.h holds the owners of device and pinned allocations (DevBuf, PinnedBuf: also
+//   factor_blocks.cpp   (no HIP) what a cached factor is: shape, projection of its own matrix, cut into HessianFactor blocks
+// window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, factor cache, totals
+// mirror, distributed state, profiler); device_buffers.h holds the owners of device and pinned allocations (DevBuf, PinnedBuf: also
 // included by solve_kernels.hip); the layouts of the workspace's pinned regions (WsHostStats, TrackHost) are below
 #pragma once
 
@@ -71,6 +72,7 @@ extern "C"
 
 #include "device_buffers.h" // DevBuf, PinnedBuf
 #include "host_math.h"
+#include "factor_blocks.h" // FactorShape and the functions over it
 #include "host_threads.h" // placement, shutdown (the window units do not touch the block solver itself)
 #include "sage_ba.h"
 #include "sage_internal.h"
@@ -396,38 +398,8 @@ struct SageWindow
   DevBuf packed_save;                     // linearize-at-candidate: the candidate's (reduced) system is formed here; an accepted
                                           // candidate swaps it with `packed` (which always is the current estimate's system)
   TermSide terms;                         // keypoint and pose-graph terms: as added, this rank's layout, device tables, results
-  // f2: per-Values factor cache (sage_window_prepass): host copies of every local edge's results and the values
-  // (all K keyframes) they were evaluated at
-  struct FactorCache
-  {
-    bool lin = false, err = false;
-    std::vector<float> pose, code, scale;         // the key: [K][12], [K][CS], [K]
-    struct Side
-    {
-      std::vector<float> A, b, s; // per local directed edge: AtA, Atb, (error, n_inliers)
-      // sage_window_prepare_factors: the projected (NearestPsd) double matrices of every local edge, computed on several
-      // host threads right after a prepass
-      std::vector<double> C;
-    } side[2];                    // [kPhoto], [kGeo]
-    // the terms of a window that has some, per term group: the group's AtA / Atb buffers as they lie on the device, and the
-    // projected matrices in the same [count][D][D] layout (a kind that owns fewer columns: its own sub-matrix, in place)
-    struct TermGroup
-    {
-      std::vector<float> A, b;
-      std::vector<double> C;
-    } term[plan::kTermGroups];
-    std::vector<float> term_s;    // [n_stats][2]: {error, inliers} of the pass the cache was pulled from
-    int psd_mode = -1;            // < 0: the projected matrices are not prepared for the cached linearisation
-    uint64_t dense_serial = 0;    // SageWindow::dense_serial when A was pulled: equal -> the device AtA still is this linearisation
-    uint64_t term_serial = 0;     // TermSide::serial when term[].A was pulled: the same for the terms' buffers
-  } fc;
-  // sage_window_prepare_factors_device (psd_project.hip's kernel): per factor type the uploaded AtA (only when the device's
-  // own has moved on), the projected matrices and the records; what the last call launched and its worst record
-  uint64_t dense_serial = 0;      // counts the linearizes that have written dense[].AtA
-  // (slots 0 / 1: the dense factor types, 2 + g: term group g)
-  DevBuf psd_in[2 + plan::kTermGroups], psd_out[2 + plan::kTermGroups], psd_stats[2 + plan::kTermGroups];
-  int psd_launches = 0;
-  SagePsdStats psd_worst{};
+  FactorCache fc;                         // f2: the per-Values factor cache (sage_window_prepass): window_state.h
+  uint64_t dense_serial = 0;              // counts the linearizes that have written dense[].AtA (FactorSlot::live_serial)
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an

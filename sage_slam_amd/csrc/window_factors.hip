@@ -1,6 +1,7 @@
 // window_factors.hip -- f2: per-edge results and the per-Values factor cache behind the gtsam adapter
 // (photometric_factor.cpp:72-219, geometric_factor.cpp:41-233): batched prepass, factor blocks, NearestPsd on host threads
-// and on the device; the same for the window's keypoint and graph terms (sage_window_keypoint_factor, sage_window_graph_factor).
+// and on the device, for the dense factors and for the window's keypoint and graph terms alike: a cached factor is a
+// FactorRef into a FactorSlot (window_state.h) with a FactorShape (factor_blocks.h).
 #include "runtime_internal.h"
 
 extern "C" int sage_window_get_edge(const SageWindow *w, int type, int e, float *AtA, float *Atb, float *err,
@@ -33,16 +34,14 @@ extern "C" int sage_window_get_edge(const SageWindow *w, int type, int e, float 
 // linearize(values) / error(values) one at a time with the SAME Values; the reference answers each with its own kernel
 // launches, .item() syncs and a NearestPsd (photometric_factor.cpp:72-219, geometric_factor.cpp:41-233).  Here the first
 // factor that sees new values triggers ONE sage_window_linearize (or sage_window_error) for the whole window and one
-// device-to-host copy of the per-edge results; every other factor is served from the host cache.
-static int local_edge_index(const SageWindow *w, int e) { return window_local_edge(w, e); }
-
+// device-to-host copy of the per-edge and per-term results; every other factor is served from the host cache.
 extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const float *codes, const float *scales,
                                    int jacobians, int *recomputed)
 {
   if (!w || !w->finalized || !pose12 || !codes || !scales)
     return SAGE_E_INVALID;
   const int K = w->K, CS = w->cfg.CS;
-  SageWindow::FactorCache &fc = w->fc;
+  FactorCache &fc = w->fc;
   const size_t np = (size_t)K * 12, nc = (size_t)K * CS;
   const bool same = fc.pose.size() == np && std::memcmp(fc.pose.data(), pose12, np * sizeof(float)) == 0 &&
                     std::memcmp(fc.code.data(), codes, nc * sizeof(float)) == 0 &&
@@ -86,40 +85,35 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
   else if ((rc = sage_window_error(w, 0)))
     return rc;
   SAGE_HIP(hipStreamSynchronize(w->stream));
-  auto pull = [&](std::vector<float> &dst, const DevBuf &src, size_t n) -> hipError_t {
+  auto pull = [](std::vector<float> &dst, const float *src, size_t n) -> hipError_t {
     dst.resize(n);
-    return n ? hipMemcpy(dst.data(), src.p, n * sizeof(float), hipMemcpyDeviceToHost) : hipSuccess;
+    return n ? hipMemcpy(dst.data(), src, n * sizeof(float), hipMemcpyDeviceToHost) : hipSuccess;
   };
-  for (int type = kPhoto; type <= kGeo; ++type)
-  {
-    if (!(type == kPhoto ? w->cfg.use_photo : w->cfg.use_geo))
-      continue;
-    const size_t D = dense_dim(type, CS);
-    if (jacobians)
-    {
-      SAGE_HIP(pull(fc.side[type].A, w->dense[type].AtA, ne * D * D));
-      SAGE_HIP(pull(fc.side[type].b, w->dense[type].Atb, ne * D));
-    }
-    SAGE_HIP(pull(fc.side[type].s, w->dense[type].stats, ne * 2));
-  }
-  if (jacobians)
-    fc.dense_serial = w->dense_serial;
-  // the terms of a window that has some: every group's systems, and the {error, inliers} set this pass wrote
   const TermSide &ts = w->terms;
-  if (ts.n_stats() > 0)
+  const bool with_terms = ts.n_stats() > 0;
+  for (int sl = 0; sl < FactorCache::kSlots; ++sl)
   {
-    for (int g = 0; g < plan::kTermGroups && jacobians; ++g)
-    {
-      const size_t n = (size_t)ts.layout.count[g], D = (size_t)TermResults::dim(g, CS);
-      SAGE_HIP(pull(fc.term[g].A, ts.AtA[g], n * D * D));
-      SAGE_HIP(pull(fc.term[g].b, ts.Atb[g], n * D));
-    }
-    const size_t nst = (size_t)2 * ts.n_stats();
-    fc.term_s.resize(nst);
-    SAGE_HIP(hipMemcpy(fc.term_s.data(), ts.results(jacobians != 0).stats, nst * sizeof(float), hipMemcpyDeviceToHost));
+    // what slot sl caches: a dense factor type's per-edge results, or a term group's systems of a window that has terms
+    const bool dense = sl < 2;
+    const int g = sl - 2;
+    if (!(dense ? (sl == kPhoto ? w->cfg.use_photo : w->cfg.use_geo) : with_terms))
+      continue;
     if (jacobians)
-      fc.term_serial = ts.serial;
+    {
+      FactorSlot &s = fc.slot[sl];
+      const size_t n = dense ? ne : (size_t)ts.layout.count[g];
+      s.D = dense ? dense_dim(sl, CS) : (size_t)TermResults::dim(g, CS);
+      s.live = dense ? &w->dense[sl].AtA : &ts.AtA[g];
+      s.live_serial = dense ? &w->dense_serial : &ts.serial;
+      SAGE_HIP(pull(s.A, s.live->as<float>(), n * s.D * s.D));
+      SAGE_HIP(pull(s.b, dense ? w->dense[sl].Atb.as<float>() : ts.Atb[g].as<float>(), n * s.D));
+      s.serial = *s.live_serial;
+    }
+    if (dense)
+      SAGE_HIP(pull(fc.stats[sl], w->dense[sl].stats.as<float>(), ne * 2));
   }
+  if (with_terms) // the {error, inliers} set this pass wrote
+    SAGE_HIP(pull(fc.stats[2], ts.results(jacobians != 0).stats, (size_t)2 * ts.n_stats()));
   fc.lin = jacobians != 0;
   fc.err = true;
   if (recomputed)
@@ -127,72 +121,40 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
   return SAGE_OK;
 }
 
-extern "C" int sage_window_factor_error(const SageWindow *w, int type, int e, double *err_out)
+// ---- a cached factor.  FactorRef: the entry of a slot it is cut from, where its {error, inliers} stand, its shape
+struct FactorRef
 {
-  if (!w || !w->finalized || (type != 0 && type != 1) || !err_out)
-    return SAGE_E_INVALID;
-  const SageWindow::FactorCache &fc = w->fc;
-  if (!fc.err)
-    return SAGE_E_STATE;
-  const int le = local_edge_index(w, e);
-  const std::vector<float> &st = fc.side[type].s;
-  if (le < 0 || (size_t)le * 2 + 1 >= st.size())
-    return SAGE_E_INVALID;
-  *err_out = (double)st[(size_t)le * 2];
-  return SAGE_OK;
-}
-
-extern "C" int sage_window_factor(const SageWindow *w, int type, int e, int psd_mode, double *G_out, double *g_out,
-                                  double *f_out, int *dims_out, int *nkeys_out)
-{
-  if (!w || !w->finalized || (type != 0 && type != 1))
-    return SAGE_E_INVALID;
-  const SageWindow::FactorCache &fc = w->fc;
-  if (!fc.lin)
-    return SAGE_E_STATE;
-  const int le = local_edge_index(w, e);
-  const int CS = w->cfg.CS;
-  const size_t D = dense_dim(type, CS);
-  const std::vector<float> &A = fc.side[type].A, &b = fc.side[type].b, &st = fc.side[type].s;
-  if (le < 0 || ((size_t)le + 1) * D * D > A.size())
-    return SAGE_E_INVALID;
-  if (f_out)
-    *f_out = (double)st[(size_t)le * 2];
-  const std::vector<double> &Cc = fc.side[type].C;
-  if (fc.psd_mode == psd_mode && ((size_t)le + 1) * D * D <= Cc.size()) // prepared on the host threads already
-    return sage_factor_cut_blocks(type, CS, Cc.data() + (size_t)le * D * D, b.data() + (size_t)le * D, G_out, g_out,
-                                  dims_out, nkeys_out);
-  return sage_factor_hessian_blocks(type, CS, A.data() + (size_t)le * D * D, b.data() + (size_t)le * D, psd_mode, G_out,
-                                    g_out, dims_out, nkeys_out);
-}
-
-// ---- a term's factor from the cache.  TermRef: where a term of this rank lives and what shape its factor has
-struct TermRef
-{
-  int family, kind;
-  plan::TermSlot slot;
-  TermShape shape;
+  int slot, entry;    // entry < 0: a directed edge that is not one of this rank's dense edges
+  int stat_set, stat; // FactorCache::stats[stat_set][2 * stat]
+  FactorShape shape;
 };
+static FactorRef dense_ref(const SageWindow *w, int type, int local_edge)
+{
+  return FactorRef{type, local_edge, type, local_edge, dense_factor_shape(type, w->cfg.CS)};
+}
 // SAGE_OK and *ref, or SAGE_E_INVALID: no such term, or another rank's
-static int term_ref(const SageWindow *w, bool graph, int term, TermRef *ref)
+static int term_ref(const SageWindow *w, bool graph, int term, FactorRef *ref)
 {
   if (!w || !w->finalized)
     return SAGE_E_INVALID;
   const TermSide &ts = w->terms;
   if (term < 0 || term >= (graph ? (int)ts.gt_added.size() : (int)ts.kp_added.size()))
     return SAGE_E_INVALID;
-  ref->family = graph ? SAGE_TERM_GRAPH : SAGE_TERM_KEYPOINT;
-  ref->kind = graph ? ts.gt_added[term].kind : ts.kp_added[term].kind;
-  ref->slot = (graph ? ts.layout.graph : ts.layout.kp)[term];
-  ref->shape = term_shape(ref->family, ref->kind, w->cfg.CS);
-  return ref->slot.local < 0 || !ref->shape.nk ? SAGE_E_INVALID : SAGE_OK;
+  const plan::TermSlot &at = (graph ? ts.layout.graph : ts.layout.kp)[term];
+  const int kind = graph ? ts.gt_added[term].kind : ts.kp_added[term].kind;
+  *ref = FactorRef{2 + at.group, at.out, 2, at.stat, term_factor_shape(graph ? SAGE_TERM_GRAPH : SAGE_TERM_KEYPOINT, kind, w->cfg.CS)};
+  return at.local < 0 || !ref->shape.nk ? SAGE_E_INVALID : SAGE_OK;
 }
 
-// every term of this rank, keypoint terms then graph terms, each family in launch order
-static std::vector<TermRef> local_terms(const SageWindow *w)
+// every cached factor of this rank: the photometric and the geometric factors by local edge, the keypoint terms and the
+// graph terms in launch order
+static std::vector<FactorRef> local_refs(const SageWindow *w)
 {
-  std::vector<TermRef> out;
-  TermRef r;
+  std::vector<FactorRef> out;
+  for (int type = kPhoto; type <= kGeo; ++type)
+    for (size_t i = 0; i < w->fc.slot[type].n(); ++i)
+      out.push_back(dense_ref(w, type, (int)i));
+  FactorRef r;
   for (int id : w->terms.layout.kp_order)
     if (term_ref(w, false, id, &r) == SAGE_OK)
       out.push_back(r);
@@ -202,46 +164,87 @@ static std::vector<TermRef> local_terms(const SageWindow *w)
   return out;
 }
 
-// the term's own sub-matrix inside entry `out` of a group's [count][D][D] array
+// the factor's own sub-matrix inside its entry of a slot's [n][D][D] array (a dense factor's: the entry)
 template <class T>
-static T *term_own(T *base, const TermRef &r)
+static T *own_matrix(T *base, const FactorRef &r)
 {
   const size_t D = (size_t)r.shape.D_group;
-  return base + (size_t)r.slot.out * D * D + (size_t)r.shape.first * (D + 1);
+  return base + (size_t)r.entry * D * D + (size_t)r.shape.first * (D + 1);
+}
+
+// NearestPsd of the factor's own matrix, into its columns of the entry of the slot's C (`own`: scratch)
+static int project_own(FactorSlot &sl, const FactorRef &r, int psd_mode, std::vector<double> &own)
+{
+  const size_t D = (size_t)r.shape.D_group, Do = (size_t)r.shape.D_own;
+  own.resize(Do * Do);
+  const int rc = factor_psd(r.shape, sl.A.data() + (size_t)r.entry * D * D, psd_mode, own.data());
+  double *dst = own_matrix(sl.C.data(), r);
+  for (size_t a = 0; a < Do && !rc; ++a)
+    std::memcpy(dst + a * D, own.data() + a * Do, Do * sizeof(double));
+  return rc;
+}
+
+// the factor from the cache: prepared for this psd_mode, so cut; otherwise project and cut.  `missing`: the status of a
+// factor the cache has no entry for (a dense edge that is not local: SAGE_E_INVALID; a term: SAGE_E_STATE, a cache pulled
+// before the window had its terms, which cannot happen after finalize)
+static int cached_factor(const FactorCache &fc, const FactorRef &r, int missing, int psd_mode, double *G_out, double *g_out,
+                         double *f_out, int32_t *dims_out, int32_t *nkeys_out)
+{
+  if (!fc.lin)
+    return SAGE_E_STATE;
+  const FactorSlot &sl = fc.slot[r.slot];
+  const std::vector<float> &st = fc.stats[r.stat_set];
+  const size_t D = (size_t)r.shape.D_group, e = (size_t)r.entry;
+  if (r.entry < 0 || (e + 1) * D * D > sl.A.size() || (size_t)r.stat * 2 + 1 >= st.size())
+    return missing;
+  if (f_out)
+    *f_out = (double)st[(size_t)r.stat * 2];
+  const float *b = sl.b.data() + e * D;
+  if (fc.psd_mode == psd_mode && (e + 1) * D * D <= sl.C.size()) // prepared already: cut the blocks from the factor's own columns
+    return factor_cut(r.shape, own_matrix(sl.C.data(), r), (int)D, b, G_out, g_out, dims_out, nkeys_out);
+  return factor_blocks(r.shape, sl.A.data() + e * D * D, b, psd_mode, G_out, g_out, dims_out, nkeys_out);
+}
+
+static int cached_error(const FactorCache &fc, const FactorRef &r, int missing, double *err_out)
+{
+  if (!fc.err)
+    return SAGE_E_STATE;
+  const std::vector<float> &st = fc.stats[r.stat_set];
+  if (r.entry < 0 || (size_t)r.stat * 2 + 1 >= st.size())
+    return missing;
+  *err_out = (double)st[(size_t)r.stat * 2];
+  return SAGE_OK;
+}
+
+extern "C" int sage_window_factor(const SageWindow *w, int type, int e, int psd_mode, double *G_out, double *g_out,
+                                  double *f_out, int *dims_out, int *nkeys_out)
+{
+  if (!w || !w->finalized || (type != 0 && type != 1))
+    return SAGE_E_INVALID;
+  return cached_factor(w->fc, dense_ref(w, type, window_local_edge(w, e)), SAGE_E_INVALID, psd_mode, G_out, g_out, f_out,
+                       dims_out, nkeys_out);
+}
+extern "C" int sage_window_factor_error(const SageWindow *w, int type, int e, double *err_out)
+{
+  if (!w || !w->finalized || (type != 0 && type != 1) || !err_out)
+    return SAGE_E_INVALID;
+  return cached_error(w->fc, dense_ref(w, type, window_local_edge(w, e)), SAGE_E_INVALID, err_out);
 }
 
 static int term_factor(const SageWindow *w, bool graph, int term, int psd_mode, double *G_out, double *g_out, double *f_out,
                        int32_t *dims_out, int32_t *nkeys_out)
 {
-  TermRef r;
+  FactorRef r;
   if (term_ref(w, graph, term, &r) || psd_mode < 0 || psd_mode > 2 || !G_out || !g_out)
     return SAGE_E_INVALID;
-  const SageWindow::FactorCache &fc = w->fc;
-  if (!fc.lin)
-    return SAGE_E_STATE;
-  const SageWindow::FactorCache::TermGroup &tg = fc.term[r.slot.group];
-  const size_t D = (size_t)r.shape.D_group, out = (size_t)r.slot.out;
-  if ((out + 1) * D * D > tg.A.size() || (size_t)r.slot.stat * 2 + 1 >= fc.term_s.size())
-    return SAGE_E_STATE; // (a cache pulled before the window had its terms: cannot happen after finalize)
-  if (f_out)
-    *f_out = (double)fc.term_s[(size_t)r.slot.stat * 2];
-  const float *b = tg.b.data() + out * D;
-  if (fc.psd_mode == psd_mode && (out + 1) * D * D <= tg.C.size()) // prepared already: cut the kind's blocks from its own columns
-    return term_factor_cut(r.family, r.kind, w->cfg.CS, term_own(tg.C.data(), r), (int)D, b, G_out, g_out, dims_out, nkeys_out);
-  return sage_term_factor_blocks(r.family, r.kind, w->cfg.CS, tg.A.data() + out * D * D, b, psd_mode, G_out, g_out, dims_out,
-                                 nkeys_out);
+  return cached_factor(w->fc, r, SAGE_E_STATE, psd_mode, G_out, g_out, f_out, dims_out, nkeys_out);
 }
-
 static int term_factor_error(const SageWindow *w, bool graph, int term, double *err_out)
 {
-  TermRef r;
+  FactorRef r;
   if (term_ref(w, graph, term, &r) || !err_out)
     return SAGE_E_INVALID;
-  const SageWindow::FactorCache &fc = w->fc;
-  if (!fc.err || (size_t)r.slot.stat * 2 + 1 >= fc.term_s.size())
-    return SAGE_E_STATE;
-  *err_out = (double)fc.term_s[(size_t)r.slot.stat * 2];
-  return SAGE_OK;
+  return cached_error(w->fc, r, SAGE_E_STATE, err_out);
 }
 
 extern "C" int sage_window_keypoint_factor(const SageWindow *w, int term, int psd_mode, double *G_out, double *g_out,
@@ -266,41 +269,24 @@ extern "C" int sage_window_graph_factor_error(const SageWindow *w, int term, dou
 // NearestPsd of EVERY cached factor on `n_threads` host threads (0 = a quarter of the host's hardware threads, at most 64): the per-factor
 // projection is the host cost of the gtsam path (an SVD / eigen-decomposition of a 45 x 45 and a 78 x 78 matrix per link
 // direction, photometric_factor.cpp:142-149) -- ISAM2 pays it factor by factor, here it is paid once per Values in
-// parallel and sage_window_factor only cuts blocks afterwards.  The window's terms join the same queue, each with its own
-// D_own x D_own matrix (sage_term_factor_blocks' definition).
+// parallel and the reads only cut blocks afterwards.  Every factor is projected on its own D_own x D_own matrix
+// (factor_psd's definition).
 extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_threads)
 {
   if (!w || !w->finalized || psd_mode < 0 || psd_mode > 2)
     return SAGE_E_INVALID;
-  SageWindow::FactorCache &fc = w->fc;
+  FactorCache &fc = w->fc;
   if (!fc.lin)
     return SAGE_E_STATE;
   if (fc.psd_mode == psd_mode)
     return SAGE_OK;
-  const int CS = w->cfg.CS;
-  const size_t Dp = dense_dim(kPhoto, CS), Dg = dense_dim(kGeo, CS);
-  const size_t nep = fc.side[kPhoto].A.size() / (Dp * Dp), neg = fc.side[kGeo].A.size() / (Dg * Dg);
   fc.psd_mode = -1; // the projected matrices are being rewritten: whatever they held is gone until this call succeeds
-  fc.side[kPhoto].C.assign(nep * Dp * Dp, 0.0);
-  fc.side[kGeo].C.assign(neg * Dg * Dg, 0.0);
+  for (FactorSlot &sl : fc.slot)
+    sl.C.assign(sl.A.size(), 0.0);
   // the work queue, longest jobs first: the geometric factors and match-geometry terms (14 + 2 CS), the photometric factors
-  // and reprojection terms (13 + CS), then the terms of 14, 12 and 1 columns; a term is projected on its own sub-matrix
-  struct Job
-  {
-    int D, type; // type: the dense factor type, or -1: terms[index]
-    size_t index;
-  };
-  const std::vector<TermRef> terms = fc.lin && w->terms.n_stats() > 0 ? local_terms(w) : std::vector<TermRef>();
-  for (int g = 0; g < plan::kTermGroups; ++g)
-    fc.term[g].C.assign(fc.term[g].A.size(), 0.0);
-  std::vector<Job> jobs;
-  for (size_t i = 0; i < neg; ++i)
-    jobs.push_back({(int)Dg, kGeo, i});
-  for (size_t i = 0; i < nep; ++i)
-    jobs.push_back({(int)Dp, kPhoto, i});
-  for (size_t i = 0; i < terms.size(); ++i)
-    jobs.push_back({terms[i].shape.D_own, -1, i});
-  std::stable_sort(jobs.begin(), jobs.end(), [](const Job &a, const Job &b) { return a.D > b.D; });
+  // and reprojection terms (13 + CS), then the terms of 14, 12 and 1 columns
+  std::vector<FactorRef> jobs = local_refs(w);
+  std::stable_sort(jobs.begin(), jobs.end(), [](const FactorRef &a, const FactorRef &b) { return a.shape.D_own > b.shape.D_own; });
   const size_t total = jobs.size();
   if (n_threads <= 0)
     n_threads = (int)std::min<unsigned>(64u, std::max(1u, std::thread::hardware_concurrency() / 4)); // a quarter of the host, <= 64
@@ -308,30 +294,13 @@ extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_th
   std::atomic<size_t> next{0};
   std::atomic<int> bad{0};
   auto work = [&]() {
-    std::vector<double> own; // a term's projected own matrix, before it goes into its columns of the group's entry
+    std::vector<double> own;
     for (;;)
     {
       const size_t i = next.fetch_add(1, std::memory_order_relaxed);
       if (i >= total)
         return;
-      const Job &j = jobs[i];
-      int rc;
-      if (j.type >= 0)
-      {
-        const size_t DD = (size_t)j.D * j.D;
-        rc = sage_factor_psd(j.type, CS, fc.side[j.type].A.data() + j.index * DD, psd_mode, fc.side[j.type].C.data() + j.index * DD);
-      }
-      else
-      {
-        const TermRef &r = terms[j.index];
-        SageWindow::FactorCache::TermGroup &tg = fc.term[r.slot.group];
-        const size_t D = (size_t)r.shape.D_group, Do = (size_t)r.shape.D_own;
-        own.resize(Do * Do);
-        rc = term_factor_psd(r.family, r.kind, CS, tg.A.data() + (size_t)r.slot.out * D * D, psd_mode, own.data());
-        double *dst = term_own(tg.C.data(), r);
-        for (size_t a = 0; a < Do && !rc; ++a)
-          std::memcpy(dst + a * D, own.data() + a * Do, Do * sizeof(double));
-      }
+      const int rc = project_own(fc.slot[jobs[i].slot], jobs[i], psd_mode, own);
       if (rc)
         bad.store(rc, std::memory_order_relaxed);
     }
@@ -349,132 +318,81 @@ extern "C" int sage_window_prepare_factors(SageWindow *w, int psd_mode, int n_th
 }
 
 // The same preparation on the device, psd_mode 1 only: one launch of the batched Higham projection (psd_project.hip) per
-// factor type present and per term group that has entries, the projected matrices and their records copied back behind
-// them, one wait.  The kernel reads the window's own per-edge AtA (a term group's AtA) while that still is the linearisation
-// the cache was pulled from (dense_serial, term_serial); after another linearize the cached copy is uploaded instead.  A term
-// group is projected as it lies, at the group's D: a kind that owns fewer columns sits in exact zeros, which the sweeps skip
-// and the acceptance test passes, and its blocks are cut from its own columns.  A factor whose record is not clean (sweep
-// cap, non-finite input) is projected again on the host, so such inputs come out as sage_window_prepare_factors leaves them.
+// slot that has entries, the projected matrices and their records copied back behind them, one wait.  The kernel reads the
+// window's own per-edge AtA (a term group's AtA) while that still is the linearisation the cache was pulled from
+// (FactorSlot::serial); after another linearize the cached copy is uploaded instead.  A term group is projected as it lies,
+// at the group's D: a kind that owns fewer columns sits in exact zeros, which the sweeps skip and the acceptance test passes,
+// and its blocks are cut from its own columns.  A factor whose record is not clean (sweep cap, non-finite input) is
+// projected again on the host, so such inputs come out as sage_window_prepare_factors leaves them.
 extern "C" int sage_window_prepare_factors_device(SageWindow *w, SagePsdStats *worst)
 {
   if (!w || !w->finalized)
     return SAGE_E_INVALID;
-  SageWindow::FactorCache &fc = w->fc;
+  FactorCache &fc = w->fc;
   if (!fc.lin)
     return SAGE_E_STATE;
-  w->psd_launches = 0;
+  fc.psd_launches = 0;
   if (fc.psd_mode == 1)
   {
     if (worst)
-      *worst = w->psd_worst;
+      *worst = fc.psd_worst;
     return SAGE_OK;
   }
-  const int CS = w->cfg.CS;
   fc.psd_mode = -1; // (as above)
-  // a batch per slot: the dense factor types, then the term groups
-  constexpr int kSlots = 2 + plan::kTermGroups;
-  struct Batch
-  {
-    size_t D = 0, n = 0;
-    const std::vector<float> *A = nullptr; // the cached input
-    std::vector<double> *C = nullptr;
-    const float *dev = nullptr;            // the device's own copy, or null: it has moved on
-    std::vector<SagePsdStats> rec;
-  } batch[kSlots];
-  const bool fresh = fc.dense_serial == w->dense_serial;
-  for (int type = kPhoto; type <= kGeo; ++type)
-  {
-    Batch &bt = batch[type];
-    bt.D = dense_dim(type, CS);
-    bt.A = &fc.side[type].A;
-    bt.C = &fc.side[type].C;
-    bt.dev = fresh ? w->dense[type].AtA.as<float>() : nullptr;
-  }
-  const bool with_terms = w->terms.n_stats() > 0, fresh_terms = fc.term_serial == w->terms.serial;
-  for (int g = 0; g < plan::kTermGroups; ++g)
-  {
-    Batch &bt = batch[2 + g];
-    bt.D = (size_t)TermResults::dim(g, CS);
-    bt.A = &fc.term[g].A;
-    bt.C = &fc.term[g].C;
-    bt.dev = with_terms && fresh_terms ? w->terms.AtA[g].as<float>() : nullptr;
-  }
+  std::vector<SagePsdStats> rec[FactorCache::kSlots];
   int rc;
-  for (int sl = 0; sl < kSlots; ++sl)
+  for (int i = 0; i < FactorCache::kSlots; ++i)
   {
-    Batch &bt = batch[sl];
-    bt.n = bt.A->size() / (bt.D * bt.D);
-    bt.C->resize(bt.n * bt.D * bt.D);
-    bt.rec.resize(bt.n);
-    if (!bt.n)
+    FactorSlot &sl = fc.slot[i];
+    const size_t n = sl.n(), elems = sl.A.size();
+    sl.C.resize(elems);
+    rec[i].resize(n);
+    if (!n)
       continue;
-    const size_t elems = bt.n * bt.D * bt.D;
-    const float *in = bt.dev;
+    const float *in = sl.live_AtA();
     if (!in)
     {
-      if ((rc = w->psd_in[sl].reserve(elems * sizeof(float))))
+      if ((rc = sl.psd_in.reserve(elems * sizeof(float))))
         return rc;
-      SAGE_HIP(hipMemcpyAsync(w->psd_in[sl].p, bt.A->data(), elems * sizeof(float), hipMemcpyHostToDevice, w->stream));
-      in = w->psd_in[sl].as<float>();
+      SAGE_HIP(hipMemcpyAsync(sl.psd_in.p, sl.A.data(), elems * sizeof(float), hipMemcpyHostToDevice, w->stream));
+      in = sl.psd_in.as<float>();
     }
-    if ((rc = w->psd_out[sl].reserve(elems * sizeof(double))) || (rc = w->psd_stats[sl].reserve(bt.n * sizeof(SagePsdStats))))
+    if ((rc = sl.psd_out.reserve(elems * sizeof(double))) || (rc = sl.psd_stats.reserve(n * sizeof(SagePsdStats))))
       return rc;
-    if ((rc = psd_project_enqueue(w->stream, (int)bt.D, (int)bt.n, in, w->psd_out[sl].as<double>(),
-                                  w->psd_stats[sl].as<SagePsdStats>())))
+    if ((rc = psd_project_enqueue(w->stream, (int)sl.D, (int)n, in, sl.psd_out.as<double>(), sl.psd_stats.as<SagePsdStats>())))
       return rc;
-    ++w->psd_launches;
+    ++fc.psd_launches;
   }
-  for (int sl = 0; sl < kSlots; ++sl)
-    if (batch[sl].n)
+  for (int i = 0; i < FactorCache::kSlots; ++i)
+    if (!rec[i].empty())
     {
-      Batch &bt = batch[sl];
-      SAGE_HIP(hipMemcpyAsync(bt.C->data(), w->psd_out[sl].p, bt.C->size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-      SAGE_HIP(hipMemcpyAsync(bt.rec.data(), w->psd_stats[sl].p, bt.n * sizeof(SagePsdStats), hipMemcpyDeviceToHost, w->stream));
+      FactorSlot &sl = fc.slot[i];
+      SAGE_HIP(hipMemcpyAsync(sl.C.data(), sl.psd_out.p, sl.C.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+      SAGE_HIP(hipMemcpyAsync(rec[i].data(), sl.psd_stats.p, rec[i].size() * sizeof(SagePsdStats), hipMemcpyDeviceToHost, w->stream));
     }
   SAGE_HIP(hipStreamSynchronize(w->stream));
+  // the worst record: the highest status, then the most sweeps, then the most bump rounds; a factor whose record is not
+  // clean: the host's projection of its own matrix, into its columns of the entry
   SagePsdStats worst_rec{};
   bool any = false;
-  // the worst record: the highest status, then the most sweeps, then the most bump rounds
-  auto look = [&](const SagePsdStats &r) {
-    if (!any || r.status > worst_rec.status || (r.status == worst_rec.status && (r.sweeps > worst_rec.sweeps ||
-        (r.sweeps == worst_rec.sweeps && r.bump_rounds > worst_rec.bump_rounds))))
-      worst_rec = r;
-    any = true;
-  };
-  for (int type = kPhoto; type <= kGeo; ++type)
-    for (size_t i = 0; i < batch[type].n; ++i)
-    {
-      const size_t DD = batch[type].D * batch[type].D;
-      look(batch[type].rec[i]);
-      if (batch[type].rec[i].status != 0 && (rc = sage_factor_psd(type, CS, fc.side[type].A.data() + i * DD, 1, fc.side[type].C.data() + i * DD)))
-        return rc;
-    }
-  if (with_terms)
+  std::vector<double> own;
+  for (const FactorRef &r : local_refs(w))
   {
-    std::vector<double> own;
-    for (const TermRef &r : local_terms(w))
-    {
-      const Batch &bt = batch[2 + r.slot.group];
-      if ((size_t)r.slot.out >= bt.n)
-        return SAGE_E_STATE;
-      look(bt.rec[r.slot.out]);
-      if (bt.rec[r.slot.out].status == 0)
-        continue;
-      // the host's projection of the term's own matrix, into its columns of the entry
-      const size_t D = bt.D, Do = (size_t)r.shape.D_own;
-      own.resize(Do * Do);
-      if ((rc = term_factor_psd(r.family, r.kind, CS, bt.A->data() + (size_t)r.slot.out * D * D, 1, own.data())))
-        return rc;
-      double *dst = term_own(bt.C->data(), r);
-      for (size_t a = 0; a < Do; ++a)
-        std::memcpy(dst + a * D, own.data() + a * Do, Do * sizeof(double));
-    }
+    if ((size_t)r.entry >= rec[r.slot].size())
+      return SAGE_E_STATE;
+    const SagePsdStats &s = rec[r.slot][r.entry];
+    if (!any || s.status > worst_rec.status || (s.status == worst_rec.status && (s.sweeps > worst_rec.sweeps ||
+        (s.sweeps == worst_rec.sweeps && s.bump_rounds > worst_rec.bump_rounds))))
+      worst_rec = s;
+    any = true;
+    if (s.status != 0 && (rc = project_own(fc.slot[r.slot], r, 1, own)))
+      return rc;
   }
-  w->psd_worst = worst_rec;
+  fc.psd_worst = worst_rec;
   if (worst)
     *worst = worst_rec;
   fc.psd_mode = 1;
   return SAGE_OK;
 }
 
-extern "C" int sage_window_prepare_factors_device_launches(const SageWindow *w) { return w ? w->psd_launches : 0; }
+extern "C" int sage_window_prepare_factors_device_launches(const SageWindow *w) { return w ? w->fc.psd_launches : 0; }

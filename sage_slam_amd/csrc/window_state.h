@@ -1,5 +1,5 @@
 // window_state.h -- the parts SageWindow (runtime_internal.h) is made of, one struct per owner: the host variables, a dense
-// factor type's device state, the terms, the totals mirror, the distributed state, the profiler.  Included from runtime_internal.h
+// factor type's device state, the terms, the factor cache, the totals mirror, the distributed state, the profiler.  Included from runtime_internal.h
 // (after DevBuf); host code only.
 #pragma once
 
@@ -114,6 +114,35 @@ struct TermSide
     }
     return rc ? rc : (int)hipMemsetAsync(stats.p, 0, bytes, s);
   }
+};
+
+// ---- f2: the per-Values factor cache behind the gtsam adapter (sage_window_prepass, window_factors.hip): host copies of this
+// rank's systems and the values (all K keyframes) they were evaluated at ----
+struct FactorSlot // the entries of one layout: a dense factor type's local directed edges, or a term group's entries
+{
+  size_t D = 0;                      // columns of an entry's system
+  std::vector<float> A, b;           // [n][D][D], [n][D]: AtA / Atb as they lie on the device
+  std::vector<double> C;             // the projected (NearestPsd) matrices in A's layout, once prepared (a factor that owns
+                                     // fewer than D columns: its own sub-matrix, in place)
+  DevBuf psd_in, psd_out, psd_stats; // device preparation: the uploaded A (only when the device's own has moved on), the
+                                     // projected matrices, the records
+  const DevBuf *live = nullptr;          // the device AtA that A was pulled from ...
+  const uint64_t *live_serial = nullptr; // ... the count of the linearizes that have written it ...
+  uint64_t serial = 0;                   // ... and its value at the pull: equal -> `live` still is the cached linearisation
+  size_t n() const { return D ? A.size() / (D * D) : 0; }
+  const float *live_AtA() const { return live && serial == *live_serial ? live->as<float>() : nullptr; }
+};
+struct FactorCache
+{
+  enum : int { kSlots = 2 + plan::kTermGroups, kStatSets = 3 }; // slots kPhoto, kGeo, 2 + g: term group g
+  bool lin = false, err = false;
+  std::vector<float> pose, code, scale; // the key: [K][12], [K][CS], [K]
+  FactorSlot slot[kSlots];
+  // {error, inliers} of the pass the cache was pulled from: [kPhoto], [kGeo] per local directed edge, [2] per term (n_stats)
+  std::vector<float> stats[kStatSets];
+  int psd_mode = -1;                    // < 0: the projected matrices are not prepared for the cached linearisation
+  int psd_launches = 0;                 // sage_window_prepare_factors_device: what the last call launched ...
+  SagePsdStats psd_worst{};             // ... and its worst record
 };
 
 // photometric linearize only: partial RECORDS per edge (`flush` sub-tiles each; the error pass counts work items)

@@ -5,7 +5,8 @@ sage_term_factor_blocks on the same linearisation (sage_window_get_keypoint_term
 Bars.  Lazy reads and the host-thread preparation: bit for bit.  The device preparation: bar 1 of
 tests/test_gpu_psd_project.py with the kind's own dimension, ||blocks - host||_F <= 32 D_own 2^-52 ||B||_F over all blocks
 of the factor, B the symmetrised own-dimension matrix; g and f byte for byte.  Errors of an error-only prepass against a
-linearising one, and their sum against the window's total: TOL_TOTAL of tests/test_gpu_window_keypoints.py."""
+linearising one, and their sum against the window's total: TOL_TOTAL of tests/test_gpu_window_keypoints.py.  One test reads
+the dense factors and every term group of one window through the cache they share, at the same bars."""
 import ctypes as C
 
 import numpy as np
@@ -230,6 +231,61 @@ def test_the_device_preparation_uploads_the_cache_when_the_terms_have_moved_on(c
     for i in rp:
         A = systems_x[(GRAPH, i)]["AtA"]
         assert not A[12:].any() and not A[:, 12:].any() and A[:12, :12].any()
+    win.close()
+
+
+# ------------------------------------------------------------------------------------------- one cache for both
+def read_all(win, ne, mode):
+    """every dense factor and every term of the window from the cache -> {key: (blocks, gs, f, dims)}"""
+    out = {("dense", t, e): win.factor(t, e, psd_mode=mode) for t in (0, 1) for e in range(ne)}
+    out.update({(fam, i): serve(win, fam, i, mode) for fam, i in all_ids(win)})
+    return out
+
+
+def same_bytes(a, b):
+    return (a[3] == b[3] and a[2] == b[2] and sorted(a[0]) == sorted(b[0]) and all(a[0][k].tobytes() == b[0][k].tobytes() for k in b[0])
+            and len(a[1]) == len(b[1]) and all(x.tobytes() == y.tobytes() for x, y in zip(a[1], b[1])))
+
+
+def test_dense_factors_and_every_term_group_go_through_one_cache(capi):
+    """the smallest window that fills all five slots (both dense types, one term of every kind, N = 1): (a) the host-thread
+    preparation serves what the lazy read serves, byte for byte, in every mode and for every factor; (b) after another
+    linearize the device preparation uploads every slot's cached systems, launches once per slot and serves mode 1 within
+    this file's device bar of (a)'s lazy host read, g and f byte for byte"""
+    CS = 16
+    w = synth.make_window(K=3, H=48, W=64, FS=16, CS=CS, L=3, n_samples=300, seed=5)
+    ne = 2 * len(w.links)
+    rng = np.random.default_rng(13)
+    kp = [rep_term(w, 0, n=1), mg_term(w, 1 % ne, "fair", n=1), lmg_term(w, w.links, 2 % ne, n=1)]
+    gt = [dict(kind="scale_prior", kf=1, target_scale0=float(np.float32(w.keyframes[1].scale * 1.1)), weight=50.0),
+          term_on_edge(w, w.links, ne - 1, "rel_pose", rng), term_on_edge(w, w.links, 0, "rel_pose_scale", rng)]
+    win = capi.Window(w, keypoint_terms=kp, graph_terms=gt)
+    assert win.prepass(*moved_values(w), jacobians=True)
+    own = {("dense", t, e): win.get_edge(t, e)["AtA"].astype(np.float64) for t in (0, 1) for e in range(ne)}
+    own.update({(fam, i): own_matrix(fam, family_kind(capi, win, fam, i), CS, h["AtA"]) for (fam, i), h in systems_now(win).items()})
+    # (a)
+    lazy = {mode: read_all(win, ne, mode) for mode in (0, 1, 2)}
+    assert set(lazy[1]) == set(own) and len(own) == 2 * ne + 6
+    assert any(not same_bytes(lazy[0][k], lazy[1][k]) for k in own if k[0] == "dense")      # the projections do work
+    assert any(not same_bytes(lazy[0][k], lazy[1][k]) for k in own if k[0] != "dense")
+    for prepared in (1, 2, 0):
+        win.prepare_factors(prepared, 2)
+        for mode in (prepared, 0, 1, 2):
+            again = read_all(win, ne, mode)
+            assert all(same_bytes(again[k], lazy[mode][k]) for k in own), (prepared, mode)
+    # (b)
+    win.linearize()
+    worst = win.prepare_factors_device()
+    assert win.prepare_factors_device_launches() == 5 and worst.status == 0
+    got = read_all(win, ne, 1)
+    for k, ref in lazy[1].items():
+        blocks, gs, f, dims = got[k]
+        assert dims == ref[3]
+        bar = 32 * sum(dims) * EPS * np.linalg.norm(psd_ref.symmetrised(own[k]))
+        err = np.sqrt(sum(np.sum((blocks[j] - ref[0][j]) ** 2) for j in ref[0]))
+        print("%s D_own %d: ||blocks - host||_F %.3g, bar %.3g" % (k, sum(dims), err, bar))
+        assert err <= bar, (k, err, bar)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(gs, ref[1])) and f == ref[2], k
     win.close()
 
 

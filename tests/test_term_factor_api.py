@@ -99,6 +99,28 @@ def test_the_full_layout_kinds_are_the_dense_types():
             assert all(a.tobytes() == c.tobytes() for a, c in zip(gs, rg))
 
 
+@pytest.mark.parametrize("CS", [16, 32])
+@pytest.mark.parametrize("type_", [0, 1])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_a_dense_type_and_its_keypoint_kind_share_one_definition(CS, type_, mode):
+    """what lets the dense factors and the terms share one path: on an indefinite (the projections do work), slightly
+    asymmetric (the symmetrisation does work) system, sage_factor_hessian_blocks(type) and
+    sage_term_factor_blocks(SAGE_TERM_KEYPOINT, kind = type) hand out the same bytes"""
+    D = shape(KP, type_, CS)[1]
+    r = np.random.default_rng([23, D])
+    J = r.standard_normal((D // 2, D)).astype(np.float32)
+    A = (J.T @ J - np.float32(0.3) * np.eye(D, dtype=np.float32)).astype(np.float32)
+    A[1, D - 2] += np.float32(0.01)
+    b = r.standard_normal(D).astype(np.float32)
+    assert np.linalg.eigvalsh(psd_ref.symmetrised(A)).min() < 0 and not np.array_equal(A, A.T)
+    blocks, gs, dims = capi.factor_hessian_blocks(type_, CS, A, b, mode)
+    tb, tg, tdims = capi.term_factor_blocks(KP, type_, CS, A, b, mode)
+    assert dims == tdims == shape(KP, type_, CS)[0]
+    assert sorted(blocks) == sorted(tb)
+    assert all(blocks[k].shape == tb[k].shape and blocks[k].tobytes() == tb[k].tobytes() for k in blocks)
+    assert len(gs) == len(tg) and all(a.tobytes() == c.tobytes() for a, c in zip(gs, tg))
+
+
 def test_a_sub_kind_ignores_the_columns_it_does_not_own():
     """REL_POSE projects its 12 x 12 and SCALE_PRIOR its 1 x 1 whatever stands in the rest of the 14 x 14"""
     r = np.random.default_rng(3)
