@@ -848,8 +848,55 @@ int sage_robust_registration_batch(SageWorkspace *ws, const SageRegistrationProb
  * NULL N with B > 0, an N out of range. */
 int sage_robust_registration_batch_plan(const int32_t *N, int B, int64_t *device_bytes, int64_t *pinned_bytes, int32_t *launches,
                                         int32_t *order /* [B] or NULL */);
-/* the kernel launches of the workspace's last sage_robust_registration_batch (0: none yet, nothing voted, or NULL ws) */
+/* the kernel launches of the workspace's last sage_robust_registration_batch (0: none yet, nothing voted, or NULL ws); in
+ * SAGE_REG_FINISH_DEVICE mode what was really spent: the votes' launches + 1 (the finish), and no row-copy pair */
 int sage_robust_registration_batch_launches(const SageWorkspace *ws);
+
+/* ---- the finish of a batch of registrations on the device: steps 3 and 4 in one kernel, one workgroup per problem ----
+ * Opt-in per workspace.  SAGE_REG_FINISH_HOST (the default): everything above as written, not a launch or a byte differs.
+ * SAGE_REG_FINISH_DEVICE: sage_robust_registration, sage_robust_registration_batch and sage_loop_precheck run
+ * reg_finish_kernel behind the vote instead of sage_registration_finish on the calling thread: the chain TIMs, the GNC-TLS
+ * rotation (the nine sums of H and the cost as fixed-order trees over 256 lanes, the 3x3 SVD of the host's own source in
+ * every lane), the three translation votes (a bitonic sort of the 2 N endpoints in LDS, ties by position as the host's
+ * stable sort, then the scale vote's scan and first smallest cost), the AND of the masks and the ascending inlier list,
+ * all in fp64.  The kernel writes R, t, the counts and the list into a pinned record of its own (128 + 8 N bytes per voting
+ * problem, behind the votes' records) and the list straight into the problem's inliers_dev row (the pre-check's
+ * inlier_kp_dev row: through kept); the host reads the records and does no arithmetic.  LAUNCHES: the votes' + 1; the
+ * row-copy kernel and its ticket do not run.  Waits: one (the pre-check: three).  LDS: 49 840 bytes per workgroup.
+ * THE CONTRACT in DEVICE mode: row b of a batch equals, byte for byte, the single call in DEVICE mode on problem b alone,
+ * whatever else is in the batch, in whatever order, for every SAGE_REG_SORT_TILE (the workgroup's size and its reduction
+ * trees are functions of N alone); two calls on the same inputs return identical bytes.  Against HOST mode: the counts, the
+ * list and rotation_iterations are equal wherever no discrete decision sits within rounding of its threshold; R and t
+ * differ by the rounding of reordered sums (tests/test_gpu_registration_finish.py states the bounds).
+ * rotation_max_iterations above SAGE_REG_FINISH_MAX_ITERATIONS: SAGE_E_UNSUPPORTED in DEVICE mode, before anything is
+ * launched (the kernel's loops are bounded; HOST mode accepts any cap).  Non-finite points: an unspecified answer in bounded
+ * time, nothing outside the problem's arrays is touched. */
+enum { SAGE_REG_FINISH_HOST = 0, SAGE_REG_FINISH_DEVICE = 1 };
+#define SAGE_REG_FINISH_MAX_ITERATIONS 1000 /* the reference ships 20 */
+/* SAGE_E_INVALID: NULL ws, a mode that is neither */
+int sage_workspace_set_registration_finish(SageWorkspace *ws, int mode);
+/* the workspace's mode; SAGE_REG_FINISH_HOST for NULL */
+int sage_workspace_registration_finish(const SageWorkspace *ws);
+/* steps 3 and 4 for given scales, on the device whatever the workspace's mode: what sage_registration_finish is on the host.
+ * probs as in sage_robust_registration_batch (probs[b].noise_bound replaces p->noise_bound; inliers_dev rows are written by
+ * the kernel); scales: HOST [B], any value is taken as given (as the host's call does).  A row with N < 2 gets the zeroed
+ * result and takes no part.  Fills valid = 1, scale (as given), R, t, n_inliers, rotation_iterations and n_rotation_inliers
+ * of res[b]; the vote's fields stay 0.  inliers_host [B][inliers_stride] and rotation_masks [B][inliers_stride] (uint8; 1:
+ * the chain TIM i -> i + 1 kept its weight) may be NULL; of a row the first n_inliers resp. N entries are written.  One
+ * launch (a workgroup per row with N >= 2) plus the ticket, one wait; nothing is launched when no row has N >= 2.  Pinned:
+ * Sum (128 + 8 N).  SAGE_E_INVALID / SAGE_E_UNSUPPORTED, before anything touches the device: as
+ * sage_robust_registration_batch (inliers_stride is checked when either host array is given), NULL scales with B > 0, and
+ * SAGE_E_UNSUPPORTED for rotation_max_iterations above SAGE_REG_FINISH_MAX_ITERATIONS.  B = 0: SAGE_OK. */
+int sage_registration_finish_batch(SageWorkspace *ws, const SageRegistrationProblem *probs, int B, const double *scales /* host [B] */,
+                                   const SageRegistrationParams *p, SageRegistrationResult *res /* [B] */,
+                                   int32_t *inliers_host /* [B][inliers_stride] or NULL */, int inliers_stride,
+                                   uint8_t *rotation_masks /* [B][inliers_stride] or NULL */);
+/* host only, no device: what sage_robust_registration_batch will do for these sizes in DEVICE mode (every output may be
+ * NULL).  launches: sage_robust_registration_batch_plan's + 1, 0 when nothing votes; pinned_bytes: Sum over the voting
+ * problems (64 + 32 N) + (128 + 8 N); lds_bytes: 49 840, the finish kernel's per workgroup (0 when nothing votes);
+ * workgroups: of the finish kernel, the voting problems.  SAGE_E_INVALID as sage_robust_registration_batch_plan. */
+int sage_registration_finish_plan(const int32_t *N, int B, int32_t *launches, int64_t *pinned_bytes, int32_t *lds_bytes,
+                                  int32_t *workgroups);
 typedef struct SageMatchPointsItem /* device pointers: one problem's arrays of sage_match_points */
 {
   const int32_t *cyc_inlier_flags;     /* [K] */

@@ -157,6 +157,8 @@ SYMBOLS = [
     "sage_cycle_match_batch", "sage_cycle_match_batch_slices", "sage_loop_precheck", "sage_loop_verify", "sage_loop_accept",
     "sage_robust_registration_batch", "sage_robust_registration_batch_plan", "sage_robust_registration_batch_launches",
     "sage_match_points_batch",
+    "sage_workspace_set_registration_finish", "sage_workspace_registration_finish", "sage_registration_finish_batch",
+    "sage_registration_finish_plan",
 ]
 
 
@@ -814,6 +816,14 @@ class Workspace:
         if self.h:
             lib().sage_workspace_destroy(self.h)
             self.h = C.c_void_p()
+
+    def set_registration_finish(self, mode: int):
+        """where this workspace's registrations run their finish: ``SAGE_REG_FINISH_HOST`` (the default) or
+        ``SAGE_REG_FINISH_DEVICE`` (``sage_workspace_set_registration_finish``)"""
+        _chk(workspace_set_registration_finish_raw(self.h, mode), "sage_workspace_set_registration_finish")
+
+    def registration_finish(self) -> int:
+        return workspace_registration_finish_raw(self.h)
 
     def __del__(self):
         try:
@@ -2231,6 +2241,82 @@ def robust_registration_batch(ws: "Workspace", problems, params=None, device_inl
             o["inliers_dev"] = inl_dev[b][:res[b].n_inliers]
         out.append(o)
     return out
+
+
+# --------------------------------------------------------------------------- the finish of a batch on the device
+SAGE_REG_FINISH_HOST, SAGE_REG_FINISH_DEVICE = 0, 1
+SAGE_REG_FINISH_MAX_ITERATIONS = 1000
+
+
+def workspace_set_registration_finish_raw(ws_handle, mode) -> int:
+    f = lib().sage_workspace_set_registration_finish
+    f.argtypes = [C.c_void_p, C.c_int]
+    return int(f(ws_handle, int(mode)))
+
+
+def workspace_registration_finish_raw(ws_handle) -> int:
+    f = lib().sage_workspace_registration_finish
+    f.argtypes = [C.c_void_p]
+    return int(f(ws_handle))
+
+
+def registration_finish_batch_raw(ws_handle, probs_ptr, B, scales_ptr, params_ptr, res_ptr, inliers_host_ptr, inliers_stride,
+                                  rotation_masks_ptr) -> int:
+    """``sage_registration_finish_batch`` with the arguments as given (handles / pointers may be None) -> status code"""
+    f = lib().sage_registration_finish_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    return int(f(ws_handle, probs_ptr, int(B), scales_ptr, params_ptr, res_ptr, inliers_host_ptr, int(inliers_stride), rotation_masks_ptr))
+
+
+def registration_finish_batch(ws: "Workspace", problems, scales, params=None, device_inliers: bool = False) -> list:
+    """The finish of B solves for given scales on the device through ``sage_registration_finish_batch``.  problems: as
+    ``robust_registration_batch`` takes them; scales: B floats.  -> a list of B dicts as ``registration_finish`` returns them
+    (``inliers``, ``rotation_mask`` [N] bool; with ``device_inliers`` also ``inliers_dev``)."""
+    import torch
+    B = len(problems)
+    p = params if isinstance(params, SageRegistrationParams) else registration_params(params)
+    arr = (SageRegistrationProblem * max(B, 1))()
+    res = (SageRegistrationResult * max(B, 1))()
+    sc = np.ascontiguousarray(scales, np.float64).reshape(-1)
+    assert sc.size == B
+    stride = max([int(q["src"].shape[0]) for q in problems] + [1])
+    inl = np.zeros((max(B, 1), stride), np.int32); rot = np.zeros((max(B, 1), stride), np.uint8)
+    inl_dev = []
+    for b, q in enumerate(problems):
+        N = int(q["src"].shape[0])
+        assert q["src"].dtype == torch.float32 and q["dst"].dtype == torch.float32 and q["noise_bounds"].dtype == torch.float32
+        assert tuple(q["dst"].shape) == (N, 3) and q["noise_bounds"].numel() == N
+        inl_dev.append(torch.zeros(max(N, 1), dtype=torch.int32, device="cuda") if device_inliers else None)
+        arr[b] = SageRegistrationProblem(dptr(q["src"]).value, dptr(q["dst"]).value, dptr(q["noise_bounds"]).value, N,
+                                         float(q["noise_bound"]), dptr(inl_dev[b]).value)
+    _chk(registration_finish_batch_raw(ws.h, C.addressof(arr), B, sc.ctypes.data if B else None, C.addressof(p), C.addressof(res),
+                                       inl.ctypes.data, stride, rot.ctypes.data), "sage_registration_finish_batch")
+    out = []
+    for b, q in enumerate(problems):
+        o = _reg_result(res[b])
+        o["inliers"] = inl[b, :res[b].n_inliers].copy()
+        o["rotation_mask"] = rot[b, :int(q["src"].shape[0])].astype(bool)
+        if device_inliers:
+            o["inliers_dev"] = inl_dev[b][:res[b].n_inliers]
+        out.append(o)
+    return out
+
+
+def registration_finish_plan_raw(N_ptr, B, launches_ptr, pinned_bytes_ptr, lds_bytes_ptr, workgroups_ptr) -> int:
+    f = lib().sage_registration_finish_plan
+    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    return int(f(N_ptr, int(B), launches_ptr, pinned_bytes_ptr, lds_bytes_ptr, workgroups_ptr))
+
+
+def registration_finish_plan(N) -> dict:
+    """What ``robust_registration_batch`` will do for these point counts in ``SAGE_REG_FINISH_DEVICE`` mode, through
+    ``sage_registration_finish_plan`` (host only) -> dict(launches, pinned_bytes, lds_bytes, workgroups)"""
+    n = np.ascontiguousarray(N, np.int32).reshape(-1)
+    launches, lds, wgs = C.c_int32(), C.c_int32(), C.c_int32()
+    pin = C.c_int64()
+    _chk(registration_finish_plan_raw(n.ctypes.data if n.size else None, n.size, C.addressof(launches), C.addressof(pin),
+                                      C.addressof(lds), C.addressof(wgs)), "sage_registration_finish_plan")
+    return dict(launches=launches.value, pinned_bytes=pin.value, lds_bytes=lds.value, workgroups=wgs.value)
 
 
 def match_points_batch_raw(ws_handle, items_ptr, B, divisor0, cam_ptr, K, W, mult, noise_from, M_ptr, mean_ptr) -> int:

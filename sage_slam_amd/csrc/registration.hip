@@ -21,12 +21,14 @@
 //   reg_count_kernel       the first smallest cost over the tiles gives the scale; one lane per pair counts |X - scale| <= r
 //   reg_publish_kernel     one workgroup: scale, cost and the counts, and the N points with their bounds (what the host
 //                          finish reads), into the workspace's pinned record; posts the ticket
-// then registration_host.cpp's finish on the host (O(N), fp64).  No float atomics (two integer counters), no workgroup
+// then registration_host.cpp's finish on the host (O(N), fp64) -- or, where the workspace asks for it
+// (SAGE_REG_FINISH_DEVICE), reg_finish_kernel below: the same finish, one workgroup per problem.  No float atomics (two integer counters), no workgroup
 // waits for another, every loop is bounded by N, the tile or the number of tiles.  All stores are plain C++.
 // Every kernel is a thin wrapper around a __device__ body that takes ONE problem's arrays and an index into them; the batched
 // kernels (sage_robust_registration_batch, sage_match_points_batch: "the batched vote" below) call the same bodies over
 // (problem, block) items, the problems lying as segments in the same allocations (the layout: registration_host.cpp).
 #include "runtime_internal.h"
+#include "registration_math.h"
 
 namespace
 {
@@ -870,6 +872,480 @@ __global__ __launch_bounds__(kBlock) void reg_match_points_batch_kernel(const Ma
 }
 } // namespace
 
+// ---- the finish on the device (SAGE_REG_FINISH_DEVICE, sage_registration_finish_batch): reg_finish_kernel ----
+// sage_registration_finish (registration_host.cpp) for one problem per workgroup of kBlock lanes, in fp64, its expressions
+// literally and in its order; what differs is the order of the sums.  Point / chain TIM i belongs to lane i % kBlock (up to
+// four per lane, ascending).  The phases:
+//   entry        the problem's scale: the first smallest cost over the vote's tile minima (what reg_publish_body reads; every
+//                wave finds it by itself with shuffles, no barrier), or the caller's.  An empty vote: lane 0 writes valid = 0,
+//                the workgroup returns as one before any barrier
+//   TIMs         ts, td = (dst_leaf - dst_i) (1 / scale) into LDS ([3][N] each: a lane reads back only what it wrote), the
+//                squared bounds and the weights in registers
+//   GNC          per iteration two barriers: the nine sums of H = sum (x w) y, then the cost sum w r^2 of the previous weights
+//                (at iteration 0 with the largest r^2).  A sum: a lane's terms ascending, a shuffle tree over the wave, the
+//                four waves ascending out of LDS -- a function of N alone.  Every lane reads the same totals and runs
+//                registration_math.h's 3x3 SVD itself: R, mu, the cost and so every exit (mu <= 0, cost_diff < threshold, the
+//                cap) are the same in all lanes, no barrier sits in a divergent branch
+//   translation  per axis: raw = dst - (scale R) src and its range into LDS (over the TIMs, which are done), the 2 N endpoints
+//                as (reg_key, 2 i + leaving) padded to the power of two P2 >= 2 N, a bitonic sort in LDS (ties by position:
+//                the host's stable sort), then the scale vote's scan (reg_term, reg_block_scan), cost and first smallest
+//                (reg_block_min) with P2 / kBlock consecutive endpoints per lane
+//   outputs      the AND of the three masks compacted ascending (a wave scan of the flags per 256 points, as
+//                reg_match_points_body) into the record's list and, if given, the problem's inliers_dev row (through the
+//                pre-check's map when there is one); the rotation mask; R, t and the counts by lane 0
+// Bounded: 60 Jacobi sweeps, rotation_max_iterations <= SAGE_REG_FINISH_MAX_ITERATIONS, a sort that does not look at the
+// data.  Every index is below N (a payload is a position this workgroup wrote, or the padding).  All stores are plain C++.
+namespace
+{
+constexpr int kFinPerLane = SAGE_REG_MAX_POINTS / kBlock; // points / TIMs per lane: i = tid + kBlock k
+constexpr int kFinEnds = 2 * SAGE_REG_MAX_POINTS;        // endpoints of a translation vote at the cap: one scan tile
+static_assert(kFinEnds == kRegTile && kFinEnds / kBlock == kRegPerLane, "a translation vote fits the scan's tile");
+
+struct RegFinishHost // the finish's pinned record: 128 bytes, then the translation inliers [N] int32, the rotation mask [N] uint8
+{
+  double R[9], t[3];
+  int32_t valid, n_inliers, rotation_iterations, n_rotation_inliers;
+  int32_t pad[4];
+};
+static_assert(sizeof(RegFinishHost) == kRegFinishRecordHeader, "device-visible layout");
+
+struct RegFinishItem // one problem
+{
+  const float *src, *dst, *nb;
+  const RegTileMin *tile_min; // its vote's tile minima [n_tiles]; NULL: the scale is the caller's
+  RegFinishHost *out;
+  int32_t *inliers_dev;   // or NULL
+  const int32_t *map;     // or NULL: inliers_dev receives map[inlier]
+  double noise_bound, scale;
+  int N, n_tiles;
+};
+struct RegFinishBatch
+{
+  RegFinishItem item[SAGE_REG_MAX_BATCH];
+  double sqrt_cbar2, cost_threshold, gnc_factor;
+  int max_iterations, pad;
+};
+static_assert(sizeof(RegFinishBatch) <= 4096, "a kernel argument");
+
+struct alignas(16) RegFinishLds
+{
+  double tim[6 * SAGE_REG_MAX_POINTS]; // ts [3][1024] | td [3][1024]; then keys [2048] u64 | (X, r) [1024] | payload [2048] u32
+  double H[kWaves][9];
+  double cost[kWaves][2];
+  double wave[kWaves][kRegQ];
+  RegMin min[kWaves];
+  int cnt[kWaves];
+};
+static_assert(sizeof(RegFinishLds) == kRegFinishLdsBytes, "what sage_registration_finish_plan reports");
+
+// the vote's first smallest cost, found by every wave on its own (reg_min_before is a strict order: the answer is
+// reg_vote_min's); no LDS, no barrier
+__device__ __forceinline__ RegMin reg_vote_min_wave(const RegTileMin *__restrict__ tile_min, int n_tiles)
+{
+  RegMin m;
+  m.cost = __longlong_as_double(0x7ff0000000000000ll);
+  m.x = 0.0;
+  m.idx = kRegNoIndex;
+  for (int t = threadIdx.x & 63; t < n_tiles; t += 64)
+  {
+    RegMin o;
+    o.cost = tile_min[t].cost;
+    o.x = tile_min[t].x;
+    o.idx = (int)tile_min[t].idx;
+    if (reg_min_before(o, m))
+      m = o;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    RegMin other;
+    other.cost = __shfl_xor(m.cost, o, 64);
+    other.x = __shfl_xor(m.x, o, 64);
+    other.idx = __shfl_xor(m.idx, o, 64);
+    if (reg_min_before(other, m))
+      m = other;
+  }
+  return m;
+}
+
+// the workgroup's number of set flags; valid in every thread.  ends behind a barrier
+__device__ __forceinline__ int reg_block_count(bool flag, int *s_cnt)
+{
+  const int n = __popcll(__ballot(flag));
+  if ((threadIdx.x & 63) == 0)
+    s_cnt[threadIdx.x >> 6] = n;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w)
+    total += s_cnt[w];
+  __syncthreads();
+  return total;
+}
+
+__device__ __forceinline__ void reg_finish_body(const RegFinishItem &it, const RegFinishBatch &G, RegFinishLds &L)
+{
+#pragma clang fp contract(off) // the host's operations one by one
+  using sage_reg::Mat3;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = it.N;
+  const float *__restrict__ src = it.src, *__restrict__ dst = it.dst, *__restrict__ nbf = it.nb;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+
+  // ---- entry
+  double scale = it.scale;
+  if (it.tile_min)
+  {
+    const RegMin vote = reg_vote_min_wave(it.tile_min, it.n_tiles);
+    if (vote.idx == kRegNoIndex) // (the same in every lane: no pair was left in the vote)
+    {
+      if (tid == 0)
+      {
+        it.out->valid = 0;
+        it.out->n_inliers = 0;
+        it.out->rotation_iterations = 0;
+        it.out->n_rotation_inliers = 0;
+      }
+      return;
+    }
+    scale = vote.x;
+  }
+
+  // ---- the chain TIMs
+  double *s_ts = L.tim, *s_td = L.tim + 3 * SAGE_REG_MAX_POINTS;
+  const double inv_scale = 1 / scale;
+  double bsq[kFinPerLane], w[kFinPerLane];
+#pragma unroll
+  for (int k = 0; k < kFinPerLane; ++k)
+  {
+    const int i = tid + k * kBlock;
+    bsq[k] = 0.0;
+    w[k] = 1.0;
+    if (i < n)
+    {
+      const int leaf = i != n - 1 ? i + 1 : 0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+      {
+        s_ts[c * SAGE_REG_MAX_POINTS + i] = (double)src[3 * leaf + c] - (double)src[3 * i + c];
+        s_td[c * SAGE_REG_MAX_POINTS + i] = ((double)dst[3 * leaf + c] - (double)dst[3 * i + c]) * inv_scale;
+      }
+      const double tb = ((double)nbf[leaf] + (double)nbf[i]) * inv_scale;
+      bsq[k] = tb * tb;
+    }
+  }
+  const double gnc_bound = it.noise_bound * (2 / scale);
+  double noise_bound_sq = gnc_bound * gnc_bound;
+  if (noise_bound_sq < 1e-16)
+    noise_bound_sq = 1e-2;
+
+  // ---- GNC-TLS
+  Mat3 R = {{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}};
+  double mu = 1, prev_cost = inf;
+  int iter = 0;
+  for (; iter < G.max_iterations; ++iter)
+  {
+    double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < kFinPerLane; ++k)
+    {
+      const int i = tid + k * kBlock;
+      if (i < n)
+      {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+        {
+          const double xw = s_ts[r * SAGE_REG_MAX_POINTS + i] * w[k];
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            h[3 * r + c] += xw * s_td[c * SAGE_REG_MAX_POINTS + i];
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+    {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1)
+        h[q] += __shfl_down(h[q], o, 64);
+      if (lane == 0)
+        L.H[wave][q] = h[q];
+    }
+    __syncthreads();
+    Mat3 H;
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+    {
+      double s = L.H[0][q];
+#pragma unroll
+      for (int v = 1; v < kWaves; ++v)
+        s += L.H[v][q];
+      H.m[q / 3][q % 3] = s;
+    }
+    R = sage_reg::svd_rot_of(H);
+
+    double rsq[kFinPerLane], part = 0.0, largest = -inf;
+#pragma unroll
+    for (int k = 0; k < kFinPerLane; ++k)
+    {
+      const int i = tid + k * kBlock;
+      rsq[k] = 0.0;
+      if (i < n)
+      {
+        const double x0 = s_ts[i], x1 = s_ts[SAGE_REG_MAX_POINTS + i], x2 = s_ts[2 * SAGE_REG_MAX_POINTS + i];
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+        {
+          const double d = s_td[r * SAGE_REG_MAX_POINTS + i] - (R.m[r][0] * x0 + R.m[r][1] * x1 + R.m[r][2] * x2);
+          s += d * d;
+        }
+        rsq[k] = s;
+        part += w[k] * s;
+        largest = fmax(largest, s);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+    {
+      part += __shfl_down(part, o, 64);
+      largest = fmax(largest, __shfl_down(largest, o, 64));
+    }
+    if (lane == 0)
+    {
+      L.cost[wave][0] = part;
+      L.cost[wave][1] = largest;
+    }
+    __syncthreads();
+    double cost = L.cost[0][0], max_residual = L.cost[0][1];
+#pragma unroll
+    for (int v = 1; v < kWaves; ++v)
+    {
+      cost += L.cost[v][0];
+      max_residual = fmax(max_residual, L.cost[v][1]);
+    }
+    if (iter == 0)
+    {
+      mu = 1 / (2 * max_residual / noise_bound_sq - 1);
+      if (mu <= 0)
+        break;
+    }
+#pragma unroll
+    for (int k = 0; k < kFinPerLane; ++k)
+    {
+      const double th1 = (mu + 1) / mu * bsq[k], th2 = mu / (mu + 1) * bsq[k];
+      if (tid + k * kBlock < n)
+      {
+        if (rsq[k] >= th1)
+          w[k] = 0;
+        else if (rsq[k] <= th2)
+          w[k] = 1;
+        else
+          w[k] = sqrt(bsq[k] * mu * (mu + 1) / rsq[k]) - mu;
+      }
+    }
+    const double cost_diff = fabs(cost - prev_cost);
+    mu = mu * G.gnc_factor;
+    prev_cost = cost;
+    if (cost_diff < G.cost_threshold)
+      break;
+  }
+
+  int32_t *list = reinterpret_cast<int32_t *>(it.out + 1);
+  uint8_t *rotation_mask = reinterpret_cast<uint8_t *>(list + n);
+  int n_rot = 0;
+#pragma unroll
+  for (int k = 0; k < kFinPerLane; ++k)
+  {
+    const int i = tid + k * kBlock;
+    const bool in = i < n && w[k] >= 0.5;
+    if (i < n)
+      rotation_mask[i] = in ? 1 : 0;
+    if (k * kBlock < n) // (uniform)
+      n_rot += reg_block_count(in, L.cnt);
+  }
+
+  // ---- the translation: three scalar votes over the TIMs' LDS
+  __syncthreads();
+  uint64_t *s_k = reinterpret_cast<uint64_t *>(L.tim);
+  double2 *s_xr = reinterpret_cast<double2 *>(L.tim + kFinEnds);
+  uint32_t *s_p = reinterpret_cast<uint32_t *>(L.tim + 2 * kFinEnds);
+  int P2 = 4;
+  while (P2 < 2 * n)
+    P2 <<= 1;
+  const int per = P2 > kBlock ? P2 / kBlock : 1; // consecutive sorted endpoints per lane of the scan
+  double alpha[kFinPerLane], raw[kFinPerLane], t[3];
+  bool mask[kFinPerLane];
+#pragma unroll
+  for (int k = 0; k < kFinPerLane; ++k)
+  {
+    const int i = tid + k * kBlock;
+    mask[k] = i < n;
+    alpha[k] = i < n ? (double)nbf[i] * G.sqrt_cbar2 : 0.0;
+  }
+  for (int r = 0; r < 3; ++r)
+  {
+    const double sR0 = scale * R.m[r][0], sR1 = scale * R.m[r][1], sR2 = scale * R.m[r][2];
+#pragma unroll
+    for (int k = 0; k < kFinPerLane; ++k)
+    {
+      const int i = tid + k * kBlock;
+      raw[k] = 0.0;
+      if (i < n)
+      {
+        raw[k] = (double)dst[3 * i + r] - (sR0 * (double)src[3 * i + 0] + sR1 * (double)src[3 * i + 1] + sR2 * (double)src[3 * i + 2]);
+        s_xr[i] = make_double2(raw[k], alpha[k]);
+        s_k[2 * i] = reg_key(raw[k] - alpha[k]);
+        s_p[2 * i] = 2u * (uint32_t)i;
+        s_k[2 * i + 1] = reg_key(raw[k] + alpha[k]);
+        s_p[2 * i + 1] = 2u * (uint32_t)i + 1u;
+      }
+    }
+    for (int q = 2 * n + tid; q < P2; q += kBlock)
+    {
+      s_k[q] = kRegPadKey;
+      s_p[q] = kRegPadPayload;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1)
+      {
+        for (int x = tid; x < P2 / 2; x += kBlock)
+        {
+          const int lo = ((x & ~(j - 1)) << 1) | (x & (j - 1)), hi = lo | j;
+          const bool up = (lo & k) == 0;
+          const uint64_t ka = s_k[lo], kb = s_k[hi];
+          const uint32_t pa = s_p[lo], pb = s_p[hi];
+          if (reg_after(ka, pa, kb, pb) == up)
+          {
+            s_k[lo] = kb;
+            s_k[hi] = ka;
+            s_p[lo] = pb;
+            s_p[hi] = pa;
+          }
+        }
+        __syncthreads();
+      }
+    // the running sums, the cost at every endpoint, the first smallest (reg_cost_body on one tile)
+    const int at = tid * per;
+    uint32_t pl[kRegPerLane];
+    double v[kRegQ] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < kRegPerLane; ++e)
+    {
+      pl[e] = (e < per && at + e < P2) ? s_p[at + e] : kRegPadPayload;
+      double q[kRegQ];
+      reg_term(pl[e], s_xr, q);
+#pragma unroll
+      for (int c = 0; c < kRegQ; ++c)
+        v[c] += q[c];
+    }
+    double run[kRegQ], total[kRegQ];
+    reg_block_scan(v, run, total, L.wave);
+    const double r_all = total[5];
+    RegMin best;
+    best.cost = inf;
+    best.x = 0.0;
+    best.idx = kRegNoIndex;
+#pragma unroll
+    for (int e = 0; e < kRegPerLane; ++e)
+    {
+      double q[kRegQ];
+      reg_term(pl[e], s_xr, q);
+#pragma unroll
+      for (int c = 0; c < kRegQ; ++c)
+        run[c] += q[c];
+      if (pl[e] != kRegPadPayload)
+      {
+        const double x = run[1] / run[0];
+        const double residual = (run[6] * x) * x + run[4] - (2.0 * run[3]) * x;
+        const double cost = residual + (r_all - run[2]);
+        if (cost < best.cost) // (false for a NaN; the first of equal costs stays)
+        {
+          best.cost = cost;
+          best.x = x;
+          best.idx = at + e;
+        }
+      }
+    }
+    best = reg_block_min(best, L.min);
+    t[r] = best.idx != kRegNoIndex ? best.x : __longlong_as_double(0x7ff8000000000000ll); // (no cost but NaNs: the host's NaN)
+#pragma unroll
+    for (int k = 0; k < kFinPerLane; ++k)
+      mask[k] = mask[k] && fabs(raw[k] - t[r]) <= alpha[k];
+  }
+
+  // ---- the inlier list, ascending
+  int total_in = 0; // the same in every thread
+#pragma unroll
+  for (int k = 0; k < kFinPerLane; ++k)
+  {
+    if (k * kBlock >= n) // (uniform)
+      continue;
+    const int i = tid + k * kBlock;
+    const bool keep = mask[k];
+    int inc = keep ? 1 : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+      const int up = __shfl_up(inc, o, 64);
+      if (lane >= o)
+        inc += up;
+    }
+    if (lane == 63)
+      L.cnt[wave] = inc;
+    __syncthreads();
+    int before = total_in, tile = 0;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v)
+    {
+      if (v < wave)
+        before += L.cnt[v];
+      tile += L.cnt[v];
+    }
+    if (keep)
+    {
+      const int m = before + inc - 1;
+      list[m] = i;
+      if (it.inliers_dev)
+        it.inliers_dev[m] = it.map ? it.map[i] : i;
+    }
+    total_in += tile;
+    __syncthreads(); // (L.cnt is written again)
+  }
+  if (tid == 0)
+  {
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+      it.out->R[q] = R.m[q / 3][q % 3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      it.out->t[q] = t[q];
+    it.out->valid = 1;
+    it.out->n_inliers = total_in;
+    it.out->rotation_iterations = iter;
+    it.out->n_rotation_inliers = n_rot;
+  }
+}
+
+// grid: the voting problems.  ticket NULL: it comes behind this launch in the stream (ws_ticket_wait); else one workgroup,
+// which posts it itself
+__global__ __launch_bounds__(kBlock) void reg_finish_kernel(const RegFinishBatch G, volatile unsigned *ticket, unsigned epoch)
+{
+  __shared__ RegFinishLds L;
+  reg_finish_body(G.item[blockIdx.x], G, L);
+  __threadfence_system();
+  if (!ticket)
+    return;
+  __syncthreads(); // (every lane arrives: the body's early return is the whole workgroup's)
+  if (threadIdx.x == 0)
+  {
+    __threadfence_system();
+    *ticket = epoch;
+  }
+}
+} // namespace
+
 // a problem's published record -> its result (zeroed by the caller): the counts, then, if the vote was not empty, the host
 // finish, which leaves the translation inliers behind the points in the record
 static int reg_finish_record(RegHost *h, int N, const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host)
@@ -892,10 +1368,24 @@ static int reg_finish_record(RegHost *h, int N, const SageRegistrationParams *p,
   return SAGE_OK;
 }
 
+// what a vote leaves to a finish kernel that follows it in the stream (SAGE_REG_FINISH_DEVICE).  Given to a vote, the vote
+// reserves extra_pinned bytes behind its own records, does not wait, and says where each segment's tile minima are
+struct RegVoteTail
+{
+  size_t extra_pinned;
+  const RegTileMin *tile_min[SAGE_REG_MAX_BATCH];
+  int n_tiles[SAGE_REG_MAX_BATCH];
+};
+
+// SAGE_REG_FINISH_DEVICE (below): a plan's votes, reg_finish_kernel behind them, one wait, the results out of the records
+static int registration_device(SageWorkspace *ws, const RegBatchPlan &plan, const SageRegistrationProblem *probs,
+                               const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host, int inliers_stride,
+                               const int32_t *const *inlier_map, int *launches_out);
+
 // one problem's vote (N >= 2): reserve, launch, wait for the ticket the publish kernel posts; the record is then at the
-// start of ws->reg_host.  *launches (may be NULL): how many kernels that took
+// start of ws->reg_host.  *launches (may be NULL): how many kernels that took.  tail (may be NULL): above
 static int reg_vote_single(SageWorkspace *ws, const float *src_dev, const float *dst_dev, const float *noise_bounds_dev, int N, double cbar2,
-                           int *launches)
+                           int *launches, RegVoteTail *tail = nullptr)
 {
   int rc;
   const int n_pairs = N * (N - 1) / 2;
@@ -911,7 +1401,8 @@ static int reg_vote_single(SageWorkspace *ws, const float *src_dev, const float 
   if ((rc = ws->reg_keys.reserve((size_t)P * sizeof(uint64_t))) || (rc = ws->reg_payload.reserve((size_t)P * sizeof(uint32_t))) ||
       (rc = ws->reg_pairs.reserve((size_t)n_pairs * sizeof(double2))) ||
       (rc = ws->reg_tiles.reserve(sums_bytes + offs_bytes + min_bytes + 4 * sizeof(int))) ||
-      (rc = ws->reg_host.reserve(offsetof(RegHost, pts) + (size_t)N * (7 * sizeof(float) + sizeof(int32_t))))) // (every earlier call has been waited for)
+      (rc = ws->reg_host.reserve(offsetof(RegHost, pts) + (size_t)N * (7 * sizeof(float) + sizeof(int32_t)) +
+                                 (tail ? tail->extra_pinned : 0)))) // (every earlier call has been waited for)
     return rc;
   uint64_t *keys = ws->reg_keys.as<uint64_t>();
   uint32_t *payload = ws->reg_payload.as<uint32_t>();
@@ -956,6 +1447,12 @@ static int reg_vote_single(SageWorkspace *ws, const float *src_dev, const float 
   SAGE_HIP(hipGetLastError());
   if (launches)
     *launches = registration_sort_launches(P, tile) + kRegSingleFixedLaunches;
+  if (tail) // (the publish kernel's ticket is nobody's: the finish kernel posts the one that is awaited)
+  {
+    tail->tile_min[0] = tile_min;
+    tail->n_tiles[0] = n_tiles;
+    return SAGE_OK;
+  }
   return ws_ticket_await(ws, epoch);
 }
 
@@ -968,9 +1465,20 @@ extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev,
   int rc;
   if ((rc = registration_check_params(p)))
     return rc;
+  if (ws->reg_finish_mode == SAGE_REG_FINISH_DEVICE && p->rotation_max_iterations > SAGE_REG_FINISH_MAX_ITERATIONS)
+    return SAGE_E_UNSUPPORTED; // (the kernel's loops are bounded)
   std::memset(res, 0, sizeof(*res));
   if (N < 2)
     return SAGE_OK; // (valid = 0: the reference never calls the solver there)
+  if (ws->reg_finish_mode == SAGE_REG_FINISH_DEVICE) // (a batch of one: the batch's contract holds by construction)
+  {
+    SageRegistrationProblem q{src_dev, dst_dev, noise_bounds_dev, N, p->noise_bound, inliers_dev};
+    const int32_t one = N;
+    RegBatchPlan plan;
+    registration_batch_plan(&one, 1, registration_sort_tile(), &plan);
+    int launches;
+    return registration_device(ws, plan, &q, p, res, inliers_host, N, nullptr, &launches);
+  }
   if ((rc = reg_vote_single(ws, src_dev, dst_dev, noise_bounds_dev, N, p->cbar2, nullptr)))
     return rc;
   RegHost *h = ws->reg_host.as<RegHost>();
@@ -990,12 +1498,12 @@ extern "C" int sage_robust_registration(SageWorkspace *ws, const float *src_dev,
 // the votes of a plan's segments (two or more): reserve, launch, one ticket behind the publish launch, wait.  record [plan.n]:
 // where each segment's pinned record is
 static int reg_vote_batch(SageWorkspace *ws, const RegBatchPlan &plan, const SageRegistrationProblem *probs, double cbar2,
-                          RegHost **record, int *launches_out)
+                          RegHost **record, int *launches_out, RegVoteTail *tail = nullptr)
 {
   int rc;
   if ((rc = ws->reg_keys.reserve((size_t)plan.keys_bytes)) || (rc = ws->reg_payload.reserve((size_t)plan.payload_bytes)) ||
       (rc = ws->reg_pairs.reserve((size_t)plan.pairs_bytes)) || (rc = ws->reg_tiles.reserve((size_t)plan.tiles_bytes)) ||
-      (rc = ws->reg_host.reserve((size_t)plan.pinned_bytes))) // (every earlier call has been waited for)
+      (rc = ws->reg_host.reserve((size_t)plan.pinned_bytes + (tail ? tail->extra_pinned : 0)))) // (every earlier call has been waited for)
     return rc;
   uint64_t *keys = ws->reg_keys.as<uint64_t>();
   uint32_t *payload = ws->reg_payload.as<uint32_t>();
@@ -1058,7 +1566,116 @@ static int reg_vote_batch(SageWorkspace *ws, const RegBatchPlan &plan, const Sag
   *launches_out = launches;
   for (int i = 0; i < plan.n; ++i)
     record[i] = Q.host[i];
+  if (tail) // (the ticket, counted above, comes behind the finish kernel)
+  {
+    for (int i = 0; i < plan.n; ++i)
+    {
+      // (reg_segment_rows: [n_tiles] sums | [n_tiles + 1] offsets | [n_tiles] minima)
+      tail->tile_min[i] = reinterpret_cast<const RegTileMin *>(tiles + plan.seg[i].rows0 +
+                                                               (2 * (size_t)plan.seg[i].n_tiles + 1) * kRegRow * sizeof(double));
+      tail->n_tiles[i] = plan.seg[i].n_tiles;
+    }
+    return SAGE_OK;
+  }
   return ws_ticket_wait(ws);
+}
+
+// the finish kernel over n items: one launch and the ticket's, or (own_ticket: one workgroup) one launch that posts it; waits
+static int reg_finish_launch(SageWorkspace *ws, const RegFinishBatch &G, int n, bool own_ticket)
+{
+  if (own_ticket)
+  {
+    const unsigned epoch = ws_ticket_next(ws);
+    hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(kBlock), 0, ws->stream, G, &ws->hs()->ticket, epoch);
+    SAGE_HIP(hipGetLastError());
+    return ws_ticket_await(ws, epoch);
+  }
+  hipLaunchKernelGGL(reg_finish_kernel, dim3(n), dim3(kBlock), 0, ws->stream, G, (volatile unsigned *)nullptr, 0u);
+  SAGE_HIP(hipGetLastError());
+  return ws_ticket_wait(ws);
+}
+
+static void reg_finish_params(const SageRegistrationParams *p, RegFinishBatch *G)
+{
+  G->sqrt_cbar2 = std::sqrt(p->cbar2);
+  G->cost_threshold = p->rotation_cost_threshold;
+  G->gnc_factor = p->rotation_gnc_factor;
+  G->max_iterations = p->rotation_max_iterations;
+}
+
+// a finish record -> the finish's fields of a result (zeroed by the caller), the list and the rotation mask
+static void reg_finish_read(const RegFinishHost *f, int N, SageRegistrationResult *res, int32_t *inliers_host, uint8_t *rotation_mask)
+{
+  res->valid = f->valid;
+  if (!f->valid)
+    return;
+  std::memcpy(res->R, f->R, sizeof(res->R));
+  std::memcpy(res->t, f->t, sizeof(res->t));
+  res->n_inliers = f->n_inliers;
+  res->rotation_iterations = f->rotation_iterations;
+  res->n_rotation_inliers = f->n_rotation_inliers;
+  const int32_t *list = reinterpret_cast<const int32_t *>(f + 1);
+  if (inliers_host)
+    std::memcpy(inliers_host, list, (size_t)f->n_inliers * sizeof(int32_t));
+  if (rotation_mask)
+    std::memcpy(rotation_mask, list + N, (size_t)N);
+}
+
+static int registration_device(SageWorkspace *ws, const RegBatchPlan &plan, const SageRegistrationProblem *probs,
+                               const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host, int inliers_stride,
+                               const int32_t *const *inlier_map, int *launches_out)
+{
+  int rc, launches = 0;
+  RegVoteTail tail{};
+  size_t off[SAGE_REG_MAX_BATCH];
+  for (int i = 0; i < plan.n; ++i)
+  {
+    off[i] = tail.extra_pinned;
+    tail.extra_pinned += (size_t)reg_finish_record_bytes(plan.seg[i].N);
+  }
+  RegHost *seg_record[SAGE_REG_MAX_BATCH];
+  if (plan.n == 1)
+  {
+    const SageRegistrationProblem &q = probs[plan.seg[0].row];
+    rc = reg_vote_single(ws, q.src_dev, q.dst_dev, q.noise_bounds_dev, q.N, p->cbar2, &launches, &tail);
+    seg_record[0] = ws->reg_host.as<RegHost>();
+  }
+  else
+    rc = reg_vote_batch(ws, plan, probs, p->cbar2, seg_record, &launches, &tail);
+  if (rc)
+    return rc;
+  char *fin = ws->reg_host.as<char>() + plan.pinned_bytes; // (the finish records: behind the votes')
+  RegFinishBatch G{};
+  reg_finish_params(p, &G);
+  for (int i = 0; i < plan.n; ++i)
+  {
+    const int b = plan.seg[i].row;
+    RegFinishItem &it = G.item[i];
+    it.src = probs[b].src_dev; it.dst = probs[b].dst_dev; it.nb = probs[b].noise_bounds_dev;
+    it.tile_min = tail.tile_min[i]; it.n_tiles = tail.n_tiles[i];
+    it.out = reinterpret_cast<RegFinishHost *>(fin + off[i]);
+    it.inliers_dev = probs[b].inliers_dev;
+    it.map = inlier_map ? inlier_map[b] : nullptr;
+    it.noise_bound = probs[b].noise_bound;
+    it.N = probs[b].N;
+  }
+  if ((rc = reg_finish_launch(ws, G, plan.n, plan.n == 1)))
+    return rc;
+  *launches_out = launches + 1;
+  for (int i = 0; i < plan.n; ++i)
+  {
+    const int b = plan.seg[i].row;
+    const RegHost *h = seg_record[i];
+    res[b].n_pairs = h->n_pairs;
+    res[b].n_degenerate_pairs = h->n_degenerate;
+    if (!h->vote_valid)
+      continue; // (valid = 0: no pair was left in the vote)
+    reg_finish_read(G.item[i].out, probs[b].N, &res[b], inliers_host ? inliers_host + (size_t)b * inliers_stride : nullptr, nullptr);
+    res[b].scale = h->scale;
+    res[b].n_scale_inlier_pairs = h->n_scale_inliers;
+    res[b].scale_cost = h->scale_cost;
+  }
+  return SAGE_OK;
 }
 
 // the batch: plan, reserve, launch, wait once, finish per problem in row order, then the inliers_dev rows in one launch.
@@ -1078,6 +1695,9 @@ static int registration_batch(SageWorkspace *ws, const SageRegistrationProblem *
   pp.noise_bound = 1.0; // (replaced per problem below: the caller's value is not read)
   if ((rc = registration_check_params(&pp)))
     return rc;
+  const bool device = ws->reg_finish_mode == SAGE_REG_FINISH_DEVICE;
+  if (device && p->rotation_max_iterations > SAGE_REG_FINISH_MAX_ITERATIONS)
+    return SAGE_E_UNSUPPORTED; // (the kernel's loops are bounded)
   int32_t Ns[SAGE_REG_MAX_BATCH];
   int max_N = 0;
   for (int b = 0; b < B; ++b)
@@ -1100,6 +1720,8 @@ static int registration_batch(SageWorkspace *ws, const SageRegistrationProblem *
   registration_batch_plan(Ns, B, registration_sort_tile(), &plan);
   if (plan.n == 0)
     return SAGE_OK; // (nothing votes: valid = 0 everywhere, no launch)
+  if (device)
+    return registration_device(ws, plan, probs, p, res, inliers_host, inliers_stride, inlier_map, &ws->reg_batch_launches);
   // a batch with ONE voting problem takes the single call's path (its publish kernel posts the ticket itself: one launch
   // fewer, and the batch of one is then no slower than the call it replaces -- measured: scripts/registration_batch_bench.py)
   RegHost *seg_record[SAGE_REG_MAX_BATCH];
@@ -1156,6 +1778,86 @@ extern "C" int sage_robust_registration_batch(SageWorkspace *ws, const SageRegis
 }
 
 extern "C" int sage_robust_registration_batch_launches(const SageWorkspace *ws) { return ws ? ws->reg_batch_launches : 0; }
+
+extern "C" int sage_workspace_set_registration_finish(SageWorkspace *ws, int mode)
+{
+  if (!ws || (mode != SAGE_REG_FINISH_HOST && mode != SAGE_REG_FINISH_DEVICE))
+    return SAGE_E_INVALID;
+  ws->reg_finish_mode = mode;
+  return SAGE_OK;
+}
+
+extern "C" int sage_workspace_registration_finish(const SageWorkspace *ws) { return ws ? ws->reg_finish_mode : SAGE_REG_FINISH_HOST; }
+
+extern "C" int sage_registration_finish_batch(SageWorkspace *ws, const SageRegistrationProblem *probs, int B, const double *scales,
+                                              const SageRegistrationParams *p, SageRegistrationResult *res, int32_t *inliers_host,
+                                              int inliers_stride, uint8_t *rotation_masks)
+{
+  if (B < 0 || B > SAGE_REG_MAX_BATCH)
+    return SAGE_E_INVALID;
+  if (B == 0)
+    return SAGE_OK;
+  if (!ws || !probs || !scales || !p || !res)
+    return SAGE_E_INVALID;
+  int rc;
+  SageRegistrationParams pp = *p;
+  pp.noise_bound = 1.0; // (replaced per problem: the caller's value is not read)
+  if ((rc = registration_check_params(&pp)))
+    return rc;
+  if (p->rotation_max_iterations > SAGE_REG_FINISH_MAX_ITERATIONS)
+    return SAGE_E_UNSUPPORTED; // (the kernel's loops are bounded)
+  int max_N = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    const SageRegistrationProblem &q = probs[b];
+    if (q.N < 0 || q.N > SAGE_REG_MAX_POINTS)
+      return SAGE_E_INVALID;
+    if (q.N >= 2 && (!q.src_dev || !q.dst_dev || !q.noise_bounds_dev || !(q.noise_bound > 0) || !std::isfinite(q.noise_bound)))
+      return SAGE_E_INVALID;
+    max_N = std::max(max_N, (int)q.N);
+  }
+  if ((inliers_host || rotation_masks) && inliers_stride < max_N)
+    return SAGE_E_INVALID;
+  RegFinishBatch G{};
+  reg_finish_params(p, &G);
+  int row[SAGE_REG_MAX_BATCH], n = 0;
+  size_t off[SAGE_REG_MAX_BATCH], bytes = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    std::memset(&res[b], 0, sizeof(res[b]));
+    if (probs[b].N < 2)
+      continue; // (takes no part)
+    off[n] = bytes;
+    bytes += (size_t)reg_finish_record_bytes(probs[b].N);
+    row[n++] = b;
+  }
+  if (n == 0)
+    return SAGE_OK;
+  if ((rc = ws->reg_host.reserve(bytes))) // (every earlier call has been waited for)
+    return rc;
+  char *fin = ws->reg_host.as<char>();
+  for (int i = 0; i < n; ++i)
+  {
+    const int b = row[i];
+    RegFinishItem &it = G.item[i];
+    it.src = probs[b].src_dev; it.dst = probs[b].dst_dev; it.nb = probs[b].noise_bounds_dev;
+    it.out = reinterpret_cast<RegFinishHost *>(fin + off[i]);
+    it.inliers_dev = probs[b].inliers_dev;
+    it.noise_bound = probs[b].noise_bound;
+    it.scale = scales[b];
+    it.N = probs[b].N;
+  }
+  if ((rc = reg_finish_launch(ws, G, n, false)))
+    return rc;
+  for (int i = 0; i < n; ++i)
+  {
+    const int b = row[i];
+    reg_finish_read(G.item[i].out, probs[b].N, &res[b], inliers_host ? inliers_host + (size_t)b * inliers_stride : nullptr,
+                    rotation_masks ? rotation_masks + (size_t)b * inliers_stride : nullptr);
+    res[b].scale = scales[b];
+  }
+  return SAGE_OK;
+}
 
 // the scalars of a gather (the pointers are left to the caller)
 static MatchPointsParams match_points_scalars(float depth_divisor0, const SageCamera *cam, int K, int W, float noise_multiplier,

@@ -8,7 +8,8 @@
 //     exit at |cost - previous| < threshold; the mask is weight >= 0.5
 //   the translation: per axis one scalar vote (ScalarTLSEstimator::estimate, :21-88) over dst - scale R src with the bounds
 //     nb sqrt(cbar2) (:361-388), and the AND of the three masks
-// All in fp64, sums sequential in the reference's order.  svdRot's 3x3 SVD is a one-sided Jacobi here (Eigen's JacobiSVD
+// All in fp64, sums sequential in the reference's order.  svdRot's 3x3 SVD (registration_math.h, shared with the device
+// finish, reg_finish_kernel in registration.hip) is a one-sided Jacobi here (Eigen's JacobiSVD
 // there): V diag(1, 1, det U det V) U^T is the same matrix whenever H has rank >= 2; at rank 1 (N = 2: the two chain TIMs
 // are antiparallel) the rotation about the one direction is open in both, and each picks its own.
 #include <algorithm>
@@ -19,122 +20,15 @@
 #include <utility>
 #include <vector>
 
+#include "registration_math.h"
 #include "registration_plan.h"
 #include "sage_ba.h"
 
 namespace
 {
-struct Mat3
-{
-  double m[3][3];
-};
+using sage_reg::Mat3;
 
-inline void cross3(const double *a, const double *b, double *c)
-{
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-inline double det3(const Mat3 &A)
-{
-  return A.m[0][0] * (A.m[1][1] * A.m[2][2] - A.m[1][2] * A.m[2][1]) - A.m[0][1] * (A.m[1][0] * A.m[2][2] - A.m[1][2] * A.m[2][0]) +
-         A.m[0][2] * (A.m[1][0] * A.m[2][1] - A.m[1][1] * A.m[2][0]);
-}
-
-// H = U S V^T by one-sided Jacobi on the columns of A = H (A V' = U S): columns ordered by descending norm; U's columns of a
-// vanishing singular value are completed to a right-handed frame (det U = +1 whenever a column is completed)
-void svd3(const Mat3 &H, Mat3 &U, Mat3 &V)
-{
-  double A[3][3], Vm[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c)
-      A[r][c] = H.m[r][c];
-  for (int sweep = 0; sweep < 60; ++sweep)
-  {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q)
-      {
-        double alpha = 0, beta = 0, gamma = 0;
-        for (int r = 0; r < 3; ++r)
-        {
-          alpha += A[r][p] * A[r][p];
-          beta += A[r][q] * A[r][q];
-          gamma += A[r][p] * A[r][q];
-        }
-        if (gamma == 0.0 || std::fabs(gamma) <= 1e-300)
-          continue;
-        off = std::max(off, std::fabs(gamma) / std::sqrt(alpha * beta));
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
-        for (int r = 0; r < 3; ++r)
-        {
-          const double ap = A[r][p], aq = A[r][q];
-          A[r][p] = c * ap - s * aq;
-          A[r][q] = s * ap + c * aq;
-          const double vp = Vm[r][p], vq = Vm[r][q];
-          Vm[r][p] = c * vp - s * vq;
-          Vm[r][q] = s * vp + c * vq;
-        }
-      }
-    if (!(off > 1e-16)) // (also leaves on a NaN)
-      break;
-  }
-  double sv[3];
-  int order[3] = {0, 1, 2};
-  for (int c = 0; c < 3; ++c)
-    sv[c] = std::sqrt(A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c]);
-  std::stable_sort(order, order + 3, [&](int a, int b) { return sv[a] > sv[b]; });
-  double u[3][3]; // u[k]: the k-th left vector
-  const double tiny = sv[order[0]] * 1e-13;
-  int rank = 0;
-  for (int k = 0; k < 3; ++k)
-  {
-    const int c = order[k];
-    for (int r = 0; r < 3; ++r)
-      V.m[r][k] = Vm[r][c];
-    if (sv[c] > tiny && sv[c] > 0.0 && rank == k)
-    {
-      for (int r = 0; r < 3; ++r)
-        u[k][r] = A[r][c] / sv[c];
-      rank = k + 1;
-    }
-  }
-  if (rank == 0)
-  {
-    u[0][0] = 1; u[0][1] = 0; u[0][2] = 0;
-    u[1][0] = 0; u[1][1] = 1; u[1][2] = 0;
-  }
-  else if (rank == 1)
-  {
-    // any unit vector perpendicular to u[0]: Gram-Schmidt on the axis u[0] is least aligned with
-    int ax = 0;
-    for (int r = 1; r < 3; ++r)
-      if (std::fabs(u[0][r]) < std::fabs(u[0][ax]))
-        ax = r;
-    double e[3] = {0, 0, 0};
-    e[ax] = 1.0;
-    const double d = u[0][ax];
-    double n = 0;
-    for (int r = 0; r < 3; ++r)
-    {
-      u[1][r] = e[r] - d * u[0][r];
-      n += u[1][r] * u[1][r];
-    }
-    n = std::sqrt(n);
-    for (int r = 0; r < 3; ++r)
-      u[1][r] /= n;
-  }
-  if (rank < 3)
-    cross3(u[0], u[1], u[2]);
-  for (int k = 0; k < 3; ++k)
-    for (int r = 0; r < 3; ++r)
-      U.m[r][k] = u[k][r];
-}
-
-// utils.h:121-136: H = X diag(W) Y^T, R = V U^T with V's last column negated when det U det V < 0
+// utils.h:121-136: H = X diag(W) Y^T, R = V U^T with V's last column negated when det U det V < 0 (registration_math.h)
 Mat3 svd_rot(const std::vector<double> &X, const std::vector<double> &Y, const std::vector<double> &W, int n)
 {
   Mat3 H;
@@ -146,16 +40,7 @@ Mat3 svd_rot(const std::vector<double> &X, const std::vector<double> &Y, const s
         s += (X[3 * i + r] * W[i]) * Y[3 * i + c];
       H.m[r][c] = s;
     }
-  Mat3 U, V;
-  svd3(H, U, V);
-  if (det3(U) * det3(V) < 0)
-    for (int r = 0; r < 3; ++r)
-      V.m[r][2] = -V.m[r][2];
-  Mat3 R;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c)
-      R.m[r][c] = V.m[r][0] * U.m[c][0] + V.m[r][1] * U.m[c][1] + V.m[r][2] * U.m[c][2];
-  return R;
+  return sage_reg::svd_rot_of(H);
 }
 
 bool params_ok(const SageRegistrationParams *p)
@@ -271,6 +156,30 @@ extern "C" int sage_robust_registration_batch_plan(const int32_t *N, int B, int6
   if (order)
     for (int b = 0; b < B; ++b)
       order[b] = b < plan.n ? plan.seg[b].row : -1;
+  return SAGE_OK;
+}
+
+extern "C" int sage_registration_finish_plan(const int32_t *N, int B, int32_t *launches, int64_t *pinned_bytes, int32_t *lds_bytes,
+                                             int32_t *workgroups)
+{
+  if (B < 0 || B > SAGE_REG_MAX_BATCH || (B > 0 && !N))
+    return SAGE_E_INVALID;
+  for (int b = 0; b < B; ++b)
+    if (N[b] < 0 || N[b] > SAGE_REG_MAX_POINTS)
+      return SAGE_E_INVALID;
+  RegBatchPlan plan;
+  registration_batch_plan(N, B, registration_sort_tile(), &plan);
+  int64_t pinned = plan.pinned_bytes;
+  for (int i = 0; i < plan.n; ++i)
+    pinned += reg_finish_record_bytes(plan.seg[i].N);
+  if (launches)
+    *launches = plan.n ? plan.launches + 1 : 0;
+  if (pinned_bytes)
+    *pinned_bytes = pinned;
+  if (lds_bytes)
+    *lds_bytes = plan.n ? kRegFinishLdsBytes : 0;
+  if (workgroups)
+    *workgroups = plan.n;
   return SAGE_OK;
 }
 

@@ -38,6 +38,12 @@ struct RegBatchPlan
 constexpr int kRegSingleFixedLaunches = 6; // pairs, sums, offsets, cost, count, publish (which posts the ticket)
 constexpr int kRegBatchFixedLaunches = 7;  // two or more voting problems: the ticket is a launch of its own
 
+// the finish on the device (SAGE_REG_FINISH_DEVICE: reg_finish_kernel in registration.hip): one workgroup per voting problem,
+// one launch behind the vote's, a pinned record of its own per problem behind the votes' records
+constexpr int kRegFinishRecordHeader = 128; // R, t, the four counts
+constexpr int kRegFinishLdsBytes = 49840;   // 48 KiB TIMs (later the translation's tile) + 688 of reduction rows
+constexpr int64_t reg_finish_record_bytes(int N) { return kRegFinishRecordHeader + 8 * (int64_t)N; } // | list [N] int32 | mask [N] uint8 |
+
 // endpoints per workgroup of the sort's LDS stages: 1024, or what SAGE_REG_SORT_TILE names (1024, 2048, 4096)
 int registration_sort_tile();
 // the launches of one bitonic sort over P endpoints with that tile (P >= 4096 >= tile, powers of two)

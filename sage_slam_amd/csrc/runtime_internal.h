@@ -244,6 +244,9 @@ struct SageWorkspace
   DevBuf reg_keys, reg_payload, reg_pairs, reg_tiles;
   PinnedBuf reg_host;
   int reg_batch_launches = 0;
+  // where the solves' finish runs (sage_workspace_set_registration_finish): SAGE_REG_FINISH_HOST, or _DEVICE: reg_finish_kernel
+  // behind the vote, its records behind the votes' in reg_host
+  int reg_finish_mode = 0;
   // batched cycle match (sage_cycle_match_batch: match_batch.hip): the slices' (response, pixel) pairs of both passes
   // [2][B][S][K], the counter of finished workgroups (zero between calls), the pinned counts [SAGE_MATCH_MAX_BATCH]; the
   // device's CU count (0: not asked yet) and the number of slices of the last call
