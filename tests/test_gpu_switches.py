@@ -10,8 +10,32 @@ import sys
 import numpy as np
 import pytest
 
+from tests import metric_cases as mc
+from tests import system_metric as sm
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _metric_summary():
+    from tests.conftest import summary_line
+    yield
+    for ln in sm.summary_lines("border taps and mixed sampler paths"):
+        summary_line(ln)
+
+
+def _metric_checks(orc, name, w, v, label):
+    """entry by entry (tests/system_metric.py): every edge the run handed out against the fp64 oracle, and the merged
+    linearize's K*B system against the separate kernels' -- next to the whole-matrix bars, which see the pose block only"""
+    K, CS = len(w.keyframes), w.CS
+    for (t, l, d), o64 in mc.named_window_oracle(orc, name, "f64").items():
+        if o64["num_inliers"] == 0:
+            continue
+        e = 2 * l + d
+        sm.check(dict(AtA=v[f"AtA_{t}_{e}"], Atb=v[f"Atb_{t}_{e}"]), o64, ("photometric", "geometric")[t], f"{label} edge {e}")
+    sm.check(mc.dense_system(v["merged"], K, w.links, CS), mc.dense_system(v["packed"], K, w.links, CS), "window",
+             f"{label} merged vs packed", segs=sm.seg_window(K, CS), against="the separate kernels' system")
 
 SNIPPET = """
 import sys, numpy as np
@@ -106,6 +130,8 @@ def test_border_taps_with_full_mask_match_oracle(tmp_path, orc, H, W, seed):
     from sage_slam_amd import synth
     from tests.helpers import oracle_geo, oracle_photo, rel
     w = synth.make_window(K=4, H=H, W=W, FS=16, CS=32, L=4, seed=seed, border=0, erode=0, pose_noise=2.0, back_links=3)
+    wname = f"border_{H}x{W}"
+    assert mc.WINDOWS[wname] == dict(K=4, H=H, W=W, FS=16, CS=32, L=4, seed=seed, border=0, erode=0, pose_noise=2.0, back_links=3)
     assert w.mask.min() == 1.0 and w.keyframes[0].homo.shape[0] == H * W
     edges = [(k0, k1) for (a, b) in w.links for (k0, k1) in ((a, b), (b, a))]
     crossers = [_edge_crossers(w, k0, k1) for k0, k1 in edges]
@@ -134,6 +160,7 @@ def test_border_taps_with_full_mask_match_oracle(tmp_path, orc, H, W, seed):
         tot = sum(o["error"] for o in oracle.values())
         assert float(v["packed"][-4] + v["packed"][-3]) == pytest.approx(tot, rel=2e-5)
         assert rel(v["merged"][:-4], v["packed"][:-4]) < 2e-6 and np.array_equal(v["merged"][-2:], v["packed"][-2:])
+        _metric_checks(orc, wname, w, v, f"border=0 {H}x{W} {name}")
         assert v["lm"][2] == 1 and v["lm"][1] < v["lm"][0]
         from tests.conftest import summary_line
         summary_line(f"[border=0 {H}x{W} {name}] {sum(c for c, _ in crossers)} inliers with a level-0 tap outside the image over "
@@ -184,6 +211,8 @@ def test_mixed_sampler_paths_inside_a_workgroup_match_oracle(tmp_path, orc):
     w = synth.make_window(K=4, H=H, W=W, FS=16, CS=32, L=4, seed=seed, border=2, erode=5, pose_noise=2.0, back_links=3)
     for k, z in enumerate(dz):
         w.keyframes[k].t[2] += np.float32(z)
+    assert dz == mc.MIXED_SAMPLER_DZ and mc.WINDOWS["mixed_sampler"] == dict(K=4, H=H, W=W, FS=16, CS=32, L=4, seed=seed, border=2,
+                                                                             erode=5, pose_noise=2.0, back_links=3)
     edges = [(k0, k1) for (a, b) in w.links for (k0, k1) in ((a, b), (b, a))]
     # the case under test exists: groups of four x-adjacent tiles (= the four waves of a workgroup's sub-tile) with both kinds
     mixed = dead = 0
@@ -214,6 +243,7 @@ def test_mixed_sampler_paths_inside_a_workgroup_match_oracle(tmp_path, orc):
         worst = [max(worst[0], ra), max(worst[1], rb)]
         assert ra < 2e-5 and rb < 2e-5, (t, e, ra, rb)
     assert rel(v["merged"][:-4], v["packed"][:-4]) < 2e-6 and np.array_equal(v["merged"][-2:], v["packed"][-2:])
+    _metric_checks(orc, "mixed_sampler", w, v, "mixed sampler paths")
     from tests.conftest import summary_line
     summary_line(f"[mixed sampler paths] {mixed} sub-tiles with staged and texture-path waves side by side, {dead} tiles without "
                  f"inliers over {len(edges)} edges; worst per-edge rel-L2 vs the oracle: AtA {worst[0]:.1e} Atb {worst[1]:.1e}")

@@ -15,6 +15,8 @@ Bars.  Inlier count: exact.  AtA, Atb: rel-L2 against the fp64 oracle below max(
 distance from fp64 on the case); error: relative, below max(1e-5, 4 x the fp32 oracle's).  2e-5 / 1e-5 are the project's
 bars (tests/test_gpu_parity.py); the kernel sums in another order with contracted multiply-adds, so it gets those or
 four times the reference's own rounding, whichever is larger.  A wrong tap, weight or lane moves these by 1e-3 or more.
+Next to them, entry by entry: dist_A / dist_b of tests/system_metric.py against the fp64 oracle under the bars of the
+"tracker_photometric" family (D = 6 and D = 7: the 7-dof scale row is small next to the pose rows in the norms above).
 
 Measured on an MI355X: the kernel's distance from the fp64 oracle as a share of its bar, the worse of dof 6 and 7
 (the bar was the project's 2e-5 / 1e-5 on every case: the fp32 oracle is 1e-8 .. 2e-6 from fp64 here)
@@ -52,6 +54,7 @@ import numpy as np
 import pytest
 
 from tests import edge_scenes as es
+from tests import system_metric as sm
 from tests.conftest import summary_line
 from tests.helpers import rel
 
@@ -65,6 +68,13 @@ def capi():
     from sage_slam_amd import capi as c
     c.lib()
     return c
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _metric_summary():
+    yield
+    for ln in sm.summary_lines("tracker edge shapes"):
+        summary_line(ln)
 
 
 @pytest.fixture(scope="module")
@@ -107,6 +117,10 @@ def test_tracker_kernels_at_edge_shapes(capi, ws, orc, case):
             worst[k] = max(worst[k], got[k] / bars[k])
             if not got[k] < bars[k]:
                 failures.append(f"dof {dof} {k}: {got[k]:.3e} against a bar of {bars[k]:.3e}")
+        try:
+            sm.check(h, o64, "tracker_photometric", f"{es.tracker_case_id(case)} dof {dof}")
+        except AssertionError as e:
+            failures.append(str(e))
         if h["num_inliers"] != o64["num_inliers"] or hn != n64:
             failures.append(f"dof {dof} inliers: {h['num_inliers']} / {hn} against {o64['num_inliers']} / {n64}")
     summary_line(f"tracker shapes {es.tracker_case_id(case):24s} share of the bar: AtA {worst['AtA']:.3f}  Atb {worst['Atb']:.3f}  "

@@ -5,7 +5,8 @@ windows, and the graph itself solved as a window.
 
 Per-term bars: 4 x the fp32 restatement's own distance from the fp64 one over the same terms, at least 2e-6, never above the
 keypoint terms' 2e-5 / 2e-5 / 1e-5 (graph_term_ref.parity_bars).  The LM-delta bar is the project's 1e-4; the assembly bar
-is the loop-graph test's 1e-10.
+is the loop-graph test's 1e-10.  Term by term and entry by entry: dist_A / dist_b of tests/system_metric.py against the fp64
+restatement under the "graph_terms" bars (measured: 3.6e-7 / 9.9e-6 against 2.1e-6 / 4.8e-5 over 203 terms).
 
 Measured on an MI355X (summary_line prints the figures on every run; DESIGN.md s3 "Pose-graph terms of a window" quotes
 them).  Per term, engine vs fp64 restatement, rel-L2 of AtA / Atb / error stacked over the terms of a window, next to the
@@ -28,6 +29,7 @@ import pytest
 from sage_slam_amd import capi as capi_module                   # (pure-numpy helpers only; the library loads in the fixture)
 from sage_slam_amd import synth
 from tests import graph_term_ref as G
+from tests import system_metric as sm
 from tests.conftest import summary_line
 from tests.helpers import rel
 
@@ -45,6 +47,13 @@ def capi():
     from sage_slam_amd import capi as c
     c.lib()
     return c
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _metric_summary():
+    yield
+    for ln in sm.summary_lines("window graph terms"):
+        summary_line(ln)
 
 
 # --------------------------------------------------------------------------------------------------------- scenes
@@ -136,6 +145,10 @@ def check_parity(win, w, links, terms, label):
                  f"fp32 restatement {fmt(d32)}, bars {fmt(bars)}")
     for k in dist:
         assert dist[k] <= bars[k], (label, k, dist[k], bars[k])
+    # ... and term by term, entry by entry (tests/system_metric.py): in the D = 14 layout the scale x scale entries are small
+    # next to pose x pose, the stacked norms above are the pose blocks
+    for i, (g, r) in enumerate(zip(got, ref)):
+        sm.check(g, r, "graph_terms", f"{label} #{i} {terms[i]['kind']}", segs=sm.seg_loop(), against="the fp64 restatement")
     for t, g in zip(terms, got):                                 # columns a kind does not have read zero
         kind = G.kind_of(t)
         if kind == 1:
@@ -146,8 +159,11 @@ def check_parity(win, w, links, terms, label):
 
 
 # --------------------------------------------------------------------------------------------------------- 1. per term
-@pytest.mark.parametrize("n", [1, TERMS_PER_WAVE - 1, TERMS_PER_WAVE, TERMS_PER_WAVE + 1,
-                               TERMS_PER_BLOCK - 1, TERMS_PER_BLOCK, TERMS_PER_BLOCK + 1, 3 * TERMS_PER_BLOCK + 5])
+COUNT_CASES = [1, TERMS_PER_WAVE - 1, TERMS_PER_WAVE, TERMS_PER_WAVE + 1,
+               TERMS_PER_BLOCK - 1, TERMS_PER_BLOCK, TERMS_PER_BLOCK + 1, 3 * TERMS_PER_BLOCK + 5]
+
+
+@pytest.mark.parametrize("n", COUNT_CASES)
 def test_term_counts_around_a_wave_and_a_workgroup(capi, n):
     w, links = theta_chain()
     terms = n_terms(w, links, n)
@@ -159,15 +175,36 @@ def test_term_counts_around_a_wave_and_a_workgroup(capi, n):
     win.close()
 
 
+def every_theta_terms(w, links):
+    """one off-target term of each binary kind on every directed edge, a scale prior on every keyframe -> (terms, the rng)"""
+    rng = np.random.default_rng(3)
+    terms = [term_on_edge(w, links, e, kind, rng) for e in range(2 * len(links)) for kind in ("rel_pose_scale", "rel_pose")]
+    terms += [dict(kind="scale_prior", kf=k, target_scale0=float(np.float32(kf.scale * 1.05)), weight=100.0)
+              for k, kf in enumerate(w.keyframes)]
+    return terms, rng
+
+
+def parity_term_sets():
+    """every set of terms check_parity sees: [(label, window, links, terms)] (host side; tests/metric_cases.py measures the
+    "graph_terms" constants of tests/system_metric.py on them)"""
+    out = []
+    for n in COUNT_CASES:
+        w, links = theta_chain()
+        out.append((f"count {n}", w, links, n_terms(w, links, n)))
+    for CS in (32, 16):
+        w, links = theta_chain(CS)
+        out.append((f"every theta, CS {CS}", w, links, every_theta_terms(w, links)[0]))
+    w = base_window()
+    out.append(("on dense links", w, w.links, graph_on_dense(w)))
+    return out
+
+
 @pytest.mark.parametrize("CS", [32, 16])
 def test_every_theta_both_directions_all_kinds(capi, CS):
     """every directed edge of the theta chain (relative rotations 0, 1e-4, 1e-2, 1, 2.5 and the chord's) carries one term of
     each binary kind, every keyframe a scale prior; then the same edges exactly on target"""
     w, links = theta_chain(CS)
-    rng = np.random.default_rng(3)
-    terms = [term_on_edge(w, links, e, kind, rng) for e in range(2 * len(links)) for kind in ("rel_pose_scale", "rel_pose")]
-    terms += [dict(kind="scale_prior", kf=k, target_scale0=float(np.float32(kf.scale * 1.05)), weight=100.0)
-              for k, kf in enumerate(w.keyframes)]
+    terms, rng = every_theta_terms(w, links)
     on = [term_on_edge(w, links, e, kind, rng, on_target=True) for e in range(2 * len(links)) for kind in ("rel_pose_scale", "rel_pose")]
     on += [dict(kind="scale_prior", kf=2, target_scale0=float(np.float32(w.keyframes[2].scale)), weight=100.0)]
     win = capi.Window(w, keypoint_links=links, graph_terms=terms + on)

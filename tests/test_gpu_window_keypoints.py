@@ -1,7 +1,9 @@
 """Matched-keypoint terms of the batched window engine (sage_window_add_keypoint_term) on the GPU: every term against the
 fp32 oracle's per-edge operator, exact assembly into the packed system, reproducibility, error pass, solve, LM and sharding.
 Tolerances are the project's own: TOL_H for per-edge AtA / Atb, 1e-5 for a per-edge error, 2e-6 for window totals, 1e-7 for
-the engine's solve against the host block solve."""
+the engine's solve against the host block solve.  Next to the whole-matrix TOL_H every term goes entry by entry against the
+fp64 oracle (tests/system_metric.py, families "window_reprojection" and "window_match_geometry": the code blocks of these terms are 1e-5
+of the norm TOL_H is taken of)."""
 import os
 import socket
 
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 
 from sage_slam_amd import synth
+from tests import system_metric as sm
 from tests.conftest import summary_line
 from tests.helpers import prior_vectors, rel
 
@@ -27,6 +30,18 @@ def capi():
     from sage_slam_amd import capi as c
     c.lib()
     return c
+
+
+# (CS, match-geometry loss) of test_every_term_matches_the_oracle; tests/metric_cases.py measures the families' constants on
+# the same terms
+TERM_CASES = [(32, "fair"), (32, "L2"), (32, "huber"), (32, "unbiased"), (16, "fair")]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _metric_summary():
+    yield
+    for ln in sm.summary_lines("window keypoint terms"):
+        summary_line(ln)
 
 
 def make(CS=32):
@@ -75,7 +90,18 @@ def engine_vars(win):
     return out
 
 
-def oracle_term(orc, w, t, xs, jac=True):
+def chunk_terms(w):
+    """the terms of test_chunking_two_terms_on_one_edge_and_single_keypoint"""
+    return [rep_term(w, 3, n=300), rep_term(w, 3, n=96, seed=1), rep_term(w, 4, n=1, outlier_share=1.0),
+            mg_term(w, 7, "fair", n=300), mg_term(w, 8, "fair", n=1, outlier_share=1.0), rep_term(w, 0, n=64),
+            rep_term(w, 1, n=65), mg_term(w, 2, "fair", n=128)]
+
+
+def term_family(t):
+    return "window_reprojection" if t["kind"] == "reprojection" else "window_match_geometry"
+
+
+def oracle_term(orc, w, t, xs, jac=True, prec="f32"):
     k0, k1 = edge_kfs(w, t["edge"])
     (R0, t0, c0, s0), (R1, t1, c1, s1) = xs[k0], xs[k1]
     R0, t0, R1, t1 = (np.asarray(v, np.float32) for v in (R0, t0, R1, t1))
@@ -84,7 +110,7 @@ def oracle_term(orc, w, t, xs, jac=True):
     if t["kind"] == "reprojection":
         if jac:
             return orc.reproj_jac_error(R10, t10, R0, t0, R1, t1, a.bias, a.basis, c0, t["loc0"], t["homo0"], t["matched_2d"],
-                                        s0, w.cams[0], w.eps, t["loss_param"], t["weight"])
+                                        s0, w.cams[0], w.eps, t["loss_param"], t["weight"], prec=prec)
         e, n = orc.reproj_error(R10, t10, a.bias, a.basis, c0, t["loc0"], t["homo0"], t["matched_2d"], s0, w.cams[0], w.eps,
                                 t["loss_param"], t["weight"])
         return dict(error=e, num_inliers=n)
@@ -92,7 +118,7 @@ def oracle_term(orc, w, t, xs, jac=True):
               homo1=t["homo1"], loc0=t["loc0"], loc1=t["loc1"], scale0=s0, scale1=s1, loss_param=t["loss_param"],
               weight=t["weight"])
     if jac:
-        return orc.match_geom_jac_error(0, t["loss"], R10, t10, R0=R0, t0=t0, R1=R1, t1=t1, **kw)
+        return orc.match_geom_jac_error(0, t["loss"], R10, t10, R0=R0, t0=t0, R1=R1, t1=t1, prec=prec, **kw)
     return dict(error=orc.match_geom_error(0, t["loss"], R10, t10, **kw))
 
 
@@ -106,13 +132,14 @@ def check_terms(orc, w, win, terms, label):
         worst["e"] = max(worst["e"], abs(h["error"] - o["error"]) / abs(o["error"]))
         if t["kind"] == "reprojection":
             assert h["num_inliers"] == o["num_inliers"], (label, i)
+        sm.check(h, oracle_term(orc, w, t, xs, prec="f64"), term_family(t), f"window term {label} #{i} edge {t['edge']}")
     summary_line(f"keypoint terms {label}: {len(terms)} terms, worst AtA {worst['A']:.2e} Atb {worst['b']:.2e} "
                  f"error {worst['e']:.2e}")
     assert worst["A"] < TOL_H and worst["b"] < TOL_H and worst["e"] < TOL_E, (label, worst)
 
 
 # --------------------------------------------------------------------------------------------------------- 1. per term
-@pytest.mark.parametrize("CS,loss", [(32, "fair"), (32, "L2"), (32, "huber"), (32, "unbiased"), (16, "fair")])
+@pytest.mark.parametrize("CS,loss", TERM_CASES)
 def test_every_term_matches_the_oracle(capi, orc, CS, loss):
     w = make(CS)
     terms = all_terms(w, rep=True, mg_loss=loss)
@@ -135,9 +162,7 @@ def test_chunking_two_terms_on_one_edge_and_single_keypoint(capi, orc):
     sum_i (n_i - log(1 + n_i)) >= ~0.1.  Terms of many points are dominated by their large residuals; for N = 1 the case is
     picked so, and the precondition is asserted on the oracle's value before the engine is compared."""
     w = make()
-    terms = [rep_term(w, 3, n=300), rep_term(w, 3, n=96, seed=1), rep_term(w, 4, n=1, outlier_share=1.0),
-             mg_term(w, 7, "fair", n=300), mg_term(w, 8, "fair", n=1, outlier_share=1.0), rep_term(w, 0, n=64),
-             rep_term(w, 1, n=65), mg_term(w, 2, "fair", n=128)]
+    terms = chunk_terms(w)
     for t in (terms[2], terms[4]):
         assert oracle_term(orc, w, t, initial_vars(w))["error"] / (2 * t["weight"]) >= 0.1
     win = capi.Window(w, keypoint_terms=terms)
