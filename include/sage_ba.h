@@ -1681,6 +1681,70 @@ int sage_window_lm_run_timed(SageWindow *w, SageLmState *st, const SageLmConfig 
  * sage_window_get_keyframe; a no-op for windows that solve the whole system on every rank. */
 int sage_window_sync_variables(SageWindow *w);
 
+/* ---- Powell's dogleg, the optimiser the reference runs its graphs with (ISAM2 in Dogleg mode, initial radius 1.0,
+ * ONE_STEP_PER_ITERATION: deepfactors.cpp:89, 397, 650, 1422).  DESIGN.md "Dogleg step" has the definitions.
+ *
+ * With A and g the window's system at damping 0 (diagonal blocks symmetrised, priors added, held rows the identity's with a
+ * zero g entry), n = A^-1 g the Gauss-Newton point and u = (g.g / g.Ag) g the steepest-descent point, every trial point of
+ * an iteration is  delta = a g + b n.  Six dot products determine its norm, its model decrease 2 g.delta - delta.A delta and
+ * the blend: dots [6] = { g.g, g.n, n.n, g.Ag, g.An, n.An }. */
+enum { SAGE_DOGLEG_SEARCH_EACH_ITERATION = 0, SAGE_DOGLEG_SEARCH_REDUCE_ONLY = 1, SAGE_DOGLEG_ONE_STEP_PER_ITERATION = 2 };
+typedef struct SageDoglegConfig
+{
+  double init_delta; /* trust radius of the first iteration (1.0) */
+  double min_delta;  /* the radius is halved only while it is above this (1e-5) */
+  int mode;          /* SAGE_DOGLEG_*: how the radius is adapted (ONE_STEP_PER_ITERATION) */
+} SageDoglegConfig;
+void sage_dogleg_config_default(SageDoglegConfig *cfg);
+/* carried from one iteration to the next: delta (<= 0 before the first iteration: cfg->init_delta is taken), solves, iters;
+ * the rest describes the last iteration.  evals: error evaluations of the last iteration; solves: factorisations so far
+ * (counted by the window step, one per iteration); accepted: 0 when the zero step was taken. */
+typedef struct SageDoglegState
+{
+  double delta, error, candidate_error, rho, step_norm, sd_norm, gn_norm, a, b;
+  double dots[6]; /* the dot products the last iteration was given */
+  int region, accepted, evals, solves, iters;
+} SageDoglegState;
+/* The dogleg point for radius delta (ComputeDoglegPoint / ComputeBlend, DoglegOptimizerImpl.cpp:25-83) as the coefficients
+ * of g and n; region: 0 steepest descent (u scaled to length delta), 1 blend, 2 Gauss-Newton.  g.g == 0: the zero step
+ * (a = b = 0, region 0), SAGE_OK.  SAGE_E_NOT_PSD for g.Ag <= 0 (or NaN), SAGE_E_INVALID for a NULL output. */
+int sage_dogleg_point(double delta, double gg, double gn, double nn, double gAg, double *a, double *b, int *region);
+/* the error at x (+) (a g + b n) -> *f_candidate; a non-zero return ends the iteration with that code */
+typedef int (*SageDoglegEvalFn)(void *ctx, double a, double b, double *f_candidate);
+/* One iteration of the trust-region policy (DoglegOptimizerImpl::Iterate, DoglegOptimizerImpl.h:137-252) around `eval`:
+ * gain ratio rho = (f_error - f_candidate) / model decrease, 0.5 when either decrease is below 1e-15 in magnitude;
+ * rho >= 0.75: delta <- max(delta, 3 |step|); 0.25 <= rho < 0.75: delta kept; 0 <= rho < 0.25: delta halved while above
+ * min_delta; rho < 0 or NaN: delta halved and the point evaluated again, at delta <= min_delta the zero step with the error
+ * kept.  The search modes repeat the evaluation as Iterate does.  SAGE_E_INVALID for a NULL argument, SAGE_E_NOT_PSD as
+ * sage_dogleg_point, otherwise what eval returned. */
+int sage_dogleg_iterate(const SageDoglegConfig *cfg, const double *dots, double f_error, SageDoglegEvalFn eval, void *ctx,
+                        SageDoglegState *st);
+/* Per keyframe the blocks of the packed buffer its rows of A v are summed from, in the order they are summed: the diagonal
+ * block first, then the links in the order they were added (duplicates and hubs included).  links [nlinks][2];
+ * offsets [K + 1]; entries [K + 2 nlinks][2] = (block: k or K + link, transposed: 0 for the link's first keyframe, whose
+ * rows the block holds, 1 for its second).  SAGE_E_INVALID for NULL, K < 1, nlinks < 0, an end outside [0, K) or a == b. */
+int sage_dogleg_incidence(int K, int nlinks, const int32_t *links, int32_t *offsets, int32_t *entries);
+
+/* One dogleg iteration on a finalized single-rank window with the device solver: linearize at the current estimate, ONE
+ * solve at damping 0, the products, sage_dogleg_iterate around the candidate kernel and the error pass, accept or keep.
+ * st->solves rises by one per call whatever st->evals is.  SAGE_E_NOT_PSD (window and st unchanged) for a non-positive
+ * pivot of the Gauss-Newton factorisation -- the caller may take an LM step instead (gtsam throws).  SAGE_E_UNSUPPORTED for
+ * sharded or reduced windows and windows without a device solver (duplicate links); SAGE_E_STATE before finalize;
+ * SAGE_E_INVALID for NULL. */
+int sage_window_dogleg_step(SageWindow *w, SageDoglegState *st, const SageDoglegConfig *cfg);
+/* n steps; trace (optional): n x {error, candidate_error, accepted, delta after the step, rho, region, evals}; *done
+ * (optional) = steps completed (an error code ends the run early). */
+int sage_window_dogleg_run(SageWindow *w, SageDoglegState *st, const SageDoglegConfig *cfg, int n, double *trace, int *done);
+/* The primitives behind the step.  _products: valid after a linearize and a sage_window_solve at damping 0; Ag and An in
+ * one pass over the packed buffer, then dots [6] (two runs agree in every bit).  _candidate: the candidate variables and
+ * their host mirrors for delta = a g + b n, exactly what the solve's retraction leaves for the same delta (so
+ * sage_window_accept, sage_window_get_delta and the error pass work unchanged); valid after _products.
+ * _get_dogleg_vectors: host copies of the last _products call's vectors (a step's included), K * B doubles each, any may
+ * be NULL. */
+int sage_window_dogleg_products(SageWindow *w, double *dots);
+int sage_window_dogleg_candidate(SageWindow *w, double a, double b);
+int sage_window_get_dogleg_vectors(SageWindow *w, double *g, double *Ag, double *n, double *An);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,69 @@ class SageLmState(C.Structure):
                 ("accepted", C.c_int), ("iters", C.c_int)]
 
 
+SAGE_DOGLEG_SEARCH_EACH_ITERATION, SAGE_DOGLEG_SEARCH_REDUCE_ONLY, SAGE_DOGLEG_ONE_STEP_PER_ITERATION = 0, 1, 2
+DOGLEG_DOTS = ("gg", "gn", "nn", "gAg", "gAn", "nAn")     # the order of every dots [6]
+
+
+class SageDoglegConfig(C.Structure):
+    _fields_ = [("init_delta", C.c_double), ("min_delta", C.c_double), ("mode", C.c_int)]
+
+
+class SageDoglegState(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("delta", "error", "candidate_error", "rho", "step_norm", "sd_norm", "gn_norm", "a", "b")] + \
+               [("dots", C.c_double * 6)] + \
+               [(n, C.c_int) for n in ("region", "accepted", "evals", "solves", "iters")]
+
+
+DOGLEG_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double))
+
+
+def dogleg_config_default() -> SageDoglegConfig:
+    cfg = SageDoglegConfig()
+    lib().sage_dogleg_config_default(C.byref(cfg))
+    return cfg
+
+
+def dogleg_point(delta, gg, gn, nn, gAg):
+    """``sage_dogleg_point`` -> (status code, a, b, region): the dogleg point for radius ``delta`` is a g + b n"""
+    f = lib().sage_dogleg_point
+    f.argtypes = [C.c_double] * 5 + [C.c_void_p] * 3
+    a, b, region = C.c_double(), C.c_double(), C.c_int()
+    rc = int(f(delta, gg, gn, nn, gAg, C.addressof(a), C.addressof(b), C.addressof(region)))
+    return rc, a.value, b.value, region.value
+
+
+def dogleg_iterate(cfg: SageDoglegConfig, dots, f_error, fn, state: SageDoglegState) -> int:
+    """``sage_dogleg_iterate`` around the Python callable ``fn(a, b) -> error`` (an exception ends the iteration with
+    SAGE_E_STATE) -> status code; ``state`` is updated in place."""
+    d = np.ascontiguousarray(dots, np.float64)
+    assert d.size == 6
+
+    def tramp(_ctx, a, b, out):
+        try:
+            out[0] = float(fn(a, b))
+            return 0
+        except Exception:                          # never unwind through the C frames
+            import traceback
+            traceback.print_exc()
+            return -4
+
+    f = lib().sage_dogleg_iterate
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, DOGLEG_EVAL_FN, C.c_void_p, C.c_void_p]
+    return int(f(C.addressof(cfg), d.ctypes.data, float(f_error), DOGLEG_EVAL_FN(tramp), None, C.addressof(state)))
+
+
+def dogleg_incidence(K: int, links):
+    """``sage_dogleg_incidence`` -> (status code, offsets [K + 1], entries [K + 2 nlinks, 2] of (block, transposed))"""
+    lk = np.ascontiguousarray(np.asarray(links, np.int32).reshape(-1, 2))
+    off = np.zeros(max(K, 0) + 1, np.int32)
+    ent = np.zeros((max(K, 0) + 2 * len(lk), 2), np.int32)
+    f = lib().sage_dogleg_incidence
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = int(f(int(K), len(lk), lk.ctypes.data if len(lk) else None, off.ctypes.data, ent.ctypes.data))
+    return rc, off, ent
+
+
 TRACK_LIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float),
                            C.POINTER(C.c_float), C.POINTER(C.c_float))
 TRACK_ERR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float))
@@ -159,6 +222,9 @@ SYMBOLS = [
     "sage_match_points_batch",
     "sage_workspace_set_registration_finish", "sage_workspace_registration_finish", "sage_registration_finish_batch",
     "sage_registration_finish_plan",
+    "sage_dogleg_config_default", "sage_dogleg_point", "sage_dogleg_iterate", "sage_dogleg_incidence",
+    "sage_window_dogleg_step", "sage_window_dogleg_run", "sage_window_dogleg_products", "sage_window_dogleg_candidate",
+    "sage_window_get_dogleg_vectors",
 ]
 
 
@@ -1533,6 +1599,40 @@ class Window:
         _chk(lib().sage_window_lm_run_timed(self.h, C.byref(state), C.byref(cfg), n, tr.ctypes.data_as(C.POINTER(C.c_double)),
                                             C.byref(done), sec.ctypes.data_as(C.POINTER(C.c_double))), "sage_window_lm_run_timed")
         return tr[:done.value], sec[:done.value]
+
+    def dogleg_step(self, state: SageDoglegState, cfg: SageDoglegConfig):
+        """one dogleg iteration (``sage_window_dogleg_step``): linearize, one solve at damping 0, the products, the
+        trust-region policy around candidate + error pass, accept or keep"""
+        _chk(lib().sage_window_dogleg_step(self.h, C.byref(state), C.byref(cfg)), "sage_window_dogleg_step")
+        return state
+
+    def dogleg_run(self, state: SageDoglegState, cfg: SageDoglegConfig, n: int):
+        """n dogleg iterations without returning to Python in between -> [n, 7] trace {error, candidate, accepted, delta
+        after the step, rho, region, evals}."""
+        tr = np.zeros((n, 7), np.float64)
+        done = C.c_int()
+        _chk(lib().sage_window_dogleg_run(self.h, C.byref(state), C.byref(cfg), n, tr.ctypes.data_as(C.POINTER(C.c_double)),
+                                          C.byref(done)), "sage_window_dogleg_run")
+        return tr[:done.value]
+
+    def dogleg_products(self):
+        """``sage_window_dogleg_products`` (after ``linearize`` and ``solve(0)``) -> dots [6] in the order of DOGLEG_DOTS"""
+        d = np.zeros(6, np.float64)
+        _chk(lib().sage_window_dogleg_products(self.h, d.ctypes.data_as(C.POINTER(C.c_double))), "sage_window_dogleg_products")
+        return d
+
+    def dogleg_candidate(self, a, b):
+        """``sage_window_dogleg_candidate``: the candidate for delta = a g + b n (after ``dogleg_products``)"""
+        f = lib().sage_window_dogleg_candidate
+        f.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        _chk(f(self.h, float(a), float(b)), "sage_window_dogleg_candidate")
+
+    def dogleg_vectors(self):
+        """host copies of (g, Ag, n, An), K * B doubles each (``sage_window_get_dogleg_vectors``)"""
+        v = [np.zeros(self.K * self.B, np.float64) for _ in range(4)]
+        _chk(lib().sage_window_get_dogleg_vectors(self.h, *[x.ctypes.data_as(C.POINTER(C.c_double)) for x in v]),
+             "sage_window_get_dogleg_vectors")
+        return tuple(v)
 
     def delta(self):
         d = np.zeros(self.K * self.B, np.float64)

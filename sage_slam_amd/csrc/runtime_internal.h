@@ -25,6 +25,8 @@
 //   window_reduce.hip   sums over ranks (hook, peer emulation), the pinned totals mirror and its waits, the total error
 //   window_solve.hip    from a system to a candidate: priors, damped solve, separator solve, accept / reset / variable exchange
 //   window_lm.hip       the LM iteration: one policy around three sequences (classic, schur, at_candidate)
+//   window_dogleg.hip   the dogleg iteration: A g, A n and the dots on the device, trial points as blends, the step
+//   dogleg_host.cpp     (no HIP) the dogleg point, gtsam's trust-region policy around a callback, the incidence lists
 //   window_profile.hip  optional kernel timing of a window: event pool, per-kernel event pairs, phase marks
 //   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
 //   window_terms.hip    keypoint and pose-graph terms: add / get, their finalize stage, their two launches
@@ -82,6 +84,7 @@ extern "C"
 #include "registration_plan.h" // RegBatchPlan
 #include "depth_scale_plan.h"  // SelBatchPlan
 #include "loop_accept.h"       // sage_loop_accept's host rules
+#include "dogleg.h"            // the dogleg step's dots, partial slots and pinned record
 
 using namespace sage;
 
@@ -403,6 +406,7 @@ struct SageWindow
   TermSide terms;                         // keypoint and pose-graph terms: as added, this rank's layout, device tables, results
   FactorCache fc;                         // f2: the per-Values factor cache (sage_window_prepass): window_state.h
   uint64_t dense_serial = 0;              // counts the linearizes that have written dense[].AtA (FactorSlot::live_serial)
+  DoglegSide dogleg;                      // the dogleg step's tables, vectors and pinned dots (window_dogleg.hip)
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an
@@ -462,6 +466,7 @@ int window_copy_floats(SageWindow *w, const float *src, float *dst, int n); // o
 void window_add_to_double(SageWindow *w, double *p, double v);              // p[0] += v on the window's stream
 // window_solve.hip
 double window_prior_error(const SageWindow *w, int set, bool owned_only = false);
+SolvePriors window_solve_priors(const SageWindow *w); // (damped_system.h) the priors as the scatter kernel takes them
 int window_sync_candidate(SageWindow *w, bool stream_idle = false);
 int window_schur_solve(SageWindow *w, double damp, double *lin_error);
 // window_profile.hip

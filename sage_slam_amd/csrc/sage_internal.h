@@ -327,5 +327,16 @@ const float *solver_host_vars(const DeviceSolver *S);
 const double *solver_host_delta(const DeviceSolver *S);
 double solver_host_step_norm2(const DeviceSolver *S);
 int solver_host_status(const DeviceSolver *S);
+// How the solver lays a solution out, for a caller that writes one on the device (window_dogleg.hip): row r of keyframe k at
+// x[pos[k] * Bp + to_solver[r]] (to_solver: -1 for a dropped row), x_count doubles in all; hold: the device's masks or null
+struct SolverLayout
+{
+  const int32_t *pos, *to_solver, *hold;
+  int Bp;
+  size_t x_count;
+};
+SolverLayout solver_layout(const DeviceSolver *S);
+// the retraction of a solve for a solution x_dev that is on the device already: the same kernel, the same mirrors
+int solver_retract_from(DeviceSolver *S, hipStream_t stream, const double *x_dev, const float *vars0, float *vars1, int CS);
 
 } // namespace sage

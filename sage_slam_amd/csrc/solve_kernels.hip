@@ -443,4 +443,24 @@ const double *solver_host_delta(const DeviceSolver *S) { return S->host_delta();
 double solver_host_step_norm2(const DeviceSolver *S) { return S->result()->step_norm2; }
 int solver_host_status(const DeviceSolver *S) { return S->result()->status; }
 
+SolverLayout solver_layout(const DeviceSolver *S)
+{
+  return SolverLayout{S->plan.pos, S->plan.to_solver, S->plan.hold, S->Bp, (size_t)S->K * S->Bp};
+}
+
+// a candidate for a solution that is on the device already (the dogleg step's blends: window_dogleg.hip): solve_retract_kernel
+// itself, so the candidate, its mirrors and |delta|^2 are what a solve with this solution leaves, in every bit.  The word
+// the kernel waits for is given before the launch
+int solver_retract_from(DeviceSolver *S, hipStream_t stream, const double *x_dev, const float *vars0, float *vars1, int CS)
+{
+  S->go_epoch = (S->go_epoch + 1) & 0x7fffffffu;
+  if (S->go_epoch == 0)
+    S->go_epoch = 1;
+  std::atomic_thread_fence(std::memory_order_release);
+  *const_cast<volatile unsigned *>(&S->result()->go) = S->go_epoch;
+  hipLaunchKernelGGL(solve_retract_kernel, dim3(1), dim3(1024), 0, stream, x_dev, S->K, S->B, S->Bp, CS, S->VS, S->plan.pos,
+                     S->plan.hold, S->plan.to_solver, vars0, vars1, S->host_vars(), S->host_delta(), S->result(), S->go_epoch);
+  return (int)hipGetLastError();
+}
+
 } // namespace sage

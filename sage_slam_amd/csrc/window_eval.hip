@@ -449,6 +449,7 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->lin_epoch = set == 0 ? w->vars_epoch : 0; // (a candidate's system becomes current only through lm_step's accept)
     w->spec_err_valid = false;
     w->dist.packed_reduced = false;
+    w->dogleg.solved0 = w->dogleg.products = false; // (a new system: its Gauss-Newton point is yet to be solved for)
   }
   return SAGE_OK;
 }

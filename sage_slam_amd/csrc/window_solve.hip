@@ -43,7 +43,7 @@ double window_prior_error(const SageWindow *w, int set, bool owned_only)
   return e;
 }
 
-static sage::SolvePriors window_solve_priors(const SageWindow *w)
+sage::SolvePriors window_solve_priors(const SageWindow *w)
 {
   const SageWindowConfig &c = w->cfg;
   sage::SolvePriors pri{};
@@ -129,10 +129,12 @@ extern "C" int sage_window_solve(SageWindow *w, double damp, double *step_norm)
       return rc;
     if (w->dpt_set == 1)
       w->dpt_set = -1; // the solve rewrites the candidate set
+    w->dogleg.solved0 = w->dogleg.products = false;
     rc = solver_run(w->solver, w->stream, w->packed.as<double>(), w->vars[0].as<float>(), w->vars[1].as<float>(), CS,
                     damp, window_solve_priors(w));
     if (rc)
       return rc;
+    w->dogleg.solved0 = damp == 0.0; // (the Gauss-Newton point: what sage_window_dogleg_products starts from)
     window_phase_mark(w, 3);
     w->cand_pending = true;
     if (step_norm)
@@ -252,6 +254,7 @@ extern "C" int sage_window_accept(SageWindow *w)
   if (rcs)
     return rcs;
   w->hv.copy_set(0, 1);
+  w->dogleg.solved0 = w->dogleg.products = false; // (the dogleg vectors belong to the estimate that is replaced here)
   ++w->vars_epoch;
   ++w->dist.emu_cur;
   w->dpt_set = w->dpt_set == 1 ? 0 : -1; // depth maps evaluated at the candidate now belong to the current set

@@ -179,6 +179,21 @@ struct TotalsMirror
   }
 };
 
+// ---- the dogleg step (window_dogleg.hip): everything is allocated by the first call that needs it ----
+struct DoglegSide
+{
+  DevBuf tables;          // int32: offsets [K + 1] | entries [K + 2 nlinks][2] (sage_dogleg_incidence) | links [nlinks][2]
+  DevBuf part;            // the block kernel's partial products: [dogleg::partial_slots][2][B]
+  DevBuf vec;             // g | Ag | n | An, [K * B] doubles each; n is fetched from the solve's pinned delta mirror
+  DevBuf x;               // a trial point a g + b n in the solver's solution layout (SolverLayout): what the retraction reads
+  PinnedBuf host;         // dogleg::HostRecord: the dots behind their ticket
+  uint64_t epoch = 0;     // ticket value of the last products call
+  bool ready = false;     // the buffers above are there
+  bool solved0 = false;   // the candidate of the current system is the device solver's at damping 0 ...
+  bool products = false;  // ... and g, Ag, n, An are that system's
+  bool vectors = false;   // a products call has filled them (sage_window_get_dogleg_vectors reads the last call's)
+};
+
 // ---- sharded windows ----
 struct WindowDist
 {
