@@ -1745,6 +1745,71 @@ int sage_window_dogleg_products(SageWindow *w, double *dots);
 int sage_window_dogleg_candidate(SageWindow *w, double a, double b);
 int sage_window_get_dogleg_vectors(SageWindow *w, double *g, double *Ag, double *n, double *An);
 
+/* Partial relinearization, as ISAM2 relinearizes (cacheLinearizedFactors, relinearizeSkip 1, per-key thresholds:
+ * core/deepfactors.cpp:1421-1437; ISAM2-impl.h:345-372): only the factors that touch a key whose linearization point moved
+ * are linearized again, every other factor keeps its cached HessianFactor.
+ *
+ * Who reads what.  A directed edge a -> b (source a; numbered as sage_window_get_edge numbers them) reads
+ *     photometric   pose a, pose b, code a, scale a      the depth map of a
+ *     geometric     pose, code and scale of both         the depth maps of a and b, the gradient of b's
+ * so a change of code b alone leaves the photometric edge a -> b clean.  "Changed" = the float bits differ (the memcmp of
+ * sage_window_prepass: -0.0f against 0.0f is a change).
+ *
+ * sage_relin_plan (host only, stateless): the reads table applied to two variable sets.  links [n_links][2] (either order of
+ * a link's keyframes; direction 0 starts at the lower one), pose [K][12], code [K][CS], scale [K]; photo_stale, geo_stale
+ * [2 * n_links]: 1 for a directed edge of that type that reads a changed group; map_read [K]: 1 for a keyframe whose depth
+ * map a stale edge reads; n_photo, n_geo (optional): the numbers of stale edges.  SAGE_E_INVALID for a NULL array, K < 1,
+ * CS < 1, n_links < 0, a link end outside [0, K) or a link of a keyframe with itself.
+ *
+ * sage_window_set_relinearization (after finalize, SAGE_E_STATE before; SAGE_E_INVALID for another mode; SAGE_E_UNSUPPORTED
+ * for SAGE_RELIN_STALE on a sharded window): in SAGE_RELIN_STALE sage_window_linearize -- and with it a linearizing
+ * sage_window_prepass -- launches only the dense edges whose inputs differ from the values their device-resident result was
+ * computed at, byte for byte what SAGE_RELIN_ALL (the default) computes for them; the other edges keep their results,
+ * {error, inliers} included: an error pass at other values in between does not touch them.  Depth maps are rebuilt only
+ * for the keyframes a launched edge reads, and only when they were built from other code / scale bits.  The keypoint and
+ * graph terms are evaluated in full every time (one launch per group of at most 512 points each: launch latency, and
+ * bit-identical anyway), and so is the assembly.  Nothing stale: no dense launch; the values and the packed system both
+ * current: nothing is launched at all.  Every edge is stale after a switch of the mode, sage_window_lm_step and the dogleg
+ * step (their merged linearize leaves mixed results), sage_window_set_runs / sage_window_tune_runs and sage_window_reset.
+ * The error pass stays whole-window.
+ * In SAGE_RELIN_STALE a recomputing sage_window_prepass copies only the re-evaluated edges' AtA / Atb rows to the host
+ * cache (the term groups in full) and keeps the clean edges' rows across an error-only prepass at other values.
+ *
+ * sage_window_last_evaluation: what the last sage_window_linearize (either mode) evaluated: dense edges and work items per
+ * factor type, depth maps and gradient maps built, and the AtA / Atb rows a prepass around it copied to the host. */
+enum { SAGE_RELIN_ALL = 0, SAGE_RELIN_STALE = 1 };
+typedef struct SageEvalCounts
+{
+  int32_t photo_edges, geo_edges, depth_maps, depth_grads, photo_items, geo_items, host_entries_pulled;
+} SageEvalCounts;
+int sage_relin_plan(int K, int CS, int n_links, const int32_t *links, const float *pose_old, const float *code_old,
+                    const float *scale_old, const float *pose_new, const float *code_new, const float *scale_new,
+                    uint8_t *photo_stale, uint8_t *geo_stale, uint8_t *map_read, int32_t *n_photo, int32_t *n_geo);
+int sage_window_set_relinearization(SageWindow *w, int mode);
+int sage_window_last_evaluation(const SageWindow *w, SageEvalCounts *out);
+/* The relinearization check and the masked accept: with them a window runs ISAM2's fluid loop -- linearize (stale),
+ * sage_window_solve or a dogleg point, marks, masked accept -- where every factor is linearized at the current point and
+ * only the work is partial.
+ * sage_relin_marks (host only, stateless): gtsam's CheckRelinearizationFull with per-key vector thresholds.  delta [K][7+CS]
+ * in the window's block order (pose 6, code CS, scale); marks [K]: the SAGE_HOLD_* bits of the groups with any
+ * |delta_i| > threshold_i (strictly; a NaN marks nothing); n_marked (optional): the number of groups marked.
+ * SAGE_E_INVALID for a NULL delta, t or marks, K < 1, CS < 1.
+ * sage_window_relin_marks: the same on the last solve's delta (sage_window_get_delta), with the groups held by
+ * sage_window_hold cleared (gtsam erases fixedVariables).  SAGE_E_STATE before finalize.
+ * sage_window_accept_marked: candidate -> current for the marked groups only (ISAM2's ExpmapMasked: the candidate is the
+ * retraction of the last solve's delta); unmarked groups keep their linearization point, held groups are never moved.  The
+ * candidate set becomes the new current set as well.  SAGE_E_INVALID for NULL or bits outside SAGE_HOLD_*; SAGE_E_STATE
+ * before finalize. */
+typedef struct SageRelinThresholds
+{
+  float pose[6];
+  float code;
+  float scale;
+} SageRelinThresholds;
+int sage_relin_marks(const double *delta, int K, int CS, const SageRelinThresholds *t, int32_t *marks, int32_t *n_marked);
+int sage_window_relin_marks(const SageWindow *w, const SageRelinThresholds *t, int32_t *marks, int32_t *n_marked);
+int sage_window_accept_marked(SageWindow *w, const int32_t *marks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,16 @@ public:
       sage_window_get_keyframe(win_, (int)k, &pose_[k * 12], &code_[k * CS_], &scale_[k]);
   }
 
+  // SAGE_RELIN_STALE (opt-in; SAGE_RELIN_ALL is the window's default): a recomputing Prepare with jacobians evaluates only
+  // the dense edges that read a key whose value differs from the last linearisation's, and copies only their rows -- what an
+  // unmodified ISAM2 (cacheLinearizedFactors, relinearizeSkip 1) asks for after it has moved a few keys; the served factors
+  // are the same bytes either way.  Call it once, after the window is finalized; sharded windows refuse the mode
+  bool SetRelinearization(int mode)
+  {
+    std::lock_guard<std::mutex> lock(mutex_);
+    return sage_window_set_relinearization(win_, mode) == SAGE_OK;
+  }
+
   // Gather the window's variables out of `c` (pose_wk as [R row-major | t], gtsam_traits.h:45-70) and make sure the
   // cache holds their linearisation (jacobians) or errors.  The first factor that sees new Values pays for the whole
   // window; every other factor of the same ISAM2 relinearisation / Dogleg trial is a cache hit.

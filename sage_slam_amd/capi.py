@@ -192,6 +192,66 @@ TRACK_ERR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_float,
 _lib = None
 
 # every symbol include/sage_ba.h declares (checked by tests/test_capi_symbols.py against the header)
+SAGE_RELIN_ALL, SAGE_RELIN_STALE = 0, 1
+
+
+class SageEvalCounts(C.Structure):
+    """what the last ``sage_window_linearize`` evaluated (``sage_window_last_evaluation``)"""
+    _fields_ = [(n, C.c_int32) for n in ("photo_edges", "geo_edges", "depth_maps", "depth_grads", "photo_items", "geo_items",
+                                         "host_entries_pulled")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class SageRelinThresholds(C.Structure):
+    _fields_ = [("pose", C.c_float * 6), ("code", C.c_float), ("scale", C.c_float)]
+
+
+def relin_thresholds(pose=1e-3, code=1e-4, scale=1e-3) -> SageRelinThresholds:
+    """per-key thresholds (the mapper's: p 1e-3, c 1e-4, s 1e-3); ``pose``: one value or six"""
+    t = SageRelinThresholds()
+    for i, v in enumerate(np.broadcast_to(np.asarray(pose, np.float32), (6,))):
+        t.pose[i] = float(v)
+    t.code, t.scale = float(code), float(scale)
+    return t
+
+
+def relin_plan_raw(K, CS, n_links, links_ptr, old_ptrs, new_ptrs, photo_ptr, geo_ptr, map_ptr, n_photo_ptr, n_geo_ptr) -> int:
+    """``sage_relin_plan`` on raw pointers (``old_ptrs`` / ``new_ptrs``: pose, code, scale) -> status code"""
+    f = lib().sage_relin_plan
+    f.argtypes = [C.c_int] * 3 + [C.c_void_p] * 12
+    return int(f(int(K), int(CS), int(n_links), links_ptr, *old_ptrs, *new_ptrs, photo_ptr, geo_ptr, map_ptr, n_photo_ptr, n_geo_ptr))
+
+
+def relin_plan(K: int, CS: int, links, old, new) -> dict:
+    """``sage_relin_plan``: ``old`` / ``new`` = (pose [K,12], code [K,CS], scale [K]) -> dict(photo_stale, geo_stale
+    [2 * n_links] uint8, map_read [K] uint8, n_photo, n_geo)"""
+    lk = np.ascontiguousarray(np.asarray(links, np.int32).reshape(-1, 2))
+    o = [_f32(np.asarray(a).reshape(-1)) for a in old]; n = [_f32(np.asarray(a).reshape(-1)) for a in new]
+    assert all(a.size == b.size == m for a, b, m in zip(o, n, (K * 12, K * CS, K)))
+    ph = np.zeros(2 * len(lk), np.uint8); ge = np.zeros(2 * len(lk), np.uint8); mr = np.zeros(K, np.uint8)
+    n_p, n_g = C.c_int32(), C.c_int32()
+    _chk(relin_plan_raw(K, CS, len(lk), lk.ctypes.data, [a.ctypes.data for a in o], [a.ctypes.data for a in n], ph.ctypes.data,
+                        ge.ctypes.data, mr.ctypes.data, C.addressof(n_p), C.addressof(n_g)), "sage_relin_plan")
+    return dict(photo_stale=ph, geo_stale=ge, map_read=mr, n_photo=n_p.value, n_geo=n_g.value)
+
+
+def relin_marks_raw(delta_ptr, K, CS, t_ptr, marks_ptr, n_marked_ptr) -> int:
+    f = lib().sage_relin_marks
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(delta_ptr, int(K), int(CS), t_ptr, marks_ptr, n_marked_ptr))
+
+
+def relin_marks(delta, K: int, CS: int, t: SageRelinThresholds):
+    """``sage_relin_marks``: delta [K, 7 + CS] -> (marks [K] int32 of SAGE_HOLD_* bits, groups marked)"""
+    d = np.ascontiguousarray(delta, np.float64).reshape(-1)
+    assert d.size == K * (7 + CS)
+    marks = np.zeros(K, np.int32); n = C.c_int32()
+    _chk(relin_marks_raw(d.ctypes.data, K, CS, C.addressof(t), marks.ctypes.data, C.addressof(n)), "sage_relin_marks")
+    return marks, n.value
+
+
 SYMBOLS = [
     "sage_camera_pyramid", "sage_version", "sage_error_string", "sage_workspace_create", "sage_workspace_destroy",
     "sage_photometric_jac_error_calculate", "sage_photometric_error_calculate",
@@ -225,6 +285,8 @@ SYMBOLS = [
     "sage_dogleg_config_default", "sage_dogleg_point", "sage_dogleg_iterate", "sage_dogleg_incidence",
     "sage_window_dogleg_step", "sage_window_dogleg_run", "sage_window_dogleg_products", "sage_window_dogleg_candidate",
     "sage_window_get_dogleg_vectors",
+    "sage_relin_plan", "sage_window_set_relinearization", "sage_window_last_evaluation", "sage_relin_marks",
+    "sage_window_relin_marks", "sage_window_accept_marked",
 ]
 
 
@@ -1633,6 +1695,32 @@ class Window:
         _chk(lib().sage_window_get_dogleg_vectors(self.h, *[x.ctypes.data_as(C.POINTER(C.c_double)) for x in v]),
              "sage_window_get_dogleg_vectors")
         return tuple(v)
+
+    def set_relinearization(self, mode: int, check=True) -> int:
+        """``sage_window_set_relinearization`` (SAGE_RELIN_ALL / SAGE_RELIN_STALE); ``check=False``: the status code"""
+        rc = int(lib().sage_window_set_relinearization(self.h, int(mode)))
+        if check:
+            _chk(rc, "sage_window_set_relinearization")
+        return rc
+
+    def last_evaluation(self) -> dict:
+        """``sage_window_last_evaluation`` -> the ``SageEvalCounts`` of the last linearize as a dict"""
+        n = SageEvalCounts()
+        _chk(lib().sage_window_last_evaluation(self.h, C.byref(n)), "sage_window_last_evaluation")
+        return n.as_dict()
+
+    def relin_marks(self, t: SageRelinThresholds):
+        """``sage_window_relin_marks`` on the last solve's delta -> (marks [K] int32, groups marked)"""
+        marks = np.zeros(self.K, np.int32); n = C.c_int32()
+        _chk(lib().sage_window_relin_marks(self.h, C.byref(t), marks.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)),
+             "sage_window_relin_marks")
+        return marks, n.value
+
+    def accept_marked(self, marks):
+        """``sage_window_accept_marked``: candidate -> current for the marked groups only"""
+        m = np.ascontiguousarray(marks, np.int32)
+        assert m.size == self.K
+        _chk(lib().sage_window_accept_marked(self.h, m.ctypes.data_as(C.POINTER(C.c_int32))), "sage_window_accept_marked")
 
     def delta(self):
         d = np.zeros(self.K * self.B, np.float64)

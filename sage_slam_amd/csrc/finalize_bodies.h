@@ -1,6 +1,8 @@
 // finalize_bodies.h -- per-edge finalize of the two dense factor types as device functions: the stand-alone finalize
 // kernels (photo_kernels.hip / geo_kernels.hip: drop-in operators, factor cache) and the window's one-launch
-// finalize + assembly (window_eval.hip) share them.  One workgroup per edge; `s` is the workgroup's LDS scratch.
+// finalize + assembly (window_eval.hip) share them.  One workgroup per edge; `s` is the workgroup's LDS scratch.  Workgroup j
+// handles edge j, or edge_list[j] where the params carry a list (the window's stale-mode linearize: only the listed edges'
+// rows of AtA / Atb / stats / wide are written).
 #pragma once
 #include "sage_internal.h"
 
@@ -32,6 +34,7 @@ struct PhotoFinalizeParams
   float wsum;
   int edge_base; // blockIdx.x = edge - edge_base
   double *wide;  // optional [n_edges][D*D + D]: the results before rounding to fp32
+  const int32_t *edge_list; // optional: workgroup j handles edge edge_list[j]
 };
 
 __device__ __forceinline__ double tile_elem(const double *s, int base, int tile, int row, int col)
@@ -40,8 +43,9 @@ __device__ __forceinline__ double tile_elem(const double *s, int base, int tile,
 }
 
 template <int CS>
-__device__ __forceinline__ void photo_finalize_body(const PhotoFinalizeParams &prm, const int e, double *s)
+__device__ __forceinline__ void photo_finalize_body(const PhotoFinalizeParams &prm, const int j, double *s)
 {
+  const int e = prm.edge_list ? prm.edge_list[j] : j;
   constexpr int PP = kPhotoScalars + photo_tiles(CS) * 256; // entries of a summed record
   constexpr int D = 13 + CS;
   // s[PP] (LDS): partial sums and every derived product stay in double until the single final rounding
@@ -185,6 +189,7 @@ struct GeoFinalizeParams
   float weight;
   int edge_base; // blockIdx.x = edge - edge_base
   double *wide;  // optional [n_edges][D*D + D]: the results before rounding to fp32
+  const int32_t *edge_list; // optional: workgroup j handles edge edge_list[j]
   // merged linearize (LaunchCommon::merge_geo_weight): the photometric launch's partial records of the same edges -- row 8
   // of their cross tiles is  sum_n w_g omega kappa D b_n  (the scale1-code0 block; every other code0 block of the
   // geometric edge rides in the photometric edge's result and reads zero here)
@@ -193,8 +198,9 @@ struct GeoFinalizeParams
 };
 
 template <int CS>
-__device__ __forceinline__ void geo_finalize_body(const GeoFinalizeParams &prm, const int e, double *s)
+__device__ __forceinline__ void geo_finalize_body(const GeoFinalizeParams &prm, const int j, double *s)
 {
+  const int e = prm.edge_list ? prm.edge_list[j] : j;
   constexpr int PP = geo_partial_floats(CS);
   constexpr int D = 14 + 2 * CS;
   constexpr int N16 = geo_n16(CS);

@@ -32,6 +32,9 @@
 //   window_terms.hip    keypoint and pose-graph terms: add / get, their finalize stage, their two launches
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
+//   window_relin.hip    partial relinearization: the stale edges of a linearize, their compacted launch plan (its kernel), the
+//                       depth maps' stamps, the relinearization marks and the masked accept
+//   relin_host.cpp      (no HIP) the reads table and gtsam's relinearization check (relin_plan.h), stateless
 //   factor_blocks.cpp   (no HIP) what a cached factor is: shape, projection of its own matrix, cut into HessianFactor blocks
 // window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, factor cache, totals
 // mirror, distributed state, profiler); device_buffers.h holds the owners of device and pinned allocations (DevBuf, PinnedBuf: also
@@ -407,6 +410,7 @@ struct SageWindow
   FactorCache fc;                         // f2: the per-Values factor cache (sage_window_prepass): window_state.h
   uint64_t dense_serial = 0;              // counts the linearizes that have written dense[].AtA (FactorSlot::live_serial)
   DoglegSide dogleg;                      // the dogleg step's tables, vectors and pinned dots (window_dogleg.hip)
+  RelinSide relin;                        // partial relinearization: mode, snapshot, depth stamps, sub work lists (window_relin.hip)
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an
@@ -450,7 +454,10 @@ struct FinalizeState
 int finalize_terms(SageWindow *w, FinalizeState &fs);  // stage 7 of sage_window_finalize
 int window_launch_terms(SageWindow *w, int set, bool jac); // the keypoint kernel, then the graph kernel, over this rank's terms
 // window_eval.hip
-int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false);
+// stale_only: the stale-mode linearize of sage_window_linearize (set 0 into `packed`, unmerged); every other call evaluates
+// every edge and, in SAGE_RELIN_STALE, leaves every edge stale
+int window_linearize_set(SageWindow *w, int set, double *dst = nullptr, bool local_blocks = false, bool merge = false,
+                         bool stale_only = false);
 int window_error_pass(SageWindow *w, int which, bool speculate_gradients);
 // window_reduce.hip
 int window_collective(SageWindow *w, double *buf, size_t n);                 // the hook's sum in place, nothing else
@@ -469,6 +476,22 @@ double window_prior_error(const SageWindow *w, int set, bool owned_only = false)
 SolvePriors window_solve_priors(const SageWindow *w); // (damped_system.h) the priors as the scatter kernel takes them
 int window_sync_candidate(SageWindow *w, bool stream_idle = false);
 int window_schur_solve(SageWindow *w, double damp, double *lin_error);
+// window_relin.hip
+// what a stale-mode linearize launches: per dense side (kPhoto, kGeo) the stale edges, their work items and where the
+// compacted plan lies on the device
+struct RelinLaunch
+{
+  bool nothing = false;              // values and packed system are current: the call launches nothing at all
+  int n_edges[2] = {0, 0}, n_items[2] = {0, 0};
+  const WorkItem *work[2] = {nullptr, nullptr};
+  const int32_t *first[2] = {nullptr, nullptr}; // LaunchCommon::edge_first of the side (the photometric side's: of its records, if it has them)
+  const int32_t *list[2] = {nullptr, nullptr};  // the stale edges, ascending: one finalize workgroup each
+  bool any() const { return n_edges[0] + n_edges[1] > 0; }
+};
+int relin_prepare(SageWindow *w, RelinLaunch &rl);  // the stale edges against the snapshot, their depth maps, the compacted plan
+void relin_commit(SageWindow *w, const RelinLaunch &rl); // the launches are enqueued: the current variables become the snapshot
+void relin_stamp_maps(SageWindow *w, int set, bool depth, bool grad); // a whole-window depth batch at `set` has been enqueued
+void relin_count_all(SageWindow *w, bool dense, bool depth, bool grad); // SageEvalCounts of a linearize of every edge
 // window_profile.hip
 void prof_attach(SageWindow *w, int which, LaunchCommon &lc); // profiling: an event pair for kernel `which` (LaunchCommon::ev_*)
 void window_phase_mark(SageWindow *w, int which); // profiling: record phase mark `which` on the window's stream

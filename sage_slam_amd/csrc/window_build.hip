@@ -121,6 +121,7 @@ static int upload_work_list(DenseSide &sd, const WorkList &wl, hipStream_t s)
   int rc;
   sd.n_work = (int)wl.work.size();
   sd.tpb = wl.tiles_per_block;
+  sd.h_tiles = wl.edge_tiles;
   if ((rc = upload(sd.work, wl.work, s)) || (rc = upload(sd.first, wl.edge_first, s)) || (rc = upload(sd.tiles, wl.edge_tiles, s)))
     return rc;
   return SAGE_OK;
@@ -143,6 +144,8 @@ static int window_plan_photo_runs(SageWindow *w, int tpb, int flush)
   int rc;
   w->photo_rec.flush = wp.flush;
   w->photo_rec.n = wp.n_records;
+  w->photo_rec.h_count = wp.rec_count;
+  w->relin.drop(); // the record layout changes: no per-edge result is this plan's
   DenseSide &ph = w->dense[kPhoto];
   if ((rc = upload_work_list(ph, wp, w->stream)) || (rc = upload(w->photo_rec.first, wp.rec_first, w->stream)) ||
       (rc = upload(w->photo_rec.count, wp.rec_count, w->stream)))
@@ -649,6 +652,8 @@ extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_
   const std::vector<int> cand = plan::tune_candidates(rule, plan::typical_edge(edge_tiles(w->Nedge)));
   const bool prof_was = w->prof.profiling;
   const int level_was = w->prof.prof_level;
+  const int relin_was = w->relin.mode; // every timed linearize evaluates every edge
+  w->relin.mode = SAGE_RELIN_ALL;
   int rc = sage_window_set_profiling(w, 1);
   double best_ms = 0.0, rule_ms = 0.0;
   int best = rule;
@@ -699,6 +704,7 @@ extern "C" int sage_window_tune_runs(SageWindow *w, int *tpb_out, int *tpb_rule_
   (void)sage_window_get_kernel_time(w, 1, nullptr, nullptr); // (drop the geometric kernels' records of these evaluations)
   (void)sage_window_get_kernel_time(w, 3, nullptr, nullptr);
   (void)sage_window_set_profiling(w, prof_was ? level_was : 0);
+  w->relin.mode = relin_was;
   if (!rc && !(best_ms < 0.96 * rule_ms))
     best = rule;
   const int rc2 = window_plan_photo_runs(w, rc ? rule : best, photo_flush_for_runs(rc ? rule : best));

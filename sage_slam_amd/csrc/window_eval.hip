@@ -362,26 +362,43 @@ static AssembleParams window_assemble_params(SageWindow *w)
 // (dst then must hold zeros everywhere else: packed_loc)
 // merge: the merged linearize of the two factor types (LaunchCommon::merge_geo_weight) -- the per-edge results are then
 // mixed (sage_window_get_edge), the assembled system is the same
-int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks, bool merge)
+int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks, bool merge, bool stale_only)
 {
   if (!w || !w->finalized)
     return SAGE_E_STATE;
   const SageWindowConfig &c = w->cfg;
   const int H = (int)c.pyr.cam[0].h, W = (int)c.pyr.cam[0].w;
+  // SAGE_RELIN_STALE: the edges this call evaluates, their depth maps rebuilt and their compacted plan on the device; the
+  // main kernels take the edge from WorkItem::edge and the partial slot from the block index or the (compacted) record plan
+  RelinLaunch rl;
+  if (stale_only)
+  {
+    if (const int rcr = relin_prepare(w, rl))
+      return rcr;
+    if (rl.nothing)
+      return SAGE_OK;
+  }
   // a rank -- or a whole window -- whose links all carry keypoint terms only has no dense edge: no depth batch, no dense
-  // kernel and no per-edge finalize then (a launch with a zero grid is an error); its terms are linearized all the same
-  const bool dense = w->n_edges > 0;
+  // kernel and no per-edge finalize then (a launch with a zero grid is an error); its terms are linearized all the same.
+  // The same holds for a stale-mode call that finds no dense edge stale
+  const bool dense = stale_only ? rl.any() : w->n_edges > 0;
+  const bool lin_photo = c.use_photo && (!stale_only || rl.n_edges[kPhoto] > 0);
+  const bool lin_geo = c.use_geo && (!stale_only || rl.n_edges[kGeo] > 0);
   LaunchCommon lcg{}, lcp{};
-  merge = merge && w->merge_ok;
+  merge = merge && w->merge_ok && !stale_only;
   if (dense)
   {
-    // depth maps of every keyframe at the current variables: both factor types read their sample depths from them
-    // (an accepted candidate's maps from the error pass are still valid: only the gradients are missing then)
-    const bool have_depth = w->dpt_set == set;
-    SAGE_HIP(launch_depth_batch(w->stream, c.CS, w->depth_items[set].as<DepthItem>(), w->n_depth, H, W, !have_depth,
-                                !(have_depth && w->dgrad_valid)));
-    w->dpt_set = set;
-    w->dgrad_valid = true;
+    if (!stale_only)
+    {
+      // depth maps of every keyframe at the current variables: both factor types read their sample depths from them
+      // (an accepted candidate's maps from the error pass are still valid: only the gradients are missing then)
+      const bool have_depth = w->dpt_set == set, have_grad = have_depth && w->dgrad_valid;
+      SAGE_HIP(launch_depth_batch(w->stream, c.CS, w->depth_items[set].as<DepthItem>(), w->n_depth, H, W, !have_depth, !have_grad));
+      w->dpt_set = set;
+      w->dgrad_valid = true;
+      relin_stamp_maps(w, set, !have_depth, !have_grad);
+      relin_count_all(w, true, !have_depth, !have_grad);
+    }
     // main kernels only (stage 1), then ONE finalize launch for both factor types (window_finalize_kernel)
     ++w->dense_serial; // the per-edge AtA are about to be rewritten (sage_window_prepare_factors_device)
     lcg = window_lc(w, kGeo);
@@ -389,13 +406,19 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     lcg.stage = 1;
     lcp.stage = 1;
     lcg.merge_geo_weight = lcp.merge_geo_weight = merge ? c.geo_weight : 0.f;
-    if (c.use_geo)
+    if (stale_only)
+    {
+      // the sub work lists; the per-edge item / record counts are the full plan's
+      lcg.work = rl.work[kGeo]; lcg.edge_first = rl.first[kGeo]; lcg.n_work = rl.n_items[kGeo];
+      lcp.work = rl.work[kPhoto]; lcp.edge_first = rl.first[kPhoto]; lcp.n_work = rl.n_items[kPhoto];
+    }
+    if (lin_geo)
     {
       prof_attach(w, 1, lcg);
       SAGE_HIP(launch_geo_linearize(w->stream, c.CS, nullptr, w->dense[kGeo].tab[set].as<GeoEdge>(), lcg, c.pyr.cam[0], c.eps,
                                     c.geo_loss_param, c.geo_weight, w->dense[kGeo].out()));
     }
-    if (c.use_photo)
+    if (lin_photo)
     {
       prof_attach(w, 0, lcp);
       SAGE_HIP(launch_photo_linearize(w->stream, c.CS, c.FS, nullptr, w->dense[kPhoto].tab[set].as<PhotoEdge>(), lcp, c.pyr,
@@ -407,12 +430,14 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
   if (dense)
   {
     WindowFinalizeParams fp{};
-    fp.n_p = c.use_photo ? w->n_edges : 0;
-    fp.n_g = c.use_geo ? w->n_edges : 0;
+    fp.n_p = !lin_photo ? 0 : (stale_only ? rl.n_edges[kPhoto] : w->n_edges);
+    fp.n_g = !lin_geo ? 0 : (stale_only ? rl.n_edges[kGeo] : w->n_edges);
     finalize_side<PhotoEdge>(fp.ph, w->dense[kPhoto], set, lcp);
     fp.ph.wsum = photo_weight_sum(c);
+    fp.ph.edge_list = rl.list[kPhoto]; // (null unless stale_only: workgroup j handles edge j)
     finalize_side<GeoEdge>(fp.ge, w->dense[kGeo], set, lcg);
     fp.ge.weight = c.geo_weight;
+    fp.ge.edge_list = rl.list[kGeo];
     if (merge)
     {
       fp.ge.photo_partials = lcp.partials;
@@ -451,6 +476,14 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
     w->dist.packed_reduced = false;
     w->dogleg.solved0 = w->dogleg.products = false; // (a new system: its Gauss-Newton point is yet to be solved for)
   }
+  if (stale_only)
+    relin_commit(w, rl);
+  else
+  {
+    if (!dense)
+      relin_count_all(w, false, false, false);
+    w->relin.drop(); // a merged linearize, one at the candidate, one assembled elsewhere: not what the snapshot stands for
+  }
   return SAGE_OK;
 }
 
@@ -458,7 +491,7 @@ extern "C" int sage_window_linearize(SageWindow *w)
 {
   if (w)
     window_phase_mark(w, 0); // a caller driving the iteration call by call: it starts here
-  return window_linearize_set(w, 0);
+  return window_linearize_set(w, 0, nullptr, false, false, w && w->relin.mode == SAGE_RELIN_STALE);
 }
 
 // a workgroup's partial record as the totals kernel reads it: floats per record, slot of the error sum, slot of the inlier count
@@ -499,7 +532,10 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     SAGE_HIP(launch_depth_batch(w->stream, c.CS, w->depth_items[which].as<DepthItem>(), w->n_depth, H, W, true, false));
     w->dpt_set = which;
     w->dgrad_valid = false;
+    relin_stamp_maps(w, which, true, false);
   }
+  // (the per-edge statistics of this pass: the error half of DenseSide::stats -- the linearization's stay)
+  float *const stats_p = w->dense[kPhoto].error_stats(), *const stats_g = w->dense[kGeo].error_stats();
   ErrorTotalsSide ph{}, ge{};
   // both factor types: ONE kernel -- the photometric error kernel also evaluates the geometric edge at the same warp
   // (PhotoEdge::dpt1_geo), which saves the geometric launch (39 us + a gap) of the error pass
@@ -511,11 +547,11 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     lc.stage = 1; // main kernel only: the per-edge statistics are formed by error_totals_kernel below
     lc.fused_geo_loss_param = fused ? c.geo_loss_param : 0.f;
     SAGE_HIP(launch_photo_error(w->stream, c.CS, c.FS, nullptr, w->dense[kPhoto].tab[which].as<PhotoEdge>(), lc, c.pyr,
-                                c.photo_weights, c.eps, w->dense[kPhoto].stats.as<float>()));
-    ph = error_totals_side(lc, w->dense[kPhoto].stats.as<float>(), 10.0f * photo_weight_sum(c), 1.0f, w->n_edges,
+                                c.photo_weights, c.eps, stats_p));
+    ph = error_totals_side(lc, stats_p, 10.0f * photo_weight_sum(c), 1.0f, w->n_edges,
                            fused ? kFusedPhoto : kOwnRecord);
     if (fused)
-      ge = error_totals_side(lc, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kFusedGeo);
+      ge = error_totals_side(lc, stats_g, 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kFusedGeo);
   }
   if (has && c.use_geo && !fused)
   {
@@ -523,8 +559,8 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
     prof_attach(w, 3, lc);
     lc.stage = 1;
     SAGE_HIP(launch_geo_error(w->stream, c.CS, nullptr, w->dense[kGeo].tab[which].as<GeoEdge>(), lc, c.pyr.cam[0], c.eps,
-                              c.geo_loss_param, c.geo_weight, w->dense[kGeo].stats.as<float>()));
-    ge = error_totals_side(lc, w->dense[kGeo].stats.as<float>(), 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kOwnRecord);
+                              c.geo_loss_param, c.geo_weight, stats_g));
+    ge = error_totals_side(lc, stats_g, 10.0f * c.geo_weight, c.geo_weight, w->n_edges, kOwnRecord);
   }
   // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
   if (const int rct = window_launch_terms(w, which, false))
@@ -544,6 +580,7 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
   {
     SAGE_HIP(launch_depth_batch(w->stream, c.CS, w->depth_items[which].as<DepthItem>(), w->n_depth, H, W, false, true));
     w->dgrad_valid = true;
+    relin_stamp_maps(w, which, false, true);
   }
   return SAGE_OK;
 }

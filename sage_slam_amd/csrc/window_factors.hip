@@ -77,6 +77,11 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
     w->have_lin = false;
   }
   const size_t ne = (size_t)w->n_edges;
+  // SAGE_RELIN_STALE: the dense slots' host rows still mirror the device's per-edge results when no linearize has written
+  // those since the last pull -- an error-only prepass at other values in between leaves both alone.  The stale-mode
+  // linearize below then re-evaluates some edges, and only their rows are pulled
+  const bool stale_mode = w->relin.mode == SAGE_RELIN_STALE;
+  const bool rows_kept = stale_mode && jacobians && fc.rows_pulled && fc.rows_serial == w->dense_serial;
   if (jacobians)
   {
     if ((rc = sage_window_linearize(w)))
@@ -89,6 +94,23 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
     dst.resize(n);
     return n ? hipMemcpy(dst.data(), src, n * sizeof(float), hipMemcpyDeviceToHost) : hipSuccess;
   };
+  // rows `edges` (ascending) of a [n][width] array, a run of consecutive edges per copy
+  auto pull_rows = [](std::vector<float> &dst, const float *src, size_t width, const std::vector<int32_t> &edges) -> hipError_t {
+    for (size_t i = 0; i < edges.size();)
+    {
+      size_t j = i + 1;
+      while (j < edges.size() && edges[j] == edges[j - 1] + 1)
+        ++j;
+      const size_t at = (size_t)edges[i] * width;
+      const hipError_t e = hipMemcpy(dst.data() + at, src + at, (j - i) * width * sizeof(float), hipMemcpyDeviceToHost);
+      if (e != hipSuccess)
+        return e;
+      i = j;
+    }
+    return hipSuccess;
+  };
+  if (jacobians)
+    w->relin.counts.host_entries_pulled = 0;
   const TermSide &ts = w->terms;
   const bool with_terms = ts.n_stats() > 0;
   for (int sl = 0; sl < FactorCache::kSlots; ++sl)
@@ -105,12 +127,29 @@ extern "C" int sage_window_prepass(SageWindow *w, const float *pose12, const flo
       s.D = dense ? dense_dim(sl, CS) : (size_t)TermResults::dim(g, CS);
       s.live = dense ? &w->dense[sl].AtA : &ts.AtA[g];
       s.live_serial = dense ? &w->dense_serial : &ts.serial;
-      SAGE_HIP(pull(s.A, s.live->as<float>(), n * s.D * s.D));
-      SAGE_HIP(pull(s.b, dense ? w->dense[sl].Atb.as<float>() : ts.Atb[g].as<float>(), n * s.D));
+      if (dense && rows_kept && s.A.size() == n * s.D * s.D && s.b.size() == n * s.D)
+      {
+        const std::vector<int32_t> &ev = w->relin.evaluated[sl];
+        SAGE_HIP(pull_rows(s.A, s.live->as<float>(), s.D * s.D, ev));
+        SAGE_HIP(pull_rows(s.b, w->dense[sl].Atb.as<float>(), s.D, ev));
+        w->relin.counts.host_entries_pulled += (int32_t)ev.size();
+      }
+      else
+      {
+        SAGE_HIP(pull(s.A, s.live->as<float>(), n * s.D * s.D));
+        SAGE_HIP(pull(s.b, dense ? w->dense[sl].Atb.as<float>() : ts.Atb[g].as<float>(), n * s.D));
+        if (dense)
+          w->relin.counts.host_entries_pulled += (int32_t)n;
+      }
       s.serial = *s.live_serial;
     }
-    if (dense)
-      SAGE_HIP(pull(fc.stats[sl], w->dense[sl].stats.as<float>(), ne * 2));
+    if (dense) // the {error, inliers} this pass wrote: the linearization's half, or the error pass's
+      SAGE_HIP(pull(fc.stats[sl], jacobians ? w->dense[sl].stats.as<float>() : w->dense[sl].error_stats(), ne * 2));
+  }
+  if (jacobians)
+  {
+    fc.rows_pulled = true;
+    fc.rows_serial = w->dense_serial;
   }
   if (with_terms) // the {error, inliers} set this pass wrote
     SAGE_HIP(pull(fc.stats[2], ts.results(jacobians != 0).stats, (size_t)2 * ts.n_stats()));

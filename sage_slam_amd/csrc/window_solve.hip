@@ -277,6 +277,7 @@ extern "C" int sage_window_reset(SageWindow *w)
     return rc;
   w->have_lin = false;
   w->dist.emu_cur = 0;
+  w->relin.drop();
   return SAGE_OK;
 }
 

@@ -47,18 +47,24 @@ struct DenseSide
   DevBuf tab[2];              // edge table per variable set (PhotoEdge / GeoEdge)
   DevBuf work, first, tiles;  // work list: items, per edge its first item and its number of items
   DevBuf part;                // workgroup partials
-  DevBuf AtA, Atb, stats;     // per-edge results
+  DevBuf AtA, Atb;            // per-edge results
+  DevBuf stats;               // [2][n_res][2]: {error, inliers} of the last linearize, of the last error pass -- apart, as the
+                              // terms' are: the linearization's statistics of an edge survive an error pass at other values
   DevBuf wide;                // ... before their fp32 rounding (EdgeOut::wide)
   int n_work = 0, tpb = 1;
+  size_t n_res = 0;           // edges the result buffers have room for
+  std::vector<int32_t> h_tiles; // host copy of `tiles` (the stale-mode linearize sizes its grids from it)
   EdgeOut out() const { return EdgeOut{AtA.as<float>(), Atb.as<float>(), stats.as<float>(), wide.as<double>()}; }
+  float *error_stats() const { return stats.as<float>() + 2 * n_res; } // the error pass's half
   // room for the results of `ne` edges with D columns and for `records` partials of `partial_floats` floats
   int reserve_results(size_t ne, size_t D, size_t records, size_t partial_floats)
   {
     int rc;
     if ((rc = part.reserve(std::max<size_t>(1, records) * partial_floats * sizeof(float))) ||
         (rc = AtA.reserve(ne * D * D * sizeof(float))) || (rc = Atb.reserve(ne * D * sizeof(float))) ||
-        (rc = stats.reserve(ne * 2 * sizeof(float))) || (rc = wide.reserve(ne * (D * D + D) * sizeof(double))))
+        (rc = stats.reserve(2 * ne * 2 * sizeof(float))) || (rc = wide.reserve(ne * (D * D + D) * sizeof(double))))
       return rc;
+    n_res = ne;
     return 0;
   }
 };
@@ -141,6 +147,10 @@ struct FactorCache
   // {error, inliers} of the pass the cache was pulled from: [kPhoto], [kGeo] per local directed edge, [2] per term (n_stats)
   std::vector<float> stats[kStatSets];
   int psd_mode = -1;                    // < 0: the projected matrices are not prepared for the cached linearisation
+  // SAGE_RELIN_STALE: the dense slots' host rows are kept while they mirror the device's per-edge results (the values those
+  // stand for: RelinSide's snapshot) -- the count of SageWindow::dense_serial at the last pull, once there was one
+  bool rows_pulled = false;
+  uint64_t rows_serial = 0;
   int psd_launches = 0;                 // sage_window_prepare_factors_device: what the last call launched ...
   SagePsdStats psd_worst{};             // ... and its worst record
 };
@@ -150,6 +160,40 @@ struct PhotoRecordPlan
 {
   DevBuf first, count;
   int flush = 0, n = 0;
+  std::vector<int32_t> h_count; // host copy of `count`
+};
+
+// ---- partial relinearization (sage_window_set_relinearization, window_relin.hip).  The snapshot: the values every per-edge
+// linearization on the device stands for -- after a stale-mode linearize each edge was either evaluated at them or read
+// nothing that differs from them.  The stamps: depth maps are shared by the variable sets and rewritten by every error pass,
+// so each keyframe's map carries the code and scale bits it was built from and whether its gradient was built from it ----
+struct RelinSide
+{
+  int mode = 0;                          // SAGE_RELIN_*
+  bool valid = false;                    // the snapshot holds; false: every edge is stale
+  bool packed_current = false;           // `packed` was assembled from the results the snapshot stands for
+  std::vector<float> pose, code, scale;  // the snapshot: [K][12], [K][CS], [K]
+  std::vector<float> map_code, map_scale; // the stamps: [K][CS], [K] ...
+  std::vector<uint8_t> map_ok, grad_ok;  // ... [K]: the map / its gradient is what the stamp says
+  std::vector<DepthItem> depth_items;    // host copy of variable set 0's depth items, by keyframe ([K]; unused ones zero)
+  DevBuf work_sub[2], first_sub[2];      // per dense side: the stale edges' work items in their order; per edge (full
+                                         // length) the compacted first item, written at the stale edges' entries only
+  DevBuf rec_first_sub;                  // the same for the photometric linearize's partial records
+  DevBuf lists, depth_sub;               // what the host sends per call: stale edges and offsets; the depth items to rebuild
+  PinnedBuf stage_lists, stage_depth;    // ... as the host writes them; stage_free: the copies out of them have been made
+  hipEvent_t stage_free = nullptr;
+  bool stage_busy = false;
+  std::vector<int32_t> evaluated[2];     // local edges the last stale-mode linearize evaluated, ascending (a prepass pulls these rows)
+  SageEvalCounts counts{};               // sage_window_last_evaluation
+  void drop() { valid = packed_current = false; }
+  RelinSide() = default;
+  RelinSide(const RelinSide &) = delete;
+  RelinSide &operator=(const RelinSide &) = delete;
+  ~RelinSide()
+  {
+    if (stage_free)
+      (void)hipEventDestroy(stage_free);
+  }
 };
 
 // ---- pinned mirror of the totals, written by the kernels; the host spins on the tickets instead of synchronising ----
