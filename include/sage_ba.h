@@ -1810,6 +1810,75 @@ int sage_relin_marks(const double *delta, int K, int CS, const SageRelinThreshol
 int sage_window_relin_marks(const SageWindow *w, const SageRelinThresholds *t, int32_t *marks, int32_t *n_marked);
 int sage_window_accept_marked(SageWindow *w, const int32_t *marks);
 
+/* =====================================================================
+ * Prepared keyframes: a keyframe's pose-independent preparation, done once and shared between windows
+ * =====================================================================
+ * sage_window_finalize prepares every keyframe it was given as a view: the channel-group relay of its pyramids with the level's
+ * focal lengths and sqrt(w_l) folded in, its sampled locations validated and relaid in 8 x 8 tile order (tile-padded where that
+ * is cheap), its pre-sampled source features.  None of that depends on a pose, a code, a scale, a link or on who else is in
+ * the window, and the mapper builds a window per new keyframe over keyframes it has seen before.  A SagePreparedKeyframe holds
+ * that preparation; any number of windows borrow it, in any mix with views, and skip those stages for it.
+ *
+ * A prepare call reads pyr, FS and photo_weights from cfg, nothing else, and the process's SAGE_SAMPLE_TILE / SAGE_SAMPLE_PAD
+ * switches as finalize does; the handle records all of them.  It OWNS the relaid planes, the ordered sample arrays and the
+ * pre-sampled features (one device allocation, sized from N before any launch: cap = max(1, ceil(5 N / 4)) sample slots --
+ * the padded order is only ever chosen at slots <= 1.25 N) and BORROWS the view's feat_pyr, grad_pyr, bias, basis, loc1d and
+ * homo, which must outlive the handle as they must outlive a window (the texture-path sampler and an unordered keyframe
+ * still read them).  The handle is immutable once the call returns, and the call returns with the workspace's stream
+ * synchronised: any window on any stream or host thread of the SAME DEVICE may take it -- a handle belongs to the device it
+ * was prepared on.  The reference count is atomic: the caller's reference, one per window that holds the handle
+ * (sage_window_add_prepared_keyframe retains; sage_window_destroy releases); the last release frees.
+ *
+ * sage_keyframe_prepare_batch: B keyframes in launches that do not depend on B -- one relay kernel over all 3 B planes, the
+ * batched location sort (two fills, mark, order), one wait for status and tile counts, a second ordering pass and wait only
+ * if some keyframe takes the padded order, one pre-sampling kernel, the final wait: 6 launches and 2 waits, or 7 and 3.
+ * sage_keyframe_prepare is the batch of one.  SAGE_E_INVALID, and no handle left behind (every out[b] NULL): a NULL
+ * argument or view pointer, N < 0, B < 1, B > SAGE_PREPARE_MAX_BATCH, FS % 4 != 0 or FS < 4, a pyramid of no or too many
+ * levels, a negative or NaN level weight, a location outside the image.
+ * sage_keyframe_prepare_plan (host only; every output pointer may be NULL): per keyframe the bytes of its allocation, the
+ * bytes of the call's scratch on the workspace, and the launches and waits of a batch without a padded keyframe.
+ * sage_keyframe_prepare_launches: what the last prepare call on ws launched.
+ * sage_keyframe_config_matches: 1 when two configurations prepare a keyframe alike -- pyr, FS and photo_weights bit for bit
+ * -- else 0; the comparison sage_window_add_prepared_keyframe makes between the handle's record and its window.
+ * sage_keyframe_get (parity tests; synchronises the device): SAGE_PREP_PACKED the three relaid planes [3][FS/4][P][4] floats,
+ * SAGE_PREP_LOC the `slots` int64 locations, SAGE_PREP_HOMO the [slots][3] rays, SAGE_PREP_F0S the [L][FS/4][slots][4]
+ * pre-sampled floats; `bytes` must be the array's size.  Of a keyframe with ordered == 0 LOC and HOMO are the caller's.
+ *
+ * sage_window_add_prepared_keyframe: as sage_window_add_keyframe, the keyframe id.  SAGE_E_STATE after finalize, SAGE_E_INVALID
+ * for NULL and for a handle whose recorded pyr / FS / photo_weights / sample switches are not bit-equal to the window's.
+ * Stages 3-5 of finalize then run for the views only (a window without views launches nothing there); nothing else in the
+ * window notices the difference, and a window built from handles computes bit for bit what its twin from views computes.
+ * sage_window_build_stats: what stages 3-5 of the last finalize did. */
+typedef struct SagePreparedKeyframe SagePreparedKeyframe;
+#define SAGE_PREPARE_MAX_BATCH 64           /* the headline window in one call */
+enum { SAGE_PREP_PACKED = 0, SAGE_PREP_LOC = 1, SAGE_PREP_HOMO = 2, SAGE_PREP_F0S = 3 };
+
+typedef struct SagePreparedInfo {           /* host */
+  int32_t N;            /* the caller's samples                                             */
+  int32_t slots;        /* what a window's kernels walk: N, or 64 * tiles when padded       */
+  int32_t ordered;      /* 0: a pixel was sampled twice, the caller's order and arrays are kept */
+  int32_t padded;       /* 1: tile-padded order (holes = location -1, ray (0,0,1))          */
+  int32_t refs;         /* the caller's reference + one per window that holds it            */
+  uint64_t device_bytes;
+} SagePreparedInfo;
+
+int  sage_keyframe_prepare(SageWorkspace *ws, const SageWindowConfig *cfg, const SageKeyframeView *view,
+                           SagePreparedKeyframe **out);
+int  sage_keyframe_prepare_batch(SageWorkspace *ws, const SageWindowConfig *cfg, const SageKeyframeView *views, int B,
+                                 SagePreparedKeyframe **out /* [B] */);
+int  sage_keyframe_prepare_plan(const SageWindowConfig *cfg, const int32_t *N /* [B] */, int B,
+                                uint64_t *device_bytes /* [B] */, uint64_t *scratch_bytes, int *launches, int *waits);
+int  sage_keyframe_prepare_launches(const SageWorkspace *ws);   /* of the last prepare call on ws */
+int  sage_keyframe_config_matches(const SageWindowConfig *a, const SageWindowConfig *b);
+int  sage_keyframe_info(const SagePreparedKeyframe *pk, SagePreparedInfo *out);
+int  sage_keyframe_get(const SagePreparedKeyframe *pk, int what, void *host, size_t bytes);   /* parity tests */
+void sage_keyframe_release(SagePreparedKeyframe *pk);            /* NULL: no-op */
+
+int  sage_window_add_prepared_keyframe(SageWindow *w, SagePreparedKeyframe *pk, const float *pose12,
+                                       const float *code, float scale);   /* returns the keyframe id, as add_keyframe */
+typedef struct SageWindowBuildStats { int32_t keyframes, prepared, repacked, ordered, presampled, launches; } SageWindowBuildStats;
+int  sage_window_build_stats(const SageWindow *w, SageWindowBuildStats *out);   /* stages 3-5 of the last finalize */
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,9 @@ SYMBOLS = [
     "sage_window_get_dogleg_vectors",
     "sage_relin_plan", "sage_window_set_relinearization", "sage_window_last_evaluation", "sage_relin_marks",
     "sage_window_relin_marks", "sage_window_accept_marked",
+    "sage_keyframe_prepare", "sage_keyframe_prepare_batch", "sage_keyframe_prepare_plan", "sage_keyframe_prepare_launches",
+    "sage_keyframe_config_matches", "sage_keyframe_info", "sage_keyframe_get", "sage_keyframe_release",
+    "sage_window_add_prepared_keyframe", "sage_window_build_stats",
 ]
 
 
@@ -307,6 +310,8 @@ def lib():
         L.sage_error_string.restype = C.c_char_p
         L.sage_window_packed_count.restype = C.c_size_t
         L.sage_shutdown.restype = None
+        L.sage_keyframe_release.restype = None
+        L.sage_keyframe_release.argtypes = [C.c_void_p]
         L.sage_window_packed_dev.restype = C.c_void_p
         L.sage_window_error_dev.restype = C.c_void_p
         L.sage_window_residuals_per_linearize.restype = C.c_double
@@ -1271,6 +1276,138 @@ class DeviceKeyframe:
                                 self.basis.data_ptr(), self.loc1d.data_ptr(), self.homo.data_ptr(), self.N)
 
 
+# --------------------------------------------------------------------------- prepared keyframes
+SAGE_PREPARE_MAX_BATCH = 64
+SAGE_PREP_PACKED, SAGE_PREP_LOC, SAGE_PREP_HOMO, SAGE_PREP_F0S = 0, 1, 2, 3
+
+
+class SagePreparedInfo(C.Structure):
+    _fields_ = [("N", C.c_int32), ("slots", C.c_int32), ("ordered", C.c_int32), ("padded", C.c_int32), ("refs", C.c_int32),
+                ("device_bytes", C.c_uint64)]
+
+
+class SageWindowBuildStats(C.Structure):
+    _fields_ = [("keyframes", C.c_int32), ("prepared", C.c_int32), ("repacked", C.c_int32), ("ordered", C.c_int32),
+                ("presampled", C.c_int32), ("launches", C.c_int32)]
+
+
+def prepare_config(win) -> SageWindowConfig:
+    """what a prepare call reads of a window's configuration (pyr, FS, photo_weights; CS rides along), from a
+    ``synth.make_window`` window"""
+    cfg = SageWindowConfig()
+    cfg.pyr = make_pyramid(win.cams[0], win.L)
+    cfg.FS, cfg.CS = win.FS, win.CS
+    for l in range(win.L):
+        cfg.photo_weights[l] = float(win.photo_weights[l])
+    return cfg
+
+
+def keyframe_prepare_batch_raw(ws_handle, cfg_ptr, views_ptr, B, out_ptr) -> int:
+    """``sage_keyframe_prepare_batch`` with its arguments as given (NULL / 0 included) -> status code"""
+    f = lib().sage_keyframe_prepare_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    return int(f(ws_handle, cfg_ptr, views_ptr, B, out_ptr))
+
+
+def keyframe_prepare_plan_raw(cfg_ptr, N_ptr, B, device_bytes_ptr, scratch_ptr, launches_ptr, waits_ptr) -> int:
+    f = lib().sage_keyframe_prepare_plan
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    return int(f(cfg_ptr, N_ptr, B, device_bytes_ptr, scratch_ptr, launches_ptr, waits_ptr))
+
+
+def keyframe_prepare_plan(cfg: SageWindowConfig, N) -> dict:
+    """``sage_keyframe_prepare_plan`` (host only): per keyframe the bytes of its handle's allocation, the call's scratch on the
+    workspace, and the launches and waits of a batch without a tile-padded keyframe (one more of each with one)"""
+    n = np.ascontiguousarray(N, dtype=np.int32).reshape(-1)
+    dev = np.zeros(max(1, n.size), dtype=np.uint64)
+    scratch, launches, waits = C.c_uint64(0), C.c_int(0), C.c_int(0)
+    _chk(keyframe_prepare_plan_raw(C.byref(cfg), n.ctypes.data, int(n.size), dev.ctypes.data, C.byref(scratch),
+                                   C.byref(launches), C.byref(waits)), "sage_keyframe_prepare_plan")
+    return dict(device_bytes=[int(x) for x in dev[:n.size]], scratch_bytes=int(scratch.value), launches=int(launches.value),
+                waits=int(waits.value))
+
+
+def keyframe_prepare_launches(ws: "Workspace") -> int:
+    f = lib().sage_keyframe_prepare_launches
+    f.argtypes = [C.c_void_p]
+    return int(f(ws.h))
+
+
+def keyframe_config_matches(a: SageWindowConfig, b: SageWindowConfig) -> bool:
+    """would a keyframe prepared under ``a`` be taken by a window of ``b``?  (pyr, FS, photo_weights, bit for bit)"""
+    f = lib().sage_keyframe_config_matches
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    r = int(f(C.byref(a), C.byref(b)))
+    if r < 0:
+        raise SageError(r, "sage_keyframe_config_matches")
+    return r == 1
+
+
+def keyframe_info_raw(handle) -> SagePreparedInfo:
+    """``sage_keyframe_info`` of a raw handle (a window may keep a handle alive whose caller has released it)"""
+    f = lib().sage_keyframe_info
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    out = SagePreparedInfo()
+    _chk(int(f(handle, C.byref(out))), "sage_keyframe_info")
+    return out
+
+
+class PreparedKeyframe:
+    """``SagePreparedKeyframe``: a keyframe's pose-independent preparation (relaid planes, ordered samples, pre-sampled source
+    features), made once and shared between windows (``Window(..., prepared={kf: handle})``).  Holds the caller's reference
+    and keeps the device arrays the handle borrows (``dk``) alive."""
+
+    def __init__(self, handle: int, dk: DeviceKeyframe, cfg: SageWindowConfig):
+        self.h = C.c_void_p(handle)
+        self.dk = dk
+        self.cfg = cfg
+
+    @classmethod
+    def prepare(cls, ws: "Workspace", cfg: SageWindowConfig, dk: DeviceKeyframe) -> "PreparedKeyframe":
+        """``sage_keyframe_prepare``"""
+        f = lib().sage_keyframe_prepare
+        f.argtypes = [C.c_void_p] * 4
+        v, out = dk.view(), C.c_void_p()
+        _chk(int(f(ws.h, C.byref(cfg), C.byref(v), C.byref(out))), "sage_keyframe_prepare")
+        return cls(out.value, dk, cfg)
+
+    @classmethod
+    def prepare_batch(cls, ws: "Workspace", cfg: SageWindowConfig, dks) -> list:
+        """``sage_keyframe_prepare_batch``: B keyframes in the launches of one"""
+        dks = list(dks)
+        views = (SageKeyframeView * max(1, len(dks)))(*[dk.view() for dk in dks])
+        out = (C.c_void_p * max(1, len(dks)))()
+        _chk(keyframe_prepare_batch_raw(ws.h, C.byref(cfg), views, len(dks), out), "sage_keyframe_prepare_batch")
+        return [cls(out[b], dk, cfg) for b, dk in enumerate(dks)]
+
+    def info(self) -> SagePreparedInfo:
+        return keyframe_info_raw(self.h)
+
+    def get(self, what: int) -> np.ndarray:
+        """``sage_keyframe_get``: SAGE_PREP_PACKED [3, FS/4, P, 4] f32, _LOC [slots] i64, _HOMO [slots, 3] f32, _F0S
+        [L, FS/4, slots, 4] f32"""
+        i, FS, L, P = self.info(), self.cfg.FS, self.cfg.pyr.levels, self.cfg.pyr.P
+        shape, dtype = {SAGE_PREP_PACKED: ((3, FS // 4, P, 4), np.float32), SAGE_PREP_LOC: ((i.slots,), np.int64),
+                        SAGE_PREP_HOMO: ((i.slots, 3), np.float32), SAGE_PREP_F0S: ((L, FS // 4, i.slots, 4), np.float32)}[what]
+        a = np.zeros(shape, dtype=dtype)
+        f = lib().sage_keyframe_get
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        _chk(int(f(self.h, int(what), a.ctypes.data, a.nbytes)), "sage_keyframe_get")
+        return a
+
+    def release(self):
+        """drops the caller's reference (``sage_keyframe_release``); windows that hold the handle keep it alive"""
+        if self.h:
+            lib().sage_keyframe_release(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 def photometric_jac_error(ws: Workspace, R10, t10, R0, t0, R1, t1, bias0, basis0, code0, mask1, loc1d, homo,
                           feat0, feat1, grad1, scale0, pyr: SagePyramid, eps, weights, FS, CS):
     """``df::photometric_jac_error_calculate<CS,FS>``; poses/code are small host arrays uploaded here (the
@@ -1402,7 +1539,7 @@ class Window:
 
     def __init__(self, win, rank: int = 0, world: int = 1, stream=None, use_photo=True, use_geo=True,
                  code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None,
-                 keypoint_links=None, holds=None, graph_terms=None):
+                 keypoint_links=None, holds=None, graph_terms=None, prepared=None):
         """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches`` /
         ``make_loop_mg_*``, or by hand): kind ("reprojection" | "match_geometry" | "loop_mg"), edge (2 * link + direction),
         loc0 [N] int32, homo0 [N,3], matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry,
@@ -1413,13 +1550,17 @@ class Window:
         ``holds``: optional dict keyframe -> mask of SAGE_HOLD_* (``sage_window_hold``).
         ``graph_terms``: optional list of dicts as ``graph_term_struct`` takes them (``synth.make_pose_graph`` makes the
         reference's loop-closure graph), added with ``sage_window_add_graph_term``.
+        ``prepared``: optional dict keyframe id -> ``PreparedKeyframe``: those keyframes are added by handle
+        (``sage_window_add_prepared_keyframe``: the window borrows their preparation, and their device arrays), the others as views.
         All are added before the finalize this constructor performs."""
         import torch
         self.win = win
         self.pyr = make_pyramid(win.cams[0], win.L)
         assert self.pyr.P == win.P
         self.mask = _dev(win.mask, np.float32)
-        self.kfs = [DeviceKeyframe(kf, win.H, win.W) for kf in win.keyframes]
+        self.prepared = dict(prepared or {})
+        self.kfs = [self.prepared[k].dk if k in self.prepared else DeviceKeyframe(kf, win.H, win.W)
+                    for k, kf in enumerate(win.keyframes)]
         cfg = SageWindowConfig()
         cfg.pyr = self.pyr
         cfg.FS, cfg.CS = win.FS, win.CS
@@ -1435,10 +1576,15 @@ class Window:
         sp = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(0)
         L = lib()
         _chk(L.sage_window_create(C.byref(cfg), sp, C.byref(self.h)), "sage_window_create")
-        for kf, dk in zip(win.keyframes, self.kfs):
-            v = dk.view()
+        for k, (kf, dk) in enumerate(zip(win.keyframes, self.kfs)):
             pose = pack_pose(kf.R, kf.t)
             code = _f32(kf.code)
+            if k in self.prepared:
+                r = self.add_prepared_keyframe(self.prepared[k], pose, code, kf.scale)
+                if r < 0:
+                    raise SageError(r, "sage_window_add_prepared_keyframe")
+                continue
+            v = dk.view()
             r = L.sage_window_add_keyframe(self.h, C.byref(v), _fp(pose), _fp(code), C.c_float(kf.scale))
             if r < 0:
                 raise SageError(r, "sage_window_add_keyframe")
@@ -1476,6 +1622,23 @@ class Window:
         self.packed_count = L.sage_window_packed_count(self.h)
         self.residuals_per_linearize = L.sage_window_residuals_per_linearize(self.h)
         self.bytes_per_linearize = L.sage_window_bytes_per_linearize(self.h)
+
+    def add_prepared_keyframe(self, pk, pose12, code, scale) -> int:
+        """``sage_window_add_prepared_keyframe`` -> keyframe id, or the negative status code (``pk``: a ``PreparedKeyframe``,
+        or None for NULL)"""
+        f = lib().sage_window_add_prepared_keyframe
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
+        pose, code = _f32(pose12), _f32(code)
+        return int(f(self.h, pk.h if pk is not None else None, pose.ctypes.data, code.ctypes.data, float(scale)))
+
+    def build_stats(self) -> SageWindowBuildStats:
+        """``sage_window_build_stats``: what stages 3-5 of the last finalize did (keyframes, prepared, repacked, ordered,
+        presampled, launches)"""
+        f = lib().sage_window_build_stats
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = SageWindowBuildStats()
+        _chk(int(f(self.h, C.byref(out))), "sage_window_build_stats")
+        return out
 
     def add_keypoint_link(self, a, b) -> int:
         """``sage_window_add_keypoint_link`` -> link id, or the negative status code"""

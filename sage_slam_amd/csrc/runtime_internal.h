@@ -29,6 +29,9 @@
 //   dogleg_host.cpp     (no HIP) the dogleg point, gtsam's trust-region policy around a callback, the incidence lists
 //   window_profile.hip  optional kernel timing of a window: event pool, per-kernel event pairs, phase marks
 //   window_build.hip    building a window: create / add / finalize (stages; policy in window_plan.h), run plan and its tuning
+//   keyframe_prepare.hip  prepared keyframes (sage_keyframe_prepare_batch): stages 3-5 of finalize for B keyframes outside any
+//                       window, its two batch kernels, the handle's reference count
+//   keyframe_prepare_host.cpp  (no HIP) the configuration fingerprint, the checks, the layouts and the plan (keyframe_prepare.h)
 //   window_terms.hip    keypoint and pose-graph terms: add / get, their finalize stage, their two launches
 //   window_dist.hip     sharded windows: NUMA placement, all-reduce hook, native RCCL binding
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
@@ -88,6 +91,7 @@ extern "C"
 #include "depth_scale_plan.h"  // SelBatchPlan
 #include "loop_accept.h"       // sage_loop_accept's host rules
 #include "dogleg.h"            // the dogleg step's dots, partial slots and pinned record
+#include "keyframe_prepare.h"  // a prepared keyframe's fingerprint, layout and plan; the handle itself
 
 using namespace sage;
 
@@ -264,6 +268,10 @@ struct SageWorkspace
   // batched projection (sage_factor_psd_batch: psd_project.hip): the matrices' pinned records [n]; what the last call launched
   PinnedBuf psd_host;
   int psd_launches = 0;
+  // prepared keyframes (sage_keyframe_prepare_batch: keyframe_prepare.hip): the call's tables, mark planes, status and tile
+  // counts (PrepScratch, keyframe_prepare.h); what the last call launched
+  DevBuf prep_scratch;
+  int prep_launches = 0;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }
@@ -352,6 +360,25 @@ struct ErrorTotalsSide
 
 #include "window_state.h"
 
+// a prepared keyframe (keyframe_prepare.hip): stages 3-5 of sage_window_finalize for one keyframe, done once.  Immutable once
+// sage_keyframe_prepare_batch has returned, refs apart: windows on any stream or host thread of its device read it
+struct SagePreparedKeyframe
+{
+  std::atomic<int> refs{1};        // the caller's reference + one per window that holds it; the last release frees
+  sage::prep::Fingerprint fp;      // what it was prepared under: a window takes it only under the same
+  SageKeyframeView view;           // the caller's arrays, borrowed (N: the caller's samples)
+  int slots = 0;                   // what a window's kernels walk: N, or 64 x tiles (padded)
+  int ordered = 0, padded = 0;     // ordered 0: a pixel sampled twice -- loc / homo below are the caller's
+  sage::prep::Layout lay;
+  DevBuf mem;                      // planes | locations | rays | pre-sampled source features (lay)
+  const float *pk = nullptr;       // [3 (f, gx, gy)][FS/4][P][4]
+  const int64_t *loc = nullptr;    // [slots]
+  const float *homo = nullptr;     // [slots][3]
+  const float *f0s = nullptr;      // negated, [L][FS/4][slots][4]
+};
+void prepared_retain(SagePreparedKeyframe *pk);
+void prepared_release(SagePreparedKeyframe *pk); // (sage_keyframe_release)
+
 struct SageWindow
 {
   SageWindowConfig cfg;
@@ -360,6 +387,10 @@ struct SageWindow
   int rank = 0, world = 1;
   int K = 0, B = 0, VS = 0; // VS: floats per keyframe in the device variable array
   std::vector<SageKeyframeView> views;
+  std::vector<SagePreparedKeyframe *> prepared; // per keyframe: the handle it was added by (a reference held), or null: a view
+  std::vector<const float *> kf_pk, kf_f0s;     // (finalize) per keyframe: its relaid planes and pre-sampled source features,
+                                                // the window's own (pk, f0s below) or its handle's
+  SageWindowBuildStats build_stats{};           // stages 3-5 of the last finalize
   HostVars hv;                      // host variables of both sets, their initial values
   std::vector<float> link_geo_loss; // per link: the geometric factors' Cauchy parameter, 0 = cfg.geo_loss_param
   std::vector<std::pair<int, int>> links; // (a, b) with a < b

@@ -43,19 +43,19 @@ extern "C" void sage_window_destroy(SageWindow *w)
   } last_out;
   // device buffers, the pinned mirror and the profiler's events go with their owners (DevBuf, TotalsMirror, WindowProfiler)
   std::free(w->dist.rccl_hook); // (the communicator itself belongs to the caller)
+  for (SagePreparedKeyframe *pk : w->prepared)
+    prepared_release(pk); // (null: a keyframe added as a view)
   sage_shard_plan_destroy(w->dist.shard);
   solver_destroy(w->solver);
   delete w;
 }
 
-extern "C" int sage_window_add_keyframe(SageWindow *w, const SageKeyframeView *v, const float *pose12,
-                                        const float *code, float scale)
+// a keyframe's arrays, its handle (null: added as a view) and its variables
+static int add_keyframe(SageWindow *w, const SageKeyframeView *v, SagePreparedKeyframe *pk, const float *pose12, const float *code,
+                        float scale)
 {
-  if (!w || !v || !pose12 || !code || w->finalized)
-    return SAGE_E_INVALID;
-  if (!v->feat_pyr || !v->grad_pyr || !v->bias || !v->basis || !v->loc1d || !v->homo || v->N < 0)
-    return SAGE_E_INVALID;
   w->views.push_back(*v);
+  w->prepared.push_back(pk);
   for (int s = 0; s < 2; ++s)
   {
     w->hv.pose[s].insert(w->hv.pose[s].end(), pose12, pose12 + 12);
@@ -66,6 +66,40 @@ extern "C" int sage_window_add_keyframe(SageWindow *w, const SageKeyframeView *v
   w->hv.code_added.insert(w->hv.code_added.end(), code, code + w->cfg.CS);
   w->hv.scale_init.push_back(scale);
   return w->K++;
+}
+
+extern "C" int sage_window_add_keyframe(SageWindow *w, const SageKeyframeView *v, const float *pose12,
+                                        const float *code, float scale)
+{
+  if (!w || !v || !pose12 || !code || w->finalized)
+    return SAGE_E_INVALID;
+  if (!v->feat_pyr || !v->grad_pyr || !v->bias || !v->basis || !v->loc1d || !v->homo || v->N < 0)
+    return SAGE_E_INVALID;
+  return add_keyframe(w, v, nullptr, pose12, code, scale);
+}
+
+// a keyframe by its handle: the window borrows the handle's planes, ordered samples and pre-sampled features instead of making
+// its own (stages 3-5 of finalize skip it) and holds a reference until it is destroyed.  Only a handle prepared under the
+// window's pyr / FS / photo_weights and the process's sample switches holds what the window itself would have made
+extern "C" int sage_window_add_prepared_keyframe(SageWindow *w, SagePreparedKeyframe *pk, const float *pose12, const float *code,
+                                                 float scale)
+{
+  if (!w || !pk || !pose12 || !code)
+    return SAGE_E_INVALID;
+  if (w->finalized)
+    return SAGE_E_STATE;
+  if (!prep::same_fingerprint(pk->fp, prep::fingerprint(w->cfg, prep::sample_switches())))
+    return SAGE_E_INVALID;
+  prepared_retain(pk);
+  return add_keyframe(w, &pk->view, pk, pose12, code, scale);
+}
+
+extern "C" int sage_window_build_stats(const SageWindow *w, SageWindowBuildStats *out)
+{
+  if (!w || !out)
+    return SAGE_E_INVALID;
+  *out = w->build_stats;
+  return SAGE_OK;
 }
 
 // a link: part of the solver's structure and of the packed buffer; dense = 0: keypoint terms only, no row of the dense edge tables
@@ -229,7 +263,8 @@ static int finalize_pyramids(SageWindow *w)
   const int FS = c.FS, K = w->K;
   int rc;
   const size_t plane_f = (size_t)FS * c.pyr.P;
-  if ((rc = w->pk.reserve((size_t)K * 3 * plane_f * sizeof(float))))
+  const size_t n_views = std::count(w->prepared.begin(), w->prepared.end(), nullptr); // (a prepared keyframe brings its planes)
+  if ((rc = w->pk.reserve(n_views * 3 * plane_f * sizeof(float))))
     return rc;
   // r05: every texel of level l also carries sqrt(w_l) (feat, fx d/dx, fy d/dy -- and with feat the pre-sampled source
   // features of stage 5): the products the kernels sum (h h^T, h r, r^2) then hold the level weight of
@@ -241,12 +276,22 @@ static int finalize_pyramids(SageWindow *w)
       return SAGE_E_INVALID;
     lvl_scale[l] = std::sqrt(c.photo_weights[l]);
   }
+  w->kf_pk.assign(K, nullptr);
+  size_t vi = 0; // views before keyframe k
   for (int k = 0; k < K; ++k)
   {
-    float *base = w->pk.as<float>() + (size_t)k * 3 * plane_f;
+    if (w->prepared[k])
+    {
+      w->kf_pk[k] = w->prepared[k]->pk;
+      continue;
+    }
+    float *base = w->pk.as<float>() + vi++ * 3 * plane_f;
     SAGE_HIP(launch_repack_groups(w->stream, base, w->views[k].feat_pyr, FS, c.pyr.P, 0, &c.pyr, lvl_scale));
     SAGE_HIP(launch_repack_groups(w->stream, base + plane_f, w->views[k].grad_pyr, FS, c.pyr.P, 1, &c.pyr, lvl_scale));
     SAGE_HIP(launch_repack_groups(w->stream, base + 2 * plane_f, w->views[k].grad_pyr + plane_f, FS, c.pyr.P, 2, &c.pyr, lvl_scale));
+    w->kf_pk[k] = base;
+    w->build_stats.repacked += 1;
+    w->build_stats.launches += 3;
   }
   return SAGE_OK;
 }
@@ -271,29 +316,46 @@ static int finalize_samples(SageWindow *w)
   }
   for (int k = 0; k < K; ++k)
     w->views[k].N = w->user_n[k];
-  // (capacity per keyframe: its samples, or -- tile-padded order -- every 8 x 8 tile of the image with all 64 slots)
-  const size_t cap_tiles = (size_t)(((int)c.pyr.cam[0].w + 7) / 8) * (size_t)(((int)c.pyr.cam[0].h + 7) / 8) * 64;
-  std::vector<size_t> soff(K + 1, 0);
-  int max_n = 0;
+  // a prepared keyframe brings its ordered samples (validated when it was prepared): the relay below is the views' alone
+  std::vector<int> vk; // the keyframes added as views, ascending
   for (int k = 0; k < K; ++k)
   {
-    soff[k + 1] = soff[k] + std::max<size_t>(std::max(1, w->views[k].N), cap_tiles);
-    max_n = std::max(max_n, w->views[k].N);
+    const SagePreparedKeyframe *h = w->prepared[k];
+    if (!h)
+    {
+      vk.push_back(k);
+      continue;
+    }
+    w->views[k].N = h->slots;
+    w->views[k].loc1d = h->loc;
+    w->views[k].homo = h->homo;
   }
-  if ((rc = w->sorted_loc.reserve(soff[K] * sizeof(int64_t))) || (rc = w->sorted_homo.reserve(soff[K] * 3 * sizeof(float))))
+  const int Kv = (int)vk.size();
+  if (Kv == 0)
+    return SAGE_OK;
+  // (capacity per keyframe: its samples, or -- tile-padded order -- every 8 x 8 tile of the image with all 64 slots)
+  const size_t cap_tiles = (size_t)(((int)c.pyr.cam[0].w + 7) / 8) * (size_t)(((int)c.pyr.cam[0].h + 7) / 8) * 64;
+  std::vector<size_t> soff(Kv + 1, 0);
+  int max_n = 0;
+  for (int j = 0; j < Kv; ++j)
+  {
+    soff[j + 1] = soff[j] + std::max<size_t>(std::max(1, w->views[vk[j]].N), cap_tiles);
+    max_n = std::max(max_n, w->views[vk[j]].N);
+  }
+  if ((rc = w->sorted_loc.reserve(soff[Kv] * sizeof(int64_t))) || (rc = w->sorted_homo.reserve(soff[Kv] * 3 * sizeof(float))))
     return rc;
-  std::vector<SortItem> items(K);
-  for (int k = 0; k < K; ++k)
-    items[k] = SortItem{reinterpret_cast<const long long *>(w->user_samples[k].first), w->user_samples[k].second,
-                        w->sorted_loc.as<long long>() + soff[k], w->sorted_homo.as<float>() + 3 * soff[k],
-                        w->views[k].N};
-  std::vector<int> status((size_t)2 * K, 0), tiles_nonempty(K, 0), pad_flags(K, 0);
+  std::vector<SortItem> items(Kv);
+  for (int j = 0; j < Kv; ++j)
+    items[j] = SortItem{reinterpret_cast<const long long *>(w->user_samples[vk[j]].first), w->user_samples[vk[j]].second,
+                        w->sorted_loc.as<long long>() + soff[j], w->sorted_homo.as<float>() + 3 * soff[j],
+                        w->views[vk[j]].N};
+  std::vector<int> status((size_t)2 * Kv, 0), tiles_nonempty(Kv, 0), pad_flags(Kv, 0);
   struct
   {
     DevBuf items, mark, status, tiles, pad;
   } d; // the relay's device temporaries (declared after the host vectors: released before they die)
-  if ((rc = upload(d.items, items, w->stream)) || (rc = d.mark.reserve((size_t)K * HW * sizeof(int))) ||
-      (rc = d.status.reserve((size_t)2 * K * sizeof(int))) || (rc = d.tiles.reserve((size_t)K * sizeof(int))))
+  if ((rc = upload(d.items, items, w->stream)) || (rc = d.mark.reserve((size_t)Kv * HW * sizeof(int))) ||
+      (rc = d.status.reserve((size_t)2 * Kv * sizeof(int))) || (rc = d.tiles.reserve((size_t)Kv * sizeof(int))))
     return rc;
   // walk order of the samples: image tiles of 8 x 8 pixels -- a wave's 64 consecutive samples then warp to a compact
   // footprint in every destination keyframe, which is what the LDS-staged sampler of the photometric linearize
@@ -305,10 +367,12 @@ static int finalize_samples(SageWindow *w)
         tw = th = 0;
     return std::make_pair(tw, th);
   }();
-  SAGE_HIP(launch_sort_locations(w->stream, d.items.as<SortItem>(), K, max_n, HW, d.mark.as<int>(), d.status.as<int>(),
+  SAGE_HIP(launch_sort_locations(w->stream, d.items.as<SortItem>(), Kv, max_n, HW, d.mark.as<int>(), d.status.as<int>(),
                                  (int)c.pyr.cam[0].w, tile.first, tile.second, nullptr, d.tiles.as<int>()));
+  w->build_stats.ordered = Kv;
+  w->build_stats.launches += max_n > 0 ? 4 : 3; // two fills, the mark pass, the ordering pass
   SAGE_HIP(hipMemcpyAsync(status.data(), d.status.p, status.size() * sizeof(int), hipMemcpyDeviceToHost, w->stream));
-  SAGE_HIP(hipMemcpyAsync(tiles_nonempty.data(), d.tiles.p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, w->stream));
+  SAGE_HIP(hipMemcpyAsync(tiles_nonempty.data(), d.tiles.p, (size_t)Kv * sizeof(int), hipMemcpyDeviceToHost, w->stream));
   SAGE_HIP(hipStreamSynchronize(w->stream));
   // r06 -- tile-padded order (producers.hip, order_locations_kernel): keyframes whose sampled tiles are not all full are relaid
   // with every sampled tile's 64 slots (holes = location -1), so that a wave of the kernels is one tile whatever the mask looks
@@ -316,40 +380,43 @@ static int finalize_samples(SageWindow *w)
   // sample set would grow several-fold and keeps the compact order).  SAGE_SAMPLE_PAD=0 turns it off.
   bool any_pad = false;
   if (tile.first * tile.second == 64 && !(getenv("SAGE_SAMPLE_PAD") && atoi(getenv("SAGE_SAMPLE_PAD")) == 0))
-    for (int k = 0; k < K; ++k)
+    for (int j = 0; j < Kv; ++j)
     {
-      const long long slots = 64ll * tiles_nonempty[k];
-      if (status[2 * k] == 0 && status[2 * k + 1] == w->views[k].N && slots > w->views[k].N && 4 * slots <= 5ll * w->views[k].N)
+      const int n = w->views[vk[j]].N;
+      const long long slots = 64ll * tiles_nonempty[j];
+      if (status[2 * j] == 0 && status[2 * j + 1] == n && slots > n && 4 * slots <= 5ll * n)
       {
-        pad_flags[k] = 1;
+        pad_flags[j] = 1;
         any_pad = true;
       }
     }
   if (any_pad)
   {
-    std::vector<int> status2((size_t)2 * K, 0);
+    std::vector<int> status2((size_t)2 * Kv, 0);
     if ((rc = upload(d.pad, pad_flags, w->stream)))
       return rc;
-    SAGE_HIP(launch_sort_locations(w->stream, d.items.as<SortItem>(), K, max_n, HW, d.mark.as<int>(), d.status.as<int>(),
+    SAGE_HIP(launch_sort_locations(w->stream, d.items.as<SortItem>(), Kv, max_n, HW, d.mark.as<int>(), d.status.as<int>(),
                                    (int)c.pyr.cam[0].w, tile.first, tile.second, d.pad.as<int>(), nullptr, true));
+    w->build_stats.launches += 1;
     SAGE_HIP(hipMemcpyAsync(status2.data(), d.status.p, status2.size() * sizeof(int), hipMemcpyDeviceToHost, w->stream));
     SAGE_HIP(hipStreamSynchronize(w->stream));
-    for (int k = 0; k < K; ++k)
-      if (pad_flags[k])
+    for (int j = 0; j < Kv; ++j)
+      if (pad_flags[j])
       {
-        if (status2[2 * k + 1] != 64 * tiles_nonempty[k])
+        if (status2[2 * j + 1] != 64 * tiles_nonempty[j])
           return SAGE_E_STATE;
-        w->views[k].N = status2[2 * k + 1]; // slots, holes included
+        w->views[vk[j]].N = status2[2 * j + 1]; // slots, holes included
       }
   }
-  for (int k = 0; k < K; ++k)
+  for (int j = 0; j < Kv; ++j)
   {
-    if (status[2 * k] > 0)
+    const int k = vk[j];
+    if (status[2 * j] > 0)
       return SAGE_E_INVALID; // a location outside the image
-    if (status[2 * k + 1] != w->user_n[k])
+    if (status[2 * j + 1] != w->user_n[k])
       continue; // (a pixel sampled twice: the compaction dropped a sample -> keep the caller's order)
-    w->views[k].loc1d = reinterpret_cast<const int64_t *>(items[k].loc_out);
-    w->views[k].homo = items[k].homo_out;
+    w->views[k].loc1d = reinterpret_cast<const int64_t *>(items[j].loc_out);
+    w->views[k].homo = items[j].homo_out;
   }
   return SAGE_OK;
 }
@@ -360,16 +427,26 @@ static int finalize_source_features(SageWindow *w, FinalizeState &fs)
   const SageWindowConfig &c = w->cfg;
   const int FS = c.FS, K = w->K;
   int rc;
-  const size_t plane_f = (size_t)FS * c.pyr.P;
+  // (a prepared keyframe brings its own: it takes no room here)
   fs.f0s_off.assign(K + 1, 0);
   for (int k = 0; k < K; ++k)
-    fs.f0s_off[k + 1] = fs.f0s_off[k] + (size_t)c.pyr.levels * FS * std::max(1, w->views[k].N);
+    fs.f0s_off[k + 1] = fs.f0s_off[k] + (w->prepared[k] ? 0 : (size_t)c.pyr.levels * FS * std::max(1, w->views[k].N));
   if ((rc = w->f0s.reserve(fs.f0s_off[K] * sizeof(float))))
     return rc;
+  w->kf_f0s.assign(K, nullptr);
   for (int k = 0; k < K; ++k)
-    SAGE_HIP(launch_presample_source(w->stream, w->f0s.as<float>() + fs.f0s_off[k],
-                                     w->pk.as<float>() + (size_t)k * 3 * plane_f, w->views[k].homo, w->views[k].N, FS,
-                                     c.pyr));
+  {
+    if (w->prepared[k])
+    {
+      w->kf_f0s[k] = w->prepared[k]->f0s;
+      continue;
+    }
+    float *f0s = w->f0s.as<float>() + fs.f0s_off[k];
+    SAGE_HIP(launch_presample_source(w->stream, f0s, w->kf_pk[k], w->views[k].homo, w->views[k].N, FS, c.pyr));
+    w->kf_f0s[k] = f0s;
+    w->build_stats.presampled += 1;
+    w->build_stats.launches += w->views[k].N > 0 ? 1 : 0;
+  }
   return SAGE_OK;
 }
 
@@ -380,7 +457,6 @@ static int finalize_edge_tables(SageWindow *w, FinalizeState &fs)
   const SageWindowConfig &c = w->cfg;
   const int CS = c.CS, FS = c.FS, K = w->K, HW = image_pixels(w);
   int rc;
-  const size_t plane_f = (size_t)FS * c.pyr.P;
   w->n_edges = (int)w->local_edges.size();
   // merged linearize (LaunchCommon::merge_geo_weight): the geometric kernel's per-pixel hand-over to the photometric one
   std::vector<size_t> &px_off = fs.px_off;
@@ -419,9 +495,9 @@ static int finalize_edge_tables(SageWindow *w, FinalizeState &fs)
         const float *x1 = w->vars[s].as<float>() + (size_t)k1 * w->VS;
         PhotoEdge pe{};
         pe.feat0 = v0.feat_pyr; pe.feat1 = v1.feat_pyr; pe.grad1 = v1.grad_pyr; pe.bias0 = v0.bias;
-        pe.feat0_pk = w->pk.as<float>() + (size_t)k0 * 3 * plane_f;
-        pe.feat1_pk = w->pk.as<float>() + (size_t)k1 * 3 * plane_f;
-        pe.f0s = w->f0s.as<float>() + fs.f0s_off[k0];
+        pe.feat0_pk = w->kf_pk[k0]; // (the window's own or the keyframe's handle's: stages 3 and 5)
+        pe.feat1_pk = w->kf_pk[k1];
+        pe.f0s = w->kf_f0s[k0];
         pe.dpt0 = w->dpt.as<float>() + (size_t)k0 * HW;
         pe.dpt1_geo = (c.use_photo && c.use_geo) ? w->dpt.as<float>() + (size_t)k1 * HW : nullptr;
         pe.geo_loss = w->link_geo_loss[l];
@@ -592,6 +668,9 @@ extern "C" int sage_window_finalize(SageWindow *w)
   if (fs.domain_solve && (window_has_holds(w) || !w->terms.gt_added.empty()))
     return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables, and no term on a single keyframe)
   w->rows = plan::solver_rows(w->hold.data(), w->K, w->cfg.CS);
+  w->build_stats = SageWindowBuildStats{};
+  w->build_stats.keyframes = w->K;
+  w->build_stats.prepared = w->K - (int)std::count(w->prepared.begin(), w->prepared.end(), nullptr);
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||
