@@ -1472,7 +1472,7 @@ int sage_window_prepare_factors_device_launches(const SageWindow *w);
 /* kernel timing with HIP events on the engine's own stream (bench.py's roofline): when enabled every launch of
  * the hot kernels is bracketed by an event pair.  which: 0 photometric linearize, 1 geometric linearize,
  * 2 photometric error, 3 geometric error, 4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term
- * error.  get_kernel_time synchronises, returns the accumulated milliseconds and
+ * error, 8 prior_eval_kernel (both passes), 9 prior_add_kernel.  get_kernel_time synchronises, returns the accumulated milliseconds and
  * launch count since the last reset, and resets them. */
 /* on: 0 off, 1 every hot kernel + the phase marks, 2 the photometric linearize only (two event records per iteration
  * instead of eleven: each record is a few microseconds of the stream's time). */
@@ -1878,6 +1878,84 @@ int  sage_window_add_prepared_keyframe(SageWindow *w, SagePreparedKeyframe *pk, 
                                        const float *code, float scale);   /* returns the keyframe id, as add_keyframe */
 typedef struct SageWindowBuildStats { int32_t keyframes, prepared, repacked, ordered, presampled, launches; } SageWindowBuildStats;
 int  sage_window_build_stats(const SageWindow *w, SageWindowBuildStats *out);   /* stages 3-5 of the last finalize */
+
+/* ---- f7: marginal priors -- a sliding window as a fixed-lag smoother ------------------------------------------------
+ * No reference counterpart (its MarginalizeFrames is commented out; ISAM2 keeps every factor).  When a window slides, the
+ * keyframes that leave are marginalised: their factors, linearised at the window's current variables, are eliminated by a
+ * Schur complement into a dense Gaussian prior over the keyframes they were linked to, and the next window carries that
+ * prior as one more term.
+ *
+ * Convention (the window's): e(d) = e - 2 g^T d + d^T A d, step A d = g.  A prior over m keyframes holds Lambda [mB x mB],
+ * eta [mB], c (B = 7 + CS; rows per keyframe: pose 6, code CS, scale 1) and the linearisation point of its keyframes.  At
+ * variables x its term is   AtA = Lambda (constant: first-estimate Jacobians, the linear-container treatment),
+ * Atb = eta - Lambda delta,   err = delta^T Lambda delta - 2 eta^T delta + c,   with
+ * delta_k = [pose_local(x0_k, x_k) (6), code - code0 (CS), scale - scale0 (1)].  pose_local(x, x) is not exactly zero in
+ * translation (fp32 rotation matrices are not exactly orthonormal): nothing here is bit-exact zero at the linearisation point.
+ *
+ * sage_schur_marginal (host, fp64): A [n x n] (symmetrised as (A + A^T) / 2 on the way in), g [n], e, and the rows to drop
+ * (distinct; the keep rows are the others, ascending) ->
+ *   Lambda = A_kk - A_kd A_dd^-1 A_dk (symmetrised exactly), eta = g_k - A_kd A_dd^-1 g_d, c = e - g_d^T A_dd^-1 g_d.
+ * Cholesky of A_dd: SAGE_E_NOT_PSD for a non-positive pivot, nothing written.  A drop row that is a row of the identity with a
+ * zero gradient (a held variable: sage_window_hold) eliminates to nothing.  n_drop = 0 is allowed, n_drop = n is not.
+ *
+ * SageMarginalPrior: opaque host handle.  _create copies the arrays (kf_ids NULL: 0 .. m-1); SAGE_E_UNSUPPORTED for m > 16
+ * (SAGE_PRIOR_MAX_KEYFRAMES) or a CS the window engine does not instantiate.  _get / _keyframes: any output of _get may be
+ * NULL.  _destroy(NULL) is a no-op.
+ * sage_prior_evaluate: host mirror of the device term at the given variables of the prior's m keyframes (pose12 [m][12],
+ * code [m][CS], scale [m]): delta [mB], Atb [mB], err, each optional.
+ * sage_prior_term_plan (host, tests): the terms of n_terms priors (m [n_terms]; kf_maps: their maps one behind the other)
+ * added in order to a window of K keyframes and `links` [nlinks][2] -> the structure-only links appended (append [.][2],
+ * room for sum m (m - 1) / 2) and where every block (i <= j) of every Lambda lands on `rank`: place [.][5] = term, i, j,
+ * packed block (keyframe id, or K + link), transposed (room for sum m (m + 1) / 2; ascending packed block, then term id);
+ * owned [n_terms]: 1 on rank 0, 0 elsewhere.  Refusals as sage_window_add_prior_term's. */
+#define SAGE_PRIOR_MAX_KEYFRAMES 16
+typedef struct SageMarginalPrior SageMarginalPrior;
+int  sage_schur_marginal(const double *A, const double *g, double e, int n, const int32_t *drop, int n_drop, double *Lambda,
+                         double *eta, double *c);
+int  sage_marginal_prior_create(int m, int CS, const double *Lambda, const double *eta, double c, const float *pose12,
+                                const float *code, const float *scale, const int32_t *kf_ids, SageMarginalPrior **out);
+int  sage_marginal_prior_dims(const SageMarginalPrior *p, int *m, int *CS);
+int  sage_marginal_prior_get(const SageMarginalPrior *p, double *Lambda, double *eta, double *c, float *pose12, float *code,
+                             float *scale);
+int  sage_marginal_prior_keyframes(const SageMarginalPrior *p, int32_t *kf_ids /* [m] */);
+void sage_marginal_prior_destroy(SageMarginalPrior *p);
+int  sage_prior_evaluate(const SageMarginalPrior *p, const float *pose12, const float *code, const float *scale, double *delta,
+                         double *Atb, double *err);
+int  sage_prior_term_plan(int K, int nlinks, const int32_t *links, int n_terms, const int32_t *m, const int32_t *kf_maps,
+                          int rank, int world, int32_t *append, int32_t *n_append, int32_t *place, int32_t *n_place,
+                          int32_t *owned);
+/* sage_window_add_prior_term: a third family of terms next to the keypoint and graph terms.  Before finalize (SAGE_E_STATE
+ * afterwards).  kf_map [m]: the keyframes of THIS window the prior's rows belong to, distinct and valid, any order
+ * (SAGE_E_INVALID otherwise, or for a prior of another CS).  The prior is copied: the handle may be destroyed.  Every pair of
+ * the prior's keyframes needs a link block: for a pair without a link the call appends a structure-only link (what
+ * sage_window_add_keypoint_link creates), in ascending (a, b) order -- link ids handed out afterwards move on by that many.
+ * Returns the term id.  A sharded window gives every prior term to rank 0 (like a scale-prior graph term); a window of the
+ * domain-decomposed solve answers SAGE_E_UNSUPPORTED at finalize.
+ * The term is evaluated on every linearize and every error pass (prior_eval_kernel; prior_add_kernel adds Lambda, unrounded,
+ * the Atb rows and the error -- in the geometric error slot, where graph terms ride -- to the packed system behind the
+ * assembly).  No atomics: bit-reproducible from run to run.  The gtsam factor cache, SAGE_RELIN_STALE and SageEvalCounts
+ * know nothing of the family.  Profiler slots (sage_window_get_kernel_time): 8 prior_eval_kernel, 9 prior_add_kernel.
+ * sage_window_get_prior_term: host copy of the last linearize in doubles, AtA [mB x mB] (= Lambda), Atb [mB], err; each
+ * optional.  SAGE_E_STATE before the first linearize, SAGE_E_INVALID for a term of another rank. */
+int  sage_window_add_prior_term(SageWindow *w, const SageMarginalPrior *prior, const int32_t *kf_map /* [m] */);
+int  sage_window_num_prior_terms(const SageWindow *w);
+int  sage_window_get_prior_term(const SageWindow *w, int term, double *AtA, double *Atb, double *err);
+/* sage_window_marginalize: the prior the keyframes drop [n_drop] leave behind.  The window must hold a linearization at its
+ * current variables (sage_window_linearize, or an accepted linearize-at-candidate step): SAGE_E_STATE otherwise, as
+ * sage_window_solve after sage_window_set_runs.  The sub-system is the sum, in double, of exactly the fp32 per-edge and
+ * per-term results that linearize left, placed by the assembly's rules, of ONLY the factors incident to a dropped keyframe:
+ * the dense edges of both directions and factor types, the keypoint and graph terms on those edges, a scale-prior graph term
+ * on a dropped keyframe, the dropped keyframes' own diagonal priors (code prior; keyframe 0's scale and pose priors), and
+ * every prior term that touches a dropped keyframe, whole.  Factors between two surviving keyframes do not enter: they stay
+ * in the next window.  The separator -- the prior's keyframes, sage_marginal_prior_keyframes -- is every surviving keyframe
+ * that shares a link or a prior term with a dropped one, ascending.  The hold rule is applied before the elimination: a held
+ * row of a dropped keyframe is a row of the identity, a held row of a separator keyframe a zero row of Lambda and eta.  The
+ * linearisation point is the window's current variables.  c counts the dropped keyframes' diagonal priors as
+ * sage_window_total_error counts them.
+ * SAGE_E_INVALID: a bad or duplicate id, dropping every keyframe, or dropped keyframes nothing links to a survivor;
+ * SAGE_E_UNSUPPORTED: a sharded window (world > 1: no rank holds every result), or a separator of more than 16 keyframes;
+ * SAGE_E_NOT_PSD: the dropped keyframes' block is not positive definite. */
+int  sage_window_marginalize(SageWindow *w, const int32_t *drop, int n_drop, SageMarginalPrior **out);
 
 #ifdef __cplusplus
 }

@@ -290,6 +290,9 @@ SYMBOLS = [
     "sage_keyframe_prepare", "sage_keyframe_prepare_batch", "sage_keyframe_prepare_plan", "sage_keyframe_prepare_launches",
     "sage_keyframe_config_matches", "sage_keyframe_info", "sage_keyframe_get", "sage_keyframe_release",
     "sage_window_add_prepared_keyframe", "sage_window_build_stats",
+    "sage_schur_marginal", "sage_marginal_prior_create", "sage_marginal_prior_dims", "sage_marginal_prior_get",
+    "sage_marginal_prior_keyframes", "sage_marginal_prior_destroy", "sage_prior_evaluate", "sage_prior_term_plan",
+    "sage_window_add_prior_term", "sage_window_num_prior_terms", "sage_window_get_prior_term", "sage_window_marginalize",
 ]
 
 
@@ -1408,6 +1411,142 @@ class PreparedKeyframe:
             pass
 
 
+SAGE_PRIOR_MAX_KEYFRAMES = 16
+
+
+def _f64(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def schur_marginal_raw(A_ptr, g_ptr, e, n, drop_ptr, n_drop, Lambda_ptr, eta_ptr, c_ptr) -> int:
+    """``sage_schur_marginal`` with raw addresses (None -> NULL) -> status code"""
+    f = lib().sage_schur_marginal
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(A_ptr, g_ptr, float(e), int(n), drop_ptr, int(n_drop), Lambda_ptr, eta_ptr, c_ptr))
+
+
+def schur_marginal(A, g, e: float, drop, check=True):
+    """``sage_schur_marginal``: the system (A [n,n], g [n], e) with the rows ``drop`` eliminated -> (Lambda, eta, c) over the
+    other rows, ascending; with ``check=False`` the status code comes first and nothing is raised."""
+    A = _f64(A); g = _f64(g)
+    n = g.size
+    d = np.ascontiguousarray(drop, np.int32).reshape(-1)
+    nk = max(n - d.size, 0)
+    Lam = np.full((nk, nk), np.nan); eta = np.full(nk, np.nan); c = C.c_double(float("nan"))
+    rc = schur_marginal_raw(A.ctypes.data, g.ctypes.data, e, n, d.ctypes.data if d.size else None, d.size, Lam.ctypes.data,
+                            eta.ctypes.data, C.addressof(c))
+    if not check:
+        return rc, Lam, eta, c.value
+    _chk(rc, "sage_schur_marginal")
+    return Lam, eta, c.value
+
+
+def marginal_prior_create_raw(m, CS, Lambda_ptr, eta_ptr, c, pose_ptr, code_ptr, scale_ptr, ids_ptr, out_ptr) -> int:
+    """``sage_marginal_prior_create`` with raw addresses (None -> NULL) -> status code"""
+    f = lib().sage_marginal_prior_create
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 5
+    return int(f(int(m), int(CS), Lambda_ptr, eta_ptr, float(c), pose_ptr, code_ptr, scale_ptr, ids_ptr, out_ptr))
+
+
+class MarginalPrior:
+    """``SageMarginalPrior``: Lambda [mB,mB], eta [mB], c over m keyframes, linearised at (pose12 [m,12], code [m,CS],
+    scale [m]); ``keyframes``: the ids they had in the window the prior came from."""
+
+    def __init__(self, Lambda=None, eta=None, c=0.0, pose12=None, code=None, scale=None, keyframes=None, handle=None):
+        L = lib()
+        L.sage_marginal_prior_destroy.restype = None
+        L.sage_marginal_prior_destroy.argtypes = [C.c_void_p]
+        if handle is not None:
+            self.h = C.c_void_p(handle)
+        else:
+            pose = _f32(pose12).reshape(-1, 12); code = _f32(code).reshape(pose.shape[0], -1); scale = _f32(scale).reshape(-1)
+            m, CS = pose.shape[0], code.shape[1]
+            Lam = _f64(Lambda); eta_ = _f64(eta)
+            assert Lam.shape == (m * (7 + CS),) * 2 and eta_.shape == (m * (7 + CS),) and scale.size == m
+            ids = np.ascontiguousarray(keyframes if keyframes is not None else np.arange(m), np.int32)
+            assert ids.size == m
+            self.h = C.c_void_p()
+            _chk(marginal_prior_create_raw(m, CS, Lam.ctypes.data, eta_.ctypes.data, c, pose.ctypes.data, code.ctypes.data,
+                                           scale.ctypes.data, ids.ctypes.data, C.addressof(self.h)), "sage_marginal_prior_create")
+        m, CS = C.c_int(), C.c_int()
+        f = L.sage_marginal_prior_dims
+        f.argtypes = [C.c_void_p] * 3
+        _chk(int(f(self.h, C.addressof(m), C.addressof(CS))), "sage_marginal_prior_dims")
+        self.m, self.CS = m.value, CS.value
+        self.B = 7 + self.CS
+
+    def get(self) -> dict:
+        """host copies: Lambda, eta, c, pose12, code, scale, keyframes"""
+        n = self.m * self.B
+        Lam = np.zeros((n, n)); eta = np.zeros(n); c = C.c_double()
+        pose = np.zeros((self.m, 12), np.float32); code = np.zeros((self.m, self.CS), np.float32)
+        scale = np.zeros(self.m, np.float32); ids = np.zeros(self.m, np.int32)
+        f = lib().sage_marginal_prior_get
+        f.argtypes = [C.c_void_p] * 7
+        _chk(int(f(self.h, Lam.ctypes.data, eta.ctypes.data, C.addressof(c), pose.ctypes.data, code.ctypes.data,
+                   scale.ctypes.data)), "sage_marginal_prior_get")
+        g = lib().sage_marginal_prior_keyframes
+        g.argtypes = [C.c_void_p] * 2
+        _chk(int(g(self.h, ids.ctypes.data)), "sage_marginal_prior_keyframes")
+        return dict(Lambda=Lam, eta=eta, c=c.value, pose12=pose, code=code, scale=scale, keyframes=ids)
+
+    def evaluate(self, pose12, code, scale) -> dict:
+        """``sage_prior_evaluate`` at the variables of the prior's m keyframes -> dict(delta, Atb, err)"""
+        return prior_evaluate(self, pose12, code, scale)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sage_marginal_prior_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prior_evaluate_raw(prior_handle, pose_ptr, code_ptr, scale_ptr, delta_ptr, Atb_ptr, err_ptr) -> int:
+    """``sage_prior_evaluate`` with raw addresses (None -> NULL) -> status code"""
+    f = lib().sage_prior_evaluate
+    f.argtypes = [C.c_void_p] * 7
+    return int(f(prior_handle, pose_ptr, code_ptr, scale_ptr, delta_ptr, Atb_ptr, err_ptr))
+
+
+def prior_evaluate(prior: MarginalPrior, pose12, code, scale) -> dict:
+    """the host mirror of the device term: delta [mB], Atb = eta - Lambda delta, err = delta' Lambda delta - 2 eta' delta + c"""
+    pose = _f32(pose12).reshape(prior.m, 12); code = _f32(code).reshape(prior.m, prior.CS); scale = _f32(scale).reshape(prior.m)
+    n = prior.m * prior.B
+    delta = np.zeros(n); Atb = np.zeros(n); err = C.c_double()
+    _chk(prior_evaluate_raw(prior.h, pose.ctypes.data, code.ctypes.data, scale.ctypes.data, delta.ctypes.data, Atb.ctypes.data,
+                            C.addressof(err)), "sage_prior_evaluate")
+    return dict(delta=delta, Atb=Atb, err=err.value)
+
+
+def prior_term_plan(K: int, links, kf_maps, rank: int = 0, world: int = 1, check=True):
+    """``sage_prior_term_plan``: the prior terms with maps ``kf_maps`` added in order to a window of K keyframes and
+    ``links`` -> dict(append: [(a, b)] the structure-only links appended, place: [(term, i, j, packed block, transposed)],
+    owned: [0 / 1 per term]); with ``check=False`` the status code comes first and nothing is raised."""
+    lk = np.ascontiguousarray(links, np.int32).reshape(-1, 2)
+    m = np.array([len(k) for k in kf_maps], np.int32)
+    maps = np.array([k for km in kf_maps for k in km], np.int32)
+    append = np.zeros((max(1, int((m * (m - 1) // 2).sum())), 2), np.int32)
+    place = np.zeros((max(1, int((m * (m + 1) // 2).sum())), 5), np.int32)
+    owned = np.zeros(max(1, m.size), np.int32)
+    na, npl = C.c_int32(), C.c_int32()
+    f = lib().sage_prior_term_plan
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+    rc = int(f(int(K), lk.shape[0], lk.ctypes.data if lk.size else None, m.size, m.ctypes.data if m.size else None,
+               maps.ctypes.data if maps.size else None, int(rank), int(world), append.ctypes.data, C.addressof(na),
+               place.ctypes.data, C.addressof(npl), owned.ctypes.data))
+    out = dict(append=[tuple(r) for r in append[:na.value].tolist()], place=[tuple(r) for r in place[:npl.value].tolist()],
+               owned=owned[:m.size].tolist()) if rc == 0 else None
+    if not check:
+        return rc, out
+    _chk(rc, "sage_prior_term_plan")
+    return out
+
+
 def photometric_jac_error(ws: Workspace, R10, t10, R0, t0, R1, t1, bias0, basis0, code0, mask1, loc1d, homo,
                           feat0, feat1, grad1, scale0, pyr: SagePyramid, eps, weights, FS, CS):
     """``df::photometric_jac_error_calculate<CS,FS>``; poses/code are small host arrays uploaded here (the
@@ -1539,7 +1678,7 @@ class Window:
 
     def __init__(self, win, rank: int = 0, world: int = 1, stream=None, use_photo=True, use_geo=True,
                  code_prior_weight=1.0e-3, scale_prior_weight=1.0e4, pose_prior_weight=1.0e4, keypoint_terms=None,
-                 keypoint_links=None, holds=None, graph_terms=None, prepared=None):
+                 keypoint_links=None, holds=None, graph_terms=None, prepared=None, prior_terms=None):
         """``keypoint_terms``: optional list of dicts (``synth.make_reprojection_matches`` / ``make_match_geometry_matches`` /
         ``make_loop_mg_*``, or by hand): kind ("reprojection" | "match_geometry" | "loop_mg"), edge (2 * link + direction),
         loc0 [N] int32, homo0 [N,3], matched_2d [N,2] or loc1 [N] + homo1 [N,3], loss_param, weight and, for match geometry,
@@ -1552,6 +1691,8 @@ class Window:
         reference's loop-closure graph), added with ``sage_window_add_graph_term``.
         ``prepared``: optional dict keyframe id -> ``PreparedKeyframe``: those keyframes are added by handle
         (``sage_window_add_prepared_keyframe``: the window borrows their preparation, and their device arrays), the others as views.
+        ``prior_terms``: optional list of (``MarginalPrior``, kf_map) added with ``sage_window_add_prior_term`` after everything
+        else; the structure-only links they append are listed behind the others in ``self.links``.
         All are added before the finalize this constructor performs."""
         import torch
         self.win = win
@@ -1613,6 +1754,11 @@ class Window:
             r = self.add_graph_term(t)
             if r < 0:
                 raise SageError(r, "sage_window_add_graph_term")
+        self.prior_terms = []
+        for prior, kf_map in (prior_terms or []):
+            r = self.add_prior_term(prior, kf_map)
+            if r < 0:
+                raise SageError(r, "sage_window_add_prior_term")
         _chk(L.sage_window_set_shard(self.h, rank, world), "sage_window_set_shard")
         _chk(L.sage_window_finalize(self.h), "sage_window_finalize")
         self.K = L.sage_window_num_keyframes(self.h)
@@ -1717,6 +1863,56 @@ class Window:
             return rc, out
         _chk(rc, "sage_window_get_graph_term")
         return out
+
+    def add_prior_term(self, prior, kf_map) -> int:
+        """``sage_window_add_prior_term`` -> term id, or the negative status code (``prior``: a ``MarginalPrior`` or None for
+        NULL; ``kf_map``: this window's keyframes behind the prior's rows, or None).  ``self.links`` grows by the
+        structure-only links the call appended."""
+        f = lib().sage_window_add_prior_term
+        f.argtypes = [C.c_void_p] * 3
+        km = np.ascontiguousarray(kf_map, np.int32) if kf_map is not None else None
+        before = lib().sage_window_num_links(self.h)
+        r = int(f(self.h, prior.h if prior is not None else None, km.ctypes.data if km is not None else None))
+        if r >= 0:
+            from itertools import combinations
+            have = set(self.links)
+            new = sorted({(min(a, b), max(a, b)) for a, b in combinations(km.tolist(), 2)} - have)
+            assert lib().sage_window_num_links(self.h) - before == len(new)
+            self.links = self.links + new
+            self.prior_terms.append((prior, km.tolist()))
+        return r
+
+    def num_prior_terms(self) -> int:
+        return int(lib().sage_window_num_prior_terms(self.h))
+
+    def get_prior_term(self, i, check=True):
+        """host copy of prior term i's last linearize in doubles -> dict(AtA [mB,mB], Atb [mB], err); with ``check=False``
+        the status code is returned next to the dict instead of raising."""
+        m = self.prior_terms[i][0].m if 0 <= i < len(self.prior_terms) else 1
+        n = m * (7 + self.win.CS)
+        A = np.zeros((n, n)); b = np.zeros(n); err = C.c_double()
+        f = lib().sage_window_get_prior_term
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = int(f(self.h, int(i), A.ctypes.data, b.ctypes.data, C.addressof(err)))
+        out = dict(AtA=A, Atb=b, err=err.value)
+        if not check:
+            return rc, out
+        _chk(rc, "sage_window_get_prior_term")
+        return out
+
+    def marginalize(self, drop, check=True):
+        """``sage_window_marginalize``: the ``MarginalPrior`` the keyframes ``drop`` leave behind; with ``check=False`` ->
+        (status code, prior or None)."""
+        d = np.ascontiguousarray(drop, np.int32).reshape(-1)
+        h = C.c_void_p()
+        f = lib().sage_window_marginalize
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        rc = int(f(self.h, d.ctypes.data if d.size else None, d.size, C.addressof(h)))
+        prior = MarginalPrior(handle=h.value) if rc == 0 else None
+        if not check:
+            return rc, prior
+        _chk(rc, "sage_window_marginalize")
+        return prior
 
     # raw-pointer views for torch.distributed (plumbing only)
     def packed_tensor(self):
@@ -1995,7 +2191,8 @@ class Window:
 
     def kernel_time(self, which: int):
         """(total_ms, launches) of hot kernel `which` since the last call (0 photo lin, 1 geo lin, 2 photo err, 3 geo err,
-        4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term error)."""
+        4 keypoint-term linearize, 5 keypoint-term error, 6 graph-term linearize, 7 graph-term error, 8 prior_eval_kernel,
+        9 prior_add_kernel)."""
         ms = C.c_double(); n = C.c_int()
         _chk(lib().sage_window_get_kernel_time(self.h, which, C.byref(ms), C.byref(n)), "sage_window_get_kernel_time")
         return ms.value, n.value

@@ -37,6 +37,9 @@
 //   window_factors.hip  f2: per-Values factor cache behind the gtsam adapter (prepass, factor blocks, NearestPsd)
 //   window_relin.hip    partial relinearization: the stale edges of a linearize, their compacted launch plan (its kernel), the
 //                       depth maps' stamps, the relinearization marks and the masked accept
+//   window_prior.hip    marginal priors on a window: add / get, their finalize stage, the evaluation and add kernels' launches,
+//                       sage_window_marginalize (the sub-system of the dropped keyframes' factors, summed on the host)
+//   marginal_host.cpp   (no HIP) the Schur complement, the prior's handle, the host mirror of the term, the layout plan's C view
 //   relin_host.cpp      (no HIP) the reads table and gtsam's relinearization check (relin_plan.h), stateless
 //   factor_blocks.cpp   (no HIP) what a cached factor is: shape, projection of its own matrix, cut into HessianFactor blocks
 // window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, factor cache, totals
@@ -92,6 +95,7 @@ extern "C"
 #include "loop_accept.h"       // sage_loop_accept's host rules
 #include "dogleg.h"            // the dogleg step's dots, partial slots and pinned record
 #include "keyframe_prepare.h"  // a prepared keyframe's fingerprint, layout and plan; the handle itself
+#include "marginal.h"          // a marginal prior's handle, the layout of a window's prior terms
 
 using namespace sage;
 
@@ -438,6 +442,8 @@ struct SageWindow
   DevBuf packed_save;                     // linearize-at-candidate: the candidate's (reduced) system is formed here; an accepted
                                           // candidate swaps it with `packed` (which always is the current estimate's system)
   TermSide terms;                         // keypoint and pose-graph terms: as added, this rank's layout, device tables, results
+  PriorSide priors;                       // marginal-prior terms: as added, this rank's layout, device arrays (window_prior.hip)
+  uint64_t results_epoch = 0;             // == vars_epoch: the per-edge and per-term results are the linearisation at the current variables
   FactorCache fc;                         // f2: the per-Values factor cache (sage_window_prepass): window_state.h
   uint64_t dense_serial = 0;              // counts the linearizes that have written dense[].AtA (FactorSlot::live_serial)
   DoglegSide dogleg;                      // the dogleg step's tables, vectors and pinned dots (window_dogleg.hip)
@@ -484,6 +490,11 @@ struct FinalizeState
 // window_terms.hip
 int finalize_terms(SageWindow *w, FinalizeState &fs);  // stage 7 of sage_window_finalize
 int window_launch_terms(SageWindow *w, int set, bool jac); // the keypoint kernel, then the graph kernel, over this rank's terms
+// window_prior.hip
+int finalize_priors(SageWindow *w);                          // stage 7b of sage_window_finalize
+int window_launch_prior_eval(SageWindow *w, int set, bool jac); // prior_eval_kernel over this rank's prior terms
+int window_launch_prior_add(SageWindow *w, double *packed, double *tail_mirror); // prior_add_kernel behind the assembly of `packed`
+const double *window_prior_partials(const SageWindow *w, bool jac, int *n_terms); // the pass's tile partials (null: no local term)
 // window_eval.hip
 // stale_only: the stale-mode linearize of sage_window_linearize (set 0 into `packed`, unmerged); every other call evaluates
 // every edge and, in SAGE_RELIN_STALE, leaves every edge stale

@@ -608,12 +608,15 @@ static int finalize_results(SageWindow *w, const FinalizeState &fs)
   {
     // the output blocks this rank's edges and keypoint terms contribute to (everything, on a single-rank window; a link block
     // that only local terms write to is listed too: it would keep the zeros of this stage on a sharded window)
+    // (... and so is a block a local prior term adds to: prior_add_kernel adds to what the assembly wrote)
     std::vector<int32_t> ids;
+    const std::vector<int> &pb = w->priors.layout.blocks;
+    auto prior_block = [&pb](int id) { return std::binary_search(pb.begin(), pb.end(), id); };
     for (int k = 0; k < K; ++k)
-      if (!fs.adjv[k].empty())
+      if (!fs.adjv[k].empty() || prior_block(k))
         ids.push_back(k);
     for (size_t l = 0; l < fs.le.size(); ++l)
-      if (fs.le[l].e_ab >= 0 || fs.le[l].e_ba >= 0 || fs.link_terms[l])
+      if (fs.le[l].e_ab >= 0 || fs.le[l].e_ba >= 0 || fs.link_terms[l] || prior_block(K + (int)l))
         ids.push_back(K + (int32_t)l);
     ids.push_back(K + (int32_t)w->links.size()); // the tail
     w->dist.n_asm_blocks = (int)ids.size();
@@ -665,8 +668,8 @@ extern "C" int sage_window_finalize(SageWindow *w)
   const char *schur = getenv("SAGE_SHARD_SCHUR"); // the request: 0 / 1
   fs.domain_solve = plan::uses_domain_solve(w->world, w->K, schur ? atoi(schur) != 0 : -1);
   w->hold.resize(w->K, 0);
-  if (fs.domain_solve && (window_has_holds(w) || !w->terms.gt_added.empty()))
-    return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables, and no term on a single keyframe)
+  if (fs.domain_solve && (window_has_holds(w) || !w->terms.gt_added.empty() || !w->priors.added.empty()))
+    return SAGE_E_UNSUPPORTED; // (the domain-decomposed solve knows no held variables, no term on a single keyframe, no prior term)
   w->rows = plan::solver_rows(w->hold.data(), w->K, w->cfg.CS);
   w->build_stats = SageWindowBuildStats{};
   w->build_stats.keyframes = w->K;
@@ -674,7 +677,7 @@ extern "C" int sage_window_finalize(SageWindow *w)
   int rc;
   if ((rc = finalize_variables(w)) || (rc = finalize_ownership(w, fs)) || (rc = finalize_pyramids(w)) ||
       (rc = finalize_samples(w)) || (rc = finalize_source_features(w, fs)) || (rc = finalize_edge_tables(w, fs)) ||
-      (rc = finalize_terms(w, fs)))
+      (rc = finalize_terms(w, fs)) || (rc = finalize_priors(w)))
     return rc;
   w->residuals_per_lin = fs.residuals;
   w->bytes_per_lin = fs.bytes;

@@ -208,9 +208,19 @@ __global__ __launch_bounds__(kFinalizeBlock) void window_finalize_kernel(const W
 // error pass of a window in ONE tail kernel: per-edge statistics of both factor types from the workgroup partials
 // (what stats_finalize_kernel does: photometric_factor_kernels.cpp:1049-1058, geometric :868-878) and their totals
 // (a wave-parallel sum in a fixed lane order) -- same summation orders, three launches and their gaps less on the step's critical path.
+// priors: the marginal-prior terms' table and the error pass's tile partials (window_prior.hip; null without local terms): their
+// errors ride in the geometric slot, as in the linearize tail
+struct PriorErrors
+{
+  const marg::PriorTermDev *table;
+  const double *part;
+  int n_terms;
+};
+
 template <bool KP>
 __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSide ph, const ErrorTotalsSide ge, double *out,
-                                                            double *mirror, double epoch, const TermResults terms)
+                                                            double *mirror, double epoch, const TermResults terms,
+                                                            const PriorErrors priors)
 {
   for (int idx = threadIdx.x; idx < ph.n_edges + ge.n_edges; idx += blockDim.x)
   {
@@ -271,6 +281,8 @@ __global__ __launch_bounds__(1024) void error_totals_kernel(const ErrorTotalsSid
     acc += __shfl_down(acc, off);
   if (lane == 0)
   {
+    if (priors.part && which == 0 && !photo)
+      acc += marg::prior_error_total(priors.table, priors.n_terms, priors.part);
     out[which * 2 + (photo ? 0 : 1)] = acc;
     if (mirror)
     {
@@ -427,6 +439,8 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
   }
   if (const int rct = window_launch_terms(w, set, true)) // every keypoint term of this rank: one launch; every graph term: one more
     return rct;
+  if (const int rcp = window_launch_prior_eval(w, set, true)) // every marginal-prior term of this rank: one launch
+    return rcp;
   if (dense)
   {
     WindowFinalizeParams fp{};
@@ -467,7 +481,10 @@ int window_linearize_set(SageWindow *w, int set, double *dst, bool local_blocks,
   else
     hipLaunchKernelGGL(assemble_kernel<false>, dim3(nblocks * ap.split), dim3(512), 0, w->stream, ap);
   SAGE_HIP(hipGetLastError());
+  if (const int rcp = window_launch_prior_add(w, ap.packed, ap.tail_mirror)) // the priors' Lambda image, Atb rows and errors on top
+    return rcp;
   window_phase_mark(w, 1);
+  w->results_epoch = set == 0 ? w->vars_epoch : 0; // (the per-edge and per-term results: sage_window_marginalize)
   if (ap.packed == w->packed.as<double>()) // (a system assembled elsewhere is booked by the caller)
   {
     w->have_lin = true;
@@ -565,15 +582,20 @@ int window_error_pass(SageWindow *w, int which, bool speculate_gradients)
   // the terms' errors are summed INSIDE the totals kernel (it overwrites its outputs and posts the mirror tickets)
   if (const int rct = window_launch_terms(w, which, false))
     return rct;
+  if (const int rcp = window_launch_prior_eval(w, which, false)) // ... and so are the marginal priors', from their tile partials
+    return rcp;
+  PriorErrors pri{};
+  pri.part = window_prior_partials(w, false, &pri.n_terms);
+  pri.table = w->priors.table.as<marg::PriorTermDev>();
   const TermResults kpt = w->terms.results(false);
   w->mirror.err_epoch += 1;
   double *const mirror = w->kernels_mirror_totals() ? w->mirror.h + TotalsMirror::kError : nullptr;
   if (kpt.stats)
     hipLaunchKernelGGL(error_totals_kernel<true>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
-                       (double)w->mirror.err_epoch, kpt);
+                       (double)w->mirror.err_epoch, kpt, pri);
   else
     hipLaunchKernelGGL(error_totals_kernel<false>, dim3(1), dim3(1024), 0, w->stream, ph, ge, w->errbuf.as<double>(), mirror,
-                       (double)w->mirror.err_epoch, kpt);
+                       (double)w->mirror.err_epoch, kpt, pri);
   SAGE_HIP(hipGetLastError());
   window_phase_mark(w, 4);
   if (speculate_gradients && has && c.use_geo && w->dpt_set == which && !w->dgrad_valid)

@@ -199,6 +199,7 @@ static int lm_accept(LmSeq seq, SageWindow *w, const SageLmState *st)
     return rc;
   w->packed.swap(w->packed_save);
   w->lin_epoch = w->vars_epoch;
+  w->results_epoch = w->vars_epoch; // (the last linearize was the accepted candidate's: its per-edge results are current too)
   w->dist.packed_reduced = true; // (summed over the ranks by window_form_system, or nothing to sum)
   w->spec_error = st->candidate_error;
   return SAGE_OK;

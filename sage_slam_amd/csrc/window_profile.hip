@@ -150,7 +150,7 @@ extern "C" int sage_window_set_profiling(SageWindow *w, int on)
 
 extern "C" int sage_window_get_kernel_time(SageWindow *w, int which, double *total_ms, int *launches)
 {
-  if (!w || which < 0 || which > 7)
+  if (!w || which < 0 || which > 9)
     return SAGE_E_INVALID;
   WindowProfiler &pf = w->prof;
   SAGE_HIP(hipStreamSynchronize(w->stream));

@@ -122,6 +122,27 @@ struct TermSide
   }
 };
 
+// ---- the window's marginal-prior terms (window_prior.hip): copies of the priors as added, then (finalize) this rank's on the
+// device behind one table, the image of their Lambda blocks in the packed layout, the per-keyframe lists of their Atb rows ----
+struct PriorSide
+{
+  struct Added
+  {
+    SageMarginalPrior prior;
+    std::vector<int32_t> kf_map;
+  };
+  std::vector<Added> added;     // sage_window_add_prior_term
+  marg::PriorLayout layout;     // (finalize) which are this rank's, where their blocks land
+  std::vector<marg::PriorTermDev> h_table; // host copy of `table` (offsets for sage_window_get_prior_term, sage_window_marginalize)
+  DevBuf table, lambda, eta, x0; // the local terms' rows and arrays
+  DevBuf atb[2], part[2];       // per pass (0: linearize, 1: error pass): Atb [sum n]; per row tile {delta^T Lambda delta, eta^T delta}
+  DevBuf image, image_blocks;   // [n_blocks][B * B] doubles and the packed block each belongs to
+  DevBuf grad, grad_start;      // PriorGradRow entries keyframe-major; per gradient workgroup its first entry (+ the end)
+  int n_tiles = 0, n_blocks = 0, n_grad_kf = 0;
+  bool evaluated = false;       // a linearize has written atb[0] / part[0]
+  int n_local() const { return (int)layout.local.size(); }
+};
+
 // ---- f2: the per-Values factor cache behind the gtsam adapter (sage_window_prepass, window_factors.hip): host copies of this
 // rank's systems and the values (all K keyframes) they were evaluated at ----
 struct FactorSlot // the entries of one layout: a dense factor type's local directed edges, or a term group's entries
@@ -279,10 +300,11 @@ struct WindowProfiler
   int phase_n = 0;
   bool profiling = false;
   int prof_level = 0; // 1: all hot kernels + phase marks, 2: the photometric linearize only
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[8]; // (4 / 5: keypoint-term linearize / error launch, 6 / 7: graph-term)
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[10]; // (4 / 5: keypoint-term linearize / error launch, 6 / 7: graph-term,
+                                                               //  8 / 9: prior_eval_kernel / prior_add_kernel)
   std::vector<hipEvent_t> ev_free; // recycled events (creating / destroying one per mark costs API time inside the region being profiled)
-  double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int prof_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double prof_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int prof_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   WindowProfiler() = default;
   WindowProfiler(const WindowProfiler &) = delete;
   WindowProfiler &operator=(const WindowProfiler &) = delete;
