@@ -1957,6 +1957,65 @@ int  sage_window_get_prior_term(const SageWindow *w, int term, double *AtA, doub
  * SAGE_E_NOT_PSD: the dropped keyframes' block is not positive definite. */
 int  sage_window_marginalize(SageWindow *w, const int32_t *drop, int n_drop, SageMarginalPrior **out);
 
+/* ---- marginal covariances (covariance_host.cpp, window_covariance.hip, depth_sigma.hip) ----
+ * How certain a window's estimate is: the blocks of Sigma = M^-1 for every keyframe and every linked pair, what gtsam hands
+ * back as ISAM2::marginalCovariance / Marginals.  M = L L^T is the block Cholesky factor a solve leaves on the host; the
+ * blocks of Sigma on the factor's pattern are one backward recursion over it (selected inverse), no second factorisation:
+ *   Sigma_ij = -(sum_{k in col(j)} Sigma_ik L_kj) L_jj^-1,   Sigma_jj = (L_jj^-T - sum_k Sigma_jk L_kj) L_jj^-1, symmetrised
+ * exactly.  One thread, one fixed order: the result is the same bit for bit from run to run.
+ *
+ * sage_block_covariance (host, fp64), the sibling of sage_block_solve: the same damped matrix
+ * (H + diag_add) + damp diag(H + diag_add) of a packed buffer (the gradient is not read), duplicate links summed.
+ * pairs [n_pairs][2]: (a, a) asks for a keyframe's diagonal block, (a, b) for a link's block, either way round: (b, a) is the
+ * transpose of (a, b) bit for bit; SAGE_E_INVALID for a pair that is not a link.  Sigma [n_pairs][B*B] row-major, rows of
+ * pairs[.][0], columns of pairs[.][1].  SAGE_E_NOT_PSD as the solve answers it, nothing written; SAGE_E_UNSUPPORTED for B > 40.
+ * sage_covariance_plan (host, tests): the blocks (lower triangle with the diagonal) the elimination plan of K keyframes and
+ * `links` stores, and how many the recursion's symbolic closure adds to them (none for the plans in use).
+ *
+ * sage_window_covariance: drains the stream and runs the recursion on the factor the window's last successful solve left
+ * (sage_window_solve, sage_window_lm_step, a dogleg solve); damp_out (optional) receives that solve's damping.  At damping 0
+ * -- after the dogleg's solve or sage_window_solve(w, 0, ..) -- Sigma is A^-1 of the system with its diagonal priors, keypoint,
+ * graph and prior terms: what ISAM2::marginalCovariance returns when the factors are served as sage_window_factor serves
+ * them (G = AtA).  With damping it is the inverse of the DAMPED system, a lower bound of that.  Sigma belongs to the
+ * linearization it was solved at: a later solve invalidates it, a later linearize or accept does not.
+ * SAGE_E_STATE before the first solve, after a solve that failed and after whatever drops the system (sage_window_tune_runs,
+ * sage_window_set_runs); SAGE_E_UNSUPPORTED for a sharded window (world > 1: as sage_window_marginalize), a window of the
+ * domain-decomposed solve and a window without a device solver (duplicate links).
+ * sage_window_get_covariance: block (kf_a, kf_b) of the stored Sigma, [B*B] row-major, rows of kf_a, in the window's row
+ * order [pose 6, code CS, scale]: kf_a == kf_b or a link (structure-only links included), either way round.  Held rows and
+ * columns are exactly 0, and so are the rows of a group that left the solver (sage_window_solver_block_size < B): a held
+ * variable has no variance.  SAGE_E_STATE without a stored Sigma, SAGE_E_INVALID for a pair without a link block.
+ *
+ * Depth uncertainty: d(p) = s (bias(p) + basis(p,:) code) has the Jacobian j = [s basis(p,:) (CS), bias(p) + basis(p,:) code]
+ * against (code, scale); with S the (code, scale) sub-block of Sigma_kk, [(CS+1) x (CS+1)],
+ *   var(p) = j^T S j,   sigma(p) = sqrtf(max(var, 0)).
+ * sage_depth_sigma_batch: n keyframes in one launch (depth_sigma_kernel: pixel tiles x keyframes, S staged in LDS, fp32, no
+ * atomics, a fixed summation order: bit-reproducible), asynchronous on the workspace's stream like sage_depth_and_grad.  S is
+ * read from the HOST by the call, symmetrised as (S + S^T) / 2 and rounded once to fp32.  CS 16 or 32 (SAGE_E_UNSUPPORTED
+ * otherwise), mode SAGE_DEPTH_VARIANCE or SAGE_DEPTH_SIGMA; argument checks come before any launch.
+ * sage_window_depth_sigma: the same launch on the window's stream for the keyframes kfs [n], with bias, basis, code and scale
+ * of the window's own depth table at the current variables (prepared keyframes included) and S from the stored Sigma:
+ * SAGE_E_STATE without one.  out_dev [n] -> [H*W] device floats.  A keyframe whose code and scale are held gives zeros.
+ * sage_window_depth_sigma_timing (scripts/covariance_bench.py): the sigma kernel over all K keyframes and depth_batch_kernel
+ * over the same keyframes, alternating, reps times each between HIP events on the window's stream -> the medians in
+ * microseconds.  It leaves the depth maps of the current variables behind, as an error pass at them would. */
+enum { SAGE_DEPTH_VARIANCE = 0, SAGE_DEPTH_SIGMA = 1 };
+typedef struct SageDepthSigmaItem
+{
+  const float *bias_dev, *basis_dev, *code_dev; /* [H*W], [H*W,CS], [CS] */
+  float scale;
+  const double *cov_code_scale;                 /* HOST, [CS+1][CS+1] */
+  float *out_dev;                               /* [H*W] */
+} SageDepthSigmaItem;
+int  sage_block_covariance(const double *packed_host, int K, int nlinks, const int32_t *links, int B, double damp,
+                           const double *diag_add, const int32_t *pairs /* [n_pairs][2] */, int n_pairs, double *Sigma);
+int  sage_covariance_plan(int K, int nlinks, const int32_t *links, int32_t *stored, int32_t *added);
+int  sage_window_covariance(SageWindow *w, double *damp_out);
+int  sage_window_get_covariance(const SageWindow *w, int kf_a, int kf_b, double *Sigma /* [B*B] */);
+int  sage_depth_sigma_batch(SageWorkspace *ws, const SageDepthSigmaItem *items, int n, int H, int W, int CS, int mode);
+int  sage_window_depth_sigma(SageWindow *w, const int32_t *kfs, int n, int mode, float *const *out_dev);
+int  sage_window_depth_sigma_timing(SageWindow *w, int mode, int reps, double *sigma_us, double *depth_batch_us);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,8 @@ SYMBOLS = [
     "sage_schur_marginal", "sage_marginal_prior_create", "sage_marginal_prior_dims", "sage_marginal_prior_get",
     "sage_marginal_prior_keyframes", "sage_marginal_prior_destroy", "sage_prior_evaluate", "sage_prior_term_plan",
     "sage_window_add_prior_term", "sage_window_num_prior_terms", "sage_window_get_prior_term", "sage_window_marginalize",
+    "sage_block_covariance", "sage_covariance_plan", "sage_window_covariance", "sage_window_get_covariance",
+    "sage_depth_sigma_batch", "sage_window_depth_sigma", "sage_window_depth_sigma_timing",
 ]
 
 
@@ -532,6 +534,36 @@ def block_solve(packed, K, links, B, damp, diag_add=None, g_add=None):
                                 C.c_double(damp), dp(da), dp(ga), delta.ctypes.data_as(C.POINTER(C.c_double))),
          "sage_block_solve")
     return delta
+
+
+def block_covariance_raw(packed, K, nlinks, links, B, damp, diag_add, pairs, n_pairs, Sigma) -> int:
+    """``sage_block_covariance`` with raw addresses (None -> NULL) -> status code"""
+    f = lib().sage_block_covariance
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    return f(packed, K, nlinks, links, B, damp, diag_add, pairs, n_pairs, Sigma)
+
+
+def block_covariance(packed, K, links, B, damp, pairs, diag_add=None):
+    """``sage_block_covariance``: the blocks ``pairs`` [n,2] (a keyframe with itself, or a link either way round) of the
+    inverse of the damped system ``sage_block_solve`` factorises -> Sigma [n,B,B] (rows pairs[.,0], columns pairs[.,1])"""
+    packed = np.ascontiguousarray(packed, dtype=np.float64)
+    lk = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1))
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    da = None if diag_add is None else np.ascontiguousarray(diag_add, np.float64)
+    Sigma = np.zeros((len(pr), B, B), np.float64)
+    _chk(block_covariance_raw(packed.ctypes.data, K, len(lk) // 2, lk.ctypes.data, B, damp, None if da is None else da.ctypes.data,
+                              pr.ctypes.data, len(pr), Sigma.ctypes.data), "sage_block_covariance")
+    return Sigma
+
+
+def covariance_plan(K, links):
+    """``sage_covariance_plan``: (blocks the plan of K keyframes and ``links`` stores, blocks the covariance closure adds)"""
+    lk = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1))
+    stored, added = C.c_int32(), C.c_int32()
+    f = lib().sage_covariance_plan
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(f(K, len(lk) // 2, lk.ctypes.data, C.addressof(stored), C.addressof(added)), "sage_covariance_plan")
+    return stored.value, added.value
 
 
 def solve_lookahead_count() -> int:
@@ -1664,6 +1696,60 @@ def depth_and_grad(ws: Workspace, bias, basis, code, scale, H, W, CS):
     return dpt, grad
 
 
+DEPTH_VARIANCE, DEPTH_SIGMA = 0, 1
+
+
+class SageDepthSigmaItem(C.Structure):
+    _fields_ = [("bias_dev", C.c_void_p), ("basis_dev", C.c_void_p), ("code_dev", C.c_void_p), ("scale", C.c_float),
+                ("cov_code_scale", C.c_void_p), ("out_dev", C.c_void_p)]
+
+
+def depth_sigma_batch_raw(ws, items, n, H, W, CS, mode) -> int:
+    """``sage_depth_sigma_batch`` with raw addresses (None -> NULL) -> status code"""
+    f = lib().sage_depth_sigma_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    return int(f(ws, items, n, H, W, CS, mode))
+
+
+def depth_sigma_batch(ws: Workspace, items, H, W, CS, mode=DEPTH_SIGMA, pad=0):
+    """``sage_depth_sigma_batch``: ``items`` = [(bias [H*W] device, basis [H*W,CS] device, code [CS] host, scale, S [(CS+1),
+    (CS+1)] host)] -> device tensor [n, H*W + pad] of depth variances / sigmas (the ``pad`` floats behind every map are
+    NaN and stay NaN).  Asynchronous on the workspace's stream: the inputs ride on the result."""
+    import torch
+    n, HW = len(items), H * W
+    out = torch.full((n, HW + pad), float("nan"), dtype=torch.float32, device="cuda")
+    table = (SageDepthSigmaItem * n)()
+    keep = []
+    for i, (bias, basis, code, scale, S) in enumerate(items):
+        code_d = _dev(code, np.float32)
+        S64 = np.ascontiguousarray(S, np.float64)
+        assert S64.shape == (CS + 1, CS + 1)
+        keep += [bias, basis, code_d, S64]
+        table[i] = SageDepthSigmaItem(bias.data_ptr(), basis.data_ptr(), code_d.data_ptr(), float(scale), S64.ctypes.data,
+                                      out[i].data_ptr())
+    _chk(depth_sigma_batch_raw(ws.h, C.addressof(table), n, H, W, CS, int(mode)), "sage_depth_sigma_batch")
+    out._sage_keepalive = keep
+    return out
+
+
+def window_covariance_raw(w, damp_out) -> int:
+    f = lib().sage_window_covariance
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    return int(f(w, damp_out))
+
+
+def window_get_covariance_raw(w, a, b, Sigma) -> int:
+    f = lib().sage_window_get_covariance
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    return int(f(w, a, b, Sigma))
+
+
+def window_depth_sigma_raw(w, kfs, n, mode, out_dev) -> int:
+    f = lib().sage_window_depth_sigma
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    return int(f(w, kfs, n, mode, out_dev))
+
+
 def gaussian_pyramid_with_grad(ws: Workspace, feat, mask, pyr: SagePyramid, FS):
     import torch
     out = torch.empty((FS, pyr.P), dtype=torch.float32, device="cuda")
@@ -1913,6 +1999,48 @@ class Window:
             return rc, prior
         _chk(rc, "sage_window_marginalize")
         return prior
+
+    def covariance(self, check=True):
+        """``sage_window_covariance``: the marginal covariances of the last solve -> that solve's damping; with
+        ``check=False`` -> (status code, damping)."""
+        damp = C.c_double(-1.0)
+        rc = window_covariance_raw(self.h, C.addressof(damp))
+        if not check:
+            return rc, damp.value
+        _chk(rc, "sage_window_covariance")
+        return damp.value
+
+    def get_covariance(self, a, b, check=True):
+        """``sage_window_get_covariance``: block (a, b) of the stored Sigma [B, B] (a == b, or a link either way round); with
+        ``check=False`` -> (status code, block)."""
+        S = np.zeros((self.B, self.B), np.float64)
+        rc = window_get_covariance_raw(self.h, int(a), int(b), S.ctypes.data)
+        if not check:
+            return rc, S
+        _chk(rc, "sage_window_get_covariance")
+        return S
+
+    def depth_sigma(self, kfs, mode=DEPTH_SIGMA, check=True):
+        """``sage_window_depth_sigma``: the depth variance / sigma maps of the keyframes ``kfs`` under the stored Sigma -> device
+        tensor [n, H, W] (the launch is enqueued on the window's stream; ``.cpu()`` of the result waits for it only on the
+        default stream: synchronise first when the window has a stream of its own); ``check=False`` -> (status code, tensor)."""
+        import torch
+        kf = np.ascontiguousarray(kfs, np.int32).reshape(-1)
+        out = torch.zeros((kf.size, self.win.H, self.win.W), dtype=torch.float32, device="cuda")
+        ptrs = (C.c_void_p * max(kf.size, 1))(*[out[i].data_ptr() for i in range(kf.size)])
+        rc = window_depth_sigma_raw(self.h, kf.ctypes.data if kf.size else None, kf.size, int(mode), ptrs)
+        if not check:
+            return rc, out
+        _chk(rc, "sage_window_depth_sigma")
+        return out
+
+    def depth_sigma_timing(self, reps, mode=DEPTH_SIGMA):
+        """``sage_window_depth_sigma_timing`` -> (median us of the sigma kernel over all keyframes, of depth_batch_kernel)"""
+        f = lib().sage_window_depth_sigma_timing
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        a, b = C.c_double(), C.c_double()
+        _chk(int(f(self.h, int(mode), int(reps), C.addressof(a), C.addressof(b))), "sage_window_depth_sigma_timing")
+        return a.value, b.value
 
     # raw-pointer views for torch.distributed (plumbing only)
     def packed_tensor(self):

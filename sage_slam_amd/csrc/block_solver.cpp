@@ -1794,13 +1794,12 @@ BlockEnvelope envelope_of(const BlockPlan &plan, int Bp)
 
 extern "C" long long sage_solve_lookahead_count(void) { return sage::g_lookahead_count.load(); }
 
-extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const int32_t *links, int B, double damp,
-                                const double *diag_add, const double *g_add, double *delta)
+namespace sage
 {
-  if (!packed || K < 1 || B < 1 || nlinks < 0 || (nlinks > 0 && !links) || !delta)
-    return SAGE_E_INVALID;
-  // the factorisation works on blocks padded to Bp rows (identity on the padding): the fixed-block kernels' sizes
-  const int Bp = sage::padded_block(B);
+int block_system_build(const double *packed, int K, int nlinks, const int32_t *links, int B, double damp, const double *diag_add,
+                       const double *g_add, BlockPlan &bp, std::vector<double> &T, std::vector<double> &y)
+{
+  const int Bp = padded_block(B);
   if (Bp == 0)
     return SAGE_E_UNSUPPORTED;
   const int BB = B * B, BBp = Bp * Bp;
@@ -1812,30 +1811,29 @@ extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const i
     lk[l] = {links[2 * l], links[2 * l + 1]}; // (plan_blocks refuses a link that is not a < b inside the window)
   // transposed-block storage (the one the window engine runs on the device-scattered storage), with the same
   // elimination order and two-core split
-  sage::BlockPlan bp;
-  int rcp = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
+  int rcp = plan_blocks(K, lk, !env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
   if (rcp == SAGE_E_UNSUPPORTED) // duplicate links accumulate on this path: plan without them
   {
     std::sort(lk.begin(), lk.end());
     lk.erase(std::unique(lk.begin(), lk.end()), lk.end());
-    rcp = sage::plan_blocks(K, lk, !sage::env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
+    rcp = plan_blocks(K, lk, !env_flag("SAGE_SOLVE_NO_SPLIT"), bp);
   }
   if (rcp != SAGE_OK)
     return rcp;
-  const int nblk = bp.nblk;
   // per keyframe, then per link: a link listed twice accumulates (damped_system.h has the element rules)
-  std::vector<double> T((size_t)nblk * BBp, 0.0), X((size_t)K * BBp), y((size_t)K * Bp, 0.0);
+  T.assign((size_t)bp.nblk * BBp, 0.0);
+  y.assign((size_t)K * Bp, 0.0);
   for (int q = 0; q < K; ++q)
   {
     const int k = bp.perm[q];
     double *D = T.data() + (size_t)bp.index(q, q) * BBp;
     for (int r = 0; r < Bp; ++r)
       for (int c = 0; c < Bp; ++c)
-        D[sage::stored_slot(r, c, Bp)] =
-            (r < B && c < B) ? sage::damped_diag_elem(diag + (size_t)k * BB, B, r, c, diag_add ? diag_add[k * B + r] : 0.0, damp)
-                             : sage::damped_pad_elem(r, c, damp);
+        D[stored_slot(r, c, Bp)] =
+            (r < B && c < B) ? damped_diag_elem(diag + (size_t)k * BB, B, r, c, diag_add ? diag_add[k * B + r] : 0.0, damp)
+                             : damped_pad_elem(r, c, damp);
     for (int r = 0; r < B; ++r)
-      y[(size_t)q * Bp + r] = sage::damped_rhs_elem(g[(size_t)k * B + r], g_add ? g_add[k * B + r] : 0.0);
+      y[(size_t)q * Bp + r] = damped_rhs_elem(g[(size_t)k * B + r], g_add ? g_add[k * B + r] : 0.0);
   }
   for (int l = 0; l < nlinks; ++l)
   {
@@ -1845,18 +1843,36 @@ extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const i
     const bool row_is_a = bp.perm[qi] == a;
     for (int r = 0; r < B; ++r)
       for (int c = 0; c < B; ++c)
-        D[sage::stored_slot(r, c, Bp)] += lnk[(size_t)l * BB + sage::link_elem(row_is_a, r, c, B)];
+        D[stored_slot(r, c, Bp)] += lnk[(size_t)l * BB + link_elem(row_is_a, r, c, B)];
   }
+  return SAGE_OK;
+}
+
+int block_system_factor(const BlockPlan &bp, int Bp, double *T, double *X, double *y)
+{
+  BlockEnvelope env = envelope_of(bp, Bp);
+  SolveLease lease; // (arm and solve: no shutdown joins a helper in between)
+  if (bp.n1 > 0)
+    env.no_lookahead = block_chol_arm(block_plan_has_arrow_rows(env), block_plan_long_arrow_chains(env));
+  return block_chol_solve_tr(env, T, X, y);
+}
+} // namespace sage
+
+extern "C" int sage_block_solve(const double *packed, int K, int nlinks, const int32_t *links, int B, double damp,
+                                const double *diag_add, const double *g_add, double *delta)
+{
+  if (!packed || K < 1 || B < 1 || nlinks < 0 || (nlinks > 0 && !links) || !delta)
+    return SAGE_E_INVALID;
+  // the factorisation works on blocks padded to Bp rows (identity on the padding): the fixed-block kernels' sizes
+  const int Bp = sage::padded_block(B);
+  sage::BlockPlan bp;
+  std::vector<double> T, y;
+  if (const int rcb = sage::block_system_build(packed, K, nlinks, links, B, damp, diag_add, g_add, bp, T, y))
+    return rcb;
+  std::vector<double> X((size_t)K * Bp * Bp);
   static const bool dbg = sage::env_flag("SAGE_DEBUG_TIMING");
   const auto t0 = std::chrono::steady_clock::now();
-  sage::BlockEnvelope env = sage::envelope_of(bp, Bp);
-  int rcf;
-  {
-    sage::SolveLease lease; // (arm and solve: no shutdown joins a helper in between)
-    if (bp.n1 > 0)
-      env.no_lookahead = sage::block_chol_arm(sage::block_plan_has_arrow_rows(env), sage::block_plan_long_arrow_chains(env));
-    rcf = sage::block_chol_solve_tr(env, T.data(), X.data(), y.data());
-  }
+  const int rcf = sage::block_system_factor(bp, Bp, T.data(), X.data(), y.data());
   if (dbg)
     fprintf(stderr, "[sage block_solve] fixed-block Cholesky + substitution %.3f ms\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());

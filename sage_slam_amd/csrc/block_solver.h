@@ -132,4 +132,11 @@ int plan_blocks(int K, const std::vector<std::pair<int, int>> &links, bool may_s
 // the envelope of a plan's storage with Bp-padded blocks: K, Bp, the five range tables, n1 / n2 and the column lists.
 // The caller adds what is its own (ready / epoch / fill / no_lookahead); the plan must outlive the envelope.
 BlockEnvelope envelope_of(const BlockPlan &plan, int Bp);
+// What sage_block_solve factorises, for whoever else wants that factor (covariance_host.cpp): the plan of `links` (duplicates
+// summed), the damped system (H + diag_add) + damp diag(H + diag_add) of a packed buffer scattered into the plan's storage T
+// at padded_block(B), and the right-hand side g + g_add in y.  SAGE_OK, or what plan_blocks / padded_block refuse.
+int block_system_build(const double *packed, int K, int nlinks, const int32_t *links, int B, double damp, const double *diag_add,
+                       const double *g_add, BlockPlan &bp, std::vector<double> &T, std::vector<double> &y);
+// ... and its factorisation under a SolveLease with the helpers armed as the plan wants them: block_chol_solve_tr's return
+int block_system_factor(const BlockPlan &bp, int Bp, double *T, double *X, double *y);
 } // namespace sage

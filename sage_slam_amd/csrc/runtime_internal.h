@@ -96,6 +96,7 @@ extern "C"
 #include "dogleg.h"            // the dogleg step's dots, partial slots and pinned record
 #include "keyframe_prepare.h"  // a prepared keyframe's fingerprint, layout and plan; the handle itself
 #include "marginal.h"          // a marginal prior's handle, the layout of a window's prior terms
+#include "covariance.h"        // the closed pattern and the recursion of the marginal covariances
 
 using namespace sage;
 
@@ -209,9 +210,41 @@ static_assert(offsetof(TrackHost, photo_AtA) == 16 * sizeof(float) && offsetof(T
 
 enum class WorkKind { none, dense, tracker }; // dense: pick_tiles_per_block's run length; tracker: one kTile per workgroup
 
+// depth_sigma.hip: what a depth-sigma launch reads besides the keyframes' planes -- the items' table and their fp32 (code,
+// scale) covariances, built in pinned memory and copied to the device on the launch's stream.  `copied` says the copy of the
+// last call has left the pinned side: the next call waits for that (not for the kernel) before it writes there again
+struct DepthSigmaStage
+{
+  PinnedBuf host;
+  DevBuf dev;
+  hipEvent_t copied = nullptr;
+  bool busy = false;
+  DepthSigmaStage() = default;
+  DepthSigmaStage(const DepthSigmaStage &) = delete;
+  DepthSigmaStage &operator=(const DepthSigmaStage &) = delete;
+  ~DepthSigmaStage()
+  {
+    if (copied)
+      (void)hipEventDestroy(copied);
+  }
+};
+struct DepthSigmaEntry // one keyframe of a launch; S: HOST, the (CS + 1) x (CS + 1) block with leading dimension ldS
+{
+  const float *bias, *basis, *code, *scale_dev; // scale_dev: where the scale lies on the device, or null: `scale`
+  float scale;
+  const double *S;
+  size_t ldS;
+  float *out;
+};
+// one launch for n > 0 keyframes on stream s; arguments are the caller's to check (CS 16 or 32, mode 0 / 1, H * W >= 1).
+// before / after: optional events recorded right around the kernel (sage_window_depth_sigma_timing)
+int depth_sigma_enqueue(hipStream_t s, DepthSigmaStage &stage, const DepthSigmaEntry *e, int n, int H, int W, int CS, int mode,
+                        hipEvent_t before = nullptr, hipEvent_t after = nullptr);
+
 struct SageWorkspace
 {
   hipStream_t stream = nullptr;
+  DepthSigmaStage sigma; // sage_depth_sigma_batch
   DevBuf work, edge_first, edge_tiles, partials, misc, dpt0;
   PinnedBuf host_stats; // WsHostStats, from sage_workspace_create on
   unsigned ticket_epoch = 0;
@@ -448,6 +481,7 @@ struct SageWindow
   uint64_t dense_serial = 0;              // counts the linearizes that have written dense[].AtA (FactorSlot::live_serial)
   DoglegSide dogleg;                      // the dogleg step's tables, vectors and pinned dots (window_dogleg.hip)
   RelinSide relin;                        // partial relinearization: mode, snapshot, depth stamps, sub work lists (window_relin.hip)
+  CovarianceSide cov;                     // marginal covariances of the last solve, opt-in (window_covariance.hip)
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an

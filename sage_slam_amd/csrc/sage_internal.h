@@ -336,6 +336,20 @@ struct SolverLayout
   size_t x_count;
 };
 SolverLayout solver_layout(const DeviceSolver *S);
+// Read-only view of the factor the last solver_run left on the host (window_covariance.hip): the elimination plan, blockwise
+// L^T and the inverses of the diagonal factors (block_solver.h), Bs solver rows padded to Bp, the damping it was formed
+// with, and the count of solves so far.  valid: that solve succeeded; the next solver_run overwrites the storage
+struct BlockPlan; // block_solver.h
+struct SolverFactor
+{
+  const BlockPlan *plan;
+  const double *T, *X;
+  int Bp, Bs;
+  double damp;
+  unsigned epoch;
+  bool valid;
+};
+SolverFactor solver_factor(const DeviceSolver *S);
 // the retraction of a solve for a solution x_dev that is on the device already: the same kernel, the same mirrors
 int solver_retract_from(DeviceSolver *S, hipStream_t stream, const double *x_dev, const float *vars0, float *vars1, int CS);
 

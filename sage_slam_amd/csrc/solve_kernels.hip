@@ -266,6 +266,8 @@ struct DeviceSolver
   std::vector<double> h_X;          // inverses of the diagonal factors
   BlockPlan host_plan;              // elimination order and block storage (what the host factorisation reads)
   std::vector<uint8_t> h_fill;      // per block: structural fill-in (not delivered by the scatter kernel: BlockEnvelope::fill)
+  bool factor_valid = false;        // h_T / h_X hold the factor of solve number `epoch`, damped by factor_damp (solver_factor)
+  double factor_damp = 0.0;
 
   double *h_blocks() const { return h_T.as<double>(); }
   SolveResult *result() const { return h_pinned.as<SolveResult>(); }
@@ -397,6 +399,7 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   S->epoch += 1;
   if (S->epoch == 0) // wrapped: 0 is the "never written" value
     S->epoch = 1;
+  S->factor_valid = false; // (the scatter below overwrites the last solve's factor)
   hipLaunchKernelGGL(solve_scatter_kernel, dim3(std::min(kScatterWorkgroups, S->nblk)), dim3(256), 0, stream, S->plan,
                      packed_dev, vars0, S->VS, CS, pri, damp, S->h_blocks(), S->h_y, S->d_order,
                      S->h_flags, S->epoch);
@@ -435,6 +438,8 @@ int solver_run(DeviceSolver *S, hipStream_t stream, const double *packed_dev, co
   if (bad)
     return SAGE_E_NOT_PSD;
   guard.word = S->go_epoch; // the solution is in h_y: go
+  S->factor_valid = true;
+  S->factor_damp = damp;
   return SAGE_OK;
 }
 
@@ -446,6 +451,11 @@ int solver_host_status(const DeviceSolver *S) { return S->result()->status; }
 SolverLayout solver_layout(const DeviceSolver *S)
 {
   return SolverLayout{S->plan.pos, S->plan.to_solver, S->plan.hold, S->Bp, (size_t)S->K * S->Bp};
+}
+
+SolverFactor solver_factor(const DeviceSolver *S)
+{
+  return SolverFactor{&S->host_plan, S->h_blocks(), S->h_X.data(), S->Bp, S->Bs, S->factor_damp, S->epoch, S->factor_valid};
 }
 
 // a candidate for a solution that is on the device already (the dogleg step's blends: window_dogleg.hip): solve_retract_kernel

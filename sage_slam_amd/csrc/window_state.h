@@ -259,6 +259,21 @@ struct DoglegSide
   bool vectors = false;   // a products call has filled them (sage_window_get_dogleg_vectors reads the last call's)
 };
 
+// ---- the marginal covariances of the last solve (window_covariance.hip): Sigma's blocks on the host, in keyframe ids and the
+// window's row order (pose 6, code CS, scale), zeros on held and dropped rows; everything is built by the first call ----
+struct CovarianceSide
+{
+  cov::CovPlan plan;          // the closed pattern of the solver's elimination plan (once per window)
+  bool planned = false;
+  std::vector<double> work;   // Sigma on that pattern, in positions and padded solver rows: what the recursion writes
+  std::vector<double> diag;   // [K][B * B]
+  std::vector<double> link;   // [nlinks][B * B]: rows of the link's first keyframe, columns of its second
+  bool valid = false;         // diag / link are Sigma of solve number `epoch` (SolverFactor::epoch) ...
+  unsigned epoch = 0;
+  double damp = 0.0;          // ... which was damped by this
+  DepthSigmaStage stage;      // sage_window_depth_sigma's table and fp32 covariances
+};
+
 // ---- sharded windows ----
 struct WindowDist
 {
