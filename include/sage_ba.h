@@ -2016,6 +2016,127 @@ int  sage_depth_sigma_batch(SageWorkspace *ws, const SageDepthSigmaItem *items, 
 int  sage_window_depth_sigma(SageWindow *w, const int32_t *kfs, int n, int mode, float *const *out_dev);
 int  sage_window_depth_sigma_timing(SageWindow *w, int mode, int reps, double *sigma_us, double *depth_batch_us);
 
+/* ---- TSDF fusion (tsdf_host.cpp, tsdf.hip, window_tsdf.hip) ----
+ * The stage that turns keyframe depth maps, poses and a per-pixel std image into the fused surface: TSDFVolume.integrate of
+ * representation/scripts/generate_reconstruction_fly_through.py:130-331 (a kernel kept as a string there).  The reference has
+ * no uncertainty to give it and fills the std image with ones (:601-606); a window hands it its depth sigma maps.
+ *
+ * The volume: dim = (dx, dy, dz) voxels in C order [x][y][z], z fastest; tsdf, weight and (optional) color, fp32, zero at
+ * creation; origin fp32 x 3; voxel_size and trunc_margin fp32.
+ * One view (a depth image with its pose): for every voxel (ix, iy, iz), in fp32, one operation at a time, NO fused
+ * multiply-add, division correctly rounded:
+ *   1. p = origin + (float)i * voxel_size                       (one multiply, then one add, per axis)
+ *   2. q = p - t                                                (pose12 = [R row-major, t], world from camera)
+ *   3. c_x = (R[0][0] q_x + R[1][0] q_y) + R[2][0] q_z, c_y and c_z with columns 1 and 2   (R^T q, summed left to right)
+ *   4. skip if c_z < min_depth
+ *   5. u = (int)roundf(fx (c_x / c_z) + cx), v likewise; roundf rounds half away from zero (-0.4 is pixel 0, inside)
+ *   6. skip if u < 0, u >= w, v < 0 or v >= h
+ *   7. d = depth[v w + u] (0 where mask[v w + u] <= 0.5), s = std[v w + u] (1 without a std image), s = fmaxf(s, std_floor);
+ *      skip if d <= 0 or s <= 0
+ *   8. diff = d - c_z; skip if diff < -trunc_margin
+ *   9. dist = fminf(1, diff / s)                                (clipped above only: the lower end is -trunc_margin / s)
+ *  10. w_new = w_old + obs_weight; tsdf = (tsdf w_old + dist obs_weight) / w_new; weight = w_new
+ *  11. with a color image (packed b 65536 + g 256 + r in one float): old and new unpacked with floorf, every channel
+ *      fminf(roundf((old w_old + new obs_weight) / w_new), 255), repacked
+ * The running average does not commute in floating point: the order of the views is part of the result.
+ * Where this departs from the reference's text: (i) the voxel's coordinates come from the linear index by integer arithmetic
+ * (the reference divides in fp32, which is wrong above 2^24 voxels, and lets index N through); (ii) the reference's bits
+ * depend on nvcc's contraction, these are the operations as written; (iii) the unused uncertainty volume does not exist;
+ * (iv) a pixel coordinate that is NaN (0 / 0: possible only with min_depth <= 0) skips the voxel.
+ * With sigma maps as the std image a voxel's value is sum_i w_i (d_i - z) / s_i / sum_i w_i wherever no view clips: its zero
+ * crossing lies at the inverse-sigma-weighted mean depth sum_i (d_i / s_i) / sum_i (1 / s_i).
+ *
+ * Host planning (no device):
+ * sage_tsdf_frustum_bounds: get_view_frustum (:376-387) folded into the running minimum / maximum of :561-567.  Five points in
+ * double -- the camera centre and the image corners (0 | w, 0 | h) at max_depth, as ((u - cx) max_depth) / fx -- taken to
+ * world coordinates and folded into bounds = [min x, y, z, max x, y, z], which the CALLER initialises: zeros reproduce the
+ * script, whose volume therefore always contains the world origin; the first view's own points can be had with +-infinity.
+ * SAGE_E_INVALID for NULL, fx or fy not positive, w or h < 1, a pose or max_depth that is not finite.
+ * sage_tsdf_plan: voxel = base_voxel cbrt(prod((max - min) / base_voxel) / max_voxels) (:569-574, applied always, as the
+ * script does; max_voxels <= 0 keeps base_voxel), dim = ceil((max - min) / voxel) (:138-141), origin = (float)min,
+ * trunc_margin = voxel trunc_multiplier.  device_bytes: the volume's arrays and its per-brick counts.  SAGE_E_INVALID for
+ * NULL, bounds that are empty along an axis or not finite, base_voxel or trunc_multiplier not positive and finite, and a
+ * voxel count above 2^31 - 1.
+ *
+ * sage_tsdf_create / _destroy / _reset (zeros, on the stream) / _get (host copies, any may be NULL; drains the stream) /
+ * _dev (the device arrays; color NULL for a volume without one).  The volume lives on its workspace's stream and must be
+ * destroyed before the workspace.
+ * sage_tsdf_integrate: one view, one launch (tsdf_integrate_kernel: one thread per voxel, lanes along z), asynchronous on the
+ * workspace's stream: the view's device arrays must stay valid until the stream has passed the call.  A view with a color
+ * image on a volume without a color array: SAGE_E_INVALID.  Argument checks come before any launch.
+ * sage_tsdf_integrate_batch: n views (1 <= n <= SAGE_TSDF_MAX_VIEWS) in ONE launch, whatever n
+ * (sage_tsdf_integrate_batch_launches).  Contract: the volume afterwards equals, byte for byte, n calls of sage_tsdf_integrate
+ * in the order given.  A workgroup owns a brick of voxels (its long side, 64, along z), keeps their tsdf, weight and color in
+ * registers while it walks the views in order and writes them once: the volume crosses HBM once, not n times.  The views'
+ * parameters are uploaded once and staged in LDS sage_tsdf_view_chunk() at a time; before it walks a chunk the workgroup
+ * drops the views none of its voxels can pass steps 4-6 of (the brick's eight corners against the four side planes and the
+ * min_depth plane, with a slack for the fp32 rounding: DESIGN.md s3).  The cull only removes work whose outcome is "skip":
+ * SAGE_TSDF_NO_CULL keeps every view and gives the same bytes.  SAGE_TSDF_BRICK_X1 / _X2 / _X4 choose the brick's extent
+ * along x (voxels per thread) for measurements; 0 is the shape in use.  No atomics, every output has one writer.
+ * sage_tsdf_last_stats: drains the stream and sums the per-brick counts of the last batch. */
+#define SAGE_TSDF_MAX_VIEWS 1024
+enum { SAGE_TSDF_NO_CULL = 1, SAGE_TSDF_BRICK_X1 = 1 << 4, SAGE_TSDF_BRICK_X2 = 2 << 4, SAGE_TSDF_BRICK_X4 = 3 << 4 };
+enum { SAGE_TSDF_STD_ONE = 0, SAGE_TSDF_STD_SIGMA = 1 };
+typedef struct SageTsdfPlan
+{
+  int32_t dim[3];
+  int32_t with_color;
+  float origin[3];
+  float voxel_size, trunc_margin;
+  int64_t voxels;       /* dim[0] dim[1] dim[2] */
+  int64_t device_bytes;
+} SageTsdfPlan;
+typedef struct SageTsdfView
+{
+  const float *depth_dev;  /* [h*w], required */
+  const float *std_dev;    /* [h*w], or NULL: 1 wherever depth > 0 (the script's ones * valid_mask) */
+  const float *mask_dev;   /* [h*w], or NULL: no mask; a pixel with mask <= 0.5 reads depth 0 (the script's depth_map * mask) */
+  const float *color_dev;  /* [h*w] packed, or NULL: the color volume is not touched */
+  int64_t image_floats;    /* the floats every image above holds: fewer than cam.w * cam.h is SAGE_E_INVALID */
+  float pose12[SAGE_POSE_FLOATS]; /* world from camera */
+  SageCamera cam;
+  float obs_weight, min_depth;
+  float std_floor;         /* s = fmaxf(s, std_floor) before the s <= 0 test; 0: the reference's rule.  A held keyframe's
+                              sigma map is exactly 0 and would otherwise contribute nothing */
+} SageTsdfView;
+typedef struct SageTsdfStats
+{
+  int64_t bricks, pairs, pairs_kept; /* pairs = bricks * views */
+  int32_t views, brick[3];
+} SageTsdfStats;
+typedef struct SageTsdfVolume SageTsdfVolume;
+int  sage_tsdf_frustum_bounds(const SageCamera *cam, const float *pose12, double max_depth, double bounds[6]);
+int  sage_tsdf_plan(const double bounds[6], double base_voxel, double max_voxels, double trunc_multiplier, int with_color,
+                    SageTsdfPlan *out);
+int  sage_tsdf_create(SageWorkspace *ws, const SageTsdfPlan *plan, SageTsdfVolume **out);
+void sage_tsdf_destroy(SageTsdfVolume *vol);
+int  sage_tsdf_reset(SageTsdfVolume *vol);
+int  sage_tsdf_get(SageTsdfVolume *vol, float *tsdf, float *weight, float *color);
+int  sage_tsdf_dev(SageTsdfVolume *vol, float **tsdf, float **weight, float **color);
+int  sage_tsdf_integrate(SageTsdfVolume *vol, const SageTsdfView *view);
+int  sage_tsdf_integrate_batch(SageTsdfVolume *vol, const SageTsdfView *views, int n, int flags);
+int  sage_tsdf_integrate_batch_launches(int n);
+int  sage_tsdf_view_chunk(void);
+int  sage_tsdf_last_stats(SageTsdfVolume *vol, SageTsdfStats *out);
+/* The window path.  sage_window_depth_range: the minimum over the positive values and the maximum of the depth maps
+ * s (bias + basis code) of the keyframes kfs [n] at the current variables, under the window's video mask (a masked pixel
+ * counts as 0; no positive value anywhere: *dmin = 0): what sage_tsdf_frustum_bounds takes as max_depth.  The maps, then one
+ * reduction kernel (a workgroup and one writer per keyframe) on the window's stream, finished on the host; drains the stream.
+ * Both calls form the listed keyframes' maps in scratch of their own with the kernel of sage_depth_and_grad -- the same bytes
+ * that call gives for the same variables; the window's depth batch rounds its dot product differently -- and leave the
+ * window's own maps and their bookkeeping alone.
+ * sage_window_fuse_tsdf: one sage_tsdf_integrate_batch on the window's stream over the keyframes kfs [n], in the order given,
+ * with the depth maps at the current variables (prepared keyframes included), the window's own poses and camera, and
+ * cfg.mask_dev as the mask.  std_mode SAGE_TSDF_STD_ONE: the reference's behaviour; SAGE_TSDF_STD_SIGMA: the sigma maps of
+ * the stored Sigma as the std image (the zero crossing then lies at the inverse-sigma-weighted mean depth, above), formed in
+ * scratch the window owns: SAGE_E_STATE without a current Sigma, SAGE_E_UNSUPPORTED where sage_window_depth_sigma answers it.
+ * The volume must live on the window's device (SAGE_E_INVALID otherwise); where its workspace's stream is not the window's
+ * the two are ordered with events.  SAGE_E_UNSUPPORTED for a sharded window; SAGE_E_STATE before finalize; SAGE_E_INVALID for
+ * NULL, n outside 1 .. SAGE_TSDF_MAX_VIEWS, a bad keyframe or std_mode and what sage_tsdf_integrate_batch refuses. */
+int  sage_window_depth_range(SageWindow *w, const int32_t *kfs, int n, float *dmin, float *dmax);
+int  sage_window_fuse_tsdf(SageWindow *w, SageTsdfVolume *vol, const int32_t *kfs, int n, int std_mode, float std_floor,
+                           float obs_weight, float min_depth);
+
 #ifdef __cplusplus
 }
 #endif

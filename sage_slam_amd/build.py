@@ -15,9 +15,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libsage_ba.so")
-SOURCES = ["photo_kernels.hip", "geo_kernels.hip", "track_kernels.hip", "producers.hip", "keypoint_kernels.hip", "graph_kernels.hip", "solve_kernels.hip", "operators.hip", "tracker.hip", "overlap.hip", "depth_scale.hip", "bow.hip", "registration.hip", "match_batch.hip", "voc_build.hip", "window.hip", "window_eval.hip", "window_reduce.hip", "window_solve.hip", "window_lm.hip", "window_profile.hip", "window_build.hip", "window_terms.hip", "window_dist.hip", "window_factors.hip", "psd_project.hip", "window_dogleg.hip", "window_relin.hip", "keyframe_prepare.hip", "window_prior.hip", "window_covariance.hip", "depth_sigma.hip",
-           "host_math.cpp", "factor_blocks.cpp", "block_solver.cpp", "host_threads.cpp", "shard_solve.cpp", "convex_hull.cpp", "bow_database.cpp", "registration_host.cpp", "voc_build_host.cpp", "depth_scale_host.cpp", "loop_accept_host.cpp", "psd_project_host.cpp", "dogleg_host.cpp", "relin_host.cpp", "keyframe_prepare_host.cpp", "marginal_host.cpp", "covariance_host.cpp"]
-HEADERS = ["sage_device.h", "sage_internal.h", "damped_system.h", "host_math.h", "factor_blocks.h", "block_solver.h", "host_threads.h", "device_buffers.h", "runtime_internal.h", "window_state.h", "finalize_bodies.h", "keypoint_batch.h", "graph_terms.h", "graph_batch.h", "term_results.h", "window_plan.h", "registration_plan.h", "registration_math.h", "depth_scale_plan.h", "loop_accept.h", "voc_build.h", "psd_project.h", "dogleg.h", "relin_plan.h", "keyframe_prepare.h", "marginal.h", "covariance.h", os.path.join(ROOT, "include", "sage_ba.h")]
+SOURCES = ["photo_kernels.hip", "geo_kernels.hip", "track_kernels.hip", "producers.hip", "keypoint_kernels.hip", "graph_kernels.hip", "solve_kernels.hip", "operators.hip", "tracker.hip", "overlap.hip", "depth_scale.hip", "bow.hip", "registration.hip", "match_batch.hip", "voc_build.hip", "window.hip", "window_eval.hip", "window_reduce.hip", "window_solve.hip", "window_lm.hip", "window_profile.hip", "window_build.hip", "window_terms.hip", "window_dist.hip", "window_factors.hip", "psd_project.hip", "window_dogleg.hip", "window_relin.hip", "keyframe_prepare.hip", "window_prior.hip", "window_covariance.hip", "depth_sigma.hip", "tsdf.hip", "window_tsdf.hip",
+           "host_math.cpp", "factor_blocks.cpp", "block_solver.cpp", "host_threads.cpp", "shard_solve.cpp", "convex_hull.cpp", "bow_database.cpp", "registration_host.cpp", "voc_build_host.cpp", "depth_scale_host.cpp", "loop_accept_host.cpp", "psd_project_host.cpp", "dogleg_host.cpp", "relin_host.cpp", "keyframe_prepare_host.cpp", "marginal_host.cpp", "covariance_host.cpp", "tsdf_host.cpp"]
+HEADERS = ["sage_device.h", "sage_internal.h", "damped_system.h", "host_math.h", "factor_blocks.h", "block_solver.h", "host_threads.h", "device_buffers.h", "runtime_internal.h", "window_state.h", "finalize_bodies.h", "keypoint_batch.h", "graph_terms.h", "graph_batch.h", "term_results.h", "window_plan.h", "registration_plan.h", "registration_math.h", "depth_scale_plan.h", "loop_accept.h", "voc_build.h", "psd_project.h", "dogleg.h", "relin_plan.h", "keyframe_prepare.h", "marginal.h", "covariance.h", "tsdf.h", os.path.join(ROOT, "include", "sage_ba.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOSTCXX = os.environ.get("HOSTCXX", "/opt/rocm/lib/llvm/bin/clang++")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -295,6 +295,9 @@ SYMBOLS = [
     "sage_window_add_prior_term", "sage_window_num_prior_terms", "sage_window_get_prior_term", "sage_window_marginalize",
     "sage_block_covariance", "sage_covariance_plan", "sage_window_covariance", "sage_window_get_covariance",
     "sage_depth_sigma_batch", "sage_window_depth_sigma", "sage_window_depth_sigma_timing",
+    "sage_tsdf_frustum_bounds", "sage_tsdf_plan", "sage_tsdf_create", "sage_tsdf_destroy", "sage_tsdf_reset", "sage_tsdf_get",
+    "sage_tsdf_dev", "sage_tsdf_integrate", "sage_tsdf_integrate_batch", "sage_tsdf_integrate_batch_launches",
+    "sage_tsdf_view_chunk", "sage_tsdf_last_stats", "sage_window_depth_range", "sage_window_fuse_tsdf",
 ]
 
 
@@ -1748,6 +1751,201 @@ def window_depth_sigma_raw(w, kfs, n, mode, out_dev) -> int:
     f = lib().sage_window_depth_sigma
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     return int(f(w, kfs, n, mode, out_dev))
+
+
+# --------------------------------------------------------------------------- TSDF fusion
+SAGE_TSDF_MAX_VIEWS = 1024
+TSDF_NO_CULL, TSDF_BRICK_X1, TSDF_BRICK_X2, TSDF_BRICK_X4 = 1, 1 << 4, 2 << 4, 3 << 4
+TSDF_STD_ONE, TSDF_STD_SIGMA = 0, 1
+
+
+class SageTsdfPlan(C.Structure):
+    _fields_ = [("dim", C.c_int32 * 3), ("with_color", C.c_int32), ("origin", C.c_float * 3), ("voxel_size", C.c_float),
+                ("trunc_margin", C.c_float), ("voxels", C.c_int64), ("device_bytes", C.c_int64)]
+
+
+class SageTsdfView(C.Structure):
+    _fields_ = [("depth_dev", C.c_void_p), ("std_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("color_dev", C.c_void_p),
+                ("image_floats", C.c_int64), ("pose12", C.c_float * 12), ("cam", SageCamera), ("obs_weight", C.c_float),
+                ("min_depth", C.c_float), ("std_floor", C.c_float)]
+
+
+class SageTsdfStats(C.Structure):
+    _fields_ = [("bricks", C.c_int64), ("pairs", C.c_int64), ("pairs_kept", C.c_int64), ("views", C.c_int32),
+                ("brick", C.c_int32 * 3)]
+
+
+def _camera_struct(cam) -> SageCamera:
+    return cam if isinstance(cam, SageCamera) else SageCamera(cam.fx, cam.fy, cam.cx, cam.cy, cam.w, cam.h)
+
+
+def tsdf_frustum_bounds_raw(cam_ptr, pose_ptr, max_depth, bounds_ptr) -> int:
+    f = lib().sage_tsdf_frustum_bounds
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    return int(f(cam_ptr, pose_ptr, max_depth, bounds_ptr))
+
+
+def tsdf_frustum_bounds(cam, pose12, max_depth, bounds=None) -> np.ndarray:
+    """``sage_tsdf_frustum_bounds``: the view's frustum folded into ``bounds`` [min xyz, max xyz] (default zeros: the
+    script's start, a volume that contains the world origin) -> the new bounds"""
+    b = np.zeros(6, np.float64) if bounds is None else np.array(bounds, np.float64).reshape(6)
+    c, p = _camera_struct(cam), _f32(pose12).reshape(12)
+    _chk(tsdf_frustum_bounds_raw(C.addressof(c), p.ctypes.data, float(max_depth), b.ctypes.data), "sage_tsdf_frustum_bounds")
+    return b
+
+
+def tsdf_plan_raw(bounds_ptr, base_voxel, max_voxels, trunc_multiplier, with_color, out_ptr) -> int:
+    f = lib().sage_tsdf_plan
+    f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]
+    return int(f(bounds_ptr, base_voxel, max_voxels, trunc_multiplier, with_color, out_ptr))
+
+
+def tsdf_plan(bounds, base_voxel=0.1, max_voxels=64.0e6, trunc_multiplier=10.0, with_color=False) -> SageTsdfPlan:
+    """``sage_tsdf_plan`` -> ``SageTsdfPlan`` (dim, origin, voxel_size, trunc_margin, voxels, device_bytes)"""
+    b = np.ascontiguousarray(bounds, np.float64).reshape(6)
+    out = SageTsdfPlan()
+    _chk(tsdf_plan_raw(b.ctypes.data, base_voxel, max_voxels, trunc_multiplier, int(with_color), C.addressof(out)), "sage_tsdf_plan")
+    return out
+
+
+def tsdf_plan_exact(dim, origin, voxel_size, trunc_margin, with_color=False) -> SageTsdfPlan:
+    """a plan of exactly these dimensions (tests, benchmarks): what ``sage_tsdf_plan`` would fill in"""
+    p = SageTsdfPlan()
+    p.dim[:] = [int(d) for d in dim]
+    p.origin[:] = [float(o) for o in origin]
+    p.with_color, p.voxel_size, p.trunc_margin = int(with_color), float(voxel_size), float(trunc_margin)
+    p.voxels = int(np.prod([int(d) for d in dim]))
+    p.device_bytes = p.voxels * 4 * (3 if with_color else 2)
+    return p
+
+
+def tsdf_view(depth, pose12, cam, std=None, mask=None, color=None, obs_weight=1.0, min_depth=1.0e-4, std_floor=0.0,
+              image_floats=None) -> SageTsdfView:
+    """a ``SageTsdfView`` of device tensors (None -> NULL); the tensors ride on the struct"""
+    v = SageTsdfView()
+    v.depth_dev, v.std_dev, v.mask_dev, v.color_dev = [t.data_ptr() if t is not None else None for t in (depth, std, mask, color)]
+    v.image_floats = int(depth.numel() if image_floats is None else image_floats)
+    v.pose12[:] = [float(x) for x in np.asarray(pose12, np.float32).reshape(12)]
+    v.cam = _camera_struct(cam)
+    v.obs_weight, v.min_depth, v.std_floor = float(obs_weight), float(min_depth), float(std_floor)
+    v._sage_keepalive = (depth, std, mask, color)
+    return v
+
+
+def tsdf_integrate_raw(vol, view_ptr) -> int:
+    f = lib().sage_tsdf_integrate
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    return int(f(vol, view_ptr))
+
+
+def tsdf_integrate_batch_raw(vol, views_ptr, n, flags) -> int:
+    f = lib().sage_tsdf_integrate_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    return int(f(vol, views_ptr, n, flags))
+
+
+def tsdf_create_raw(ws, plan_ptr, out_ptr) -> int:
+    f = lib().sage_tsdf_create
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    return int(f(ws, plan_ptr, out_ptr))
+
+
+def tsdf_integrate_batch_launches(n: int) -> int:
+    return int(lib().sage_tsdf_integrate_batch_launches(int(n)))
+
+
+def tsdf_view_chunk() -> int:
+    return int(lib().sage_tsdf_view_chunk())
+
+
+def window_depth_range_raw(w, kfs, n, dmin, dmax) -> int:
+    f = lib().sage_window_depth_range
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    return int(f(w, kfs, n, dmin, dmax))
+
+
+def window_fuse_tsdf_raw(w, vol, kfs, n, std_mode, std_floor, obs_weight, min_depth) -> int:
+    f = lib().sage_window_fuse_tsdf
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+    return int(f(w, vol, kfs, n, std_mode, std_floor, obs_weight, min_depth))
+
+
+def window_depth_range(win: "Window", kfs, check=True):
+    """``sage_window_depth_range`` -> (dmin, dmax); ``check=False`` -> (status code, dmin, dmax)"""
+    kf = np.ascontiguousarray(kfs, np.int32).reshape(-1)
+    lo, hi = C.c_float(), C.c_float()
+    rc = window_depth_range_raw(win.h, kf.ctypes.data if kf.size else None, kf.size, C.addressof(lo), C.addressof(hi))
+    if not check:
+        return rc, lo.value, hi.value
+    _chk(rc, "sage_window_depth_range")
+    return lo.value, hi.value
+
+
+def window_fuse_tsdf(win: "Window", vol: "TsdfVolume", kfs, std_mode=TSDF_STD_ONE, std_floor=0.0, obs_weight=1.0,
+                     min_depth=1.0e-4, check=True) -> int:
+    """``sage_window_fuse_tsdf``: the window's keyframes ``kfs`` into ``vol``, in the order given -> status code"""
+    kf = np.ascontiguousarray(kfs, np.int32).reshape(-1)
+    rc = window_fuse_tsdf_raw(win.h if win is not None else None, vol.h if vol is not None else None,
+                              kf.ctypes.data if kf.size else None, kf.size, int(std_mode), std_floor, obs_weight, min_depth)
+    if check:
+        _chk(rc, "sage_window_fuse_tsdf")
+    return rc
+
+
+class TsdfVolume:
+    """``SageTsdfVolume``: tsdf, weight and (optional) color volumes on a workspace's stream; close it before the workspace."""
+
+    def __init__(self, ws: Workspace, plan: SageTsdfPlan):
+        self.ws, self.plan = ws, plan
+        self.dim = tuple(int(d) for d in plan.dim)
+        self.h = C.c_void_p()
+        _chk(tsdf_create_raw(ws.h, C.addressof(plan), C.addressof(self.h)), "sage_tsdf_create")
+
+    def reset(self):
+        f = lib().sage_tsdf_reset
+        f.argtypes = [C.c_void_p]
+        _chk(int(f(self.h)), "sage_tsdf_reset")
+
+    def get(self, color=False):
+        """``sage_tsdf_get`` -> (tsdf, weight) or (tsdf, weight, color), numpy [dx, dy, dz]; drains the stream"""
+        f = lib().sage_tsdf_get
+        f.argtypes = [C.c_void_p] * 4
+        out = [np.empty(self.dim, np.float32) for _ in range(3 if color else 2)]
+        _chk(int(f(self.h, *[o.ctypes.data for o in out], *([None] if not color else []))), "sage_tsdf_get")
+        return tuple(out)
+
+    def integrate(self, view: SageTsdfView, check=True) -> int:
+        rc = tsdf_integrate_raw(self.h, C.addressof(view))
+        if check:
+            _chk(rc, "sage_tsdf_integrate")
+        return rc
+
+    def integrate_batch(self, views, flags=0, check=True) -> int:
+        table = (SageTsdfView * max(len(views), 1))(*views)
+        rc = tsdf_integrate_batch_raw(self.h, C.addressof(table), len(views), int(flags))
+        if check:
+            _chk(rc, "sage_tsdf_integrate_batch")
+        return rc
+
+    def last_stats(self) -> SageTsdfStats:
+        f = lib().sage_tsdf_last_stats
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = SageTsdfStats()
+        _chk(int(f(self.h, C.addressof(out))), "sage_tsdf_last_stats")
+        return out
+
+    def close(self):
+        if self.h:
+            f = lib().sage_tsdf_destroy
+            f.argtypes, f.restype = [C.c_void_p], None
+            f(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def gaussian_pyramid_with_grad(ws: Workspace, feat, mask, pyr: SagePyramid, FS):

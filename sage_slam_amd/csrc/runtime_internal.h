@@ -42,6 +42,10 @@
 //   marginal_host.cpp   (no HIP) the Schur complement, the prior's handle, the host mirror of the term, the layout plan's C view
 //   relin_host.cpp      (no HIP) the reads table and gtsam's relinearization check (relin_plan.h), stateless
 //   factor_blocks.cpp   (no HIP) what a cached factor is: shape, projection of its own matrix, cut into HessianFactor blocks
+//   tsdf.hip            TSDF fusion of depth maps into a voxel volume (sage_tsdf_*): the volume, the per-view kernel, all views
+//                       in one pass over the volume (bricks in registers, views staged in LDS, the conservative cull)
+//   tsdf_host.cpp       (no HIP) the frustum bounds, the volume's plan, the calls' argument checks
+//   window_tsdf.hip     a window's keyframes into a volume (sage_window_fuse_tsdf), the depth range of its maps
 // window_state.h holds the parts SageWindow is made of (host variables, dense factor side, term side, factor cache, totals
 // mirror, distributed state, profiler); device_buffers.h holds the owners of device and pinned allocations (DevBuf, PinnedBuf: also
 // included by solve_kernels.hip); the layouts of the workspace's pinned regions (WsHostStats, TrackHost) are below
@@ -97,6 +101,7 @@ extern "C"
 #include "keyframe_prepare.h"  // a prepared keyframe's fingerprint, layout and plan; the handle itself
 #include "marginal.h"          // a marginal prior's handle, the layout of a window's prior terms
 #include "covariance.h"        // the closed pattern and the recursion of the marginal covariances
+#include "tsdf.h"              // a TSDF volume's brick shapes, the view checks
 
 using namespace sage;
 
@@ -309,10 +314,27 @@ struct SageWorkspace
   // counts (PrepScratch, keyframe_prepare.h); what the last call launched
   DevBuf prep_scratch;
   int prep_launches = 0;
+  // TSDF fusion (sage_tsdf_integrate_batch: tsdf.hip): the views' table, built in pinned memory and copied to the device on
+  // the launch's stream (the staging protocol of the sigma launch)
+  DepthSigmaStage tsdf_stage;
 
   WsHostStats *hs() const { return host_stats.as<WsHostStats>(); }
   TrackHost *trk() const { return trk_host.as<TrackHost>(); }
 };
+
+// a TSDF volume (tsdf.hip): its arrays, the per-brick counts of the last batch and what that batch was
+struct SageTsdfVolume
+{
+  SageWorkspace *ws = nullptr;
+  SageTsdfPlan plan{};
+  DevBuf tsdf, weight, color; // [voxels] each; color only with plan.with_color
+  DevBuf kept;                // [bricks of the smallest brick shape] int32: views the brick kept in the last batch
+  hipEvent_t order = nullptr; // orders the workspace's stream and a caller's (sage_window_fuse_tsdf)
+  int last_views = 0, last_brick_x = 0; // the last batch: 0 views = none yet
+};
+// sage_tsdf_integrate_batch on stream s (arguments checked by the caller: tsdf::check_batch); s != the volume's stream: s waits
+// for what the volume's stream holds, and the volume's stream for the launch
+int tsdf_integrate_batch_on(SageTsdfVolume *vol, hipStream_t s, const SageTsdfView *views, int n, int flags);
 
 // operators.hip
 // enqueue a one-lane kernel that posts a ticket behind everything in the workspace's stream and spin until it shows up
@@ -482,6 +504,7 @@ struct SageWindow
   DoglegSide dogleg;                      // the dogleg step's tables, vectors and pinned dots (window_dogleg.hip)
   RelinSide relin;                        // partial relinearization: mode, snapshot, depth stamps, sub work lists (window_relin.hip)
   CovarianceSide cov;                     // marginal covariances of the last solve, opt-in (window_covariance.hip)
+  TsdfSide tsdf;                          // scratch of sage_window_fuse_tsdf and sage_window_depth_range (window_tsdf.hip)
   WindowProfiler prof;            // optional kernel timing (window_profile.hip)
 
   // do the assembly and the error pass mirror their totals into pinned memory themselves?  Single-rank windows WITHOUT an
@@ -568,6 +591,10 @@ int relin_prepare(SageWindow *w, RelinLaunch &rl);  // the stale edges against t
 void relin_commit(SageWindow *w, const RelinLaunch &rl); // the launches are enqueued: the current variables become the snapshot
 void relin_stamp_maps(SageWindow *w, int set, bool depth, bool grad); // a whole-window depth batch at `set` has been enqueued
 void relin_count_all(SageWindow *w, bool dense, bool depth, bool grad); // SageEvalCounts of a linearize of every edge
+// window_covariance.hip
+int covariance_refusal(const SageWindow *w);  // why the window cannot have a covariance at all, or SAGE_OK
+bool covariance_current(const SageWindow *w); // the stored Sigma belongs to the solver's last factor
+DepthSigmaEntry window_sigma_entry(const SageWindow *w, int k, float *out); // keyframe k's row of a sigma launch, S from the stored Sigma
 // window_profile.hip
 void prof_attach(SageWindow *w, int which, LaunchCommon &lc); // profiling: an event pair for kernel `which` (LaunchCommon::ev_*)
 void window_phase_mark(SageWindow *w, int which); // profiling: record phase mark `which` on the window's stream

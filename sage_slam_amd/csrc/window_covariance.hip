@@ -11,7 +11,7 @@
 #include "runtime_internal.h"
 
 // why the window cannot have a covariance at all, or SAGE_OK
-static int covariance_refusal(const SageWindow *w)
+int covariance_refusal(const SageWindow *w)
 {
   if (!w->finalized)
     return SAGE_E_STATE;
@@ -22,7 +22,7 @@ static int covariance_refusal(const SageWindow *w)
   return SAGE_OK;
 }
 
-static bool covariance_current(const SageWindow *w)
+bool covariance_current(const SageWindow *w)
 {
   return w->cov.valid && w->cov.epoch == solver_factor(w->solver).epoch;
 }
@@ -106,7 +106,7 @@ extern "C" int sage_window_get_covariance(const SageWindow *w, int kf_a, int kf_
 
 // bias, basis, code and scale as the window's own depth items name them (window_build.hip): the planes of the keyframe's view
 // -- its handle's, for a prepared keyframe -- and the current variable set on the device; S from the stored Sigma
-static DepthSigmaEntry window_sigma_entry(const SageWindow *w, int k, float *out)
+DepthSigmaEntry window_sigma_entry(const SageWindow *w, int k, float *out)
 {
   const float *vp = w->vars[0].as<float>() + (size_t)k * w->VS;
   const size_t B = (size_t)w->B;

@@ -274,6 +274,14 @@ struct CovarianceSide
   DepthSigmaStage stage;      // sage_window_depth_sigma's table and fp32 covariances
 };
 
+// ---- fusing the window's keyframes into a TSDF volume (window_tsdf.hip), opt-in: everything is built by the first call ----
+struct TsdfSide
+{
+  DevBuf depth;      // [n][H * W]: the listed keyframes' depth maps at the current variables
+  DevBuf sigma;      // [n][H * W]: the sigma maps of a SAGE_TSDF_STD_SIGMA fuse
+  PinnedBuf range;   // sage_window_depth_range: the kernel's (min, max) [n][2]
+};
+
 // ---- sharded windows ----
 struct WindowDist
 {

@@ -764,3 +764,54 @@ def make_loop_candidates(seed: int, B: int, H: int = 48, W: int = 64, C: int = 1
         cands.append(c)
     return dict(H=H, W=W, C=C, K=K, cam=Camera(fx, fy, cx, cy, float(W), float(H)), desc_q=desc_q, dmap_q=dmap_q, depth_divisor=1.0,
                 cands=cands)
+
+
+def make_tsdf_scene(seed: int, dims=(24, 20, 28), hw=(24, 32), n: int = 5, voxel_size: float = 0.04, trunc_voxels: float = 3.0,
+                    sigma=(0.02, 0.12), depth_holes: float = 0.10, std_holes: float = 0.05, spread=(0.55, 1.15)) -> dict:
+    """Inputs of ``sage_tsdf_integrate`` / ``_batch``: a volume of ``dims`` voxels around a sphere (a smooth surface with an
+    analytic ray intersection) and ``n`` views of it.  Nothing is axis-aligned: the origin and the voxel size are no round
+    numbers, every camera looks at the volume's centre from a random direction with a random roll and a random tilt of up to
+    ~0.2 rad, and the intrinsics are non-integer, so projected coordinates do not land on .5.  The cameras stand ``spread``
+    times the volume's half diagonal from the centre: some inside the volume (voxels behind the camera), all with a field of
+    view the volume overflows on every side.  A view's depth is the z of the nearest intersection (0 where the ray misses,
+    and in ``depth_holes`` of the pixels), its std a smooth field in ``sigma`` (0 in ``std_holes`` of the pixels), its color
+    a packed b 65536 + g 256 + r image.
+    -> dict(dims, origin [3] f32, voxel_size f32, trunc_margin f32, cam, views): per view dict(depth, std, color [H, W] f32,
+    pose12 [12] f32 world-from-camera).  Deterministic per argument set."""
+    H, W = hw
+    rng = np.random.default_rng([seed, *dims, H, W, n])
+    vs = F32(voxel_size * (1.0 + 0.013 * rng.uniform(-1, 1)))
+    origin = (np.array([-0.37, 0.21, 1.13]) + 0.1 * rng.uniform(-1, 1, 3)).astype(F32)
+    ext = np.array(dims, np.float64) * float(vs)
+    centre = origin.astype(np.float64) + 0.5 * ext
+    radius = 0.3 * float(ext.min())
+    half_diag = 0.5 * float(np.linalg.norm(ext))
+    cam = Camera(F32(0.9 * W + rng.uniform(-0.4, 0.4)), F32(0.9 * W + rng.uniform(-0.4, 0.4)), F32((W - 1) / 2 + rng.uniform(-0.3, 0.3)),
+                 F32((H - 1) / 2 + rng.uniform(-0.3, 0.3)), F32(W), F32(H))
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    rays = np.stack([(xx - float(cam.cx)) / float(cam.fx), (yy - float(cam.cy)) / float(cam.fy), np.ones((H, W))], -1)
+    views = []
+    for i in range(n):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        pos = centre + d * half_diag * rng.uniform(*spread)
+        z = -d                                                      # looks at the centre ...
+        up = rng.normal(size=3)
+        x = np.cross(up, z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z], 1) @ so3_exp(rng.uniform(-0.2, 0.2, 3))   # ... rolled and tilted
+        o = R.T @ (pos - centre)                                    # the camera's centre from the sphere's, camera axes
+        b = rays @ o
+        a = np.sum(rays * rays, -1)
+        disc = b * b - a * (o @ o - radius * radius)
+        lam = (-b - np.sqrt(np.maximum(disc, 0.0))) / a
+        depth = np.where((disc > 0) & (lam > 0), lam, 0.0)          # (the rays have z = 1: lambda is the depth)
+        depth[rng.uniform(size=(H, W)) < depth_holes] = 0.0
+        fy_, fx_ = rng.uniform(0.5, 2.0, 2)
+        std = sigma[0] + (sigma[1] - sigma[0]) * (0.5 + 0.5 * np.sin(fx_ * xx * (6.0 / W) + rng.uniform(0, 6)) * np.cos(fy_ * yy * (6.0 / H)))
+        std[rng.uniform(size=(H, W)) < std_holes] = 0.0
+        rgb = rng.integers(0, 256, (3, H, W)).astype(np.float64)
+        views.append(dict(depth=depth.astype(F32), std=std.astype(F32), color=(rgb[2] * 65536 + rgb[1] * 256 + rgb[0]).astype(F32),
+                          pose12=np.concatenate([R.reshape(-1), pos]).astype(F32)))
+    return dict(dims=tuple(int(v) for v in dims), origin=origin, voxel_size=vs, trunc_margin=F32(float(vs) * trunc_voxels), cam=cam,
+                views=views)
